@@ -22,6 +22,11 @@ fixed, value = frame rays / max-over-ranks time.  `--extras`: the timed launch a
 sigmas / rgbs / edges per sample (the default frame path writes rgb_map, depth_map, opacity only, as the reference's
 render_frame consumes only those, rendering.py:169-171).
 
+`--dump-outputs DIR`: after the timed steps, rank 0 writes what the timed path returned in its last step as
+DIR/<name>.npy (float32; float64 stays float64; at most 64 MB): a frame's rgb and depth (the raw launch adds opacity and
+its per-sample outputs on a fixed sample of 4096 rays), a training step's loss, ray colours and updated parameters.  All
+inputs are seeded, so two builds run with the same arguments can be compared array by array.
+
 The JSON line also carries
   roofline     - the fused kernel against the dense 16-bit MFMA peak (2.5 PFLOP/s), from HIP-event
                  timing of the launches inside the timed region; algorithmic FLOPs per ray =
@@ -85,6 +90,39 @@ FLOP_DENSITY = 982528
 FLOP_FULL = 1186816
 FLOP_PER_RAY = S * FLOP_DENSITY + (S + NI) * FLOP_FULL
 PEAK_TFLOPS = 2500.0  # dense bf16/fp16 MFMA, MI355X_MICROARCH.md
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_RAYS = 4096  # per-sample outputs (--extras): this many rays of the frame, a fixed seeded choice
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs DIR`: what the timed path returned in its last step, one DIR/<name>.npy per array (float64 kept,
+    everything else as float32), so that two builds of the project can be compared output for output.  The inputs of
+    every workload are seeded: the same arguments give the same inputs."""
+    import numpy as np
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    arrays = {k: a if a.dtype == np.float64 else a.astype(np.float32) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes of outputs, more than the {DUMP_MAX_BYTES} allowed")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
+def sample_rays(t):
+    """DUMP_SAMPLE_RAYS rows of a per-ray tensor, the same rows in every run."""
+    if t.shape[0] <= DUMP_SAMPLE_RAYS:
+        return t
+    idx = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE_RAYS].sort().values
+    return t[idx.to(t.device)]
+
+
+def dump_training(out_dir, loss, rgb, model):
+    """A training step's outputs: the loss, the rendered colours of its ray batch, and the parameters it updated."""
+    dump_outputs(out_dir, {"loss": loss.reshape(1), "rgb": rgb,
+                           **{"param." + k: p for k, p in model.named_parameters()}})
 
 
 def init_sd(seed):
@@ -275,7 +313,7 @@ def train_main(args, rank, world, dev, dist, backend):
         opt.grads.allreduce(average=False)  # ONE RCCL all-reduce (sum) of the bucket; nothing else crosses GPUs
         opt.step(grad_div=float(world))     # ... the 1/world of the mean is folded into the Adam launch
         sched.step()
-        return loss.detach()
+        return loss.detach(), rgb.detach()
 
     def barrier():
         if world > 1:
@@ -288,11 +326,13 @@ def train_main(args, rank, world, dev, dist, backend):
     _gc_quiet()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, rgb = step()
     barrier()
     dt = time.perf_counter() - t0
     _gc_restore()
     assert bool(torch.isfinite(loss))
+    if rank == 0 and getattr(args, "dump_outputs", None):
+        dump_training(args.dump_outputs, loss, rgb, model)
     if world > 1:
         t = torch.tensor([dt], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -377,6 +417,8 @@ def occ_main(args, rank, world, dev, dist, backend):
     dt = time.perf_counter() - t0
     _gc_restore()
     assert bool(torch.isfinite(out[0]).all()) and ops.range_ok(dev) and model.precision == args.precision
+    if rank == 0 and getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, {"rgb": out[0], "depth": out[1]})
     if world > 1:
         t = torch.tensor([dt], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -480,7 +522,7 @@ def train_occ_main(args, rank, world, dev, dist, backend):
         with torch.no_grad():
             shadow.update_every_n_steps(step=256 + i, occ_eval_fn=occ_eval_fn, occ_thre=1e-2)  # past the warm-up
         kept.append(ri.numel())
-        return loss.detach()
+        return loss.detach(), rgb.detach()
 
     def barrier():
         if world > 1:
@@ -509,7 +551,7 @@ def train_occ_main(args, rank, world, dev, dist, backend):
     t0 = time.perf_counter()
     for i in range(args.steps):
         ts = time.perf_counter()
-        loss = step(args.warmup + i)
+        loss, rgb = step(args.warmup + i)
         per.append((time.perf_counter() - ts) * 1e3)
     barrier()
     dt = time.perf_counter() - t0
@@ -520,6 +562,8 @@ def train_occ_main(args, rank, world, dev, dist, backend):
               ("num_device_alloc", "num_device_free", "num_alloc_retries", "allocation.all.allocated")}, "gc", gc_log, file=sys.stderr, flush=True)
         gc.callbacks.remove(_gc_cb)
     assert bool(torch.isfinite(loss))
+    if rank == 0 and getattr(args, "dump_outputs", None):
+        dump_training(args.dump_outputs, loss, rgb, model)
     if world > 1:
         t = torch.tensor([dt], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -818,11 +862,16 @@ def main():
     ap.add_argument("--raw-launch", action="store_true",
                     help="time ops.render_fused directly instead of the product path render_frame (A/B of the host path)")
     ap.add_argument("--dry-run", action="store_true", help="launcher self-test on the CPU (gloo); not a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (rank 0; at most "
+                         "64 MB: per-sample outputs as a fixed sample of 4096 rays)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 20 if args.workload.startswith("train") else 3
     if args.warmup is None:
         args.warmup = 3 if args.workload.startswith("train") else 1
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -882,12 +931,15 @@ def main():
         n0 = len(ev_raw)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
+        rest = {}
         if args.raw_launch or strong or args.extras:
             # rays are generated inside the launch from (pose, pixel index): a frame (or a rank's row block) is one launch
-            rgb, op, depth, _ = ops.render_fused(pc, pf, None, None, near=NEAR, far=FAR, n_samples=S, n_importance=NI,
-                                                 bkgd=(1.0, 1.0, 1.0), want_extras=args.extras,
-                                                 camera=(pose, H, W, FOCAL, row0, nrows, dev),
-                                                 two_phase=os.environ.get("FSN_TWO_PHASE", "1") == "1")
+            rgb, op, depth, ex = ops.render_fused(pc, pf, None, None, near=NEAR, far=FAR, n_samples=S, n_importance=NI,
+                                                  bkgd=(1.0, 1.0, 1.0), want_extras=args.extras,
+                                                  camera=(pose, H, W, FOCAL, row0, nrows, dev),
+                                                  two_phase=os.environ.get("FSN_TWO_PHASE", "1") == "1")
+            if args.dump_outputs:  # (held only then: a frame's per-sample extras are GBs)
+                rest = {"opacity": op, **ex}
         else:
             # the PRODUCT path (rendering.py:110-177): render_frame -> one fused launch, range-guard read-back, depth clamp
             rgb, depth = Rm.render_frame((H, W, FOCAL), NEAR, FAR, pose, 1 << 30, est, coarse, white_bkgd=True,
@@ -897,7 +949,7 @@ def main():
             ev.append((e0, e1))
         else:
             del ev_raw[n0:]
-        return rgb, depth
+        return rgb, depth, rest
 
     def barrier():
         if world > 1:
@@ -921,6 +973,9 @@ def main():
     assert ops.range_ok(dev), "an fp16-mode launch reported activations outside the fp16 range"
     assert coarse.precision == args.precision and fine.precision == args.precision, "no range fallback in the timed region"
     assert coarse.range_events + fine.range_events == events0, "no re-calibration in the timed region"
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"rgb": out[0], "depth": out[1],
+                                         **{k: v if k == "opacity" else sample_rays(v) for k, v in out[2].items()}})
     if world > 1:
         t = torch.tensor([dt], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

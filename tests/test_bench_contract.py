@@ -4,7 +4,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -82,6 +84,50 @@ def test_occupancy_lines_contract():
     assert KEYS <= set(t) and t["steps"] == 3 and "trained rays/sec (occupancy" in t["metric"]
     assert t["config"]["rays_per_step"] == 4096 and t["config"]["marched_samples_per_ray"] > t["config"]["kept_samples_per_ray"] > 5
     assert 0.0 < t["loss"] < 1.0 and t["value"] > 1e4
+
+
+@pytest.mark.gpu
+def test_dump_outputs(tmp_path):
+    """`--dump-outputs DIR`: what the timed path returned in its last step, float32, within 64 MB; the raw launch's
+    per-sample outputs as a fixed sample of rays; the training step's loss, colours and updated parameters."""
+    j = _run("--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "frame"))
+    assert j["steps"] == 2
+    rgb, depth = np.load(tmp_path / "frame" / "rgb.npy"), np.load(tmp_path / "frame" / "depth.npy")
+    assert rgb.shape == (800, 800, 3) and depth.shape == (800, 800) and rgb.dtype == depth.dtype == np.float32
+    assert np.isfinite(rgb).all() and 2.0 <= depth.min() and depth.max() <= 6.0
+    _run("--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--raw-launch", "--extras", "--dump-outputs",
+         str(tmp_path / "raw"))
+    raw = {f[:-4]: np.load(tmp_path / "raw" / f) for f in os.listdir(tmp_path / "raw")}
+    assert set(raw) == {"rgb", "depth", "opacity", "weights", "alphas", "trans", "sigmas", "rgbs", "edges", "weights_coarse"}
+    assert sum(a.nbytes for a in raw.values()) <= 64 << 20 and all(a.dtype == np.float32 for a in raw.values())
+    assert raw["rgb"].shape == (640000, 3) and raw["opacity"].shape == (640000, 1)
+    assert raw["weights"].shape == (4096, 192) and raw["rgbs"].shape == (4096, 192, 3) and raw["edges"].shape == (4096, 193)
+    assert np.allclose(raw["rgb"], rgb.reshape(-1, 3), rtol=0, atol=1e-5), "the same frame through the raw launch"
+    t = _run("--workload", "train", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "train"))
+    files = os.listdir(tmp_path / "train")
+    assert {"loss.npy", "rgb.npy", "param.sigma.weight.npy"} <= set(files)
+    assert abs(float(np.load(tmp_path / "train" / "loss.npy")[0]) - t["loss"]) < 1e-6
+    assert np.load(tmp_path / "train" / "rgb.npy").shape == (4096, 3)
+
+
+def test_dump_helpers(tmp_path):
+    sys.path.insert(0, ROOT)
+    import bench
+    x = torch.arange(10000 * 7, dtype=torch.int32).reshape(10000, 7)
+    s = bench.sample_rays(x)
+    assert s.shape == (4096, 7) and torch.equal(s, bench.sample_rays(x)), "the same rows in every run"
+    rows = s[:, 0] // 7
+    assert torch.equal(rows, rows.unique()), "distinct rows, in order"
+    bench.dump_outputs(str(tmp_path / "d"), {"s": s, "f64": torch.ones(3, dtype=torch.float64)})
+    assert np.load(tmp_path / "d" / "s.npy").dtype == np.float32 and np.load(tmp_path / "d" / "f64.npy").dtype == np.float64
+    with pytest.raises(RuntimeError, match="64"):
+        bench.dump_outputs(str(tmp_path / "big"), {"a": torch.zeros((64 << 20) // 4 + 1)})
+    assert not os.path.exists(tmp_path / "big")
+
+
+def test_steps_must_be_positive():
+    out = _launch("--steps", "0", "--dry-run")
+    assert out.returncode != 0 and "--steps" in out.stderr
 
 
 # ---- the N>1 launcher (CPU: `--dry-run` children join a gloo group instead of touching the GPU)
