@@ -120,9 +120,7 @@ class _NerfTrainFn(torch.autograd.Function):
         # loss scaler's - and into this model's own accumulated word, which the host reads every `range_check_every`
         # training calls; it then warns and continues in bf16x3.
         if ctx.word is not None:
-            for f in model._step_flags(d_out.device):
-                f.bitwise_or_(ctx.word)
-            model._train_status(d_out.device)[0:1].bitwise_or_(ctx.word)
+            model.fold_status(ctx.word, d_out.device, 0)
             model._train_calls += 1
             if model.range_check and model._train_calls % model.range_check_every == 0:
                 model._guard_weights("training steps", training=True)
@@ -218,6 +216,11 @@ class NeRF(nn.Module):
     def fp16_family(prec: int) -> bool:
         return prec in (L.FSN_PREC_FP16X3, L.FSN_PREC_FP16, L.FSN_PREC_FP16X2)
 
+    @property
+    def fp16_mode(self) -> bool:
+        """`precision` is one of the fp16 modes now (range-guarded; `fall_back` leaves them)."""
+        return self.fp16_family(self.PRECISIONS[self.precision])
+
     def _bwd_stage_state(self, dev):
         """(scales, maxima) of the backward chain's delayed per-stage scaling (fsn_nerf_train_bwd), device-resident."""
         st = self._bwd_stage
@@ -251,6 +254,13 @@ class NeRF(nn.Module):
         if w is None or w.device != dev:
             w = self._train_word = torch.zeros(2, dtype=torch.int32, device=dev)
         return w
+
+    def fold_status(self, word: Tensor, dev, slot: int) -> None:
+        """A training-time launch's range word (device int32 [1]) joins the step's guard on the device, no host sync: ORed
+        into every step flag of this model (FusedAdam skips a flagged step) and into slot `slot` of `_train_status`."""
+        for f in self._step_flags(dev):
+            f.bitwise_or_(word)
+        self._train_status(dev)[slot:slot + 1].bitwise_or_(word)
 
     def _read_train_status(self, dev) -> Tuple[int, int]:
         """Host look at the accumulated words (one 8-byte read-back) and clear -> (training kernels' bits, sampler's
@@ -432,8 +442,7 @@ class NeRF(nn.Module):
         # arithmetic of training and of `act_scaling = False`)
         if not training and self.infer_prec() == L.FSN_PREC_FP16X3U:
             return
-        if self.range_check and self.weight_check and self.fp16_family(self.PRECISIONS[self.precision]) and \
-                self._weights_below_envelope():
+        if self.range_check and self.weight_check and self.fp16_mode and self._weights_below_envelope():
             self.fall_back(what + " (a layer's largest weight is below 2^-20)", L.FSN_STATUS_FP16_SMALL, scaled=False)
 
     def packed(self, probe=None) -> ops.PackedMLP:
@@ -499,35 +508,7 @@ class NeRF(nn.Module):
             d = rays_d[ri]
             return rays_o[ri] + d * (t_starts[idx] + t_ends[idx])[:, None] / 2.0, d
 
-        return self._guarded(dev, "NeRF.forward_rays", probe, lambda: ops.mlp_fwd_rays(self.packed(probe), *args))
-
-    def _guarded(self, dev, what: str, probe, launch):
-        """`launch()` under the fp16 range guard of an inference call.  range_check True: read the launch's word back
-        (one host sync); a flagged call is re-run after `fall_back` (re-calibration, or bf16x3).  "deferred": no wait -
-        the word of the PREVIOUS launch is looked at now (ops.range_poll), this launch posts its own for the next call /
-        the end of the frame (render_frame) to look at.  False: never look."""
-        f16 = lambda: self.fp16_family(self.PRECISIONS[self.precision])
-        if not self.range_check or not f16():
-            return launch()
-        if self.range_check == "deferred":
-            bits = ops.range_poll(dev)
-            if bits:
-                self.fall_back("an EARLIER call (deferred range check: its outputs are invalid)", bits, probe,
-                               earlier_invalid=True)
-            out = launch()
-            if f16():
-                ops.range_post(dev)
-            return out
-        out = launch()
-        for _ in range(5):
-            bits = ops.range_flags(dev)
-            if not bits:
-                break
-            self.fall_back(what, bits, probe)
-            out = launch()
-            if not f16():
-                break
-        return out
+        return guarded_launch([self], dev, "NeRF.forward_rays", probe, lambda: ops.mlp_fwd_rays(self.packed(probe), *args))
 
     # -- reference surface ---------------------------------------------------------
     def forward(self, x: Tensor, dirs: Optional[Tensor] = None) -> Tensor:
@@ -546,6 +527,61 @@ class NeRF(nn.Module):
                 return xs, dirs.reshape(-1, 3)
             return xs, torch.tensor([0.0, 0.0, 1.0], device=dev).expand_as(xs)  # (density only: any direction)
 
-        return self._guarded(dev, "NeRF.forward", probe,
-                             lambda: ops.mlp_fwd(self.packed(probe), x, dirs, self._mask(self.pos_mask, dev),
-                                                 self._mask(self.dir_mask, dev)))
+        return guarded_launch([self], dev, "NeRF.forward", probe,
+                              lambda: ops.mlp_fwd(self.packed(probe), x, dirs, self._mask(self.pos_mask, dev),
+                                                  self._mask(self.dir_mask, dev)))
+
+
+def guarded_launch(nets: Sequence[NeRF], dev, what: str, probe, launch, earlier: str = "call"):
+    """`launch()` under the fp16 range guard for the NeRFs `nets` it evaluates (one precision mode for all of them).
+    range_check True: read the launch's word back (one host sync); a flagged call is re-run after `fall_back`
+    (re-calibration of the scaled fp16x3 path, or bf16x3).  "deferred": no wait - the word of the PREVIOUS launch is
+    looked at now (a raised flag re-calibrates / switches the nets and says that the previous call's outputs are
+    invalid), this launch posts its own for the next call / `frame_flagged` to look at.  False: never look."""
+    guarded = [m for m in nets if m.range_check and m.fp16_mode]
+    if guarded and all(m.range_check == "deferred" for m in guarded):
+        bits = ops.range_poll(dev)
+        if bits:
+            _fall_back(nets, f"an EARLIER {earlier} (deferred range check: its outputs are invalid)", bits, probe, True)
+        out = launch()
+        if any(m.fp16_mode for m in nets):
+            ops.range_post(dev)
+        return out
+    out = launch()
+    for _ in range(5):
+        bits = ops.range_flags(dev) if guarded else 0
+        if not bits:
+            break
+        _fall_back(nets, what, bits, probe)
+        out = launch()
+        guarded = [m for m in nets if m.range_check and m.fp16_mode]
+    return out
+
+
+def _fall_back(nets: Sequence[NeRF], what: str, bits: int, probe, earlier_invalid: bool = False) -> None:
+    for m in nets:  # the coarse and the fine pass run in one precision mode
+        if m.fp16_mode:
+            m.fall_back(what, bits, probe, earlier_invalid=earlier_invalid)
+    if len({m.infer_prec() for m in nets}) > 1:  # one net could re-calibrate, another had to give up: both go to bf16x3
+        for m in nets:
+            if m.fp16_mode:
+                m.act_scaling = False
+                m.fall_back(what, bits, scaled=False)
+
+
+def frame_flagged(nets: Sequence[NeRF], dev, events_before: Optional[int] = None, probe=None) -> bool:
+    """Deferred range check (`NeRF.range_check = "deferred"`): the one look per frame.  True when a launch of the frame
+    left the fp16 envelope - the LAST one (its word is polled here) or an EARLIER chunk, which the following chunk's poll
+    has consumed already (the chunk that overflowed is in the list of results all the same): any range event
+    since `events_before` (the nets' summed `range_events`) says so.  The nets have been re-calibrated / switched to
+    their bf16 mode (with a RuntimeWarning); the caller renders the frame again."""
+    earlier = events_before is not None and sum(m.range_events for m in nets) != events_before
+    if not any(m.range_check == "deferred" and m.fp16_mode for m in nets):
+        return earlier
+    bits = ops.range_poll(dev)
+    if not bits:
+        return earlier
+    for m in nets:
+        if m.fp16_mode:
+            m.fall_back("render_frame (deferred range check at the end of the frame)", bits, probe, earlier_invalid=True)
+    return True
