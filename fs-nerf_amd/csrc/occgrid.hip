@@ -78,15 +78,20 @@ __global__ void k_occ_ema(float* __restrict__ occs, const int64_t* __restrict__ 
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int64_t c = cells[i];
+  if (c < 0) return;  // an unused draw of fsn_occgrid_select
   occs[c] = fmaxf(occs[c] * decay, vals[i]);
 }
 
 // ---------------------------------------------------------------- update_every_n_steps: cell selection on the device
 // (run-nerf.py:288-295 -> OccGridEstimator.update_every_n_steps; round 3 chose the cells with randint / nonzero / unique /
 // stack torch ops - two host syncs - and expanded the bit field to bools on every call.)  Past the warm-up an update
-// re-evaluates n_uniform cells drawn uniformly and n_occupied cells drawn uniformly from the OCCUPIED ones (both with
-// replacement), each at a random point inside the cell.  Counter-based randomness (a 32-bit mixing hash of (seed,
-// draw index, stream): no generator state on the device, the oracle restates it): draw i of stream k is
+// re-evaluates n_uniform cells drawn uniformly (with replacement) and n_occupied cells from the OCCUPIED ones, each at
+// a random point inside the cell.  The occupied half follows nerfacc's rule (OccGridEstimator.
+// _sample_uniform_and_occupied_cells): a level with m <= n_occupied occupied cells takes each of them exactly once
+// (draw n_uniform + q -> the q-th occupied cell in index order, q < m; the draws q >= m are the sentinel cell -1, which
+// the EMA skips); only m > n_occupied draws n_occupied of them uniformly with replacement.  The draw count stays
+// n_uniform + n_occupied either way and nothing is read back to the host.  Counter-based randomness (a 32-bit mixing
+// hash of (seed, draw index, stream): no generator state on the device, the oracle restates it): draw i of stream k is
 // r(i, k) = mix(mix(i + seed_lo) ^ (seed_hi + 0x9e3779b9 (k + 1))).
 __device__ __host__ __forceinline__ uint32_t occ_mix(uint32_t x) {
   x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
@@ -117,7 +122,8 @@ __global__ __launch_bounds__(1024) void k_occ_word_prefix(const uint32_t* __rest
   if (threadIdx.x == 1023) prefix[n_words] = part[1023];
 }
 
-// draw i -> cell of level `lvl` (index inside the level) and a point inside it.  all_cells: draw i IS cell i (warm-up).
+// draw i -> cell of level `lvl` (global index, or -1 for an unused occupied draw) and a point inside it.  all_cells:
+// draw i IS cell i (warm-up).  A sentinel draw still gets a point: the one of its uniform cell r(i, 0) % res^3.
 __global__ void k_occ_select(const uint32_t* __restrict__ bits, const int32_t* __restrict__ prefix, int res, int64_t lvl_cell0,
                              int64_t n_draws, int64_t n_uniform, int all_cells, uint32_t seed_lo, uint32_t seed_hi,
                              float lox, float loy, float loz, float hix, float hiy, float hiz,
@@ -127,20 +133,29 @@ __global__ void k_occ_select(const uint32_t* __restrict__ bits, const int32_t* _
   const uint32_t res3 = (uint32_t)res * res * res;
   const int n_words = (int)(res3 >> 5);
   uint32_t cell;
+  bool unused = false;
   if (all_cells) {
     cell = (uint32_t)i;
   } else {
     const uint32_t r = occ_rand((uint32_t)i, 0u, seed_lo, seed_hi);
-    const int32_t total = i < n_uniform ? 0 : prefix[n_words];  // (prefix may be null when nothing is drawn from it)
-    if (i < n_uniform || total == 0) {
-      cell = r % res3;
-    } else {
-      const int32_t j = (int32_t)(r % (uint32_t)total);  // the j-th occupied cell of the level
-      int lo = 0, hi = n_words;                          // last word w with prefix[w] <= j
-      while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (prefix[mid] <= j) lo = mid; else hi = mid; }
-      uint32_t m = bits[lo];
-      for (int q = j - prefix[lo]; q > 0; --q) m &= m - 1u;  // drop the lowest set bits below the wanted one
-      cell = ((uint32_t)lo << 5) + (uint32_t)(__ffs((int)m) - 1);
+    cell = r % res3;
+    if (i >= n_uniform) {  // (prefix is only read here: it may be null when nothing is drawn from it)
+      const int32_t total = prefix[n_words];
+      const int64_t q = i - n_uniform, n_occupied = n_draws - n_uniform;
+      int32_t j;  // the j-th occupied cell of the level
+      if ((int64_t)total > n_occupied) {
+        j = (int32_t)(r % (uint32_t)total);
+      } else {
+        j = (int32_t)q;
+        unused = q >= (int64_t)total;
+      }
+      if (!unused) {
+        int lo = 0, hi = n_words;  // last word w with prefix[w] <= j
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (prefix[mid] <= j) lo = mid; else hi = mid; }
+        uint32_t m = bits[lo];
+        for (int b = j - prefix[lo]; b > 0; --b) m &= m - 1u;  // drop the lowest set bits below the wanted one
+        cell = ((uint32_t)lo << 5) + (uint32_t)(__ffs((int)m) - 1);
+      }
     }
   }
   const uint32_t ix = cell / ((uint32_t)res * res), iy = (cell / (uint32_t)res) % (uint32_t)res, iz = cell % (uint32_t)res;
@@ -149,7 +164,7 @@ __global__ void k_occ_select(const uint32_t* __restrict__ bits, const int32_t* _
   const float u1 = (float)(occ_rand((uint32_t)i, 2u, seed_lo, seed_hi) >> 8) * inv24;
   const float u2 = (float)(occ_rand((uint32_t)i, 3u, seed_lo, seed_hi) >> 8) * inv24;
   const float fr = (float)res;
-  cells[i] = lvl_cell0 + (int64_t)cell;
+  cells[i] = unused ? (int64_t)-1 : lvl_cell0 + (int64_t)cell;
   x[3 * i + 0] = lox + (((float)ix + u0) / fr) * (hix - lox);
   x[3 * i + 1] = loy + (((float)iy + u1) / fr) * (hiy - loy);
   x[3 * i + 2] = loz + (((float)iz + u2) / fr) * (hiz - loz);
@@ -165,8 +180,9 @@ __global__ void k_occ_scatter_max(uint32_t* __restrict__ pending, const int64_t*
                                   const float* __restrict__ vals, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  const int64_t c = cells[i];
   const float v = vals[i];
-  if (v == v) atomicMax(pending + cells[i], occ_key(v));  // (NaN never enters the grid)
+  if (c >= 0 && v == v) atomicMax(pending + c, occ_key(v));  // (NaN never enters the grid; c = -1: unused draw)
 }
 __global__ void k_occ_ema_pending(float* __restrict__ occs, uint32_t* __restrict__ pending, int64_t n_cells, float decay) {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

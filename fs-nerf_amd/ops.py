@@ -947,7 +947,11 @@ def occgrid_update(occs: Tensor, bits: Tensor, cells: Optional[Tensor], vals: Op
 def occgrid_select(bits: Tensor, aabb: Sequence[float], res: int, levels: int, lvl: int, all_cells: bool, n_uniform: int,
                    n_occupied: int, seed: int, scratch: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
     """Cells of level `lvl` an update re-evaluates and a random point inside each (fsn_occgrid_select) ->
-    (cells int64 [n] global indices, x [n,3]); n = res^3 (all_cells) or n_uniform + n_occupied.  No host sync."""
+    (cells int64 [n] global indices, x [n,3]); n = res^3 (all_cells) or n_uniform + n_occupied.  No host sync.
+    n_uniform draws are uniform over the level, with replacement.  The n_occupied draws follow nerfacc's rule: with
+    m <= n_occupied occupied cells they are those cells in index order, each once, then the sentinel cell -1 (its x is
+    still a point inside the level's box; occgrid_update / occgrid_update_multi skip it); with m > n_occupied they are
+    uniform over the occupied cells, with replacement."""
     res3 = res ** 3
     n = res3 if all_cells else int(n_uniform) + int(n_occupied)
     dev = bits.device

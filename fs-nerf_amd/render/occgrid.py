@@ -26,9 +26,22 @@ class OccGridEstimator(nn.Module):
         self.register_buffer("occs", torch.zeros(n_cells, dtype=torch.float32))
         self.register_buffer("bits", torch.zeros(n_cells // 32, dtype=torch.int32))
         self.generator: Optional[torch.Generator] = None
-        self._updates = 0      # update_every_n_steps calls that ran (part of the draws' seed)
+        self._updates = 0      # update_every_n_steps calls that ran (part of the draws' seed; in the state_dict)
         self._pending = None   # scratch of the duplicate-safe EMA / the selection's popcount prefix (device)
         self._prefix = None
+
+    # -- state ---------------------------------------------------------------------
+    # The update count is part of the draws' seed (update_seed): the state_dict carries it, so that a resumed run continues
+    # the sequence of draws instead of replaying the first ones.  A state_dict saved before it did loads with the count 0.
+    def get_extra_state(self) -> Tensor:
+        return torch.tensor(self._updates, dtype=torch.int64)
+
+    def set_extra_state(self, state) -> None:
+        self._updates = int(state)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        state_dict.setdefault(prefix + "_extra_state", 0)  # (load_state_dict hands each module its own copy)
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     # -- helpers -------------------------------------------------------------------
     @property
@@ -81,9 +94,12 @@ class OccGridEstimator(nn.Module):
     @torch.no_grad()
     def update_every_n_steps(self, step: int, occ_eval_fn: Callable, occ_thre: float = 1e-2, ema_decay: float = 0.95,
                              warmup_steps: int = 256, n: int = 16) -> None:
-        """Every n-th training step (run-nerf.py:288-295): re-evaluate cells - all of them during warm-up, else res^3/4
-        drawn uniformly + res^3/4 drawn uniformly from the occupied ones, with replacement - at a random point inside
-        each, occs = max(occs*decay, occ), binaries = occs > min(mean, thre).
+        """Every n-th training step (run-nerf.py:288-295): re-evaluate cells - all of them during warm-up, else per level
+        res^3/4 drawn uniformly with replacement + res^3/4 from the occupied ones - at a random point inside each,
+        occs = max(occs*decay, occ), binaries = occs > min(mean, thre).  The occupied half follows nerfacc's rule: a
+        level with at most res^3/4 occupied cells re-evaluates each of them exactly once (its other draws are unused:
+        cell -1, skipped by the EMA, though occ_eval_fn still sees a point for them, so its batch size is fixed); only a
+        denser level draws res^3/4 of them with replacement.
         Round 4: selection, jitter and the duplicate-safe EMA are kernels reading the bit field directly
         (fsn_occgrid_select / fsn_occgrid_update_multi); no host sync, no bool expansion of the grid.  Randomness is a
         counter-based hash of (seed, draw): seed = the estimator generator's (or torch's) initial seed and the number of

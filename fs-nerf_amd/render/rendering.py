@@ -134,26 +134,34 @@ def _probe_on_rays(rays_o, rays_d, camera, t_lo: float, t_hi: float, n_rays: int
     return x.reshape(-1, 3), d[:, None, :].expand(-1, n_t, -1).reshape(-1, 3)
 
 
-def _probe_in_box(rays_o, rays_d, camera, aabb, n: int = 16384):
-    """Probe batch for the occupancy estimator's path: positions uniform in the grid's box (every sample the march
-    produces lies inside it), directions from an even subset of the call's rays."""
+def _probe_in_box(rays_o, rays_d, camera, estimator, n: int = 16384):
+    """Probe batch for the occupancy estimator's path: positions uniform in each of the grid's level boxes, an equal
+    share per level (every sample the march produces lies in one of them), directions from an even subset of the call's
+    rays - random unit directions when the call has none."""
     if rays_o is None:
         pose, H, W, focal, row0, nrows, dev = camera
         rays_o, rays_d = ops.get_rays(pose, int(H), int(W), float(focal), dev, int(row0), int(nrows))
     dev = rays_d.device
     R = rays_d.reshape(-1, 3).shape[0]
-    idx = torch.linspace(0, max(R - 1, 0), n, device=dev).long()
     g = torch.Generator(device="cpu").manual_seed(0)
-    lo = torch.tensor([float(v) for v in aabb[:3]], device=dev)
-    hi = torch.tensor([float(v) for v in aabb[3:]], device=dev)
-    x = lo + (hi - lo) * torch.rand(n, 3, generator=g).to(dev)
-    return x, rays_d.reshape(-1, 3)[idx].float()
+    levels = estimator.levels
+    xs = []
+    for lvl in range(levels):
+        lo, hi = estimator.level_aabb(lvl)
+        lo, hi = torch.tensor(lo, device=dev), torch.tensor(hi, device=dev)
+        m = n // levels + (1 if lvl < n % levels else 0)
+        xs.append(lo + (hi - lo) * torch.rand(m, 3, generator=g).to(dev))
+    if R == 0:
+        d = torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=-1).to(dev)
+    else:
+        d = rays_d.reshape(-1, 3)[torch.linspace(0, R - 1, n, device=dev).long()].float()
+    return torch.cat(xs), d
 
 
 def _probe(estimator, rays_o, rays_d, camera=None):
     """The calibration probe of a call on these rays (or this camera), for its estimator."""
     if isinstance(estimator, OccGridEstimator):
-        return lambda: _probe_in_box(rays_o, rays_d, camera, estimator.aabb)
+        return lambda: _probe_in_box(rays_o, rays_d, camera, estimator)
     if isinstance(estimator, StratifiedEstimator):
         return lambda: _probe_on_rays(rays_o, rays_d, camera, *estimator.bounds())
     return None

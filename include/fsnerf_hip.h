@@ -462,12 +462,15 @@ int fsn_packed_visibility(const float* sigmas, const float* t_starts, const floa
 int fsn_occgrid_update(float* occs, int64_t n_cells, const int64_t* cells, const float* vals, int64_t n, float decay,
                        const float* threshold_dev, uint32_t* bits, fsn_stream_t stream);
 /* update_every_n_steps on the device (round 4; run-nerf.py:288-295): which cells of level `lvl` an update re-evaluates,
- * and where.  all_cells != 0 (warm-up): draw i is cell i, n = res^3.  Else n = n_uniform + n_occupied draws WITH
- * replacement: the first n_uniform uniform over the level's cells, the rest uniform over its OCCUPIED cells read straight
- * from the bit field (popcount prefix over its words in prefix_scratch, DEVICE int32 [res^3/32 + 1]; uniform when the
- * level is empty).  Each draw gets a point uniform inside its cell of the level's box.  Randomness: the counter-based
- * hash of csrc/occgrid.hip (occ_rand) of (seed, draw index) - no generator state, no host sync, restated by the oracle.
- * cells: int64 [n] (global cell index, + lvl res^3), x: [n,3].
+ * and where.  all_cells != 0 (warm-up): draw i is cell i, n = res^3.  Else n = n_uniform + n_occupied draws: the first
+ * n_uniform uniform over the level's cells, with replacement; the rest from its OCCUPIED cells, read straight from the
+ * bit field (popcount prefix over its words in prefix_scratch, DEVICE int32 [res^3/32 + 1]).  A level with m <= n_occupied
+ * occupied cells gives each of them exactly once (draw n_uniform + q -> the q-th occupied cell in index order) and the
+ * sentinel cell -1 to the draws q >= m; with m > n_occupied the draws are uniform over the occupied cells, with
+ * replacement.  Each draw gets a point uniform inside its cell of the level's box (a sentinel draw: inside its uniform
+ * cell).  Randomness: the counter-based hash of csrc/occgrid.hip (occ_rand) of (seed, draw index) - no generator state,
+ * no host sync, restated by the oracle.  cells: int64 [n] (global cell index, + lvl res^3, or -1), x: [n,3].
+ * fsn_occgrid_update and fsn_occgrid_update_multi skip the cells < 0.
  * fsn_occgrid_update_multi: fsn_occgrid_update's EMA for draws that may repeat a cell: occs[c] = max(occs[c] * decay,
  * max of the vals drawn for c) - the maximum is taken first (pending: DEVICE uint32 [n_cells], all zero between calls),
  * so the result does not depend on the order of the draws. */

@@ -20,7 +20,7 @@ Pinning status ("Oracle"):
     hierarchical 64+128 sampling, frequency mask); the reference has no such
     code.  PARITY UNPINNED; with mask == 1 and one network they reduce to the
     reference formulas.
-  * occgrid_march, packed_visibility (end of file) restate this build's definition of the
+  * occgrid_march, packed_visibility, occgrid_select, occgrid_update (end of file) restate this build's definition of the
     estimator contract the reference fills with nerfacc's OccGridEstimator.  PARITY UNPINNED.
 
 All functions take / return torch CPU tensors; `dtype` follows the inputs so the
@@ -569,24 +569,56 @@ def occ_rand(i, k: int, seed: int):
 
 def occgrid_select(binaries_lvl: Tensor, aabb_lvl, res: int, all_cells: bool, n_uniform: int, n_occupied: int, seed: int):
     """-> (cells int64 [n] indices inside the level, x float32 [n,3]).  binaries_lvl: [res,res,res] bool of the level
-    (cell index (ix*res + iy)*res + iz), aabb_lvl = (lo[3], hi[3]) of the level's box."""
+    (cell index (ix*res + iy)*res + iz), aabb_lvl = (lo[3], hi[3]) of the level's box.
+    Past the warm-up the first n_uniform draws are uniform over the level's cells (with replacement).  The occupied half
+    follows nerfacc's rule (OccGridEstimator._sample_uniform_and_occupied_cells): with m <= n_occupied occupied cells,
+    draw n_uniform + q is the q-th occupied cell in ascending order for q < m and the sentinel -1 for q >= m; with
+    m > n_occupied the draws are uniform over the occupied cells, with replacement.  Every draw, a sentinel one too, gets
+    a point inside a cell of the level's box: its own cell, or for a sentinel its uniform cell r(i, 0) % res^3."""
     import numpy as np
     res3 = res ** 3
     n = res3 if all_cells else n_uniform + n_occupied
     i = np.arange(n, dtype=np.uint64)
+    unused = np.zeros(n, bool)
     if all_cells:
         cell = i.copy()
     else:
         r = occ_rand(i, 0, seed)
         occ_idx = np.flatnonzero(binaries_lvl.reshape(-1).cpu().numpy())  # ascending = (word, bit) order of the bit field
         cell = r % np.uint64(res3)
-        if occ_idx.size > 0 and n_occupied > 0:
-            j = (r[n_uniform:] % np.uint64(occ_idx.size)).astype(np.int64)
+        m = occ_idx.size
+        if n_occupied > 0 and m > n_occupied:
+            j = (r[n_uniform:] % np.uint64(m)).astype(np.int64)
             cell[n_uniform:] = occ_idx[j].astype(np.uint64)
-    cell = cell.astype(np.int64)
+        elif n_occupied > 0:
+            cell[n_uniform:n_uniform + m] = occ_idx.astype(np.uint64)
+            unused[n_uniform + m:] = True
+    cell = cell.astype(np.int64)  # (a sentinel draw keeps its uniform cell here: its point lies in it)
     ix, iy, iz = cell // (res * res), (cell // res) % res, cell % res
     u = [(occ_rand(i, k, seed) >> np.uint64(8)).astype(np.float32) * np.float32(1.0 / 16777216.0) for k in (1, 2, 3)]
     lo, hi = [np.float32(v) for v in aabb_lvl[0]], [np.float32(v) for v in aabb_lvl[1]]
     fr = np.float32(res)
     x = np.stack([lo[a] + ((c.astype(np.float32) + u[a]) / fr) * (hi[a] - lo[a]) for a, c in enumerate((ix, iy, iz))], -1)
-    return torch.from_numpy(cell), torch.from_numpy(x.astype(np.float32))
+    cells = np.where(unused, -1, cell)
+    return torch.from_numpy(cells), torch.from_numpy(x.astype(np.float32))
+
+
+def occgrid_update(occs: Tensor, cells: Tensor, vals: Tensor, decay: float = 0.95, occ_thre: float = 1e-2):
+    """One update_every_n_steps over all levels, after the selection: `cells` int64 [n] global cell indices (the levels'
+    draws concatenated; -1 = an unused draw, skipped), `vals` [n] the occ_eval_fn values of the draws.  Float32: every
+    touched cell once, occs = max(occs * decay, max over the cell's draws) (NaN values are skipped, as the kernel does);
+    threshold = min(mean(occs), occ_thre) with the mean in float64; binaries = occs > threshold (in float32).
+    -> (occs float32 [n_cells], touched bool [n_cells], threshold float, binaries bool [n_cells])."""
+    import numpy as np
+    f = np.float32
+    occ = occs.detach().cpu().numpy().astype(f).copy()
+    c = cells.detach().cpu().numpy().astype(np.int64).reshape(-1)
+    v = vals.detach().cpu().numpy().astype(f).reshape(-1)
+    ok = (c >= 0) & ~np.isnan(v)
+    best = np.full(occ.shape[0], -np.inf, f)
+    np.maximum.at(best, c[ok], v[ok])
+    touched = np.zeros(occ.shape[0], bool)
+    touched[c[ok]] = True
+    occ[touched] = np.maximum(occ[touched] * f(decay), best[touched])
+    thr = min(float(occ.astype(np.float64).mean()), float(occ_thre))
+    return torch.from_numpy(occ), torch.from_numpy(touched), thr, torch.from_numpy(occ > f(thr))

@@ -151,19 +151,18 @@ def test_update_and_render_through_reference_call_shape():
     seed1 = est.update_seed(0)
     est.update_every_n_steps(step=512, occ_eval_fn=occ_eval_fn)  # past warm-up: subset + EMA decay
     assert not torch.equal(before, est.occs)
-    # ... replayed: res^3/4 uniform draws + res^3/4 draws from the occupied cells (read from the bit field on the device),
-    # duplicates resolved by a maximum, every touched cell decayed exactly once
+    # ... replayed: res^3/4 uniform draws + res^3/4 draws from the occupied cells (read from the bit field on the device;
+    # each occupied cell once when there are at most res^3/4), duplicates resolved by a maximum, every touched cell
+    # decayed exactly once
     k = 32 ** 3 // 4
     cells_o, x_o = O.occgrid_select(bin_before, est.level_aabb(0), 32, False, k, k, seed1)
     cells_h, x_h = ops.occgrid_select(bits_before, est.aabb, 32, 1, 0, False, k, k, seed1)
     assert torch.equal(cells_h.cpu(), cells_o) and torch.equal(x_h.cpu(), x_o), "the device's draws = the oracle's"
-    assert bool(bin_before.reshape(-1)[cells_o[k:]].all()), "the second half of the draws are occupied cells"
+    occ_draws = cells_o[k:][cells_o[k:] >= 0]  # (-1: an unused draw of a level with at most k occupied cells)
+    assert bool(bin_before.reshape(-1)[occ_draws].all()), "the second half of the draws are occupied cells"
     with torch.no_grad():
         v = (m(x_o.to(dev)).reshape(-1) * step).cpu()
-    want = before.cpu().clone()
-    best = torch.full_like(want, float("-inf")).scatter_reduce(0, cells_o, v, "amax", include_self=True)
-    hit = torch.isfinite(best)
-    want[hit] = torch.maximum(want[hit] * 0.95, best[hit])
+    want, hit, _, _ = O.occgrid_update(before, cells_o, v, 0.95)
     assert torch.allclose(est.occs.cpu(), want, rtol=1e-5, atol=1e-6)
     assert int(hit.sum()) < 2 * k, "draws with replacement: some cells were drawn more than once"
     # render + one optimisation step through the packed path
