@@ -2,7 +2,7 @@
 """A run-nerf.py-shaped driver on the drop-in modules (no dataset files, no network): a teacher NeRF renders the
 "photographs" of a Lego-style orbit, a student is trained on them with the reference's loop structure
 (src/run-nerf.py:216-299: ray batch -> render_rays(train=True) -> MSE -> backward -> Adam -> ExponentialDecay ->
-estimator.update_every_n_steps) and evaluated with render_frame + PSNR (run-nerf.py:140-190).
+estimator.update_every_n_steps) and evaluated with render_frame + PSNR and SSIM (run-nerf.py:140-190).
 
     python examples/train_synthetic.py [--estimator occgrid|stratified] [--iters 400] [--hw 64]
 """
@@ -16,6 +16,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import fs_nerf_amd  # noqa: E402,F401
+from fs_nerf_amd.core import metrics  # noqa: E402
 from fs_nerf_amd.core import models as M  # noqa: E402
 from fs_nerf_amd.core.loss import WeightNormRegularizer  # noqa: E402
 from fs_nerf_amd.core.optim import FusedAdam  # noqa: E402
@@ -107,9 +108,10 @@ def main():
         img, _ = R.render_frame(hwf, near, far, orbit_pose(22.5), 1 << 20, estimator, model, white_bkgd=True,
                                 render_step_size=step, device=dev)
         ref, _ = R.render_frame(hwf, near, far, orbit_pose(22.5), 1 << 20, t_est, teacher, white_bkgd=True, device=dev)
-    mse = float(torch.nn.functional.mse_loss(img, ref))
+    psnr = float(metrics.psnr(img, ref))  # run-nerf.py:157-160
+    ssim = float(metrics.ssim(img, ref, channel_axis=-1, data_range=1.0, gaussian_weights=True))  # run-nerf.py:180-189
     print(f"{a.iters} iterations of {a.batch} rays in {dt:.1f} s ({a.iters * a.batch / dt:,.0f} rays/s); held-out view PSNR "
-          f"{-10 * math.log10(max(mse, 1e-10)):.2f} dB; frame as uint8: {tuple(R.to8b(img).shape)}")
+          f"{psnr:.2f} dB, SSIM {ssim:.4f}; frame as uint8: {tuple(R.to8b(img).shape)}")
 
 
 if __name__ == "__main__":

@@ -19,6 +19,8 @@ FSN_PREC_FP16X2 = 6  # two passes (weights high part only), inference only
 FSN_STATUS_FP16_RANGE = 1  # a value reached fp16 infinity
 FSN_STATUS_FP16_SMALL = 2  # a layer's activations were all below 2^-14: outside the split's float32-grade envelope
 FSN_STATUS_GRAD_RANGE = 4  # backward with per-stage scales: a stored gradient overflowed (skipped step, scale drops; no fallback)
+FSN_SSIM_GAUSSIAN = 0  # fsn_ssim windows: skimage's gaussian_weights=True (11 taps, sigma 1.5) ...
+FSN_SSIM_UNIFORM = 1  # ... and its default 7 x 7 box
 
 
 class MlpDesc(C.Structure):
@@ -107,6 +109,11 @@ SIGNATURES = {
     "fsn_weight_norm_fwd": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "fsn_weight_norm_bwd": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "fsn_composite_packed_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fsn_ssim_workspace_doubles": (_i64, [_i64, _i, _i, _i]),
+    "fsn_ssim": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp, _vp]),
+    "fsn_psnr_workspace_doubles": (_i64, [_i64, _i, _i, _i]),
+    "fsn_psnr": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "fsn_debug_report_metrics": (_i, [_vp]),
 }
 
 _lib = None

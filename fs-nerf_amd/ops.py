@@ -973,3 +973,54 @@ def occgrid_update_multi(occs: Tensor, pending: Tensor, cells: Tensor, vals: Ten
     with torch.cuda.device(occs.device):
         L.check(L.lib().fsn_occgrid_update_multi(_p(occs), occs.numel(), _p(pending), _p(cells), _p(_f32(vals, "vals").reshape(-1)),
                                                  n, float(decay), _stream()), "fsn_occgrid_update_multi")
+
+
+# ------------------------------------------------------------------ evaluation metrics (run-nerf.py:108-191)
+def _f32_view(t: Tensor, name: str) -> Tensor:
+    """_f32 without the copy to a contiguous tensor: the metric kernels take any element strides."""
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: expected a GPU tensor (the HIP path has no CPU fallback)")
+    return t if t.dtype == torch.float32 else t.float()
+
+
+def _nchw_strides(t: Tensor):
+    assert t.dim() == 4
+    return (C.c_int64 * 4)(*t.stride())
+
+
+def ssim_nchw(x: Tensor, y: Tensor, window: int, use_sample_covariance: bool, data_range: float, K1: float, K2: float,
+              smap: Optional[Tensor] = None) -> Tensor:
+    """fsn_ssim on two (N, C, H, W) views of any strides -> float64 [N + 1]: each image's SSIM, then their mean.
+    smap (optional): a float32 (N, C, H, W) view of any strides that receives the uncropped S map."""
+    x, y = _f32_view(x, "im1"), _f32_view(y, "im2")
+    N, Ch, H, W = x.shape
+    assert y.shape == x.shape and y.device == x.device
+    dev = x.device
+    out = torch.empty(N + 1, dtype=torch.float64, device=dev)
+    nws = L.lib().fsn_ssim_workspace_doubles(N, Ch, H, W)
+    if nws < 0:
+        L.check(int(nws), "fsn_ssim_workspace_doubles")
+    ws = torch.empty(max(int(nws), 1), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().fsn_ssim(_p(x), _p(y), N, Ch, H, W, _nchw_strides(x), _nchw_strides(y), int(window),
+                                 1 if use_sample_covariance else 0, float(data_range), float(K1), float(K2), _p(ws), _p(out),
+                                 _p(smap), None if smap is None else _nchw_strides(smap), _stream()), "fsn_ssim")
+    return out
+
+
+def psnr_nchw(x: Tensor, y: Tensor) -> Tensor:
+    """fsn_psnr on two (N, C, H, W) views of any strides -> float32 [N + 1]: each image's -10 log10(MSE), then the
+    stack's (one MSE over every element)."""
+    x, y = _f32_view(x, "pred"), _f32_view(y, "gt")
+    N, Ch, H, W = x.shape
+    assert y.shape == x.shape and y.device == x.device
+    dev = x.device
+    out = torch.empty(N + 1, dtype=torch.float32, device=dev)
+    nws = L.lib().fsn_psnr_workspace_doubles(N, Ch, H, W)
+    if nws < 0:
+        L.check(int(nws), "fsn_psnr_workspace_doubles")
+    ws = torch.empty(max(int(nws), 1), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().fsn_psnr(_p(x), _p(y), N, Ch, H, W, _nchw_strides(x), _nchw_strides(y), _p(ws), _p(out), _stream()),
+                "fsn_psnr")
+    return out

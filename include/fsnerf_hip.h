@@ -491,6 +491,33 @@ int fsn_to8b_nchw(const float* frames, int64_t n_frames, int64_t hw, uint8_t* ou
 int fsn_depth_colormap(const float* depth, int64_t n_frames, int64_t hw, const float* vmin_vmax,
                        const uint8_t* lut_rgb8, uint8_t* out, fsn_stream_t stream);
 
+/* Evaluation metrics of the reference's evaluation() (src/run-nerf.py:108-191), on N image pairs x, y (float32,
+ * DEVICE) of C channels and H x W pixels.  Element (n, c, h, w) of an image is at ptr[n*s[0] + c*s[1] + h*s[2] + w*s[3]]
+ * with the strides (in elements) of a HOST int64 array s[4]: NHWC, NCHW and permuted views need no copy.  Sums are
+ * taken in float64 in a fixed order (no atomics): the results are bitwise reproducible.  N = 0 is a no-op.
+ * fsn_ssim: skimage.metrics.structural_similarity (scikit-image 0.22) per image, each channel on its own:
+ *   window FSN_SSIM_GAUSSIAN (gaussian_weights=True: sigma 1.5, truncate 3.5, 11 taps) or FSN_SSIM_UNIFORM (7 x 7 box),
+ *   separable, scipy's mode='reflect' edges; moments ux, uy, uxx, uyy, uxy; v = cn (uxx - ux^2) ...,
+ *   cn = NP / (NP - 1) with NP = win^2 when use_sample_covariance, else 1; C1 = (K1 data_range)^2, C2 = (K2 data_range)^2;
+ *   S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)).  out: N + 1 doubles = the mean of S over the
+ *   interior (the map cropped by the window radius) and the channels of each image, then the mean over the N images.
+ *   smap (optional, with smap_strides_host): the uncropped S map in float32.  H and W must be at least the window width.
+ *   workspace: fsn_ssim_workspace_doubles(N, C, H, W) doubles.
+ * fsn_psnr: out: N + 1 floats = -10 log10(MSE) of each image, then of the whole stack (one MSE over every element).
+ *   workspace: fsn_psnr_workspace_doubles(N, C, H, W) doubles. */
+#define FSN_SSIM_GAUSSIAN 0
+#define FSN_SSIM_UNIFORM 1
+int64_t fsn_ssim_workspace_doubles(int64_t N, int C, int H, int W);
+int fsn_ssim(const float* x, const float* y, int64_t N, int C, int H, int W, const int64_t* x_strides_host,
+             const int64_t* y_strides_host, int window, int use_sample_covariance, double data_range, double K1, double K2,
+             double* workspace, double* out, float* smap, const int64_t* smap_strides_host, fsn_stream_t stream);
+int64_t fsn_psnr_workspace_doubles(int64_t N, int C, int H, int W);
+int fsn_psnr(const float* x, const float* y, int64_t N, int C, int H, int W, const int64_t* x_strides_host,
+             const int64_t* y_strides_host, double* workspace, float* out, fsn_stream_t stream);
+/* Debug build only: the LDS index record of k_ssim_tile (4 uint32, as fsn_debug_report's), cleared by the call.  The
+ * release library returns FSN_E_UNSUPPORTED. */
+int fsn_debug_report_metrics(uint32_t* out_host);
+
 #ifdef __cplusplus
 }
 #endif
