@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — rendered rays/sec of the fused HIP ray-rendering path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 N=1 runs in this process.  N>1: under `python -m torch.distributed.run --nproc-per-node N ...` (RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* in the environment) every process is one rank; started plainly, `bench.py --gpus N` is its own
@@ -35,20 +35,25 @@ The JSON line also carries
                  rocprofv3 PMC pass (profiles/), or null;
                  `clock_ghz` = the clock the chip held DURING the timed launches (s_memtime / s_memrealtime stamps of
                  workgroup 0, fsn_render_args.clock_out), `mfma_busy_derived` = issued MFMAs x 16 cycles / (1024 SIMDs x
-                 that clock x the kernel time); `bare_stream` = the kernel's own GEMM code with nothing else in the
-                 kernel (fsn_bench_bare_stream: 256 -> 256 layers back to back, weight stream walking the real blob),
-                 launched on the same device right after the timed region, and `frac_of_bare_stream`; `fill` = the
-                 second ceiling: L2 -> LDS bytes the weight streams move per launch (every 128-sample tile streams a
-                 whole network) against the LDS-DMA fill rate MI355X_MICROARCH.md states and the bare stream reaches;
-  other_workloads - (default N=1 run only) the other rows' workloads timed in-process after the headline: `train`
+                 that clock x the kernel time); `fill` = the second ceiling: L2 -> LDS bytes the weight streams move
+                 per launch (every 128-sample tile streams a whole network) against the LDS-DMA fill rate
+                 MI355X_MICROARCH.md states.
+
+A plain run stops there: it sets up, warms up, times the steps, dumps and prints.  `--full` also measures, after the
+timed region and outside it:
+  roofline.bare_stream - the kernel's own GEMM code with nothing else in the kernel (fsn_bench_bare_stream: 256 -> 256
+                 layers back to back, weight stream walking the real blob), launched on the same device, with
+                 `frac_of_bare_stream` and `fill.bare_stream_tbps` (x3 modes only; null in a plain run);
+  other_workloads - (N=1 only) the other rows' workloads timed in-process after the headline: `train`
                  (configs[3]), `occgrid` (the reference's own render path), `train-occ` (its training loop body), `bf16`
                  (the headline frame in config 5's dtype) and `bf16_c5` (configs[4]: 1600x1600, 128+256): value,
-                 ms_per_step and fraction of the MFMA peak each, so that the driver's one run records them;
+                 ms_per_step and fraction of the MFMA peak each, so that one run records them all;
   cpu_baseline - the CPU oracle (PyTorch CPU ops, same operator sequence as the reference) timed on
                  this box's host cores on a bounded sample of the same workload (rank 0, N=1 only);
   cpu_baseline_c1 - BASELINE.json configs[0] exactly (100x100 orbit pool, 4096-ray batch drawn with
                  manual_seed(42), 64 coarse samples only, 4x128 MLP, mask off) on the host cores, all threads and
                  one thread, with the fused HIP launch on the same batch beside it.
+`--no-other-workloads` and `--no-cpu-baseline` leave parts of that out again.
 
 `--workload train` times the TRAINING step instead (BASELINE.json configs[3]): forward-facing
 LLFF-style scene, 8 views of 378x504 (focal 407.6), NDC rays, near 0 / far 1, 64+128 samples, one 8x256 NeRF,
@@ -742,7 +747,7 @@ def bare_stream_measure(ops, pm, dev, layers=4000):
 
 
 def other_workloads(args, dev, dist, backend):
-    """The other rows' workloads in-process (N=1 default run), so that the driver's ONE run records them (VERDICT r3
+    """The other rows' workloads in-process (N=1 `--full` run), so that ONE run records them (VERDICT r3
     missing #3): a few steps each, ~10 s together.  Each entry: value, unit, ms_per_step, frac (of the 2.5 PFLOP/s MFMA
     peak, algorithmic FLOPs of that workload), steps."""
     import types
@@ -852,8 +857,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--workload", choices=("render", "train", "occgrid", "train-occ"), default="render")
     ap.add_argument("--precision", default=os.environ.get("FSN_BENCH_PREC", "fp16x3"))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-workloads", action="store_true", help="skip the in-process train / occgrid / train-occ / bf16 lines")
+    ap.add_argument("--full", action="store_true",
+                    help="render workload: after the headline also measure the bare MFMA stream, the other workloads "
+                         "and the CPU baselines (a plain run does only what the headline needs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines (and the other workloads)")
+    ap.add_argument("--no-other-workloads", action="store_true", help="--full: skip the in-process train / occgrid / train-occ / bf16 lines")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="N>1: every rank its own frames (weak), or row blocks of the same frame (strong)")
     ap.add_argument("--cull-precision", choices=("bf16",), default=None,
@@ -994,7 +1002,7 @@ def main():
         clock_ghz = clk[0] / clk[1] * 0.1 if clk[1] > 0 else None
         mfma_per_launch = passes * FLOP_PER_RAY * nrows * W / 16384.0  # v_mfma_f32_16x16x32: 16,384 FLOP, 16 pipe cycles
         busy = mfma_per_launch * 16.0 / (1024 * clock_ghz * 1e9 * kern_ms * 1e-3) if clock_ghz else None
-        bare = bare_stream_measure(ops, pf, dev) if args.precision in ("fp16x3", "bf16x3") else None
+        bare = bare_stream_measure(ops, pf, dev) if args.full and args.precision in ("fp16x3", "bf16x3") else None
         kern_mfma_tflops = passes * achieved
         # the second ceiling: every 128-sample tile streams a whole network L2 -> LDS
         ub = 2 if passes > 1 else 1
@@ -1038,9 +1046,9 @@ def main():
                          "frac_of_bare_stream": None if bare is None else kern_mfma_tflops / bare["mfma_tflops"],
                          "fill": fill},
         }
-        if world == 1 and not args.no_cpu_baseline and not args.no_other_workloads:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.no_other_workloads:
             line["other_workloads"] = other_workloads(args, dev, dist, backend)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(10.0)
             line["cpu_baseline_c1"] = cpu_baseline_c1(dev)
         print(json.dumps(line), flush=True)

@@ -1,8 +1,10 @@
-"""bench.py prints ONE JSON line with the driver's contract keys plus `roofline` and `cpu_baseline`."""
+"""bench.py prints ONE JSON line with the driver's contract keys plus `roofline`; `--full` adds `cpu_baseline`,
+`other_workloads` and the roofline's bare stream."""
 import json
 import os
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -23,8 +25,23 @@ def _run(*args):
 
 
 @pytest.mark.gpu
+def test_plain_run_is_lean():
+    """A plain run does only what its headline needs: no CPU baselines, no other workloads, no bare stream, and at most
+    30 s of the whole process's time outside its warm-up and timed steps."""
+    t0 = time.perf_counter()
+    j = _run("--steps", "2", "--warmup", "1")
+    wall = time.perf_counter() - t0
+    assert KEYS <= set(j) and j["steps"] == 2 and j["warmup"] == 1 and j["unit"] == "rays/s"
+    assert not {"cpu_baseline", "cpu_baseline_c1", "other_workloads"} & set(j)
+    r = j["roofline"]
+    assert r["bare_stream"] is None and r["frac_of_bare_stream"] is None and r["fill"]["bare_stream_tbps"] is None
+    assert 0.05 < r["frac"] < 0.34 and 1.0 < r["clock_ghz"] < 2.6
+    assert wall - 3 * j["ms_per_step"] * 1e-3 < 30.0, (wall, j["ms_per_step"])
+
+
+@pytest.mark.gpu
 def test_render_line_contract():
-    j = _run("--steps", "1", "--warmup", "1")
+    j = _run("--steps", "1", "--warmup", "1", "--full")
     assert KEYS <= set(j) and "cpu_baseline" in j
     assert j["n_gpus"] == 1 and j["steps"] == 1 and j["warmup"] == 1 and j["higher_is_better"] is True
     assert j["scaling"] == "weak" and j["vs_baseline"] is None and j["data"] == "synthetic" and j["unit"] == "rays/s"
@@ -123,6 +140,11 @@ def test_dump_helpers(tmp_path):
     with pytest.raises(RuntimeError, match="64"):
         bench.dump_outputs(str(tmp_path / "big"), {"a": torch.zeros((64 << 20) // 4 + 1)})
     assert not os.path.exists(tmp_path / "big")
+
+
+def test_full_is_an_option():
+    out = _launch("--full", "--dry-run")
+    assert out.returncode == 0 and json.loads(out.stdout.splitlines()[-1])["dry_run"], out.stderr[-2000:]
 
 
 def test_steps_must_be_positive():
