@@ -114,6 +114,11 @@ SIGNATURES = {
     "fsn_psnr_workspace_doubles": (_i64, [_i64, _i, _i, _i]),
     "fsn_psnr": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "fsn_debug_report_metrics": (_i, [_vp]),
+    "fsn_lpips_pack_bytes": (_i64, []),
+    "fsn_lpips_pack": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fsn_lpips_workspace_floats": (_i64, [_i, _i]),
+    "fsn_lpips_vgg": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "fsn_debug_report_lpips": (_i, [_vp]),
 }
 
 _lib = None

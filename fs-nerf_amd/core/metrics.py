@@ -6,13 +6,18 @@ restates its arithmetic in HIP (csrc/metrics.hip): the Gaussian window of `gauss
 the default 7 x 7 box, scipy's `mode='reflect'` edges, the mean of the SSIM map over its interior in float64.  `psnr` is
 the reference's `-10 * log10(F.mse_loss(rgbs, rgbs_gt))`.  Both read their inputs in place through their strides (NHWC,
 NCHW or a permuted view), return device tensors and never copy a frame to the host.  There is no CPU fallback: CPU
-tensors raise.  LPIPS is not provided: the reference computes it and then discards it (`val_lpips = None`, :178)."""
+tensors raise.
+
+`LPIPS(net="vgg")` is the `lpips` package's LPIPS v0.1 with the VGG16 backbone, as a module with that package's
+parameter names, run by csrc/lpips.hip (implicit-GEMM convolutions on the f32 MFMA).  It ships no weights and downloads
+nothing: load the package's own state dict (`m.load_state_dict(torch.load("lpips_vgg.pt"))`).  `evaluation()` computes
+LPIPS only when it is given this class; the reference computes it and then discards it (`val_lpips = None`, :178)."""
 from __future__ import annotations
 
 from typing import Optional
 
 import torch
-from torch import Tensor
+from torch import Tensor, nn
 
 from .. import _lib as L
 from .. import ops
@@ -116,13 +121,148 @@ def psnr(pred: Tensor, gt: Tensor, reduction: str = "stack") -> Tensor:
     return out[N] if reduction == "stack" else out[:N]
 
 
+# ---------------------------------------------------------------- LPIPS (VGG16, v0.1)
+_VGG_CONVS = ((1, 0, 3, 64), (1, 2, 64, 64), (2, 5, 64, 128), (2, 7, 128, 128), (3, 10, 128, 256), (3, 12, 256, 256),
+              (3, 14, 256, 256), (4, 17, 256, 512), (4, 19, 512, 512), (4, 21, 512, 512), (5, 24, 512, 512),
+              (5, 26, 512, 512), (5, 28, 512, 512))  # (slice, torchvision `features` index, Cin, Cout)
+_SLICE_RANGES = {1: range(0, 4), 2: range(4, 9), 3: range(9, 16), 4: range(16, 23), 5: range(23, 30)}
+_TAP_CHANNELS = (64, 128, 256, 512, 512)
+_SHIFT = (-0.030, -0.088, -0.188)
+_SCALE = (0.458, 0.448, 0.450)
+_MIN_SIDE = 16  # four 2x2 pools leave relu5_3 at least one pixel
+
+
+class _ScalingLayer(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.register_buffer("shift", torch.tensor(_SHIFT)[None, :, None, None])
+        self.register_buffer("scale", torch.tensor(_SCALE)[None, :, None, None])
+
+
+class _LinLayer(nn.Module):
+    def __init__(self, c: int):
+        super().__init__()
+        self.model = nn.Sequential(nn.Dropout(), nn.Conv2d(c, 1, 1, stride=1, padding=0, bias=False))
+
+
+class _VGG16Slices(nn.Module):
+    """`lpips.pretrained_networks.vgg16`'s module tree: slice1..slice5 hold torchvision's `features` modules under
+    their original indices, so the state-dict keys are the package's (net.slice1.0.weight ... net.slice5.28.bias)."""
+
+    def __init__(self):
+        super().__init__()
+        convs = {idx: (cin, cout) for _, idx, cin, cout in _VGG_CONVS}
+        for k, rng in _SLICE_RANGES.items():
+            seq = nn.Sequential()
+            for i in rng:
+                if i in convs:
+                    seq.add_module(str(i), nn.Conv2d(convs[i][0], convs[i][1], 3, padding=1))
+                elif i in (4, 9, 16, 23):
+                    seq.add_module(str(i), nn.MaxPool2d(2, 2))
+                else:
+                    seq.add_module(str(i), nn.ReLU(inplace=False))
+            setattr(self, f"slice{k}", seq)
+
+    def convs(self):
+        return [getattr(getattr(self, f"slice{s}"), str(i)) for s, i, _, _ in _VGG_CONVS]
+
+
+class LPIPS(nn.Module):
+    """LPIPS v0.1 with the VGG16 backbone on the device: the `lpips` package's `LPIPS(net="vgg")` forward (no spatial
+    map, no gradients).  Parameter and buffer names are the package's, so its state dict loads as it is; the
+    `lins.K.model.1.weight` aliases of its module list are accepted, and `scaling_layer.*` is optional (the package's
+    constants).  The constructor downloads nothing and the module holds no usable weights until `load_state_dict`:
+    calling it before raises.  The weights are packed for the kernels once per weight version (csrc/lpips.hip)."""
+
+    def __init__(self, net: str = "vgg", version: str = "0.1"):
+        super().__init__()
+        if net != "vgg":
+            raise NotImplementedError(f"LPIPS(net={net!r}): only the VGG16 backbone is built")
+        if version != "0.1":
+            raise NotImplementedError(f"LPIPS(version={version!r}): only v0.1 is built")
+        self.scaling_layer = _ScalingLayer()
+        self.net = _VGG16Slices()
+        for k, c in enumerate(_TAP_CHANNELS):
+            setattr(self, f"lin{k}", _LinLayer(c))
+        for p in self.parameters():
+            p.requires_grad_(False)
+        self._loaded = False
+        self._packed = None
+        self._packed_key = None
+        self._register_load_state_dict_pre_hook(self._accept_package_keys)
+
+    @staticmethod
+    def _accept_package_keys(state_dict, prefix, *args):
+        for k in range(len(_TAP_CHANNELS)):
+            alias, key = f"{prefix}lins.{k}.model.1.weight", f"{prefix}lin{k}.model.1.weight"
+            if alias in state_dict:
+                v = state_dict.pop(alias)
+                state_dict.setdefault(key, v)
+        for name, val in (("shift", _SHIFT), ("scale", _SCALE)):
+            state_dict.setdefault(f"{prefix}scaling_layer.{name}", torch.tensor(val)[None, :, None, None])
+
+    def load_state_dict(self, state_dict, strict: bool = True, **kwargs):
+        out = super().load_state_dict(state_dict, strict=strict, **kwargs)
+        self._loaded = not out.missing_keys
+        self._packed_key = None
+        return out
+
+    def _tensors(self):
+        return ([c.weight for c in self.net.convs()] + [c.bias for c in self.net.convs()]
+                + [getattr(self, f"lin{k}").model[1].weight for k in range(len(_TAP_CHANNELS))]
+                + [self.scaling_layer.shift, self.scaling_layer.scale])
+
+    def packed(self) -> Tensor:
+        """The kernels' weight blob, re-packed when a parameter or buffer changed (data pointer or version)."""
+        ts = self._tensors()
+        key = tuple((t.data_ptr(), t._version) for t in ts)
+        if self._packed is None or key != self._packed_key:
+            self._packed = ops.lpips_pack(ts[:13], ts[13:26], ts[26:31], ts[31], ts[32], out=self._packed)
+            self._packed_key = key
+        return self._packed
+
+    def forward(self, in0: Tensor, in1: Tensor, retPerLayer: bool = False, normalize: bool = False):
+        """in0, in1: (N, 3, H, W) device tensors (any strides), in [-1, 1], or in [0, 1] with normalize=True.
+        Returns float32 (N, 1, 1, 1), and with retPerLayer the five taps' values as a list of (N, 1, 1, 1) too."""
+        if not self._loaded:
+            raise RuntimeError("LPIPS: no weights loaded (load the lpips package's VGG state dict with load_state_dict)")
+        if in0.shape != in1.shape:
+            raise ValueError(f"in0 and in1 must have the same shape: {tuple(in0.shape)} vs {tuple(in1.shape)}")
+        if in0.dim() != 4 or in0.shape[1] != 3:
+            raise ValueError(f"expected (N, 3, H, W) images, got shape {tuple(in0.shape)}")
+        if in0.shape[2] < _MIN_SIDE or in0.shape[3] < _MIN_SIDE:
+            raise ValueError(f"LPIPS-VGG needs images of at least {_MIN_SIDE} x {_MIN_SIDE}, got "
+                             f"{in0.shape[2]} x {in0.shape[3]}")
+        _check_device(in0, "in0")
+        _check_device(in1, "in1")
+        dev = self.scaling_layer.shift.device
+        if in0.device != dev or in1.device != dev:
+            raise RuntimeError(f"LPIPS: inputs on {in0.device} / {in1.device}, weights on {dev} (use .to(device))")
+        if torch.is_grad_enabled() and (in0.requires_grad or in1.requires_grad
+                                        or any(p.requires_grad for p in self.parameters())):
+            raise RuntimeError("LPIPS: gradients are not implemented (evaluation only); call it under torch.no_grad()")
+        N = in0.shape[0]
+        if N == 0:
+            val, per = in0.new_empty(0, dtype=torch.float32), in0.new_empty(5, 0, dtype=torch.float32)
+        else:
+            val, per = ops.lpips_vgg(self.packed(), in0.detach(), in1.detach(), normalize)
+        val = val.view(N, 1, 1, 1)
+        if retPerLayer:
+            return val, [per[k].view(N, 1, 1, 1) for k in range(len(_TAP_CHANNELS))]
+        return val
+
+
 def evaluation(hwf, model, estimator, lpips_net, data_loader, chunksize: int, device, render_step_size: float = 5e-3, *,
                white_bkgd: bool = False):
     """The reference's evaluation() (run-nerf.py:108-191) on this package: every validation view through render_frame,
     the frames kept on the device, then PSNR over the stack and SSIM per frame averaged over frames, each in one launch.
-    data_loader: an iterable of (rgb_gt [1,H,W,3], pose [1,4,4]) whose `.dataset` has near, far and ndc.  lpips_net is
-    accepted and ignored (the reference discards LPIPS).  white_bkgd is keyword-only: the reference reads it from its
-    global `args`.  Returns (psnr: 0-dim float32 tensor on the device, ssim: float, None)."""
+    data_loader: an iterable of (rgb_gt [1,H,W,3], pose [1,4,4]) whose `.dataset` has near, far and ndc.  white_bkgd is
+    keyword-only: the reference reads it from its global `args`.  Returns (psnr: 0-dim float32 tensor on the device,
+    ssim: float, lpips).  lpips: when lpips_net is this package's `LPIPS`, the mean over frames of
+    `lpips_net(rgbs, rgbs_gt)` (NCHW, [0, 1] inputs and normalize=False, the reference's call) as a 0-dim float32
+    device tensor; for any other lpips_net (None, the `lpips` package's module, ...) None, as the reference returns
+    (it computes the value and then discards it).  The reference's formula for 25 views or more (a sum of up to six
+    chunk means divided by five) is not restated: the value is always the mean over all frames."""
     from ..render import rendering as R
 
     ds = data_loader.dataset
@@ -137,4 +277,8 @@ def evaluation(hwf, model, estimator, lpips_net, data_loader, chunksize: int, de
     gts = torch.cat(gts, dim=0).to(device=rgbs.device, dtype=torch.float32)
     val_psnr = psnr(rgbs, gts)
     val_ssim = float(ssim(rgbs, gts, channel_axis=-1, data_range=1.0, gaussian_weights=True))
-    return val_psnr, val_ssim, None
+    val_lpips = None
+    if isinstance(lpips_net, LPIPS):
+        with torch.no_grad():
+            val_lpips = lpips_net(rgbs.permute(0, 3, 1, 2), gts.permute(0, 3, 1, 2)).mean()
+    return val_psnr, val_ssim, val_lpips

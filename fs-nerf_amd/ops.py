@@ -1024,3 +1024,43 @@ def psnr_nchw(x: Tensor, y: Tensor) -> Tensor:
         L.check(L.lib().fsn_psnr(_p(x), _p(y), N, Ch, H, W, _nchw_strides(x), _nchw_strides(y), _p(ws), _p(out), _stream()),
                 "fsn_psnr")
     return out
+
+
+# ------------------------------------------------------------------ LPIPS-VGG (csrc/lpips.hip)
+def lpips_pack(conv_w: Sequence[Tensor], conv_b: Sequence[Tensor], lin_w: Sequence[Tensor], shift: Tensor,
+               scale: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """fsn_lpips_pack: the 13 VGG16 convolutions ([Cout, Cin, 3, 3], [Cout]), the 5 lin heads ([1, C, 1, 1]) and the
+    scaling layer's shift / scale (3 values each) -> the kernels' uint8 blob on their device (re-uses `out`)."""
+    dev = conv_w[0].device
+    keep = [t.detach().to(dev, torch.float32).contiguous() for t in list(conv_w) + list(conv_b) + list(lin_w)]
+    keep += [shift.detach().to(dev, torch.float32).reshape(-1).contiguous(),
+             scale.detach().to(dev, torch.float32).reshape(-1).contiguous()]
+    if not all(t.is_cuda for t in keep):
+        raise RuntimeError("lpips_pack: expected GPU tensors (the HIP path has no CPU fallback)")
+    nbytes = int(L.lib().fsn_lpips_pack_bytes())
+    if out is None or out.numel() != nbytes or out.device != dev:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ptrs = [C.c_void_p(t.data_ptr()) for t in keep]
+    w_arr, b_arr, l_arr = (C.c_void_p * 13)(*ptrs[:13]), (C.c_void_p * 13)(*ptrs[13:26]), (C.c_void_p * 5)(*ptrs[26:31])
+    with torch.cuda.device(dev):
+        L.check(L.lib().fsn_lpips_pack(w_arr, b_arr, l_arr, ptrs[31], ptrs[32], _p(out), _stream()), "fsn_lpips_pack")
+    return out
+
+
+def lpips_vgg(packed: Tensor, x: Tensor, y: Tensor, normalize: bool) -> Tuple[Tensor, Tensor]:
+    """fsn_lpips_vgg on two (N, 3, H, W) views of any strides -> (float32 [N], float32 [5, N]): each pair's LPIPS and
+    its five per-tap values.  The workspace depends on H and W only."""
+    x, y = _f32_view(x, "in0"), _f32_view(y, "in1")
+    N, Ch, H, W = x.shape
+    assert Ch == 3 and y.shape == x.shape and y.device == x.device
+    dev = x.device
+    out = torch.empty(N, dtype=torch.float32, device=dev)
+    per = torch.empty(5, N, dtype=torch.float32, device=dev)
+    nws = L.lib().fsn_lpips_workspace_floats(H, W)
+    if nws < 0:
+        L.check(int(nws), "fsn_lpips_workspace_floats")
+    ws = torch.empty(int(nws), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().fsn_lpips_vgg(_p(packed), _p(x), _p(y), N, H, W, _nchw_strides(x), _nchw_strides(y),
+                                      1 if normalize else 0, _p(out), _p(per), _p(ws), _stream()), "fsn_lpips_vgg")
+    return out, per

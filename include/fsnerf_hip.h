@@ -518,6 +518,28 @@ int fsn_psnr(const float* x, const float* y, int64_t N, int C, int H, int W, con
  * release library returns FSN_E_UNSUPPORTED. */
 int fsn_debug_report_metrics(uint32_t* out_host);
 
+/* LPIPS v0.1, VGG16 backbone (the `lpips` package's LPIPS(net="vgg")), of N image pairs x, y (float32, DEVICE, 3
+ * channels, H x W >= 16 x 16), read through their element strides (n, c, h, w) as the metrics above.  Per pair: the
+ * optional 2x - 1 (normalize != 0), the scaling layer (x - shift) / scale, the 13 convolutions of VGG16's `features`
+ * (3x3, padding 1, bias, ReLU; 2x2 stride-2 max-pools, floor on odd sizes) on the f32 MFMA, and at relu1_2, relu2_2,
+ * relu3_3, relu4_3, relu5_3: each pixel's channel vector over (its norm + 1e-10), the squared difference, the 1x1 lin
+ * weights, the spatial mean; their sum.  Head sums in float64 in a fixed order: bitwise reproducible.
+ * fsn_lpips_pack: the weights (DEVICE float32, contiguous) into `packed` (fsn_lpips_pack_bytes() bytes, device):
+ *   conv_w_host / conv_b_host: HOST arrays of 13 device pointers ([Cout][Cin][3][3] and [Cout], VGG16 order),
+ *   lin_w_host: HOST array of 5 device pointers ([C] = the [1][C][1][1] lin weights), shift / scale: 3 floats each.
+ * fsn_lpips_vgg: out: N floats (one per pair); per_layer (optional): [5][N] floats, the five taps' values.
+ *   workspace: fsn_lpips_workspace_floats(H, W) floats (device), independent of N: the pairs run one after another.
+ *   N = 0 is a no-op. */
+int64_t fsn_lpips_pack_bytes(void);
+int fsn_lpips_pack(const float* const* conv_w_host, const float* const* conv_b_host, const float* const* lin_w_host,
+                   const float* shift, const float* scale, void* packed, fsn_stream_t stream);
+int64_t fsn_lpips_workspace_floats(int H, int W);
+int fsn_lpips_vgg(const void* packed, const float* x, const float* y, int64_t N, int H, int W,
+                  const int64_t* x_strides_host, const int64_t* y_strides_host, int normalize, float* out,
+                  float* per_layer, float* workspace, fsn_stream_t stream);
+/* Debug build only: the LDS index record of k_lpips_conv (4 uint32, as fsn_debug_report's), cleared by the call. */
+int fsn_debug_report_lpips(uint32_t* out_host);
+
 #ifdef __cplusplus
 }
 #endif
