@@ -51,6 +51,10 @@ def main():
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--cull-bf16", action="store_true",
                     help="opt-in: the occupancy estimator's visibility cull in single-pass bf16 (NeRF.cull_precision; not the parity mode)")
+    ap.add_argument("--refresh-precision", choices=("fp16", "bf16"), default=None,
+                    help="opt-in: the occupancy-grid refresh in that single-pass mode, one fused launch for all levels "
+                         "(NeRF.occ_eval_fn: the project's equivalent of the reference's autocast around it; default: "
+                         "the plain closure in the model's own mode)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     hwf = (a.hw, a.hw, 0.5 * a.hw / math.tan(0.5 * 0.6911112))
@@ -83,6 +87,9 @@ def main():
 
     def occ_eval_fn(x):
         return model(x) * step
+
+    if a.refresh_precision:
+        occ_eval_fn = model.occ_eval_fn(step, a.refresh_precision)
 
     t0 = time.perf_counter()
     for k in range(a.iters):

@@ -144,6 +144,7 @@ class NeRF(nn.Module):
     PRECISIONS = {"bf16x3": L.FSN_PREC_BF16X3, "bf16": L.FSN_PREC_BF16, "fp16x3": L.FSN_PREC_FP16X3,
                   "fp16": L.FSN_PREC_FP16, "fp16x2": L.FSN_PREC_FP16X2}
     FALLBACK = {"fp16x3": "bf16x3", "fp16x2": "bf16x3", "fp16": "bf16"}  # same pass structure, float32 range
+    SINGLE_PASS = ("fp16", "bf16")  # modes of `packed_single`: cull_precision, autocast_precision, OccEvalFn
 
     def __init__(self, d_pos: int = 3, d_dir: int = 3, n_layers: int = 8, d_hidden: int = 256,
                  skip: Tuple[int, ...] = (4,), precision: str = "fp16x3", **kwargs) -> None:
@@ -187,8 +188,12 @@ class NeRF(nn.Module):
         # That pass only decides which marched samples are KEPT (transmittance >= early_stop_eps); the kept samples are
         # then evaluated, integrated and differentiated in the model's own mode.  See `packed_cull`.
         self.cull_precision: Optional[str] = None
-        self._packed_cull = None
-        self._packed_cull_key = None
+        self._packed_single = {}  # mode -> (key, PackedMLP): `packed_single`
+        # OPT-IN, not a parity mode: this project's equivalent of running under autocast.  "fp16" / "bf16": a `forward`
+        # made under torch.no_grad() AND inside an enabled CUDA autocast region (the reference's occupancy refresh,
+        # run-nerf.py:288-295) runs in that single-pass mode, float32 tensor out.  None: autocast is ignored.  Training
+        # forwards never look at it.  A flagged fp16 call is re-run in bf16 and the attribute stays "bf16" (RuntimeWarning).
+        self.autocast_precision: Optional[str] = None
         # per-layer activation scaling of the fp16x3 inference path (module docstring)
         self.act_scaling = True
         self.act_target_exp = self.ACT_TARGET_EXP
@@ -471,20 +476,48 @@ class NeRF(nn.Module):
             self._packed_key = key
         return self._packed
 
+    def packed_single(self, precision: str) -> ops.PackedMLP:
+        """The weights packed for the single-pass mode `precision` ("fp16" / "bf16": no calibration), one cached blob
+        per mode beside the model's own (`packed`), re-packed when a parameter changed."""
+        if precision not in self.SINGLE_PASS:
+            raise ValueError(f"single-pass precision: one of {self.SINGLE_PASS}, not {precision!r}")
+        ws, bs = self._tensors()
+        key = (ws[0].device,) + self._param_key()
+        ent = self._packed_single.get(precision)
+        if ent is None or ent[0] != key:
+            pm = None if ent is None else ent[1]
+            if pm is None or pm.blob.device != ws[0].device:
+                desc = ops.make_desc(self.n_layers, self.d_hidden, self.skip, self.pos_encoder.freqs, self.dir_encoder.freqs)
+                pm = ops.PackedMLP(desc, self.PRECISIONS[precision], ws[0].device)
+            pm.pack(ws, bs)
+            self._packed_single[precision] = (key, pm)
+        return self._packed_single[precision][1]
+
     def packed_cull(self) -> ops.PackedMLP:
         """The weights packed for the mode `cull_precision` names (single-pass bf16: float32's range, no calibration and
         no range flags), re-packed when a parameter changed."""
         if self.cull_precision != "bf16":
             raise ValueError("NeRF.cull_precision: None or 'bf16'")
-        ws, bs = self._tensors()
-        key = (self.cull_precision, ws[0].device) + self._param_key()
-        if self._packed_cull is None or key != self._packed_cull_key:
-            desc = ops.make_desc(self.n_layers, self.d_hidden, self.skip, self.pos_encoder.freqs, self.dir_encoder.freqs)
-            if self._packed_cull is None or self._packed_cull.blob.device != ws[0].device:
-                self._packed_cull = ops.PackedMLP(desc, self.PRECISIONS[self.cull_precision], ws[0].device)
-            self._packed_cull.pack(ws, bs)
-            self._packed_cull_key = key
-        return self._packed_cull
+        return self.packed_single(self.cull_precision)
+
+    def occ_eval_fn(self, render_step_size: float, precision: str = "fp16") -> "OccEvalFn":
+        """`occ_eval_fn` for `update_every_n_steps`: x -> self(x) * render_step_size in the single-pass mode `precision`
+        (what the reference's closure computes under its autocast).  `OccGridEstimator` recognises the object and runs
+        the whole refresh in one launch; any other estimator just calls it.  See `OccEvalFn`."""
+        return OccEvalFn(self, render_step_size, precision)
+
+    def _autocast_mode(self) -> Optional[str]:
+        """The single-pass mode this inference forward runs in on account of `autocast_precision`, or None."""
+        ap = self.autocast_precision
+        if ap is None:
+            return None
+        if ap not in self.SINGLE_PASS:
+            raise ValueError(f"NeRF.autocast_precision: None or one of {self.SINGLE_PASS}, not {ap!r}")
+        return ap if not torch.is_grad_enabled() and torch.is_autocast_enabled("cuda") else None
+
+    def _leave_fp16_autocast(self, what: str, bits: int) -> str:
+        self.autocast_precision = "bf16"
+        return _warn_single_pass(self, what, bits)
 
     def _mask(self, m: Optional[Tensor], dev) -> Optional[Tensor]:
         return None if m is None else m.to(dev, torch.float32)
@@ -520,6 +553,11 @@ class NeRF(nn.Module):
             ws, bs = self._tensors()
             return _NerfTrainFn.apply(self, x, dirs, *ws, *bs)
         dev = x.device
+        mode = self._autocast_mode()
+        if mode is not None:
+            return single_pass_launch(self, mode, dev, "NeRF.forward (autocast_precision)", self._leave_fp16_autocast,
+                                      lambda pm: ops.mlp_fwd(pm, x, dirs, self._mask(self.pos_mask, dev),
+                                                             self._mask(self.dir_mask, dev)))
 
         def probe():
             xs = x.reshape(-1, 3)
@@ -530,6 +568,57 @@ class NeRF(nn.Module):
         return guarded_launch([self], dev, "NeRF.forward", probe,
                               lambda: ops.mlp_fwd(self.packed(probe), x, dirs, self._mask(self.pos_mask, dev),
                                                   self._mask(self.dir_mask, dev)))
+
+
+def _warn_single_pass(model: NeRF, what: str, bits: int) -> str:
+    model.range_events += 1
+    warnings.warn(f"fs-nerf HIP path: {what}: hidden activations left the fp16 range envelope of precision 'fp16' "
+                  f"({ops.describe_flags(bits)}); re-running / continuing in 'bf16'", RuntimeWarning, stacklevel=4)
+    return "bf16"
+
+
+def single_pass_launch(model: NeRF, precision: str, dev, what: str, leave_fp16, launch, undo=None):
+    """`launch(packed blob)` in the opt-in single-pass mode `precision` under the fp16 range guard (`guarded_launch`'s
+    policy for a mode that is not the model's own): "bf16" has float32's range and raises no flags - no host read;
+    "fp16" reads the launch's word back (one host sync, unless `model.range_check` is False), and a flagged launch leaves
+    no trace: `undo()`, `leave_fp16(what, bits)` (warns, moves its owner to "bf16" for good), and the call is made again
+    in bf16."""
+    out = launch(model.packed_single(precision))
+    if precision == "fp16" and model.range_check:
+        bits = ops.range_flags(dev)
+        if bits:
+            if undo is not None:
+                undo()
+            out = launch(model.packed_single(leave_fp16(what, bits)))
+    return out
+
+
+class OccEvalFn:
+    """`NeRF.occ_eval_fn(render_step_size, precision)`: the callable for the `occ_eval_fn` slot of
+    `update_every_n_steps` (run-nerf.py:288-295).  Called with points it returns `model(x) * render_step_size`, the density
+    pass evaluated in the single-pass mode `precision` through `fsn_mlp_fwd` - this project's equivalent of the
+    autocast region the reference wraps that call in, not a bit-for-bit copy of it.  `OccGridEstimator`
+    does not call it: it reads `model`, `render_step_size` and `precision` and runs selection, density pass and maximum
+    of all levels in one launch (`ops.occgrid_refresh`), with the same values bit for bit.  `precision` becomes "bf16"
+    for good after an fp16 call that left the range envelope (RuntimeWarning; the flagged call is repeated)."""
+
+    def __init__(self, model: NeRF, render_step_size: float, precision: str = "fp16") -> None:
+        if precision not in NeRF.SINGLE_PASS:
+            raise ValueError(f"OccEvalFn: precision is one of {NeRF.SINGLE_PASS}, not {precision!r}")
+        self.model, self.render_step_size, self.precision = model, float(render_step_size), precision
+
+    def _leave_fp16(self, what: str, bits: int) -> str:
+        self.precision = "bf16"
+        return _warn_single_pass(self.model, what, bits)
+
+    def guarded(self, dev, what: str, launch, undo=None):
+        """`launch(packed blob)` in this object's mode under the range guard (`single_pass_launch`)."""
+        return single_pass_launch(self.model, self.precision, dev, what, self._leave_fp16, launch, undo)
+
+    @torch.no_grad()
+    def __call__(self, x: Tensor) -> Tensor:
+        m, dev = self.model, x.device
+        return self.guarded(dev, "OccEvalFn", lambda pm: ops.mlp_fwd(pm, x, None, m._mask(m.pos_mask, dev))) * self.render_step_size
 
 
 def guarded_launch(nets: Sequence[NeRF], dev, what: str, probe, launch, earlier: str = "call"):

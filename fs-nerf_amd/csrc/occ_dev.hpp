@@ -117,4 +117,87 @@ __device__ __forceinline__ int march_ray(const GridDev& G, const uint32_t* __res
   return total;
 }
 
+// ---------------------------------------------------------------- update_every_n_steps: one draw of the cell selection
+// Shared by k_occ_select (occgrid.hip) and the fused refresh (occ_refresh.hip): ONE definition, so that both produce the
+// same cell and the same point bit for bit.  The rule is stated at k_occ_select.
+__device__ __host__ __forceinline__ uint32_t occ_mix(uint32_t x) {
+  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+  return x;
+}
+__device__ __host__ __forceinline__ uint32_t occ_rand(uint32_t i, uint32_t k, uint32_t seed_lo, uint32_t seed_hi) {
+  return occ_mix(occ_mix(i + seed_lo) ^ (seed_hi + 0x9e3779b9u * (k + 1u)));
+}
+
+// order-preserving integer key of a float (0 is below every key: "untouched" in the pending array)
+__device__ __forceinline__ uint32_t occ_key(float f) {
+  const uint32_t u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+struct OccDraw {
+  int32_t cell;  // cell index inside the level, or -1 for an unused occupied draw
+  float x, y, z;
+};
+
+// draw i of a level (bits / prefix: that level's words and popcount prefix; lo / hi: its box).  all_cells: draw i IS
+// cell i (warm-up).  A sentinel draw still gets a point: the one of its uniform cell r(i, 0) % res^3.
+__device__ __forceinline__ OccDraw occ_draw(const uint32_t* __restrict__ bits, const int32_t* __restrict__ prefix, int res,
+                                            int64_t i, int64_t n_draws, int64_t n_uniform, int all_cells, uint32_t seed_lo,
+                                            uint32_t seed_hi, float lox, float loy, float loz, float hix, float hiy,
+                                            float hiz) {
+  const uint32_t res3 = (uint32_t)res * res * res;
+  const int n_words = (int)(res3 >> 5);
+  uint32_t cell;
+  bool unused = false;
+  if (all_cells) {
+    cell = (uint32_t)i;
+  } else {
+    const uint32_t r = occ_rand((uint32_t)i, 0u, seed_lo, seed_hi);
+    cell = r % res3;
+    if (i >= n_uniform) {  // (prefix is only read here: it may be null when nothing is drawn from it)
+      const int32_t total = prefix[n_words];
+      const int64_t q = i - n_uniform, n_occupied = n_draws - n_uniform;
+      int32_t j;  // the j-th occupied cell of the level
+      if ((int64_t)total > n_occupied) {
+        j = (int32_t)(r % (uint32_t)total);
+      } else {
+        j = (int32_t)q;
+        unused = q >= (int64_t)total;
+      }
+      if (!unused) {
+        int lo = 0, hi = n_words;  // last word w with prefix[w] <= j
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (prefix[mid] <= j) lo = mid; else hi = mid; }
+        uint32_t m = bits[lo];
+        for (int b = j - prefix[lo]; b > 0; --b) m &= m - 1u;  // drop the lowest set bits below the wanted one
+        cell = ((uint32_t)lo << 5) + (uint32_t)(__ffs((int)m) - 1);
+      }
+    }
+  }
+  const uint32_t ix = cell / ((uint32_t)res * res), iy = (cell / (uint32_t)res) % (uint32_t)res, iz = cell % (uint32_t)res;
+  const float inv24 = 1.0f / 16777216.0f;
+  const float u0 = (float)(occ_rand((uint32_t)i, 1u, seed_lo, seed_hi) >> 8) * inv24;
+  const float u1 = (float)(occ_rand((uint32_t)i, 2u, seed_lo, seed_hi) >> 8) * inv24;
+  const float u2 = (float)(occ_rand((uint32_t)i, 3u, seed_lo, seed_hi) >> 8) * inv24;
+  const float fr = (float)res;
+  OccDraw d;
+  d.cell = unused ? -1 : (int32_t)cell;
+  d.x = lox + (((float)ix + u0) / fr) * (hix - lox);
+  d.y = loy + (((float)iy + u1) / fr) * (hiy - loy);
+  d.z = loz + (((float)iz + u2) / fr) * (hiz - loz);
+  return d;
+}
+
+// box of level `lvl`: the roi scaled by 2^lvl about its centre (OccGridEstimator.level_aabb)
+inline void level_box(const float* aabb_host, int lvl, float (&lo)[3], float (&hi)[3]) {
+  for (int a = 0; a < 3; ++a) {
+    const double c = ((double)aabb_host[a] + (double)aabb_host[3 + a]) / 2.0;
+    const double h = ((double)aabb_host[3 + a] - (double)aabb_host[a]) / 2.0 * (double)(1 << lvl);
+    lo[a] = (float)(c - h);
+    hi[a] = (float)(c + h);
+  }
+}
+
+// popcount prefix of `levels` consecutive levels' bit fields (occgrid.hip): prefix[l * (n_words + 1) + w]
+int launch_occ_word_prefix(const uint32_t* bits, int n_words, int levels, int32_t* prefix, hipStream_t s);
+
 }  // namespace fsn

@@ -93,18 +93,14 @@ __global__ void k_occ_ema(float* __restrict__ occs, const int64_t* __restrict__ 
 // n_uniform + n_occupied either way and nothing is read back to the host.  Counter-based randomness (a 32-bit mixing
 // hash of (seed, draw index, stream): no generator state on the device, the oracle restates it): draw i of stream k is
 // r(i, k) = mix(mix(i + seed_lo) ^ (seed_hi + 0x9e3779b9 (k + 1))).
-__device__ __host__ __forceinline__ uint32_t occ_mix(uint32_t x) {
-  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-  return x;
-}
-__device__ __host__ __forceinline__ uint32_t occ_rand(uint32_t i, uint32_t k, uint32_t seed_lo, uint32_t seed_hi) {
-  return occ_mix(occ_mix(i + seed_lo) ^ (seed_hi + 0x9e3779b9u * (k + 1u)));
-}
-
+// (occ_mix / occ_rand and the draw itself, occ_draw: occ_dev.hpp, shared with the fused refresh of occ_refresh.hip.)
 // exclusive prefix of the per-word popcounts of one level's bit field (n_words words): prefix[w], prefix[n_words] = total.
-// One block of 1024 threads: contiguous chunks per thread, block scan of the chunk sums.
+// One block of 1024 threads per level (block b: words b*n_words .., prefix b*(n_words+1) ..): contiguous chunks per
+// thread, block scan of the chunk sums.
 __global__ __launch_bounds__(1024) void k_occ_word_prefix(const uint32_t* __restrict__ bits, int n_words, int32_t* __restrict__ prefix) {
   __shared__ int32_t part[1024];
+  bits += (int64_t)blockIdx.x * n_words;
+  prefix += (int64_t)blockIdx.x * (n_words + 1);
   const int per = (n_words + 1023) / 1024;
   const int w0 = threadIdx.x * per, w1 = min(w0 + per, n_words);
   int32_t sum = 0;
@@ -122,60 +118,22 @@ __global__ __launch_bounds__(1024) void k_occ_word_prefix(const uint32_t* __rest
   if (threadIdx.x == 1023) prefix[n_words] = part[1023];
 }
 
-// draw i -> cell of level `lvl` (global index, or -1 for an unused occupied draw) and a point inside it.  all_cells:
-// draw i IS cell i (warm-up).  A sentinel draw still gets a point: the one of its uniform cell r(i, 0) % res^3.
+// draw i -> cell of level `lvl` (global index, or -1 for an unused occupied draw) and a point inside it (occ_draw).
 __global__ void k_occ_select(const uint32_t* __restrict__ bits, const int32_t* __restrict__ prefix, int res, int64_t lvl_cell0,
                              int64_t n_draws, int64_t n_uniform, int all_cells, uint32_t seed_lo, uint32_t seed_hi,
                              float lox, float loy, float loz, float hix, float hiy, float hiz,
                              int64_t* __restrict__ cells, float* __restrict__ x) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_draws) return;
-  const uint32_t res3 = (uint32_t)res * res * res;
-  const int n_words = (int)(res3 >> 5);
-  uint32_t cell;
-  bool unused = false;
-  if (all_cells) {
-    cell = (uint32_t)i;
-  } else {
-    const uint32_t r = occ_rand((uint32_t)i, 0u, seed_lo, seed_hi);
-    cell = r % res3;
-    if (i >= n_uniform) {  // (prefix is only read here: it may be null when nothing is drawn from it)
-      const int32_t total = prefix[n_words];
-      const int64_t q = i - n_uniform, n_occupied = n_draws - n_uniform;
-      int32_t j;  // the j-th occupied cell of the level
-      if ((int64_t)total > n_occupied) {
-        j = (int32_t)(r % (uint32_t)total);
-      } else {
-        j = (int32_t)q;
-        unused = q >= (int64_t)total;
-      }
-      if (!unused) {
-        int lo = 0, hi = n_words;  // last word w with prefix[w] <= j
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (prefix[mid] <= j) lo = mid; else hi = mid; }
-        uint32_t m = bits[lo];
-        for (int b = j - prefix[lo]; b > 0; --b) m &= m - 1u;  // drop the lowest set bits below the wanted one
-        cell = ((uint32_t)lo << 5) + (uint32_t)(__ffs((int)m) - 1);
-      }
-    }
-  }
-  const uint32_t ix = cell / ((uint32_t)res * res), iy = (cell / (uint32_t)res) % (uint32_t)res, iz = cell % (uint32_t)res;
-  const float inv24 = 1.0f / 16777216.0f;
-  const float u0 = (float)(occ_rand((uint32_t)i, 1u, seed_lo, seed_hi) >> 8) * inv24;
-  const float u1 = (float)(occ_rand((uint32_t)i, 2u, seed_lo, seed_hi) >> 8) * inv24;
-  const float u2 = (float)(occ_rand((uint32_t)i, 3u, seed_lo, seed_hi) >> 8) * inv24;
-  const float fr = (float)res;
-  cells[i] = unused ? (int64_t)-1 : lvl_cell0 + (int64_t)cell;
-  x[3 * i + 0] = lox + (((float)ix + u0) / fr) * (hix - lox);
-  x[3 * i + 1] = loy + (((float)iy + u1) / fr) * (hiy - loy);
-  x[3 * i + 2] = loz + (((float)iz + u2) / fr) * (hiz - loz);
+  const OccDraw d = occ_draw(bits, prefix, res, i, n_draws, n_uniform, all_cells, seed_lo, seed_hi, lox, loy, loz, hix, hiy, hiz);
+  cells[i] = d.cell < 0 ? (int64_t)-1 : lvl_cell0 + (int64_t)d.cell;
+  x[3 * i + 0] = d.x;
+  x[3 * i + 1] = d.y;
+  x[3 * i + 2] = d.z;
 }
 
 // EMA with duplicate cells (draws with replacement): pending[c] = max over the draws that hit c (order-preserving
 // integer keys, 0 = untouched), then ONE pass over all cells applies occs = max(occs * decay, pending) and clears it.
-__device__ __forceinline__ uint32_t occ_key(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 __global__ void k_occ_scatter_max(uint32_t* __restrict__ pending, const int64_t* __restrict__ cells,
                                   const float* __restrict__ vals, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -203,6 +161,12 @@ __global__ void k_occ_binarize(const float* __restrict__ occs, int64_t n_cells, 
   const int lane = threadIdx.x & 63;
   if (lane == 0 && c < n_cells) bits[c >> 5] = (uint32_t)m;
   if (lane == 32 && c < n_cells) bits[c >> 5] = (uint32_t)(m >> 32);
+}
+
+int launch_occ_word_prefix(const uint32_t* bits, int n_words, int levels, int32_t* prefix, hipStream_t s) {
+  k_occ_word_prefix<<<(unsigned)levels, 1024, 0, s>>>(bits, n_words, prefix);
+  FSN_LAUNCH_CHECK("k_occ_word_prefix");
+  return FSN_OK;
 }
 
 }  // namespace fsn
@@ -278,13 +242,8 @@ extern "C" int fsn_occgrid_select(const uint32_t* bits, int res, int levels, int
     k_occ_word_prefix<<<1, 1024, 0, s>>>(lb, (int)(res3 >> 5), prefix_scratch);
     FSN_LAUNCH_CHECK("k_occ_word_prefix");
   }
-  // level box: the roi scaled by 2^lvl about its centre (OccGridEstimator.level_aabb)
   float lo[3], hi[3];
-  for (int a = 0; a < 3; ++a) {
-    const double c = ((double)aabb_host[a] + (double)aabb_host[3 + a]) / 2.0, h = ((double)aabb_host[3 + a] - (double)aabb_host[a]) / 2.0 * (double)(1 << lvl);
-    lo[a] = (float)(c - h);
-    hi[a] = (float)(c + h);
-  }
+  level_box(aabb_host, lvl, lo, hi);
   k_occ_select<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(lb, prefix_scratch, res, (int64_t)lvl * res3, n,
                                                            (!all_cells && n_occupied == 0) ? n : n_uniform, all_cells ? 1 : 0,
                                                            (uint32_t)seed, (uint32_t)(seed >> 32), lo[0], lo[1], lo[2], hi[0],
@@ -302,6 +261,15 @@ extern "C" int fsn_occgrid_update_multi(float* occs, int64_t n_cells, uint32_t* 
   k_occ_scatter_max<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(pending, cells, vals, n);
   FSN_LAUNCH_CHECK("k_occ_scatter_max");
   k_occ_ema_pending<<<(unsigned)((n_cells + 255) / 256), 256, 0, s>>>(occs, pending, n_cells, decay);
+  FSN_LAUNCH_CHECK("k_occ_ema_pending");
+  return FSN_OK;
+}
+
+extern "C" int fsn_occgrid_apply_pending(float* occs, int64_t n_cells, uint32_t* pending, float decay, fsn_stream_t stream) {
+  FSN_REQUIRE(n_cells >= 0, FSN_E_INVALID, "fsn_occgrid_apply_pending: bad arguments");
+  if (n_cells == 0) return FSN_OK;
+  FSN_REQUIRE(occs && pending, FSN_E_INVALID, "fsn_occgrid_apply_pending: null pointer");
+  k_occ_ema_pending<<<(unsigned)((n_cells + 255) / 256), 256, 0, as_stream(stream)>>>(occs, pending, n_cells, decay);
   FSN_LAUNCH_CHECK("k_occ_ema_pending");
   return FSN_OK;
 }

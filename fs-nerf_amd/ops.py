@@ -975,6 +975,37 @@ def occgrid_update_multi(occs: Tensor, pending: Tensor, cells: Tensor, vals: Ten
                                                  n, float(decay), _stream()), "fsn_occgrid_update_multi")
 
 
+def occgrid_refresh(pm: PackedMLP, bits: Tensor, aabb: Sequence[float], res: int, levels: int, all_cells: bool,
+                    n_uniform: int, n_occupied: int, seeds: Sequence[int], step: float, pending: Tensor,
+                    prefix: Optional[Tensor] = None, pos_mask: Optional[Tensor] = None) -> None:
+    """The draws of ALL levels of an update, their densities in the single-pass mode of `pm` (FSN_PREC_FP16 / _BF16) and
+    pending[cell] = max(key(sigma * step)) in one launch (fsn_occgrid_refresh): what occgrid_select -> mlp_fwd -> `* step`
+    -> the first half of occgrid_update_multi do per level, same draws (seeds[l]: level l's seed) and same values bit
+    for bit, without the points, cells and densities in memory.  occgrid_apply_pending makes it the grid's.  prefix:
+    int32 [levels * (res^3/32 + 1)] scratch of the occupied draws.  Reports into the device's range word."""
+    res3 = int(res) ** 3
+    dev = bits.device
+    if prefix is None and not all_cells and n_occupied > 0:
+        prefix = torch.empty(int(levels) * (res3 // 32 + 1), dtype=torch.int32, device=dev)
+    if len(seeds) != int(levels):
+        raise ValueError("occgrid_refresh: one seed per level")
+    ab = (C.c_float * 6)(*[float(v) for v in aabb])
+    sd = (C.c_uint64 * int(levels))(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in seeds])
+    pmk = None if pos_mask is None else _f32(pos_mask, "pos_mask")
+    with torch.cuda.device(dev):
+        L.check(L.lib().fsn_occgrid_refresh(C.byref(pm.desc), pm.prec, _p(pm.blob), _p(pmk), _p(bits), int(res), int(levels), ab,
+                                            1 if all_cells else 0, int(n_uniform), int(n_occupied), sd, float(step),
+                                            _p(prefix), _p(pending), _p(status_word(dev)), _stream()), "fsn_occgrid_refresh")
+
+
+def occgrid_apply_pending(occs: Tensor, pending: Tensor, decay: float) -> None:
+    """occs[c] = max(occs[c] * decay, pending[c]) for the cells a refresh touched; `pending` is cleared
+    (fsn_occgrid_apply_pending: the second half of occgrid_update_multi)."""
+    with torch.cuda.device(occs.device):
+        L.check(L.lib().fsn_occgrid_apply_pending(_p(occs), occs.numel(), _p(pending), float(decay), _stream()),
+                "fsn_occgrid_apply_pending")
+
+
 # ------------------------------------------------------------------ evaluation metrics (run-nerf.py:108-191)
 def _f32_view(t: Tensor, name: str) -> Tensor:
     """_f32 without the copy to a contiguous tensor: the metric kernels take any element strides."""

@@ -11,6 +11,7 @@ import torch
 from torch import Tensor, nn
 
 from .. import ops
+from ..core.models import OccEvalFn
 
 
 class OccGridEstimator(nn.Module):
@@ -29,6 +30,7 @@ class OccGridEstimator(nn.Module):
         self._updates = 0      # update_every_n_steps calls that ran (part of the draws' seed; in the state_dict)
         self._pending = None   # scratch of the duplicate-safe EMA / the selection's popcount prefix (device)
         self._prefix = None
+        self._prefix_levels = None  # ... of all levels at once (the fused refresh)
 
     # -- state ---------------------------------------------------------------------
     # The update count is part of the draws' seed (update_seed): the state_dict carries it, so that a resumed run continues
@@ -100,6 +102,9 @@ class OccGridEstimator(nn.Module):
         level with at most res^3/4 occupied cells re-evaluates each of them exactly once (its other draws are unused:
         cell -1, skipped by the EMA, though occ_eval_fn still sees a point for them, so its batch size is fixed); only a
         denser level draws res^3/4 of them with replacement.
+        An `OccEvalFn` (`NeRF.occ_eval_fn(step, precision)`) in the slot is not called: selection, its density pass in
+        that single-pass mode, `* step` and the maximum per cell run in ONE launch for all levels (`_refresh_fused`) -
+        same draws, same schedule, same values as calling it level by level, bit for bit.
         Round 4: selection, jitter and the duplicate-safe EMA are kernels reading the bit field directly
         (fsn_occgrid_select / fsn_occgrid_update_multi); no host sync, no bool expansion of the grid.  Randomness is a
         counter-based hash of (seed, draw): seed = the estimator generator's (or torch's) initial seed and the number of
@@ -110,16 +115,35 @@ class OccGridEstimator(nn.Module):
         if self._pending is None or self._pending.device != self.occs.device:
             self._pending = torch.zeros(self.occs.numel(), dtype=torch.int32, device=self.occs.device)
             self._prefix = torch.empty(res3 // 32 + 1, dtype=torch.int32, device=self.occs.device)
-        for lvl in range(self.levels):
-            seed = self.update_seed(lvl)
-            warm = step < warmup_steps
-            cells, x = ops.occgrid_select(self.bits, self.aabb, res, self.levels, lvl, warm, res3 // 4, res3 // 4, seed,
-                                          self._prefix)
-            occ = occ_eval_fn(x).reshape(-1).float()
-            ops.occgrid_update_multi(self.occs, self._pending, cells, occ, ema_decay)
+        warm = step < warmup_steps
+        if isinstance(occ_eval_fn, OccEvalFn):
+            self._refresh_fused(occ_eval_fn, warm, ema_decay)
+        else:
+            for lvl in range(self.levels):
+                seed = self.update_seed(lvl)
+                cells, x = ops.occgrid_select(self.bits, self.aabb, res, self.levels, lvl, warm, res3 // 4, res3 // 4, seed,
+                                              self._prefix)
+                occ = occ_eval_fn(x).reshape(-1).float()
+                ops.occgrid_update_multi(self.occs, self._pending, cells, occ, ema_decay)
         self._updates += 1
         thr = torch.clamp(self.occs.mean(), max=occ_thre).reshape(1)
         ops.occgrid_update(self.occs, self.bits, None, None, 1.0, thr)
+
+    def _refresh_fused(self, fn: OccEvalFn, warm: bool, ema_decay: float) -> None:
+        """The level loop of update_every_n_steps in one launch (fsn_occgrid_refresh) + one EMA pass.  fp16: the range
+        word is read once (one host sync per refresh); a flagged refresh is undone (`pending` cleared - `occs` has not
+        been touched yet) and repeated in bf16, and `fn` stays in bf16."""
+        res, res3, dev = self.resolution, self.resolution ** 3, self.occs.device
+        if self._prefix_levels is None or self._prefix_levels.device != dev:
+            self._prefix_levels = torch.empty(self.levels * (res3 // 32 + 1), dtype=torch.int32, device=dev)
+        seeds = [self.update_seed(lvl) for lvl in range(self.levels)]
+        m = fn.model
+        fn.guarded(dev, "OccGridEstimator.update_every_n_steps",
+                   lambda pm: ops.occgrid_refresh(pm, self.bits, self.aabb, res, self.levels, warm, res3 // 4, res3 // 4, seeds,
+                                                  fn.render_step_size, self._pending, self._prefix_levels,
+                                                  m._mask(m.pos_mask, dev)),
+                   undo=self._pending.zero_)
+        ops.occgrid_apply_pending(self.occs, self._pending, ema_decay)
 
     def update_seed(self, lvl: int = 0) -> int:
         """64-bit seed of the NEXT update's draws at level `lvl` (see update_every_n_steps)."""

@@ -479,6 +479,23 @@ int fsn_occgrid_select(const uint32_t* bits, int res, int levels, int lvl, const
                        float* x, fsn_stream_t stream);
 int fsn_occgrid_update_multi(float* occs, int64_t n_cells, uint32_t* pending, const int64_t* cells, const float* vals,
                              int64_t n, float decay, fsn_stream_t stream);
+/* update_every_n_steps in ONE launch for all levels, the density pass in a single-pass mode (csrc/occ_refresh.hip): per
+ * draw (lvl, i), i < n = res^3 (all_cells) or n_uniform + n_occupied, the cell and the point of fsn_occgrid_select (same
+ * rule, counters and operation order; seeds_host: HOST uint64 [levels], level l's seed), the density of the packed
+ * network `blob` (fsn_mlp_pack in `prec`; FSN_PREC_FP16 or FSN_PREC_BF16, any other mode: FSN_E_UNSUPPORTED) at that
+ * point with pos_mask as in fsn_mlp_fwd, occ = sigma * step in float32, and pending[cell] = max(pending[cell], key(occ))
+ * as fsn_occgrid_update_multi forms it (NaN and the sentinel cell -1 skipped).  Points, cells and densities are not
+ * written anywhere.  prefix_scratch: DEVICE int32 [levels * (res^3/32 + 1)] (needed when n_occupied > 0 and not
+ * all_cells); pending: DEVICE uint32 [levels * res^3], all zero before the call; status: the range word of fsn_mlp_fwd.
+ * levels * res^3 and levels * n must be below 2^31.
+ * fsn_occgrid_apply_pending: the second half of fsn_occgrid_update_multi on its own - occs[c] = max(occs[c] * decay,
+ * pending[c]) for the touched cells, pending cleared.  (Apart, so that a caller can look at the status word - or zero
+ * `pending` and repeat the refresh in FSN_PREC_BF16 - before the grid changes.) */
+int fsn_occgrid_refresh(const fsn_mlp_desc* desc, int prec, const void* blob, const float* pos_mask, const uint32_t* bits,
+                        int res, int levels, const float* aabb_host, int all_cells, int64_t n_uniform, int64_t n_occupied,
+                        const uint64_t* seeds_host, float step, int32_t* prefix_scratch, uint32_t* pending,
+                        uint32_t* status, fsn_stream_t stream);
+int fsn_occgrid_apply_pending(float* occs, int64_t n_cells, uint32_t* pending, float decay, fsn_stream_t stream);
 
 /* f3: to8b(x) = (255 * clip(x, 0, 1)).astype(uint8)                    src/render/rendering.py:21 */
 int fsn_to8b(const float* x, int64_t n, uint8_t* out, fsn_stream_t stream);
