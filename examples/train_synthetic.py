@@ -4,7 +4,11 @@
 (src/run-nerf.py:216-299: ray batch -> render_rays(train=True) -> MSE -> backward -> Adam -> ExponentialDecay ->
 estimator.update_every_n_steps) and evaluated with render_frame + PSNR and SSIM (run-nerf.py:140-190).
 
-    python examples/train_synthetic.py [--estimator occgrid|stratified] [--iters 400] [--hw 64]
+    python examples/train_synthetic.py [--estimator occgrid|stratified] [--iters 400] [--hw 64] [--u8-dataset]
+
+--u8-dataset: the teacher's frames become uint8 "photographs" (R.to8b) held in a device-resident RayDataset; the loop
+takes its batches from a RayLoader the way run-nerf.py:236-240 takes them from its DataLoader, and the held-out view
+comes from a FrameLoader (fs_nerf_amd.nerfdata).
 """
 import argparse
 import math
@@ -21,6 +25,7 @@ from fs_nerf_amd.core import models as M  # noqa: E402
 from fs_nerf_amd.core.loss import WeightNormRegularizer  # noqa: E402
 from fs_nerf_amd.core.optim import FusedAdam  # noqa: E402
 from fs_nerf_amd.core.scheduler import ExponentialDecay  # noqa: E402
+from fs_nerf_amd.nerfdata import FrameLoader, RayDataset, RayLoader  # noqa: E402
 from fs_nerf_amd.render import rendering as R  # noqa: E402
 from fs_nerf_amd.render.occgrid import OccGridEstimator  # noqa: E402
 from fs_nerf_amd.utils import utilities as U  # noqa: E402
@@ -55,6 +60,9 @@ def main():
                     help="opt-in: the occupancy-grid refresh in that single-pass mode, one fused launch for all levels "
                          "(NeRF.occ_eval_fn: the project's equivalent of the reference's autocast around it; default: "
                          "the plain closure in the model's own mode)")
+    ap.add_argument("--u8-dataset", action="store_true",
+                    help="train on uint8 images through the device-resident RayDataset / RayLoader (epochs without "
+                         "replacement, one launch per batch) instead of float tables indexed with torch.randint")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     hwf = (a.hw, a.hw, 0.5 * a.hw / math.tan(0.5 * 0.6911112))
@@ -70,6 +78,16 @@ def main():
             rd.append(d.reshape(-1, 3))
             gt.append(R.render_frame(hwf, near, far, p, 1 << 20, t_est, teacher, white_bkgd=True, device=dev)[0].reshape(-1, 3))
     ro, rd, gt = torch.cat(ro), torch.cat(rd), torch.cat(gt)
+    held_out = orbit_pose(22.5)
+    if a.u8_dataset:  # the frames as photographs: bytes, resident; the float tables above are dropped
+        frames8 = R.to8b(gt).reshape(len(poses), a.hw, a.hw, 3)
+        train_set = RayDataset(frames8, torch.stack(poses), hwf, near=near, far=far, device=dev)
+        train_loader = RayLoader(train_set, a.batch, shuffle=True, seed=0)
+        iterator = iter(train_loader)
+        with torch.no_grad():
+            ref8 = R.to8b(R.render_frame(hwf, near, far, held_out, 1 << 20, t_est, teacher, white_bkgd=True, device=dev)[0])
+        val_loader = FrameLoader(RayDataset(ref8.reshape(1, a.hw, a.hw, 3), held_out[None], hwf, near=near, far=far, device=dev))
+        del ro, rd, gt
 
     model = make_model(2, dev).train()
     if a.cull_bf16:
@@ -93,10 +111,18 @@ def main():
 
     t0 = time.perf_counter()
     for k in range(a.iters):
-        idx = torch.randint(0, ro.shape[0], (a.batch,), device=dev, generator=gen)
-        (rgb, _, depth, _), _, _ = R.render_rays(ro[idx], rd[idx], estimator, model, train=True, white_bkgd=True,
+        if a.u8_dataset:
+            try:  # (run-nerf.py:236-240)
+                rays_o, rays_d, rgb_gt = next(iterator)
+            except StopIteration:
+                iterator = iter(train_loader)
+                rays_o, rays_d, rgb_gt = next(iterator)
+        else:
+            idx = torch.randint(0, ro.shape[0], (a.batch,), device=dev, generator=gen)
+            rays_o, rays_d, rgb_gt = ro[idx], rd[idx], gt[idx]
+        (rgb, _, depth, _), _, _ = R.render_rays(rays_o, rays_d, estimator, model, train=True, white_bkgd=True,
                                                  render_step_size=step, device=dev)
-        loss = torch.nn.functional.mse_loss(rgb, gt[idx])
+        loss = torch.nn.functional.mse_loss(rgb, rgb_gt)
         if wnorm.active(k):
             loss = loss + alpha * wnorm()
         loss.backward()
@@ -112,9 +138,12 @@ def main():
     model.eval()
     estimator.eval()
     with torch.no_grad():
-        img, _ = R.render_frame(hwf, near, far, orbit_pose(22.5), 1 << 20, estimator, model, white_bkgd=True,
+        img, _ = R.render_frame(hwf, near, far, held_out, 1 << 20, estimator, model, white_bkgd=True,
                                 render_step_size=step, device=dev)
-        ref, _ = R.render_frame(hwf, near, far, orbit_pose(22.5), 1 << 20, t_est, teacher, white_bkgd=True, device=dev)
+        if a.u8_dataset:
+            ref = next(iter(val_loader))[0][0]  # (rgb_gt [1,H,W,3], pose [1,4,4]) as evaluation() consumes them
+        else:
+            ref, _ = R.render_frame(hwf, near, far, held_out, 1 << 20, t_est, teacher, white_bkgd=True, device=dev)
     psnr = float(metrics.psnr(img, ref))  # run-nerf.py:157-160
     ssim = float(metrics.ssim(img, ref, channel_axis=-1, data_range=1.0, gaussian_weights=True))  # run-nerf.py:180-189
     print(f"{a.iters} iterations of {a.batch} rays in {dt:.1f} s ({a.iters * a.batch / dt:,.0f} rays/s); held-out view PSNR "

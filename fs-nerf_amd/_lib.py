@@ -21,6 +21,9 @@ FSN_STATUS_FP16_SMALL = 2  # a layer's activations were all below 2^-14: outside
 FSN_STATUS_GRAD_RANGE = 4  # backward with per-stage scales: a stored gradient overflowed (skipped step, scale drops; no fallback)
 FSN_SSIM_GAUSSIAN = 0  # fsn_ssim windows: skimage's gaussian_weights=True (11 taps, sigma 1.5) ...
 FSN_SSIM_UNIFORM = 1  # ... and its default 7 x 7 box
+FSN_RAY_ORDER_IDENTITY = 0  # fsn_ray_batch orders: index = start + i ...
+FSN_RAY_ORDER_PERMUTED = 1  # ... the epoch permutation of (seed, epoch) ...
+FSN_RAY_ORDER_EXPLICIT = 2  # ... an explicit device index list
 
 
 class MlpDesc(C.Structure):
@@ -69,6 +72,10 @@ SIGNATURES = {
     "fsn_get_rays": (_i, [_vp, _i, _i, _d, _i, _i, _vp, _vp, _vp]),
     "fsn_to_ndc": (_i, [_vp, _vp, _i64, _i, _i, _d, _d, _vp, _vp, _vp]),
     "fsn_build_rays": (_i, [_vp, _i64, _i, _i, _d, _i, _d, _vp, _vp, _vp, _vp, _vp]),
+    "fsn_ray_batch": (_i, [_vp, _i64, _vp, _i, _i, _i, _d, _i, _d, _i, _i, C.c_uint64, _i64, _vp, _i64, _i64, _vp, _vp, _vp,
+                           _vp, _vp]),
+    "fsn_ray_perm_host": (_i, [_i64, C.c_uint64, _i64, _i64, _i64, _vp]),
+    "fsn_debug_report_raydata": (_i, [_vp]),
     "fsn_posenc_fwd": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp]),
     "fsn_stratified_edges": (_i, [_f, _f, _i, _i64, _vp, _i, _vp, _vp]),
     "fsn_edges_to_packed": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp]),

@@ -226,6 +226,23 @@ __device__ __forceinline__ void pinhole_ray(const float* __restrict__ m, float h
   }
 }
 
+// World ray -> normalised device coordinates (src/utils/utilities.py:84-120), in place.  The one definition used by
+// k_to_ndc, k_build_rays (ray_ops.hip) and k_ray_batch (raydata.hip).
+__device__ __forceinline__ void ndc_ray(float (&o)[3], float (&d)[3], float sx, float sy, float near, float two_near) {
+  const float dx = d[0], dy = d[1], dz = d[2];
+  float ox = o[0], oy = o[1], oz = o[2];
+  const float t = -(near + oz) / dz;
+  ox = ox + t * dx;
+  oy = oy + t * dy;
+  oz = oz + t * dz;
+  o[0] = sx * ox / oz;
+  o[1] = sy * oy / oz;
+  o[2] = 1.0f + two_near / oz;
+  d[0] = sx * (dx / dz - ox / oz);
+  d[1] = sy * (dy / dz - oy / oz);
+  d[2] = -two_near / oz;
+}
+
 // edge i of the fixed-count stratified sampler (oracle.stratified_edges)
 __device__ __forceinline__ float stratified_edge(float near, float step, int S, int i, int u_mode,
                                                  const float* __restrict__ u_ray) {

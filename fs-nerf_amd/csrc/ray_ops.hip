@@ -27,22 +27,8 @@ __global__ void k_get_rays(Pose34 P, int W, float half_w, float half_h, float fo
 }
 
 // ---------------------------------------------------------------- to_ndc
-// reference: src/utils/utilities.py:84-120.  The one definition used by k_to_ndc and k_build_rays.
-__device__ __forceinline__ void ndc_ray(float (&o)[3], float (&d)[3], float sx, float sy, float near, float two_near) {
-  const float dx = d[0], dy = d[1], dz = d[2];
-  float ox = o[0], oy = o[1], oz = o[2];
-  const float t = -(near + oz) / dz;
-  ox = ox + t * dx;
-  oy = oy + t * dy;
-  oz = oz + t * dz;
-  o[0] = sx * ox / oz;
-  o[1] = sy * oy / oz;
-  o[2] = 1.0f + two_near / oz;
-  d[0] = sx * (dx / dz - ox / oz);
-  d[1] = sy * (dy / dz - oy / oz);
-  d[2] = -two_near / oz;
-}
-
+// reference: src/utils/utilities.py:84-120; ndc_ray (ray_dev.hpp) is the one definition used by k_to_ndc, k_build_rays
+// and k_ray_batch (raydata.hip).
 __global__ void k_to_ndc(const float* __restrict__ ro, const float* __restrict__ rd, int64_t n,
                          float sx, float sy, float near, float two_near, float* __restrict__ no,
                          float* __restrict__ nd) {

@@ -1,0 +1,170 @@
+// raydata.hip — the training loop's data layer on the device (reference: src/nerfdata/datasets/{blender,llff}.py and the
+// loaders of src/nerfdata/splitter.py:123-132).  The ray tables are pure functions of (pose, pixel), so a batch needs
+// nothing resident but the uint8 images and the poses: ONE launch, one thread per output ray,
+//   position in the epoch -> shuffled ray index (ray_perm.hpp) -> (view, row, column) -> ray (+ NDC) -> colour.
+// Rays: pinhole_ray / ndc_ray (ray_dev.hpp) with the arguments of k_build_rays: bit for bit row `index` of its tables.
+// Colours: bit for bit the reference's float images, which fixes the arithmetic (the library is built with
+// -ffp-contract=off):
+//   byte v -> (float)v / 255.0f   (the reference divides in float64 and rounds to float32: the same float for all 256
+//                                  bytes; a multiplication by 1.0f / 255.0f is not)
+//   white background (blender.py:114-117): c * a + (1.0f - a), three separate float32 operations in that order.
+// A latency-bound gather of a few hundred KB: 12-byte rows rule out 16-byte vector stores; plain coalesced stores.
+#include "common.hpp"
+#include "ray_dev.hpp"
+#include "ray_perm.hpp"
+
+namespace fsn {
+
+// debug build: an explicit index outside [0, N) is recorded (count, source line, index, N - both truncated to 32 bits),
+// read by fsn_debug_report_raydata.  In every build such a thread leaves its output rows untouched.
+FSN_DEBUG_DEFINE_RECORD(g_dbg_raydata)
+
+struct RayBatchArgs {
+  const float* poses;      // [n, 12]
+  const uint8_t* images;   // [n, H, W, C]
+  const int64_t* indices;  // explicit order: [count]
+  int64_t n_rays, per_view, start, count;
+  int W, C, ndc, white_bkgd, order;
+  float half_w, half_h, focal, sx, sy, near, two_near;
+  RayPerm perm;
+  float* rays_o;
+  float* rays_d;
+  float* rgb;
+  int64_t* index;
+};
+
+__global__ void __launch_bounds__(256) k_ray_batch(RayBatchArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.count) return;
+  int64_t idx;
+  if (a.order == FSN_RAY_ORDER_IDENTITY) {
+    idx = a.start + i;
+  } else if (a.order == FSN_RAY_ORDER_PERMUTED) {
+    idx = (int64_t)ray_perm_at(a.perm, (uint64_t)(a.start + i));
+  } else {
+    idx = a.indices[i];
+    if (idx < 0 || idx >= a.n_rays) {  // never reaches memory
+#ifdef FSN_DEBUG
+      if (atomicAdd(g_dbg_raydata, 1u) == 0u) {
+        g_dbg_raydata[1] = (unsigned)__LINE__;
+        g_dbg_raydata[2] = (unsigned)idx;
+        g_dbg_raydata[3] = (unsigned)a.n_rays;
+      }
+#endif
+      return;
+    }
+  }
+  if (a.index) a.index[i] = idx;
+  if (a.rays_o || a.rays_d) {
+    const int64_t view = idx / a.per_view, pix = idx - view * a.per_view;
+    float o[3], d[3];
+    pinhole_ray(a.poses + 12 * view, a.half_w, a.half_h, a.focal, (int)(pix / a.W), (int)(pix % a.W), o, d);
+    if (a.ndc) ndc_ray(o, d, a.sx, a.sy, a.near, a.two_near);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      if (a.rays_d) a.rays_d[3 * i + k] = d[k];
+      if (a.rays_o) a.rays_o[3 * i + k] = o[k];
+    }
+  }
+  if (a.rgb) {
+    const uint8_t* px = a.images + idx * a.C;
+    float c[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[k] = (float)px[k] / 255.0f;
+    if (a.white_bkgd) {
+      const float al = (float)px[3] / 255.0f;
+      const float rest = 1.0f - al;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const float m = c[k] * al;
+        c[k] = m + rest;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) a.rgb[3 * i + k] = c[k];
+  }
+}
+
+}  // namespace fsn
+
+using namespace fsn;
+
+extern "C" int fsn_ray_batch(const float* poses, int64_t n_views, const uint8_t* images, int H, int W, int C, double focal,
+                             int ndc, double near, int white_bkgd, int order, uint64_t seed, int64_t epoch,
+                             const int64_t* indices, int64_t start, int64_t count, float* rays_o, float* rays_d,
+                             float* rgb, int64_t* index, fsn_stream_t stream) {
+  FSN_REQUIRE(n_views >= 0 && H > 0 && W > 0 && focal > 0, FSN_E_INVALID,
+              "fsn_ray_batch: bad geometry n=%lld H=%d W=%d focal=%g", (long long)n_views, H, W, focal);
+  FSN_REQUIRE(C == 3 || C == 4, FSN_E_INVALID, "fsn_ray_batch: %d channels (the images are RGB or RGBA bytes: 3 or 4)", C);
+  FSN_REQUIRE(!white_bkgd || C == 4, FSN_E_INVALID,
+              "fsn_ray_batch: white_bkgd composes over the alpha channel and needs 4-channel images, got %d", C);
+  FSN_REQUIRE(order == FSN_RAY_ORDER_IDENTITY || order == FSN_RAY_ORDER_PERMUTED || order == FSN_RAY_ORDER_EXPLICIT,
+              FSN_E_INVALID, "fsn_ray_batch: unknown order %d", order);
+  FSN_REQUIRE(n_views <= ((int64_t)1 << 62) / ((int64_t)H * W), FSN_E_UNSUPPORTED, "fsn_ray_batch: more than 2^62 rays");
+  const int64_t per_view = (int64_t)H * W, n_rays = n_views * per_view;
+  FSN_REQUIRE(start >= 0 && count >= 0 && epoch >= 0, FSN_E_INVALID, "fsn_ray_batch: negative start, count or epoch");
+  if (order == FSN_RAY_ORDER_EXPLICIT) {
+    FSN_REQUIRE(start == 0, FSN_E_INVALID, "fsn_ray_batch: an explicit index list is served from its beginning (start = 0)");
+  } else {
+    FSN_REQUIRE(start <= n_rays && count <= n_rays - start, FSN_E_INVALID,
+                "fsn_ray_batch: positions [%lld, +%lld) leave the %lld rays of the dataset (start + count > N)",
+                (long long)start, (long long)count, (long long)n_rays);
+  }
+  FSN_REQUIRE(poses && images, FSN_E_INVALID, "fsn_ray_batch: null poses or images");
+  if (count == 0) return FSN_OK;
+  FSN_REQUIRE(order != FSN_RAY_ORDER_EXPLICIT || indices, FSN_E_INVALID, "fsn_ray_batch: null index list");
+  FSN_REQUIRE(rays_o || rays_d || rgb || index, FSN_E_INVALID, "fsn_ray_batch: null pointer for every output");
+  RayBatchArgs a{};
+  a.poses = poses;
+  a.images = images;
+  a.indices = indices;
+  a.n_rays = n_rays;
+  a.per_view = per_view;
+  a.start = start;
+  a.count = count;
+  a.W = W;
+  a.C = C;
+  a.ndc = ndc ? 1 : 0;
+  a.white_bkgd = white_bkgd ? 1 : 0;
+  a.order = order;
+  // the same roundings as fsn_build_rays: W * 0.5 etc. formed in double, then float32
+  a.half_w = (float)(W * 0.5);
+  a.half_h = (float)(H * 0.5);
+  a.focal = (float)focal;
+  a.sx = (float)(-1.0 / (W / (2.0 * focal)));
+  a.sy = (float)(-1.0 / (H / (2.0 * focal)));
+  a.near = (float)near;
+  a.two_near = (float)(2.0 * near);
+  if (order == FSN_RAY_ORDER_PERMUTED) a.perm = ray_perm_make((uint64_t)n_rays, seed, (uint64_t)epoch);
+  a.rays_o = rays_o;
+  a.rays_d = rays_d;
+  a.rgb = rgb;
+  a.index = index;
+  k_ray_batch<<<(unsigned)((count + 255) / 256), 256, 0, as_stream(stream)>>>(a);
+  FSN_LAUNCH_CHECK("k_ray_batch");
+  return FSN_OK;
+}
+
+extern "C" int fsn_ray_perm_host(int64_t N, uint64_t seed, int64_t epoch, int64_t start, int64_t count, int64_t* out_host) {
+  FSN_REQUIRE(N >= 0 && N <= ((int64_t)1 << 62) && epoch >= 0, FSN_E_INVALID, "fsn_ray_perm_host: bad N or epoch");
+  FSN_REQUIRE(start >= 0 && count >= 0 && start <= N && count <= N - start, FSN_E_INVALID,
+              "fsn_ray_perm_host: positions [%lld, +%lld) leave [0, %lld)", (long long)start, (long long)count, (long long)N);
+  if (count == 0) return FSN_OK;
+  FSN_REQUIRE(out_host, FSN_E_INVALID, "fsn_ray_perm_host: null pointer");
+  const RayPerm p = ray_perm_make((uint64_t)N, seed, (uint64_t)epoch);
+  for (int64_t i = 0; i < count; ++i) out_host[i] = (int64_t)ray_perm_at(p, (uint64_t)(start + i));
+  return FSN_OK;
+}
+
+extern "C" int fsn_debug_report_raydata(uint32_t* out_host) {
+  FSN_REQUIRE(out_host, FSN_E_INVALID, "fsn_debug_report_raydata: null pointer");
+#ifdef FSN_DEBUG
+  FSN_HIP(hipDeviceSynchronize());
+  unsigned zero[4] = {0u, 0u, 0u, 0u};
+  FSN_HIP(hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_dbg_raydata), sizeof(unsigned) * 4));
+  FSN_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_dbg_raydata), zero, sizeof(zero)));
+  return FSN_OK;
+#else
+  FSN_REQUIRE(false, FSN_E_UNSUPPORTED, "fsn_debug_report_raydata: not a debug build (make -C fs-nerf_amd/csrc debug)");
+#endif
+}

@@ -1,0 +1,197 @@
+"""Device-resident ray dataset and loaders: the arithmetic of the reference's src/nerfdata/datasets/{blender,llff}.py and
+the three loaders of src/nerfdata/splitter.py:123-132, behind the duck-typed surface its train() and evaluation()
+consume (run-nerf.py:134-152, 236-240, 384-456).
+
+The ray tables are pure functions of (pose, pixel), so only the uint8 images (3-4 bytes per pixel instead of 36 bytes
+of float tables), the poses and the region of interest are kept on the GPU.  A batch is ONE launch (ops.ray_batch /
+fsn_ray_batch): position in the epoch -> shuffled ray index -> (view, row, column) -> ray (+ NDC) -> ground-truth
+colour, bit for bit what the reference's float tables hold.  There is no CPU implementation."""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+from torch import Tensor
+
+from .. import ops
+from ..utils import utilities as U
+
+_NDC_NEAR = 1.0  # the reference maps to NDC with near = 1 (llff.py:76), as U.build_rays does
+
+
+class RayDataset:
+    """imgs: uint8 [n,H,W,3|4] (numpy or tensor), poses [n,3|4,4], hwf = (H, W, focal).
+
+    len() = n*H*W rays in the reference's order (view-major, then row-major pixels); dataset[i] and
+    dataset[index_tensor] -> (ray_o, ray_d, rgb), rows `i` of the reference's tables.  Attributes the reference's loops
+    read: near, far, ndc, hwf, aabb (device), poses ([n,4,4] float32 on the host, as the reference keeps them)."""
+
+    def __init__(self, imgs, poses, hwf: Tuple[int, int, float], *, near: float, far: float, ndc: bool = False,
+                 white_bkgd: bool = False, device=torch.device("cuda")):
+        device = U._need_gpu(device, "RayDataset")
+        imgs = torch.as_tensor(imgs)
+        if imgs.dtype != torch.uint8:
+            raise TypeError(f"RayDataset: images must be uint8 bytes, got {imgs.dtype}.  The colours served are bit for bit "
+                            "the reference's byte / 255.0 (and its alpha composition); a float image has already been "
+                            "rounded once and cannot give them back.  Pass the decoded bytes (R.to8b for renders).")
+        H, W, focal = int(hwf[0]), int(hwf[1]), float(hwf[2])
+        if imgs.dim() != 4 or tuple(imgs.shape[1:3]) != (H, W) or imgs.shape[3] not in (3, 4):
+            raise ValueError(f"RayDataset: images {tuple(imgs.shape)} are not [n, {H}, {W}, 3 or 4]")
+        if white_bkgd and imgs.shape[3] != 4:
+            raise ValueError("RayDataset: white_bkgd composes over the alpha channel and needs RGBA images")
+        P = torch.as_tensor(np.asarray(poses) if not isinstance(poses, Tensor) else poses).detach().to("cpu", torch.float32)
+        if P.dim() != 3 or P.shape[0] != imgs.shape[0] or P.shape[1] not in (3, 4) or P.shape[2] != 4:
+            raise ValueError(f"RayDataset: poses {tuple(P.shape)} are not [{imgs.shape[0]}, 3 or 4, 4]")
+        if P.shape[1] == 3:
+            P = torch.cat([P, torch.tensor([0.0, 0.0, 0.0, 1.0]).expand(P.shape[0], 1, 4)], dim=1)
+        self.hwf = (H, W, focal)
+        self.near, self.far, self.ndc, self.white_bkgd = near, far, bool(ndc), bool(white_bkgd)
+        self.poses = P.contiguous()
+        self.imgs = imgs.to(device).contiguous()
+        self.poses12 = self.poses[:, :3, :4].reshape(-1, 12).contiguous().to(device)
+        self.device = self.imgs.device
+        # the region of interest of the occupancy estimator (llff.py:77-86, blender.py:140)
+        if self.ndc and len(self):
+            _o, _d, self.aabb = U.build_rays(self.poses, self.hwf, self.device, ndc=True)  # the existing reduction;
+            del _o, _d                                                                     # its tables are dropped
+        else:
+            self.aabb = torch.tensor([-1.5, -1.5, -1.5, 1.5, 1.5, 1.5], device=self.device)
+
+    @classmethod
+    def blender(cls, imgs_rgba, poses, hwf, white_bkgd: bool = False, device=torch.device("cuda")) -> "RayDataset":
+        """BlenderDataset's constants (blender.py:104-106, 140): near 2, far 6, no NDC, region of interest +-1.5."""
+        return cls(imgs_rgba, poses, hwf, near=2.0, far=6.0, ndc=False, white_bkgd=white_bkgd, device=device)
+
+    @classmethod
+    def llff(cls, imgs, poses, min_bound: float, max_bound: float, hwf, ndc: bool = True,
+             device=torch.device("cuda")) -> "RayDataset":
+        """LLFFDataset's bounds (llff.py:48-53) and region of interest (llff.py:77-86)."""
+        near, far = (0.0, 1.0) if ndc else (min_bound * 0.9, max_bound * 1.0)
+        return cls(imgs, poses, hwf, near=near, far=far, ndc=ndc, white_bkgd=False, device=device)
+
+    # ------------------------------------------------------------------
+    @property
+    def n_views(self) -> int:
+        return self.imgs.shape[0]
+
+    def __len__(self) -> int:
+        return self.imgs.shape[0] * self.imgs.shape[1] * self.imgs.shape[2]
+
+    def batch(self, order: str, *, start: int = 0, count: Optional[int] = None, seed: int = 0, epoch: int = 0,
+              indices: Optional[Tensor] = None, want_rays: bool = True, want_rgb: bool = True, want_index: bool = False):
+        """ops.ray_batch on this dataset's tensors: (rays_o, rays_d, rgb, index), None where not wanted."""
+        H, W, focal = self.hwf
+        return ops.ray_batch(self.poses12, self.imgs, H, W, focal, ndc=self.ndc, near=_NDC_NEAR, white_bkgd=self.white_bkgd,
+                             order=order, seed=seed, epoch=epoch, indices=indices, start=start, count=count,
+                             want_rays=want_rays, want_rgb=want_rgb, want_index=want_index)
+
+    def __getitem__(self, idx):
+        """Not the hot path (the loaders never come here): a tensor of indices costs one min / max read-back so that an
+        index outside [0, len) raises IndexError BEFORE anything is launched."""
+        n = len(self)
+        if isinstance(idx, Tensor) and idx.dim() > 0:
+            if idx.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+                raise TypeError(f"RayDataset: indices must be integers, got {idx.dtype}")
+            if idx.numel():
+                lo, hi = (int(v) for v in torch.stack([idx.min(), idx.max()]).tolist())
+                if lo < 0 or hi >= n:
+                    raise IndexError(f"RayDataset: index {lo if lo < 0 else hi} is outside [0, {n})")
+            o, d, rgb, _ = self.batch("explicit", indices=idx.reshape(-1).to(self.device, torch.int64))
+            return o, d, rgb
+        i = int(idx)
+        if i < 0 or i >= n:
+            raise IndexError(f"RayDataset: index {i} is outside [0, {n})")
+        o, d, rgb, _ = self.batch("identity", start=i, count=1)
+        return o[0], d[0], rgb[0]
+
+
+def _seed_or_default(seed: Optional[int]) -> int:
+    return int(torch.initial_seed() if seed is None else seed) & 0xFFFFFFFFFFFFFFFF
+
+
+class RayLoader:
+    """The train loader (splitter.py:123-126: DataLoader(train_set, batch_size, shuffle=True)): every next() is ONE
+    launch returning device tensors (rays_o [B,3], rays_d [B,3], rgb [B,3]) (+ index [B] with `with_index`), no host
+    synchronisation.  Every iter() starts the next epoch under a new permutation (an abandoned iterator counts), an
+    epoch serves every ray exactly once, the last batch is short, then StopIteration.
+
+    world > 1 (ray-batch data parallelism, shard.py): all ranks walk the same permutation; global batch g is positions
+    [g*B*world, (g+1)*B*world) and rank r takes its r-th slice of B; the tail shorter than B*world is dropped so that
+    every rank makes the same number of steps.
+
+    state_dict() = (seed, epoch, next position); after load_state_dict() the next iter() continues that epoch at that
+    position with the very batches the original would have served."""
+
+    def __init__(self, dataset: RayDataset, batch_size: int, shuffle: bool = True, seed: Optional[int] = None, rank: int = 0,
+                 world: int = 1, with_index: bool = False):
+        if batch_size <= 0 or world <= 0 or not 0 <= rank < world:
+            raise ValueError(f"RayLoader: bad batch_size {batch_size}, rank {rank} or world {world}")
+        self.dataset, self.batch_size, self.shuffle = dataset, int(batch_size), bool(shuffle)
+        self.seed = _seed_or_default(seed)
+        self.rank, self.world, self.with_index = int(rank), int(world), bool(with_index)
+        self.epoch = -1       # epoch of the latest iterator (-1: none yet)
+        self.position = 0     # global batches of that epoch already served
+        self._resume = False  # load_state_dict(): the next iter() continues instead of advancing
+
+    def __len__(self) -> int:
+        n, stride = len(self.dataset), self.batch_size * self.world
+        return -(-n // stride) if self.world == 1 else n // stride
+
+    def __iter__(self) -> "_RayIterator":
+        if self._resume:
+            self._resume = False
+        else:
+            self.epoch += 1
+            self.position = 0
+        return _RayIterator(self, self.epoch, self.position)
+
+    def state_dict(self) -> dict:
+        return {"seed": self.seed, "epoch": self.epoch, "position": self.position}
+
+    def load_state_dict(self, state: dict) -> None:
+        self.seed, self.epoch, self.position = int(state["seed"]), int(state["epoch"]), int(state["position"])
+        self._resume = self.epoch >= 0
+
+
+class _RayIterator:
+    def __init__(self, loader: RayLoader, epoch: int, position: int):
+        self.loader, self.epoch, self.position = loader, epoch, position
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        ld = self.loader
+        if self.position >= len(ld):
+            raise StopIteration
+        B, n = ld.batch_size, len(ld.dataset)
+        start = (self.position * ld.world + ld.rank) * B
+        o, d, rgb, index = ld.dataset.batch("permuted" if ld.shuffle else "identity", start=start, count=min(B, n - start),
+                                            seed=ld.seed, epoch=self.epoch, want_index=ld.with_index)
+        self.position += 1
+        if ld.epoch == self.epoch:  # (an iterator abandoned for a newer one no longer moves the loader's state)
+            ld.position = self.position
+        return (o, d, rgb, index) if ld.with_index else (o, d, rgb)
+
+
+class FrameLoader:
+    """The val / test loader evaluation() consumes (splitter.py:127-132, image mode, batch size 1): yields
+    (rgb_gt [1,H,W,3] float32 on the device, pose [1,4,4]) per view, one launch per frame (identity order over that
+    frame's pixels, no rays).  shuffle: the views in the epoch permutation of (seed, epoch), a new one per iter()."""
+
+    def __init__(self, dataset: RayDataset, shuffle: bool = False, seed: Optional[int] = None):
+        self.dataset, self.shuffle, self.seed = dataset, bool(shuffle), _seed_or_default(seed)
+        self.epoch = -1
+
+    def __len__(self) -> int:
+        return self.dataset.n_views
+
+    def __iter__(self):
+        self.epoch += 1
+        ds, n = self.dataset, self.dataset.n_views
+        H, W, _ = ds.hwf
+        order = ops.ray_perm_host(n, self.seed, self.epoch).tolist() if self.shuffle else range(n)
+        for v in order:
+            _, _, rgb, _ = ds.batch("identity", start=v * H * W, count=H * W, want_rays=False)
+            yield rgb.reshape(1, H, W, 3), ds.poses[v:v + 1]

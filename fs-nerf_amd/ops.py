@@ -81,6 +81,50 @@ def build_rays(poses: Tensor, H: int, W: int, focal: float, device, ndc: bool = 
     return o, d, aabb
 
 
+_RAY_ORDERS = {"identity": L.FSN_RAY_ORDER_IDENTITY, "permuted": L.FSN_RAY_ORDER_PERMUTED, "explicit": L.FSN_RAY_ORDER_EXPLICIT}
+
+
+def ray_batch(poses12: Tensor, images: Tensor, H: int, W: int, focal: float, *, ndc: bool = False, near: float = 1.0,
+              white_bkgd: bool = False, order: str = "identity", seed: int = 0, epoch: int = 0,
+              indices: Optional[Tensor] = None, start: int = 0, count: Optional[int] = None, want_rays: bool = True,
+              want_rgb: bool = True, want_index: bool = False):
+    """One batch of the data layer in ONE launch (fsn_ray_batch), no host synchronisation: `count` rays from position
+    `start` of `order` ("identity", "permuted" by (seed, epoch), or "explicit" = the device int64 list `indices`) over
+    the rays of the resident dataset (poses12 [n,12] float32, images uint8 [n,H,W,3|4], both on the GPU) ->
+    (rays_o [count,3], rays_d [count,3], rgb [count,3], index [count] int64); an output not asked for is None."""
+    if not (poses12.is_cuda and images.is_cuda):
+        raise RuntimeError("ray_batch: expected GPU tensors (the HIP path has no CPU fallback)")
+    if images.dtype != torch.uint8 or poses12.dtype != torch.float32 or images.dim() != 4:
+        raise TypeError("ray_batch: images are uint8 [n,H,W,C] and poses float32 [n,12]")
+    assert images.is_contiguous() and poses12.is_contiguous() and images.shape[:3] == (poses12.shape[0], H, W)
+    if order == "explicit":
+        indices = _i64(indices, "indices")
+        count = indices.numel()
+    elif count is None:
+        raise ValueError("ray_batch: count is needed for the identity and permuted orders")
+    dev = images.device
+    o = torch.empty(count, 3, device=dev, dtype=torch.float32) if want_rays else None
+    d = torch.empty(count, 3, device=dev, dtype=torch.float32) if want_rays else None
+    rgb = torch.empty(count, 3, device=dev, dtype=torch.float32) if want_rgb else None
+    index = torch.empty(count, device=dev, dtype=torch.int64) if want_index else None
+    with torch.cuda.device(dev):
+        L.check(L.lib().fsn_ray_batch(_p(poses12), poses12.shape[0], _p(images), int(H), int(W), images.shape[3], float(focal),
+                                      1 if ndc else 0, float(near), 1 if white_bkgd else 0, _RAY_ORDERS[order],
+                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), _p(indices), int(start), int(count),
+                                      _p(o), _p(d), _p(rgb), _p(index), _stream()), "fsn_ray_batch")
+    return o, d, rgb, index
+
+
+def ray_perm_host(n: int, seed: int, epoch: int, start: int = 0, count: Optional[int] = None) -> Tensor:
+    """Positions [start, start + count) of the epoch permutation of [0, n) as a CPU int64 tensor (fsn_ray_perm_host: the
+    kernel's own function compiled for the host; no device is touched)."""
+    count = n - start if count is None else count
+    out = torch.empty(max(count, 0), dtype=torch.int64)
+    L.check(L.lib().fsn_ray_perm_host(int(n), int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), int(start), int(count),
+                                      C.c_void_p(out.data_ptr())), "fsn_ray_perm_host")
+    return out
+
+
 def to_ndc(rays_o: Tensor, rays_d: Tensor, H: int, W: int, focal: float, near: float) -> Tuple[Tensor, Tensor]:
     o, d = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d")
     n = o.numel() // 3

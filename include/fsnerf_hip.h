@@ -106,6 +106,36 @@ int fsn_to_ndc(const float* rays_o, const float* rays_d, int64_t n, int H, int W
 int fsn_build_rays(const float* poses, int64_t n_poses, int H, int W, double focal, int ndc, double near,
                    float* rays_o, float* rays_d, float* aabb, uint32_t* aabb_keys, fsn_stream_t stream);
 
+/* ---- the data layer: ray batches from the resident uint8 images and poses
+ *                                          src/nerfdata/datasets/{blender,llff}.py, splitter.py:123-132
+ * ONE launch, one thread per output ray: `count` rays starting at position `start` of an order over the
+ * N = n_views*H*W rays of the dataset (flat ray index = view*H*W + h*W + w, the row of fsn_build_rays' tables):
+ *   FSN_RAY_ORDER_IDENTITY   index = start + i
+ *   FSN_RAY_ORDER_PERMUTED   index = perm(start + i; N, seed, epoch): a stateless bijection of [0, N) keyed by
+ *                            (seed, epoch) (csrc/ray_perm.hpp: 4-round Feistel network + cycle walking); no N-sized table
+ *   FSN_RAY_ORDER_EXPLICIT   index = indices[i] (DEVICE int64 [count]; start must be 0).  An index outside [0, N) never
+ *                            reaches memory: its thread leaves its output rows untouched (and, in the debug build,
+ *                            records it for fsn_debug_report_raydata).
+ * poses: DEVICE [n_views, 12] (rows 0..2 of camera-to-world); images: DEVICE uint8 [n_views, H, W, C], C = 3 or 4;
+ * ndc / near as fsn_build_rays.  Outputs (DEVICE; each may be NULL = not wanted): rays_o, rays_d [count, 3] - bit for
+ * bit row `index` of fsn_build_rays' tables; rgb [count, 3] - bit for bit the reference's float images: byte / 255 and,
+ * with white_bkgd (C = 4 only), c * a + (1 - a) in three separate float32 operations (blender.py:114-117), else the
+ * first three channels; index [count] int64 - the flat ray index served.
+ * Errors (FSN_E_INVALID): null poses / images, C not in {3, 4}, white_bkgd with C = 3, start + count > N. */
+#define FSN_RAY_ORDER_IDENTITY 0
+#define FSN_RAY_ORDER_PERMUTED 1
+#define FSN_RAY_ORDER_EXPLICIT 2
+int fsn_ray_batch(const float* poses, int64_t n_views, const uint8_t* images, int H, int W, int C, double focal, int ndc,
+                  double near, int white_bkgd, int order, uint64_t seed, int64_t epoch, const int64_t* indices,
+                  int64_t start, int64_t count, float* rays_o, float* rays_d, float* rgb, int64_t* index,
+                  fsn_stream_t stream);
+/* The same permutation on the host (plain C++, no device is touched): out_host[i] = perm(start + i; N, seed, epoch) for
+ * i < count, start + count <= N <= 2^62. */
+int fsn_ray_perm_host(int64_t N, uint64_t seed, int64_t epoch, int64_t start, int64_t count, int64_t* out_host);
+/* Debug build only: the record of explicit indices outside [0, N) met by k_ray_batch (4 uint32: count, source line, the
+ * first index and N truncated to 32 bits), cleared by the call.  The release library returns FSN_E_UNSUPPORTED. */
+int fsn_debug_report_raydata(uint32_t* out_host);
+
 /* ---- a4: PositionalEncoder.forward(x)                    src/core/models.py:43-50
  * x [n, d_in] -> out [n, d_in*(1+2*n_freqs)], block order x, sin f0, cos f0, sin f1, ...
  * freqs_host: n_freqs float32 values (models.py:31-34).  mask (device, [d_out]) may be NULL:
