@@ -48,17 +48,6 @@ static int fill_pack_args(const fsn_mlp_desc* d, int prec, const float* const* W
   return FSN_OK;
 }
 
-static NetParams make_net_params(const fsn_mlp_desc& d, const NetGeom& G, const void* blob, uint32_t* status) {
-  NetParams p;
-  p.blob = static_cast<const char*>(blob);
-  p.aux_off = (int32_t)G.aux_off; p.aux_floats = G.aux_floats; p.stream_off = (int32_t)G.stream_off;
-  p.nph_density = G.nph_density; p.nph_full = G.nph_full;
-  p.n_layers = d.n_layers; p.skip_mask = d.skip_mask;
-  p.n_freqs_pos = d.n_freqs_pos; p.n_freqs_dir = d.n_freqs_dir;
-  p.status = status;
-  return p;
-}
-
 // ------------------------------------------------------------------ NeRF.forward kernel
 struct MlpFwdArgs {
   NetParams net;
@@ -99,9 +88,6 @@ struct TileSrc {
 // Persistent workgroups; tile = 128 NG consecutive samples; wave w / lane (c = lane&15, g = lane>>4) owns samples
 // tile0 + 16*(NG*w + q) + c, q < NG (NG = 2 sample groups per wave in the single-pass modes of 256-wide networks,
 // mlp_dev.hpp gemm_layer2).  LDS: [weight ring 64 KiB][aux + masks][tile inputs 128 NG x 6 floats].
-template <int NT, int PREC>
-constexpr int groups_per_wave() { return ((PREC & 1) == 1 && NT == 8) ? 2 : 1; }
-
 template <int NT, int PREC, bool FULL>
 __global__ __launch_bounds__(kThreads) void k_mlp_fwd(MlpFwdArgs a) {
   constexpr int NG = groups_per_wave<NT, PREC>(), TILE = 128 * NG;
@@ -321,21 +307,9 @@ static int mlp_fwd_any(const char* who, const fsn_mlp_desc* desc, int prec, cons
   FSN_REQUIRE(G.aux_floats <= kAuxCapFloats, FSN_E_UNSUPPORTED, "%s: network too deep for the LDS aux area", who);
   const int cus = fsn_device_cus();
   if (cus <= 0) return FSN_E_HIP;
-  a.net = make_net_params(*desc, G, blob, status);
+  a.net = net_params(*desc, G, blob, status);
   hipStream_t s = as_stream(stream);
-  if (prec == FSN_PREC_FP16X2) return desc->d_hidden == 256 ? launch_mlp_fwd<8, 6>(a, cus, s) : launch_mlp_fwd<4, 6>(a, cus, s);
-  if (prec == FSN_PREC_FP16X3U) return desc->d_hidden == 256 ? launch_mlp_fwd<8, 4>(a, cus, s) : launch_mlp_fwd<4, 4>(a, cus, s);
-  const int key = (desc->d_hidden == 256 ? 4 : 0) + prec;
-  switch (key) {
-    case 0: return launch_mlp_fwd<4, 0>(a, cus, s);
-    case 1: return launch_mlp_fwd<4, 1>(a, cus, s);
-    case 2: return launch_mlp_fwd<4, 2>(a, cus, s);
-    case 3: return launch_mlp_fwd<4, 3>(a, cus, s);
-    case 4: return launch_mlp_fwd<8, 0>(a, cus, s);
-    case 5: return launch_mlp_fwd<8, 1>(a, cus, s);
-    case 6: return launch_mlp_fwd<8, 2>(a, cus, s);
-    default: return launch_mlp_fwd<8, 3>(a, cus, s);
-  }
+  return dispatch_net(PrecInference{}, desc->d_hidden, prec, [&](auto NT, auto PREC) { return launch_mlp_fwd<NT(), PREC()>(a, cus, s); });
 }
 
 extern "C" int fsn_mlp_fwd(const fsn_mlp_desc* desc, int prec, const void* blob, const float* x, const float* dirs,
@@ -373,8 +347,8 @@ extern "C" int fsn_mlp_layer_maxima(const fsn_mlp_desc* desc, int prec, const vo
   if (cus <= 0) return FSN_E_HIP;
   MlpFwdArgs a{};
   a.x = x; a.dirs = dirs; a.pos_mask = pos_mask; a.dir_mask = dir_mask; a.n = n;
-  a.net = make_net_params(*desc, G, blob, nullptr);
+  a.net = net_params(*desc, G, blob, nullptr);
   hipStream_t s = as_stream(stream);
-  if (prec == FSN_PREC_BF16X3) return desc->d_hidden == 256 ? launch_mlp_maxima<8, 0>(a, maxima, cus, s) : launch_mlp_maxima<4, 0>(a, maxima, cus, s);
-  return desc->d_hidden == 256 ? launch_mlp_maxima<8, 4>(a, maxima, cus, s) : launch_mlp_maxima<4, 4>(a, maxima, cus, s);
+  return dispatch_net(PrecModes<FSN_PREC_BF16X3, FSN_PREC_FP16X3U>{}, desc->d_hidden, prec,
+                      [&](auto NT, auto PREC) { return launch_mlp_maxima<NT(), PREC()>(a, maxima, cus, s); });
 }

@@ -10,13 +10,13 @@
 //  * weights (A operands, pre-packed by mlp_layout.hpp) are streamed L2 -> LDS by
 //    global_load_lds_dwordx4 into a ring of 16-KiB phases shared by the 8 waves, two phases
 //    ahead, with counted vmcnt + raw s_barrier (no full drain inside the stream);
-//  * x3 modes (FSN_PREC_FP16X3 default, FSN_PREC_BF16X3): a.w = ah.wh + (al.wh + ah.wl), three MFMA
+//  * x3 modes (FSN_PREC_FP16X3, FSN_PREC_BF16X3): a.w = ah.wh + (al.wh + ah.wl), three MFMA
 //    passes on 16-bit high/low parts with fp32 accumulation; the two correction products have their
 //    own accumulator, and in the fp16 modes the low parts are kept scaled by 2^11 (mlp_layout.hpp,
 //    kLoScaleF16) so that they are normal fp16 numbers for |v| down to ~6e-5: fp16x3 ~ fp32 accuracy
 //    for layer scales from 2^-14 to 65504 (both ends are detected, never silent); bf16x3
 //    ~1e-5 per product, float32's range; FSN_PREC_BF16 / FSN_PREC_FP16: one pass.
-//  * FSN_PREC_FP16X3U (PREC 4, round 4; inference kernels): the same three products with UNSCALED low parts, all into one
+//  * FSN_PREC_FP16X3U (PREC 4, round 4; inference kernels, where it is the fp16x3 default): the same three products with UNSCALED low parts, all into one
 //    accumulator tile, no merge and a three-instruction split in the epilogue (rounds 1-2's arithmetic, 6 % faster).  It
 //    is float32-grade because the packed network is SCALED: a power of two per layer, folded into weights / biases /
 //    heads by the packer (mlp_pack.hpp) and calibrated from the layers' measured maxima, keeps every layer's activations
@@ -40,68 +40,30 @@ typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(8))) short s16x8;  // 8 raw 16-bit elements (bf16 or fp16 bits)
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-// threadIdx.x behind an empty asm (FSN_LAUNDER_ALL, a measured experiment, off): values derived from it are recomputed
-// where they are used instead of being hoisted out of the tile loops and spilled.  It takes the fused kernel to ZERO
-// spilled VGPRs in bf16 and 11 in fp16x3 - and makes the frames 8 % and 3.5 % SLOWER (141.2 against 130.5 ms, 427.2
-// against 412.8 ms): the recomputation lands inside the unit loop, and the volatile asm statements order against the
-// hand-scheduled blocks.  The per-group laundering in render.hip (57 -> 20 spills) is the part that pays.
-#ifdef FSN_LAUNDER_ALL
-__device__ __forceinline__ unsigned fsn_tidx() {
-  unsigned t = threadIdx.x;
-  asm volatile("" : "+v"(t));
-  return t;
-}
-#define FSN_TIDX (fsn_tidx())
-#else
-#define FSN_TIDX threadIdx.x
-#endif
-
-#ifndef FSN_NSLOT
-#define FSN_NSLOT 4
-#endif
-#ifndef FSN_LAG
-#define FSN_LAG 0
-#endif
-constexpr int kNSlot = FSN_NSLOT;     // LDS ring slots (phases)
-// FSN_LAG = 1: waves 4..7 of the workgroup run the weight stream ONE PHASE behind waves 0..3 (their SIMD partners):
-// they execute the same instruction stream, delayed by one barrier event (WStream::pass_begin / pass_end), so that
-// one wave's pair epilogue / bookkeeping falls into the middle of its partner's MFMA k-loop instead of both waves
-// leaving the matrix pipe idle at the same time.  Needs two more ring slots (see kLook).
-constexpr int kLag = FSN_LAG;
-#ifndef FSN_LEAD
-#ifdef FSN_KLOOP_ASM_D3
-#define FSN_LEAD 3
-#else
-#define FSN_LEAD 2
-#endif
-#endif
+constexpr int kNSlot = 4;  // LDS ring slots (phases)
 // A phase is "opened" (its loads waited for, workgroup barrier, next stage issued) kLead units
 // before the previous phase's last unit, so that the first LDS reads of the new phase are issued
 // underneath the tail MFMAs of the old one instead of behind the barrier.
-constexpr int kLead = FSN_LEAD;
-// phases staged ahead of the one being opened; with kLead > 0 the phase before the opened one is
-// still being read, so one more slot must stay untouched
-// Ring safety (E_b = the b-th barrier event; a phase q is read by the leading waves between E_q and E_q+1 - plus
-// the two units after E_q+1 on the compiler-scheduled path - and by lagging waves one event later; the stage issued
-// at E_b overwrites the slot of phase b + kLook - kNSlot): kNSlot >= kLook + 2 + kLag.
-constexpr int kLook = kLead > 0 ? kNSlot - 2 - kLag : kNSlot - 1;
-// loads of this wave that may stay in flight when a phase is opened: the lagging waves' share of a phase must have
-// landed one event before they read it themselves (the leading waves read it then), hence "- kLag"
-// LDS-DMA is issued by kLoaders loader waves only (one per SIMD; which half of the workgroup: FSN_LOADER_XOR): issuing a 1-KiB load costs the wave
+constexpr int kLead = 2;
+// phases staged ahead of the one being opened; the phase before the opened one is still being read, so one more slot
+// must stay untouched.  Ring safety (E_b = the b-th barrier event; a phase q is read between E_q and E_q+1 - plus the two units after
+// E_q+1 on the compiler-scheduled path; the stage issued at E_b overwrites the slot of phase b + kLook - kNSlot):
+// kNSlot >= kLook + 2.
+constexpr int kLook = 2;
+static_assert(kNSlot >= kLook + 2, "ring safety");
+// LDS-DMA is issued by kLoaders loader waves only (one per SIMD): issuing a 1-KiB load costs the wave
 // 60-185 cycles, and with the workgroup barrier in front of it every wave of the CU used to pay that at the same
-// moment; now the partner wave of each loader (w + 4) runs its MFMAs meanwhile.
+// moment; now the partner wave of each loader (w - 4) runs its MFMAs meanwhile.
 constexpr int kLoaders = 4;
-#ifndef FSN_LOADER_XOR  // 4: the loaders are waves 4..7, the later-dispatched wave of every SIMD (0: waves 0..3;
-#define FSN_LOADER_XOR 4  // measured 396.6 against 399.9 ms per fp16x3 frame, no difference in bf16)
-#endif
-constexpr int kOpenVmcnt = (kLook - 1 - kLag) * (kPhaseBytes / 1024 / kLoaders);
-#ifndef FSN_RING_EXPERIMENT  // (timing experiments with other ring depths: compiler-scheduled paths only)
+// wave ^ kLoaderXor < kLoaders: the loaders are waves 4..7, the later-dispatched wave of every SIMD (against waves
+// 0..3: measured 396.6 against 399.9 ms per fp16x3 frame, no difference in bf16)
+constexpr int kLoaderXor = 4;
+// loads of this wave that may stay in flight when a phase is opened
+constexpr int kOpenVmcnt = (kLook - 1) * (kPhaseBytes / 1024 / kLoaders);
 static_assert(kOpenVmcnt == 4, "the generated k-loop blocks wait with vmcnt(4)");
-#endif
 __device__ __forceinline__ uint32_t slot_add(uint32_t s, uint32_t k) {  // (s + k) mod kNSlot, s < kNSlot, k <= kNSlot
-  if ((kNSlot & (kNSlot - 1)) == 0) return (s + k) & (kNSlot - 1);
-  const uint32_t t = s + k;
-  return t >= (uint32_t)kNSlot ? t - kNSlot : t;
+  static_assert((kNSlot & (kNSlot - 1)) == 0, "power-of-two ring");
+  return (s + k) & (kNSlot - 1);
 }
 constexpr int kWaves = 8;             // wavefronts per workgroup (two per SIMD)
 constexpr int kThreads = 64 * kWaves;
@@ -117,14 +79,11 @@ __host__ __device__ constexpr int64_t t_layout_off(int NPL, int P, int pr, int s
   return (((int64_t)(s >> 4) * P + pr) * kTRow + (s & 15)) * NPL;
 }
 
-// properties of the arithmetic mode PREC (FSN_PREC_*)
-constexpr bool prec_f16(int P) { return P >= 2; }
-constexpr bool prec_x3(int P) { return (P & 1) == 0; }
-constexpr bool prec_lo_scaled_k(int P) { return P == 2 || P == 6; }  // fp16 low parts stored as fp16((v - high) * 2^11)
+// (properties of an arithmetic mode that host and device share: mlp_layout.hpp, prec_is_x3 ...)
 #ifndef FSN_BF16X3_ONEACC  // bf16x3 (low parts unscaled anyway) on the one-accumulator form too in the INFERENCE kernels:
 #define FSN_BF16X3_ONEACC 0  // 383.3 against 399.3 ms per headline frame (render.hip / render_occ.hip / mlp.hip set it)
 #endif
-constexpr bool prec_one_acc(int P) { return P == 4 || (FSN_BF16X3_ONEACC && P == 0); }  // one accumulator per tile, no merge
+constexpr bool prec_one_acc(int P) { return P == FSN_PREC_FP16X3U || (FSN_BF16X3_ONEACC && P == FSN_PREC_BF16X3); }  // one accumulator per tile, no merge
 
 struct Frag {  // one k-step (32 features x 16 samples) of activations as MFMA B operand
   s16x8 hi, lo;
@@ -177,7 +136,7 @@ struct WStream {
     // wave-uniform SALU arithmetic only (as next_stage below): the M0 base and the loader predicate are formed once
     // in init(), the end of a pass is a real branch
     const uint32_t m0v = m0_base + s_slot * kPhaseBytes;
-    const uint32_t voff = ((FSN_TIDX >> 6) ^ FSN_LOADER_XOR) * (kGldsPerWave * 1024) + (FSN_TIDX & 63) * 16;
+    const uint32_t voff = ((threadIdx.x >> 6) ^ kLoaderXor) * (kGldsPerWave * 1024) + (threadIdx.x & 63) * 16;
     const uint64_t sbase = (uint64_t)s_ptr;
     uint32_t keep;
     if (is_loader) {
@@ -206,16 +165,16 @@ struct WStream {
                                        uint32_t nB, uint32_t rB) {
     ring = ring_;
     ring_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)ring_;
-    m0_base = __builtin_amdgcn_readfirstlane(ring_lds + ((FSN_TIDX >> 6) ^ FSN_LOADER_XOR) * (kGldsPerWave * 1024));
-    is_loader = __builtin_amdgcn_readfirstlane((((FSN_TIDX >> 6) ^ FSN_LOADER_XOR) < (uint32_t)kLoaders) ? 1u : 0u);
+    m0_base = __builtin_amdgcn_readfirstlane(ring_lds + ((threadIdx.x >> 6) ^ kLoaderXor) * (kGldsPerWave * 1024));
+    is_loader = __builtin_amdgcn_readfirstlane((((threadIdx.x >> 6) ^ kLoaderXor) < (uint32_t)kLoaders) ? 1u : 0u);
     ptrA = pA; nphA = nA; repA = nA ? rA : 0;
     ptrB = pB; nphB = nB; repB = nB ? rB : 0;
     s_rep = 0; s_slot = 0; c_slot = 0;
     begin_pass_(repA ? 0u : 1u);
-    c_base = n_base = ring + (FSN_TIDX & 63) * 16;
+    c_base = n_base = ring + (threadIdx.x & 63) * 16;
 #pragma unroll
     for (int i = 0; i < kLook; ++i) stage();
-    if (kLead > 0) open_next();  // every pass finds its first phase already opened
+    open_next();  // every pass finds its first phase already opened
   }
   // Data-dependent schedules (render_occ.hip: the number of density-only and full tiles of a batch is only known
   // while it runs).  Both kinds of tile stream the SAME blob from its first phase and differ in where they stop, so the
@@ -227,27 +186,9 @@ struct WStream {
   // allowing the (kLook-1)*kGldsPerWave youngest loads to stay in flight retires exactly the oldest
   // staged phase), every wave is past the phase whose slot is restaged next.
   __device__ __forceinline__ void open_next() {
-#ifdef FSN_ABL_NOSTREAM  // timing experiment: no waits, barriers or staging
-    n_base = ring + c_slot * kPhaseBytes + (FSN_TIDX & 63) * 16;
-    c_slot = slot_add(c_slot, 1);
-    return;
-#endif
-#ifdef FSN_NLW_SKIP_VMWAIT
-    // Only the loader waves have LDS-DMA loads in flight; a non-loader wave's vmcnt counts nothing but its OWN stores
-    // (the training savers), which nobody needs to wait for here: it goes straight to the barrier, behind which every
-    // loader has seen its share of the phase land.
-    if (kLead > 0) {
-      if (is_loader) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kOpenVmcnt) : "memory");
-      asm volatile("s_barrier" ::: "memory");
-    } else
-#else
-    if (kLead > 0)
-      asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(kOpenVmcnt) : "memory");
-    else
-#endif
-      asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"((kLook - 1) * kGldsPerWave) : "memory");
+    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(kOpenVmcnt) : "memory");
     stage();
-    n_base = ring + c_slot * kPhaseBytes + (FSN_TIDX & 63) * 16;
+    n_base = ring + c_slot * kPhaseBytes + (threadIdx.x & 63) * 16;
     c_slot = slot_add(c_slot, 1);
   }
   __device__ __forceinline__ void enter_phase() { c_base = n_base; }
@@ -269,28 +210,19 @@ struct WStream {
     }
   }
   __device__ __forceinline__ uint32_t phase_lds(uint32_t k) const {
-    return ring_lds + slot_add(slot_add(c_slot, kNSlot - 1), k) * kPhaseBytes + (FSN_TIDX & 63) * 16;
+    return ring_lds + slot_add(slot_add(c_slot, kNSlot - 1), k) * kPhaseBytes + (threadIdx.x & 63) * 16;
   }
   __device__ __forceinline__ void opened(uint32_t n) {
     c_slot = slot_add(c_slot, n);
-    n_base = ring + slot_add(c_slot, kNSlot - 1) * kPhaseBytes + (FSN_TIDX & 63) * 16;
+    n_base = ring + slot_add(c_slot, kNSlot - 1) * kPhaseBytes + (threadIdx.x & 63) * 16;
     c_base = n_base;
   }
-  // ---- the one-phase lag between the two waves of a SIMD (kLag).  A "pass" is a run of MLP tiles between two
-  // workgroup barriers of the caller.  Waves 4..7 join one barrier event before their first unit (they then read
-  // phase p while waves 0..3 read phase p+1); waves 0..3 join one after their last so that every wave has taken
-  // part in the same number of events when the pass ends.  No staging, no waits: events only.
-  static __device__ __forceinline__ bool lagging() { return kLag && (__builtin_amdgcn_readfirstlane(FSN_TIDX) >= 256); }
-  __device__ __forceinline__ void pass_begin() const {
-#ifdef FSN_ABL_LAGSLEEP  // timing experiment (with the barrier-free ablation of the generator): waves 4..7 start every
-    // pass FSN_ABL_LAGSLEEP x 64 cycles late, so that the two waves of a SIMD run out of step
-    if (__builtin_amdgcn_readfirstlane(FSN_TIDX) >= 256) __builtin_amdgcn_s_sleep(FSN_ABL_LAGSLEEP);
-#endif
-    if (kLag && lagging()) asm volatile("s_barrier" ::: "memory");
-  }
-  __device__ __forceinline__ void pass_end() const {
-    if (kLag && !lagging()) asm volatile("s_barrier" ::: "memory");
-  }
+  // Pass boundaries of the caller: a "pass" is a run of MLP tiles between two workgroup barriers (render.hip).  Nothing
+  // happens at them.  The calls stay because hipcc's code for k_render_fused depends on their presence (without them the
+  // guards of the two tile loops come out with the opposite compare / branch polarity), and that kernel is kept
+  // instruction for instruction.
+  __device__ __forceinline__ void pass_begin() const {}
+  __device__ __forceinline__ void pass_end() const {}
   // before the workgroup exits (or touches the ring for anything else)
   __device__ __forceinline__ void drain() {
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -332,7 +264,6 @@ __device__ __forceinline__ void split_store_cpp(const float v[8], Frag& f) {
 // wait states only for instructions it sees.
 template <bool F16, bool X3, bool LS = (F16 && X3)>
 __device__ __forceinline__ void split_store(const float v[8], Frag& f) {
-#ifndef FSN_SPLIT_CPP
   if constexpr (F16 && X3 && !LS) {
     // UNSCALED low parts (FSN_PREC_FP16X3U): packed convert + one mixed-precision fma per value, low = fp16(v -
     // float(high)) with a single rounding - bit-identical to split_store_cpp (checked on 65,536 values incl. subnormals
@@ -380,7 +311,6 @@ __device__ __forceinline__ void split_store(const float v[8], Frag& f) {
     f.lo = __builtin_bit_cast(s16x8, l);
     return;
   }
-#endif
   split_store_cpp<F16, X3, LS>(v, f);
 }
 
@@ -440,7 +370,7 @@ __device__ __forceinline__ void range_report(uint32_t* status, const RangeState&
   const bool bad = (f & 0xffffu) >= 0x7c00u || (f >> 16) >= 0x7c00u;
   uint32_t bits = __builtin_amdgcn_readfirstlane((int)__any(bad)) ? range_bit : 0u;
   if (__builtin_amdgcn_readfirstlane((int)r.small)) bits |= 2u;
-  if (bits && status) { if ((FSN_TIDX & 63) == 0) __hip_atomic_fetch_or(status, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  if (bits && status) { if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_or(status, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 }
 
 // Network description as the kernel needs it (wave-uniform).  Aux offsets follow build_geom():
@@ -454,6 +384,46 @@ struct NetParams {  // host -> kernel argument
   int32_t n_freqs_pos, n_freqs_dir;
   uint32_t* status;  // device word or null: bit 0 is set when a hidden activation leaves the fp16 range
 };
+
+inline NetParams net_params(const fsn_mlp_desc& d, const NetGeom& G, const void* blob, uint32_t* status) {
+  NetParams p;
+  p.blob = static_cast<const char*>(blob);
+  p.aux_off = (int32_t)G.aux_off; p.aux_floats = G.aux_floats; p.stream_off = (int32_t)G.stream_off;
+  p.nph_density = G.nph_density; p.nph_full = G.nph_full;
+  p.n_layers = d.n_layers; p.skip_mask = d.skip_mask;
+  p.n_freqs_pos = d.n_freqs_pos; p.n_freqs_dir = d.n_freqs_dir;
+  p.status = status;
+  return p;
+}
+
+// Host-side dispatch from (d_hidden, prec) to the <NT, PREC> instantiation of an entry point.  MODES is the list of
+// arithmetic modes the entry point instantiates; f(NT, PREC) receives both as std::integral_constant (NT = 8 for
+// d_hidden 256, 4 for 128) and returns the entry point's code.  Anything else is FSN_E_UNSUPPORTED - unreachable behind
+// the entry points' own argument checks (build_geom and their FSN_REQUIRE on prec), which give the message.
+template <int... MODES>
+struct PrecModes {};
+template <int... MODES, class F>
+inline int dispatch_net(PrecModes<MODES...>, int d_hidden, int prec, F&& f) {
+  int rc = FSN_E_UNSUPPORTED;
+  auto mode = [&](auto PREC) {
+    if (prec != decltype(PREC)::value) return false;
+    if (d_hidden == 256) rc = f(std::integral_constant<int, 8>{}, PREC);
+    else if (d_hidden == 128) rc = f(std::integral_constant<int, 4>{}, PREC);
+    return true;
+  };
+  (void)(mode(std::integral_constant<int, MODES>{}) || ...);
+  return rc;
+}
+// the same for entry points that choose the arithmetic only
+template <int... MODES, class F>
+inline int dispatch_prec(PrecModes<MODES...>, int prec, F&& f) {
+  int rc = FSN_E_UNSUPPORTED;
+  auto mode = [&](auto PREC) { return prec == decltype(PREC)::value && (rc = f(PREC), true); };
+  (void)(mode(std::integral_constant<int, MODES>{}) || ...);
+  return rc;
+}
+using PrecInference = PrecModes<FSN_PREC_BF16X3, FSN_PREC_BF16, FSN_PREC_FP16X3, FSN_PREC_FP16, FSN_PREC_FP16X3U, FSN_PREC_FP16X2>;
+using PrecTraining = PrecModes<FSN_PREC_BF16X3, FSN_PREC_BF16, FSN_PREC_FP16X3, FSN_PREC_FP16>;
 
 struct NetDev {
   const float* aux;       // LDS copy of the blob's aux region
@@ -531,9 +501,6 @@ __device__ __forceinline__ void encode(float x0, float x1, float x2, int n_freqs
   if (g == 3) v[SLOTS - 2] = x2 * mask[2];
 #pragma unroll
   for (int k = 0; k < NKS; ++k) split_store<F16, X3, LS>(&v[8 * k], out[k]);
-#ifdef FSN_ABL_SAVE_NOLOADER
-  if (SAVE && (((FSN_TIDX >> 6) ^ FSN_LOADER_XOR) < (uint32_t)kLoaders)) return;
-#endif
   if constexpr (SAVE) {
     // packed T-layout (train_fused.hip): slots (k, 2i), (k, 2i+1) are rows 32k + 8g + 2i, +1 = pair-row 16k + 4g + i;
     // `save` = this lane's sample at pair-row 4g (t_layout_off); x3: the two parts of a pair as one 8-byte store
@@ -573,12 +540,6 @@ struct AFrag {  // A operand (weights) of one unit
 // A operands are read from the LDS ring one k-step (two units) ahead of their MFMAs; the pair in flight
 // carries over from GEMM to GEMM, tile to tile and pass to pass: on entry to a GEMM `cur` holds its
 // units 0 and 1.
-#ifndef FSN_KLOOP_D
-#define FSN_KLOOP_D 2
-#endif
-#ifndef FSN_KLOOP_NSETS
-#define FSN_KLOOP_NSETS (FSN_KLOOP_D + 1)
-#endif
 constexpr int kKD = FSN_KLOOP_D;  // A-operand units landed ahead of a pair on entry to a hand-scheduled block
 constexpr int kNS = FSN_KLOOP_NSETS;  // A register sets in rotation (unit u lives in set u mod kNS)
 struct ARing {
@@ -587,66 +548,28 @@ struct ARing {
 template <int PREC>
 __device__ __forceinline__ void load_afrag(const char* p, AFrag& f) {
   f.hi = *reinterpret_cast<const s16x8*>(p);
-  if ((PREC & 1) == 0 && PREC != 6) f.lo = *reinterpret_cast<const s16x8*>(p + 1024);
+  if (prec_reads_w_lo(PREC)) f.lo = *reinterpret_cast<const s16x8*>(p + 1024);
 }
 // acc: main sum (high x high); cor: the correction products (x3 modes; scaled by 2^11 in the fp16 modes)
 template <int PREC>
 __device__ __forceinline__ void unit_mfma_r(const AFrag& a, const Frag& b, f32x4& acc, f32x4& cor) {
-  constexpr bool F16 = PREC >= 2, X3 = (PREC & 1) == 0;
+  constexpr bool F16 = prec_is_f16(PREC), X3 = prec_is_x3(PREC);
   acc = mfma16<F16>(a.hi, b.hi, acc);
   if (X3) {
     f32x4& c = prec_one_acc(PREC) ? acc : cor;  // (FSN_PREC_FP16X3U: everything into the main tile)
-    if (PREC != 6) c = mfma16<F16>(a.lo, b.hi, c);  // (fp16x2: the weights' low parts are dropped)
+    if (prec_reads_w_lo(PREC)) c = mfma16<F16>(a.lo, b.hi, c);  // (fp16x2: the weights' low parts are dropped)
     c = mfma16<F16>(a.hi, b.lo, c);
   }
 }
 
 template <int PREC>
 __device__ __forceinline__ void unit_mfma(const char* ubase, const Frag& b, f32x4& acc, f32x4& cor) {
-  constexpr bool F16 = PREC >= 2, X3 = (PREC & 1) == 0;
-#ifdef FSN_ABL_NOLDS  // timing experiment: operands from registers instead of the LDS ring
-  acc = mfma16<F16>(b.lo, b.hi, acc);
-  if (X3) {
-    acc = mfma16<F16>(b.hi, b.hi, acc);
-    acc = mfma16<F16>(b.lo, b.lo, acc);
-  }
-  return;
-#endif
-#ifdef FSN_ABL_LDSDUMMY  // timing experiment: LDS reads are issued but no MFMA depends on them
-  {
-    // FSN_ABL_LDSDUMMY = 1: the kernel's two 16-byte reads; 2: one 16-byte read; 3: two 8-byte reads; 4: four 8-byte
-#if FSN_ABL_LDSDUMMY == 1
-    const s16x8 dh = *reinterpret_cast<const s16x8*>(ubase);
-    const s16x8 dl = *reinterpret_cast<const s16x8*>(ubase + 1024);
-#elif FSN_ABL_LDSDUMMY == 2
-    const s16x8 dh = *reinterpret_cast<const s16x8*>(ubase);
-    const int dl = 0;
-#elif FSN_ABL_LDSDUMMY == 3
-    typedef __attribute__((ext_vector_type(2))) int i32x2;
-    const i32x2 dh = *reinterpret_cast<const i32x2*>(ubase - (FSN_TIDX & 63) * 8);
-    const i32x2 dl = *reinterpret_cast<const i32x2*>(ubase - (FSN_TIDX & 63) * 8 + 1024);
-#else
-    typedef __attribute__((ext_vector_type(2))) int i32x2;
-    const i32x2 dh = *reinterpret_cast<const i32x2*>(ubase - (FSN_TIDX & 63) * 8);
-    const i32x2 dl = *reinterpret_cast<const i32x2*>(ubase - (FSN_TIDX & 63) * 8 + 512);
-    const i32x2 d2 = *reinterpret_cast<const i32x2*>(ubase - (FSN_TIDX & 63) * 8 + 1024);
-    const i32x2 d3 = *reinterpret_cast<const i32x2*>(ubase - (FSN_TIDX & 63) * 8 + 1536);
-    asm volatile("" ::"v"(d2), "v"(d3));
-#endif
-    acc = mfma16<F16>(b.lo, b.hi, acc);
-    if (X3) {
-      acc = mfma16<F16>(b.hi, b.hi, acc);
-      acc = mfma16<F16>(b.lo, b.lo, acc);
-    }
-    asm volatile("" ::"v"(dh), "v"(dl));
-    return;
-  }
-#endif
+  constexpr bool F16 = prec_is_f16(PREC), X3 = prec_is_x3(PREC);
   const s16x8 ah = *reinterpret_cast<const s16x8*>(ubase);
   acc = mfma16<F16>(ah, b.hi, acc);
   if (X3) {
     f32x4& c = prec_one_acc(PREC) ? acc : cor;
-    if (PREC != 6) {
+    if (prec_reads_w_lo(PREC)) {
       const s16x8 al = *reinterpret_cast<const s16x8*>(ubase + 1024);
       c = mfma16<F16>(al, b.hi, c);
     }
@@ -676,35 +599,15 @@ template <int PREC, int NP_OUT, int EPI, int NOUT, class HK>
 __device__ __forceinline__ void pair_epilogue(const NetDev& net, int tp, const f32x4& acc0, const f32x4& acc1,
                                               const f32x4& cor0, const f32x4& cor1, Frag (&out)[NOUT], Heads& heads,
                                               int g, HK& hk) {
-  constexpr bool F16 = PREC >= 2, X3 = (PREC & 1) == 0, LS = prec_lo_scaled_k(PREC);
-#if defined(FSN_PRIO) && FSN_PRIO == 1
-    __builtin_amdgcn_s_setprio(0);
-#elif defined(FSN_PRIO) && FSN_PRIO == 2
-    __builtin_amdgcn_s_setprio(1);
-#elif defined(FSN_PRIO) && FSN_PRIO == 4
-    __builtin_amdgcn_s_setprio(2);
-#endif
+  constexpr bool F16 = prec_is_f16(PREC), X3 = prec_is_x3(PREC), LS = prec_lo_scaled(PREC);
     float v[8];
     if constexpr (X3 && !prec_one_acc(PREC)) {
       // value = main + 2^-11 x corrections (fp16 modes: exact power-of-two unscaling inside the fma); bf16: scale 1
       constexpr float IK = F16 ? 1.0f / kLoScaleF16 : 1.0f;
-#ifndef FSN_EPI_PK_FMA
       // eight v_fma_f32: measured 0.6 % faster on the frame than four v_pk_fma_f32 (418.7 -> 416.2 ms), as
       // MI355X_MICROARCH.md prices packed fp32 VALU beside MFMAs
 #pragma unroll
       for (int j = 0; j < 4; ++j) { v[j] = __builtin_fmaf(cor0[j], IK, acc0[j]); v[4 + j] = __builtin_fmaf(cor1[j], IK, acc1[j]); }
-#else
-      typedef __attribute__((ext_vector_type(2))) float f32x2;
-      const f32x2 ik2 = {IK, IK};
-#pragma unroll
-      for (int j = 0; j < 4; j += 2) {  // v_pk_fma_f32: two values per instruction
-        const f32x2 a0 = {acc0[j], acc0[j + 1]}, c0 = {cor0[j], cor0[j + 1]};
-        const f32x2 a1 = {acc1[j], acc1[j + 1]}, c1 = {cor1[j], cor1[j + 1]};
-        const f32x2 r0 = __builtin_elementwise_fma(c0, ik2, a0), r1 = __builtin_elementwise_fma(c1, ik2, a1);
-        v[j] = r0[0]; v[j + 1] = r0[1];
-        v[4 + j] = r1[0]; v[4 + j + 1] = r1[1];
-      }
-#endif
     } else {
 #pragma unroll
       for (int j = 0; j < 4; ++j) { v[j] = acc0[j]; v[4 + j] = acc1[j]; }
@@ -758,10 +661,6 @@ __device__ __forceinline__ void pair_epilogue(const NetDev& net, int tp, const f
     if (EPI == EPI_RGB) asm volatile("" : "+v"(heads.rgb[0]), "+v"(heads.rgb[1]), "+v"(heads.rgb[2]));
     if (EPI == EPI_RELU_CVT || EPI == EPI_CVT || EPI == EPI_LAST_FULL) {
       Frag& o = out[tp < NOUT ? tp : 0];
-#ifdef FSN_ABL_NOCVT  // timing experiment: skip the fp32 -> hi/lo split
-      asm volatile("" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]));
-      o = out[0];
-#else
       // The asm form of the split must not read MFMA results directly (hipcc pads the XDL-write -> VALU-read wait
       // states only for instructions it knows; found as 1e-3 gradient errors in the backward chain).  In the x3
       // modes v[] comes out of the merge fma above, a compiler-visible VALU instruction; the single-pass modes'
@@ -771,7 +670,6 @@ __device__ __forceinline__ void pair_epilogue(const NetDev& net, int tp, const f
       if constexpr (prec_one_acc(PREC) && (EPI == EPI_CVT || EPI == EPI_NONE)) split_store_cpp<F16, X3, LS>(v, o);
       else split_store<F16, X3, LS>(v, o);
       if constexpr (F16) range_track<EPI == EPI_CVT || EPI == EPI_NONE>(heads.rs.fmax, o.hi);
-#endif
       if (X3) asm volatile("" : "+v"(o.hi), "+v"(o.lo));
       else asm volatile("" : "+v"(o.hi));
     }
@@ -889,7 +787,7 @@ __device__ __forceinline__ void kloop_block(WStream& st, const Frag (&act)[NACT]
   constexpr int NU = 2 * (KS_ACT + KS_ENC);
   uint32_t a[4], mv[3], keep;
   uint64_t gb[3];
-  const uint32_t voff = ((FSN_TIDX >> 6) ^ FSN_LOADER_XOR) * (kGldsPerWave * 1024) + (FSN_TIDX & 63) * 16;
+  const uint32_t voff = ((threadIdx.x >> 6) ^ kLoaderXor) * (kGldsPerWave * 1024) + (threadIdx.x & 63) * 16;
   if constexpr (MODE == 2) {
     FSN_KLOOP_CASE(X3S, 16, 0)
     FSN_KLOOP_CASE(X3S, 20, 0)
@@ -936,7 +834,7 @@ template <int PREC, int NP_OUT, int KS_ACT, int KS_ENC, int EPI, int NACT, int N
 __device__ __forceinline__ void gemm_layer(WStream& st, const NetDev& net, int aux_bias, const Frag (&act)[NACT],
                                            const Frag (&enc)[NENC], Frag (&out)[NOUT], Heads& heads, ARing& ring,
                                            int g, HK& hk) {
-  constexpr bool F16 = PREC >= 2, X3 = (PREC & 1) == 0;
+  constexpr bool F16 = prec_is_f16(PREC), X3 = prec_is_x3(PREC);
   // range guard (fp16 modes): layers whose epilogue forms 16-bit parts close their per-layer maximum; the split modes'
   // forward passes (bias-initialised accumulators; the backward chain starts from zero) also check the layer's scale
   constexpr bool kConverts = EPI == EPI_RELU_CVT || EPI == EPI_CVT || EPI == EPI_LAST_FULL;
@@ -976,14 +874,11 @@ __device__ __forceinline__ void gemm_layer(WStream& st, const NetDev& net, int a
       constexpr int NS = kNS;  // A register sets
       constexpr int R0 = (tp * NU) % NS, OFF = (tp * NU) % UPP, PAR = tp & 1;
       hk.pre(tp);
-#if defined(FSN_PRIO) && FSN_PRIO == 4
-      if (__builtin_amdgcn_readfirstlane(FSN_TIDX) & 256) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
-#endif
 #ifdef FSN_STAMP
       const uint64_t ts0 = __builtin_amdgcn_s_memtime();
 #endif
       const uint32_t abn = bias_lds + 128u * (tp + 1 < NP_OUT ? tp + 1 : tp);  // (last pair: a harmless reload)
-      kloop_block<F16, PREC == 6 ? 1 : (prec_one_acc(PREC) ? 2 : 0), KS_ACT, KS_ENC, OFF, PAR>(st, act, enc, acc, abn, ring.cur[R0], ring.cur[(R0 + 1) % NS],
+      kloop_block<F16, !prec_reads_w_lo(PREC) ? 1 : (prec_one_acc(PREC) ? 2 : 0), KS_ACT, KS_ENC, OFF, PAR>(st, act, enc, acc, abn, ring.cur[R0], ring.cur[(R0 + 1) % NS],
                                                             ring.cur[(R0 + 2) % NS]);
 #ifdef FSN_STAMP
       const uint64_t ts1 = __builtin_amdgcn_s_memtime();
@@ -1028,13 +923,6 @@ __device__ __forceinline__ void gemm_layer(WStream& st, const NetDev& net, int a
       acc1 = *reinterpret_cast<const f32x4*>(bias + 32 * tp + 16 + 4 * g);
     }
     hk.pre(tp);
-#if defined(FSN_PRIO) && FSN_PRIO == 1
-    __builtin_amdgcn_s_setprio(1);
-#elif defined(FSN_PRIO) && FSN_PRIO == 2
-    __builtin_amdgcn_s_setprio(0);
-#elif defined(FSN_PRIO) && FSN_PRIO == 4
-    if (__builtin_amdgcn_readfirstlane(FSN_TIDX) & 256) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
-#endif
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const Frag& b = ks < KS_ACT ? act[ks < KS_ACT ? ks : 0] : enc[ks >= KS_ACT ? ks - KS_ACT : 0];
@@ -1110,6 +998,12 @@ __device__ __forceinline__ void gemm_layer(WStream& st, const NetDev& net, int a
 }
 
 // ---------------------------------------------------------------- two sample groups per wave (single-pass modes)
+// sample groups of 16 per wave: 2 in the single-pass modes of 256-wide networks (gemm_layer2 below), so that a
+// workgroup tile is 256 samples and every weight phase - one barrier, one round of LDS-DMA, 16 KiB from L2 - is used
+// by twice as many samples
+template <int NT, int PREC>
+constexpr int groups_per_wave() { return (!prec_is_x3(PREC) && NT == 8) ? 2 : 1; }
+
 // 32 samples per wave as two 16-sample groups that share every A operand: one ds_read_b128 feeds two MFMAs, and a
 // 16-KiB weight phase (one barrier, one round of LDS-DMA) covers 256 samples of the workgroup instead of 128.  The
 // single-pass modes carry no low parts, so both groups' activations (2 x 64 registers in, 2 x 64 out) still fit two
@@ -1119,8 +1013,8 @@ __device__ __forceinline__ void gemm_layer2(WStream& st, const NetDev& net, int 
                                             const Frag (&act1)[NACT], const Frag (&enc0)[NENC], const Frag (&enc1)[NENC],
                                             Frag (&out0)[NOUT], Frag (&out1)[NOUT], Heads& heads0, Heads& heads1,
                                             ARing& ring, int g) {
-  constexpr bool F16 = PREC >= 2;
-  static_assert((PREC & 1) == 1, "two groups per wave: single-pass modes only");
+  constexpr bool F16 = prec_is_f16(PREC);
+  static_assert(!prec_is_x3(PREC), "two groups per wave: single-pass modes only");
   constexpr int UPP = 16, UB = 1024;
   constexpr int KS = KS_ACT + KS_ENC;
   constexpr int TOTAL = 2 * NP_OUT * KS;
@@ -1170,8 +1064,8 @@ template <int NT, int PREC, bool FULL, class Src>
 __device__ __forceinline__ void mlp_tile2(WStream& st, const NetDev& net, const Src& src0, const Src& src1, ARing& ring,
                                           float (&sigma)[2], float (&rgb)[2][3]) {
   constexpr int NA = NT;
-  constexpr bool F16 = PREC >= 2;
-  const int g = (FSN_TIDX >> 4) & 3;
+  constexpr bool F16 = prec_is_f16(PREC);
+  const int g = (threadIdx.x >> 4) & 3;
   constexpr int D = 32 * NT;
   const int L = net.n_layers;
   const float* misc = net.aux + (L + 5) * D;
@@ -1246,8 +1140,8 @@ __device__ __forceinline__ void mlp_tile2(WStream& st, const NetDev& net, const 
 // A-operand pair primed for the very first GEMM of a kernel (after WStream::init opened phase 0)
 template <int PREC, int NT = 0>
 __device__ __forceinline__ void prime_ring(const WStream& st, ARing& ring) {
-  constexpr int UB = (PREC & 1) == 0 ? 2048 : 1024;
-  if (kKloopAsm && (PREC & 1) == 0 && NT == 8) {  // hand-scheduled x3 / x2 path: units 0 and 1 of the first GEMM
+  constexpr int UB = prec_is_x3(PREC) ? 2048 : 1024;
+  if (kKloopAsm && prec_is_x3(PREC) && NT == 8) {  // hand-scheduled x3 / x2 path: units 0 and 1 of the first GEMM
 #pragma unroll
     for (int i = 0; i < kKD; ++i) load_afrag<PREC>(st.n_base + i * UB, ring.cur[i]);
 #pragma unroll
@@ -1255,16 +1149,16 @@ __device__ __forceinline__ void prime_ring(const WStream& st, ARing& ring) {
     return;
   }
 #ifdef FSN_X3_PF1
-  if ((PREC & 1) == 0) {
+  if (prec_is_x3(PREC)) {
     load_afrag<PREC>(st.n_base, ring.cur[0]);
     return;
   }
 #else
-  if ((PREC & 1) == 0) return;  // the x3 modes read their operands in place
+  if (prec_is_x3(PREC)) return;  // the x3 modes read their operands in place
 #endif
   load_afrag<PREC>(st.n_base, ring.cur[0]);
   load_afrag<PREC>(st.n_base + UB, ring.cur[1]);
-  if ((PREC & 1) != 0) ring.cur[0].lo = ring.cur[1].lo = ring.cur[0].hi;  // single pass: no low parts
+  if (!prec_is_x3(PREC)) ring.cur[0].lo = ring.cur[1].lo = ring.cur[0].hi;  // single pass: no low parts
 }
 
 // ---------------------------------------------------------------- whole network, one tile
@@ -1286,8 +1180,8 @@ template <int NT, int PREC, bool FULL, class Src, class SV>
 __device__ __forceinline__ void mlp_tile(WStream& st, const NetDev& net, const Src& src, ARing& ring, float& sigma,
                                          float (&rgb)[3], const SV& sv) {
   constexpr int NA = NT;  // k-steps of 32 across the hidden width
-  constexpr bool F16 = PREC >= 2, X3 = (PREC & 1) == 0, LS = prec_lo_scaled_k(PREC);
-  const int g = (FSN_TIDX >> 4) & 3;
+  constexpr bool F16 = prec_is_f16(PREC), X3 = prec_is_x3(PREC), LS = prec_lo_scaled(PREC);
+  const int g = (threadIdx.x >> 4) & 3;
   constexpr int D = 32 * NT;
   const int L = net.n_layers;
   const float* misc = net.aux + (L + 5) * D;
@@ -1379,12 +1273,12 @@ __device__ __forceinline__ void load_net(const NetParams& p, const float* __rest
                                          const float* __restrict__ dir_mask_g, float* lds, NetDev& net) {
   const f32x4* src = reinterpret_cast<const f32x4*>(p.blob + p.aux_off);
   f32x4* dst = reinterpret_cast<f32x4*>(lds);
-  for (int i = FSN_TIDX; i < p.aux_floats / 4; i += blockDim.x) dst[i] = src[i];
+  for (int i = threadIdx.x; i < p.aux_floats / 4; i += blockDim.x) dst[i] = src[i];
   float* pm = lds + p.aux_floats;
   float* dm = pm + 64;
   const int npe = 3 * (1 + 2 * p.n_freqs_pos), nde = 3 * (1 + 2 * p.n_freqs_dir);
-  for (int i = FSN_TIDX; i < 64; i += blockDim.x) pm[i] = (pos_mask_g && i < npe) ? pos_mask_g[i] : 1.0f;
-  for (int i = FSN_TIDX; i < 32; i += blockDim.x) dm[i] = (dir_mask_g && i < nde) ? dir_mask_g[i] : 1.0f;
+  for (int i = threadIdx.x; i < 64; i += blockDim.x) pm[i] = (pos_mask_g && i < npe) ? pos_mask_g[i] : 1.0f;
+  for (int i = threadIdx.x; i < 32; i += blockDim.x) dm[i] = (dir_mask_g && i < nde) ? dir_mask_g[i] : 1.0f;
   net.aux = lds;
   net.pos_mask = pm;
   net.dir_mask = dm;

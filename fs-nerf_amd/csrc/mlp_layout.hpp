@@ -33,8 +33,13 @@ constexpr int kKsPos = 2;  // k-steps (of 32) reserved for the positional encodi
 constexpr int kKsDir = 1;  // k-steps reserved for the direction encoding: 32 slots
 constexpr int kMaxLayers = 16;
 
-FSN_HD bool prec_is_x3(int prec) { return (prec & 1) == 0; }
-FSN_HD bool prec_is_f16(int prec) { return prec >= 2; }
+// Properties of an arithmetic mode (FSN_PREC_*), for host and device, run time and compile time.  The numbering
+// carries two of them: the odd modes are the single-pass ones, and every fp16 mode is numbered from FSN_PREC_FP16X3 up.
+constexpr int kPrecSinglePassBit = 1;
+FSN_HD constexpr bool prec_is_x3(int prec) { return (prec & kPrecSinglePassBit) == 0; }  // high / low parts (x3 and x2)
+FSN_HD constexpr bool prec_is_f16(int prec) { return prec >= FSN_PREC_FP16X3; }
+// the weights' low parts are read (FSN_PREC_FP16X2 streams the x3 blob and drops them)
+FSN_HD constexpr bool prec_reads_w_lo(int prec) { return prec_is_x3(prec) && prec != FSN_PREC_FP16X2; }
 // Low parts of the split fp16 modes (weights in the blob, activations in registers and in the training workspace) are
 // stored SCALED: low = fp16((v - high) * 2^11).  The unscaled remainder of a value below ~0.1 is an fp16 subnormal
 // (fixed 2^-24 resolution: an activation of 1e-3 kept ~15 bits, a sigma error of 4e-4); scaled it is a normal fp16
@@ -46,7 +51,7 @@ constexpr float kLoScaleF16 = 2048.0f;
 // per-layer power-of-two scales folded into the packed weights (mlp_pack.hpp, PackArgs::sc_*) keep every layer's
 // activations at 2^4 .. 2^10, where an activation's unscaled low part is a normal fp16 number or negligible against the
 // layer's scale.
-FSN_HD bool prec_lo_scaled(int prec) { return prec == FSN_PREC_FP16X3 || prec == FSN_PREC_FP16X2; }
+FSN_HD constexpr bool prec_lo_scaled(int prec) { return prec == FSN_PREC_FP16X3 || prec == FSN_PREC_FP16X2; }
 FSN_HD float lo_scale(int prec) { return prec_lo_scaled(prec) ? kLoScaleF16 : 1.0f; }
 FSN_HD int unit_bytes(int prec) { return prec_is_x3(prec) ? 2048 : 1024; }
 FSN_HD int units_per_phase(int prec) { return kPhaseBytes / unit_bytes(prec); }

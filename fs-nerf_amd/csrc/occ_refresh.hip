@@ -37,10 +37,6 @@ struct DrawSrc {
   __device__ __forceinline__ void dir(float& x, float& y, float& z) const { x = 0.f; y = 0.f; z = 1.f; }  // (density only: unused)
 };
 
-// sample groups of 16 per wave and tile, as k_mlp_fwd: two in the single-pass modes of 256-wide networks
-template <int NT, int PREC>
-constexpr int groups_per_wave() { return ((PREC & 1) == 1 && NT == 8) ? 2 : 1; }
-
 // Persistent workgroups over the concatenated draws of all levels (draw d = level d / n_draws, index d % n_draws), tile
 // and lane layout of k_mlp_fwd: wave w owns draws tile0 + 16 NG w + l, l < 16 NG.  Lane l draws that one (cell and
 // point), stages it in the wave's own LDS slots - the tile loop reads a point more than once (skip layers), and six
@@ -147,12 +143,7 @@ extern "C" int fsn_occgrid_refresh(const fsn_mlp_desc* desc, int prec, const voi
   const int cus = fsn_device_cus();
   if (cus <= 0) return FSN_E_HIP;
   OccRefreshArgs a{};
-  a.net.blob = static_cast<const char*>(blob);
-  a.net.aux_off = (int32_t)G.aux_off; a.net.aux_floats = G.aux_floats; a.net.stream_off = (int32_t)G.stream_off;
-  a.net.nph_density = G.nph_density; a.net.nph_full = G.nph_full;
-  a.net.n_layers = desc->n_layers; a.net.skip_mask = desc->skip_mask;
-  a.net.n_freqs_pos = desc->n_freqs_pos; a.net.n_freqs_dir = desc->n_freqs_dir;
-  a.net.status = status;
+  a.net = net_params(*desc, G, blob, status);
   a.pos_mask = pos_mask;
   a.bits = bits; a.prefix = from_occupied ? prefix_scratch : nullptr; a.pending = pending;
   for (int l = 0; l < levels; ++l) {
@@ -169,7 +160,6 @@ extern "C" int fsn_occgrid_refresh(const fsn_mlp_desc* desc, int prec, const voi
     rc = launch_occ_word_prefix(bits, (int)(res3 >> 5), levels, prefix_scratch, s);
     if (rc != FSN_OK) return rc;
   }
-  const bool wide = desc->d_hidden == 256;
-  if (prec == FSN_PREC_FP16) return wide ? launch_occ_refresh<8, 3>(a, cus, s) : launch_occ_refresh<4, 3>(a, cus, s);
-  return wide ? launch_occ_refresh<8, 1>(a, cus, s) : launch_occ_refresh<4, 1>(a, cus, s);
+  return dispatch_net(PrecModes<FSN_PREC_BF16, FSN_PREC_FP16>{}, desc->d_hidden, prec,
+                      [&](auto NT, auto PREC) { return launch_occ_refresh<NT(), PREC()>(a, cus, s); });
 }

@@ -7,20 +7,8 @@
 // group to ray group; per-ray scans/reductions are done by one wavefront per ray (ray_dev.hpp).
 // HBM traffic is the rays in and the requested outputs out.
 #include "common.hpp"
-// Wave priorities (s_setprio around the k-loop / the pair epilogue, FSN_PRIO) are off: round 1's "+1.8 %" was measured
-// with a lane-divergent condition, which compiles to both s_setprio instructions executed by every wave; with the
-// wave-uniform form the asymmetric priorities cost 2.3 % (A/B on MI355X, tools/ab_fused.py).
 // hand-scheduled k-loop of the x3 modes (kloop_gen.hpp): A operands two units ahead, counted waits
 #define FSN_KLOOP_ASM
-// waves 4..7 one weight phase behind waves 0..3 (mlp_dev.hpp, kLag): six ring slots
-// (measured: 510 ms against 432 ms per frame without it - the workgroup barrier of every phase opening re-joins the
-// two groups, so the wave that is not in its epilogue only waits at the next barrier; kept as an experiment switch)
-#ifndef FSN_LAG
-#define FSN_LAG 0
-#endif
-#if FSN_LAG
-#define FSN_NSLOT 6
-#endif
 #define FSN_BF16X3_ONEACC 1  // inference: bf16x3 accumulates its three products in one tile (mlp_dev.hpp)
 #include "mlp_dev.hpp"
 #include "ray_dev.hpp"
@@ -30,22 +18,10 @@ namespace fsn {
 FSN_DEBUG_DEFINE_RECORD(g_dbg_render)
 #define FSN_DEBUG_RECORD g_dbg_render
 
-#ifdef FSN_RENDER_BIG  // experiment: groups of up to 8 rays (158.8 KB of LDS)
-constexpr int kMaxGroupSamples = 1536;  // G * (S + n_imp) <= this
-constexpr int kMaxGroupCoarse = 768;    // G * S <= this
-constexpr int kMaxG = 8;
-#else
 constexpr int kMaxGroupSamples = 768;  // G * (S + n_imp) <= this
 constexpr int kMaxGroupCoarse = 768;   // G * S <= this
 constexpr int kMaxG = 4;
-#endif
 constexpr int kMaxRaySamples = 384;    // S + n_imp <= this
-// sample groups of 16 per wave: 2 in the single-pass modes of 256-wide networks (mlp_dev.hpp gemm_layer2), so that a
-// workgroup tile is 256 samples and every weight phase - one barrier, one round of LDS-DMA, 16 KiB from L2 - is used
-// by twice as many samples
-template <int NT, int PREC>
-constexpr int groups_per_wave() { return ((PREC & 1) == 1 && NT == 8) ? 2 : 1; }
-
 struct RenderKArgs {
   NetParams netC, netF;
   fsn_render_args a;
@@ -151,8 +127,7 @@ __global__ __launch_bounds__(kThreads) void k_render_fused(RenderKArgs k) {
   // are then RECOMPUTED per group (a few VALU instructions) instead of being hoisted to the kernel's entry, spilled
   // around the MFMA passes and reloaded per tile - each reload a VMEM load whose compiler-inserted vmcnt(0) also drains
   // the hand-counted LDS-DMA prefetch.  57 -> 20 spilled VGPRs, 144 -> 68 bytes of scratch per lane; fp16x3 frame
-  // unchanged (427.2 / 427.5 ms), bf16 frame 137.5 -> 134.8 ms (FSN_NO_LAUNDER_TID: the plain form).
-#ifndef FSN_NO_LAUNDER_TID
+  // unchanged (427.2 / 427.5 ms), bf16 frame 137.5 -> 134.8 ms.
   int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
 #define FSN_RELAUNDER()                                              \
   do {                                                               \
@@ -160,10 +135,6 @@ __global__ __launch_bounds__(kThreads) void k_render_fused(RenderKArgs k) {
     asm volatile("" : "+v"(t_));                                     \
     tid = t_; wave = __builtin_amdgcn_readfirstlane(t_ >> 6); lane = t_ & 63; \
   } while (0)
-#else
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-#define FSN_RELAUNDER() do {} while (0)
-#endif
   constexpr int NG = groups_per_wave<NT, PREC>(), TILE = 128 * NG;
   ARing ring;
   prime_ring<PREC, NT>(st, ring);
@@ -324,11 +295,7 @@ __global__ __launch_bounds__(kThreads) void k_render_fused(RenderKArgs k) {
         const int g = small_div(e, GRP_SO + 1), i = e - g * (GRP_SO + 1);
         // (streaming: written once here, read once below, 494 MB per 800x800 frame - kept out of the way of the
         // weight streams the XCD's L2 is there for)
-#ifdef FSN_EDGES_PLAIN  // experiment: plain (L2 write-back) hand-over stores / loads
-        if (r0 + g < GRP_R) a.edges_out[(r0 + g) * (GRP_SO + 1) + i] = FSN_AT(S_.edgesF, e);
-#else
         if (r0 + g < GRP_R) __builtin_nontemporal_store(FSN_AT(S_.edgesF, e), a.edges_out + (r0 + g) * (GRP_SO + 1) + i);
-#endif
       }
       lds_barrier();
     }
@@ -350,11 +317,7 @@ __global__ __launch_bounds__(kThreads) void k_render_fused(RenderKArgs k) {
       load_rays(r0);
       for (int e = tid; e < GRP_G * (GRP_SO + 1); e += kThreads) {
         const int g = small_div(e, GRP_SO + 1), i = e - g * (GRP_SO + 1);
-#ifdef FSN_EDGES_PLAIN
-        FSN_AT(S_.edgesF, e) = a.edges_out[min(r0 + g, GRP_R - 1) * (GRP_SO + 1) + i];
-#else
         FSN_AT(S_.edgesF, e) = __builtin_nontemporal_load(a.edges_out + min(r0 + g, GRP_R - 1) * (GRP_SO + 1) + i);
-#endif
       }
       lds_barrier();
       fine_stage(r0, FSN_SPAN(S_.edgesF, 0, GRP_G * (GRP_SO + 1)), false);
@@ -434,12 +397,10 @@ static int launch_render(RenderKArgs k, int cus, hipStream_t s) {
   // Rays per workgroup group: the per-ray stages (weights, resampling, integration) run one wave per ray, so a group of
   // two rays (one 128-sample tile of a 64-sample coarse pass) leaves six waves idle in them; the x3 modes take two
   // tiles' worth (four rays at 64+128: 424.3 -> 421.7 ms per frame), the two-group single-pass modes already do.
-#ifndef FSN_RENDER_G1
-#define FSN_RENDER_G1 2
-#endif
-  constexpr int NG = groups_per_wave<NT, PREC>(), TILE = 128 * NG, CAP = NG == 1 ? 384 * FSN_RENDER_G1 : kMaxGroupSamples;
+  constexpr int kTilesG1 = 2;  // coarse tiles' worth of rays per group in the one-group (x3) modes
+  constexpr int NG = groups_per_wave<NT, PREC>(), TILE = 128 * NG, CAP = NG == 1 ? 384 * kTilesG1 : kMaxGroupSamples;
   const int So = k.a.S + k.a.n_imp;
-  int g = (NG == 1 ? FSN_RENDER_G1 : 1) * TILE / k.a.S;
+  int g = (NG == 1 ? kTilesG1 : 1) * TILE / k.a.S;
   if (g < 1) g = 1;
   if (g > CAP / So) g = CAP / So;
   if (g > kMaxG) g = kMaxG;
@@ -456,17 +417,6 @@ static int launch_render(RenderKArgs k, int cus, hipStream_t s) {
   else k_render_fused<NT, PREC, false><<<grid, kThreads, 0, s>>>(k);
   FSN_LAUNCH_CHECK("k_render_fused");
   return FSN_OK;
-}
-
-static NetParams net_params(const fsn_mlp_desc& d, const NetGeom& G, const void* blob, uint32_t* status) {
-  NetParams p;
-  p.blob = static_cast<const char*>(blob);
-  p.aux_off = (int32_t)G.aux_off; p.aux_floats = G.aux_floats; p.stream_off = (int32_t)G.stream_off;
-  p.nph_density = G.nph_density; p.nph_full = G.nph_full;
-  p.n_layers = d.n_layers; p.skip_mask = d.skip_mask;
-  p.n_freqs_pos = d.n_freqs_pos; p.n_freqs_dir = d.n_freqs_dir;
-  p.status = status;
-  return p;
 }
 
 }  // namespace fsn
@@ -532,19 +482,7 @@ extern "C" int fsn_render_rays_fused(const fsn_mlp_desc* desc, int prec, const v
   const int cus = fsn_device_cus();
   if (cus <= 0) return FSN_E_HIP;
   hipStream_t s = as_stream(stream);
-  if (prec == FSN_PREC_FP16X2) return desc->d_hidden == 256 ? launch_render<8, 6>(k, cus, s) : launch_render<4, 6>(k, cus, s);
-  if (prec == FSN_PREC_FP16X3U) return desc->d_hidden == 256 ? launch_render<8, 4>(k, cus, s) : launch_render<4, 4>(k, cus, s);
-  const int key = (desc->d_hidden == 256 ? 4 : 0) + prec;
-  switch (key) {
-    case 0: return launch_render<4, 0>(k, cus, s);
-    case 1: return launch_render<4, 1>(k, cus, s);
-    case 2: return launch_render<4, 2>(k, cus, s);
-    case 3: return launch_render<4, 3>(k, cus, s);
-    case 4: return launch_render<8, 0>(k, cus, s);
-    case 5: return launch_render<8, 1>(k, cus, s);
-    case 6: return launch_render<8, 2>(k, cus, s);
-    default: return launch_render<8, 3>(k, cus, s);
-  }
+  return dispatch_net(PrecInference{}, desc->d_hidden, prec, [&](auto NT, auto PREC) { return launch_render<NT(), PREC()>(k, cus, s); });
 }
 
 extern "C" int fsn_bench_bare_stream(const fsn_mlp_desc* desc, int prec, const void* blob, int layers, uint64_t* clock_out,
@@ -560,11 +498,12 @@ extern "C" int fsn_bench_bare_stream(const fsn_mlp_desc* desc, int prec, const v
   if (cus <= 0) return FSN_E_HIP;
   const char* sp = static_cast<const char*>(blob) + G.stream_off;
   hipStream_t s = as_stream(stream);
-  if (prec == FSN_PREC_BF16X3) k_bare_stream<0><<<cus, kThreads, 0, s>>>(sp, (uint32_t)G.nph_density, layers, clock_out);
-  else if (prec == FSN_PREC_FP16X3) k_bare_stream<2><<<cus, kThreads, 0, s>>>(sp, (uint32_t)G.nph_density, layers, clock_out);
-  else k_bare_stream<4><<<cus, kThreads, 0, s>>>(sp, (uint32_t)G.nph_density, layers, clock_out);
-  FSN_LAUNCH_CHECK("k_bare_stream");
-  return cus;
+  const int launched = dispatch_prec(PrecModes<FSN_PREC_BF16X3, FSN_PREC_FP16X3, FSN_PREC_FP16X3U>{}, prec, [&](auto PREC) {
+    k_bare_stream<PREC()><<<cus, kThreads, 0, s>>>(sp, (uint32_t)G.nph_density, layers, clock_out);
+    FSN_LAUNCH_CHECK("k_bare_stream");
+    return FSN_OK;
+  });
+  return launched == FSN_OK ? cus : launched;
 }
 
 namespace fsn { int debug_report_occ(unsigned* host4); }  // render_occ.hip

@@ -62,10 +62,6 @@ struct OccLds {
   uint16_t slotk[kCap];
 };
 
-// sample groups per wave of a tile (mlp.hip / render.hip): two in the single-pass modes of 256-wide networks
-template <int NT, int PREC>
-constexpr int groups_per_wave() { return ((PREC & 1) == 1 && NT == 8) ? 2 : 1; }
-
 constexpr int kOccLdsBytes = kRingBytes + (kAuxCapFloats + 96) * 4 + (int)sizeof(OccLds);
 static_assert(kOccLdsBytes <= 160 * 1024, "LDS budget");
 
@@ -134,13 +130,11 @@ __global__ __launch_bounds__(kThreads) void k_render_occ(OccKArgs k) {
   };
 
   for (;;) {
-#ifndef FSN_NO_LAUNDER_TID
     {
       int t_ = threadIdx.x;
       asm volatile("" : "+v"(t_));
       tid = t_; wave = __builtin_amdgcn_readfirstlane(t_ >> 6); lane = t_ & 63;
     }
-#endif
     // ------------------------------------------------------------ build a batch
     if (tid == 0) { S.n_cand = 0; S.n_rays = 0; S.stop = 0; }
     __syncthreads();
@@ -441,14 +435,7 @@ extern "C" int fsn_render_rays_occgrid(const fsn_mlp_desc* desc, int prec, const
                 FSN_E_INVALID, "fsn_render_rays_occgrid: no rays and no valid camera");
   }
   FSN_REQUIRE(G.aux_floats <= kAuxCapFloats, FSN_E_UNSUPPORTED, "fsn_render_rays_occgrid: network too deep for LDS");
-  NetParams p;
-  p.blob = static_cast<const char*>(blob);
-  p.aux_off = (int32_t)G.aux_off; p.aux_floats = G.aux_floats; p.stream_off = (int32_t)G.stream_off;
-  p.nph_density = G.nph_density; p.nph_full = G.nph_full;
-  p.n_layers = desc->n_layers; p.skip_mask = desc->skip_mask;
-  p.n_freqs_pos = desc->n_freqs_pos; p.n_freqs_dir = desc->n_freqs_dir;
-  p.status = a.status;
-  k.net = p;
+  k.net = net_params(*desc, G, blob, a.status);
   k.a = a;
   k.cam_hw = (float)(a.cam_W * 0.5);
   k.cam_hh = (float)(a.cam_H * 0.5);
@@ -458,18 +445,8 @@ extern "C" int fsn_render_rays_occgrid(const fsn_mlp_desc* desc, int prec, const
   if (cus <= 0) return FSN_E_HIP;
   hipStream_t s = as_stream(stream);
   FSN_HIP(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned long long), s));
-  if (prec == FSN_PREC_FP16X3U) return desc->d_hidden == 256 ? launch_occ<8, 4>(k, cus, s) : launch_occ<4, 4>(k, cus, s);
-  const int key = (desc->d_hidden == 256 ? 4 : 0) + prec;
-  switch (key) {
-    case 0: return launch_occ<4, 0>(k, cus, s);
-    case 1: return launch_occ<4, 1>(k, cus, s);
-    case 2: return launch_occ<4, 2>(k, cus, s);
-    case 3: return launch_occ<4, 3>(k, cus, s);
-    case 4: return launch_occ<8, 0>(k, cus, s);
-    case 5: return launch_occ<8, 1>(k, cus, s);
-    case 6: return launch_occ<8, 2>(k, cus, s);
-    default: return launch_occ<8, 3>(k, cus, s);
-  }
+  return dispatch_net(PrecModes<FSN_PREC_BF16X3, FSN_PREC_BF16, FSN_PREC_FP16X3, FSN_PREC_FP16, FSN_PREC_FP16X3U>{}, desc->d_hidden,
+                      prec, [&](auto NT, auto PREC) { return launch_occ<NT(), PREC()>(k, cus, s); });
 }
 
 namespace fsn {

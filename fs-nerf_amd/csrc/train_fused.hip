@@ -120,11 +120,7 @@ static int make_fused_layout(const fsn_mlp_desc& d, int prec, int64_t n, FusedLa
 }
 
 // saved activations / gradients are written once and read by a later kernel: streaming stores
-#ifdef FSN_NO_NT
-#define FSN_STREAM_STORE(v, p) (*(p) = (v))
-#else
 #define FSN_STREAM_STORE(v, p) __builtin_nontemporal_store((v), (p))
-#endif
 
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
@@ -135,15 +131,9 @@ template <bool X3>
 __device__ __forceinline__ void store_pair_parts(uint32_t* p, int tp, const Frag& o) {
   typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
   const u32x4 h = __builtin_bit_cast(u32x4, o.hi), l = __builtin_bit_cast(u32x4, o.lo);
-#ifdef FSN_ABL_SAVE_NOLOADER  // timing experiment: the loader waves of the weight stream store nothing
-  if (((threadIdx.x >> 6) ^ FSN_LOADER_XOR) < (uint32_t)kLoaders) return;
-#endif
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int pr = 16 * tp + 8 * (i >> 1) + (i & 1);
-#ifdef FSN_ABL_SAVE_NONE  // timing experiment: no saved parts at all
-    continue;
-#endif
     if (X3) FSN_STREAM_STORE(((u32x2){h[i], l[i]}), reinterpret_cast<u32x2*>(p + pr * kTRow * 2));
     else FSN_STREAM_STORE(h[i], p + pr * kTRow);
   }
@@ -160,30 +150,13 @@ struct FwdSaver {
     static constexpr bool kLayerEnd = false;
     uint32_t* p;    // this lane's sample at pair-row 2g of the layer's tile
     uint8_t* mk;    // this lane's 8 mask bytes (one per output pair), or null (layer without activation)
-#ifdef FSN_MASK_WORDS  // experiment (measured: no change, 9.86 ms per step either way): four pairs' bytes gathered in a
-    // register, one 4-byte store per four pairs instead of four byte stores
-    uint32_t acc = 0u;
-    int last = 7;   // index of the layer's last output pair
-#endif
     __device__ __forceinline__ void pre(int) {}
     __device__ __forceinline__ void post(int tp, float (&v)[8]) {
-#ifdef FSN_ABL_SAVE_NOLOADER
-      if (((threadIdx.x >> 6) ^ FSN_LOADER_XOR) < (uint32_t)kLoaders) return;
-#endif
       if (mk) {
         uint32_t b = 0;
 #pragma unroll
         for (int j = 0; j < 8; ++j) b |= (v[j] > 0.f ? 1u : 0u) << j;
-#ifdef FSN_MASK_WORDS
-        acc |= b << (8 * (tp & 3));
-        if ((tp & 3) == 3 || tp == last) {
-          if ((tp & 3) == 3) *reinterpret_cast<uint32_t*>(mk + (tp & ~3)) = acc;
-          else for (int q = 0; q <= (tp & 3); ++q) mk[(tp & ~3) + q] = (uint8_t)(acc >> (8 * q));
-          acc = 0u;
-        }
-#else
         mk[tp] = (uint8_t)b;  // byte stores: accumulating the 64-bit word in registers tips the x3 modes into scratch
-#endif
       }
     }
     template <bool X3>
@@ -199,13 +172,8 @@ struct FwdSaver {
     return Hook{h0 + l * hstride, l < n_layers ? reinterpret_cast<uint8_t*>(mk0 + l * mstride) : nullptr};
   }
   __device__ __forceinline__ Hook branch() const {
-    Hook h{bo, reinterpret_cast<uint8_t*>(mk0 + n_layers * mstride)};
-#ifdef FSN_MASK_WORDS
-    h.last = branch_pairs - 1;
-#endif
-    return h;
+    return Hook{bo, reinterpret_cast<uint8_t*>(mk0 + n_layers * mstride)};
   }
-  int branch_pairs;  // output pairs of the branch layer (D / 64)
   __device__ __forceinline__ uint32_t* enc_pos(int) const { return pe; }
   __device__ __forceinline__ uint32_t* enc_dir(int) const { return de; }
   __device__ __forceinline__ void layer_done(int, Hook&) const {}
@@ -247,9 +215,7 @@ __global__ __launch_bounds__(kThreads) void k_train_fwd(TrainFwdArgs a) {
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     // (thread id laundered per tile: lane-derived addresses are recomputed, not hoisted and spilled - render.hip)
     int t_ = threadIdx.x;
-#ifndef FSN_NO_LAUNDER_TID
     asm volatile("" : "+v"(t_));
-#endif
     const int wave = t_ >> 6, lane = t_ & 63, g = lane >> 4;
     const int col = wave * 16 + (lane & 15);
     const int64_t s = tile * kTC + col;
@@ -274,7 +240,7 @@ __global__ __launch_bounds__(kThreads) void k_train_fwd(TrainFwdArgs a) {
     const TileSrcT src{in_lds + col * 6};
     FwdSaver sv;
     uint32_t* wsu = reinterpret_cast<uint32_t*>(a.ws);
-    constexpr int NPL = (PREC & 1) == 0 ? 2 : 1;
+    constexpr int NPL = prec_is_x3(PREC) ? 2 : 1;
     sv.h0 = wsu + a.off_h + tile * D * kTC + t_layout_off(NPL, D / 2, 2 * g, col);
     sv.hstride = a.h_stride;
     sv.bo = wsu + a.off_bo + tile * (D / 2) * kTC + t_layout_off(NPL, D / 4, 2 * g, col);
@@ -283,7 +249,6 @@ __global__ __launch_bounds__(kThreads) void k_train_fwd(TrainFwdArgs a) {
     sv.mk0 = reinterpret_cast<uint32_t*>(a.ws + a.off_mask) + ((tile * 4 + g) * kTC + col) * 2;
     sv.mstride = a.mask_stride;
     sv.n_layers = net.n_layers;
-    sv.branch_pairs = D / 64;
     float sigma, rgb[3] = {0.f, 0.f, 0.f};
     mlp_tile<NT, PREC, true>(st, net, src, ring, sigma, rgb, sv);
     if (lane < 16 && s < a.n) {
@@ -422,7 +387,7 @@ struct TrainBwdArgs {
 
 template <int NT, int PREC>
 __global__ __launch_bounds__(kThreads) void k_train_bwd(TrainBwdArgs a) {
-  constexpr bool F16 = PREC >= 2, X3 = (PREC & 1) == 0;
+  constexpr bool F16 = prec_is_f16(PREC), X3 = prec_is_x3(PREC);
   __shared__ __attribute__((aligned(1024))) char smem[kRingBytes + (kAuxCapFloats + 96 + 2 * (kMaxLayers + 2)) * 4];
   float* aux_lds = reinterpret_cast<float*>(smem + kRingBytes);
   float* bs_lds = aux_lds + kAuxCapFloats + 96;                                // per-stage factors
@@ -572,11 +537,6 @@ struct WgArgs {
 
 template <bool F16>
 __device__ __forceinline__ f32x16 mfma32(const s16x8& a, const s16x8& b, const f32x16& c) {
-#ifdef FSN_WGRAD_NOMFMA  // timing experiment: the memory side of k_wgrad by itself (one VALU op keeps the operands live)
-  f32x16 r = c;
-  r[0] += (float)a[0] * (float)b[0];
-  return r;
-#endif
   if (F16)
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
@@ -588,9 +548,6 @@ __device__ __forceinline__ f32x16 mfma32(const s16x8& a, const s16x8& b, const f
 // case it is the value rounds 1-2 stored).  Gradients are asserted to 2e-4 of a tensor's largest entry, far above that.
 template <bool F16X3>
 __device__ __forceinline__ u32x4 unscale_lo(u32x4 w) {
-#ifdef FSN_WGRAD_NOUNZIP
-  return w;
-#endif
   if constexpr (F16X3) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) asm("v_pk_mul_f16 %0, %0, %1" : "+v"(w[i]) : "s"(0x10001000u));  // 2^-11 | 2^-11
@@ -600,11 +557,6 @@ __device__ __forceinline__ u32x4 unscale_lo(u32x4 w) {
 
 // the two rows of a pair-row out of 8 packed dwords (8 samples): low halves -> row 2q, high halves -> row 2q+1
 __device__ __forceinline__ void unzip_rows(const u32x4& d0, const u32x4& d1, s16x8& even, s16x8& odd) {
-#ifdef FSN_WGRAD_NOUNZIP  // timing experiment: the k_wgrad stream without its VALU work (results are garbage)
-  even = __builtin_bit_cast(s16x8, d0);
-  odd = __builtin_bit_cast(s16x8, d1);
-  return;
-#endif
   u32x4 e, o;
   e[0] = __builtin_amdgcn_perm(d0[1], d0[0], 0x05040100u); o[0] = __builtin_amdgcn_perm(d0[1], d0[0], 0x07060302u);
   e[1] = __builtin_amdgcn_perm(d0[3], d0[2], 0x05040100u); o[1] = __builtin_amdgcn_perm(d0[3], d0[2], 0x07060302u);
@@ -691,7 +643,7 @@ __device__ __forceinline__ void wg_dma(uint32_t voff, const void* gbase, uint32_
 
 template <int NW, int MG, int BT, int PREC>
 __global__ __launch_bounds__(64 * NW, 2) void k_wgrad(WgArgs a) {  // (2 waves per SIMD: <= 256 registers)
-  constexpr bool F16 = PREC >= 2, X3 = (PREC & 1) == 0;
+  constexpr bool F16 = prec_is_f16(PREC), X3 = prec_is_x3(PREC);
   constexpr int NPL = X3 ? 2 : 1;  // parts per value: high (, low)
   constexpr int CG = NW / MG;
   constexpr int A_ROWS = 64 * MG;
@@ -843,19 +795,10 @@ __global__ __launch_bounds__(64 * NW, 2) void k_wgrad(WgArgs a) {  // (2 waves p
         for (int ti = 0; ti < 2; ++ti) {
           acc[ti][bt] = mfma32<F16>(af[ti].hi, bfr[bt].hi, acc[ti][bt]);
           if (X3) {
-            // experiment switches (profiles/EXPERIMENTS_r4.md 11): bit 0 drops (dPre low) x (input high), bit 1 drops
-            // (dPre high) x (input low); _BIG for the 256x256 jobs only, _ALL for every job
-#ifndef FSN_EXP_WGRAD_DROP_BIG
-#define FSN_EXP_WGRAD_DROP_BIG 0
-#endif
-#ifndef FSN_EXP_WGRAD_DROP_ALL
-#define FSN_EXP_WGRAD_DROP_ALL 0
-#endif
-            constexpr int kDrop = FSN_EXP_WGRAD_DROP_ALL | ((MG == 4 && BT == 4) ? FSN_EXP_WGRAD_DROP_BIG : 0);
-            if constexpr (!(kDrop & 1)) acc[ti][bt] = mfma32<F16>(af[ti].lo, bfr[bt].hi, acc[ti][bt]);
-#ifndef FSN_WGRAD_NOBLO  // experiment: drop the (dPre high) x (input low) product
-            if constexpr (!(kDrop & 2)) acc[ti][bt] = mfma32<F16>(F16 ? ahs[ti] : af[ti].hi, bfr[bt].lo, acc[ti][bt]);
-#endif
+            // (dPre low) x (input high), (dPre high) x (input low): dropping either fails the gradient bound
+            // (profiles/EXPERIMENTS_r4.md 11)
+            acc[ti][bt] = mfma32<F16>(af[ti].lo, bfr[bt].hi, acc[ti][bt]);
+            acc[ti][bt] = mfma32<F16>(F16 ? ahs[ti] : af[ti].hi, bfr[bt].lo, acc[ti][bt]);
           }
         }
     }
@@ -1038,7 +981,7 @@ struct HeadsArgs {
 
 template <int NT, int PREC>
 __global__ __launch_bounds__(kThreads) void k_heads_wgrad(HeadsArgs a) {
-  constexpr bool F16 = PREC >= 2, X3 = (PREC & 1) == 0;
+  constexpr bool F16 = prec_is_f16(PREC), X3 = prec_is_x3(PREC);
   constexpr int D = 32 * NT, PH = 2 * NT, PB = NT;     // pair-rows of H / Bo per wave
   constexpr int CH = 16 / PH, CB = 16 / PB;             // chunks the wave's lanes cover side by side
   constexpr int NCH = kTC / 16;
@@ -1187,17 +1130,6 @@ __global__ void k_bwd_rescale(float* __restrict__ bs, uint32_t* __restrict__ ama
 }
 
 // ------------------------------------------------------------------ host side
-static NetParams net_params(const fsn_mlp_desc& d, const NetGeom& G, const void* blob, uint32_t* status) {
-  NetParams p;
-  p.blob = static_cast<const char*>(blob);
-  p.aux_off = (int32_t)G.aux_off; p.aux_floats = G.aux_floats; p.stream_off = (int32_t)G.stream_off;
-  p.nph_density = G.nph_density; p.nph_full = G.nph_full;
-  p.n_layers = d.n_layers; p.skip_mask = d.skip_mask;
-  p.n_freqs_pos = d.n_freqs_pos; p.n_freqs_dir = d.n_freqs_dir;
-  p.status = status;
-  return p;
-}
-
 int64_t fused_train_workspace_floats(const fsn_mlp_desc& d, int prec, int64_t n) {
   FusedLayout F;
   const char* why;
@@ -1224,14 +1156,11 @@ static int launch_wgrad(int prec, const WgArgs& a, int njobs, hipStream_t s) {
   const int a_rows = a.job[0].a_rows;  // (jobs of one launch share their shape)
   FSN_REQUIRE(a_rows % (64 * MG) == 0, FSN_E_HIP, "internal: wgrad row blocks");
   dim3 grid((unsigned)a.nsplit, (unsigned)njobs, (unsigned)(a_rows / (64 * MG)));
-  switch (prec) {
-    case 0: k_wgrad<NW, MG, BT, 0><<<grid, 64 * NW, 0, s>>>(a); break;
-    case 1: k_wgrad<NW, MG, BT, 1><<<grid, 64 * NW, 0, s>>>(a); break;
-    case 2: k_wgrad<NW, MG, BT, 2><<<grid, 64 * NW, 0, s>>>(a); break;
-    default: k_wgrad<NW, MG, BT, 3><<<grid, 64 * NW, 0, s>>>(a); break;
-  }
-  FSN_LAUNCH_CHECK("k_wgrad");
-  return FSN_OK;
+  return dispatch_prec(PrecTraining{}, prec, [&](auto PREC) {
+    k_wgrad<NW, MG, BT, PREC()><<<grid, 64 * NW, 0, s>>>(a);
+    FSN_LAUNCH_CHECK("k_wgrad");
+    return FSN_OK;
+  });
 }
 
 int fused_train_fwd(const fsn_mlp_desc* d, int prec, const float* const* W, const float* const* b, const float* x,
@@ -1253,21 +1182,7 @@ int fused_train_fwd(const fsn_mlp_desc* d, int prec, const float* const* W, cons
                  F.mask, F.mask_stride, F.D, nullptr, nullptr, nullptr, nullptr, nullptr};
   if (rays) { a.rays_o = rays->rays_o; a.rays_d = rays->rays_d; a.t0 = rays->t0; a.t1 = rays->t1; a.ri = rays->ri; }
   const unsigned grid = (unsigned)(F.T < cus ? F.T : cus);
-  const int key = (F.D == 256 ? 4 : 0) + prec;
-  switch (key) {
-    case 0: return launch_fwd<4, 0>(a, grid, s);
-    case 1: return launch_fwd<4, 1>(a, grid, s);
-    case 2: return launch_fwd<4, 2>(a, grid, s);
-    case 3: return launch_fwd<4, 3>(a, grid, s);
-    case 4: return launch_fwd<8, 0>(a, grid, s);
-    case 5: return launch_fwd<8, 1>(a, grid, s);
-#ifdef FSN_EXP_TRAIN_ONEACC  // timing experiment (round 4): forward / backward in the one-accumulator arithmetic (results garbage)
-    case 6: return launch_fwd<8, 4>(a, grid, s);
-#else
-    case 6: return launch_fwd<8, 2>(a, grid, s);
-#endif
-    default: return launch_fwd<8, 3>(a, grid, s);
-  }
+  return dispatch_net(PrecTraining{}, F.D, prec, [&](auto NT, auto PREC) { return launch_fwd<NT(), PREC()>(a, grid, s); });
 }
 
 int fused_train_bwd(const fsn_mlp_desc* d, int prec, const float* const* W, int64_t n, float* ws, const float* out,
@@ -1304,21 +1219,7 @@ int fused_train_bwd(const fsn_mlp_desc* d, int prec, const float* const* W, int6
                    grad_scale_dev, ws, F.h, F.h_stride, F.bo, F.dhead, F.dbo, F.dp, F.mask, F.mask_stride,
                    prec_is_f16(prec) ? bscale : nullptr, prec_is_f16(prec) ? bamax : nullptr};
     const unsigned grid = (unsigned)(F.T < cus ? F.T : cus);
-    const int key = (D == 256 ? 4 : 0) + prec;
-    switch (key) {
-      case 0: rc = launch_bwd<4, 0>(a, grid, s); break;
-      case 1: rc = launch_bwd<4, 1>(a, grid, s); break;
-      case 2: rc = launch_bwd<4, 2>(a, grid, s); break;
-      case 3: rc = launch_bwd<4, 3>(a, grid, s); break;
-      case 4: rc = launch_bwd<8, 0>(a, grid, s); break;
-      case 5: rc = launch_bwd<8, 1>(a, grid, s); break;
-#ifdef FSN_EXP_TRAIN_ONEACC
-      case 6: rc = launch_bwd<8, 4>(a, grid, s); break;
-#else
-      case 6: rc = launch_bwd<8, 2>(a, grid, s); break;
-#endif
-      default: rc = launch_bwd<8, 3>(a, grid, s); break;
-    }
+    rc = dispatch_net(PrecTraining{}, D, prec, [&](auto NT, auto PREC) { return launch_bwd<NT(), PREC()>(a, grid, s); });
     if (rc != FSN_OK) return rc;
   }
   // ---- wgrad jobs
@@ -1356,12 +1257,7 @@ int fused_train_bwd(const fsn_mlp_desc* d, int prec, const float* const* W, int6
   const WgArgs &big = wa[WG_BIG], &enc = wa[WG_ENC], &br = wa[WG_BR], &bd = wa[WG_BD];
   const int nbig = cnt[WG_BIG], nenc = cnt[WG_ENC], nbr = cnt[WG_BR], nbd = cnt[WG_BD];
   if (D == 256) {
-#ifdef FSN_WGRAD_4W  // experiment: two 4-wave workgroups per CU, 128 rows of A each (twice the chunks in flight, but
-    // B is read and staged twice): 3.55 ms against 2.80 ms for the 8-wave form
-    if ((rc = launch_wgrad<4, 2, 4>(prec, big, nbig, s)) != FSN_OK) return rc;
-#else
     if ((rc = launch_wgrad<8, 4, 4>(prec, big, nbig, s)) != FSN_OK) return rc;
-#endif
     if ((rc = launch_wgrad<8, 4, 1>(prec, enc, nenc, s)) != FSN_OK) return rc;
     if ((rc = launch_wgrad<8, 2, 2>(prec, br, nbr, s)) != FSN_OK) return rc;
     if ((rc = launch_wgrad<8, 2, 1>(prec, bd, nbd, s)) != FSN_OK) return rc;
@@ -1384,17 +1280,12 @@ int fused_train_bwd(const fsn_mlp_desc* d, int prec, const float* const* W, int6
   {
     HeadsArgs ha{U(H(L - 1)), U(ws + F.bo), ws + F.dhead, ws + F.hpart, F.T, F.nsplit_heads};
     const unsigned hg = (unsigned)F.nsplit_heads;
-    switch ((D == 256 ? 4 : 0) + prec) {
-      case 0: k_heads_wgrad<4, 0><<<hg, kThreads, 0, s>>>(ha); break;
-      case 1: k_heads_wgrad<4, 1><<<hg, kThreads, 0, s>>>(ha); break;
-      case 2: k_heads_wgrad<4, 2><<<hg, kThreads, 0, s>>>(ha); break;
-      case 3: k_heads_wgrad<4, 3><<<hg, kThreads, 0, s>>>(ha); break;
-      case 4: k_heads_wgrad<8, 0><<<hg, kThreads, 0, s>>>(ha); break;
-      case 5: k_heads_wgrad<8, 1><<<hg, kThreads, 0, s>>>(ha); break;
-      case 6: k_heads_wgrad<8, 2><<<hg, kThreads, 0, s>>>(ha); break;
-      default: k_heads_wgrad<8, 3><<<hg, kThreads, 0, s>>>(ha); break;
-    }
-    FSN_LAUNCH_CHECK("k_heads_wgrad");
+    rc = dispatch_net(PrecTraining{}, D, prec, [&](auto NT, auto PREC) {
+      k_heads_wgrad<NT(), PREC()><<<hg, kThreads, 0, s>>>(ha);
+      FSN_LAUNCH_CHECK("k_heads_wgrad");
+      return FSN_OK;
+    });
+    if (rc != FSN_OK) return rc;
     HeadsRdArgs hr{ws + F.hpart, F.nsplit_heads, D, grad_scale_dev, dW[L], db[L], dW[L + 3], db[L + 3],
                    prec_is_f16(prec) ? status : nullptr, accumulate ? 1 : 0};
     const int nn = D + 3 * (D / 2) + 4;

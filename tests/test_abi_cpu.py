@@ -72,6 +72,16 @@ def test_training_and_occgrid_entry_points_validate_without_gpu():
     assert lib.fsn_occgrid_march(None, None, 5, bad, 16, 1, None, 0.0, 1.0, 0.1, None, 8, None, None, None, None, None, None) != 0
     assert lib.fsn_occgrid_update(None, 64, None, None, 0, 0.95, None, None, None) != 0
     assert lib.fsn_packed_visibility(None, None, None, None, 0, 0, 1e-4, 0.0, None, None) == 0  # empty: nothing to do
+    # modes an entry point has no kernel for are refused by name, in front of the launch dispatch (FSN_E_UNSUPPORTED = -2)
+    o = L.OccRenderArgs()
+    o.R, o.step, o.max_steps = 0, 0.1, 8
+    assert lib.fsn_render_rays_occgrid(C.byref(d), L.FSN_PREC_FP16X2, None, C.byref(o), None) == -2
+    assert b"fsn_render_rays_occgrid: precision mode 6" in lib.fsn_last_error()
+    assert lib.fsn_mlp_layer_maxima(C.byref(d), L.FSN_PREC_FP16, None, None, None, None, None, 0, None, None) == -2
+    assert b"fsn_mlp_layer_maxima: precision mode 3" in lib.fsn_last_error()
+    for x3 in (L.FSN_PREC_BF16X3, L.FSN_PREC_FP16X3, L.FSN_PREC_FP16X3U, L.FSN_PREC_FP16X2):
+        assert lib.fsn_occgrid_refresh(C.byref(d), x3, None, None, None, 16, 1, aabb, 0, 0, 0, None, 0.1, None, None, None, None) == -2
+        assert b"fsn_occgrid_refresh: precision mode" in lib.fsn_last_error()
 
 
 def test_host_layer_has_no_cpu_fallback():

@@ -53,12 +53,11 @@ ABL = os.environ.get("FSN_KLOOP_ABL", "")
 WAIT2 = os.environ.get("FSN_KLOOP_WAIT2", "1") == "1"
 UPP = 8        # units per 16-KiB phase (a unit = 1 KiB high + 1 KiB low parts)
 UB = 2048      # bytes per unit in the x3 stream layout
-D = int(os.environ.get("FSN_KLOOP_D", "2"))   # units of A operands in flight ahead of the MFMAs (D + 1 register sets)
-LEAD = D       # a phase is opened LEAD units before the previous one ends
+D = 2          # units of A operands in flight ahead of the MFMAs (D + 1 register sets)
+LEAD = D       # a phase is opened LEAD units before the previous one ends (mlp_dev.hpp kLead)
 LOADS = 4     # LDS-DMA loads (1 KiB each) of a loader wave per phase: four loader waves x 4 KiB
-LOOK = int(os.environ.get("FSN_KLOOP_LOOK", "2"))  # phases staged ahead of the one being opened (mlp_dev.hpp kLook =
-# kNSlot - 2): a phase opening may leave (LOOK - 1) x LOADS loads of this wave in flight.  2 = the four-slot ring of the
-# product; 3 = a five-slot ring (experiment, with -DFSN_NSLOT=5 -DFSN_RING_EXPERIMENT)
+LOOK = 2       # phases staged ahead of the one being opened (mlp_dev.hpp kLook, the four-slot ring): a phase opening
+# may leave (LOOK - 1) x LOADS loads of this wave in flight
 NSETS = D + 1  # A register sets
 SETS = {0: (240, 248), 1: (248, 240)}  # parity -> (first register of the current set, of the other set)
 CSET = 232     # first register of the correction set
