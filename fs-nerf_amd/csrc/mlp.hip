@@ -63,31 +63,9 @@ struct MlpFwdArgs {
   int32_t full;
 };
 
-// sample s of the ray form: x = o + d (t0 + t1) / 2 in the reference's operation order (rendering.py:59-61, 77-79:
-// to + td * (t_starts + t_ends)[:, None] / 2.0), dirs = d
-__device__ __forceinline__ void ray_sample(const float* __restrict__ ro, const float* __restrict__ rd,
-                                           const int64_t* __restrict__ ri, const float* __restrict__ t0,
-                                           const float* __restrict__ t1, int64_t s, float* q, bool with_dir) {
-  const int64_t r = ri[s];
-  const float tm = t0[s] + t1[s];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float dc = rd[3 * r + c];
-    q[c] = ro[3 * r + c] + dc * tm / 2.0f;
-    if (with_dir) q[3 + c] = dc;
-  }
-}
-
-// sample source of the standalone kernel: the tile's positions / directions staged in LDS
-struct TileSrc {
-  const float* p;  // this lane's [x,y,z,dx,dy,dz] in LDS
-  __device__ __forceinline__ void pos(float& x, float& y, float& z) const { x = p[0]; y = p[1]; z = p[2]; }
-  __device__ __forceinline__ void dir(float& x, float& y, float& z) const { x = p[3]; y = p[4]; z = p[5]; }
-};
-
 // Persistent workgroups; tile = 128 NG consecutive samples; wave w / lane (c = lane&15, g = lane>>4) owns samples
 // tile0 + 16*(NG*w + q) + c, q < NG (NG = 2 sample groups per wave in the single-pass modes of 256-wide networks,
-// mlp_dev.hpp gemm_layer2).  LDS: [weight ring 64 KiB][aux + masks][tile inputs 128 NG x 6 floats].
+// mlp_dev.hpp groups_per_wave / tile_slot).  LDS: [weight ring 64 KiB][aux + masks][tile inputs 128 NG x 6 floats].
 template <int NT, int PREC, bool FULL>
 __global__ __launch_bounds__(kThreads) void k_mlp_fwd(MlpFwdArgs a) {
   constexpr int NG = groups_per_wave<NT, PREC>(), TILE = 128 * NG;
@@ -119,34 +97,22 @@ __global__ __launch_bounds__(kThreads) void k_mlp_fwd(MlpFwdArgs a) {
       }
     }
     __builtin_amdgcn_wave_barrier();
-    const int64_t s = tile * TILE + wave * (16 * NG) + (lane & 15);
-    if constexpr (NG == 1) {
-      const TileSrc src{in_lds + (wave * 16 + (lane & 15)) * 6};
-      float sigma, rgb[3] = {0.f, 0.f, 0.f};
-      mlp_tile<NT, PREC, FULL>(st, net, src, ring, sigma, rgb);
-      if (lane < 16 && s < a.n) {
-        if (full) {
-          f32x4 o = {rgb[0], rgb[1], rgb[2], sigma};
-          *reinterpret_cast<f32x4*>(a.out + 4 * s) = o;
-        } else {
-          a.out[s] = sigma;
-        }
-      }
-    } else {
-      const TileSrc src0{in_lds + (wave * 32 + (lane & 15)) * 6}, src1{in_lds + (wave * 32 + 16 + (lane & 15)) * 6};
-      float sigma[2], rgb[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
-      mlp_tile2<NT, PREC, FULL>(st, net, src0, src1, ring, sigma, rgb);
-      if (lane < 32) {  // lanes 0-15 write group 0, lanes 16-31 group 1 (every lane holds both results)
-        const int q = lane >> 4;
-        const int64_t sq = s + 16 * q;
-        if (sq < a.n) {
-          if (full) {
-            f32x4 o = {rgb[q][0], rgb[q][1], rgb[q][2], sigma[q]};
-            *reinterpret_cast<f32x4*>(a.out + 4 * sq) = o;
-          } else {
-            a.out[sq] = sigma[q];
-          }
-        }
+    const int64_t s0 = tile * TILE + tile_slot<NG>(wave, lane, 0);
+    TileSrc src[NG];
+    FSN_PER_GROUP(q, src[q] = TileSrc{in_lds + tile_slot<NG>(wave, lane, q) * 6};);
+    float sigma[NG], rgb[NG][3] = {};
+    mlp_tile<NT, PREC, FULL>(st, net, src, ring, sigma, rgb);
+    // (One condition here, the store group formed twice, where the other kernels nest `if (tile_stores)` around the
+    // slot: with the nested form hipcc spills ~30 more SGPRs in this kernel's one-group x3 instances - <4, fp16x3, full>
+    // 45 -> 77 - and the conjunction costs the others.  Same predicate either way.)
+    if (tile_stores<NG>(lane) && s0 + 16 * tile_store_group<NG>(lane) < a.n) {
+      const int qs = tile_store_group<NG>(lane);  // the group whose result this lane stores
+      const int64_t s = s0 + 16 * qs;
+      if (full) {
+        f32x4 o = {rgb[qs][0], rgb[qs][1], rgb[qs][2], sigma[qs]};
+        *reinterpret_cast<f32x4*>(a.out + 4 * s) = o;
+      } else {
+        a.out[s] = sigma[qs];
       }
     }
   }
@@ -210,8 +176,8 @@ __global__ __launch_bounds__(kThreads) void k_mlp_maxima(MlpFwdArgs a, float* __
       q[3] = a.dirs[3 * sc]; q[4] = a.dirs[3 * sc + 1]; q[5] = a.dirs[3 * sc + 2];
     }
     __builtin_amdgcn_wave_barrier();
-    const TileSrc src{in_lds + (wave * 16 + (lane & 15)) * 6};
-    float sigma, rgb[3] = {0.f, 0.f, 0.f};
+    const TileSrc src[1] = {{in_lds + tile_slot<1>(wave, lane, 0) * 6}};
+    float sigma[1], rgb[1][3] = {};
     mlp_tile<NT, PREC, true>(st, net, src, ring, sigma, rgb, sv);
   }
   st.drain();

@@ -72,6 +72,27 @@ constexpr int kRingBytes = kNSlot * kPhaseBytes;
 constexpr int kAuxCapFloats = 3456;  // LDS reserved per network for biases / heads (8x256 needs 3392)
 constexpr int kTileCols = 128;       // samples per workgroup tile = columns of a T-layout tile (train_fused.hip)
 constexpr int kTRow = 16;            // T-layout: samples of a chunk (consecutive pair-rows lie kTRow x NPL dwords apart)
+// Sample groups of 16 per wave in the inference kernels: 2 in the single-pass modes of 256-wide networks (gemm_layer's
+// two-group body), so that a workgroup tile is 256 samples and every weight phase - one barrier, one round of LDS-DMA,
+// 16 KiB from L2 - is used by twice as many samples.  (mlp_tile's NG is not always this: the training forward and the
+// calibration pass run one group with a saver in every mode.)
+template <int NT, int PREC>
+constexpr int groups_per_wave() { return (!prec_is_x3(PREC) && NT == 8) ? 2 : 1; }
+// Lane layout of a tile of 128 NG samples.  Wave w evaluates the NG groups of 16 consecutive samples NG w + q, q < NG;
+// lane l works on sample l & 15 of each of them (the four lanes l, l + 16, l + 32, l + 48 share a sample).  After
+// mlp_tile EVERY lane holds every group's result; lanes [16 q, 16 q + 16) are the ones that store group q's, i.e.
+// lane l < 16 NG stores group l >> 4, the tile's slot tile_slot(wave, l, 0) + 16 (l >> 4).
+template <int NG>
+__device__ __forceinline__ constexpr int tile_slot(int wave, int lane, int q) {  // slot of group q's sample in the tile
+  return (wave * NG + q) * 16 + (lane & 15);
+}
+template <int NG>
+__device__ __forceinline__ constexpr bool tile_stores(int lane) { return lane < 16 * NG; }  // this lane stores a result ...
+template <int NG>
+__device__ __forceinline__ constexpr int tile_store_group(int lane) {  // ... namely that of this group
+  static_assert(NG == 1 || NG == 2, "sample groups per wave");
+  return (lane >> 4) & (NG - 1);
+}
 // T-layout (train_fused.hip) of a saved matrix with 2 P rows, per 128-sample tile: [chunk of 16 samples][P pair-rows]
 // [16 samples][NPL parts] dwords, NPL = 2 in the x3 modes (high part, low part side by side), 1 in the single-pass
 // modes.  Offset of the first part of (pair-row pr, sample s of the tile) inside the tile's block of 2 P x 128 dwords:
@@ -998,21 +1019,17 @@ __device__ __forceinline__ void gemm_layer(WStream& st, const NetDev& net, int a
 }
 
 // ---------------------------------------------------------------- two sample groups per wave (single-pass modes)
-// sample groups of 16 per wave: 2 in the single-pass modes of 256-wide networks (gemm_layer2 below), so that a
-// workgroup tile is 256 samples and every weight phase - one barrier, one round of LDS-DMA, 16 KiB from L2 - is used
-// by twice as many samples
-template <int NT, int PREC>
-constexpr int groups_per_wave() { return (!prec_is_x3(PREC) && NT == 8) ? 2 : 1; }
-
 // 32 samples per wave as two 16-sample groups that share every A operand: one ds_read_b128 feeds two MFMAs, and a
 // 16-KiB weight phase (one barrier, one round of LDS-DMA) covers 256 samples of the workgroup instead of 128.  The
 // single-pass modes carry no low parts, so both groups' activations (2 x 64 registers in, 2 x 64 out) still fit two
-// waves per SIMD.  Same blob, same unit order, same epilogue arithmetic per group as gemm_layer.
+// waves per SIMD.  Same blob, same unit order, same epilogue arithmetic per group as the one-group gemm_layer.
+// (The NG == 2 body behind mlp_tile's FSN_GEMM_LAYER; nothing else calls it.  The k-loops really differ - one group:
+// the hand-scheduled x3 blocks or the prefetch paths; two groups: every A operand shared by four MFMAs - so each keeps
+// its body.)
 template <int PREC, int NP_OUT, int KS_ACT, int KS_ENC, int EPI, int NACT, int NENC, int NOUT>
-__device__ __forceinline__ void gemm_layer2(WStream& st, const NetDev& net, int aux_bias, const Frag (&act0)[NACT],
-                                            const Frag (&act1)[NACT], const Frag (&enc0)[NENC], const Frag (&enc1)[NENC],
-                                            Frag (&out0)[NOUT], Frag (&out1)[NOUT], Heads& heads0, Heads& heads1,
-                                            ARing& ring, int g) {
+__device__ __forceinline__ void gemm_layer_two_groups(WStream& st, const NetDev& net, int aux_bias,
+                                                      const Frag (&act)[2][NACT], const Frag (&enc)[2][NENC],
+                                                      Frag (&out)[2][NOUT], Heads (&heads)[2], ARing& ring, int g) {
   constexpr bool F16 = prec_is_f16(PREC);
   static_assert(!prec_is_x3(PREC), "two groups per wave: single-pass modes only");
   constexpr int UPP = 16, UB = 1024;
@@ -1028,8 +1045,8 @@ __device__ __forceinline__ void gemm_layer2(WStream& st, const NetDev& net, int 
     f32x4 a00 = b0, a01 = b1, a10 = b0, a11 = b1;  // [group][tile]
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      const Frag& x0 = ks < KS_ACT ? act0[ks < KS_ACT ? ks : 0] : enc0[ks >= KS_ACT ? ks - KS_ACT : 0];
-      const Frag& x1 = ks < KS_ACT ? act1[ks < KS_ACT ? ks : 0] : enc1[ks >= KS_ACT ? ks - KS_ACT : 0];
+      const Frag& x0 = ks < KS_ACT ? act[0][ks < KS_ACT ? ks : 0] : enc[0][ks >= KS_ACT ? ks - KS_ACT : 0];
+      const Frag& x1 = ks < KS_ACT ? act[1][ks < KS_ACT ? ks : 0] : enc[1][ks >= KS_ACT ? ks - KS_ACT : 0];
       const int u = (tp * KS + ks) * 2;  // compile-time after unrolling
       if (((u + kLead) % UPP == 0 && u + kLead <= TOTAL) || (u + kLead == TOTAL && TOTAL % UPP != 0)) st.open_next();
       if (u % UPP == 0) st.enter_phase();
@@ -1054,86 +1071,8 @@ __device__ __forceinline__ void gemm_layer2(WStream& st, const NetDev& net, int 
     // asm - gained 0.9 % and was NOT safe: hipcc does not see the XDL hazards of registers an asm statement touches,
     // and the bf16 density pass came out different from run to run.  tests/test_parity_fp64.py now renders the
     // same rays alone and inside a frame in this mode too.)
-    pair_epilogue<PREC, NP_OUT, EPI>(net, tp, a00, a01, a00, a01, out0, heads0, g, hk);  // (single pass: no corrections)
-    pair_epilogue<PREC, NP_OUT, EPI>(net, tp, a10, a11, a10, a11, out1, heads1, g, hk);
-  }
-}
-
-// Whole network for one tile of 256 samples (two groups per wave); src0 / src1 supply this lane's sample of each group.
-template <int NT, int PREC, bool FULL, class Src>
-__device__ __forceinline__ void mlp_tile2(WStream& st, const NetDev& net, const Src& src0, const Src& src1, ARing& ring,
-                                          float (&sigma)[2], float (&rgb)[2][3]) {
-  constexpr int NA = NT;
-  constexpr bool F16 = prec_is_f16(PREC);
-  const int g = (threadIdx.x >> 4) & 3;
-  constexpr int D = 32 * NT;
-  const int L = net.n_layers;
-  const float* misc = net.aux + (L + 5) * D;
-  Frag A0[NA], A1[NA], B0[NA], B1[NA];
-  Frag none[1];
-  Heads h0{0.f, {0.f, 0.f, 0.f}, {0u, 0u, 0u}}, h1{0.f, {0.f, 0.f, 0.f}, {0u, 0u, 0u}};
-  auto enc_pos = [&](Frag (&p0)[kKsPos], Frag (&p1)[kKsPos]) __attribute__((always_inline)) {
-    float x, y, z;
-    src0.pos(x, y, z);
-    encode<kKsPos, F16, false, false>(x, y, z, net.n_freqs_pos, misc + 4, net.pos_mask, g, p0);
-    src1.pos(x, y, z);
-    encode<kKsPos, F16, false, false>(x, y, z, net.n_freqs_pos, misc + 4, net.pos_mask, g, p1);
-  };
-  {
-    Frag p0[kKsPos], p1[kKsPos];
-    enc_pos(p0, p1);
-    gemm_layer2<PREC, NT, 0, kKsPos, EPI_RELU_CVT>(st, net, 0, none, none, p0, p1, A0, A1, h0, h1, ring, g);
-  }
-#define FSN_HIDDEN2(EPI, I0, I1, O0, O1, LIDX)                                                              \
-  do {                                                                                                      \
-    if ((net.skip_mask >> ((LIDX)-1)) & 1u) {                                                               \
-      Frag p0[kKsPos], p1[kKsPos];                                                                          \
-      enc_pos(p0, p1);                                                                                      \
-      gemm_layer2<PREC, NT, NA, kKsPos, EPI>(st, net, (LIDX)*D, I0, I1, p0, p1, O0, O1, h0, h1, ring, g);    \
-    } else                                                                                                  \
-      gemm_layer2<PREC, NT, NA, 0, EPI>(st, net, (LIDX)*D, I0, I1, none, none, O0, O1, h0, h1, ring, g);    \
-  } while (0)
-  for (int l = 1; l <= L - 2; l += 2) {
-    FSN_HIDDEN2(EPI_RELU_CVT, A0, A1, B0, B1, l);
-    if (l + 1 <= L - 2) {
-      FSN_HIDDEN2(EPI_RELU_CVT, B0, B1, A0, A1, l + 1);
-    } else {
-#pragma unroll
-      for (int i = 0; i < NA; ++i) { A0[i] = B0[i]; A1[i] = B1[i]; }
-    }
-  }
-  FSN_HIDDEN2((FULL ? EPI_LAST_FULL : EPI_LAST_DENS), A0, A1, B0, B1, L - 1);
-#undef FSN_HIDDEN2
-  {
-    float s0 = h0.sigma, s1 = h1.sigma;
-    s0 += __shfl_xor(s0, 16, 64); s1 += __shfl_xor(s1, 16, 64);
-    s0 += __shfl_xor(s0, 32, 64); s1 += __shfl_xor(s1, 32, 64);
-    sigma[0] = s0 + misc[0];
-    sigma[1] = s1 + misc[0];
-  }
-  if (FULL) {
-    gemm_layer2<PREC, NT, NA, 0, EPI_CVT>(st, net, L * D, B0, B1, none, none, A0, A1, h0, h1, ring, g);
-    Frag d0[kKsDir], d1[kKsDir];
-    float x, y, z;
-    src0.dir(x, y, z);
-    encode<kKsDir, F16, false, false>(x, y, z, net.n_freqs_dir, misc + 20, net.dir_mask, g, d0);
-    src1.dir(x, y, z);
-    encode<kKsDir, F16, false, false>(x, y, z, net.n_freqs_dir, misc + 20, net.dir_mask, g, d1);
-    gemm_layer2<PREC, NT / 2, NA, kKsDir, EPI_RGB>(st, net, (L + 1) * D, A0, A1, d0, d1, B0, B1, h0, h1, ring, g);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      float z0 = h0.rgb[c], z1 = h1.rgb[c];
-      z0 += __shfl_xor(z0, 16, 64); z1 += __shfl_xor(z1, 16, 64);
-      z0 += __shfl_xor(z0, 32, 64); z1 += __shfl_xor(z1, 32, 64);
-      rgb[0][c] = 1.0f / (1.0f + expf(-(z0 + misc[1 + c])));
-      rgb[1][c] = 1.0f / (1.0f + expf(-(z1 + misc[1 + c])));
-    }
-  }
-  if constexpr (F16) {
-    // (single pass: one running maximum per group for the whole tile, no per-layer scale check)
-    asm("v_pk_max_u16 %0, %0, %1" : "+v"(h0.rs.fmax) : "v"(h1.rs.fmax));
-    range_layer_end<false>(h0.rs);
-    range_report(net.status, h0.rs);
+    pair_epilogue<PREC, NP_OUT, EPI>(net, tp, a00, a01, a00, a01, out[0], heads[0], g, hk);  // (single pass: no corrections)
+    pair_epilogue<PREC, NP_OUT, EPI>(net, tp, a10, a11, a10, a11, out[1], heads[1], g, hk);
   }
 }
 
@@ -1162,9 +1101,9 @@ __device__ __forceinline__ void prime_ring(const WStream& st, ARing& ring) {
 }
 
 // ---------------------------------------------------------------- whole network, one tile
-// `src` supplies this lane's sample on demand: src.pos(x,y,z) and src.dir(x,y,z) (the four lanes
-// l, l+16, l+32, l+48 hold the same sample).  The direction is read only in front of the branch
-// layer.  Outputs (valid in all lanes): sigma, and rgb when FULL.
+// The tile is 128 NG samples, NG groups of 16 per wave (tile_slot above).  src[q] supplies this lane's sample of group
+// q on demand: src[q].pos(x,y,z) and src[q].dir(x,y,z) (the four lanes l, l+16, l+32, l+48 hold the same sample).  The
+// direction is read only in front of the branch layer.  Outputs (valid in all lanes): sigma[q], and rgb[q] when FULL.
 // Saver of the inference kernels: nothing is kept.
 struct NoSave {
   static constexpr bool kSave = false;
@@ -1176,95 +1115,162 @@ struct NoSave {
   __device__ __forceinline__ void layer_done(int, Hook&) const {}  // after GEMM l (kernel order) of a tile
 };
 
-template <int NT, int PREC, bool FULL, class Src, class SV>
-__device__ __forceinline__ void mlp_tile(WStream& st, const NetDev& net, const Src& src, ARing& ring, float& sigma,
-                                         float (&rgb)[3], const SV& sv) {
+// A statement for every sample group of the wave, Q naming the group's (constexpr) index in it.  Spelled without a
+// loop or a lambda: for one group the code then is, token for token, straight-line code on group 0 (hipcc's code for
+// a kernel depends on such things).  Expects NG in scope.  The kernels' call sites use it too.
+// Spellings tried for the per-group steps, each compared kernel by kernel with the two-function form this replaced
+// (figures of tools/kernel_regs.sh): `#pragma unroll for (q < NG)` and an always_inline lambda per step both moved
+// registers in every one-group kernel (k_mlp_fwd<4, fp16x3u, full>: 45 -> 85 spilled SGPRs; <8, bf16, full>: 4 -> 11
+// spilled VGPRs); a forwarding gemm_layer function added ~25 instructions to the 256-wide x3 kernels; a loop around
+// the A = B copy reversed the order of its moves.  This form leaves the one-group kernels as they were up to register
+// numbering.
+#define FSN_PER_GROUP(Q, ...)               \
+  do {                                      \
+    {                                       \
+      constexpr int Q = 0;                  \
+      __VA_ARGS__                           \
+    }                                       \
+    if constexpr (NG == 2) {                \
+      constexpr int Q = NG - 1;             \
+      __VA_ARGS__                           \
+    }                                       \
+  } while (0)
+
+// Private to mlp_tile (st, net, heads, ring, g, hk and NG of its scope; undefined after it): one GEMM layer for the
+// wave's NG sample groups - operands, outputs and heads per group - selected here once: one group runs gemm_layer, two
+// run gemm_layer_two_groups.  A macro, not a function: a forwarding function changes hipcc's code for the one-group
+// kernels.  TA: the template arguments in parentheses.
+#define FSN_TEMPLATE_ARGS(...) __VA_ARGS__
+#define FSN_GEMM_LAYER(TA, BIAS, IN, ENC, OUT)                                                                          \
+  do {                                                                                                                  \
+    if constexpr (NG == 1) gemm_layer<FSN_TEMPLATE_ARGS TA>(st, net, BIAS, IN[0], ENC[0], OUT[0], heads[0], ring, g, hk); \
+    else gemm_layer_two_groups<FSN_TEMPLATE_ARGS TA>(st, net, BIAS, IN, ENC, OUT, heads, ring, g);                       \
+  } while (0)
+
+template <int NT, int PREC, bool FULL, int NG, class Src, class SV>
+__device__ __forceinline__ void mlp_tile(WStream& st, const NetDev& net, const Src (&src)[NG], ARing& ring,
+                                         float (&sigma)[NG], float (&rgb)[NG][3], const SV& sv) {
   constexpr int NA = NT;  // k-steps of 32 across the hidden width
   constexpr bool F16 = prec_is_f16(PREC), X3 = prec_is_x3(PREC), LS = prec_lo_scaled(PREC);
+  // one group: every mode, every saver.  Two groups share each A operand (gemm_layer_two_groups): single-pass modes, nothing saved
+  static_assert(NG == 1 || (NG == 2 && !X3 && std::is_same<SV, NoSave>::value), "sample groups per wave");
   const int g = (threadIdx.x >> 4) & 3;
   constexpr int D = 32 * NT;
   const int L = net.n_layers;
   const float* misc = net.aux + (L + 5) * D;
-  Frag A[NA], B[NA];
-  Frag none[1];
-  Heads heads{0.f, {0.f, 0.f, 0.f}, {0u, 0u, 0u}};
+  Frag A[NG][NA], B[NG][NA];
+  Frag none[NG][1];
+  Heads heads[NG];
+  FSN_PER_GROUP(q, heads[q] = Heads{0.f, {0.f, 0.f, 0.f}, {0u, 0u, 0u}};);
+  // positional encoding of every group's sample into PE (SAVE: the training forward keeps the first one)
+#define FSN_ENC_POS(SAVE, PE)                                                                                 \
+  FSN_PER_GROUP(q, float px, py, pz; src[q].pos(px, py, pz);                                                     \
+                encode<kKsPos, F16, X3, SAVE, LS>(px, py, pz, net.n_freqs_pos, misc + 4, net.pos_mask, g, PE[q], \
+                                                  SAVE ? sv.enc_pos(g) : nullptr);)
   {
-    Frag pe[kKsPos];
-    float px, py, pz;
-    src.pos(px, py, pz);
-    encode<kKsPos, F16, X3, SV::kSave, LS>(px, py, pz, net.n_freqs_pos, misc + 4, net.pos_mask, g, pe, sv.enc_pos(g));
+    Frag pe[NG][kKsPos];
+    FSN_ENC_POS(SV::kSave, pe);
     typename SV::Hook hk = sv.hidden(0);
-    gemm_layer<PREC, NT, 0, kKsPos, EPI_RELU_CVT>(st, net, 0, none, pe, A, heads, ring, g, hk);
+    FSN_GEMM_LAYER((PREC, NT, 0, kKsPos, EPI_RELU_CVT), 0, none, pe, A);
     sv.layer_done(0, hk);
   }
-  // A wide (skip) layer re-encodes the position instead of keeping the 16 registers of `pe` alive across the layers
-  // in between (same function of the same inputs: identical values; fused kernel: 360 -> 256 B of scratch, +1.5 %).
-#define FSN_HIDDEN(EPI, IN, OUT, LIDX)                                                        \
-  do {                                                                                        \
-    typename SV::Hook hk = sv.hidden(LIDX);                                                   \
-    if ((net.skip_mask >> ((LIDX)-1)) & 1u) {                                                 \
-      Frag pe2[kKsPos];                                                                       \
-      float qx, qy, qz;                                                                       \
-      src.pos(qx, qy, qz);                                                                    \
-      encode<kKsPos, F16, X3, false, LS>(qx, qy, qz, net.n_freqs_pos, misc + 4, net.pos_mask, g, pe2); \
-      gemm_layer<PREC, NT, NA, kKsPos, EPI>(st, net, (LIDX)*D, IN, pe2, OUT, heads, ring, g, hk); \
-    } else                                                                                    \
-      gemm_layer<PREC, NT, NA, 0, EPI>(st, net, (LIDX)*D, IN, none, OUT, heads, ring, g, hk);     \
-    sv.layer_done(LIDX, hk);                                                                  \
+  // Hidden layer LIDX.  A wide (skip) layer re-encodes the position instead of keeping the 16 registers of `pe` alive
+  // across the layers in between (same function of the same inputs: identical values; fused kernel: 360 -> 256 B of
+  // scratch, +1.5 %).
+#define FSN_HIDDEN(EPI, IN, OUT, LIDX)                                                              \
+  do {                                                                                              \
+    typename SV::Hook hk = sv.hidden(LIDX);                                                         \
+    if ((net.skip_mask >> ((LIDX)-1)) & 1u) {                                                       \
+      Frag pe2[NG][kKsPos];                                                                         \
+      FSN_ENC_POS(false, pe2);                                                                      \
+      FSN_GEMM_LAYER((PREC, NT, NA, kKsPos, EPI), (LIDX)*D, IN, pe2, OUT);   \
+    } else                                                                                          \
+      FSN_GEMM_LAYER((PREC, NT, NA, 0, EPI), (LIDX)*D, IN, none, OUT);       \
+    sv.layer_done(LIDX, hk);                                                                        \
   } while (0)
   for (int l = 1; l <= L - 2; l += 2) {
     FSN_HIDDEN(EPI_RELU_CVT, A, B, l);
     if (l + 1 <= L - 2) {
       FSN_HIDDEN(EPI_RELU_CVT, B, A, l + 1);
     } else {
-#pragma unroll
-      for (int i = 0; i < NA; ++i) A[i] = B[i];
+      FSN_PER_GROUP(q, Frag(&a)[NA] = A[q]; const Frag(&b)[NA] = B[q];
+                    _Pragma("unroll") for (int i = 0; i < NA; ++i) a[i] = b[i];);
     }
   }
   // last hidden layer (index L-1): sigma head on its fp32 output (models.py:127,141)
   FSN_HIDDEN((FULL ? EPI_LAST_FULL : EPI_LAST_DENS), A, B, L - 1);
 #undef FSN_HIDDEN
+#undef FSN_ENC_POS
   {
-    float sg = heads.sigma;
-    sg += __shfl_xor(sg, 16, 64);
-    sg += __shfl_xor(sg, 32, 64);
-    sigma = sg + misc[0];
+    // a head's dot product is spread over the four lanes of a sample: two butterfly steps
+    float sg[NG];
+    FSN_PER_GROUP(q, sg[q] = heads[q].sigma;);
+    FSN_PER_GROUP(q, sg[q] += __shfl_xor(sg[q], 16, 64););
+    FSN_PER_GROUP(q, sg[q] += __shfl_xor(sg[q], 32, 64););
+    FSN_PER_GROUP(q, sigma[q] = sg[q] + misc[0];);
   }
   if (FULL) {
     // connection (no activation, models.py:130), then branch on [feat, dir_enc] (models.py:131-133)
     {
       typename SV::Hook hk = sv.hidden(L);
-      gemm_layer<PREC, NT, NA, 0, EPI_CVT>(st, net, L * D, B, none, A, heads, ring, g, hk);
+      FSN_GEMM_LAYER((PREC, NT, NA, 0, EPI_CVT), L * D, B, none, A);
       sv.layer_done(L, hk);
     }
-    Frag de[kKsDir];
-    float dx, dy, dz;
-    src.dir(dx, dy, dz);
-    encode<kKsDir, F16, X3, SV::kSave, LS>(dx, dy, dz, net.n_freqs_dir, misc + 20, net.dir_mask, g, de, sv.enc_dir(g));
+    Frag de[NG][kKsDir];
+    FSN_PER_GROUP(q, float dx, dy, dz; src[q].dir(dx, dy, dz);
+                  encode<kKsDir, F16, X3, SV::kSave, LS>(dx, dy, dz, net.n_freqs_dir, misc + 20, net.dir_mask, g, de[q], sv.enc_dir(g)););
     {
       typename SV::Hook hk = sv.branch();
-      gemm_layer<PREC, NT / 2, NA, kKsDir, EPI_RGB>(st, net, (L + 1) * D, A, de, B, heads, ring, g, hk);
+      FSN_GEMM_LAYER((PREC, NT / 2, NA, kKsDir, EPI_RGB), (L + 1) * D, A, de, B);
       sv.layer_done(L + 1, hk);
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      float z = heads.rgb[c];
-      z += __shfl_xor(z, 16, 64);
-      z += __shfl_xor(z, 32, 64);
-      z += misc[1 + c];
-      rgb[c] = 1.0f / (1.0f + expf(-z));  // sigmoid (models.py:135)
+      float z[NG];
+      FSN_PER_GROUP(q, z[q] = heads[q].rgb[c];);
+      FSN_PER_GROUP(q, z[q] += __shfl_xor(z[q], 16, 64););
+      FSN_PER_GROUP(q, z[q] += __shfl_xor(z[q], 32, 64););
+      FSN_PER_GROUP(q, z[q] += misc[1 + c]; rgb[q][c] = 1.0f / (1.0f + expf(-z[q])););  // sigmoid (models.py:135)
     }
   }
   if constexpr (F16) {
-    range_layer_end<false>(heads.rs);  // (single-pass modes keep one running maximum)
-    range_report(net.status, heads.rs);
+    // (single-pass modes keep one running maximum per group for the whole tile, no per-layer scale check; two groups:
+    // their maxima are merged for the report)
+    if constexpr (NG == 2) asm("v_pk_max_u16 %0, %0, %1" : "+v"(heads[0].rs.fmax) : "v"(heads[1].rs.fmax));
+    range_layer_end<false>(heads[0].rs);
+    range_report(net.status, heads[0].rs);
   }
 }
 
-template <int NT, int PREC, bool FULL, class Src>
-__device__ __forceinline__ void mlp_tile(WStream& st, const NetDev& net, const Src& src, ARing& ring, float& sigma,
-                                         float (&rgb)[3]) {
+#undef FSN_GEMM_LAYER
+#undef FSN_TEMPLATE_ARGS
+
+template <int NT, int PREC, bool FULL, int NG, class Src>
+__device__ __forceinline__ void mlp_tile(WStream& st, const NetDev& net, const Src (&src)[NG], ARing& ring,
+                                         float (&sigma)[NG], float (&rgb)[NG][3]) {
   mlp_tile<NT, PREC, FULL>(st, net, src, ring, sigma, rgb, NoSave{});
+}
+
+// Sample source of the kernels that stage a tile's inputs in LDS (k_mlp_fwd, k_mlp_maxima, k_train_fwd)
+struct TileSrc {
+  const float* p;  // this lane's [x,y,z,dx,dy,dz] in LDS
+  __device__ __forceinline__ void pos(float& x, float& y, float& z) const { x = p[0]; y = p[1]; z = p[2]; }
+  __device__ __forceinline__ void dir(float& x, float& y, float& z) const { x = p[3]; y = p[4]; z = p[5]; }
+};
+
+// sample s of their ray form: x = o + d (t0 + t1) / 2 in the reference's operation order (rendering.py:59-61, 77-79:
+// to + td * (t_starts + t_ends)[:, None] / 2.0), dirs = d
+__device__ __forceinline__ void ray_sample(const float* __restrict__ ro, const float* __restrict__ rd,
+                                           const int64_t* __restrict__ ri, const float* __restrict__ t0,
+                                           const float* __restrict__ t1, int64_t s, float* q, bool with_dir) {
+  const int64_t r = ri[s];
+  const float tm = t0[s] + t1[s];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float dc = rd[3 * r + c];
+    q[c] = ro[3 * r + c] + dc * tm / 2.0f;
+    if (with_dir) q[3 + c] = dc;
+  }
 }
 
 // Copy a blob's aux region and the two frequency masks into LDS (all threads of the workgroup;

@@ -81,19 +81,12 @@ __global__ __launch_bounds__(kThreads) void k_occ_refresh(OccRefreshArgs a) {
       *reinterpret_cast<f32x4*>(in_lds + (wave * (16 * NG) + lane) * 4) = v;
     }
     __builtin_amdgcn_wave_barrier();
-    float occ;
-    if constexpr (NG == 1) {
-      const DrawSrc src{in_lds + (wave * 16 + (lane & 15)) * 4};
-      float sigma, rgb[3] = {0.f, 0.f, 0.f};
-      mlp_tile<NT, PREC, false>(st, net, src, ring, sigma, rgb);
-      occ = sigma * a.step;
-    } else {
-      const DrawSrc src0{in_lds + (wave * 32 + (lane & 15)) * 4}, src1{in_lds + (wave * 32 + 16 + (lane & 15)) * 4};
-      float sigma[2], rgb[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
-      mlp_tile2<NT, PREC, false>(st, net, src0, src1, ring, sigma, rgb);
-      occ = (lane >= 16 ? sigma[1] : sigma[0]) * a.step;  // (every lane holds both groups' results)
-    }
-    if (lane < 16 * NG) {
+    DrawSrc src[NG];
+    FSN_PER_GROUP(q, src[q] = DrawSrc{in_lds + tile_slot<NG>(wave, lane, q) * 4};);
+    float sigma[NG], rgb[NG][3] = {};
+    mlp_tile<NT, PREC, false>(st, net, src, ring, sigma, rgb);
+    if (tile_stores<NG>(lane)) {
+      const float occ = sigma[tile_store_group<NG>(lane)] * a.step;  // (every lane holds every group's result)
       const int32_t cell = __float_as_int(in_lds[(wave * (16 * NG) + lane) * 4 + 3]);  // (this lane drew it)
       if (cell >= 0 && occ == occ) atomicMax(a.pending + cell, occ_key(occ));  // (NaN never enters the grid)
     }

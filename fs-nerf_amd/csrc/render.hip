@@ -182,23 +182,21 @@ __global__ __launch_bounds__(kThreads) void k_render_fused(RenderKArgs k) {
     if (!GRP_HIER) return;
     st.pass_begin();
     for (int sub = 0; sub < S_.nsubC; ++sub) {
-      // sample slot of this lane in group q of its wave
-      auto slot = [&](int q) { return sub * TILE + (wave * NG + q) * 16 + (lane & 15); };
+      // sample slot of this lane in group q of its wave (group q + 1: 16 further)
+      auto slot = [&](int q) { return sub * TILE + tile_slot<NG>(wave, lane, q); };
       auto source = [&](int idx) {
         const int idc = min(idx, GRP_G * GRP_S - 1);
         const int g = small_div(idc, GRP_S), i = idc - g * GRP_S;
         return RaySrc{FSN_SPAN(S_.rays, 6 * g, 6), FSN_SPAN(S_.edgesC, g * (GRP_S + 1) + i, 2)};
       };
-      if constexpr (NG == 1) {
-        const int idx = slot(0);
-        float sigma, rgb[3];
-        mlp_tile<NT, PREC, false>(st, netC, source(idx), ring, sigma, rgb);
-        if (lane < 16 && idx < GRP_G * GRP_S) FSN_AT(S_.sigC, idx) = sigma;
-      } else {
-        float sigma[2], rgb[2][3];
-        mlp_tile2<NT, PREC, false>(st, netC, source(slot(0)), source(slot(1)), ring, sigma, rgb);
-        const int q = (lane >> 4) & 1, idx = slot(q);  // lanes 0-15 store group 0, lanes 16-31 group 1
-        if (lane < 32 && idx < GRP_G * GRP_S) FSN_AT(S_.sigC, idx) = sigma[q];
+      const int idx0 = slot(0);
+      RaySrc src[NG];
+      FSN_PER_GROUP(q, src[q] = source(idx0 + 16 * q););
+      float sigma[NG], rgb[NG][3];
+      mlp_tile<NT, PREC, false>(st, netC, src, ring, sigma, rgb);
+      if (tile_stores<NG>(lane)) {
+        const int qs = tile_store_group<NG>(lane), idx = idx0 + 16 * qs;  // (the sample this lane stores)
+        if (idx < GRP_G * GRP_S) FSN_AT(S_.sigC, idx) = sigma[qs];
       }
     }
     st.pass_end();
@@ -221,31 +219,24 @@ __global__ __launch_bounds__(kThreads) void k_render_fused(RenderKArgs k) {
   auto fine_stage = [&](int64_t r0, const float* edges, bool write_edges) __attribute__((always_inline)) {
     st.pass_begin();
     for (int sub = 0; sub < S_.nsubF; ++sub) {
-      auto slot = [&](int q) { return sub * TILE + (wave * NG + q) * 16 + (lane & 15); };
+      auto slot = [&](int q) { return sub * TILE + tile_slot<NG>(wave, lane, q); };
       auto source = [&](int idx) {
         const int idc = min(idx, GRP_G * GRP_SO - 1);
         const int g = small_div(idc, GRP_SO), i = idc - g * GRP_SO;
         return RaySrc{FSN_SPAN(S_.rays, 6 * g, 6), edges + g * (GRP_SO + 1) + i};
       };
-      if constexpr (NG == 1) {
-        const int idx = slot(0);
-        float sigma, rgb[3];
-        mlp_tile<NT, PREC, true>(st, netF, source(idx), ring, sigma, rgb);
-        if (lane < 16 && idx < GRP_G * GRP_SO) {
-          FSN_AT(S_.sigF, idx) = sigma;
-          FSN_AT(S_.rgbF, 3 * idx + 0) = rgb[0];
-          FSN_AT(S_.rgbF, 3 * idx + 1) = rgb[1];
-          FSN_AT(S_.rgbF, 3 * idx + 2) = rgb[2];
-        }
-      } else {
-        float sigma[2], rgb[2][3];
-        mlp_tile2<NT, PREC, true>(st, netF, source(slot(0)), source(slot(1)), ring, sigma, rgb);
-        const int q = (lane >> 4) & 1, idx = slot(q);
-        if (lane < 32 && idx < GRP_G * GRP_SO) {
-          FSN_AT(S_.sigF, idx) = sigma[q];
-          FSN_AT(S_.rgbF, 3 * idx + 0) = rgb[q][0];
-          FSN_AT(S_.rgbF, 3 * idx + 1) = rgb[q][1];
-          FSN_AT(S_.rgbF, 3 * idx + 2) = rgb[q][2];
+      const int idx0 = slot(0);
+      RaySrc src[NG];
+      FSN_PER_GROUP(q, src[q] = source(idx0 + 16 * q););
+      float sigma[NG], rgb[NG][3];
+      mlp_tile<NT, PREC, true>(st, netF, src, ring, sigma, rgb);
+      if (tile_stores<NG>(lane)) {
+        const int qs = tile_store_group<NG>(lane), idx = idx0 + 16 * qs;
+        if (idx < GRP_G * GRP_SO) {
+          FSN_AT(S_.sigF, idx) = sigma[qs];
+          FSN_AT(S_.rgbF, 3 * idx + 0) = rgb[qs][0];
+          FSN_AT(S_.rgbF, 3 * idx + 1) = rgb[qs][1];
+          FSN_AT(S_.rgbF, 3 * idx + 2) = rgb[qs][2];
         }
       }
     }

@@ -192,12 +192,6 @@ struct TrainFwdArgs {
   const int64_t* ri;
 };
 
-struct TileSrcT {
-  const float* p;
-  __device__ __forceinline__ void pos(float& x, float& y, float& z) const { x = p[0]; y = p[1]; z = p[2]; }
-  __device__ __forceinline__ void dir(float& x, float& y, float& z) const { x = p[3]; y = p[4]; z = p[5]; }
-};
-
 template <int NT, int PREC>
 __global__ __launch_bounds__(kThreads) void k_train_fwd(TrainFwdArgs a) {
   __shared__ __attribute__((aligned(1024))) char smem[kRingBytes + (kAuxCapFloats + 96) * 4 + 128 * 6 * 4];
@@ -222,22 +216,15 @@ __global__ __launch_bounds__(kThreads) void k_train_fwd(TrainFwdArgs a) {
     const int64_t sc = s < a.n ? s : a.n - 1;
     if (lane < 16) {
       float* q = in_lds + col * 6;
-      if (a.ri) {  // x = o + d (t0 + t1) / 2, the reference's operation order (rendering.py:77-79); dirs = d
-        const int64_t r = a.ri[sc];
-        const float tm = a.t0[sc] + a.t1[sc];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const float dc = a.rays_d[3 * r + c];
-          q[c] = a.rays_o[3 * r + c] + dc * tm / 2.0f;
-          q[3 + c] = dc;
-        }
+      if (a.ri) {
+        ray_sample(a.rays_o, a.rays_d, a.ri, a.t0, a.t1, sc, q, true);
       } else {
         q[0] = a.x[3 * sc]; q[1] = a.x[3 * sc + 1]; q[2] = a.x[3 * sc + 2];
         q[3] = a.dirs[3 * sc]; q[4] = a.dirs[3 * sc + 1]; q[5] = a.dirs[3 * sc + 2];
       }
     }
     __builtin_amdgcn_wave_barrier();
-    const TileSrcT src{in_lds + col * 6};
+    const TileSrc src[1] = {{in_lds + col * 6}};
     FwdSaver sv;
     uint32_t* wsu = reinterpret_cast<uint32_t*>(a.ws);
     constexpr int NPL = prec_is_x3(PREC) ? 2 : 1;
@@ -249,10 +236,10 @@ __global__ __launch_bounds__(kThreads) void k_train_fwd(TrainFwdArgs a) {
     sv.mk0 = reinterpret_cast<uint32_t*>(a.ws + a.off_mask) + ((tile * 4 + g) * kTC + col) * 2;
     sv.mstride = a.mask_stride;
     sv.n_layers = net.n_layers;
-    float sigma, rgb[3] = {0.f, 0.f, 0.f};
+    float sigma[1], rgb[1][3] = {};
     mlp_tile<NT, PREC, true>(st, net, src, ring, sigma, rgb, sv);
-    if (lane < 16 && s < a.n) {
-      f32x4 o = {rgb[0], rgb[1], rgb[2], sigma};
+    if (tile_stores<1>(lane) && s < a.n) {
+      f32x4 o = {rgb[0][0], rgb[0][1], rgb[0][2], sigma[0]};
       *reinterpret_cast<f32x4*>(a.out + 4 * s) = o;
     }
   }
