@@ -5,10 +5,16 @@
 estimator.update_every_n_steps) and evaluated with render_frame + PSNR and SSIM (run-nerf.py:140-190).
 
     python examples/train_synthetic.py [--estimator occgrid|stratified] [--iters 400] [--hw 64] [--u8-dataset]
+                                       [--depth-weight W] [--distortion-weight W]
 
 --u8-dataset: the teacher's frames become uint8 "photographs" (R.to8b) held in a device-resident RayDataset; the loop
 takes its batches from a RayLoader the way run-nerf.py:236-240 takes them from its DataLoader, and the held-out view
 comes from a FrameLoader (fs_nerf_amd.nerfdata).
+
+--depth-weight / --distortion-weight (both 0 by default: the loop is then the one above): few-shot regularisers on the
+renderer's other outputs through render_rays(full_grad=True) - an MSE between the rendered depth and the teacher's on
+the rays where the teacher hit something (float tables only: the uint8 photographs carry no depth), and the distortion
+loss of the compositor's weights (core.loss.DistortionLoss).
 """
 import argparse
 import math
@@ -22,7 +28,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import fs_nerf_amd  # noqa: E402,F401
 from fs_nerf_amd.core import metrics  # noqa: E402
 from fs_nerf_amd.core import models as M  # noqa: E402
-from fs_nerf_amd.core.loss import WeightNormRegularizer  # noqa: E402
+from fs_nerf_amd.core.loss import DistortionLoss, WeightNormRegularizer  # noqa: E402
 from fs_nerf_amd.core.optim import FusedAdam  # noqa: E402
 from fs_nerf_amd.core.scheduler import ExponentialDecay  # noqa: E402
 from fs_nerf_amd.nerfdata import FrameLoader, RayDataset, RayLoader  # noqa: E402
@@ -63,21 +69,30 @@ def main():
     ap.add_argument("--u8-dataset", action="store_true",
                     help="train on uint8 images through the device-resident RayDataset / RayLoader (epochs without "
                          "replacement, one launch per batch) instead of float tables indexed with torch.randint")
+    ap.add_argument("--depth-weight", type=float, default=0.0,
+                    help="opt-in: weight of a depth-supervision term against the teacher's depth (render_rays(full_grad=True))")
+    ap.add_argument("--distortion-weight", type=float, default=0.0,
+                    help="opt-in: weight of the distortion loss on the compositor's weights (render_rays(full_grad=True))")
     a = ap.parse_args()
+    if a.depth_weight and a.u8_dataset:
+        ap.error("--depth-weight needs the float tables: the uint8 dataset carries no depth")
+    full_grad = a.depth_weight != 0.0 or a.distortion_weight != 0.0
     dev = torch.device("cuda:0")
     hwf = (a.hw, a.hw, 0.5 * a.hw / math.tan(0.5 * 0.6911112))
     near, far, step = 2.0, 6.0, 2e-2
     teacher = make_model(1, dev).eval()
     t_est = R.StratifiedEstimator(near, far, 64, 128)
     poses = [orbit_pose(phi) for phi in range(0, 360, 45)]
-    ro, rd, gt = [], [], []
+    ro, rd, gt, gd = [], [], [], []
     with torch.no_grad():  # the "dataset": rays of every view (blender.py:174-191) and their colours
         for p in poses:
             o, d = U.get_rays(p, hwf, dev)
             ro.append(o.reshape(-1, 3))
             rd.append(d.reshape(-1, 3))
-            gt.append(R.render_frame(hwf, near, far, p, 1 << 20, t_est, teacher, white_bkgd=True, device=dev)[0].reshape(-1, 3))
-    ro, rd, gt = torch.cat(ro), torch.cat(rd), torch.cat(gt)
+            frame, frame_depth = R.render_frame(hwf, near, far, p, 1 << 20, t_est, teacher, white_bkgd=True, device=dev)
+            gt.append(frame.reshape(-1, 3))
+            gd.append(frame_depth.reshape(-1, 1))
+    ro, rd, gt, gd = torch.cat(ro), torch.cat(rd), torch.cat(gt), torch.cat(gd)
     held_out = orbit_pose(22.5)
     if a.u8_dataset:  # the frames as photographs: bytes, resident; the float tables above are dropped
         frames8 = R.to8b(gt).reshape(len(poses), a.hw, a.hw, 3)
@@ -100,6 +115,7 @@ def main():
     optimizer = FusedAdam(model.parameters(), lr=5e-4)  # torch.optim.Adam's arithmetic, one launch over flat arenas
     wnorm = WeightNormRegularizer(model.named_parameters(), reg="l2", reg_ratio=0.5, Td=a.iters)  # run-nerf.py:266-279
     alpha = 1e-5
+    distortion = DistortionLoss()
     scheduler = ExponentialDecay(optimizer, a.iters, 5e-4, r=0.1)
     gen = torch.Generator(device=dev).manual_seed(0)
 
@@ -120,9 +136,15 @@ def main():
         else:
             idx = torch.randint(0, ro.shape[0], (a.batch,), device=dev, generator=gen)
             rays_o, rays_d, rgb_gt = ro[idx], rd[idx], gt[idx]
-        (rgb, _, depth, _), _, _ = R.render_rays(rays_o, rays_d, estimator, model, train=True, white_bkgd=True,
-                                                 render_step_size=step, device=dev)
+        (rgb, _, depth, extras), ray_indices, _ = R.render_rays(rays_o, rays_d, estimator, model, train=True, white_bkgd=True,
+                                                                render_step_size=step, device=dev, full_grad=full_grad)
         loss = torch.nn.functional.mse_loss(rgb, rgb_gt)
+        if a.depth_weight and depth.requires_grad:  # (an all-background batch renders no samples: nothing to supervise)
+            hit = (gd[idx] > near).float()  # render_frame clamps depth to [near, far]: `near` = the teacher saw background
+            loss = loss + a.depth_weight * (hit * (depth - gd[idx]) ** 2).sum() / hit.sum().clamp(min=1.0)
+        if a.distortion_weight and extras is not None and extras["weights"].requires_grad:
+            loss = loss + a.distortion_weight * distortion(extras["weights"], extras["t_starts"], extras["t_ends"],
+                                                           ray_indices, rays_o.shape[0])
         if wnorm.active(k):
             loss = loss + alpha * wnorm()
         loss.backward()

@@ -118,6 +118,10 @@ SIGNATURES = {
     "fsn_weight_norm_fwd": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "fsn_weight_norm_bwd": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "fsn_composite_packed_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fsn_composite_packed_bwd_full": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           _vp, _vp, _vp]),
+    "fsn_distortion_fwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "fsn_distortion_bwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "fsn_ssim_workspace_doubles": (_i64, [_i64, _i, _i, _i]),
     "fsn_ssim": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp, _vp]),
     "fsn_psnr_workspace_doubles": (_i64, [_i64, _i, _i, _i]),

@@ -785,6 +785,72 @@ def composite_packed_bwd(sigmas, rgbs, t_starts, t_ends, ray_indices, n_rays, bk
     return ds, dr
 
 
+def composite_packed_bwd_full(sigmas, rgbs, t_starts, t_ends, ray_indices, n_rays, bkgd, d_colors, d_opacity, opacity=None,
+                              depth=None, d_depth=None, d_weights=None, d_alphas=None, d_trans=None):
+    """The full backward of `composite_packed` (fsn_composite_packed_bwd_full): -> (d_sigmas [N], d_rgbs [N,3]) from the
+    cotangents of all six outputs.  Every cotangent may be None: it reaches the kernel as a NULL pointer and its term is
+    absent.  `opacity` / `depth` are the forward's outputs, needed when `d_depth` is given."""
+    sig, rgb = _f32(sigmas, "sigmas"), _f32(rgbs, "rgbs")
+    t0, t1 = _f32(t_starts, "t_starts"), _f32(t_ends, "t_ends")
+    ri = _i64(ray_indices, "ray_indices")
+    N = sig.numel()
+
+    def opt(t, name, n):
+        if t is None:
+            return None
+        t = _f32(t, name).reshape(-1)
+        if t.numel() != n:
+            raise ValueError(f"{name}: expected {n} values, got {t.numel()}")
+        return t
+
+    dc = opt(d_colors, "d_colors", 3 * n_rays)
+    dop, op, dep, dd = (opt(t, name, n_rays) for t, name in ((d_opacity, "d_opacity"), (opacity, "opacity"), (depth, "depth"),
+                                                            (d_depth, "d_depth")))
+    dw, da, dt = (opt(t, name, N) for t, name in ((d_weights, "d_weights"), (d_alphas, "d_alphas"), (d_trans, "d_trans")))
+    if t0.numel() != N or t1.numel() != N or ri.numel() != N or rgb.numel() != 3 * N:
+        raise ValueError("composite_packed_bwd_full: sigmas, rgbs, t_starts, t_ends and ray_indices disagree in length")
+    ds, dr = torch.empty_like(sig), torch.empty_like(rgb)
+    with torch.cuda.device(sig.device):
+        L.check(L.lib().fsn_composite_packed_bwd_full(_p(sig), _p(rgb), _p(t0), _p(t1), _p(ri), N, n_rays, _bk(bkgd), _p(dc),
+                                                      _p(dop), _p(op), _p(dep), _p(dd), _p(dw), _p(da), _p(dt), _p(ds),
+                                                      _p(dr), _stream()), "fsn_composite_packed_bwd_full")
+    return ds, dr
+
+
+class _DistortionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, w, t0, t1, ri, n_rays):
+        N = w.numel()
+        out = torch.empty(n_rays, device=w.device, dtype=torch.float32)
+        with torch.cuda.device(w.device):
+            L.check(L.lib().fsn_distortion_fwd(_p(w), _p(t0), _p(t1), _p(ri), N, n_rays, _p(out), _stream()),
+                    "fsn_distortion_fwd")
+        ctx.save_for_backward(w, t0, t1, ri)
+        ctx.n_rays = n_rays
+        return out.reshape(n_rays, 1)
+
+    @staticmethod
+    def backward(ctx, g):
+        w, t0, t1, ri = ctx.saved_tensors
+        g = _f32(g, "grad").reshape(-1)
+        d_w = torch.empty_like(w)
+        with torch.cuda.device(w.device):
+            L.check(L.lib().fsn_distortion_bwd(_p(w), _p(t0), _p(t1), _p(ri), w.numel(), ctx.n_rays, _p(g), _p(d_w),
+                                               _stream()), "fsn_distortion_bwd")
+        return d_w, None, None, None, None
+
+
+def distortion(weights: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor, n_rays: int) -> Tensor:
+    """Per-ray distortion of the compositor's weights -> [n_rays, 1] (fsn_distortion_fwd / _bwd; core.loss.DistortionLoss
+    has the definition).  Differentiable w.r.t. `weights` only; a ray without samples gives 0."""
+    w = _f32(weights, "weights").reshape(-1)
+    t0, t1 = _f32(t_starts.detach(), "t_starts").reshape(-1), _f32(t_ends.detach(), "t_ends").reshape(-1)
+    ri = _i64(ray_indices, "ray_indices").reshape(-1)
+    if not (t0.numel() == t1.numel() == ri.numel() == w.numel()):
+        raise ValueError("distortion: weights, t_starts, t_ends and ray_indices disagree in length")
+    return _DistortionFn.apply(w, t0, t1, ri, int(n_rays))
+
+
 # ------------------------------------------------------------------ occupancy-grid sampler (SURVEY 8f, row f2)
 def occgrid_march(rays_o: Tensor, rays_d: Tensor, aabb: Sequence[float], res: int, levels: int, bits: Tensor,
                   near_plane: float, far_plane: float, step: float, u: Optional[Tensor], max_steps: int):

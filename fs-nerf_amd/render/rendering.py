@@ -95,11 +95,36 @@ class _CompositeFn(torch.autograd.Function):
         return ds.reshape(sig.shape), dr.reshape(rgb.shape), None, None, None, None, None
 
 
+class _CompositeFullFn(torch.autograd.Function):
+    """Volume integration with gradients to sigmas and rgbs through ALL six outputs (`rendering(full_grad=True)`):
+    colors, opacity, depth and the per-sample weights / alphas / trans.  A cotangent nothing asked for arrives as None
+    and reaches the kernel as a NULL pointer (fsn_composite_packed_bwd_full)."""
+
+    @staticmethod
+    def forward(ctx, sigmas, rgbs, t_starts, t_ends, ray_indices, n_rays, bkgd):
+        colors, opacity, depth, ex = ops.composite_packed(sigmas, rgbs, t_starts, t_ends, ray_indices, n_rays, bkgd)
+        ctx.save_for_backward(ex["sigmas"], ex["rgbs"], t_starts, t_ends, ray_indices, opacity, depth)
+        ctx.n_rays, ctx.bkgd = n_rays, bkgd
+        ctx.set_materialize_grads(False)
+        return colors, opacity, depth, ex["weights"], ex["alphas"], ex["trans"]
+
+    @staticmethod
+    def backward(ctx, d_colors, d_opacity, d_depth, d_weights, d_alphas, d_trans):
+        sig, rgb, t0, t1, ri, opacity, depth = ctx.saved_tensors
+        ds, dr = ops.composite_packed_bwd_full(sig, rgb, t0, t1, ri, ctx.n_rays, ctx.bkgd, d_colors, d_opacity,
+                                               opacity=opacity, depth=depth, d_depth=d_depth, d_weights=d_weights,
+                                               d_alphas=d_alphas, d_trans=d_trans)
+        return ds.reshape(sig.shape), dr.reshape(rgb.shape), None, None, None, None, None
+
+
 def rendering(t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor, n_rays: int,
-              rgb_sigma_fn: Callable, render_bkgd: Optional[Tensor] = None):
+              rgb_sigma_fn: Callable, render_bkgd: Optional[Tensor] = None, full_grad: bool = False):
     """nerfacc.volrend.rendering's contract: -> (colors [n_rays,3], opacities [n_rays,1],
     depths [n_rays,1], extras).  AssertionError on the same shape violations.  Differentiable with
-    respect to the rgbs / sigmas returned by `rgb_sigma_fn` (depth carries no gradient)."""
+    respect to the rgbs / sigmas returned by `rgb_sigma_fn`: through colors and opacities by default (the lean
+    backward of the timed training step; depth and the extras are detached), through EVERY output - depths and
+    extras["weights" | "alphas" | "trans"] as well, as nerfacc's are - with `full_grad=True` (depth supervision,
+    distortion / entropy losses on the weights, opacity priors).  No gradient goes to t_starts / t_ends."""
     rgbs, sigmas = rgb_sigma_fn(t_starts, t_ends, ray_indices)
     assert rgbs.shape[-1] == 3, "rgbs must have 3 channels, got {}".format(rgbs.shape)
     assert sigmas.shape == t_starts.shape, "sigmas must have shape of (N,)! Got {}".format(sigmas.shape)
@@ -110,8 +135,8 @@ def rendering(t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor, n_rays: int
     kernel_bk = None if bk_grad else render_bkgd
     if torch.is_grad_enabled() and (rgbs.requires_grad or sigmas.requires_grad):
         bk = None if kernel_bk is None else [float(v) for v in kernel_bk.detach().cpu().tolist()]
-        colors, opacity, depth, w, a, tr = _CompositeFn.apply(sigmas, rgbs.contiguous(), t_starts, t_ends,
-                                                             ray_indices, n_rays, bk)
+        fn = _CompositeFullFn if full_grad else _CompositeFn
+        colors, opacity, depth, w, a, tr = fn.apply(sigmas, rgbs.contiguous(), t_starts, t_ends, ray_indices, n_rays, bk)
         ex = {"weights": w, "alphas": a, "trans": tr, "sigmas": sigmas, "rgbs": rgbs}
     else:
         colors, opacity, depth, ex = ops.composite_packed(sigmas, rgbs, t_starts, t_ends, ray_indices, n_rays, kernel_bk)
@@ -295,8 +320,9 @@ def _estimator_sampling(rays_o, rays_d, estimator, model, train, render_step_siz
                               near_plane=0.0, far_plane=1e10, **jitter)
 
 
-def _render_samples(samples, rays_o, rays_d, fine, train, white_bkgd, needs_grad, device):
-    """The sampler routes' common tail: the fine network's full pass on the packed samples -> `rendering`."""
+def _render_samples(samples, rays_o, rays_d, fine, train, white_bkgd, needs_grad, device, full_grad=False):
+    """The sampler routes' common tail: the fine network's full pass on the packed samples -> `rendering`.  With
+    `full_grad` the extras also carry the packed interval edges ("t_starts", "t_ends")."""
     ray_indices, t_starts, t_ends = samples
 
     def rgb_sigma_fn(t_starts, t_ends, ray_indices):
@@ -319,7 +345,9 @@ def _render_samples(samples, rays_o, rays_d, fine, train, white_bkgd, needs_grad
         render_bkgd = torch.full((3,), float(white_bkgd))
     try:
         output = rendering(t_starts, t_ends, ray_indices, n_rays=len(rays_o), rgb_sigma_fn=rgb_sigma_fn,
-                           render_bkgd=render_bkgd)
+                           render_bkgd=render_bkgd, full_grad=full_grad)
+        if full_grad:  # render_rays returns the midpoints only; a distortion loss needs the widths
+            output[3].update(t_starts=t_starts, t_ends=t_ends)
     except AssertionError:  # same fallback as the reference (rendering.py:97-103)
         output = (torch.ones_like(rays_o) * white_bkgd, None,
                   torch.zeros_like(rays_o[:, 0].unsqueeze(1), dtype=torch.float32), None)
@@ -380,10 +408,14 @@ _SAMPLERS = {"stratified-sampler": _stratified_sampler, "occ-sampler": _occ_samp
 def render_rays(rays_o: Tensor, rays_d: Tensor, estimator, model: nn.Module, train: bool = False,
                 white_bkgd: bool = False, render_step_size: float = 5e-3,
                 device: torch.device = torch.device("cuda"), *, model_fine: Optional[nn.Module] = None,
-                u: Optional[Tensor] = None, u_fine: Optional[Tensor] = None, want_extras: bool = True):
+                u: Optional[Tensor] = None, u_fine: Optional[Tensor] = None, want_extras: bool = True,
+                full_grad: bool = False):
     """See module docstring.  Keyword-only extras over the reference: `model_fine` (second network
     of the hierarchical pass; default = `model`, as the reference uses one network for both of
-    its passes), explicit jitter tensors `u` / `u_fine`, `want_extras`."""
+    its passes), explicit jitter tensors `u` / `u_fine`, `want_extras`, and `full_grad`: a training call whose depth,
+    opacity and extras["weights" | "alphas" | "trans"] all carry gradients to the model (`rendering(full_grad=True)`;
+    the default differentiates through rgb and opacity only), with the packed interval edges as extras["t_starts"] /
+    extras["t_ends"].  It is ignored on the forward-only one-launch routes, which have no gradients."""
     rays_o = rays_o.to(device)
     rays_d = rays_d.to(device)
     fine = model_fine if model_fine is not None else model
@@ -394,7 +426,7 @@ def render_rays(rays_o: Tensor, rays_d: Tensor, estimator, model: nn.Module, tra
         return _ONE_LAUNCH[route](rays_o, rays_d, None, estimator, model, model_fine, train, float(white_bkgd),
                                   render_step_size, u, u_fine, want_extras)
     samples = _SAMPLERS[route](rays_o, rays_d, estimator, model, train, render_step_size, u, u_fine, needs_grad)
-    return _render_samples(samples, rays_o, rays_d, fine, train, white_bkgd, needs_grad, device)
+    return _render_samples(samples, rays_o, rays_d, fine, train, white_bkgd, needs_grad, device, full_grad)
 
 
 # A frame under the deferred range check is rendered at most this many times: every repeat follows a re-calibration (at

@@ -433,11 +433,40 @@ int fsn_nerf_train_bwd(const fsn_mlp_desc* desc, int prec, const float* const* w
  * are the launch's reduction words). */
 int fsn_grad_scale(const float* d_out, int64_t n, float* buf, fsn_stream_t stream);
 /* backward of fsn_composite_packed_fwd with respect to sigmas and rgbs, given dL/dcolors [R,3] and
- * (optional) dL/dopacity [R]; dL/ddepth is not propagated. */
+ * (optional) dL/dopacity [R]; dL/ddepth is not propagated (the lean backward of the default training step;
+ * fsn_composite_packed_bwd_full propagates every output's cotangent). */
 int fsn_composite_packed_bwd(const float* sigmas, const float* rgbs, const float* t_starts, const float* t_ends,
                              const int64_t* ray_indices, int64_t N, int64_t R, const float* bkgd_host,
                              const float* d_colors, const float* d_opacity, float* d_sigmas, float* d_rgbs,
                              fsn_stream_t stream);
+/* The FULL backward of fsn_composite_packed_fwd: every output carries a cotangent.  Arguments of
+ * fsn_composite_packed_bwd plus, all DEVICE pointers:
+ *   opacity, depth [R]                 the forward's outputs; required when d_depth is given
+ *   d_depth [R]                        optional dL/ddepth
+ *   d_weights, d_alphas, d_trans [N]   optional dL/dweights, dL/dalphas, dL/dtrans
+ * Any optional pointer may be NULL, and here d_colors as well (that term is absent; nothing is loaded through it: a
+ * loss on depth alone has no colour cotangent).  With only d_colors /
+ * d_opacity given the results equal fsn_composite_packed_bwd's bit for bit.  The depth term follows
+ * depth = sum w m / max(opacity, eps): d depth / d w_i = (m_i - depth) / opacity for opacity >= eps, m_i / eps below.
+ * No gradient goes to t_starts / t_ends.  One wave per ray, no atomics: deterministic. */
+int fsn_composite_packed_bwd_full(const float* sigmas, const float* rgbs, const float* t_starts, const float* t_ends,
+                                  const int64_t* ray_indices, int64_t N, int64_t R, const float* bkgd_host,
+                                  const float* d_colors, const float* d_opacity, const float* opacity,
+                                  const float* depth, const float* d_depth, const float* d_weights,
+                                  const float* d_alphas, const float* d_trans, float* d_sigmas, float* d_rgbs,
+                                  fsn_stream_t stream);
+
+/* Distortion loss of the compositor's weights (mip-NeRF 360, interval form; this package's own definition), per ray:
+ *   out[r] = sum_i [ 2 w_i (m_i W_i - V_i) + w_i^2 dt_i / 3 ],  W_i = sum_{j<i} w_j,  V_i = sum_{j<i} w_j m_j,
+ * m = (t_starts + t_ends)/2, dt = t_ends - t_starts, samples of a ray contiguous and sorted (ray_indices int64 [N]
+ * non-decreasing).  out [n_rays]; a ray without samples gives 0 (N == 0: out, when given, is zeroed).  One wave per
+ * ray, two scans, no atomics: deterministic. */
+int fsn_distortion_fwd(const float* weights, const float* t_starts, const float* t_ends, const int64_t* ray_indices,
+                       int64_t N, int64_t n_rays, float* out, fsn_stream_t stream);
+/* backward of fsn_distortion_fwd w.r.t. weights: d_weights[k] = d_out[ray of k] *
+ *   ( 2 (m_k W_k - V_k + V'_k - m_k W'_k) + 2 w_k dt_k / 3 ),  W'_k / V'_k the sums over j > k.  d_out [n_rays]. */
+int fsn_distortion_bwd(const float* weights, const float* t_starts, const float* t_ends, const int64_t* ray_indices,
+                       int64_t N, int64_t n_rays, const float* d_out, float* d_weights, fsn_stream_t stream);
 
 /* f1: optimizer side of the training step on ONE flat float32 parameter arena (run-nerf.py:217, 266-285).
  * fsn_adam_step: torch.optim.Adam's update (no amsgrad), operation for operation in float32, one launch over the
