@@ -5,7 +5,7 @@
 estimator.update_every_n_steps) and evaluated with render_frame + PSNR and SSIM (run-nerf.py:140-190).
 
     python examples/train_synthetic.py [--estimator occgrid|stratified] [--iters 400] [--hw 64] [--u8-dataset]
-                                       [--depth-weight W] [--distortion-weight W]
+                                       [--depth-weight W] [--distortion-weight W] [--cone-angle A] [--near-plane T]
 
 --u8-dataset: the teacher's frames become uint8 "photographs" (R.to8b) held in a device-resident RayDataset; the loop
 takes its batches from a RayLoader the way run-nerf.py:236-240 takes them from its DataLoader, and the held-out view
@@ -15,6 +15,10 @@ comes from a FrameLoader (fs_nerf_amd.nerfdata).
 renderer's other outputs through render_rays(full_grad=True) - an MSE between the rendered depth and the teacher's on
 the rays where the teacher hit something (float tables only: the uint8 photographs carry no depth), and the distortion
 loss of the compositor's weights (core.loss.DistortionLoss).
+
+--cone-angle / --near-plane (both 0 by default): `sampling_kwargs` of render_rays / render_frame / render_path - the
+occupancy march's step grows with distance, dt = max(t * cone_angle, step), and nothing is sampled in front of the near
+plane - in training, evaluation and the path render alike.
 """
 import argparse
 import math
@@ -73,7 +77,15 @@ def main():
                     help="opt-in: weight of a depth-supervision term against the teacher's depth (render_rays(full_grad=True))")
     ap.add_argument("--distortion-weight", type=float, default=0.0,
                     help="opt-in: weight of the distortion loss on the compositor's weights (render_rays(full_grad=True))")
+    ap.add_argument("--cone-angle", type=float, default=0.0,
+                    help="opt-in: the occupancy march's step grows with distance, dt = max(t * cone_angle, step) "
+                         "(sampling_kwargs of render_rays / render_frame; nerfacc uses 0.004 for unbounded scenes)")
+    ap.add_argument("--near-plane", type=float, default=0.0,
+                    help="opt-in: no samples in front of this distance (sampling_kwargs, any estimator)")
     a = ap.parse_args()
+    if a.cone_angle and a.estimator != "occgrid":
+        ap.error("--cone-angle belongs to the occupancy estimator")
+    sampling_kwargs = {k: v for k, v in (("cone_angle", a.cone_angle), ("near_plane", a.near_plane)) if v != 0.0} or None
     if a.depth_weight and a.u8_dataset:
         ap.error("--depth-weight needs the float tables: the uint8 dataset carries no depth")
     full_grad = a.depth_weight != 0.0 or a.distortion_weight != 0.0
@@ -137,7 +149,8 @@ def main():
             idx = torch.randint(0, ro.shape[0], (a.batch,), device=dev, generator=gen)
             rays_o, rays_d, rgb_gt = ro[idx], rd[idx], gt[idx]
         (rgb, _, depth, extras), ray_indices, _ = R.render_rays(rays_o, rays_d, estimator, model, train=True, white_bkgd=True,
-                                                                render_step_size=step, device=dev, full_grad=full_grad)
+                                                                render_step_size=step, device=dev, full_grad=full_grad,
+                                                                sampling_kwargs=sampling_kwargs)
         loss = torch.nn.functional.mse_loss(rgb, rgb_gt)
         if a.depth_weight and depth.requires_grad:  # (an all-background batch renders no samples: nothing to supervise)
             hit = (gd[idx] > near).float()  # render_frame clamps depth to [near, far]: `near` = the teacher saw background
@@ -161,15 +174,18 @@ def main():
     estimator.eval()
     with torch.no_grad():
         img, _ = R.render_frame(hwf, near, far, held_out, 1 << 20, estimator, model, white_bkgd=True,
-                                render_step_size=step, device=dev)
+                                render_step_size=step, device=dev, sampling_kwargs=sampling_kwargs)
         if a.u8_dataset:
             ref = next(iter(val_loader))[0][0]  # (rgb_gt [1,H,W,3], pose [1,4,4]) as evaluation() consumes them
         else:
             ref, _ = R.render_frame(hwf, near, far, held_out, 1 << 20, t_est, teacher, white_bkgd=True, device=dev)
+    # a short camera path (rendering.py:180-248), with the same sampling options
+    frames, _ = R.render_path(torch.stack([orbit_pose(phi) for phi in (10.0, 20.0)]), hwf, near, far, 1 << 20, model, estimator,
+                              white_bkgd=True, render_step_size=step, device=dev, sampling_kwargs=sampling_kwargs)
     psnr = float(metrics.psnr(img, ref))  # run-nerf.py:157-160
     ssim = float(metrics.ssim(img, ref, channel_axis=-1, data_range=1.0, gaussian_weights=True))  # run-nerf.py:180-189
     print(f"{a.iters} iterations of {a.batch} rays in {dt:.1f} s ({a.iters * a.batch / dt:,.0f} rays/s); held-out view PSNR "
-          f"{psnr:.2f} dB, SSIM {ssim:.4f}; frame as uint8: {tuple(R.to8b(img).shape)}")
+          f"{psnr:.2f} dB, SSIM {ssim:.4f}; frame as uint8: {tuple(R.to8b(img).shape)}; path frames {frames.shape}")
 
 
 if __name__ == "__main__":

@@ -106,6 +106,9 @@ SIGNATURES = {
     "fsn_occ_gather_samples": (_i, [_vp, _vp, _vp, _i, _i64, _f, _vp, _vp, _vp, _vp]),
     "fsn_occ_gather_extras": (_i, [_vp, _vp, _vp, _i, _i64, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fsn_occgrid_march": (_i, [_vp, _vp, _i64, _vp, _i, _i, _vp, _f, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fsn_occgrid_march_ex": (_i, [_vp, _vp, _i64, _vp, _i, _i, _vp, _f, _f, _f, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp,
+                                  _vp]),
+    "fsn_ray_aabb_intersect": (_i, [_vp, _vp, _i64, _vp, _i, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "fsn_packed_visibility": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _f, _f, _vp, _vp]),
     "fsn_occgrid_update": (_i, [_vp, _i64, _vp, _vp, _i64, _f, _vp, _vp, _vp]),
     "fsn_occgrid_select": (_i, [_vp, _i, _i, _i, _vp, _i, _i64, _i64, C.c_uint64, _vp, _vp, _vp, _vp]),

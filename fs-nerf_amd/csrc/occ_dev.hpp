@@ -117,6 +117,56 @@ __device__ __forceinline__ int march_ray(const GridDev& G, const uint32_t* __res
   return total;
 }
 
+// Per-ray bounds (fsn_occgrid_march_ex): t_lo = max(t_enter, near_r, t_min_r), t_hi = min(t_exit, far_plane, t_max_r),
+// in that order; the lattice itself (near_r, step) is ray_lattice's.  +-inf bounds are allowed; t_max_r <= t_min_r
+// leaves no samples.
+__device__ __forceinline__ RayLattice ray_lattice_bounded(const GridDev& G, const float (&o)[3], const float (&d)[3],
+                                                          float near_plane, float far_plane, float step, bool has_u,
+                                                          float u_r, float t_min_r, float t_max_r) {
+  RayLattice L = ray_lattice(G, o, d, near_plane, far_plane, step, has_u, u_r);
+  L.t_lo = fmaxf(L.t_lo, t_min_r);
+  L.t_hi = fminf(L.t_hi, t_max_r);
+  L.any = L.any && L.t_hi > L.t_lo;  // (tightening never revives a ray that missed)
+  int k0 = L.any ? (int)ceilf((L.t_lo - L.near_r) / step) : 0;
+  L.k0 = k0 < 0 ? 0 : k0;
+  return L;
+}
+
+// Cone regime (cone_angle > 0, near_plane >= 0): the step grows with distance, dt(t) = max(t cone_angle, step), in
+// blocks of 64 intervals of ONE width, so that the block recurrence is wave-uniform and every lane's interval follows
+// from the block start with one multiply and one add:
+//   t_0 = t_lo + (u ? u_r dt(t_lo) : 0);  block b: dt_b = dt(t_b), ts_j = t_b + j dt_b, te_j = t_b + (j + 1) dt_b,
+//   t_{b+1} = t_b + 64 dt_b (= te_63); interval j of block b is a sample iff 64 b + j < max_steps, ts_j < t_hi and
+//   the cell of its midpoint is occupied; the march ends after the block with !(t_{b+1} < t_hi).
+// te_j is bitwise ts_{j+1}: consecutive samples of a ray in a full grid are contiguous.  `L`: the (bounded) range of
+// the ray with near_r = near_plane (no lattice shift: u moves the first block's start).  Same sink as march_ray.
+template <class Sink>
+__device__ __forceinline__ int march_ray_cone(const GridDev& G, const uint32_t* __restrict__ bits, const float (&o)[3],
+                                              const float (&d)[3], const RayLattice& L, float step, float cone_angle,
+                                              bool has_u, float u_r, int32_t max_steps, Sink&& sink) {
+  const int lane = (int)(threadIdx.x & 63);
+  int total = 0;
+  if (!L.any) return 0;
+  float tb = has_u ? L.t_lo + u_r * fmaxf(L.t_lo * cone_angle, step) : L.t_lo;
+  for (int it = 0; it < max_steps; it += 64) {
+    const float dtb = fmaxf(tb * cone_angle, step);
+    const float ts = tb + (float)lane * dtb;
+    const float te = tb + (float)(lane + 1) * dtb;
+    const bool in_range = (it + lane) < max_steps && ts < L.t_hi;
+    bool keep = false;
+    if (in_range) {
+      const float tm = (ts + te) / 2.0f;
+      keep = grid_occupied(G, bits, o[0] + d[0] * tm, o[1] + d[1] * tm, o[2] + d[2] * tm);
+    }
+    const uint64_t m = __ballot(keep);
+    sink(ts, te, keep, m, total);
+    total += __popcll(m);
+    tb = tb + 64.0f * dtb;  // wave-uniform and exact: every lane computes the same value
+    if (!(tb < L.t_hi)) break;
+  }
+  return total;
+}
+
 // ---------------------------------------------------------------- update_every_n_steps: one draw of the cell selection
 // Shared by k_occ_select (occgrid.hip) and the fused refresh (occ_refresh.hip): ONE definition, so that both produce the
 // same cell and the same point bit for bit.  The rule is stated at k_occ_select.

@@ -11,6 +11,9 @@
 //    min(t_exit, far_plane)) of the outermost box and the cell of its MIDPOINT, at the finest level containing
 //    the midpoint, is occupied.  One wavefront per ray, 64 lattice points per iteration, ballot + popcount
 //    ranks; two passes (count, fill) around an exclusive scan of the counts.
+//  * march_ex: the same march inside per-ray bounds [t_min_r, t_max_r], and the cone regime (cone_angle > 0): the step
+//    grows with distance, dt = max(t cone_angle, step), taken once per block of 64 intervals (occ_dev.hpp,
+//    march_ray_cone; include/fsnerf_hip.h has the definition, tests/occ_cone_ref.py restates it).
 //  * visibility: T_i = exp(-sum_{j<i} sigma_j dt_j) per ray (prefix scan), keep iff T_i >= early_stop_eps and
 //    alpha_i >= alpha_thre.
 //  * update: occs[c] = max(occs[c]*decay, occ_c) for the evaluated cells; bit = occs > threshold.
@@ -43,6 +46,69 @@ __global__ void k_occ_march(const float* __restrict__ rays_o, const float* __res
     }
   });
   if (!FILL && lane == 0) counts[r] = total;
+}
+
+// fsn_occgrid_march_ex: k_occ_march with per-ray bounds t_min / t_max (either may be null) and the cone regime
+// (cone_angle > 0: march_ray_cone; == 0: today's lattice inside the tightened range).  Same launch structure.
+template <bool FILL>
+__global__ void k_occ_march_ex(const float* __restrict__ rays_o, const float* __restrict__ rays_d, int64_t R, GridDev G,
+                               const uint32_t* __restrict__ bits, float near_plane, float far_plane, float step,
+                               const float* __restrict__ u, int32_t max_steps, const float* __restrict__ t_min,
+                               const float* __restrict__ t_max, float cone_angle, int64_t* __restrict__ counts,
+                               const int64_t* __restrict__ offsets, int64_t* __restrict__ ray_indices,
+                               float* __restrict__ t_starts, float* __restrict__ t_ends) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + wave;
+  if (r >= R) return;
+  const float o[3] = {rays_o[3 * r], rays_o[3 * r + 1], rays_o[3 * r + 2]};
+  const float d[3] = {rays_d[3 * r], rays_d[3 * r + 1], rays_d[3 * r + 2]};
+  const bool cone = cone_angle > 0.0f;
+  const float u_r = u ? u[r] : 0.f;
+  const float lo_r = t_min ? t_min[r] : -__builtin_huge_valf(), hi_r = t_max ? t_max[r] : __builtin_huge_valf();
+  const RayLattice L = ray_lattice_bounded(G, o, d, near_plane, far_plane, step, !cone && u != nullptr, u_r, lo_r, hi_r);
+  const int64_t base_out = FILL ? offsets[r] : 0;
+  auto sink = [&](float ts, float te, bool keep, uint64_t m, int before) {
+    if (FILL && keep) {
+      const int64_t pos = base_out + before + __popcll(m & ((1ull << lane) - 1ull));
+      ray_indices[pos] = r;
+      t_starts[pos] = ts;
+      t_ends[pos] = te;
+    }
+  };
+  const int total = cone ? march_ray_cone(G, bits, o, d, L, step, cone_angle, u != nullptr, u_r, max_steps, sink)
+                         : march_ray(G, bits, o, d, L, step, max_steps, sink);
+  if (!FILL && lane == 0) counts[r] = total;
+}
+
+// ray_aabb_intersect: one thread per (ray, box); the slab arithmetic is ray_lattice's (division form; a zero direction
+// component tests the origin against the slab).  hit = !miss && min(t_exit, far) > max(t_enter, near); a hit writes
+// those two clipped values, a miss writes miss_value twice.
+__global__ void k_ray_aabb(const float* __restrict__ rays_o, const float* __restrict__ rays_d, int64_t R,
+                           const float* __restrict__ aabbs, int32_t M, float near_plane, float far_plane,
+                           float miss_value, float* __restrict__ t_mins, float* __restrict__ t_maxs,
+                           uint8_t* __restrict__ hits) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= R * M) return;
+  const int64_t r = i / M;
+  const float* box = aabbs + 6 * (i - r * M);
+  float tmin = -__builtin_huge_valf(), tmax = __builtin_huge_valf();
+  bool miss = false;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float lo = box[a], hi = box[3 + a], oa = rays_o[3 * r + a], da = rays_d[3 * r + a];
+    if (da == 0.0f) {
+      miss = miss || oa < lo || oa > hi;
+    } else {
+      const float ta = (lo - oa) / da, tb = (hi - oa) / da;
+      tmin = fmaxf(tmin, fminf(ta, tb));
+      tmax = fminf(tmax, fmaxf(ta, tb));
+    }
+  }
+  const float t0 = fmaxf(tmin, near_plane), t1 = fminf(tmax, far_plane);
+  const bool hit = !miss && t1 > t0;
+  t_mins[i] = hit ? t0 : miss_value;
+  t_maxs[i] = hit ? t1 : miss_value;
+  hits[i] = hit ? 1 : 0;
 }
 
 // keep[i] = T_i >= eps && alpha_i >= alpha_thre, packed samples sorted by ray
@@ -194,6 +260,49 @@ extern "C" int fsn_occgrid_march(const float* rays_o, const float* rays_d, int64
                                                             max_steps, counts, nullptr, nullptr, nullptr, nullptr);
   }
   FSN_LAUNCH_CHECK("k_occ_march");
+  return FSN_OK;
+}
+
+extern "C" int fsn_occgrid_march_ex(const float* rays_o, const float* rays_d, int64_t R, const float* aabb_host, int res,
+                                    int levels, const uint32_t* bits, float near_plane, float far_plane, float step,
+                                    const float* u, int max_steps, const float* t_min, const float* t_max,
+                                    float cone_angle, int64_t* counts, const int64_t* offsets, int64_t* ray_indices,
+                                    float* t_starts, float* t_ends, fsn_stream_t stream) {
+  GridDev G;
+  const int rc = make_grid(aabb_host, res, levels, G);
+  if (rc != FSN_OK) return rc;
+  FSN_REQUIRE(R >= 0 && step > 0.f && max_steps > 0, FSN_E_INVALID, "fsn_occgrid_march_ex: bad arguments");
+  FSN_REQUIRE(cone_angle >= 0.f, FSN_E_INVALID, "fsn_occgrid_march_ex: cone_angle must not be negative");
+  FSN_REQUIRE(!(cone_angle > 0.f && near_plane < 0.f), FSN_E_INVALID,
+              "fsn_occgrid_march_ex: the cone regime needs near_plane >= 0");
+  if (R == 0) return FSN_OK;
+  FSN_REQUIRE(rays_o && rays_d && bits, FSN_E_INVALID, "fsn_occgrid_march_ex: null pointer");
+  const unsigned grid = (unsigned)((R + 3) / 4);
+  if (offsets) {
+    FSN_REQUIRE(ray_indices && t_starts && t_ends, FSN_E_INVALID, "fsn_occgrid_march_ex: fill pass needs the outputs");
+    k_occ_march_ex<true><<<grid, 256, 0, as_stream(stream)>>>(rays_o, rays_d, R, G, bits, near_plane, far_plane, step, u,
+                                                              max_steps, t_min, t_max, cone_angle, nullptr, offsets,
+                                                              ray_indices, t_starts, t_ends);
+  } else {
+    FSN_REQUIRE(counts, FSN_E_INVALID, "fsn_occgrid_march_ex: count pass needs `counts`");
+    k_occ_march_ex<false><<<grid, 256, 0, as_stream(stream)>>>(rays_o, rays_d, R, G, bits, near_plane, far_plane, step, u,
+                                                               max_steps, t_min, t_max, cone_angle, counts, nullptr,
+                                                               nullptr, nullptr, nullptr);
+  }
+  FSN_LAUNCH_CHECK("k_occ_march_ex");
+  return FSN_OK;
+}
+
+extern "C" int fsn_ray_aabb_intersect(const float* rays_o, const float* rays_d, int64_t R, const float* aabbs, int M,
+                                      float near_plane, float far_plane, float miss_value, float* t_mins, float* t_maxs,
+                                      uint8_t* hits, fsn_stream_t stream) {
+  FSN_REQUIRE(R >= 0 && M >= 0 && R * (int64_t)M < (1ll << 40), FSN_E_INVALID, "fsn_ray_aabb_intersect: bad sizes");
+  if (R == 0 || M == 0) return FSN_OK;
+  FSN_REQUIRE(rays_o && rays_d && aabbs && t_mins && t_maxs && hits, FSN_E_INVALID, "fsn_ray_aabb_intersect: null pointer");
+  const int64_t n = R * (int64_t)M;
+  k_ray_aabb<<<(unsigned)((n + 255) / 256), 256, 0, as_stream(stream)>>>(rays_o, rays_d, R, aabbs, M, near_plane,
+                                                                         far_plane, miss_value, t_mins, t_maxs, hits);
+  FSN_LAUNCH_CHECK("k_ray_aabb");
   return FSN_OK;
 }
 

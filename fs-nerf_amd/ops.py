@@ -4,6 +4,7 @@ No function in this module computes anything on the CPU."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -853,20 +854,31 @@ def distortion(weights: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indices: T
 
 # ------------------------------------------------------------------ occupancy-grid sampler
 def occgrid_march(rays_o: Tensor, rays_d: Tensor, aabb: Sequence[float], res: int, levels: int, bits: Tensor,
-                  near_plane: float, far_plane: float, step: float, u: Optional[Tensor], max_steps: int):
+                  near_plane: float, far_plane: float, step: float, u: Optional[Tensor], max_steps: int,
+                  t_min: Optional[Tensor] = None, t_max: Optional[Tensor] = None, cone_angle: float = 0.0):
     """Lattice march through the occupancy grid -> (ray_indices int64 [N], t_starts [N], t_ends [N], counts [R]).
-    Two launches around an exclusive scan of the per-ray counts; one host sync for N (as nerfacc's does)."""
+    Two launches around an exclusive scan of the per-ray counts; one host sync for N (as nerfacc's does).
+    Per-ray bounds `t_min` / `t_max` [R] or a `cone_angle` > 0 (the step grows with distance) take the extended entry
+    point fsn_occgrid_march_ex (include/fsnerf_hip.h has the definition); without them the call is fsn_occgrid_march."""
     o, d = _f32(rays_o, "rays_o").reshape(-1, 3), _f32(rays_d, "rays_d").reshape(-1, 3)
     R = o.shape[0]
     ab = (C.c_float * 6)(*[float(v) for v in aabb])
     u_ = None if u is None else _f32(u, "u").reshape(-1)
     if u_ is not None and u_.numel() != R:
         raise ValueError("u must hold one value per ray")
-    counts = torch.zeros(R, device=o.device, dtype=torch.int64)
     args = (_p(o), _p(d), R, ab, int(res), int(levels), _p(bits), float(near_plane), float(far_plane), float(step), _p(u_),
             int(max_steps))
+    name = "fsn_occgrid_march"
+    if t_min is not None or t_max is not None or cone_angle != 0.0:
+        bounds = [None if t is None else _f32(t, k).reshape(-1) for t, k in ((t_min, "t_min"), (t_max, "t_max"))]
+        if any(t is not None and t.numel() != R for t in bounds):
+            raise ValueError("t_min / t_max must hold one value per ray")
+        args += (_p(bounds[0]), _p(bounds[1]), float(cone_angle))
+        name = "fsn_occgrid_march_ex"
+    counts = torch.zeros(R, device=o.device, dtype=torch.int64)
     with torch.cuda.device(o.device):
-        L.check(L.lib().fsn_occgrid_march(*args, _p(counts), None, None, None, None, _stream()), "fsn_occgrid_march")
+        march = getattr(L.lib(), name)
+        L.check(march(*args, _p(counts), None, None, None, None, _stream()), name)
         ends = torch.cumsum(counts, 0)
         offsets = (ends - counts).contiguous()
         N = int(ends[-1].item()) if R > 0 else 0
@@ -874,8 +886,25 @@ def occgrid_march(rays_o: Tensor, rays_d: Tensor, aabb: Sequence[float], res: in
         t0 = torch.empty(N, device=o.device, dtype=torch.float32)
         t1 = torch.empty(N, device=o.device, dtype=torch.float32)
         if N > 0:
-            L.check(L.lib().fsn_occgrid_march(*args, None, _p(offsets), _p(ri), _p(t0), _p(t1), _stream()), "fsn_occgrid_march")
+            L.check(march(*args, None, _p(offsets), _p(ri), _p(t0), _p(t1), _stream()), name)
     return ri, t0, t1, counts
+
+
+def ray_aabb_intersect(rays_o: Tensor, rays_d: Tensor, aabbs: Tensor, near_plane: float = -math.inf,
+                       far_plane: float = math.inf, miss_value: float = math.inf):
+    """Rays [R,3] against boxes [M,6] -> (t_mins [R,M], t_maxs [R,M], hits bool [R,M]) (fsn_ray_aabb_intersect: the
+    march's slab test; a hit holds the range clipped to [near_plane, far_plane], a miss `miss_value` twice)."""
+    o, d = _f32(rays_o, "rays_o").reshape(-1, 3), _f32(rays_d, "rays_d").reshape(-1, 3)
+    boxes = _f32(torch.as_tensor(aabbs, dtype=torch.float32).to(o.device), "aabbs").reshape(-1, 6)
+    R, M = o.shape[0], boxes.shape[0]
+    t0 = torch.empty(R, M, device=o.device, dtype=torch.float32)
+    t1 = torch.empty(R, M, device=o.device, dtype=torch.float32)
+    hits = torch.empty(R, M, device=o.device, dtype=torch.uint8)
+    with torch.cuda.device(o.device):
+        L.check(L.lib().fsn_ray_aabb_intersect(_p(o), _p(d), R, _p(boxes), M, float(near_plane), float(far_plane),
+                                               float(miss_value), _p(t0), _p(t1), _p(hits), _stream()),
+                "fsn_ray_aabb_intersect")
+    return t0, t1, hits.bool()
 
 
 def occ_sample_fused(pm: PackedMLP, rays_o: Tensor, rays_d: Tensor, *, aabb: Sequence[float], res: int, levels: int, bits: Tensor,

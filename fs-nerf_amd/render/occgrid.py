@@ -1,7 +1,8 @@
 """Occupancy-grid estimator for the `estimator` slot of render_rays: the duck-typed interface
 the reference uses from nerfacc's OccGridEstimator — construction `OccGridEstimator(roi_aabb=, resolution=, levels=)`
 (src/run-nerf.py:96-98), `.sampling(rays_o, rays_d, sigma_fn=, render_step_size=, stratified=, near_plane=,
-far_plane=)` (src/render/rendering.py:66-74), `.update_every_n_steps(step=, occ_eval_fn=, occ_thre=)`
+far_plane=)` (src/render/rendering.py:66-74; nerfacc's `t_min=`, `t_max=`, `cone_angle=` and its `ray_aabb_intersect`
+helper as well), `.update_every_n_steps(step=, occ_eval_fn=, occ_thre=)`
 (src/run-nerf.py:293-295), nn.Module modes / `.to()`.  nerfacc itself is not part of the reference; the sampling
 rule is this build's definition of that contract (see csrc/occgrid.hip), on HIP kernels."""
 import math
@@ -12,6 +13,14 @@ from torch import Tensor, nn
 
 from .. import ops
 from ..core.models import OccEvalFn
+
+
+def ray_aabb_intersect(rays_o: Tensor, rays_d: Tensor, aabbs, near_plane: float = -math.inf, far_plane: float = math.inf,
+                       miss_value: float = math.inf):
+    """nerfacc's helper of the same name: rays [R,3] against boxes [M,6] {xmin, ymin, zmin, xmax, ymax, zmax} ->
+    (t_mins [R,M], t_maxs [R,M], hits bool [R,M]), with the march's own slab test - so `t_min` / `t_max` taken from the
+    grid's outermost box change nothing.  A miss holds `miss_value` twice."""
+    return ops.ray_aabb_intersect(rays_o, rays_d, aabbs, near_plane, far_plane, miss_value)
 
 
 class OccGridEstimator(nn.Module):
@@ -65,11 +74,20 @@ class OccGridEstimator(nn.Module):
         h = [(self.aabb[3 + a] - self.aabb[a]) / 2.0 * 2 ** lvl for a in range(3)]
         return [c[a] - h[a] for a in range(3)], [c[a] + h[a] for a in range(3)]
 
-    def max_steps(self, render_step_size: float) -> int:
-        """Lattice points a ray can have inside the outermost box (its diagonal / step, + 2)."""
+    def max_steps(self, render_step_size: float, cone_angle: float = 0.0, near_plane: float = 0.0) -> int:
+        """Lattice points a ray can have inside the outermost box (its diagonal / step, + 2).  With a `cone_angle` the
+        step grows with distance: the count is the block recurrence of the cone march (64 intervals of width
+        max(t cone_angle, step) per block) run from `near_plane` over the diagonal - a ray that enters later only takes
+        larger steps, so it needs no more blocks for the same length."""
         lo, hi = self.level_aabb(self.levels - 1)
         diag = math.sqrt(sum((hi[a] - lo[a]) ** 2 for a in range(3)))
-        return int(min(16384, math.ceil(diag / render_step_size) + 2))
+        if cone_angle == 0.0:
+            return int(min(16384, math.ceil(diag / render_step_size) + 2))
+        t, n = float(near_plane), 0
+        while t < near_plane + diag and n < 16384:
+            t += 64.0 * max(t * cone_angle, render_step_size)
+            n += 64
+        return n
 
     # -- reference surface ---------------------------------------------------------
     @torch.no_grad()
@@ -78,15 +96,21 @@ class OccGridEstimator(nn.Module):
                  t_min: Optional[Tensor] = None, t_max: Optional[Tensor] = None, render_step_size: float = 1e-3,
                  early_stop_eps: float = 1e-4, alpha_thre: float = 0.0, stratified: bool = False,
                  cone_angle: float = 0.0, u: Optional[Tensor] = None):
-        """-> (ray_indices int64 [N], t_starts [N], t_ends [N]), packed and sorted by ray."""
-        if alpha_fn is not None or t_min is not None or t_max is not None or cone_angle != 0.0:
-            raise NotImplementedError("alpha_fn / t_min / t_max / cone_angle are not used by the reference")
+        """-> (ray_indices int64 [N], t_starts [N], t_ends [N]), packed and sorted by ray.
+        `t_min` / `t_max` [n_rays] tighten each ray's range (e.g. from `ray_aabb_intersect`); `cone_angle` > 0 lets the
+        step grow with distance, dt = max(t cone_angle, render_step_size) (needs near_plane >= 0; the definition is in
+        include/fsnerf_hip.h at fsn_occgrid_march_ex).  `alpha_fn` is out of scope."""
+        if alpha_fn is not None:
+            raise NotImplementedError("alpha_fn is not supported: pass sigma_fn (DESIGN.md 9)")
+        if cone_angle < 0.0 or (cone_angle > 0.0 and near_plane < 0.0):
+            raise ValueError("cone_angle must not be negative, and a cone_angle > 0 needs near_plane >= 0")
         R = rays_o.shape[0]
         if u is None and stratified:
             u = torch.rand(R, device=rays_o.device, generator=self.generator)
-        max_steps = self.max_steps(render_step_size)
+        max_steps = self.max_steps(render_step_size, cone_angle, near_plane)
         ri, t0, t1, _ = ops.occgrid_march(rays_o, rays_d, self.aabb, self.resolution, self.levels, self.bits, near_plane,
-                                          far_plane, render_step_size, u, max_steps)
+                                          far_plane, render_step_size, u, max_steps, t_min=t_min, t_max=t_max,
+                                          cone_angle=cone_angle)
         if sigma_fn is not None and (early_stop_eps > 0.0 or alpha_thre > 0.0) and ri.numel() > 0:
             sig = sigma_fn(t0, t1, ri)
             keep = ops.packed_visibility(sig.reshape(-1), t0, t1, ri, R, early_stop_eps, alpha_thre)

@@ -49,9 +49,13 @@ class StratifiedEstimator(nn.Module):
     @torch.no_grad()
     def sampling(self, rays_o: Tensor, rays_d: Tensor, sigma_fn: Optional[Callable] = None,
                  render_step_size: float = 5e-3, stratified: bool = False, near_plane: float = 0.0,
-                 far_plane: float = 1e10, u: Optional[Tensor] = None, u_fine: Optional[Tensor] = None):
+                 far_plane: float = 1e10, u: Optional[Tensor] = None, u_fine: Optional[Tensor] = None,
+                 cone_angle: float = 0.0, t_min: Optional[Tensor] = None, t_max: Optional[Tensor] = None):
         """-> (ray_indices int64 [N], t_starts [N], t_ends [N]); N = n_rays*(n_samples+n_importance).
-        `render_step_size` is accepted for signature compatibility (the step is (far-near)/n_samples)."""
+        `render_step_size` is accepted for signature compatibility (the step is (far-near)/n_samples).  A fixed-count
+        sampler has no cone-angle steps and no per-ray bounds: `cone_angle` / `t_min` / `t_max` are a ValueError."""
+        if cone_angle != 0.0 or t_min is not None or t_max is not None:
+            raise ValueError("StratifiedEstimator: cone_angle / t_min / t_max belong to the occupancy estimator")
         R = rays_o.shape[0]
         near, far = self.bounds(near_plane, far_plane)
         if u is None and stratified:
@@ -204,34 +208,62 @@ def _launch_size(rays_o, camera):
     return rays_o.shape[0], rays_o.device
 
 
-def _stratified_args(estimator, net: NeRF, R: int, dev, u, u_fine, train: bool) -> dict:
+# `sampling_kwargs` of render_rays / render_frame / render_path: what the reference hard-codes in its estimator.sampling
+# call (rendering.py:66-74) plus the occupancy march's cone angle and per-ray bounds.  The four scalars are arguments of
+# every occupancy kernel, fused ones included; cone_angle and t_min / t_max exist in the standalone march only.
+_SAMPLING_DEFAULTS = dict(near_plane=0.0, far_plane=1e10, early_stop_eps=1e-4, alpha_thre=0.0)
+_SAMPLING_MARCH_ONLY = ("cone_angle", "t_min", "t_max")
+
+
+def _sampling_options(sampling_kwargs: Optional[dict], per_ray: bool = True) -> dict:
+    """A checked copy of `sampling_kwargs` ({} for None); an unknown key is a TypeError.  Frames (`per_ray=False`)
+    accept no per-ray t_min / t_max."""
+    opts = dict(sampling_kwargs or {})
+    allowed = tuple(_SAMPLING_DEFAULTS) + (_SAMPLING_MARCH_ONLY if per_ray else ("cone_angle",))
+    unknown = sorted(k for k in opts if k not in allowed)
+    if unknown:
+        raise TypeError(f"sampling_kwargs: unexpected key(s) {unknown}; accepted: {list(allowed)}")
+    return opts
+
+
+def _march_only(opts: Optional[dict]) -> bool:
+    """The options ask for what only the standalone march has: a cone angle or per-ray bounds."""
+    opts = opts or {}
+    return opts.get("cone_angle", 0.0) != 0.0 or opts.get("t_min") is not None or opts.get("t_max") is not None
+
+
+def _stratified_args(estimator, net: NeRF, R: int, dev, u, u_fine, train: bool, opts: Optional[dict] = None) -> dict:
     """The stratified estimator's launch arguments; a training call draws the jitter the caller did not pass (coarse,
-    then fine)."""
+    then fine).  Of the sampling options a fixed-count sampler knows the two planes (`bounds`)."""
+    opts = opts or {}
+    if any(k not in ("near_plane", "far_plane") for k in opts):
+        raise ValueError("StratifiedEstimator: sampling_kwargs may hold near_plane / far_plane only")
     if u is None and train:
         u = estimator.draw_u(R, dev)
     if u_fine is None and train and estimator.n_importance > 0:
         u_fine = torch.rand(R, estimator.n_importance, device=dev, generator=estimator.generator)
-    near, far = estimator.bounds()
+    near, far = estimator.bounds(opts.get("near_plane", 0.0), opts.get("far_plane", 1e10))
     return dict(near=near, far=far, n_samples=estimator.n_samples, n_importance=estimator.n_importance, u=u,
                 u_fine=u_fine, pos_mask=net._mask(net.pos_mask, dev), dir_mask=net._mask(net.dir_mask, dev))
 
 
-def _occ_args(estimator, model: NeRF, render_step_size: float, u, dev) -> dict:
+def _occ_args(estimator, model: NeRF, render_step_size: float, u, dev, opts: Optional[dict] = None) -> dict:
     """The reference's estimator.sampling call (rendering.py:66-74: near_plane 0, far_plane 1e10, early_stop_eps 1e-4,
-    alpha_thre 0) as the occupancy kernels' arguments; `u` = stratified jitter (one value per ray) or None."""
+    alpha_thre 0, unless `opts` moves them) as the occupancy kernels' arguments; `u` = stratified jitter (one value per
+    ray) or None."""
+    scalars = {k: float((opts or {}).get(k, v)) for k, v in _SAMPLING_DEFAULTS.items()}
     return dict(aabb=estimator.aabb, res=estimator.resolution, levels=estimator.levels, bits=estimator.bits,
-                near_plane=0.0, far_plane=1e10, step=render_step_size, max_steps=estimator.max_steps(render_step_size),
-                u=u, early_stop_eps=1e-4, alpha_thre=0.0, pos_mask=model._mask(model.pos_mask, dev),
-                dir_mask=model._mask(model.dir_mask, dev))
+                step=render_step_size, max_steps=estimator.max_steps(render_step_size), u=u,
+                pos_mask=model._mask(model.pos_mask, dev), dir_mask=model._mask(model.dir_mask, dev), **scalars)
 
 
 def _fused_launch(rays_o, rays_d, camera, estimator, model, model_fine, train, bk, render_step_size, u, u_fine,
-                  want_extras):
+                  want_extras, opts=None):
     """stratified-fused: ONE fused launch (ops.render_fused) for ray tensors or for a camera (rays generated in the
     launch), under the fp16 range guard -> render_rays' return."""
     fine = model_fine if model_fine is not None else model
     R, dev = _launch_size(rays_o, camera)
-    kw = _stratified_args(estimator, fine, R, dev, u, u_fine, train)
+    kw = _stratified_args(estimator, fine, R, dev, u, u_fine, train, opts)
     probe = _probe(estimator, rays_o, rays_d, camera)
     launch = lambda: ops.render_fused(model.packed(probe) if estimator.n_importance > 0 else None, fine.packed(probe),
                                       rays_o, rays_d, bkgd=(bk, bk, bk), want_extras=want_extras, camera=camera, **kw)
@@ -246,14 +278,14 @@ def _fused_launch(rays_o, rays_d, camera, estimator, model, model_fine, train, b
 
 
 def _fused_occ_launch(rays_o, rays_d, camera, estimator, model, model_fine, train, bk, render_step_size, u, u_fine,
-                      want_extras):
+                      want_extras, opts=None):
     """occ-frame / occ-extras: the reference's own render path (occupancy estimator in the slot, rendering.py:58-107)
     as ONE launch (ops.render_occ_fused: march -> density pass -> visibility -> full pass -> packed integration, no host
     sync) under the fp16 range guard -> render_rays' return.  The extras mode (the reference's FULL return contract
     without gradients) is that launch + one gather behind one host read."""
     R, dev = _launch_size(rays_o, camera)
     kw = _occ_args(estimator, model, render_step_size, torch.rand(R, device=dev, generator=estimator.generator)
-                   if train else None, dev)
+                   if train else None, dev, opts)
     probe = _probe(estimator, rays_o, rays_d, camera)
     launch = lambda: ops.render_occ_fused(model.packed(probe), rays_o, rays_d, bkgd=(bk, bk, bk), camera=camera,
                                           want_extras=want_extras, **kw)
@@ -281,24 +313,25 @@ def _sampler_launch(model: NeRF, needs_grad: bool, dev, probe, launch):
         return guarded_launch([model], dev, "the sampler's density pass", probe, lambda: launch(model.packed(probe)))
 
 
-def _stratified_sampler(rays_o, rays_d, estimator, model, train, render_step_size, u, u_fine, needs_grad):
+def _stratified_sampler(rays_o, rays_d, estimator, model, train, render_step_size, u, u_fine, needs_grad, opts=None):
     """The hierarchical sampler as ONE launch (ops.sample_fused) instead of stratified edges -> packed -> density pass
     -> weights -> resampling -> packed: same edges bit for bit."""
     dev = rays_o.device
-    kw = _stratified_args(estimator, model, rays_o.shape[0], dev, u, u_fine, train)
+    kw = _stratified_args(estimator, model, rays_o.shape[0], dev, u, u_fine, train, opts)
     edges = _sampler_launch(model, needs_grad, dev, _probe(estimator, rays_o, rays_d),
                             lambda pm, status=None: ops.sample_fused(pm, rays_o, rays_d, status=status, **kw))
     with torch.no_grad():
         return ops.edges_to_packed(edges)
 
 
-def _occ_sampler(rays_o, rays_d, estimator, model, train, render_step_size, u, u_fine, needs_grad):
+def _occ_sampler(rays_o, rays_d, estimator, model, train, render_step_size, u, u_fine, needs_grad, opts=None):
     """estimator.sampling(..., sigma_fn) of the reference's training step (rendering.py:66-74) as one launch + one
     gather (ops.occ_sample_fused): the same samples bit for bit as march -> density pass -> visibility -> compaction,
     one host read instead of two."""
     dev = rays_o.device
     kw = _occ_args(estimator, model, render_step_size, torch.rand(rays_o.shape[0], device=dev,
-                                                                  generator=estimator.generator) if train else None, dev)
+                                                                  generator=estimator.generator) if train else None, dev,
+                   opts)
     launch = lambda pm, status=None: ops.occ_sample_fused(pm, rays_o, rays_d, status=status, **kw)
     if model.cull_precision is not None:
         # opt-in (NeRF.cull_precision): the cull's density pass in single-pass bf16 - no range flags to guard
@@ -307,7 +340,7 @@ def _occ_sampler(rays_o, rays_d, estimator, model, train, render_step_size, u, u
     return _sampler_launch(model, needs_grad, dev, _probe(estimator, rays_o, rays_d), launch)
 
 
-def _estimator_sampling(rays_o, rays_d, estimator, model, train, render_step_size, u, u_fine, needs_grad):
+def _estimator_sampling(rays_o, rays_d, estimator, model, train, render_step_size, u, u_fine, needs_grad, opts=None):
     def sigma_fn(t_starts, t_ends, ray_indices):
         if isinstance(model, NeRF):  # same values, gathers and midpoints inside the launch (no [N,3] tensors)
             return model.forward_rays(rays_o, rays_d, ray_indices, t_starts, t_ends, full=False).squeeze(-1)
@@ -316,8 +349,9 @@ def _estimator_sampling(rays_o, rays_d, estimator, model, train, render_step_siz
         return model(x).squeeze(-1)
 
     jitter = {"u": u, "u_fine": u_fine} if isinstance(estimator, StratifiedEstimator) else {}
+    planes = {"near_plane": 0.0, "far_plane": 1e10, **(opts or {})}  # (None: the reference's own call)
     return estimator.sampling(rays_o, rays_d, sigma_fn=sigma_fn, render_step_size=render_step_size, stratified=train,
-                              near_plane=0.0, far_plane=1e10, **jitter)
+                              **planes, **jitter)
 
 
 def _render_samples(samples, rays_o, rays_d, fine, train, white_bkgd, needs_grad, device, full_grad=False):
@@ -378,8 +412,12 @@ def _stratified_fusable(estimator, model, fine) -> bool:
 
 
 def _rays_route(estimator, model, model_fine, needs_grad: bool, want_extras: bool, n_rays: int,
-                render_step_size: float) -> str:
-    """render_rays' launch route, from plain attribute tests (the FUSED_OCC_* switches are read at call time)."""
+                render_step_size: float, sampling_kwargs: Optional[dict] = None) -> str:
+    """render_rays' launch route, from plain attribute tests (the FUSED_OCC_* switches are read at call time).  The
+    scalar sampling options (planes, thresholds) are arguments of every route's kernels and choose nothing; a cone
+    angle or per-ray bounds exist in the standalone march only."""
+    if _march_only(sampling_kwargs):
+        return "estimator-sampling"
     # (NeRF.cull_precision, opt-in: the cull's density pass runs as its own launch in that mode - the occupancy sampler)
     own_cull = isinstance(model, NeRF) and model.cull_precision is not None
     if not needs_grad and not own_cull and _occ_fusable(estimator, model, model_fine, render_step_size):
@@ -409,23 +447,28 @@ def render_rays(rays_o: Tensor, rays_d: Tensor, estimator, model: nn.Module, tra
                 white_bkgd: bool = False, render_step_size: float = 5e-3,
                 device: torch.device = torch.device("cuda"), *, model_fine: Optional[nn.Module] = None,
                 u: Optional[Tensor] = None, u_fine: Optional[Tensor] = None, want_extras: bool = True,
-                full_grad: bool = False):
+                full_grad: bool = False, sampling_kwargs: Optional[dict] = None):
     """See module docstring.  Keyword-only extras over the reference: `model_fine` (second network
     of the hierarchical pass; default = `model`, as the reference uses one network for both of
     its passes), explicit jitter tensors `u` / `u_fine`, `want_extras`, and `full_grad`: a training call whose depth,
     opacity and extras["weights" | "alphas" | "trans"] all carry gradients to the model (`rendering(full_grad=True)`;
     the default differentiates through rgb and opacity only), with the packed interval edges as extras["t_starts"] /
-    extras["t_ends"].  It is ignored on the forward-only one-launch routes, which have no gradients."""
+    extras["t_ends"].  It is ignored on the forward-only one-launch routes, which have no gradients.
+    `sampling_kwargs`: options of the estimator's sampling call the reference hard-codes - `near_plane`, `far_plane`,
+    `early_stop_eps`, `alpha_thre` (every occupancy route takes them) - and of the occupancy march: `cone_angle`
+    (dt = max(t cone_angle, render_step_size)) and per-ray `t_min` / `t_max` [n_rays], which go through
+    `estimator.sampling`.  None is the reference's call; an unknown key is a TypeError."""
+    opts = _sampling_options(sampling_kwargs)
     rays_o = rays_o.to(device)
     rays_d = rays_d.to(device)
     fine = model_fine if model_fine is not None else model
     needs_grad = torch.is_grad_enabled() and isinstance(fine, nn.Module) and fine.training and \
         any(p.requires_grad for p in fine.parameters())
-    route = _rays_route(estimator, model, model_fine, needs_grad, want_extras, rays_o.shape[0], render_step_size)
+    route = _rays_route(estimator, model, model_fine, needs_grad, want_extras, rays_o.shape[0], render_step_size, opts)
     if route in _ONE_LAUNCH:
         return _ONE_LAUNCH[route](rays_o, rays_d, None, estimator, model, model_fine, train, float(white_bkgd),
-                                  render_step_size, u, u_fine, want_extras)
-    samples = _SAMPLERS[route](rays_o, rays_d, estimator, model, train, render_step_size, u, u_fine, needs_grad)
+                                  render_step_size, u, u_fine, want_extras, opts)
+    samples = _SAMPLERS[route](rays_o, rays_d, estimator, model, train, render_step_size, u, u_fine, needs_grad, opts)
     return _render_samples(samples, rays_o, rays_d, fine, train, white_bkgd, needs_grad, device, full_grad)
 
 
@@ -434,8 +477,11 @@ def render_rays(rays_o: Tensor, rays_d: Tensor, estimator, model: nn.Module, tra
 _FRAME_RERUNS = 6
 
 
-def _frame_route(estimator, model, model_fine, training: bool, ndc: bool, render_step_size: float) -> str:
-    """render_frame's launch route, from plain attribute tests."""
+def _frame_route(estimator, model, model_fine, training: bool, ndc: bool, render_step_size: float,
+                 sampling_kwargs: Optional[dict] = None) -> str:
+    """render_frame's launch route, from plain attribute tests (sampling options: as in _rays_route)."""
+    if _march_only(sampling_kwargs):
+        return "chunked"
     if not training and not ndc and _stratified_fusable(estimator, model, model_fine if model_fine is not None else model):
         # SURVEY 8f row f3: ONE persistent launch per frame - the rays are generated inside it from (pose, pixel
         # index), nothing per sample or per ray is kept in HBM besides the image, so `chunksize` (the reference's
@@ -449,7 +495,7 @@ def _frame_route(estimator, model, model_fine, training: bool, ndc: bool, render
 
 
 def _camera_frame(route, hwf, pose, chunksize, estimator, model, model_fine, training, train, ndc, white_bkgd,
-                  render_step_size, device):
+                  render_step_size, device, opts=None):
     """ONE launch with the rays generated inside it -> (rgb, depth, flagged).  The end-of-frame look gets no
     `events_before`: a range event the synchronous guard handled inside the launch leaves nothing to render again."""
     H, W, focal = hwf
@@ -459,13 +505,13 @@ def _camera_frame(route, hwf, pose, chunksize, estimator, model, model_fine, tra
     cam = (pose, H, W, focal, 0, H, dev)
     launch = _fused_launch if route == "camera-stratified" else _fused_occ_launch
     (rgb, _, depth, _), _, _ = launch(None, None, cam, estimator, model, model_fine, train, float(white_bkgd),
-                                      render_step_size, None, None, False)
+                                      render_step_size, None, None, False, opts)
     nets = _nerfs(model, model_fine if model_fine is not None else model)
     return rgb, depth, frame_flagged(nets, dev, probe=_probe(estimator, None, None, cam))
 
 
 def _chunked_frame(route, hwf, pose, chunksize, estimator, model, model_fine, training, train, ndc, white_bkgd,
-                   render_step_size, device):
+                   render_step_size, device, opts=None):
     """get_rays -> (ndc) -> render_rays per chunk -> (rgb, depth, flagged); no image when flagged: some chunk is invalid
     (this look, or an earlier chunk's flag consumed by the next chunk's poll)."""
     fine = model_fine if model_fine is not None else model
@@ -481,7 +527,7 @@ def _chunked_frame(route, hwf, pose, chunksize, estimator, model, model_fine, tr
     for co, cd in zip(U.get_chunks(rays_o, chunksize), U.get_chunks(rays_d, chunksize)):
         (rgb, _, d, _), *_ = render_rays(co, cd, estimator, model, train=train, white_bkgd=white_bkgd,
                                          render_step_size=render_step_size, device=device, model_fine=model_fine,
-                                         want_extras=False)
+                                         want_extras=False, sampling_kwargs=opts or None)
         img.append(rgb)
         depth.append(d)
     if img and frame_flagged(nets, img[0].device, events0, _probe(estimator, rays_o, rays_d)):
@@ -492,21 +538,23 @@ def _chunked_frame(route, hwf, pose, chunksize, estimator, model, model_fine, tr
 def render_frame(hwf: Tuple[int, int, float], near: float, far: float, pose: Tensor, chunksize: int, estimator,
                  model: nn.Module, train: bool = False, ndc: bool = False, white_bkgd: bool = False,
                  render_step_size: float = 5e-3, device: torch.device = torch.device("cuda"), *,
-                 model_fine: Optional[nn.Module] = None) -> Tuple[Tensor, Tensor]:
+                 model_fine: Optional[nn.Module] = None, sampling_kwargs: Optional[dict] = None) -> Tuple[Tensor, Tensor]:
     """One image: get_rays -> (ndc) -> chunks -> render_rays -> cat; depth clamped to [near, far]
     (rendering.py:146-177).  Deliberate difference: the reference passes `white_bkgd` positionally
     into render_rays' `train` slot (rendering.py:160-168), so its frames are always composited on
-    black; here `train` and `white_bkgd` go to the parameters they name."""
+    black; here `train` and `white_bkgd` go to the parameters they name.  `sampling_kwargs`: as render_rays', without
+    the per-ray t_min / t_max."""
+    opts = _sampling_options(sampling_kwargs, per_ray=False)
     H, W, _ = hwf
     fine = model_fine if model_fine is not None else model
     training = torch.is_grad_enabled() and isinstance(fine, nn.Module) and fine.training
     for _ in range(_FRAME_RERUNS):
         # deferred range check: one look per frame; a flagged frame is rendered again after the models' re-calibration
         # on the frame's OWN rays (or their switch to bf16x3), and the repeat is looked at as well
-        route = _frame_route(estimator, model, model_fine, training, ndc, render_step_size)
+        route = _frame_route(estimator, model, model_fine, training, ndc, render_step_size, opts)
         run = _chunked_frame if route == "chunked" else _camera_frame
         rgb, depth, flagged = run(route, hwf, pose, chunksize, estimator, model, model_fine, training, train, ndc,
-                                  white_bkgd, render_step_size, device)
+                                  white_bkgd, render_step_size, device, opts)
         if not flagged:
             break
     return rgb.reshape(H, W, 3), depth.clamp(near, far).reshape(H, W)
@@ -522,7 +570,7 @@ def to8b(x):
 def render_path(render_poses: Tensor, hwf: Tuple[int, int, float], near: float, far: float, chunksize: int,
                 model: nn.Module, estimator, ndc: bool = False, train: bool = False, white_bkgd: bool = False,
                 render_step_size: float = 5e-3, device: torch.device = torch.device("cuda"), *,
-                model_fine: Optional[nn.Module] = None):
+                model_fine: Optional[nn.Module] = None, sampling_kwargs: Optional[dict] = None):
     """One frame per pose under no_grad -> (frames [N,H,W,3], d_frames [N,H,W]) as numpy arrays, like the
     reference (rendering.py:180-248; no progress bar).  Each frame is get_rays + one fused launch per chunk."""
     H, W, _ = hwf
@@ -531,7 +579,7 @@ def render_path(render_poses: Tensor, hwf: Tuple[int, int, float], near: float, 
         with torch.no_grad():
             rgb, depth = render_frame(hwf, near, far, pose, chunksize, estimator, model, train=train, ndc=ndc,
                                       white_bkgd=white_bkgd, render_step_size=render_step_size, device=device,
-                                      model_fine=model_fine)
+                                      model_fine=model_fine, sampling_kwargs=sampling_kwargs)
         frames.append(rgb.reshape(H, W, 3).detach().cpu().numpy())
         d_frames.append(depth.reshape(H, W).detach().cpu().numpy())
     return np.stack(frames, 0), np.stack(d_frames, 0)

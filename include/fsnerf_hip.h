@@ -515,6 +515,32 @@ int fsn_occgrid_march(const float* rays_o, const float* rays_d, int64_t R, const
                       const uint32_t* bits, float near_plane, float far_plane, float step, const float* u,
                       int max_steps, int64_t* counts, const int64_t* offsets, int64_t* ray_indices, float* t_starts,
                       float* t_ends, fsn_stream_t stream);
+/* fsn_occgrid_march_ex: fsn_occgrid_march with per-ray bounds and a step that grows with distance (nerfacc's `t_min` /
+ * `t_max` / `cone_angle` keywords; nerfacc's source is absent, so this is the build's own definition, float32 with plain
+ * operations throughout - tests/occ_cone_ref.py restates it in NumPy, bit for bit).
+ *   bounds: t_min / t_max = DEVICE float [R] or NULL; t_lo = max(t_enter, near_r, t_min[r]), t_hi = min(t_exit,
+ *   far_plane, t_max[r]) (fmaxf / fminf in that order); +-inf allowed, t_max <= t_min: no samples.
+ *   cone_angle == 0: fsn_occgrid_march's lattice t_k = near_r + k*step (anchored at the near plane) inside [t_lo, t_hi).
+ *   cone_angle > 0 (needs near_plane >= 0; near_r = near_plane): dt(t) = fmaxf(t * cone_angle, step); the first block
+ *   starts at t_0 = t_lo + (u ? u[r] * dt(t_lo) : 0); block b holds 64 intervals of ONE width dt_b = dt(t_b):
+ *   ts_j = t_b + (float)j * dt_b, te_j = t_b + (float)(j+1) * dt_b (te_j is bitwise ts_{j+1}), t_{b+1} = t_b + 64 dt_b.
+ *   Interval j of block b is a sample iff 64 b + j < max_steps, ts_j < t_hi and the cell of its midpoint
+ *   (ts_j + te_j) / 2 (finest level containing it) is occupied; the march ends after the block with !(t_{b+1} < t_hi).
+ *   A sample is never wider than clamp(t * cone_angle, step, inf) at its own start, and at most 1 + 64 cone_angle
+ *   times narrower.  Passes, outputs and scan as fsn_occgrid_march.  FSN_E_INVALID: null pointers, step <= 0,
+ *   cone_angle < 0, cone_angle > 0 with near_plane < 0.
+ * fsn_ray_aabb_intersect: rays [R] against boxes aabbs (DEVICE float [M,6]: xmin ymin zmin xmax ymax zmax) with the
+ *   march's slab arithmetic (division form; a zero direction component tests the origin against the slab):
+ *   hit = !miss && min(t_exit, far_plane) > max(t_enter, near_plane); t_mins / t_maxs [R,M] hold those two clipped
+ *   values for a hit and miss_value for a miss; hits: uint8 [R,M]. */
+int fsn_occgrid_march_ex(const float* rays_o, const float* rays_d, int64_t R, const float* aabb_host, int res, int levels,
+                         const uint32_t* bits, float near_plane, float far_plane, float step, const float* u,
+                         int max_steps, const float* t_min, const float* t_max, float cone_angle, int64_t* counts,
+                         const int64_t* offsets, int64_t* ray_indices, float* t_starts, float* t_ends,
+                         fsn_stream_t stream);
+int fsn_ray_aabb_intersect(const float* rays_o, const float* rays_d, int64_t R, const float* aabbs, int M,
+                           float near_plane, float far_plane, float miss_value, float* t_mins, float* t_maxs,
+                           uint8_t* hits, fsn_stream_t stream);
 int fsn_packed_visibility(const float* sigmas, const float* t_starts, const float* t_ends, const int64_t* ray_indices,
                           int64_t N, int64_t R, float early_stop_eps, float alpha_thre, uint8_t* keep,
                           fsn_stream_t stream);
