@@ -31,6 +31,7 @@ from typing import Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor, nn
+from torch.autograd.function import once_differentiable
 
 from .. import _lib as L
 from .. import ops
@@ -57,37 +58,51 @@ class PositionalEncoder(nn.Module):
 class _NerfTrainFn(torch.autograd.Function):
     """NeRF.forward with gradients.  `fsn_nerf_train_fwd` runs the MFMA kernel of the inference
     path with the fp32 activations saved; `fsn_nerf_train_bwd` the dgrad chain + wgrad GEMMs on the matrix cores
-    (csrc/train_fused.hip), in the model's precision mode.  Gradients flow to the parameters only (sample positions /
-    directions need none on this path).  (The plain-fp32 library-GEMM formulation these kernels were first checked
-    against lives entirely under tests/ref_fp32, binding included; nothing in this package can reach it.)"""
+    (csrc/train_fused.hip), in the model's precision mode.  Gradients flow to the parameters and - when they ask for
+    them - to the inputs: sample positions and directions, or rays_o / rays_d in the ray form
+    (`fsn_nerf_train_bwd_inputs`, csrc/input_grad.hip; a call whose inputs need none runs exactly the launches it ran
+    before).  First order only (`once_differentiable`).  (The plain-fp32 library-GEMM formulation these kernels were
+    first checked against lives entirely under tests/ref_fp32, binding included; nothing in this package can reach it.)"""
 
     @staticmethod
-    def forward(ctx, model, x, dirs, *params):
-        """`x` / `dirs` [..., 3] tensors, or - ray form - x = (rays_o, rays_d, ray_indices, t_starts, t_ends), dirs = None:
-        the samples are the midpoints of the packed intervals, formed inside the launch (no gathered [N,3] tensors)."""
+    def forward(ctx, model, packed, a, b, *params):
+        """Point form: `packed` None, `a` / `b` = x / dirs [..., 3].  Ray form: `packed` = (ray_indices, t_starts,
+        t_ends), `a` / `b` = rays_o / rays_d: the samples are the midpoints of the packed intervals, formed inside the
+        launch (no gathered [N,3] tensors)."""
         n = len(params) // 2
         weights, biases = params[:n], params[n:]
         desc = ops.make_desc(model.n_layers, model.d_hidden, model.skip, model.pos_encoder.freqs,
                              model.dir_encoder.freqs)
-        ray_form = isinstance(x, tuple)
-        dev = x[0].device if ray_form else x.device
+        ray_form = packed is not None
+        dev = a.device
         prec = model.train_prec()
         # range-guard word of THIS call (one network, one step): the kernels of its forward and backward report into
         # it, and only they consult it - a flag raised by another network or by an inference launch must not zero
         # this network's gradients (the sticky per-device word of the inference path is not used here)
         word = torch.zeros(1, dtype=torch.int32, device=dev) if model.fp16_family(prec) else None
+        pm, dm = model._mask(model.pos_mask, dev), model._mask(model.dir_mask, dev)
         if ray_form:
-            out, work = ops.nerf_train_fwd_rays(desc, prec, weights, biases, *x, model._mask(model.pos_mask, dev),
-                                                model._mask(model.dir_mask, dev), status=word)
+            out, work = ops.nerf_train_fwd_rays(desc, prec, weights, biases, a, b, *packed, pm, dm, status=word)
         else:
-            out, work = ops.nerf_train_fwd(desc, prec, weights, biases, x, dirs, model._mask(model.pos_mask, dev),
-                                           model._mask(model.dir_mask, dev), status=word)
+            out, work = ops.nerf_train_fwd(desc, prec, weights, biases, a, b, pm, dm, status=word)
         ctx.desc, ctx.prec, ctx.work, ctx.out, ctx.model, ctx.word = desc, prec, work, out, model, word
         ctx.weights = [w.detach() for w in weights]
         ctx.params = params  # (the leaf Parameters themselves: backward may accumulate into their .grad buffers)
-        return out if ray_form else out.reshape(*x.shape[:-1], 4)
+        ctx.inputs = None
+        need_a, need_b = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        if need_a or need_b:  # the backward reads the inputs again
+            # ray form: d rays_d = sum (m_i d_x_i + d_dirs_i), so EITHER ray tensor needs the per-sample position gradient
+            ctx.inputs = {"pos_mask": pm, "dir_mask": dm, "want_x": need_a or (ray_form and need_b), "want_dirs": need_b}
+            ctx.need = (need_a, need_b)
+            if ray_form:
+                ctx.inputs["rays"] = (a.detach(), b.detach(), *packed)
+            else:
+                ctx.inputs.update(x=a.detach(), dirs=b.detach())
+            ctx.in_shapes = (a.shape, b.shape)
+        return out if ray_form else out.reshape(*a.shape[:-1], 4)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, d_out):
         if ctx.work is None:
             raise RuntimeError("NeRF backward ran twice on one forward: the saved activations are released after the "
@@ -96,30 +111,58 @@ class _NerfTrainFn(torch.autograd.Function):
         # the device - exactly what autograd's AccumulateGrad would do with returned tensors, minus 24 temporaries and 24
         # add launches per step - and autograd is handed None for them.  Anything else gets the gradients returned.
         n = len(ctx.params) // 2
-        sink = all(getattr(p, "_fsn_grad_sink", False) and p.requires_grad and p.grad is not None and p.grad.is_contiguous()
+        inputs = ctx.inputs
+        # no parameter asks: a frozen network or a helper call (density_gradient) - the chain and the input gradient
+        # only.  Such calls are no training steps: they keep per-stage factors and a range word of their own, so a
+        # normals regulariser between two steps neither retunes the training backward's factors nor gates the optimizer.
+        want_params = any(ctx.needs_input_grad[4:])
+        sink = want_params and all(getattr(p, "_fsn_grad_sink", False) and p.requires_grad and p.grad is not None and p.grad.is_contiguous()
                    and p.grad.dtype == torch.float32 and p.grad.device == d_out.device for p in ctx.params)
         into = ([p.grad for p in ctx.params[:n]], [p.grad for p in ctx.params[n:]]) if sink else None
         model = ctx.model
         d_out = d_out.contiguous()
-        stage = model._bwd_stage_state(d_out.device) if model.fp16_family(ctx.prec) else None
-        if stage is not None and not model._bwd_calibrated and d_out.shape[0] > 0:
+        which = "" if want_params else "_inputs"
+        stage = model._bwd_stage_state(d_out.device, which) if model.fp16_family(ctx.prec) else None
+        src = {} if inputs is None else {k: inputs[k] for k in ("x", "dirs", "rays", "pos_mask", "dir_mask") if k in inputs}
+        if stage is not None and not getattr(model, "_bwd_calibrated" + which) and d_out.shape[0] > 0:
             # first backward of this model in an fp16 mode: one throw-away pass to measure the per-stage gradient
             # magnitudes (delayed scaling needs a previous call; its own status word, scratch outputs).  A call without
             # samples - the all-background first batch of an empty occupancy grid - launches nothing and calibrates
             # nothing: the next one with samples does.
-            ops.nerf_train_bwd(ctx.desc, ctx.prec, ctx.weights, ctx.work, ctx.out, d_out,
-                               status=torch.zeros_like(ctx.word) if ctx.word is not None else None, stage_state=stage)
-            model._bwd_calibrated = True
-        dW, db = ops.nerf_train_bwd(ctx.desc, ctx.prec, ctx.weights, ctx.work, ctx.out, d_out, status=ctx.word,
-                                    into=into, stage_state=stage)
+            scratch = torch.zeros_like(ctx.word) if ctx.word is not None else None
+            if want_params:
+                ops.nerf_train_bwd(ctx.desc, ctx.prec, ctx.weights, ctx.work, ctx.out, d_out, status=scratch, stage_state=stage)
+            else:  # (the chain alone)
+                ops.nerf_train_bwd_inputs(ctx.desc, ctx.prec, ctx.weights, ctx.work, ctx.out, d_out, **src, want_x=False,
+                                          want_dirs=False, param_grads=False, status=scratch, stage_state=stage)
+            setattr(model, "_bwd_calibrated" + which, True)
+        if inputs is None:
+            dW, db = ops.nerf_train_bwd(ctx.desc, ctx.prec, ctx.weights, ctx.work, ctx.out, d_out, status=ctx.word,
+                                        into=into, stage_state=stage)
+            g_a = g_b = None
+        else:
+            dW, db, g_x, g_dirs = ops.nerf_train_bwd_inputs(ctx.desc, ctx.prec, ctx.weights, ctx.work, ctx.out, d_out, **src,
+                                                            want_x=inputs["want_x"], want_dirs=inputs["want_dirs"],
+                                                            param_grads=want_params, status=ctx.word, into=into,
+                                                            stage_state=stage)
+            if "rays" in inputs:  # per-sample gradients -> per-ray sums (one wave per ray, fixed order)
+                o, _, ri, t0, t1 = inputs["rays"]
+                g_a, g_b = ops.ray_grad_reduce(g_x, g_dirs, ri, t0, t1, o.shape[0], want_o=ctx.need[0], want_d=ctx.need[1])
+            else:
+                g_a, g_b = g_x, g_dirs
+            g_a = None if g_a is None else g_a.reshape(ctx.in_shapes[0])
+            g_b = None if g_b is None else g_b.reshape(ctx.in_shapes[1])
         ctx.work = None
         ctx.params = None
+        ctx.inputs = None
         # fp16 range guard without a per-step host sync.  When this call's launches reported values outside the fp16
         # range, the backward kernels have written ITS gradients as zeros on the device; the call's word is folded
         # (device ops) into the device's step flag, on which FusedAdam skips the whole update - a skipped step, like a
         # loss scaler's - and into this model's own accumulated word, which the host reads every `range_check_every`
         # training calls; it then warns and continues in bf16x3.
-        if ctx.word is not None:
+        if ctx.word is not None and not want_params:
+            model._fold_input_status(ctx.word, d_out.device)
+        elif ctx.word is not None:
             model.fold_status(ctx.word, d_out.device, 0)
             model._train_calls += 1
             if model.range_check and model._train_calls % model.range_check_every == 0:
@@ -134,10 +177,10 @@ class _NerfTrainFn(torch.autograd.Function):
                 # not, so that the scales follow the network long before a guard trips.
                 if sampler_bits or (model._train_calls // model.range_check_every) % 4 == 0:
                     model._needs_calibration = True
-        if sink:
-            return (None, None, None) + (None,) * (2 * n)
+        if sink or not want_params:
+            return (None, None, g_a, g_b) + (None,) * (2 * n)
         db = [g.reshape(-1) for g in db]
-        return (None, None, None, *dW, *db)
+        return (None, None, g_a, g_b, *dW, *db)
 
 
 class NeRF(nn.Module):
@@ -177,6 +220,10 @@ class NeRF(nn.Module):
         self._train_word: Optional[Tensor] = None
         self._bwd_stage = None       # (scales, maxima) of the backward's delayed per-stage gradient scaling (fp16 modes)
         self._bwd_calibrated = False
+        self._bwd_stage_inputs = None  # ... of backward calls that compute input gradients only (no training steps)
+        self._bwd_calibrated_inputs = False
+        self._input_word: Optional[Tensor] = None
+        self._input_calls = 0
         self.grad_overflow_looks = 0  # host looks that found a step skipped by the delayed gradient scaling
         self.train_precision: Optional[str] = None  # None: same mode as `precision`
         self.pos_mask: Optional[Tensor] = None
@@ -226,14 +273,36 @@ class NeRF(nn.Module):
         """`precision` is one of the fp16 modes now (range-guarded; `fall_back` leaves them)."""
         return self.fp16_family(self.PRECISIONS[self.precision])
 
-    def _bwd_stage_state(self, dev):
-        """(scales, maxima) of the backward chain's delayed per-stage scaling (fsn_nerf_train_bwd), device-resident."""
-        st = self._bwd_stage
+    def _bwd_stage_state(self, dev, which: str = ""):
+        """(scales, maxima) of the backward chain's delayed per-stage scaling (fsn_nerf_train_bwd), device-resident.
+        `which` = "" for training steps, "_inputs" for calls that compute input gradients only (a frozen network,
+        `density_gradient`): their cotangents are other quantities, so they steer a pair of arrays of their own."""
+        st = getattr(self, "_bwd_stage" + which)
         if st is None or st[0].device != dev:
             n = self.n_layers + 2
-            st = self._bwd_stage = (torch.ones(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev))
-            self._bwd_calibrated = False
+            st = (torch.ones(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev))
+            setattr(self, "_bwd_stage" + which, st)
+            setattr(self, "_bwd_calibrated" + which, False)
         return st
+
+    def _fold_input_status(self, word: Tensor, dev) -> None:
+        """Range word of a backward that computed input gradients only (fp16 modes; its gradients are zeros when the
+        word is set).  Not a training step: it joins neither the optimizer's step flags nor `_train_calls`; it is ORed
+        into a word of its own that the host reads every `range_check_every` such calls - a flagged one then warns and
+        the model continues in the bf16 mode, as after a flagged training step."""
+        w = self._input_word
+        if w is None or w.device != dev:
+            w = self._input_word = torch.zeros(1, dtype=torch.int32, device=dev)
+        w.bitwise_or_(word)
+        self._input_calls += 1
+        if self.range_check and self._input_calls % self.range_check_every == 0:
+            bits = int(w.item())
+            if bits:
+                w.zero_()
+            if bits & L.FSN_STATUS_GRAD_RANGE:
+                self.grad_overflow_looks += 1
+            if bits & (L.FSN_STATUS_FP16_RANGE | L.FSN_STATUS_FP16_SMALL):
+                self.fall_back("input-gradient calls (a flagged call's gradients were written as zeros)", bits, scaled=False)
 
     def _step_flags(self, dev):
         """The step-flag words a training launch of this model reports into (device int32 [1] each): the word of every
@@ -527,10 +596,11 @@ class NeRF(nn.Module):
         """`self(x, d)` (full) or `self(x)` (density only) on the midpoints of packed intervals - what the reference's
         closures compute as `to = rays_o[ri]; td = rays_d[ri]; x = to + td * (t0 + t1)[:, None] / 2; model(x, td)`
         (rendering.py:58-64, 76-84) - with the gathers and the midpoint arithmetic inside the launch: no [N,3] tensor
-        is materialised.  Same values bit for bit; gradients (training mode, full pass) flow to the parameters."""
-        if full and self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        is materialised.  Same values bit for bit; gradients (full pass) flow to the parameters of a model in training
+        mode and to `rays_o` / `rays_d` when they require grad (any mode; none to the interval edges)."""
+        if full and self._differentiable(rays_o, rays_d):
             ws, bs = self._tensors()
-            return _NerfTrainFn.apply(self, (rays_o, rays_d, ray_indices, t_starts, t_ends), None, *ws, *bs)
+            return _NerfTrainFn.apply(self, (ray_indices, t_starts, t_ends), rays_o, rays_d, *ws, *bs)
         dev = rays_o.device
         args = (rays_o, rays_d, ray_indices, t_starts, t_ends, full, self._mask(self.pos_mask, dev), self._mask(self.dir_mask, dev))
 
@@ -544,14 +614,43 @@ class NeRF(nn.Module):
         return guarded_launch([self], dev, "NeRF.forward_rays", probe, lambda: ops.mlp_fwd_rays(self.packed(probe), *args))
 
     # -- reference surface ---------------------------------------------------------
+    def _differentiable(self, *inputs: Optional[Tensor]) -> bool:
+        """This call runs the training pair (`_NerfTrainFn`): grad is enabled and either the model trains with
+        parameters that require grad, or one of the inputs requires grad (training or eval mode)."""
+        if not torch.is_grad_enabled():
+            return False
+        if self.training and any(p.requires_grad for p in self.parameters()):
+            return True
+        return any(t is not None and t.requires_grad for t in inputs)
+
+    def density_gradient(self, x: Tensor) -> Tuple[Tensor, Tensor]:
+        """-> (sigma [N], d sigma / d x [N,3]) at positions x [N,3]: one full pass with the cotangent (0, 0, 0, 1) and a
+        fixed direction (sigma does not depend on it), the network treated as frozen - no parameter gradient is computed
+        or touched.  Surface normals are `-F.normalize(grad, dim=-1)`."""
+        xg = x.detach().reshape(-1, 3).to(torch.float32).contiguous().requires_grad_(True)
+        dirs = torch.tensor([0.0, 0.0, 1.0], device=xg.device).expand(xg.shape[0], 3).contiguous()
+        ws, bs = self._tensors()
+        with torch.enable_grad():
+            out = _NerfTrainFn.apply(self, None, xg, dirs, *[t.detach() for t in ws + bs])
+            cot = torch.zeros_like(out)
+            cot[:, 3] = 1.0
+            (grad,) = torch.autograd.grad(out, xg, cot)
+        return out[:, 3].detach(), grad
+
     def forward(self, x: Tensor, dirs: Optional[Tensor] = None) -> Tensor:
-        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        if self._differentiable(x, dirs):
             if dirs is None:
+                if not self._differentiable():  # (only x asks: as before, the density-only pass carries no graph)
+                    return self._forward_inference(x, dirs)
                 raise NotImplementedError(
                     "NeRF.forward(x) with gradients: the density-only pass has no backward (the reference runs it "
-                    "under torch.no_grad(), rendering.py:58-64); call it under torch.no_grad()")
+                    "under torch.no_grad(), rendering.py:58-64); call it under torch.no_grad() (density_gradient(x) gives "
+                    "sigma and its gradient with respect to x)")
             ws, bs = self._tensors()
-            return _NerfTrainFn.apply(self, x, dirs, *ws, *bs)
+            return _NerfTrainFn.apply(self, None, x, dirs, *ws, *bs)
+        return self._forward_inference(x, dirs)
+
+    def _forward_inference(self, x: Tensor, dirs: Optional[Tensor]) -> Tensor:
         dev = x.device
         mode = self._autocast_mode()
         if mode is not None:

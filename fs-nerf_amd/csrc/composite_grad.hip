@@ -9,16 +9,6 @@
 
 namespace fsn {
 
-// first index of the sorted a[0..n) that is >= key
-__device__ __forceinline__ int64_t ray_lower_bound(const int64_t* __restrict__ a, int64_t n, int64_t key) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (a[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
 // Per ray, samples i in packed order: dt_i = t1_i - t0_i, m_i = (t0_i + t1_i)/2, T_i = exp(-sum_{j<i} sigma_j dt_j),
 // e_i = exp(-sigma_i dt_i), alpha_i = 1 - e_i, w_i = T_i alpha_i, O = sum w, D = sum w m / max(O, eps).  With the
 // cotangents g (colors), g_O, g_D per ray and u_i, a_i, tau_i per sample (weights, alphas, trans):

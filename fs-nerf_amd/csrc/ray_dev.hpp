@@ -31,6 +31,16 @@ __device__ __forceinline__ float wave_excl_scan(float v, float& total) {
   return inc - v;
 }
 
+// first index of the sorted a[0..n) that is >= key
+__device__ __forceinline__ int64_t ray_lower_bound(const int64_t* __restrict__ a, int64_t n, int64_t key) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (a[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
 struct CompositeOut {
   float* colors;   // [3]
   float* opacity;  // [1]

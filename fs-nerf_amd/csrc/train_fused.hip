@@ -1174,7 +1174,8 @@ int fused_train_fwd(const fsn_mlp_desc* d, int prec, const float* const* W, cons
 
 int fused_train_bwd(const fsn_mlp_desc* d, int prec, const float* const* W, int64_t n, float* ws, const float* out,
                     const float* d_out, const float* grad_scale_dev, float* const* dW, float* const* db,
-                    bool accumulate, float* bscale, uint32_t* bamax, uint32_t* status, hipStream_t s) {
+                    bool accumulate, float* bscale, uint32_t* bamax, uint32_t* status, hipStream_t s,
+                    const InputGradReq* ig) {
   FusedLayout F;
   const char* why;
   int rc = make_fused_layout(*d, prec, n, F, &why);
@@ -1209,6 +1210,22 @@ int fused_train_bwd(const fsn_mlp_desc* d, int prec, const float* const* W, int6
     rc = dispatch_net(PrecTraining{}, D, prec, [&](auto NT, auto PREC) { return launch_bwd<NT(), PREC()>(a, grid, s); });
     if (rc != FSN_OK) return rc;
   }
+  // the per-stage factors move at the END of the call: the weight-gradient reduces and the input gradient read the ones
+  // the chain above used
+  auto rescale = [&]() {
+    if (prec_is_f16(prec) && bscale && bamax) {
+      k_bwd_rescale<<<1, 64, 0, s>>>(bscale, bamax, L + 2);
+      FSN_LAUNCH_CHECK("k_bwd_rescale");
+    }
+    return FSN_OK;
+  };
+  if (ig) {  // ---- input gradient (input_grad.hip)
+    const InputGradWs o{F.blob_b, F.pe - F.blob_b, F.dp, F.h_stride, F.dbo};
+    rc = input_grad_launch(*d, prec, W, n, ws, o, grad_scale_dev, prec_is_f16(prec) ? bscale : nullptr,
+                           prec_is_f16(prec) ? status : nullptr, *ig, s);
+    if (rc != FSN_OK) return rc;
+  }
+  if (!dW) return rescale();  // frozen network: no weight-gradient launches
   // ---- wgrad jobs
   WgArgs wa[4] = {};
   int cnt[4] = {0, 0, 0, 0};
@@ -1279,11 +1296,7 @@ int fused_train_bwd(const fsn_mlp_desc* d, int prec, const float* const* W, int6
     k_heads_reduce<<<(unsigned)((nn + 255) / 256), 256, 0, s>>>(hr);
     FSN_LAUNCH_CHECK("k_heads_reduce");
   }
-  if (prec_is_f16(prec) && bscale && bamax) {
-    k_bwd_rescale<<<1, 64, 0, s>>>(bscale, bamax, L + 2);
-    FSN_LAUNCH_CHECK("k_bwd_rescale");
-  }
-  return FSN_OK;
+  return rescale();
 }
 
 }  // namespace fsn

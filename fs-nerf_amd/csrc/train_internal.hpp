@@ -9,12 +9,30 @@ struct TrainRays {  // ray form of the forward's inputs: sample s = midpoint of 
   const int64_t* ri;
 };
 
+struct InputGradReq {  // gradients to the network's inputs (fsn_nerf_train_bwd_inputs): the forward's inputs again
+  const float *x, *dirs;     // point form, or null with `rays`
+  const TrainRays* rays;
+  const float *pos_mask, *dir_mask;
+  float *d_x, *d_dirs;       // [n,3] each, either may be null
+};
+
 int64_t fused_train_workspace_floats(const fsn_mlp_desc& d, int prec, int64_t n);
 int fused_train_fwd(const fsn_mlp_desc* d, int prec, const float* const* W, const float* const* b, const float* x,
                     const float* dirs, const float* pos_mask, const float* dir_mask, int64_t n, float* ws, float* out,
                     uint32_t* status, hipStream_t s, const TrainRays* rays = nullptr);
 int fused_train_bwd(const fsn_mlp_desc* d, int prec, const float* const* W, int64_t n, float* ws, const float* out,
                     const float* d_out, const float* grad_scale_dev, float* const* dW, float* const* db,
-                    bool accumulate, float* bscale, uint32_t* bamax, uint32_t* status, hipStream_t s);
+                    bool accumulate, float* bscale, uint32_t* bamax, uint32_t* status, hipStream_t s,
+                    const InputGradReq* ig = nullptr);
+
+// k_input_grad (input_grad.hip), launched by fused_train_bwd between the dgrad chain and k_bwd_rescale.  The packed
+// weight slices go where the chain's transposed-weight stream lay (dead once the chain has run).
+struct InputGradWs {
+  int64_t blob, blob_floats;      // float offsets into the workspace: the backward blob and its size
+  int64_t dp, h_stride, dbo;      // dPre_0 (stage l at dp + l h_stride), dBo
+};
+int input_grad_launch(const fsn_mlp_desc& d, int prec, const float* const* W, int64_t n, float* ws, const InputGradWs& o,
+                      const float* grad_scale_dev, const float* bscale, const uint32_t* status, const InputGradReq& rq,
+                      hipStream_t s);
 
 }  // namespace fsn

@@ -736,6 +736,18 @@ def grad_scale_for(d_out: Tensor) -> Tensor:
     return buf[:1]
 
 
+def _check_into(into, ws_):
+    """`into` = (weight .grad buffers, bias .grad buffers) of nerf_train_bwd -> (d_weights, flat d_biases), validated."""
+    for g in list(into[0]) + list(into[1]):
+        if not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous()):
+            raise ValueError("nerf_train_bwd: `into` buffers must be contiguous float32 GPU tensors (they are written in place)")
+    dW, db = list(into[0]), [g.view(-1) for g in into[1]]
+    if len(dW) != len(ws_) or len(db) != len(ws_) or any(g.shape != w.shape for g, w in zip(dW, ws_)) or \
+            any(g.numel() != w.shape[0] for g, w in zip(db, ws_)):
+        raise ValueError("nerf_train_bwd: `into` must hold one gradient buffer per weight / bias, of its shape")
+    return dW, db
+
+
 def nerf_train_bwd(desc: L.MlpDesc, prec: int, weights: Sequence[Tensor], work: Tensor, out: Tensor, d_out: Tensor,
                    status: Optional[Tensor] = None, into: Optional[Tuple[Sequence[Tensor], Sequence[Tensor]]] = None,
                    stage_state: Optional[Tuple[Tensor, Tensor]] = None):
@@ -748,13 +760,7 @@ def nerf_train_bwd(desc: L.MlpDesc, prec: int, weights: Sequence[Tensor], work: 
     d_out = _f32(d_out, "d_out").reshape(-1, 4)
     n = d_out.shape[0]
     if into is not None:
-        for g in list(into[0]) + list(into[1]):
-            if not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous()):
-                raise ValueError("nerf_train_bwd: `into` buffers must be contiguous float32 GPU tensors (they are written in place)")
-        dW, db = list(into[0]), [g.view(-1) for g in into[1]]
-        if len(dW) != len(ws_) or len(db) != len(ws_) or any(g.shape != w.shape for g, w in zip(dW, ws_)) or \
-                any(g.numel() != w.shape[0] for g, w in zip(db, ws_)):
-            raise ValueError("nerf_train_bwd: `into` must hold one gradient buffer per weight / bias, of its shape")
+        dW, db = _check_into(into, ws_)
         if n == 0:
             return dW, db
     else:
@@ -770,6 +776,85 @@ def nerf_train_bwd(desc: L.MlpDesc, prec: int, weights: Sequence[Tensor], work: 
                                            _p(stage_state[1]) if stage_state else None, _p(status), _stream()),
                 "fsn_nerf_train_bwd")
     return dW, db
+
+
+def nerf_train_bwd_inputs(desc: L.MlpDesc, prec: int, weights: Sequence[Tensor], work: Tensor, out: Tensor, d_out: Tensor, *,
+                          x: Optional[Tensor] = None, dirs: Optional[Tensor] = None,
+                          rays: Optional[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]] = None,
+                          pos_mask: Optional[Tensor] = None, dir_mask: Optional[Tensor] = None, want_x: bool = True,
+                          want_dirs: bool = True, param_grads: bool = True, status: Optional[Tensor] = None,
+                          into: Optional[Tuple[Sequence[Tensor], Sequence[Tensor]]] = None,
+                          stage_state: Optional[Tuple[Tensor, Tensor]] = None):
+    """nerf_train_bwd plus the gradients of the network's inputs (fsn_nerf_train_bwd_inputs) -> (d_weights, d_biases,
+    d_x, d_dirs).  The forward's inputs are handed in again: `x` and `dirs`, or `rays` = (rays_o, rays_d, ray_indices,
+    t_starts, t_ends), with its `pos_mask` / `dir_mask`.  d_x / d_dirs: per-SAMPLE float32 [n,3] gradients of the
+    positions / directions (None where not wanted; the ray form's per-ray sums are `ray_grad_reduce`).
+    `param_grads=False`: a frozen network - the dgrad chain and the input gradient only, no weight-gradient launches,
+    d_weights = d_biases = None (with neither `want_x` nor `want_dirs`: the chain alone, which still moves `stage_state`).
+    `status`, `into`, `stage_state` as in nerf_train_bwd; the parameter gradients are those of nerf_train_bwd bit for bit."""
+    if (rays is None) == (x is None) or (rays is None and dirs is None):
+        raise ValueError("nerf_train_bwd_inputs: give x and dirs, or rays")
+    ws_ = [_f32(w.detach(), "weight") for w in weights]
+    d_out = _f32(d_out, "d_out").reshape(-1, 4)
+    n = d_out.shape[0]
+    dev = d_out.device
+    if rays is not None:
+        o, d, ri, t0, t1 = rays
+        src = (None, None, _f32(o.detach(), "rays_o"), _f32(d.detach(), "rays_d"), _i64(ri, "ray_indices"),
+               _f32(t0, "t_starts"), _f32(t1, "t_ends"))
+        n_in = src[4].numel()
+    else:
+        src = (_f32(x.detach(), "x").reshape(-1, 3), _f32(dirs.detach(), "dirs").reshape(-1, 3), None, None, None, None, None)
+        n_in = src[0].shape[0] if src[0].shape[0] == src[1].shape[0] else -1
+    if n_in != n:
+        raise ValueError("nerf_train_bwd_inputs: the inputs are not the forward's samples")
+    # (the kernel writes every row of a call with samples; a call without samples launches nothing)
+    d_x = torch.empty(n, 3, device=dev, dtype=torch.float32) if want_x else None
+    d_dirs = torch.empty(n, 3, device=dev, dtype=torch.float32) if want_dirs else None
+    if not param_grads:
+        dW = db = None
+        if into is not None:
+            raise ValueError("nerf_train_bwd_inputs: `into` needs param_grads")
+    elif into is not None:
+        dW, db = _check_into(into, ws_)
+    elif n == 0:  # e.g. the all-background first batch of an empty occupancy grid (run-nerf.py:243 precedes :293)
+        dW, db = [torch.zeros_like(w) for w in ws_], [torch.zeros(w.shape[0], device=w.device) for w in ws_]
+    else:
+        dW = [torch.empty_like(w) for w in ws_]
+        db = [torch.empty(w.shape[0], device=w.device, dtype=torch.float32) for w in ws_]
+    if n == 0:
+        return dW, db, d_x, d_dirs
+    scale = grad_scale_for(d_out) if prec in (L.FSN_PREC_FP16X3, L.FSN_PREC_FP16) else None
+    pm = None if pos_mask is None else _f32(pos_mask, "pos_mask")
+    dm = None if dir_mask is None else _f32(dir_mask, "dir_mask")
+    with torch.cuda.device(work.device):
+        L.check(L.lib().fsn_nerf_train_bwd_inputs(
+            C.byref(desc), prec, _ptr_array(ws_), n, _p(work), _p(out), _p(d_out), _p(scale),
+            _ptr_array(dW) if param_grads else None, _ptr_array(db) if param_grads else None, 0 if into is None else 1,
+            _p(stage_state[0]) if stage_state else None, _p(stage_state[1]) if stage_state else None, _p(status),
+            *[_p(t) for t in src], _p(pm), _p(dm), _p(d_x), _p(d_dirs), _stream()), "fsn_nerf_train_bwd_inputs")
+    return dW, db, d_x, d_dirs
+
+
+def ray_grad_reduce(d_x: Optional[Tensor], d_dirs: Optional[Tensor], ray_indices: Tensor, t_starts: Tensor, t_ends: Tensor,
+                    n_rays: int, want_o: bool = True, want_d: bool = True) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """The ray form's reduction of per-sample input gradients (fsn_ray_grad_reduce): d_rays_o[r] = sum d_x, d_rays_d[r] =
+    sum ((t0 + t1) / 2 d_x + d_dirs) over ray r's samples -> ([n_rays,3] or None, [n_rays,3] or None).  One wave per ray,
+    fixed order: deterministic; rays without samples get zeros."""
+    ri, t0, t1 = _i64(ray_indices, "ray_indices"), _f32(t_starts, "t_starts"), _f32(t_ends, "t_ends")
+    n = ri.numel()
+    dev = ri.device
+    d_x = None if d_x is None else _f32(d_x, "d_x")
+    d_dirs = None if d_dirs is None else _f32(d_dirs, "d_dirs")
+    for g in (d_x, d_dirs):
+        if g is not None and tuple(g.shape) != (n, 3):
+            raise ValueError("ray_grad_reduce: d_x / d_dirs must be [n_samples, 3]")
+    d_o = torch.empty(n_rays, 3, device=dev, dtype=torch.float32) if want_o else None
+    d_d = torch.empty(n_rays, 3, device=dev, dtype=torch.float32) if want_d else None
+    with torch.cuda.device(dev):
+        L.check(L.lib().fsn_ray_grad_reduce(_p(d_x), _p(d_dirs), _p(ri), _p(t0), _p(t1), n, n_rays, _p(d_o), _p(d_d),
+                                            _stream()), "fsn_ray_grad_reduce")
+    return d_o, d_d
 
 
 def composite_packed_bwd(sigmas, rgbs, t_starts, t_ends, ray_indices, n_rays, bkgd, d_colors, d_opacity):

@@ -462,8 +462,10 @@ def render_rays(rays_o: Tensor, rays_d: Tensor, estimator, model: nn.Module, tra
     rays_o = rays_o.to(device)
     rays_d = rays_d.to(device)
     fine = model_fine if model_fine is not None else model
-    needs_grad = torch.is_grad_enabled() and isinstance(fine, nn.Module) and fine.training and \
-        any(p.requires_grad for p in fine.parameters())
+    # (rays that require grad - camera-pose refinement - take the differentiable route too: forward_rays carries their
+    # gradients, with a frozen or an eval-mode network as well)
+    needs_grad = torch.is_grad_enabled() and isinstance(fine, nn.Module) and \
+        ((fine.training and any(p.requires_grad for p in fine.parameters())) or rays_o.requires_grad or rays_d.requires_grad)
     route = _rays_route(estimator, model, model_fine, needs_grad, want_extras, rays_o.shape[0], render_step_size, opts)
     if route in _ONE_LAUNCH:
         return _ONE_LAUNCH[route](rays_o, rays_d, None, estimator, model, model_fine, train, float(white_bkgd),

@@ -391,7 +391,7 @@ int fsn_occlusion_reg_bwd(const float* t_vals, int64_t N, const float* ray_sums,
 
 /* f1: the training step around the path.                         src/run-nerf.py:243-285, models.py:111-143
  * NeRF.forward keeping what its backward needs in a caller-provided workspace, and that backward (gradients of
- * every parameter; sample positions / directions receive none on this path).
+ * every parameter; fsn_nerf_train_bwd_inputs adds those of the sample positions / directions).
  *   prec 0..3 (FSN_PREC_*).  Forward = the inference kernel with fp32 activations saved in tiles of
  *     128 samples; backward = register-resident dgrad chain on transposed weights + split-K wgrad GEMMs over all
  *     samples (csrc/train_fused.hip).  grad_scale: DEVICE pointer to one float, a power of two that d_out is
@@ -427,6 +427,28 @@ int fsn_nerf_train_bwd(const fsn_mlp_desc* desc, int prec, const float* const* w
                        const float* out, const float* d_out, const float* grad_scale, float* const* d_weights,
                        float* const* d_biases, int accumulate, float* stage_scales, uint32_t* stage_amax,
                        uint32_t* status, fsn_stream_t stream);
+/* fsn_nerf_train_bwd plus the gradients of the network's INPUTS (csrc/input_grad.hip): d_x [n,3] = dL/d(sample
+ * positions), d_dirs [n,3] = dL/d(directions), float32, either may be NULL.  The inputs of the forward are handed in
+ * again - x and dirs (point form), or rays_o, rays_d, ray_indices, t_starts, t_ends (ray form, all five; x and dirs NULL:
+ * d_x / d_dirs are then per SAMPLE, fsn_ray_grad_reduce sums them per ray) - with the forward's pos_mask / dir_mask.
+ *   d_weights == NULL && d_biases == NULL: the dgrad chain and the input gradient only, no weight-gradient launches
+ *   (frozen networks: normals, pose-only optimisation).  Otherwise the parameter gradients are bit for bit those of
+ *   fsn_nerf_train_bwd.  The workspace size is unchanged (the packed weight slices reuse the chain's transposed-weight
+ *   stream, dead by then); the stage arrays advance exactly once per call, and the input gradient is formed with the
+ *   factors this call's chain used.  fp16 modes: a flagged call (FSN_STATUS_FP16_RANGE or FSN_STATUS_GRAD_RANGE in
+ *   *status) writes d_x / d_dirs as zeros, like the weight gradients.  n == 0: nothing is launched, FSN_OK. */
+int fsn_nerf_train_bwd_inputs(const fsn_mlp_desc* desc, int prec, const float* const* weights, int64_t n, float* workspace,
+                              const float* out, const float* d_out, const float* grad_scale, float* const* d_weights,
+                              float* const* d_biases, int accumulate, float* stage_scales, uint32_t* stage_amax,
+                              uint32_t* status, const float* x, const float* dirs, const float* rays_o,
+                              const float* rays_d, const int64_t* ray_indices, const float* t_starts, const float* t_ends,
+                              const float* pos_mask, const float* dir_mask, float* d_x, float* d_dirs, fsn_stream_t stream);
+/* The ray form's reduction of per-sample input gradients: d_rays_o[r] = sum_i d_x[i], d_rays_d[r] = sum_i (m_i d_x[i] +
+ * d_dirs[i]) over ray r's samples (ray_indices sorted), m_i = (t_starts[i] + t_ends[i]) / 2.  d_x, d_dirs [N,3] (either
+ * may be NULL: that term is absent), outputs [R,3] (either may be NULL).  One wave per ray, fixed summation order, no
+ * atomics: deterministic; a ray without samples gets zeros.  No gradient goes to t_starts / t_ends. */
+int fsn_ray_grad_reduce(const float* d_x, const float* d_dirs, const int64_t* ray_indices, const float* t_starts,
+                        const float* t_ends, int64_t N, int64_t R, float* d_rays_o, float* d_rays_d, fsn_stream_t stream);
 /* The power-of-two `grad_scale` of the fp16 modes' backward in one launch: 2^floor(log2(1024 / max|d_out|)), exponent
  * clamped to [-40, 60], 1 when the maximum is 0 / inf / NaN (the arithmetic of ops.grad_scale_for, which took nine
  * elementwise / reduction launches).  buf: 4 device floats, ZEROED by the caller; buf[0] receives the scale (buf[1..2]
