@@ -1,9 +1,10 @@
-// composite_grad.hip — the FULL backward of the packed volume integration (every output of fsn_composite_packed_fwd
-// carries a cotangent: colors, opacity, depth, weights, alphas, trans) and the distortion loss on the compositor's
-// weights, the first consumer of dL/dweights.  The lean backward of the timed training step (colors and opacity only)
-// stays k_composite_packed_bwd in train.hip; the kernel here has its structure: one wavefront per ray, the ray's sample
-// range by binary search over ray_indices, lane l owns a contiguous run of samples, prefix by wave_excl_scan, suffix =
-// total - prefix.  No LDS, no atomics, every sum in a fixed order.  DESIGN.md, "Full compositor backward".
+// composite_grad.hip — the backward of the packed volume integration (every output of fsn_composite_packed_fwd may
+// carry a cotangent: colors, opacity, depth, weights, alphas, trans) and the distortion loss on the compositor's
+// weights, the first consumer of dL/dweights.  ONE kernel serves both entry points: fsn_composite_packed_bwd (the
+// timed training step: colors and opacity only) is fsn_composite_packed_bwd_full with the other cotangents NULL.
+// One wavefront per ray, the ray's sample range by ray_span over ray_indices, lane l owns a contiguous run of samples,
+// prefix by wave_excl_scan, suffix = total - prefix.  No LDS, no atomics, every sum in a fixed order.  DESIGN.md,
+// "Full compositor backward".
 #include "common.hpp"
 #include "ray_dev.hpp"
 
@@ -17,8 +18,8 @@ namespace fsn {
 //   dL/dalpha_i = A_i = q_i T_i + a_i,   dL/dT_i = B_i = q_i alpha_i + tau_i
 //   dL/dsigma_i = dt_i ( A_i e_i - sum_{j>i} B_j T_j ),   dL/dc_i = w_i g
 // Every optional pointer is a kernel argument, so its NULL branch is wave-uniform and nothing is loaded through it.
-// (d_colors and d_opacity included: an absent one is zero).  With d_depth = d_w = d_a = d_tr = NULL the float op
-// sequence is k_composite_packed_bwd's: same bits.
+// (d_colors and d_opacity included: an absent one is zero).  With d_depth = d_w = d_a = d_tr = NULL what is left is
+//   q_i = g.c_i - g.bkgd + g_O,   dL/dsigma_i = dt_i ( q_i T_i e_i - sum_{j>i} q_j w_j ).
 __global__ void k_composite_packed_bwd_full(const float* __restrict__ sig, const float* __restrict__ rgb,
                                             const float* __restrict__ t0, const float* __restrict__ t1,
                                             const int64_t* __restrict__ ri, int64_t N, int64_t R, float b0, float b1,
@@ -31,8 +32,7 @@ __global__ void k_composite_packed_bwd_full(const float* __restrict__ sig, const
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * 4 + wave;
   if (r >= R) return;
-  const int64_t beg = ray_lower_bound(ri, N, r);
-  const int S = (int)(ray_lower_bound(ri, N, r + 1) - beg);
+  const auto [beg, S] = ray_span(ri, N, r);
   if (S <= 0) return;
   const float* s_ = sig + beg; const float* c_ = rgb + 3 * beg; const float* a_ = t0 + beg; const float* e_ = t1 + beg;
   const float* u_ = d_w ? d_w + beg : nullptr;
@@ -107,8 +107,7 @@ __global__ void k_distortion_fwd(const float* __restrict__ w, const float* __res
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * 4 + wave;
   if (r >= R) return;
-  const int64_t beg = ray_lower_bound(ri, N, r);
-  const int S = (int)(ray_lower_bound(ri, N, r + 1) - beg);
+  const auto [beg, S] = ray_span(ri, N, r);
   if (S <= 0) {
     if (lane == 0) out[r] = 0.f;
     return;
@@ -142,8 +141,7 @@ __global__ void k_distortion_bwd(const float* __restrict__ w, const float* __res
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * 4 + wave;
   if (r >= R) return;
-  const int64_t beg = ray_lower_bound(ri, N, r);
-  const int S = (int)(ray_lower_bound(ri, N, r + 1) - beg);
+  const auto [beg, S] = ray_span(ri, N, r);
   if (S <= 0) return;
   const float* w_ = w + beg; const float* a_ = t0 + beg; const float* e_ = t1 + beg;
   const float g = d_out[r];
@@ -169,18 +167,17 @@ __global__ void k_distortion_bwd(const float* __restrict__ w, const float* __res
 
 using namespace fsn;
 
-extern "C" int fsn_composite_packed_bwd_full(const float* sigmas, const float* rgbs, const float* t_starts,
-                                             const float* t_ends, const int64_t* ray_indices, int64_t N, int64_t R,
-                                             const float* bkgd_host, const float* d_colors, const float* d_opacity,
-                                             const float* opacity, const float* depth, const float* d_depth,
-                                             const float* d_weights, const float* d_alphas, const float* d_trans,
-                                             float* d_sigmas, float* d_rgbs, fsn_stream_t stream) {
-  FSN_REQUIRE(N >= 0 && R >= 0, FSN_E_INVALID, "fsn_composite_packed_bwd_full: bad sizes");
-  FSN_REQUIRE(!d_depth || (opacity && depth), FSN_E_INVALID,
-              "fsn_composite_packed_bwd_full: d_depth needs the forward's opacity and depth");
+// the shared checks, the two memsets and the launch of both compositor-backward entry points
+static int composite_bwd_launch(const char* who, const float* sigmas, const float* rgbs, const float* t_starts,
+                                const float* t_ends, const int64_t* ray_indices, int64_t N, int64_t R,
+                                const float* bkgd_host, const float* d_colors, const float* d_opacity, const float* opacity,
+                                const float* depth, const float* d_depth, const float* d_weights, const float* d_alphas,
+                                const float* d_trans, float* d_sigmas, float* d_rgbs, fsn_stream_t stream) {
+  FSN_REQUIRE(N >= 0 && R >= 0, FSN_E_INVALID, "%s: bad sizes", who);
+  FSN_REQUIRE(!d_depth || (opacity && depth), FSN_E_INVALID, "%s: d_depth needs the forward's opacity and depth", who);
   if (N == 0 || R == 0) return FSN_OK;
   FSN_REQUIRE(sigmas && rgbs && t_starts && t_ends && ray_indices && d_sigmas && d_rgbs, FSN_E_INVALID,
-              "fsn_composite_packed_bwd_full: null pointer");
+              "%s: null pointer", who);
   const float b0 = bkgd_host ? bkgd_host[0] : 0.f, b1 = bkgd_host ? bkgd_host[1] : 0.f, b2 = bkgd_host ? bkgd_host[2] : 0.f;
   FSN_HIP(hipMemsetAsync(d_sigmas, 0, (size_t)N * sizeof(float), as_stream(stream)));
   FSN_HIP(hipMemsetAsync(d_rgbs, 0, (size_t)N * 3 * sizeof(float), as_stream(stream)));
@@ -189,6 +186,28 @@ extern "C" int fsn_composite_packed_bwd_full(const float* sigmas, const float* r
       d_weights, d_alphas, d_trans, d_sigmas, d_rgbs);
   FSN_LAUNCH_CHECK("k_composite_packed_bwd_full");
   return FSN_OK;
+}
+
+extern "C" int fsn_composite_packed_bwd_full(const float* sigmas, const float* rgbs, const float* t_starts,
+                                             const float* t_ends, const int64_t* ray_indices, int64_t N, int64_t R,
+                                             const float* bkgd_host, const float* d_colors, const float* d_opacity,
+                                             const float* opacity, const float* depth, const float* d_depth,
+                                             const float* d_weights, const float* d_alphas, const float* d_trans,
+                                             float* d_sigmas, float* d_rgbs, fsn_stream_t stream) {
+  return composite_bwd_launch("fsn_composite_packed_bwd_full", sigmas, rgbs, t_starts, t_ends, ray_indices, N, R,
+                              bkgd_host, d_colors, d_opacity, opacity, depth, d_depth, d_weights, d_alphas, d_trans,
+                              d_sigmas, d_rgbs, stream);
+}
+
+// colors and opacity only (the training step); unlike the full form it requires d_colors
+extern "C" int fsn_composite_packed_bwd(const float* sigmas, const float* rgbs, const float* t_starts, const float* t_ends,
+                                        const int64_t* ray_indices, int64_t N, int64_t R, const float* bkgd_host,
+                                        const float* d_colors, const float* d_opacity, float* d_sigmas, float* d_rgbs,
+                                        fsn_stream_t stream) {
+  FSN_REQUIRE(d_colors || N <= 0 || R <= 0, FSN_E_INVALID, "fsn_composite_packed_bwd: null pointer");
+  return composite_bwd_launch("fsn_composite_packed_bwd", sigmas, rgbs, t_starts, t_ends, ray_indices, N, R, bkgd_host,
+                              d_colors, d_opacity, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_sigmas, d_rgbs,
+                              stream);
 }
 
 extern "C" int fsn_distortion_fwd(const float* weights, const float* t_starts, const float* t_ends,

@@ -324,10 +324,9 @@ __global__ void k_ray_grad(const float* __restrict__ d_x, const float* __restric
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * 4 + wave;
   if (r >= R) return;
-  const int64_t beg = ray_lower_bound(ri, N, r);
-  const int64_t S = ray_lower_bound(ri, N, r + 1) - beg;
+  const auto [beg, S] = ray_span(ri, N, r);
   float so[3] = {0.f, 0.f, 0.f}, sd[3] = {0.f, 0.f, 0.f};
-  for (int64_t i = lane; i < S; i += 64) {
+  for (int i = lane; i < S; i += 64) {
     const int64_t k = beg + i;
     const float m = (t0[k] + t1[k]) / 2.0f;
 #pragma unroll
@@ -358,30 +357,11 @@ extern "C" int fsn_nerf_train_bwd_inputs(const fsn_mlp_desc* desc, int prec, con
                                          const float* rays_d, const int64_t* ray_indices, const float* t_starts,
                                          const float* t_ends, const float* pos_mask, const float* dir_mask, float* d_x,
                                          float* d_dirs, fsn_stream_t stream) {
-  FSN_REQUIRE(desc, FSN_E_INVALID, "null desc");
-  NetGeom G;
-  const char* why;
-  const int rc = build_geom(*desc, FSN_PREC_FP16X3, G, &why);
-  FSN_REQUIRE(rc == FSN_OK, rc, "training path: %s", why);
-  FSN_REQUIRE(prec >= 0 && prec <= FSN_PREC_FP16, FSN_E_INVALID, "fsn_nerf_train_bwd_inputs: unknown precision");
-  FSN_REQUIRE(n >= 0, FSN_E_INVALID, "fsn_nerf_train_bwd_inputs: n < 0");
-  if (n == 0) return FSN_OK;
-  FSN_REQUIRE(W && ws && out && d_out, FSN_E_INVALID, "fsn_nerf_train_bwd_inputs: null pointer");
-  FSN_REQUIRE((dW == nullptr) == (db == nullptr), FSN_E_INVALID,
-              "fsn_nerf_train_bwd_inputs: d_weights and d_biases go together (both NULL: input gradients only)");
-  FSN_REQUIRE(n < (1ll << 31), FSN_E_UNSUPPORTED, "fsn_nerf_train_bwd_inputs: n too large for one call");
-  FSN_REQUIRE((stage_scales == nullptr) == (stage_amax == nullptr), FSN_E_INVALID,
-              "fsn_nerf_train_bwd_inputs: stage_scales and stage_amax go together");
   const bool ray_form = rays_o || rays_d || ray_indices || t_starts || t_ends;
-  if (ray_form)
-    FSN_REQUIRE(rays_o && rays_d && ray_indices && t_starts && t_ends && !x && !dirs, FSN_E_INVALID,
-                "fsn_nerf_train_bwd_inputs: the ray form takes all five ray pointers and neither x nor dirs");
-  else
-    FSN_REQUIRE(x && dirs, FSN_E_INVALID, "fsn_nerf_train_bwd_inputs: needs x and dirs, or the ray form's five pointers");
   const TrainRays rays{rays_o, rays_d, t_starts, t_ends, ray_indices};
   const InputGradReq rq{x, dirs, ray_form ? &rays : nullptr, pos_mask, dir_mask, d_x, d_dirs};
-  return fused_train_bwd(desc, prec, W, n, ws, out, d_out, grad_scale, dW, db, accumulate != 0, stage_scales, stage_amax,
-                         status, as_stream(stream), &rq);
+  return train_bwd_checked("fsn_nerf_train_bwd_inputs", desc, prec, W, n, ws, out, d_out, grad_scale, dW, db, accumulate,
+                           stage_scales, stage_amax, status, stream, &rq);
 }
 
 extern "C" int fsn_ray_grad_reduce(const float* d_x, const float* d_dirs, const int64_t* ray_indices, const float* t_starts,

@@ -117,9 +117,9 @@ __device__ __forceinline__ int march_ray(const GridDev& G, const uint32_t* __res
   return total;
 }
 
-// Per-ray bounds (fsn_occgrid_march_ex): t_lo = max(t_enter, near_r, t_min_r), t_hi = min(t_exit, far_plane, t_max_r),
-// in that order; the lattice itself (near_r, step) is ray_lattice's.  +-inf bounds are allowed; t_max_r <= t_min_r
-// leaves no samples.
+// Per-ray bounds (k_occ_march; +-inf where fsn_occgrid_march_ex got none, and for fsn_occgrid_march):
+// t_lo = max(t_enter, near_r, t_min_r), t_hi = min(t_exit, far_plane, t_max_r), in that order; the lattice itself
+// (near_r, step) is ray_lattice's.  +-inf bounds are allowed; t_max_r <= t_min_r leaves no samples.
 __device__ __forceinline__ RayLattice ray_lattice_bounded(const GridDev& G, const float (&o)[3], const float (&d)[3],
                                                           float near_plane, float far_plane, float step, bool has_u,
                                                           float u_r, float t_min_r, float t_max_r) {

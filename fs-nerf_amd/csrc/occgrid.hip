@@ -11,9 +11,10 @@
 //    min(t_exit, far_plane)) of the outermost box and the cell of its MIDPOINT, at the finest level containing
 //    the midpoint, is occupied.  One wavefront per ray, 64 lattice points per iteration, ballot + popcount
 //    ranks; two passes (count, fill) around an exclusive scan of the counts.
-//  * march_ex: the same march inside per-ray bounds [t_min_r, t_max_r], and the cone regime (cone_angle > 0): the step
-//    grows with distance, dt = max(t cone_angle, step), taken once per block of 64 intervals (occ_dev.hpp,
-//    march_ray_cone; include/fsnerf_hip.h has the definition, tests/occ_cone_ref.py restates it).
+//    ONE kernel (k_occ_march) serves fsn_occgrid_march and fsn_occgrid_march_ex: the latter adds per-ray bounds
+//    [t_min_r, t_max_r] and the cone regime (cone_angle > 0): the step grows with distance, dt = max(t cone_angle, step),
+//    taken once per block of 64 intervals (occ_dev.hpp, march_ray_cone; include/fsnerf_hip.h has the definition,
+//    tests/occ_cone_ref.py restates it).  The plain entry point is the extended one with no bounds and cone_angle 0.
 //  * visibility: T_i = exp(-sum_{j<i} sigma_j dt_j) per ray (prefix scan), keep iff T_i >= early_stop_eps and
 //    alpha_i >= alpha_thre.
 //  * update: occs[c] = max(occs[c]*decay, occ_c) for the evaluated cells; bit = occs > threshold.
@@ -23,40 +24,16 @@
 
 namespace fsn {
 
-// pass 0: counts[r]; pass 1: fill ray_indices / t_starts / t_ends at offsets[r]
+// pass 0: counts[r]; pass 1: fill ray_indices / t_starts / t_ends at offsets[r].  Per-ray bounds t_min / t_max (either
+// may be null: -inf / +inf) and the cone regime (cone_angle > 0: march_ray_cone; == 0: the lattice inside the tightened
+// range, a wave-uniform branch).  Both entry points launch this kernel; the plain one passes no bounds and cone 0.
 template <bool FILL>
 __global__ void k_occ_march(const float* __restrict__ rays_o, const float* __restrict__ rays_d, int64_t R, GridDev G,
                             const uint32_t* __restrict__ bits, float near_plane, float far_plane, float step,
-                            const float* __restrict__ u, int32_t max_steps, int64_t* __restrict__ counts,
+                            const float* __restrict__ u, int32_t max_steps, const float* __restrict__ t_min,
+                            const float* __restrict__ t_max, float cone_angle, int64_t* __restrict__ counts,
                             const int64_t* __restrict__ offsets, int64_t* __restrict__ ray_indices,
                             float* __restrict__ t_starts, float* __restrict__ t_ends) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + wave;
-  if (r >= R) return;
-  const float o[3] = {rays_o[3 * r], rays_o[3 * r + 1], rays_o[3 * r + 2]};
-  const float d[3] = {rays_d[3 * r], rays_d[3 * r + 1], rays_d[3 * r + 2]};
-  const RayLattice L = ray_lattice(G, o, d, near_plane, far_plane, step, u != nullptr, u ? u[r] : 0.f);
-  const int64_t base_out = FILL ? offsets[r] : 0;
-  const int total = march_ray(G, bits, o, d, L, step, max_steps, [&](float ts, float te, bool keep, uint64_t m, int before) {
-    if (FILL && keep) {
-      const int64_t pos = base_out + before + __popcll(m & ((1ull << lane) - 1ull));
-      ray_indices[pos] = r;
-      t_starts[pos] = ts;
-      t_ends[pos] = te;
-    }
-  });
-  if (!FILL && lane == 0) counts[r] = total;
-}
-
-// fsn_occgrid_march_ex: k_occ_march with per-ray bounds t_min / t_max (either may be null) and the cone regime
-// (cone_angle > 0: march_ray_cone; == 0: today's lattice inside the tightened range).  Same launch structure.
-template <bool FILL>
-__global__ void k_occ_march_ex(const float* __restrict__ rays_o, const float* __restrict__ rays_d, int64_t R, GridDev G,
-                               const uint32_t* __restrict__ bits, float near_plane, float far_plane, float step,
-                               const float* __restrict__ u, int32_t max_steps, const float* __restrict__ t_min,
-                               const float* __restrict__ t_max, float cone_angle, int64_t* __restrict__ counts,
-                               const int64_t* __restrict__ offsets, int64_t* __restrict__ ray_indices,
-                               float* __restrict__ t_starts, float* __restrict__ t_ends) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * 4 + wave;
   if (r >= R) return;
@@ -118,12 +95,7 @@ __global__ void k_visibility(const float* __restrict__ sig, const float* __restr
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * 4 + wave;
   if (r >= R) return;
-  int64_t lo = 0, hi = N;
-  while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (ri[mid] < r) lo = mid + 1; else hi = mid; }
-  const int64_t beg = lo;
-  hi = N;
-  while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (ri[mid] < r + 1) lo = mid + 1; else hi = mid; }
-  const int S = (int)(lo - beg);
+  const auto [beg, S] = ray_span(ri, N, r);
   if (S == 0) return;
   const int per = (S + 63) >> 6;
   const int i0 = lane * per, i1 = min(i0 + per, S);
@@ -239,28 +211,43 @@ int launch_occ_word_prefix(const uint32_t* bits, int n_words, int levels, int32_
 
 using namespace fsn;
 
+// the argument checks and the count / fill launch of both march entry points (`who` prefixes the messages; the plain
+// entry point passes cone_angle 0, which the two cone checks let through)
+static int occ_march_launch(const char* who, const float* rays_o, const float* rays_d, int64_t R, const float* aabb_host,
+                            int res, int levels, const uint32_t* bits, float near_plane, float far_plane, float step,
+                            const float* u, int max_steps, const float* t_min, const float* t_max, float cone_angle,
+                            int64_t* counts, const int64_t* offsets, int64_t* ray_indices, float* t_starts, float* t_ends,
+                            fsn_stream_t stream) {
+  GridDev G;
+  const int rc = make_grid(aabb_host, res, levels, G);
+  if (rc != FSN_OK) return rc;
+  FSN_REQUIRE(R >= 0 && step > 0.f && max_steps > 0, FSN_E_INVALID, "%s: bad arguments", who);
+  FSN_REQUIRE(cone_angle >= 0.f, FSN_E_INVALID, "%s: cone_angle must not be negative", who);
+  FSN_REQUIRE(!(cone_angle > 0.f && near_plane < 0.f), FSN_E_INVALID, "%s: the cone regime needs near_plane >= 0", who);
+  if (R == 0) return FSN_OK;
+  FSN_REQUIRE(rays_o && rays_d && bits, FSN_E_INVALID, "%s: null pointer", who);
+  const unsigned grid = (unsigned)((R + 3) / 4);
+  if (offsets) {
+    FSN_REQUIRE(ray_indices && t_starts && t_ends, FSN_E_INVALID, "%s: fill pass needs the outputs", who);
+    k_occ_march<true><<<grid, 256, 0, as_stream(stream)>>>(rays_o, rays_d, R, G, bits, near_plane, far_plane, step, u,
+                                                           max_steps, t_min, t_max, cone_angle, nullptr, offsets,
+                                                           ray_indices, t_starts, t_ends);
+  } else {
+    FSN_REQUIRE(counts, FSN_E_INVALID, "%s: count pass needs `counts`", who);
+    k_occ_march<false><<<grid, 256, 0, as_stream(stream)>>>(rays_o, rays_d, R, G, bits, near_plane, far_plane, step, u,
+                                                            max_steps, t_min, t_max, cone_angle, counts, nullptr, nullptr,
+                                                            nullptr, nullptr);
+  }
+  FSN_LAUNCH_CHECK("k_occ_march");
+  return FSN_OK;
+}
+
 extern "C" int fsn_occgrid_march(const float* rays_o, const float* rays_d, int64_t R, const float* aabb_host, int res,
                                  int levels, const uint32_t* bits, float near_plane, float far_plane, float step,
                                  const float* u, int max_steps, int64_t* counts, const int64_t* offsets,
                                  int64_t* ray_indices, float* t_starts, float* t_ends, fsn_stream_t stream) {
-  GridDev G;
-  const int rc = make_grid(aabb_host, res, levels, G);
-  if (rc != FSN_OK) return rc;
-  FSN_REQUIRE(R >= 0 && step > 0.f && max_steps > 0, FSN_E_INVALID, "fsn_occgrid_march: bad arguments");
-  if (R == 0) return FSN_OK;
-  FSN_REQUIRE(rays_o && rays_d && bits, FSN_E_INVALID, "fsn_occgrid_march: null pointer");
-  const unsigned grid = (unsigned)((R + 3) / 4);
-  if (offsets) {
-    FSN_REQUIRE(ray_indices && t_starts && t_ends, FSN_E_INVALID, "fsn_occgrid_march: fill pass needs the outputs");
-    k_occ_march<true><<<grid, 256, 0, as_stream(stream)>>>(rays_o, rays_d, R, G, bits, near_plane, far_plane, step, u,
-                                                           max_steps, nullptr, offsets, ray_indices, t_starts, t_ends);
-  } else {
-    FSN_REQUIRE(counts, FSN_E_INVALID, "fsn_occgrid_march: count pass needs `counts`");
-    k_occ_march<false><<<grid, 256, 0, as_stream(stream)>>>(rays_o, rays_d, R, G, bits, near_plane, far_plane, step, u,
-                                                            max_steps, counts, nullptr, nullptr, nullptr, nullptr);
-  }
-  FSN_LAUNCH_CHECK("k_occ_march");
-  return FSN_OK;
+  return occ_march_launch("fsn_occgrid_march", rays_o, rays_d, R, aabb_host, res, levels, bits, near_plane, far_plane, step,
+                          u, max_steps, nullptr, nullptr, 0.f, counts, offsets, ray_indices, t_starts, t_ends, stream);
 }
 
 extern "C" int fsn_occgrid_march_ex(const float* rays_o, const float* rays_d, int64_t R, const float* aabb_host, int res,
@@ -268,29 +255,9 @@ extern "C" int fsn_occgrid_march_ex(const float* rays_o, const float* rays_d, in
                                     const float* u, int max_steps, const float* t_min, const float* t_max,
                                     float cone_angle, int64_t* counts, const int64_t* offsets, int64_t* ray_indices,
                                     float* t_starts, float* t_ends, fsn_stream_t stream) {
-  GridDev G;
-  const int rc = make_grid(aabb_host, res, levels, G);
-  if (rc != FSN_OK) return rc;
-  FSN_REQUIRE(R >= 0 && step > 0.f && max_steps > 0, FSN_E_INVALID, "fsn_occgrid_march_ex: bad arguments");
-  FSN_REQUIRE(cone_angle >= 0.f, FSN_E_INVALID, "fsn_occgrid_march_ex: cone_angle must not be negative");
-  FSN_REQUIRE(!(cone_angle > 0.f && near_plane < 0.f), FSN_E_INVALID,
-              "fsn_occgrid_march_ex: the cone regime needs near_plane >= 0");
-  if (R == 0) return FSN_OK;
-  FSN_REQUIRE(rays_o && rays_d && bits, FSN_E_INVALID, "fsn_occgrid_march_ex: null pointer");
-  const unsigned grid = (unsigned)((R + 3) / 4);
-  if (offsets) {
-    FSN_REQUIRE(ray_indices && t_starts && t_ends, FSN_E_INVALID, "fsn_occgrid_march_ex: fill pass needs the outputs");
-    k_occ_march_ex<true><<<grid, 256, 0, as_stream(stream)>>>(rays_o, rays_d, R, G, bits, near_plane, far_plane, step, u,
-                                                              max_steps, t_min, t_max, cone_angle, nullptr, offsets,
-                                                              ray_indices, t_starts, t_ends);
-  } else {
-    FSN_REQUIRE(counts, FSN_E_INVALID, "fsn_occgrid_march_ex: count pass needs `counts`");
-    k_occ_march_ex<false><<<grid, 256, 0, as_stream(stream)>>>(rays_o, rays_d, R, G, bits, near_plane, far_plane, step, u,
-                                                               max_steps, t_min, t_max, cone_angle, counts, nullptr,
-                                                               nullptr, nullptr, nullptr);
-  }
-  FSN_LAUNCH_CHECK("k_occ_march_ex");
-  return FSN_OK;
+  return occ_march_launch("fsn_occgrid_march_ex", rays_o, rays_d, R, aabb_host, res, levels, bits, near_plane, far_plane,
+                          step, u, max_steps, t_min, t_max, cone_angle, counts, offsets, ray_indices, t_starts, t_ends,
+                          stream);
 }
 
 extern "C" int fsn_ray_aabb_intersect(const float* rays_o, const float* rays_d, int64_t R, const float* aabbs, int M,

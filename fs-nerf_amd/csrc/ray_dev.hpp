@@ -41,6 +41,18 @@ __device__ __forceinline__ int64_t ray_lower_bound(const int64_t* __restrict__ a
   return lo;
 }
 
+// samples [beg, beg + S) of ray r in packed order (ri: the sorted ray index of each of the N samples)
+struct RaySpan {
+  int64_t beg;
+  int S;
+};
+__device__ __forceinline__ RaySpan ray_span(const int64_t* __restrict__ ri, int64_t N, int64_t r) {
+  // (both searches over all of [0, N): they share their first probes, which the second then finds in the cache.
+  // profiles/r07_bench_composite_bwd.jsonl has both forms timed: tag branch-span-from-beg started the second at `beg`)
+  const int64_t beg = ray_lower_bound(ri, N, r);
+  return {beg, (int)(ray_lower_bound(ri, N, r + 1) - beg)};
+}
+
 struct CompositeOut {
   float* colors;   // [3]
   float* opacity;  // [1]

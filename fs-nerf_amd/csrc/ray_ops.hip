@@ -177,17 +177,8 @@ __global__ void k_composite_dense(const float* __restrict__ sig, const float* __
   composite_ray(sig + b, rgb + 3 * b, t0 + b, t1 + b, S, bk.has != 0, bk.c[0], bk.c[1], bk.c[2], o);
 }
 
-// packed form: the ray's sample range is found by two binary searches in the sorted
-// ray_indices, then the same per-wave routine runs on that slice.
-__device__ __forceinline__ int64_t lower_bound_i64(const int64_t* __restrict__ a, int64_t n, int64_t key) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (a[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
+// packed form: the ray's sample range in the sorted ray_indices (ray_span), then the same per-wave routine runs on
+// that slice.
 __global__ void k_composite_packed(const float* __restrict__ sig, const float* __restrict__ rgb,
                                    const float* __restrict__ t0, const float* __restrict__ t1,
                                    const int64_t* __restrict__ ri, int64_t N, int64_t R, Bkgd bk,
@@ -197,11 +188,10 @@ __global__ void k_composite_packed(const float* __restrict__ sig, const float* _
   const int wave = threadIdx.x >> 6;
   const int64_t r = (int64_t)blockIdx.x * 4 + wave;
   if (r >= R) return;
-  const int64_t b = lower_bound_i64(ri, N, r);
-  const int64_t e = lower_bound_i64(ri, N, r + 1);
+  const auto [b, S] = ray_span(ri, N, r);
   CompositeOut o{colors + 3 * r, opacity + r, depth + r, weights ? weights + b : nullptr,
                  alphas ? alphas + b : nullptr, trans ? trans + b : nullptr};
-  composite_ray(sig + b, rgb + 3 * b, t0 + b, t1 + b, (int)(e - b), bk.has != 0, bk.c[0], bk.c[1], bk.c[2], o);
+  composite_ray(sig + b, rgb + 3 * b, t0 + b, t1 + b, S, bk.has != 0, bk.c[0], bk.c[1], bk.c[2], o);
 }
 
 // ---------------------------------------------------------------- "next" rows
@@ -214,14 +204,14 @@ __global__ void k_occl_ray_sums(const float* __restrict__ sig, const float* __re
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * 4 + wave;
   if (r >= R) return;
-  const int64_t lo = lower_bound_i64(ri, N, r), hi = lower_bound_i64(ri, N, r + 1);
+  const auto [beg, S] = ray_span(ri, N, r);
   float acc = 0.f;
-  for (int64_t i = lo + lane; i < hi; i += 64) {
+  for (int64_t i = beg + lane; i < beg + S; i += 64) {
     const float w = func == 0 ? (-a * t[i] + b) : (a * expf(-b * t[i]));
     acc += w * sig[i];
   }
   acc = wave_sum(acc);
-  if (lane == 0) sums[r] = (hi > lo) ? acc : __builtin_nanf("");  // NaN marks "no samples"
+  if (lane == 0) sums[r] = S > 0 ? acc : __builtin_nanf("");  // NaN marks "no samples"
 }
 
 __global__ void k_occl_mean(const float* __restrict__ sums, int64_t R, float* __restrict__ out) {

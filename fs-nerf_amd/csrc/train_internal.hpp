@@ -1,4 +1,5 @@
-// train_internal.hpp — entry points of the fused (MFMA) training path, called from the C-ABI in train.hip.
+// train_internal.hpp — entry points of the fused (MFMA) training path, called from the C-ABI in train.hip and
+// input_grad.hip.
 #pragma once
 #include "common.hpp"
 
@@ -24,6 +25,14 @@ int fused_train_bwd(const fsn_mlp_desc* d, int prec, const float* const* W, int6
                     const float* d_out, const float* grad_scale_dev, float* const* dW, float* const* db,
                     bool accumulate, float* bscale, uint32_t* bamax, uint32_t* status, hipStream_t s,
                     const InputGradReq* ig = nullptr);
+
+// train.hip: the descriptor check of the training path, and the validated body shared by fsn_nerf_train_bwd (rq null)
+// and fsn_nerf_train_bwd_inputs (`who` prefixes the messages).
+int check_desc(const fsn_mlp_desc* d);
+int train_bwd_checked(const char* who, const fsn_mlp_desc* desc, int prec, const float* const* W, int64_t n, float* ws,
+                      const float* out, const float* d_out, const float* grad_scale, float* const* dW, float* const* db,
+                      int accumulate, float* stage_scales, uint32_t* stage_amax, uint32_t* status, fsn_stream_t stream,
+                      const InputGradReq* rq);
 
 // k_input_grad (input_grad.hip), launched by fused_train_bwd between the dgrad chain and k_bwd_rescale.  The packed
 // weight slices go where the chain's transposed-weight stream lay (dead once the chain has run).

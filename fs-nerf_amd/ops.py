@@ -748,6 +748,24 @@ def _check_into(into, ws_):
     return dW, db
 
 
+def _grad_buffers(ws_, n: int, into, prec: int, d_out: Tensor, param_grads: bool = True):
+    """-> (d_weights, d_biases, scale) of a training backward over n samples: `into` validated, else fresh buffers (zeros
+    at n == 0, where nothing is launched; both None without `param_grads`), and the fp16 modes' loss scale."""
+    if not param_grads:
+        if into is not None:
+            raise ValueError("nerf_train_bwd_inputs: `into` needs param_grads")
+        dW = db = None
+    elif into is not None:
+        dW, db = _check_into(into, ws_)
+    elif n == 0:  # e.g. the all-background first batch of an empty occupancy grid (run-nerf.py:243 precedes :293)
+        dW, db = [torch.zeros_like(w) for w in ws_], [torch.zeros(w.shape[0], device=w.device) for w in ws_]
+    else:
+        dW = [torch.empty_like(w) for w in ws_]
+        db = [torch.empty(w.shape[0], device=w.device, dtype=torch.float32) for w in ws_]
+    scale = grad_scale_for(d_out) if n > 0 and prec in (L.FSN_PREC_FP16X3, L.FSN_PREC_FP16) else None
+    return dW, db, scale
+
+
 def nerf_train_bwd(desc: L.MlpDesc, prec: int, weights: Sequence[Tensor], work: Tensor, out: Tensor, d_out: Tensor,
                    status: Optional[Tensor] = None, into: Optional[Tuple[Sequence[Tensor], Sequence[Tensor]]] = None,
                    stage_state: Optional[Tuple[Tensor, Tensor]] = None):
@@ -759,16 +777,9 @@ def nerf_train_bwd(desc: L.MlpDesc, prec: int, weights: Sequence[Tensor], work: 
     ws_ = [_f32(w.detach(), "weight") for w in weights]
     d_out = _f32(d_out, "d_out").reshape(-1, 4)
     n = d_out.shape[0]
-    if into is not None:
-        dW, db = _check_into(into, ws_)
-        if n == 0:
-            return dW, db
-    else:
-        if n == 0:  # e.g. the all-background first batch of an empty occupancy grid (run-nerf.py:243 precedes :293)
-            return [torch.zeros_like(w) for w in ws_], [torch.zeros(w.shape[0], device=w.device) for w in ws_]
-        dW = [torch.empty_like(w) for w in ws_]
-        db = [torch.empty(w.shape[0], device=w.device, dtype=torch.float32) for w in ws_]
-    scale = grad_scale_for(d_out) if prec in (L.FSN_PREC_FP16X3, L.FSN_PREC_FP16) else None
+    dW, db, scale = _grad_buffers(ws_, n, into, prec, d_out)
+    if n == 0:
+        return dW, db
     with torch.cuda.device(work.device):
         L.check(L.lib().fsn_nerf_train_bwd(C.byref(desc), prec, _ptr_array(ws_), n, _p(work), _p(out), _p(d_out),
                                            _p(scale), _ptr_array(dW), _ptr_array(db), 0 if into is None else 1,
@@ -811,20 +822,9 @@ def nerf_train_bwd_inputs(desc: L.MlpDesc, prec: int, weights: Sequence[Tensor],
     # (the kernel writes every row of a call with samples; a call without samples launches nothing)
     d_x = torch.empty(n, 3, device=dev, dtype=torch.float32) if want_x else None
     d_dirs = torch.empty(n, 3, device=dev, dtype=torch.float32) if want_dirs else None
-    if not param_grads:
-        dW = db = None
-        if into is not None:
-            raise ValueError("nerf_train_bwd_inputs: `into` needs param_grads")
-    elif into is not None:
-        dW, db = _check_into(into, ws_)
-    elif n == 0:  # e.g. the all-background first batch of an empty occupancy grid (run-nerf.py:243 precedes :293)
-        dW, db = [torch.zeros_like(w) for w in ws_], [torch.zeros(w.shape[0], device=w.device) for w in ws_]
-    else:
-        dW = [torch.empty_like(w) for w in ws_]
-        db = [torch.empty(w.shape[0], device=w.device, dtype=torch.float32) for w in ws_]
+    dW, db, scale = _grad_buffers(ws_, n, into, prec, d_out, param_grads)
     if n == 0:
         return dW, db, d_x, d_dirs
-    scale = grad_scale_for(d_out) if prec in (L.FSN_PREC_FP16X3, L.FSN_PREC_FP16) else None
     pm = None if pos_mask is None else _f32(pos_mask, "pos_mask")
     dm = None if dir_mask is None else _f32(dir_mask, "dir_mask")
     with torch.cuda.device(work.device):
@@ -857,25 +857,10 @@ def ray_grad_reduce(d_x: Optional[Tensor], d_dirs: Optional[Tensor], ray_indices
     return d_o, d_d
 
 
-def composite_packed_bwd(sigmas, rgbs, t_starts, t_ends, ray_indices, n_rays, bkgd, d_colors, d_opacity):
-    sig, rgb = _f32(sigmas, "sigmas"), _f32(rgbs, "rgbs")
-    t0, t1 = _f32(t_starts, "t_starts"), _f32(t_ends, "t_ends")
-    ri = _i64(ray_indices, "ray_indices")
-    N = sig.numel()
-    dc = _f32(d_colors, "d_colors")
-    dop = None if d_opacity is None else _f32(d_opacity, "d_opacity").reshape(-1)
-    ds, dr = torch.empty_like(sig), torch.empty_like(rgb)
-    with torch.cuda.device(sig.device):
-        L.check(L.lib().fsn_composite_packed_bwd(_p(sig), _p(rgb), _p(t0), _p(t1), _p(ri), N, n_rays, _bk(bkgd), _p(dc),
-                                                 _p(dop), _p(ds), _p(dr), _stream()), "fsn_composite_packed_bwd")
-    return ds, dr
-
-
-def composite_packed_bwd_full(sigmas, rgbs, t_starts, t_ends, ray_indices, n_rays, bkgd, d_colors, d_opacity, opacity=None,
-                              depth=None, d_depth=None, d_weights=None, d_alphas=None, d_trans=None):
-    """The full backward of `composite_packed` (fsn_composite_packed_bwd_full): -> (d_sigmas [N], d_rgbs [N,3]) from the
-    cotangents of all six outputs.  Every cotangent may be None: it reaches the kernel as a NULL pointer and its term is
-    absent.  `opacity` / `depth` are the forward's outputs, needed when `d_depth` is given."""
+def _composite_bwd(lean, sigmas, rgbs, t_starts, t_ends, ray_indices, n_rays, bkgd, d_colors, d_opacity, opacity=None,
+                   depth=None, d_depth=None, d_weights=None, d_alphas=None, d_trans=None):
+    """Both forms of the compositor's backward: `lean` calls fsn_composite_packed_bwd, which takes the first two
+    cotangents only; the kernel behind the two entry points is the same one."""
     sig, rgb = _f32(sigmas, "sigmas"), _f32(rgbs, "rgbs")
     t0, t1 = _f32(t_starts, "t_starts"), _f32(t_ends, "t_ends")
     ri = _i64(ray_indices, "ray_indices")
@@ -894,13 +879,32 @@ def composite_packed_bwd_full(sigmas, rgbs, t_starts, t_ends, ray_indices, n_ray
                                                             (d_depth, "d_depth")))
     dw, da, dt = (opt(t, name, N) for t, name in ((d_weights, "d_weights"), (d_alphas, "d_alphas"), (d_trans, "d_trans")))
     if t0.numel() != N or t1.numel() != N or ri.numel() != N or rgb.numel() != 3 * N:
-        raise ValueError("composite_packed_bwd_full: sigmas, rgbs, t_starts, t_ends and ray_indices disagree in length")
+        raise ValueError(f"composite_packed_bwd{'' if lean else '_full'}: sigmas, rgbs, t_starts, t_ends and ray_indices "
+                         "disagree in length")
     ds, dr = torch.empty_like(sig), torch.empty_like(rgb)
+    head, tail = (_p(sig), _p(rgb), _p(t0), _p(t1), _p(ri), N, n_rays, _bk(bkgd), _p(dc), _p(dop)), (_p(ds), _p(dr), _stream())
     with torch.cuda.device(sig.device):
-        L.check(L.lib().fsn_composite_packed_bwd_full(_p(sig), _p(rgb), _p(t0), _p(t1), _p(ri), N, n_rays, _bk(bkgd), _p(dc),
-                                                      _p(dop), _p(op), _p(dep), _p(dd), _p(dw), _p(da), _p(dt), _p(ds),
-                                                      _p(dr), _stream()), "fsn_composite_packed_bwd_full")
+        if lean:
+            L.check(L.lib().fsn_composite_packed_bwd(*head, *tail), "fsn_composite_packed_bwd")
+        else:
+            L.check(L.lib().fsn_composite_packed_bwd_full(*head, _p(op), _p(dep), _p(dd), _p(dw), _p(da), _p(dt), *tail),
+                    "fsn_composite_packed_bwd_full")
     return ds, dr
+
+
+def composite_packed_bwd(sigmas, rgbs, t_starts, t_ends, ray_indices, n_rays, bkgd, d_colors, d_opacity):
+    """The backward of `composite_packed` for the cotangents of colours (required) and opacity: the training step's."""
+    return _composite_bwd(True, sigmas, rgbs, t_starts, t_ends, ray_indices, n_rays, bkgd, _f32(d_colors, "d_colors"),
+                          d_opacity)
+
+
+def composite_packed_bwd_full(sigmas, rgbs, t_starts, t_ends, ray_indices, n_rays, bkgd, d_colors, d_opacity, opacity=None,
+                              depth=None, d_depth=None, d_weights=None, d_alphas=None, d_trans=None):
+    """The full backward of `composite_packed` (fsn_composite_packed_bwd_full): -> (d_sigmas [N], d_rgbs [N,3]) from the
+    cotangents of all six outputs.  Every cotangent may be None: it reaches the kernel as a NULL pointer and its term is
+    absent.  `opacity` / `depth` are the forward's outputs, needed when `d_depth` is given."""
+    return _composite_bwd(False, sigmas, rgbs, t_starts, t_ends, ray_indices, n_rays, bkgd, d_colors, d_opacity, opacity,
+                          depth, d_depth, d_weights, d_alphas, d_trans)
 
 
 class _DistortionFn(torch.autograd.Function):
@@ -943,27 +947,24 @@ def occgrid_march(rays_o: Tensor, rays_d: Tensor, aabb: Sequence[float], res: in
                   t_min: Optional[Tensor] = None, t_max: Optional[Tensor] = None, cone_angle: float = 0.0):
     """Lattice march through the occupancy grid -> (ray_indices int64 [N], t_starts [N], t_ends [N], counts [R]).
     Two launches around an exclusive scan of the per-ray counts; one host sync for N (as nerfacc's does).
-    Per-ray bounds `t_min` / `t_max` [R] or a `cone_angle` > 0 (the step grows with distance) take the extended entry
-    point fsn_occgrid_march_ex (include/fsnerf_hip.h has the definition); without them the call is fsn_occgrid_march."""
+    Optional per-ray bounds `t_min` / `t_max` [R] and a `cone_angle` > 0 (the step grows with distance): every call
+    goes through fsn_occgrid_march_ex (include/fsnerf_hip.h has the definition), of which fsn_occgrid_march is the form
+    without bounds and with cone_angle 0 - one kernel serves both."""
     o, d = _f32(rays_o, "rays_o").reshape(-1, 3), _f32(rays_d, "rays_d").reshape(-1, 3)
     R = o.shape[0]
     ab = (C.c_float * 6)(*[float(v) for v in aabb])
     u_ = None if u is None else _f32(u, "u").reshape(-1)
     if u_ is not None and u_.numel() != R:
         raise ValueError("u must hold one value per ray")
+    bounds = [None if t is None else _f32(t, k).reshape(-1) for t, k in ((t_min, "t_min"), (t_max, "t_max"))]
+    if any(t is not None and t.numel() != R for t in bounds):
+        raise ValueError("t_min / t_max must hold one value per ray")
     args = (_p(o), _p(d), R, ab, int(res), int(levels), _p(bits), float(near_plane), float(far_plane), float(step), _p(u_),
-            int(max_steps))
-    name = "fsn_occgrid_march"
-    if t_min is not None or t_max is not None or cone_angle != 0.0:
-        bounds = [None if t is None else _f32(t, k).reshape(-1) for t, k in ((t_min, "t_min"), (t_max, "t_max"))]
-        if any(t is not None and t.numel() != R for t in bounds):
-            raise ValueError("t_min / t_max must hold one value per ray")
-        args += (_p(bounds[0]), _p(bounds[1]), float(cone_angle))
-        name = "fsn_occgrid_march_ex"
+            int(max_steps), _p(bounds[0]), _p(bounds[1]), float(cone_angle))
     counts = torch.zeros(R, device=o.device, dtype=torch.int64)
     with torch.cuda.device(o.device):
-        march = getattr(L.lib(), name)
-        L.check(march(*args, _p(counts), None, None, None, None, _stream()), name)
+        march = L.lib().fsn_occgrid_march_ex
+        L.check(march(*args, _p(counts), None, None, None, None, _stream()), "fsn_occgrid_march_ex")
         ends = torch.cumsum(counts, 0)
         offsets = (ends - counts).contiguous()
         N = int(ends[-1].item()) if R > 0 else 0
@@ -971,7 +972,7 @@ def occgrid_march(rays_o: Tensor, rays_d: Tensor, aabb: Sequence[float], res: in
         t0 = torch.empty(N, device=o.device, dtype=torch.float32)
         t1 = torch.empty(N, device=o.device, dtype=torch.float32)
         if N > 0:
-            L.check(march(*args, None, _p(offsets), _p(ri), _p(t0), _p(t1), _stream()), name)
+            L.check(march(*args, None, _p(offsets), _p(ri), _p(t0), _p(t1), _stream()), "fsn_occgrid_march_ex")
     return ri, t0, t1, counts
 
 

@@ -81,44 +81,33 @@ class StratifiedEstimator(nn.Module):
 
 
 class _CompositeFn(torch.autograd.Function):
-    """Volume integration with gradients to sigmas and rgbs (training step)."""
+    """Volume integration with gradients to sigmas and rgbs (training step).  Lean form: through colors
+    and opacity only.  `full` (`rendering(full_grad=True)`): through ALL six outputs - colors, opacity, depth and the
+    per-sample weights / alphas / trans; a cotangent nothing asked for arrives as None and reaches the kernel as a NULL
+    pointer (fsn_composite_packed_bwd_full)."""
 
     @staticmethod
-    def forward(ctx, sigmas, rgbs, t_starts, t_ends, ray_indices, n_rays, bkgd):
+    def forward(ctx, sigmas, rgbs, t_starts, t_ends, ray_indices, n_rays, bkgd, full):
         colors, opacity, depth, ex = ops.composite_packed(sigmas, rgbs, t_starts, t_ends, ray_indices, n_rays, bkgd)
-        ctx.save_for_backward(ex["sigmas"], ex["rgbs"], t_starts, t_ends, ray_indices)
-        ctx.n_rays, ctx.bkgd = n_rays, bkgd
-        ctx.mark_non_differentiable(depth, ex["weights"], ex["alphas"], ex["trans"])
-        return colors, opacity, depth, ex["weights"], ex["alphas"], ex["trans"]
-
-    @staticmethod
-    def backward(ctx, d_colors, d_opacity, *_):
-        sig, rgb, t0, t1, ri = ctx.saved_tensors
-        ds, dr = ops.composite_packed_bwd(sig, rgb, t0, t1, ri, ctx.n_rays, ctx.bkgd, d_colors.contiguous(),
-                                          None if d_opacity is None else d_opacity.contiguous())
-        return ds.reshape(sig.shape), dr.reshape(rgb.shape), None, None, None, None, None
-
-
-class _CompositeFullFn(torch.autograd.Function):
-    """Volume integration with gradients to sigmas and rgbs through ALL six outputs (`rendering(full_grad=True)`):
-    colors, opacity, depth and the per-sample weights / alphas / trans.  A cotangent nothing asked for arrives as None
-    and reaches the kernel as a NULL pointer (fsn_composite_packed_bwd_full)."""
-
-    @staticmethod
-    def forward(ctx, sigmas, rgbs, t_starts, t_ends, ray_indices, n_rays, bkgd):
-        colors, opacity, depth, ex = ops.composite_packed(sigmas, rgbs, t_starts, t_ends, ray_indices, n_rays, bkgd)
-        ctx.save_for_backward(ex["sigmas"], ex["rgbs"], t_starts, t_ends, ray_indices, opacity, depth)
-        ctx.n_rays, ctx.bkgd = n_rays, bkgd
-        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(ex["sigmas"], ex["rgbs"], t_starts, t_ends, ray_indices, *((opacity, depth) if full else ()))
+        ctx.n_rays, ctx.bkgd, ctx.full = n_rays, bkgd, full
+        if full:
+            ctx.set_materialize_grads(False)
+        else:
+            ctx.mark_non_differentiable(depth, ex["weights"], ex["alphas"], ex["trans"])
         return colors, opacity, depth, ex["weights"], ex["alphas"], ex["trans"]
 
     @staticmethod
     def backward(ctx, d_colors, d_opacity, d_depth, d_weights, d_alphas, d_trans):
-        sig, rgb, t0, t1, ri, opacity, depth = ctx.saved_tensors
-        ds, dr = ops.composite_packed_bwd_full(sig, rgb, t0, t1, ri, ctx.n_rays, ctx.bkgd, d_colors, d_opacity,
-                                               opacity=opacity, depth=depth, d_depth=d_depth, d_weights=d_weights,
-                                               d_alphas=d_alphas, d_trans=d_trans)
-        return ds.reshape(sig.shape), dr.reshape(rgb.shape), None, None, None, None, None
+        sig, rgb, t0, t1, ri, *fwd = ctx.saved_tensors
+        if ctx.full:
+            ds, dr = ops.composite_packed_bwd_full(sig, rgb, t0, t1, ri, ctx.n_rays, ctx.bkgd, d_colors, d_opacity,
+                                                   opacity=fwd[0], depth=fwd[1], d_depth=d_depth, d_weights=d_weights,
+                                                   d_alphas=d_alphas, d_trans=d_trans)
+        else:
+            ds, dr = ops.composite_packed_bwd(sig, rgb, t0, t1, ri, ctx.n_rays, ctx.bkgd, d_colors.contiguous(),
+                                              None if d_opacity is None else d_opacity.contiguous())
+        return ds.reshape(sig.shape), dr.reshape(rgb.shape), None, None, None, None, None, None
 
 
 def rendering(t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor, n_rays: int,
@@ -139,8 +128,8 @@ def rendering(t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor, n_rays: int
     kernel_bk = None if bk_grad else render_bkgd
     if torch.is_grad_enabled() and (rgbs.requires_grad or sigmas.requires_grad):
         bk = None if kernel_bk is None else [float(v) for v in kernel_bk.detach().cpu().tolist()]
-        fn = _CompositeFullFn if full_grad else _CompositeFn
-        colors, opacity, depth, w, a, tr = fn.apply(sigmas, rgbs.contiguous(), t_starts, t_ends, ray_indices, n_rays, bk)
+        colors, opacity, depth, w, a, tr = _CompositeFn.apply(sigmas, rgbs.contiguous(), t_starts, t_ends, ray_indices,
+                                                              n_rays, bk, bool(full_grad))
         ex = {"weights": w, "alphas": a, "trans": tr, "sigmas": sigmas, "rgbs": rgbs}
     else:
         colors, opacity, depth, ex = ops.composite_packed(sigmas, rgbs, t_starts, t_ends, ray_indices, n_rays, kernel_bk)

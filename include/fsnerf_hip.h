@@ -455,8 +455,8 @@ int fsn_ray_grad_reduce(const float* d_x, const float* d_dirs, const int64_t* ra
  * are the launch's reduction words). */
 int fsn_grad_scale(const float* d_out, int64_t n, float* buf, fsn_stream_t stream);
 /* backward of fsn_composite_packed_fwd with respect to sigmas and rgbs, given dL/dcolors [R,3] and
- * (optional) dL/dopacity [R]; dL/ddepth is not propagated (the lean backward of the default training step;
- * fsn_composite_packed_bwd_full propagates every output's cotangent). */
+ * (optional) dL/dopacity [R]; dL/ddepth is not propagated (the lean backward of the default training step: a call of
+ * fsn_composite_packed_bwd_full's kernel with the other cotangents NULL; here d_colors is required). */
 int fsn_composite_packed_bwd(const float* sigmas, const float* rgbs, const float* t_starts, const float* t_ends,
                              const int64_t* ray_indices, int64_t N, int64_t R, const float* bkgd_host,
                              const float* d_colors, const float* d_opacity, float* d_sigmas, float* d_rgbs,
@@ -467,8 +467,8 @@ int fsn_composite_packed_bwd(const float* sigmas, const float* rgbs, const float
  *   d_depth [R]                        optional dL/ddepth
  *   d_weights, d_alphas, d_trans [N]   optional dL/dweights, dL/dalphas, dL/dtrans
  * Any optional pointer may be NULL, and here d_colors as well (that term is absent; nothing is loaded through it: a
- * loss on depth alone has no colour cotangent).  With only d_colors /
- * d_opacity given the results equal fsn_composite_packed_bwd's bit for bit.  The depth term follows
+ * loss on depth alone has no colour cotangent).  With only d_colors / d_opacity given this IS fsn_composite_packed_bwd:
+ * one kernel serves both entry points.  The depth term follows
  * depth = sum w m / max(opacity, eps): d depth / d w_i = (m_i - depth) / opacity for opacity >= eps, m_i / eps below.
  * No gradient goes to t_starts / t_ends.  One wave per ray, no atomics: deterministic. */
 int fsn_composite_packed_bwd_full(const float* sigmas, const float* rgbs, const float* t_starts, const float* t_ends,
@@ -528,7 +528,8 @@ int fsn_weight_norm_bwd(const float* arena, int n_seg, const int64_t* seg_off_ho
  *   [t_k, t_k+step) is a sample iff t_k lies in [max(t_enter, near_r), min(t_exit, far_plane)) of the outermost box
  *   and the cell of its midpoint (finest level containing it) is occupied; at most max_steps lattice points per ray.
  *   Two passes: offsets == NULL -> counts[R] (int64); else fill ray_indices / t_starts / t_ends at offsets[r]
- *   (exclusive scan of the counts, by the caller).
+ *   (exclusive scan of the counts, by the caller).  It is fsn_occgrid_march_ex with t_min = t_max = NULL and
+ *   cone_angle = 0: one kernel serves both entry points.
  * fsn_packed_visibility: keep[i] = (T_i >= early_stop_eps && alpha_i >= alpha_thre), T = exp(-exclusive sum of
  *   sigma*dt) per ray, samples packed and sorted by ray.
  * fsn_occgrid_update: occs[cells[i]] = max(occs[cells[i]]*decay, vals[i]) (cells must be unique), then, when

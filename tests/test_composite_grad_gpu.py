@@ -61,6 +61,8 @@ def _reference_grads(S, which):
 def _select(case, cot, which):
     if which == "all":
         return cot
+    if which == "colors+opacity":
+        return {k: cot[k] for k in ("colors", "opacity")}
     if which == "depth-ray7":
         d = torch.zeros_like(cot["depth"])
         d[CR.ZERO_RAY] = cot["depth"][CR.ZERO_RAY]
@@ -131,7 +133,8 @@ def test_full_backward_vs_float64_autograd(S, which):
 @pytest.mark.gpu
 @pytest.mark.parametrize("S", SIZES)
 def test_full_entry_point_equals_the_lean_one_bit_for_bit(S):
-    """G2: with only d_colors / d_opacity given."""
+    """G2: with only d_colors / d_opacity given.  Both entry points launch one kernel, so the equality shows that the
+    lean one hands its arguments through; the lean result is also held to float64 autograd on its own."""
     from fs_nerf_amd import ops
     case, cot, _, g, _ = _setup(S)
     dev = g["sig"].device
@@ -142,6 +145,11 @@ def test_full_entry_point_equals_the_lean_one_bit_for_bit(S):
             full = ops.composite_packed_bwd_full(g["sig"], g["rgb"], g["t0"], g["t1"], g["ri"], case["R"], bkgd, dc, op)
             assert torch.equal(full[0], lean[0]) and torch.equal(full[1], lean[1])
             assert float(lean[0].abs().max()) > 0
+    gs, gr = _reference_grads(S, "colors+opacity")
+    ds, dr = ops.composite_packed_bwd(g["sig"], g["rgb"], g["t0"], g["t1"], g["ri"], case["R"], BK, dc, dop)
+    es, er = _rel(ds, gs), _rel(dr, gr)
+    print(f"S={S} lean entry point against float64 autograd: d_sigmas={es:.3e} d_rgbs={er:.3e}")
+    assert es < TOL_GRAD and er < TOL_GRAD, (es, er)
 
 
 @pytest.mark.gpu

@@ -88,6 +88,38 @@ def test_march_matches_the_restatement(dev, kind, cone):
                 assert int(n[254]) > 0 and int(n[255]) > 0 and int((n[:120] > 0).sum()) == 120
 
 
+def test_plain_and_extended_entry_points_agree(dev):
+    """fsn_occgrid_march and fsn_occgrid_march_ex (null bounds, cone 0) called through the C ABI, count and fill pass:
+    the same samples, and those of the restatement."""
+    import ctypes as C
+    from fs_nerf_amd import _lib
+    from fs_nerf_amd.ops import _p, _stream
+    bins = field("random")
+    est = estimator(BOX1, 16, 3, bins, dev)
+    o, d = mixed_rays()
+    od, dd = o.to(dev), d.to(dev)
+    ms = est.max_steps(STEP)
+    ab = (C.c_float * 6)(*BOX1)
+    lib = _lib.lib()
+    for uu in (None, torch.rand(N_RAYS, generator=torch.Generator().manual_seed(1))):
+        ud = None if uu is None else uu.to(dev)
+        head = (_p(od), _p(dd), N_RAYS, ab, 16, 3, _p(est.bits), 0.0, 1e10, STEP, _p(ud), ms)
+        got = []
+        for fn, extra in ((lib.fsn_occgrid_march, ()), (lib.fsn_occgrid_march_ex, (None, None, 0.0))):
+            counts = torch.zeros(N_RAYS, device=dev, dtype=torch.int64)
+            _lib.check(fn(*head, *extra, _p(counts), None, None, None, None, _stream()), "count pass")
+            offsets = (torch.cumsum(counts, 0) - counts).contiguous()
+            n = int(counts.sum())
+            ri = torch.full((n,), -1, device=dev, dtype=torch.int64)
+            t0, t1 = torch.full((n,), -1.0, device=dev), torch.full((n,), -1.0, device=dev)
+            _lib.check(fn(*head, *extra, None, _p(offsets), _p(ri), _p(t0), _p(t1), _stream()), "fill pass")
+            got.append((counts, ri, t0, t1))
+        want = CR.march(o, d, BOX1, 16, 3, bins, 0.0, 1e10, STEP, uu, ms, cone_angle=0.0)
+        assert want[0].numel() > 1000
+        assert all(torch.equal(a, b) for a, b in zip(*got)), uu is not None
+        assert torch.equal(got[0][0].cpu(), torch.bincount(want[0], minlength=N_RAYS)) and same(got[0][1:], want)
+
+
 def test_march_real_configuration(dev):
     """run-nerf.py:92-98: 128^3, four levels over +-1.5, step 5e-3, with nerfacc's cone angle for unbounded scenes."""
     aabb = [-1.5, -1.5, -1.5, 1.5, 1.5, 1.5]

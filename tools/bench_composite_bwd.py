@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Time the backward of the packed compositor at the training step's shape (4096 rays x 192 samples): the lean entry
 point (fsn_composite_packed_bwd: colours and opacity, the default training step) and the full one
-(fsn_composite_packed_bwd_full) with the same two cotangents, with d_depth, with d_weights and with all six; and the
+(fsn_composite_packed_bwd_full) with the same two cotangents, with d_depth, with d_weights and with all six (one kernel
+behind both entry points: "lean" and "full_colors_opacity" differ in the host call only; lines recorded before the
+merge timed a separate lean kernel); and the
 distortion loss's two kernels.  Device events around the ops-level call (its two memsets and the kernel) after
 warm-ups, the variants alternated run by run, median of --iters runs.  GB/s is against the byte model: 40 B per sample
 for the lean backward (sigma, rgb, t0, t1 read; d_sigma, d_rgb written) plus 4 B per sample for each per-sample

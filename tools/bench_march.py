@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Time OccGridEstimator.sampling with and without cone-angle steps, from device events after a warm-up: 4096 rays
 through the sphere grid of tests/test_occgrid.py at 128^3 cells, step 5e-3 (the reference's LLFF configuration,
-run-nerf.py:92-98), one level and four, cone_angle 0 (the uniform march, fsn_occgrid_march - the parent commit's) against
-0.004 (fsn_occgrid_march_ex), alternated call by call in one process:
+run-nerf.py:92-98), one level and four, cone_angle 0 (the uniform march) against 0.004, alternated call by call in one
+process.  Both go through fsn_occgrid_march_ex and its one kernel (lines recorded before the plain and the extended
+kernel were merged timed the plain kernel as "uniform"):
 
   march      sampling without sigma_fn: count pass, scan, one host read, fill pass
   sampling   with the model's density pass and the visibility cull behind it (sigma_fn = forward_rays)
