@@ -93,6 +93,7 @@ SIGNATURES = {
     "fsn_render_rays_fused": (_i, [_PD, _i, _vp, _vp, C.POINTER(RenderArgs), _vp]),
     "fsn_bench_bare_stream": (_i, [_PD, _i, _vp, _i, _vp, _vp]),
     "fsn_render_rays_occgrid": (_i, [_PD, _i, _vp, C.POINTER(OccRenderArgs), _vp]),
+    "fsn_render_rays_occgrid_ex": (_i, [_PD, _i, _vp, C.POINTER(OccRenderArgs), _f, _vp, _vp, _vp, _vp]),
     "fsn_occlusion_reg_fwd": (_i, [_vp, _vp, _vp, _i64, _i64, _f, _f, _i, _vp, _vp, _vp]),
     "fsn_to8b": (_i, [_vp, _i64, _vp, _vp]),
     "fsn_to8b_nchw": (_i, [_vp, _i64, _i64, _vp, _vp]),
@@ -108,6 +109,7 @@ SIGNATURES = {
     "fsn_occlusion_reg_bwd": (_i, [_vp, _i64, _vp, _i64, _f, _f, _i, _vp, _vp, _vp, _vp]),
     "fsn_occ_gather_samples": (_i, [_vp, _vp, _vp, _i, _i64, _f, _vp, _vp, _vp, _vp]),
     "fsn_occ_gather_extras": (_i, [_vp, _vp, _vp, _i, _i64, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fsn_occ_gather_ex": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fsn_occgrid_march": (_i, [_vp, _vp, _i64, _vp, _i, _i, _vp, _f, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fsn_occgrid_march_ex": (_i, [_vp, _vp, _i64, _vp, _i, _i, _vp, _f, _f, _f, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp,
                                   _vp]),
@@ -159,7 +161,9 @@ def lib() -> C.CDLL:
             raise RuntimeError(f"{LIB_PATH} not found: run `python -c 'import __graft_entry__ as g; g.build()'` "
                                "(there is no CPU fallback for the HIP path)")
         l = C.CDLL(LIB_PATH)
-        partial = os.environ.get("FSN_LIB_PARTIAL") == "1"  # the sanitizer build of the host side exports a subset
+        # FSN_LIB_PARTIAL: the library may export a subset - the sanitizer build of the host side, and an older
+        # build loaded for an A/B timing (tools/bench_occ_cone.py loads the parent commit's library this way)
+        partial = os.environ.get("FSN_LIB_PARTIAL") == "1"
         for name, (res, args) in SIGNATURES.items():
             if partial and not hasattr(l, name):
                 continue

@@ -167,6 +167,23 @@ __device__ __forceinline__ int march_ray_cone(const GridDev& G, const uint32_t* 
   return total;
 }
 
+// The choice of regime, ONE definition for k_occ_march (occgrid.hip) and k_render_occ (render_occ.hip): the ray's range
+// with its per-ray bounds (+-inf: none; the cone regime has no lattice shift, so `has_u` does not reach the range), then
+// march_ray_cone for cone_angle > 0 and march_ray otherwise - a wave-uniform branch.  A count pass and the fill pass
+// that follows it call both functions with the same arguments.
+__device__ __forceinline__ RayLattice ray_range(const GridDev& G, const float (&o)[3], const float (&d)[3], float near_plane,
+                                                float far_plane, float step, float cone_angle, bool has_u, float u_r,
+                                                float t_min_r, float t_max_r) {
+  return ray_lattice_bounded(G, o, d, near_plane, far_plane, step, !(cone_angle > 0.0f) && has_u, u_r, t_min_r, t_max_r);
+}
+template <class Sink>
+__device__ __forceinline__ int march_ray_regime(const GridDev& G, const uint32_t* __restrict__ bits, const float (&o)[3],
+                                                const float (&d)[3], const RayLattice& L, float step, float cone_angle,
+                                                bool has_u, float u_r, int32_t max_steps, Sink&& sink) {
+  return cone_angle > 0.0f ? march_ray_cone(G, bits, o, d, L, step, cone_angle, has_u, u_r, max_steps, sink)
+                           : march_ray(G, bits, o, d, L, step, max_steps, sink);
+}
+
 // ---------------------------------------------------------------- update_every_n_steps: one draw of the cell selection
 // Shared by k_occ_select (occgrid.hip) and the fused refresh (occ_refresh.hip): ONE definition, so that both produce the
 // same cell and the same point bit for bit.  The rule is stated at k_occ_select.

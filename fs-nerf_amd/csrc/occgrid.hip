@@ -39,10 +39,9 @@ __global__ void k_occ_march(const float* __restrict__ rays_o, const float* __res
   if (r >= R) return;
   const float o[3] = {rays_o[3 * r], rays_o[3 * r + 1], rays_o[3 * r + 2]};
   const float d[3] = {rays_d[3 * r], rays_d[3 * r + 1], rays_d[3 * r + 2]};
-  const bool cone = cone_angle > 0.0f;
   const float u_r = u ? u[r] : 0.f;
   const float lo_r = t_min ? t_min[r] : -__builtin_huge_valf(), hi_r = t_max ? t_max[r] : __builtin_huge_valf();
-  const RayLattice L = ray_lattice_bounded(G, o, d, near_plane, far_plane, step, !cone && u != nullptr, u_r, lo_r, hi_r);
+  const RayLattice L = ray_range(G, o, d, near_plane, far_plane, step, cone_angle, u != nullptr, u_r, lo_r, hi_r);
   const int64_t base_out = FILL ? offsets[r] : 0;
   auto sink = [&](float ts, float te, bool keep, uint64_t m, int before) {
     if (FILL && keep) {
@@ -52,8 +51,7 @@ __global__ void k_occ_march(const float* __restrict__ rays_o, const float* __res
       t_ends[pos] = te;
     }
   };
-  const int total = cone ? march_ray_cone(G, bits, o, d, L, step, cone_angle, u != nullptr, u_r, max_steps, sink)
-                         : march_ray(G, bits, o, d, L, step, max_steps, sink);
+  const int total = march_ray_regime(G, bits, o, d, L, step, cone_angle, u != nullptr, u_r, max_steps, sink);
   if (!FILL && lane == 0) counts[r] = total;
 }
 

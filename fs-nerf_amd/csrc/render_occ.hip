@@ -17,6 +17,9 @@
 // Every sample is evaluated independently of its tile position and every ray is integrated by one wave with the
 // arithmetic of the standalone kernels (occ_dev.hpp, ray_dev.hpp): the image does not depend on how batches form and is
 // the unfused path's (march -> k_mlp_fwd -> k_visibility -> k_mlp_fwd -> k_composite_packed).
+// The march is k_occ_march's in either regime (occ_dev.hpp: ray_range / march_ray_regime - per-ray bounds, and for
+// cone_angle > 0 blocks of 64 intervals whose width grows with distance; include/fsnerf_hip.h has the definition at
+// fsn_occgrid_march_ex), so every candidate carries its own interval END and nothing below assumes a common width.
 #include "common.hpp"
 #define FSN_KLOOP_ASM
 #define FSN_BF16X3_ONEACC 1  // inference: bf16x3 accumulates its three products in one tile (mlp_dev.hpp)
@@ -38,6 +41,11 @@ struct OccKArgs {
   GridDev G;
   float cam_hw, cam_hh, cam_f;
   int32_t use_vis;
+  // fsn_render_rays_occgrid_ex: the march's regime and per-ray bounds, the slot rows of the interval ends
+  float cone_angle;
+  const float* t_min;
+  const float* t_max;
+  float* sample_t1;
 };
 
 struct OccLds {
@@ -45,6 +53,10 @@ struct OccLds {
   GridDev G;
   float cam_hw, cam_hh, cam_f;
   int32_t use_vis;
+  float cone_angle;
+  const float* t_min;
+  const float* t_max;
+  float* sample_t1;
   // batch state (written by thread 0 between barriers)
   int64_t chunk_base, carry_base;
   int32_t chunk_from, carry_from, chunk_take, carry_take, stop, n_cand, n_kept, n_rays;
@@ -53,24 +65,31 @@ struct OccLds {
   float rays[kMaxRays * 6];
   int64_t ray_id[kMaxRays];
   int32_t cand_off[kMaxRays], cand_cnt[kMaxRays], kept_off[kMaxRays + 1], kept_cnt[kMaxRays];
-  // candidate samples (march order: sorted by ray slot, then t)
+  // candidate samples (march order: sorted by ray slot, then t): interval [t0c, t1c), the ends as the march's sink
+  // receives them (the cone regime's te is not bitwise ts + width)
   float t0c[kCap], sigc[kCap];
   uint16_t slotc[kCap];
   uint8_t keepf[kCap];
-  // kept samples
-  float t0k[kCap], t1k[kCap], sigk[kCap], rgbk[3 * kCap];
+  // kept samples.  t1c shares sigk's storage: the ends are written by the batch's march and last read by the
+  // compaction (-> t1k); sigk is written by the full pass, which follows the compaction, and read until the barrier
+  // that ends the batch (the sampler mode never touches it).
+  float t0k[kCap], t1k[kCap], rgbk[3 * kCap];
+  union {
+    float sigk[kCap];
+    float t1c[kCap];
+  };
   uint16_t slotk[kCap];
 };
 
 constexpr int kOccLdsBytes = kRingBytes + (kAuxCapFloats + 96) * 4 + (int)sizeof(OccLds);
 static_assert(kOccLdsBytes <= 160 * 1024, "LDS budget");
 
-// sample source: interval [t0, t0 + step) of ray `ray`: x = o + d (t0 + t1) / 2 (rendering.py:59-61, 77-79)
+// sample source: interval [t0, t1) of ray `ray`: x = o + d (t0 + t1) / 2 (rendering.py:59-61, 77-79)
 struct OccSrc {
   const float* ray;
-  float t0, step;
+  float t0, t1;
   __device__ __forceinline__ void pos(float& x, float& y, float& z) const {
-    const float tm = t0 + (t0 + step);
+    const float tm = t0 + t1;
     x = ray[0] + ray[3] * tm / 2.0f;
     y = ray[1] + ray[4] * tm / 2.0f;
     z = ray[2] + ray[5] * tm / 2.0f;
@@ -97,7 +116,11 @@ __device__ __forceinline__ int wave_excl_scan_i(int v, int& total) {
   return inc - v;
 }
 
-template <int NT, int PREC>
+// EX: the launch has a cone angle or per-ray bounds (fsn_render_rays_occgrid_ex).  Without them (EX = false) the march
+// is the plain lattice's and an interval end is its start + step, computed where it is used: the code of the kernel
+// before it knew the extended march - as a run-time branch with the ends always stored, the default frame was 0.5 %
+// slower (tools/bench_occ_cone.py).  Both instantiations give the same uniform-regime results bit for bit.
+template <int NT, int PREC, bool EX>
 __global__ __launch_bounds__(kThreads) void k_render_occ(OccKArgs k) {
   __shared__ __attribute__((aligned(1024))) char smem[kOccLdsBytes];
   float* aux = reinterpret_cast<float*>(smem + kRingBytes);
@@ -105,6 +128,7 @@ __global__ __launch_bounds__(kThreads) void k_render_occ(OccKArgs k) {
   int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;  // (laundered per batch below: render.hip)
   if (tid == 0) {
     S.a = k.a; S.G = k.G; S.cam_hw = k.cam_hw; S.cam_hh = k.cam_hh; S.cam_f = k.cam_f; S.use_vis = k.use_vis;
+    S.cone_angle = k.cone_angle; S.t_min = k.t_min; S.t_max = k.t_max; S.sample_t1 = k.sample_t1;
     S.carry_from = kWaves; S.carry_base = 0; S.carry_take = 0;
   }
   __syncthreads();
@@ -118,6 +142,15 @@ __global__ __launch_bounds__(kThreads) void k_render_occ(OccKArgs k) {
   ARing ring;
   prime_ring<PREC, NT>(st, ring);
 
+  // interval end of candidate / kept sample i
+  auto cand_end = [&](int i) -> float {
+    if constexpr (EX) return FSN_AT(S.t1c, i);
+    else return FSN_AT(S.t0c, i) + a.step;
+  };
+  auto kept_end = [&](int i) -> float {
+    if constexpr (EX) return FSN_AT(S.t1k, i);
+    else return FSN_AT(S.t0k, i) + a.step;
+  };
   // this wave's ray of a chunk -> registers (every lane holds the same values)
   auto fetch_ray = [&](int64_t ray, float (&o)[3], float (&d)[3]) {
     if (a.rays_o) {
@@ -166,10 +199,21 @@ __global__ __launch_bounds__(kThreads) void k_render_occ(OccKArgs k) {
       RayLattice L;
       L.any = false; L.near_r = L.t_lo = L.t_hi = 0.f; L.k0 = 0;
       int c = 0;
+      // (EX: the march of occ_dev.hpp in either regime, as k_occ_march runs it: count here, fill below)
+      const float cone = EX ? S.cone_angle : 0.f;
+      float u_r = 0.f;
       if (active) {
         fetch_ray(ray, o, d);
-        L = ray_lattice(S.G, o, d, a.near_plane, a.far_plane, a.step, a.u != nullptr, a.u ? a.u[ray] : 0.f);
-        c = march_ray(S.G, a.bits, o, d, L, a.step, a.max_steps, [](float, float, bool, uint64_t, int) {});
+        u_r = a.u ? a.u[ray] : 0.f;
+        if constexpr (EX) {
+          const float lo_r = S.t_min ? S.t_min[ray] : -__builtin_huge_valf(), hi_r = S.t_max ? S.t_max[ray] : __builtin_huge_valf();
+          L = ray_range(S.G, o, d, a.near_plane, a.far_plane, a.step, cone, a.u != nullptr, u_r, lo_r, hi_r);
+          c = march_ray_regime(S.G, a.bits, o, d, L, a.step, cone, a.u != nullptr, u_r, a.max_steps,
+                               [](float, float, bool, uint64_t, int) {});
+        } else {
+          L = ray_lattice(S.G, o, d, a.near_plane, a.far_plane, a.step, a.u != nullptr, u_r);
+          c = march_ray(S.G, a.bits, o, d, L, a.step, a.max_steps, [](float, float, bool, uint64_t, int) {});
+        }
       }
       if (lane == 0) FSN_AT(S.cnt, wave) = active ? c : -1;
       __syncthreads();
@@ -202,13 +246,16 @@ __global__ __launch_bounds__(kThreads) void k_render_occ(OccKArgs k) {
           FSN_AT(S.cand_off, my_slot) = my_off;
           FSN_AT(S.cand_cnt, my_slot) = c;
         }
-        march_ray(S.G, a.bits, o, d, L, a.step, a.max_steps, [&](float ts, float, bool keep, uint64_t m, int before) {
+        auto fill = [&](float ts, float te, bool keep, uint64_t m, int before) {
           if (keep) {
             const int pos = my_off + before + __popcll(m & ((1ull << lane) - 1ull));
             FSN_AT(S.t0c, pos) = ts;
+            if constexpr (EX) FSN_AT(S.t1c, pos) = te;
             FSN_AT(S.slotc, pos) = (uint16_t)my_slot;
           }
-        });
+        };
+        if constexpr (EX) march_ray_regime(S.G, a.bits, o, d, L, a.step, cone, a.u != nullptr, u_r, a.max_steps, fill);
+        else march_ray(S.G, a.bits, o, d, L, a.step, a.max_steps, fill);
       }
       __syncthreads();
       if (S.stop) break;
@@ -226,7 +273,7 @@ __global__ __launch_bounds__(kThreads) void k_render_occ(OccKArgs k) {
         const int idx0 = sub * TILE + tile_slot<NG>(wave, lane, 0);
         OccSrc src[NG];
         FSN_PER_GROUP(q, const int ic = min(idx0 + 16 * q, n_cand - 1);
-                            src[q] = OccSrc{FSN_SPAN(S.rays, 6 * FSN_AT(S.slotc, ic), 6), FSN_AT(S.t0c, ic), a.step};);
+                            src[q] = OccSrc{FSN_SPAN(S.rays, 6 * FSN_AT(S.slotc, ic), 6), FSN_AT(S.t0c, ic), cand_end(ic)};);
         float sigma[NG], rgb[NG][3];
         st.begin_tile(nph_density);
         mlp_tile<NT, PREC, false>(st, net, src, ring, sigma, rgb);
@@ -242,12 +289,12 @@ __global__ __launch_bounds__(kThreads) void k_render_occ(OccKArgs k) {
         const int per = (Sn + 63) >> 6;
         const int i0 = lane * per, i1 = min(i0 + per, Sn);
         float lsum = 0.f;
-        for (int i = i0; i < i1; ++i) lsum += FSN_AT(S.sigc, beg + i) * ((FSN_AT(S.t0c, beg + i) + a.step) - FSN_AT(S.t0c, beg + i));
+        for (int i = i0; i < i1; ++i) lsum += FSN_AT(S.sigc, beg + i) * (cand_end(beg + i) - FSN_AT(S.t0c, beg + i));
         float tot;
         float run = wave_excl_scan(lsum, tot);
         int nk = 0;
         for (int i = i0; i < i1; ++i) {
-          const float sdt = FSN_AT(S.sigc, beg + i) * ((FSN_AT(S.t0c, beg + i) + a.step) - FSN_AT(S.t0c, beg + i));
+          const float sdt = FSN_AT(S.sigc, beg + i) * (cand_end(beg + i) - FSN_AT(S.t0c, beg + i));
           const float T = expf(-run), alpha = 1.0f - expf(-sdt);
           const bool kp = T >= a.early_stop_eps && alpha >= a.alpha_thre;
           FSN_AT(S.keepf, beg + i) = kp ? 1 : 0;
@@ -282,9 +329,8 @@ __global__ __launch_bounds__(kThreads) void k_render_occ(OccKArgs k) {
       int pos = ko + wave_excl_scan_i(nk, tk);
       for (int i = i0; i < i1; ++i) {
         if (FSN_AT(S.keepf, beg + i)) {
-          const float t0 = FSN_AT(S.t0c, beg + i);
-          FSN_AT(S.t0k, pos) = t0;
-          FSN_AT(S.t1k, pos) = t0 + a.step;
+          FSN_AT(S.t0k, pos) = FSN_AT(S.t0c, beg + i);
+          FSN_AT(S.t1k, pos) = cand_end(beg + i);
           FSN_AT(S.slotk, pos) = (uint16_t)r;
           ++pos;
         }
@@ -296,6 +342,9 @@ __global__ __launch_bounds__(kThreads) void k_render_occ(OccKArgs k) {
         const int64_t ray = FSN_AT(S.ray_id, r);
         const int ko = FSN_AT(S.kept_off, r), Sk = FSN_AT(S.kept_cnt, r);
         for (int i = lane; i < Sk; i += 64) a.sample_t0[ray * a.sample_cap + i] = FSN_AT(S.t0k, ko + i);
+        if constexpr (EX)
+          if (S.sample_t1)  // (cone regime: the ends are not t0 + step)
+            for (int i = lane; i < Sk; i += 64) S.sample_t1[ray * a.sample_cap + i] = FSN_AT(S.t1k, ko + i);
         if (lane == 0) {
           if (a.n_cand) a.n_cand[ray] = FSN_AT(S.cand_cnt, r);
           a.n_kept[ray] = Sk;
@@ -311,7 +360,7 @@ __global__ __launch_bounds__(kThreads) void k_render_occ(OccKArgs k) {
       const int idx0 = sub * TILE + tile_slot<NG>(wave, lane, 0);
       OccSrc src[NG];
       FSN_PER_GROUP(q, const int ic = min(idx0 + 16 * q, n_kept - 1);
-                       src[q] = OccSrc{FSN_SPAN(S.rays, 6 * FSN_AT(S.slotk, ic), 6), FSN_AT(S.t0k, ic), a.step};);
+                       src[q] = OccSrc{FSN_SPAN(S.rays, 6 * FSN_AT(S.slotk, ic), 6), FSN_AT(S.t0k, ic), kept_end(ic)};);
       float sigma[NG], rgb[NG][3];
       st.begin_tile(nph_full);
       mlp_tile<NT, PREC, true>(st, net, src, ring, sigma, rgb);
@@ -340,6 +389,9 @@ __global__ __launch_bounds__(kThreads) void k_render_occ(OccKArgs k) {
           a.sample_t0[row + i] = FSN_AT(S.t0k, ko + i);
           a.ex_sigmas[row + i] = FSN_AT(S.sigk, ko + i);
         }
+        if constexpr (EX)
+          if (S.sample_t1)
+            for (int i = lane; i < Sk; i += 64) S.sample_t1[row + i] = FSN_AT(S.t1k, ko + i);
         for (int i = lane; i < 3 * Sk; i += 64) a.ex_rgbs[3 * row + i] = FSN_AT(S.rgbk, 3 * ko + i);
       }
       if (lane == 0) {
@@ -356,7 +408,9 @@ template <int NT, int PREC>
 static int launch_occ(const OccKArgs& k, int cus, hipStream_t s) {
   const int64_t chunks = (k.a.R + kWaves - 1) / kWaves;
   const unsigned grid = (unsigned)(chunks < cus ? chunks : cus);
-  k_render_occ<NT, PREC><<<grid, kThreads, 0, s>>>(k);
+  // (sample_t1 alone - end rows asked for in the uniform regime without bounds - is served by the extended kernel too)
+  if (k.cone_angle > 0.f || k.t_min || k.t_max || k.sample_t1) k_render_occ<NT, PREC, true><<<grid, kThreads, 0, s>>>(k);
+  else k_render_occ<NT, PREC, false><<<grid, kThreads, 0, s>>>(k);
   FSN_LAUNCH_CHECK("k_render_occ");
   return FSN_OK;
 }
@@ -378,46 +432,58 @@ int debug_report_occ(unsigned* host4) {  // (fsn_debug_report, render.hip)
 
 using namespace fsn;
 
-extern "C" int fsn_render_rays_occgrid(const fsn_mlp_desc* desc, int prec, const void* blob,
-                                       const fsn_occ_render_args* args, fsn_stream_t stream) {
-  FSN_REQUIRE(desc && args, FSN_E_INVALID, "fsn_render_rays_occgrid: null pointer");
+// the argument checks and the launch of both render entry points (`who` prefixes the messages; the plain entry point
+// passes cone_angle 0 and no bounds / end rows, which the new checks let through)
+static int occ_render_launch(const char* who, const fsn_mlp_desc* desc, int prec, const void* blob,
+                             const fsn_occ_render_args* args, float cone_angle, const float* t_min, const float* t_max,
+                             float* sample_t1, fsn_stream_t stream) {
+  FSN_REQUIRE(desc && args, FSN_E_INVALID, "%s: null pointer", who);
   const fsn_occ_render_args& a = *args;
-  FSN_REQUIRE(a.R >= 0 && a.step > 0.f && a.max_steps > 0, FSN_E_INVALID, "fsn_render_rays_occgrid: bad sizes");
-  FSN_REQUIRE(prec >= 0 && prec <= FSN_PREC_FP16X3U, FSN_E_UNSUPPORTED, "fsn_render_rays_occgrid: precision mode %d", prec);
+  FSN_REQUIRE(a.R >= 0 && a.step > 0.f && a.max_steps > 0, FSN_E_INVALID, "%s: bad sizes", who);
+  FSN_REQUIRE(cone_angle >= 0.f, FSN_E_INVALID, "%s: cone_angle must not be negative", who);
+  FSN_REQUIRE(!(cone_angle > 0.f && a.near_plane < 0.f), FSN_E_INVALID, "%s: the cone regime needs near_plane >= 0", who);
+  FSN_REQUIRE(prec >= 0 && prec <= FSN_PREC_FP16X3U, FSN_E_UNSUPPORTED, "%s: precision mode %d", who, prec);
   NetGeom G;
   const char* why;
   int rc = build_geom(*desc, prec, G, &why);
-  FSN_REQUIRE(rc == FSN_OK, rc, "fsn_render_rays_occgrid: %s", why);
+  FSN_REQUIRE(rc == FSN_OK, rc, "%s: %s", who, why);
   OccKArgs k;
   rc = make_grid(a.aabb, a.res, a.levels, k.G);
   if (rc != FSN_OK) return rc;
   if (a.R == 0) return FSN_OK;
-  FSN_REQUIRE(blob && a.bits && a.work_counter, FSN_E_INVALID, "fsn_render_rays_occgrid: null pointer");
+  FSN_REQUIRE(a.rays_o || !(t_min || t_max), FSN_E_INVALID, "%s: per-ray t_min / t_max need ray arrays, not a camera", who);
+  FSN_REQUIRE(!(cone_angle > 0.f && a.sample_t0 && !sample_t1), FSN_E_INVALID,
+              "%s: the sampler / extras mode in the cone regime needs sample_t1", who);
+  FSN_REQUIRE(blob && a.bits && a.work_counter, FSN_E_INVALID, "%s: null pointer", who);
   if (a.ex_weights)
     FSN_REQUIRE(a.sample_t0 && a.ex_alphas && a.ex_trans && a.ex_sigmas && a.ex_rgbs && a.colors && a.opacity && a.depth,
-                FSN_E_INVALID, "fsn_render_rays_occgrid: the extras mode needs sample_t0, all five ex_* arrays and the per-ray outputs");
+                FSN_E_INVALID, "%s: the extras mode needs sample_t0, all five ex_* arrays and the per-ray outputs", who);
   if (a.sample_t0) {
     FSN_REQUIRE(a.n_kept && a.sample_cap >= a.max_steps, FSN_E_INVALID,
-                "fsn_render_rays_occgrid: the sampler / extras mode needs n_kept and sample_cap >= max_steps");
+                "%s: the sampler / extras mode needs n_kept and sample_cap >= max_steps", who);
   } else {
-    FSN_REQUIRE(a.colors && a.opacity && a.depth, FSN_E_INVALID, "fsn_render_rays_occgrid: null output pointer");
+    FSN_REQUIRE(a.colors && a.opacity && a.depth, FSN_E_INVALID, "%s: null output pointer", who);
   }
-  FSN_REQUIRE(a.max_steps <= kCap, FSN_E_UNSUPPORTED,
-              "fsn_render_rays_occgrid: max_steps %d > %d samples of one ray group (use the unfused path)", a.max_steps, kCap);
+  FSN_REQUIRE(a.max_steps <= kCap, FSN_E_UNSUPPORTED, "%s: max_steps %d > %d samples of one ray group (use the unfused path)",
+              who, a.max_steps, kCap);
   if (a.rays_o) {
-    FSN_REQUIRE(a.rays_d, FSN_E_INVALID, "fsn_render_rays_occgrid: rays_o without rays_d");
+    FSN_REQUIRE(a.rays_d, FSN_E_INVALID, "%s: rays_o without rays_d", who);
   } else {
     FSN_REQUIRE(a.cam_H > 0 && a.cam_W > 0 && a.cam_focal > 0 && a.cam_row0 >= 0 &&
                     a.R <= (int64_t)(a.cam_H - a.cam_row0) * a.cam_W,
-                FSN_E_INVALID, "fsn_render_rays_occgrid: no rays and no valid camera");
+                FSN_E_INVALID, "%s: no rays and no valid camera", who);
   }
-  FSN_REQUIRE(G.aux_floats <= kAuxCapFloats, FSN_E_UNSUPPORTED, "fsn_render_rays_occgrid: network too deep for LDS");
+  FSN_REQUIRE(G.aux_floats <= kAuxCapFloats, FSN_E_UNSUPPORTED, "%s: network too deep for LDS", who);
   k.net = net_params(*desc, G, blob, a.status);
   k.a = a;
   k.cam_hw = (float)(a.cam_W * 0.5);
   k.cam_hh = (float)(a.cam_H * 0.5);
   k.cam_f = (float)a.cam_focal;
   k.use_vis = (a.early_stop_eps > 0.f || a.alpha_thre > 0.f) ? 1 : 0;
+  k.cone_angle = cone_angle;
+  k.t_min = t_min;
+  k.t_max = t_max;
+  k.sample_t1 = a.sample_t0 ? sample_t1 : nullptr;  // (the end rows belong to the sampler / extras mode)
   const int cus = fsn_device_cus();
   if (cus <= 0) return FSN_E_HIP;
   hipStream_t s = as_stream(stream);
@@ -426,14 +492,26 @@ extern "C" int fsn_render_rays_occgrid(const fsn_mlp_desc* desc, int prec, const
                       prec, [&](auto NT, auto PREC) { return launch_occ<NT(), PREC()>(k, cus, s); });
 }
 
+extern "C" int fsn_render_rays_occgrid(const fsn_mlp_desc* desc, int prec, const void* blob,
+                                       const fsn_occ_render_args* args, fsn_stream_t stream) {
+  return occ_render_launch("fsn_render_rays_occgrid", desc, prec, blob, args, 0.f, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int fsn_render_rays_occgrid_ex(const fsn_mlp_desc* desc, int prec, const void* blob,
+                                          const fsn_occ_render_args* args, float cone_angle, const float* t_min,
+                                          const float* t_max, float* sample_t1, fsn_stream_t stream) {
+  return occ_render_launch("fsn_render_rays_occgrid_ex", desc, prec, blob, args, cone_angle, t_min, t_max, sample_t1, stream);
+}
+
 namespace fsn {
 struct GatherEx {  // EXTRAS mode: slot rows -> packed arrays (weights, alphas, trans, sigmas; rgbs x3), or all null
   const float* slot[5];
   float* out[5];
 };
+// (t1s: the cone regime's end rows, or null: t_end = t_start + step)
 __global__ void k_occ_gather(const int32_t* __restrict__ n_kept, const int64_t* __restrict__ offsets,
-                             const float* __restrict__ t0s, int cap, int64_t R, float step, int64_t* __restrict__ ri,
-                             float* __restrict__ ts, float* __restrict__ te, GatherEx ex) {
+                             const float* __restrict__ t0s, const float* __restrict__ t1s, int cap, int64_t R, float step,
+                             int64_t* __restrict__ ri, float* __restrict__ ts, float* __restrict__ te, GatherEx ex) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * 4 + wave;
   if (r >= R) return;
@@ -443,7 +521,7 @@ __global__ void k_occ_gather(const int32_t* __restrict__ n_kept, const int64_t* 
     const float t = t0s[r * cap + i];
     ri[off + i] = r;
     ts[off + i] = t;
-    te[off + i] = t + step;
+    te[off + i] = t1s ? t1s[r * cap + i] : t + step;
   }
   if (ex.slot[0]) {
 #pragma unroll
@@ -454,34 +532,47 @@ __global__ void k_occ_gather(const int32_t* __restrict__ n_kept, const int64_t* 
 }
 }  // namespace fsn
 
+// the checks and the launch of the three gather entry points (`slots` / `out` both null: samples only)
+static int occ_gather_launch(const char* who, const int32_t* n_kept, const int64_t* offsets, const float* sample_t0,
+                             const float* sample_t1, int sample_cap, int64_t R, float step, int64_t* ray_indices,
+                             float* t_starts, float* t_ends, bool extras, const float* const* slots, float* const* out,
+                             fsn_stream_t stream) {
+  FSN_REQUIRE(R >= 0 && sample_cap > 0, FSN_E_INVALID, "%s: bad sizes", who);
+  if (R == 0) return FSN_OK;
+  FSN_REQUIRE(n_kept && offsets && sample_t0 && ray_indices && t_starts && t_ends && (!extras || (slots && out)),
+              FSN_E_INVALID, "%s: null pointer", who);
+  GatherEx ex{};
+  if (extras)
+    for (int k = 0; k < 5; ++k) {
+      FSN_REQUIRE(slots[k] && out[k], FSN_E_INVALID, "%s: null slot / output array %d", who, k);
+      ex.slot[k] = slots[k];
+      ex.out[k] = out[k];
+    }
+  k_occ_gather<<<(unsigned)((R + 3) / 4), 256, 0, as_stream(stream)>>>(n_kept, offsets, sample_t0, sample_t1, sample_cap, R,
+                                                                       step, ray_indices, t_starts, t_ends, ex);
+  FSN_LAUNCH_CHECK("k_occ_gather");
+  return FSN_OK;
+}
+
 extern "C" int fsn_occ_gather_samples(const int32_t* n_kept, const int64_t* offsets, const float* sample_t0, int sample_cap,
                                       int64_t R, float step, int64_t* ray_indices, float* t_starts, float* t_ends,
                                       fsn_stream_t stream) {
-  FSN_REQUIRE(R >= 0 && sample_cap > 0, FSN_E_INVALID, "fsn_occ_gather_samples: bad sizes");
-  if (R == 0) return FSN_OK;
-  FSN_REQUIRE(n_kept && offsets && sample_t0 && ray_indices && t_starts && t_ends, FSN_E_INVALID,
-              "fsn_occ_gather_samples: null pointer");
-  k_occ_gather<<<(unsigned)((R + 3) / 4), 256, 0, as_stream(stream)>>>(n_kept, offsets, sample_t0, sample_cap, R, step,
-                                                                       ray_indices, t_starts, t_ends, GatherEx{});
-  FSN_LAUNCH_CHECK("k_occ_gather");
-  return FSN_OK;
+  return occ_gather_launch("fsn_occ_gather_samples", n_kept, offsets, sample_t0, nullptr, sample_cap, R, step, ray_indices,
+                           t_starts, t_ends, false, nullptr, nullptr, stream);
 }
 
 extern "C" int fsn_occ_gather_extras(const int32_t* n_kept, const int64_t* offsets, const float* sample_t0, int sample_cap,
                                      int64_t R, float step, int64_t* ray_indices, float* t_starts, float* t_ends,
                                      const float* const* slots, float* const* out, fsn_stream_t stream) {
-  FSN_REQUIRE(R >= 0 && sample_cap > 0, FSN_E_INVALID, "fsn_occ_gather_extras: bad sizes");
-  if (R == 0) return FSN_OK;
-  FSN_REQUIRE(n_kept && offsets && sample_t0 && ray_indices && t_starts && t_ends && slots && out, FSN_E_INVALID,
-              "fsn_occ_gather_extras: null pointer");
-  GatherEx ex;
-  for (int k = 0; k < 5; ++k) {
-    FSN_REQUIRE(slots[k] && out[k], FSN_E_INVALID, "fsn_occ_gather_extras: null slot / output array %d", k);
-    ex.slot[k] = slots[k];
-    ex.out[k] = out[k];
-  }
-  k_occ_gather<<<(unsigned)((R + 3) / 4), 256, 0, as_stream(stream)>>>(n_kept, offsets, sample_t0, sample_cap, R, step,
-                                                                       ray_indices, t_starts, t_ends, ex);
-  FSN_LAUNCH_CHECK("k_occ_gather");
-  return FSN_OK;
+  return occ_gather_launch("fsn_occ_gather_extras", n_kept, offsets, sample_t0, nullptr, sample_cap, R, step, ray_indices,
+                           t_starts, t_ends, true, slots, out, stream);
+}
+
+extern "C" int fsn_occ_gather_ex(const int32_t* n_kept, const int64_t* offsets, const float* sample_t0,
+                                 const float* sample_t1, int sample_cap, int64_t R, float step, int64_t* ray_indices,
+                                 float* t_starts, float* t_ends, const float* const* slots, float* const* out,
+                                 fsn_stream_t stream) {
+  FSN_REQUIRE(!slots == !out, FSN_E_INVALID, "fsn_occ_gather_ex: slots and outputs come together");
+  return occ_gather_launch("fsn_occ_gather_ex", n_kept, offsets, sample_t0, sample_t1, sample_cap, R, step, ray_indices,
+                           t_starts, t_ends, slots != nullptr, slots, out, stream);
 }

@@ -993,21 +993,37 @@ def ray_aabb_intersect(rays_o: Tensor, rays_d: Tensor, aabbs: Tensor, near_plane
     return t0, t1, hits.bool()
 
 
+def _occ_march_options(R: int, cone_angle: float, t_min: Optional[Tensor], t_max: Optional[Tensor], camera, keep: list):
+    """The extended arguments of fsn_render_rays_occgrid_ex (cone_angle, t_min, t_max), checked: per-ray bounds hold one
+    value per ray and need ray tensors.  The bound tensors are appended to `keep`."""
+    if t_min is not None or t_max is not None:
+        if camera is not None:
+            raise TypeError("per-ray t_min / t_max need ray tensors, not a camera")
+    if any(t is not None and t.numel() != R for t in (t_min, t_max)):
+        raise ValueError("t_min / t_max must hold one value per ray")
+    bounds = [None if t is None else _f32(t, k).reshape(-1) for t, k in ((t_min, "t_min"), (t_max, "t_max"))]
+    keep.extend(bounds)
+    return float(cone_angle), _p(bounds[0]), _p(bounds[1])
+
+
 def occ_sample_fused(pm: PackedMLP, rays_o: Tensor, rays_d: Tensor, *, aabb: Sequence[float], res: int, levels: int, bits: Tensor,
                      near_plane: float, far_plane: float, step: float, max_steps: int, u: Optional[Tensor] = None,
                      early_stop_eps: float = 1e-4, alpha_thre: float = 0.0, pos_mask: Optional[Tensor] = None,
-                     dir_mask: Optional[Tensor] = None, status: Optional[Tensor] = None):
+                     dir_mask: Optional[Tensor] = None, status: Optional[Tensor] = None, cone_angle: float = 0.0,
+                     t_min: Optional[Tensor] = None, t_max: Optional[Tensor] = None):
     """OccGridEstimator.sampling(..., sigma_fn = the model's density) of a training step as ONE launch + one gather:
     grid march -> density pass -> visibility cull inside persistent workgroups (the sampler mode of
     fsn_render_rays_occgrid), the kept samples of every ray in a slot of its own, then an exclusive scan of the counts,
     ONE host read (the sample count sizes the outputs) and fsn_occ_gather_samples.  -> (ray_indices int64 [N], t_starts
     [N], t_ends [N]): what occgrid_march (two launches + a read) -> density pass -> packed_visibility -> compaction
-    (a second read) give, bit for bit."""
+    (a second read) give, bit for bit.  `cone_angle` / `t_min` / `t_max`: occgrid_march's (fsn_render_rays_occgrid_ex);
+    with a cone angle the launch also leaves the kept samples' interval ends in slot rows, which the gather copies."""
     o, d = _f32(rays_o, "rays_o").reshape(-1, 3), _f32(rays_d, "rays_d").reshape(-1, 3)
     Rn, dev = o.shape[0], o.device
     a = L.OccRenderArgs()
     a.R, a.rays_o, a.rays_d = Rn, o.data_ptr(), d.data_ptr()
     keep = [o, d]
+    march = _occ_march_options(Rn, cone_angle, t_min, t_max, None, keep)
     for i in range(6):
         a.aabb[i] = float(aabb[i])
     a.res, a.levels, a.bits = int(res), int(levels), bits.data_ptr()
@@ -1026,6 +1042,7 @@ def occ_sample_fused(pm: PackedMLP, rays_o: Tensor, rays_d: Tensor, *, aabb: Seq
             setattr(a, name, m.data_ptr())
     n_kept = torch.zeros(Rn, dtype=torch.int32, device=dev)
     slots = torch.empty(max(Rn, 1), int(max_steps), dtype=torch.float32, device=dev)
+    ends = torch.empty_like(slots) if cone_angle > 0.0 else None  # (uniform regime: t_end = t_start + step)
     a.n_kept, a.sample_t0, a.sample_cap = n_kept.data_ptr(), slots.data_ptr(), int(max_steps)
     # (one queue counter PER CALL - ADVICE r3: a per-device buffer let two launches on different streams race on it; the
     # launch zeroes it itself)
@@ -1035,16 +1052,16 @@ def occ_sample_fused(pm: PackedMLP, rays_o: Tensor, rays_d: Tensor, *, aabb: Seq
     a.status = (status_word(dev) if status is None else status).data_ptr()
     with torch.cuda.device(dev):
         if Rn > 0:
-            L.check(L.lib().fsn_render_rays_occgrid(C.byref(pm.desc), pm.prec, _p(pm.blob), C.byref(a), _stream()),
-                    "fsn_render_rays_occgrid (sampler mode)")
+            L.check(L.lib().fsn_render_rays_occgrid_ex(C.byref(pm.desc), pm.prec, _p(pm.blob), C.byref(a), *march, _p(ends),
+                                                       _stream()), "fsn_render_rays_occgrid_ex (sampler mode)")
         incl = torch.cumsum(n_kept, 0, dtype=torch.int64)
         N = int(incl[-1].item()) if Rn > 0 else 0  # the one host read: the sample count sizes the outputs
         ri = torch.empty(N, dtype=torch.int64, device=dev)
         ts, te = torch.empty(N, device=dev), torch.empty(N, device=dev)
         if N > 0:
             offs = incl - n_kept
-            L.check(L.lib().fsn_occ_gather_samples(_p(n_kept), _p(offs), _p(slots), int(max_steps), Rn, float(step), _p(ri),
-                                                   _p(ts), _p(te), _stream()), "fsn_occ_gather_samples")
+            L.check(L.lib().fsn_occ_gather_ex(_p(n_kept), _p(offs), _p(slots), _p(ends), int(max_steps), Rn, float(step),
+                                              _p(ri), _p(ts), _p(te), None, None, _stream()), "fsn_occ_gather_ex")
     return ri, ts, te
 
 
@@ -1052,7 +1069,8 @@ def render_occ_fused(pm: PackedMLP, rays_o: Optional[Tensor], rays_d: Optional[T
                      levels: int, bits: Tensor, near_plane: float, far_plane: float, step: float, max_steps: int,
                      u: Optional[Tensor] = None, early_stop_eps: float = 1e-4, alpha_thre: float = 0.0,
                      bkgd=(0.0, 0.0, 0.0), pos_mask: Optional[Tensor] = None, dir_mask: Optional[Tensor] = None,
-                     camera=None, want_counts: bool = False, want_extras: bool = False):
+                     camera=None, want_counts: bool = False, want_extras: bool = False, cone_angle: float = 0.0,
+                     t_min: Optional[Tensor] = None, t_max: Optional[Tensor] = None):
     """render_rays with the occupancy estimator in ONE launch (fsn_render_rays_occgrid): grid march -> density pass ->
     visibility cull -> full pass -> packed integration, no host sync.  -> colors [R,3], opacity [R,1], depth [R,1],
     counts {"n_cand", "n_kept"} (int32 [R]) when asked for.  `camera` as in render_fused.
@@ -1060,7 +1078,9 @@ def render_occ_fused(pm: PackedMLP, rays_o: Optional[Tensor], rays_d: Optional[T
     interval starts in per-ray slot rows; behind an exclusive scan of the kept counts and ONE host read (the sample count
     sizes the outputs) fsn_occ_gather_extras packs them: -> colors, opacity, depth, counts, (ray_indices int64 [N],
     t_starts [N], t_ends [N], extras {weights, alphas, trans, sigmas [N], rgbs [N,3]}) - render_rays' full return
-    contract (rendering.py:88-107) from one launch + one gather."""
+    contract (rendering.py:88-107) from one launch + one gather.
+    `cone_angle` / `t_min` / `t_max`: occgrid_march's (fsn_render_rays_occgrid_ex; the bounds need ray tensors); with a
+    cone angle the extras mode holds a ninth slot row per sample, the interval ends."""
     if camera is not None:
         pose, cH, cW, cfocal, crow0, cnrows, dev = camera
         dev = torch.device(dev)
@@ -1073,6 +1093,7 @@ def render_occ_fused(pm: PackedMLP, rays_o: Optional[Tensor], rays_d: Optional[T
     a = L.OccRenderArgs()
     a.R = R
     keep = [o, d]
+    march = _occ_march_options(R, cone_angle, t_min, t_max, camera, keep)
     if camera is None:
         a.rays_o, a.rays_d = o.data_ptr(), d.data_ptr()
     else:
@@ -1111,6 +1132,8 @@ def render_occ_fused(pm: PackedMLP, rays_o: Optional[Tensor], rays_d: Optional[T
         cap = int(max_steps)
         slots = {k: torch.empty(max(R, 1), cap, device=dev) for k in ("t0", "weights", "alphas", "trans", "sigmas")}
         slots["rgbs"] = torch.empty(max(R, 1), cap, 3, device=dev)
+        if cone_angle > 0.0:  # (uniform regime: t_end = t_start + step)
+            slots["t1"] = torch.empty(max(R, 1), cap, device=dev)
         a.sample_t0, a.sample_cap = slots["t0"].data_ptr(), cap
         a.ex_weights, a.ex_alphas, a.ex_trans = slots["weights"].data_ptr(), slots["alphas"].data_ptr(), slots["trans"].data_ptr()
         a.ex_sigmas, a.ex_rgbs = slots["sigmas"].data_ptr(), slots["rgbs"].data_ptr()
@@ -1124,8 +1147,9 @@ def render_occ_fused(pm: PackedMLP, rays_o: Optional[Tensor], rays_d: Optional[T
         if launch_timer is not None:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-        L.check(L.lib().fsn_render_rays_occgrid(C.byref(pm.desc), pm.prec, _p(pm.blob), C.byref(a), _stream()),
-                "fsn_render_rays_occgrid")
+        L.check(L.lib().fsn_render_rays_occgrid_ex(C.byref(pm.desc), pm.prec, _p(pm.blob), C.byref(a), *march,
+                                                   _p(slots.get("t1")) if slots else None, _stream()),
+                "fsn_render_rays_occgrid_ex")
         if launch_timer is not None:
             e1.record()
             launch_timer.append((e0, e1))
@@ -1141,8 +1165,9 @@ def render_occ_fused(pm: PackedMLP, rays_o: Optional[Tensor], rays_d: Optional[T
                 order = ("weights", "alphas", "trans", "sigmas", "rgbs")
                 sp = (C.c_void_p * 5)(*[slots[k].data_ptr() for k in order])
                 op = (C.c_void_p * 5)(*[ex[k].data_ptr() for k in order])
-                L.check(L.lib().fsn_occ_gather_extras(_p(n_kept), _p(incl - n_kept), _p(slots["t0"]), int(max_steps), R, float(step),
-                                                      _p(ri), _p(ts), _p(te), sp, op, _stream()), "fsn_occ_gather_extras")
+                L.check(L.lib().fsn_occ_gather_ex(_p(n_kept), _p(incl - n_kept), _p(slots["t0"]), _p(slots.get("t1")),
+                                                  int(max_steps), R, float(step), _p(ri), _p(ts), _p(te), sp, op, _stream()),
+                        "fsn_occ_gather_ex")
             return colors, opacity, depth, counts, (ri, ts, te, ex)
     return colors, opacity, depth, counts
 

@@ -199,7 +199,8 @@ def _launch_size(rays_o, camera):
 
 # `sampling_kwargs` of render_rays / render_frame / render_path: what the reference hard-codes in its estimator.sampling
 # call (rendering.py:66-74) plus the occupancy march's cone angle and per-ray bounds.  The four scalars are arguments of
-# every occupancy kernel, fused ones included; cone_angle and t_min / t_max exist in the standalone march only.
+# every occupancy kernel, fused ones included; cone_angle and t_min / t_max are arguments of the standalone march and of
+# the one-launch kernel's extended entry point, which the routes use for them when FUSED_OCC_CONE is on (below).
 _SAMPLING_DEFAULTS = dict(near_plane=0.0, far_plane=1e10, early_stop_eps=1e-4, alpha_thre=0.0)
 _SAMPLING_MARCH_ONLY = ("cone_angle", "t_min", "t_max")
 
@@ -215,10 +216,21 @@ def _sampling_options(sampling_kwargs: Optional[dict], per_ray: bool = True) -> 
     return opts
 
 
-def _march_only(opts: Optional[dict]) -> bool:
-    """The options ask for what only the standalone march has: a cone angle or per-ray bounds."""
+def _has_march_options(opts: Optional[dict]) -> bool:
     opts = opts or {}
     return opts.get("cone_angle", 0.0) != 0.0 or opts.get("t_min") is not None or opts.get("t_max") is not None
+
+
+def _march_only(opts: Optional[dict]) -> bool:
+    """The options ask for a cone angle or per-ray bounds and the one-launch routes are closed to them (FUSED_OCC_CONE
+    off, read at call time): the call goes through the standalone march."""
+    return _has_march_options(opts) and not FUSED_OCC_CONE
+
+
+def _occ_max_steps(estimator, render_step_size: float, opts: Optional[dict]) -> int:
+    """Intervals a ray can have under the options: the cone march's count where a cone angle is given."""
+    opts = opts or {}
+    return estimator.max_steps(render_step_size, float(opts.get("cone_angle", 0.0)), float(opts.get("near_plane", 0.0)))
 
 
 def _stratified_args(estimator, net: NeRF, R: int, dev, u, u_fine, train: bool, opts: Optional[dict] = None) -> dict:
@@ -239,11 +251,13 @@ def _stratified_args(estimator, net: NeRF, R: int, dev, u, u_fine, train: bool, 
 def _occ_args(estimator, model: NeRF, render_step_size: float, u, dev, opts: Optional[dict] = None) -> dict:
     """The reference's estimator.sampling call (rendering.py:66-74: near_plane 0, far_plane 1e10, early_stop_eps 1e-4,
     alpha_thre 0, unless `opts` moves them) as the occupancy kernels' arguments; `u` = stratified jitter (one value per
-    ray) or None."""
-    scalars = {k: float((opts or {}).get(k, v)) for k, v in _SAMPLING_DEFAULTS.items()}
+    ray) or None.  A cone angle and per-ray bounds (FUSED_OCC_CONE) go through as they are."""
+    opts = opts or {}
+    scalars = {k: float(opts.get(k, v)) for k, v in _SAMPLING_DEFAULTS.items()}
     return dict(aabb=estimator.aabb, res=estimator.resolution, levels=estimator.levels, bits=estimator.bits,
-                step=render_step_size, max_steps=estimator.max_steps(render_step_size), u=u,
-                pos_mask=model._mask(model.pos_mask, dev), dir_mask=model._mask(model.dir_mask, dev), **scalars)
+                step=render_step_size, max_steps=_occ_max_steps(estimator, render_step_size, opts), u=u,
+                pos_mask=model._mask(model.pos_mask, dev), dir_mask=model._mask(model.dir_mask, dev),
+                cone_angle=float(opts.get("cone_angle", 0.0)), t_min=opts.get("t_min"), t_max=opts.get("t_max"), **scalars)
 
 
 def _fused_launch(rays_o, rays_d, camera, estimator, model, model_fine, train, bk, render_step_size, u, u_fine,
@@ -389,11 +403,23 @@ FUSED_OCC_SAMPLER = True
 FUSED_OCC_EXTRAS = True  # render_rays(want_extras=True) without gradients through the occupancy estimator: one launch + one gather
 FUSED_OCC_SAMPLER_MIN_RAYS = 4096
 FUSED_OCC_EXTRAS_MAX_SLOTS = 1 << 26  # rays x max_steps of the extras mode's per-ray slot rows (8 arrays of that many floats)
+# A cone angle or per-ray t_min / t_max on the one-launch routes (fsn_render_rays_occgrid_ex): off, because
+# tests/test_occ_cone_cpu.py pins such calls to estimator-sampling / chunked; on, they take the route the same call takes
+# without them, sized by the cone march's interval count.  tools/bench_occ_cone.py measures both settings.
+FUSED_OCC_CONE = False
 
 
-def _occ_fusable(estimator, model, model_fine, render_step_size: float) -> bool:
+def _occ_fusable(estimator, model, model_fine, render_step_size: float, opts: Optional[dict] = None) -> bool:
     return isinstance(estimator, OccGridEstimator) and isinstance(model, NeRF) and model_fine is None and \
-        model.precision in ("fp16x3", "bf16x3", "fp16", "bf16") and estimator.max_steps(render_step_size) <= FUSED_OCC_MAX_STEPS
+        model.precision in ("fp16x3", "bf16x3", "fp16", "bf16") and \
+        _occ_max_steps(estimator, render_step_size, opts) <= FUSED_OCC_MAX_STEPS
+
+
+def _extras_slots_fit(estimator, n_rays: int, render_step_size: float, opts: Optional[dict]) -> bool:
+    """The extras mode's per-ray slot rows against FUSED_OCC_EXTRAS_MAX_SLOTS, which counts eight arrays per slot: the
+    cone regime holds a ninth (the interval ends)."""
+    arrays = 9 if (opts or {}).get("cone_angle", 0.0) > 0.0 else 8
+    return n_rays * _occ_max_steps(estimator, render_step_size, opts) * arrays <= FUSED_OCC_EXTRAS_MAX_SLOTS * 8
 
 
 def _stratified_fusable(estimator, model, fine) -> bool:
@@ -404,15 +430,17 @@ def _rays_route(estimator, model, model_fine, needs_grad: bool, want_extras: boo
                 render_step_size: float, sampling_kwargs: Optional[dict] = None) -> str:
     """render_rays' launch route, from plain attribute tests (the FUSED_OCC_* switches are read at call time).  The
     scalar sampling options (planes, thresholds) are arguments of every route's kernels and choose nothing; a cone
-    angle or per-ray bounds exist in the standalone march only."""
+    angle or per-ray bounds take the standalone march unless FUSED_OCC_CONE opens the one-launch routes to them, which
+    then apply the rules below with the cone march's interval count."""
     if _march_only(sampling_kwargs):
         return "estimator-sampling"
+    opts = sampling_kwargs
     # (NeRF.cull_precision, opt-in: the cull's density pass runs as its own launch in that mode - the occupancy sampler)
     own_cull = isinstance(model, NeRF) and model.cull_precision is not None
-    if not needs_grad and not own_cull and _occ_fusable(estimator, model, model_fine, render_step_size):
+    if not needs_grad and not own_cull and _occ_fusable(estimator, model, model_fine, render_step_size, opts):
         if not want_extras:
             return "occ-frame"
-        if FUSED_OCC_EXTRAS and n_rays * estimator.max_steps(render_step_size) <= FUSED_OCC_EXTRAS_MAX_SLOTS:
+        if FUSED_OCC_EXTRAS and _extras_slots_fit(estimator, n_rays, render_step_size, opts):
             return "occ-extras"
     # the fused launch is forward-only; a training step goes through sampler -> model(x, d) -> rendering, each
     # differentiable where the reference's is
@@ -422,7 +450,7 @@ def _rays_route(estimator, model, model_fine, needs_grad: bool, want_extras: boo
             model.precision in ("fp16x3", "bf16x3", "fp16", "bf16", "fp16x2"):
         return "stratified-sampler"
     if FUSED_OCC_SAMPLER and (n_rays >= max(1, FUSED_OCC_SAMPLER_MIN_RAYS) or own_cull) and \
-            _occ_fusable(estimator, model, None, render_step_size):
+            _occ_fusable(estimator, model, None, render_step_size, opts):
         return "occ-sampler"
     return "estimator-sampling"
 
@@ -446,7 +474,8 @@ def render_rays(rays_o: Tensor, rays_d: Tensor, estimator, model: nn.Module, tra
     `sampling_kwargs`: options of the estimator's sampling call the reference hard-codes - `near_plane`, `far_plane`,
     `early_stop_eps`, `alpha_thre` (every occupancy route takes them) - and of the occupancy march: `cone_angle`
     (dt = max(t cone_angle, render_step_size)) and per-ray `t_min` / `t_max` [n_rays], which go through
-    `estimator.sampling`.  None is the reference's call; an unknown key is a TypeError."""
+    `estimator.sampling` (with FUSED_OCC_CONE on: through the route the call takes without them).  None is the
+    reference's call; an unknown key is a TypeError."""
     opts = _sampling_options(sampling_kwargs)
     rays_o = rays_o.to(device)
     rays_d = rays_d.to(device)
@@ -480,7 +509,8 @@ def _frame_route(estimator, model, model_fine, training: bool, ndc: bool, render
         # the chunked one.
         return "camera-stratified"
     own_cull = isinstance(model, NeRF) and model.cull_precision is not None  # (opt-in: sampler launch + full pass)
-    if not training and not ndc and not own_cull and _occ_fusable(estimator, model, model_fine, render_step_size):
+    if not training and not ndc and not own_cull and \
+            _occ_fusable(estimator, model, model_fine, render_step_size, sampling_kwargs):
         return "camera-occupancy"  # the reference's own frame path (occupancy estimator): ONE launch
     return "chunked"
 

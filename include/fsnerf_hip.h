@@ -362,6 +362,21 @@ typedef struct fsn_occ_render_args {
 
 int fsn_render_rays_occgrid(const fsn_mlp_desc* desc, int prec, const void* blob, const fsn_occ_render_args* args_host,
                             fsn_stream_t stream);
+/* fsn_render_rays_occgrid_ex: the same launch with the march of fsn_occgrid_march_ex - its definition below, per-ray
+ * bounds and cone regime included, is the fused kernel's as well (one device function serves both kernels), so the
+ * results stay the unfused sequence's with fsn_occgrid_march_ex in the first place.  fsn_render_rays_occgrid is this
+ * entry point with cone_angle = 0 and NULL pointers: one kernel template serves both, instantiated without the extended
+ * march for such a launch (the code of the plain lattice) and with it otherwise - the same results where both apply.
+ *   cone_angle / t_min / t_max (DEVICE float [R] or NULL): as fsn_occgrid_march_ex; every candidate keeps the interval
+ *   end the march gave it (no common width).  max_steps counts the cone march's intervals (<= 2048 here).
+ *   sample_t1: DEVICE float [R, sample_cap] or NULL: in the sampler / extras mode the kept samples' interval ENDS, next
+ *   to their starts in sample_t0; required there when cone_angle > 0 (an end is not start + step), ignored outside
+ *   those modes.
+ * FSN_E_INVALID (before any device work): cone_angle < 0; cone_angle > 0 with near_plane < 0; t_min / t_max with a
+ * camera instead of ray arrays; cone_angle > 0 in the sampler / extras mode without sample_t1. */
+int fsn_render_rays_occgrid_ex(const fsn_mlp_desc* desc, int prec, const void* blob, const fsn_occ_render_args* args_host,
+                               float cone_angle, const float* t_min, const float* t_max, float* sample_t1,
+                               fsn_stream_t stream);
 /* Packed (ray_indices, t_starts, t_ends = t_start + step) from the sampler mode's per-ray slots: offsets = exclusive
  * scan of n_kept (int64 [R]); the outputs hold sum(n_kept) entries, sorted by ray then t - what fsn_occgrid_march +
  * fsn_packed_visibility + a compaction produce, bit for bit. */
@@ -373,6 +388,12 @@ int fsn_occ_gather_samples(const int32_t* n_kept, const int64_t* offsets, const 
 int fsn_occ_gather_extras(const int32_t* n_kept, const int64_t* offsets, const float* sample_t0, int sample_cap, int64_t R,
                           float step, int64_t* ray_indices, float* t_starts, float* t_ends,
                           const float* const* slots_host_of_dev, float* const* out_host_of_dev, fsn_stream_t stream);
+/* Both gathers with optional end rows: sample_t1 (fsn_render_rays_occgrid_ex) != NULL: t_ends are copied from it; NULL:
+ * t_start + step.  slots / outputs both NULL: samples only.  The two entry points above are this one with
+ * sample_t1 = NULL. */
+int fsn_occ_gather_ex(const int32_t* n_kept, const int64_t* offsets, const float* sample_t0, const float* sample_t1,
+                      int sample_cap, int64_t R, float step, int64_t* ray_indices, float* t_starts, float* t_ends,
+                      const float* const* slots_host_of_dev, float* const* out_host_of_dev, fsn_stream_t stream);
 
 /* ---- "next" rows ------------------------------------------------------------------ */
 
