@@ -6,6 +6,7 @@ estimator.update_every_n_steps) and evaluated with render_frame + PSNR and SSIM 
 
     python examples/train_synthetic.py [--estimator occgrid|stratified] [--iters 400] [--hw 64] [--u8-dataset]
                                        [--depth-weight W] [--distortion-weight W] [--cone-angle A] [--near-plane T]
+                                       [--mark-invisible] [--min-views K]
 
 --u8-dataset: the teacher's frames become uint8 "photographs" (R.to8b) held in a device-resident RayDataset; the loop
 takes its batches from a RayLoader the way run-nerf.py:236-240 takes them from its DataLoader, and the held-out view
@@ -19,6 +20,10 @@ loss of the compositor's weights (core.loss.DistortionLoss).
 --cone-angle / --near-plane (both 0 by default): `sampling_kwargs` of render_rays / render_frame / render_path - the
 occupancy march's step grows with distance, dt = max(t * cone_angle, step), and nothing is sampled in front of the near
 plane - in training, evaluation and the path render alike.
+
+--mark-invisible (off by default): before the first step the occupancy estimator takes every cell that fewer than
+--min-views K (default 1) training views see out of the grid for good (OccGridEstimator.mark_invisible_from_views: a
+conservative frustum / box test); no later refresh switches such a cell on.
 """
 import argparse
 import math
@@ -82,9 +87,16 @@ def main():
                          "(sampling_kwargs of render_rays / render_frame; nerfacc uses 0.004 for unbounded scenes)")
     ap.add_argument("--near-plane", type=float, default=0.0,
                     help="opt-in: no samples in front of this distance (sampling_kwargs, any estimator)")
+    ap.add_argument("--mark-invisible", action="store_true",
+                    help="opt-in: cells outside the training views' frusta leave the occupancy grid before the first step "
+                         "(OccGridEstimator.mark_invisible_from_views)")
+    ap.add_argument("--min-views", type=int, default=1,
+                    help="with --mark-invisible: a cell stays only if at least this many training views see it (few-shot: 2)")
     a = ap.parse_args()
     if a.cone_angle and a.estimator != "occgrid":
         ap.error("--cone-angle belongs to the occupancy estimator")
+    if a.mark_invisible and a.estimator != "occgrid":
+        ap.error("--mark-invisible belongs to the occupancy estimator")
     sampling_kwargs = {k: v for k, v in (("cone_angle", a.cone_angle), ("near_plane", a.near_plane)) if v != 0.0} or None
     if a.depth_weight and a.u8_dataset:
         ap.error("--depth-weight needs the float tables: the uint8 dataset carries no depth")
@@ -124,6 +136,13 @@ def main():
     else:
         estimator = R.StratifiedEstimator(near, far, 64, 128)
     estimator.train()
+    if a.mark_invisible:  # once, before the first step (nerfacc's mark_invisible_cells, on the reference's cameras)
+        if a.u8_dataset:
+            estimator.mark_invisible_from_views(train_set.poses, train_set.hwf, ndc=train_set.ndc, min_views=a.min_views)
+        else:
+            estimator.mark_invisible_from_views(torch.stack(poses), hwf, min_views=a.min_views)
+        print(f"marked: {100.0 * (1.0 - float(estimator.visible.float().mean())):.1f} % of the grid's cells are seen by fewer "
+              f"than {a.min_views} of the {len(poses)} training views", flush=True)
     optimizer = FusedAdam(model.parameters(), lr=5e-4)  # torch.optim.Adam's arithmetic, one launch over flat arenas
     wnorm = WeightNormRegularizer(model.named_parameters(), reg="l2", reg_ratio=0.5, Td=a.iters)  # run-nerf.py:266-279
     alpha = 1e-5

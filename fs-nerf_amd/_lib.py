@@ -120,6 +120,8 @@ SIGNATURES = {
     "fsn_occgrid_update_multi": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _f, _vp]),
     "fsn_occgrid_refresh": (_i, [_PD, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i64, _i64, _vp, _f, _vp, _vp, _vp, _vp]),
     "fsn_occgrid_apply_pending": (_i, [_vp, _i64, _vp, _f, _vp]),
+    "fsn_occgrid_visibility": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _f, _i, _i, _f, _f, _f, _vp, _vp]),
+    "fsn_occgrid_update_masked": (_i, [_vp, _i64, _vp, _f, _i, _vp, _vp, _vp]),
     "fsn_adam_step": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _d, _d, _d, _d, _d, _d, _vp, _vp, _vp]),
     "fsn_adam_step_dev": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _d, _d, _d, _d, _d, _d, _vp, _vp, _vp]),
     "fsn_weight_norm_workspace_floats": (_i64, [_i, _vp]),

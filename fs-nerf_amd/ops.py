@@ -1256,6 +1256,37 @@ def occgrid_apply_pending(occs: Tensor, pending: Tensor, decay: float) -> None:
                 "fsn_occgrid_apply_pending")
 
 
+def occgrid_visibility(aabb: Sequence[float], res: int, levels: int, cams: Tensor, width: int, height: int,
+                       near_plane: float, min_views: int, visible: Tensor, ndc: Optional[Tuple[float, float, float]] = None) -> None:
+    """visible (int32 [levels res^3 / 32], layout of `bits`) = the cells at least `min_views` of the cameras cover and
+    none is too near to (fsn_occgrid_visibility; the rule is in include/fsnerf_hip.h).  cams: device float32 [N,16], the
+    world -> camera map [3,4] then fx, fy, cx, cy.  ndc: (W / 2f, H / 2f, near) of a grid in NDC space."""
+    if not cams.is_cuda or not visible.is_cuda:
+        raise RuntimeError("occgrid_visibility: needs device tensors (there is no CPU path)")
+    if cams.dtype != torch.float32 or cams.dim() != 2 or cams.shape[1] != 16 or not cams.is_contiguous():
+        raise ValueError("occgrid_visibility: cams must be a contiguous float32 [N,16]")
+    if visible.dtype != torch.int32 or visible.numel() != int(levels) * int(res) ** 3 // 32:
+        raise ValueError("occgrid_visibility: visible must be int32 [levels res^3 / 32]")
+    ab = (C.c_float * 6)(*[float(v) for v in aabb])
+    wf, hf, nr = (0.0, 0.0, 0.0) if ndc is None else (float(v) for v in ndc)
+    with torch.cuda.device(visible.device):
+        L.check(L.lib().fsn_occgrid_visibility(ab, int(res), int(levels), _p(cams), cams.shape[0], int(width), int(height),
+                                               float(near_plane), int(min_views), 0 if ndc is None else 1, wf, hf, nr,
+                                               _p(visible), _stream()), "fsn_occgrid_visibility")
+
+
+def occgrid_update_masked(occs: Tensor, bits: Optional[Tensor], visible: Tensor, occ_thre: float, scratch: Tensor,
+                          revive: bool = False) -> None:
+    """The end of an update on a marked grid (fsn_occgrid_update_masked): occs = -1 at the invisible cells, bits =
+    (occs > min(mean of occs over the visible cells, occ_thre)) & visible (bits None: occs only; revive: a visible cell
+    holding -1 becomes 0).  scratch: float64 [2048].  No host sync."""
+    if scratch.dtype != torch.float64 or scratch.numel() < 2048:
+        raise ValueError("occgrid_update_masked: scratch must be float64 [2048]")
+    with torch.cuda.device(occs.device):
+        L.check(L.lib().fsn_occgrid_update_masked(_p(occs), occs.numel(), _p(visible), float(occ_thre), 1 if revive else 0,
+                                                  _p(scratch), _p(bits), _stream()), "fsn_occgrid_update_masked")
+
+
 # ------------------------------------------------------------------ evaluation metrics (run-nerf.py:108-191)
 def _f32_view(t: Tensor, name: str) -> Tensor:
     """_f32 without the copy to a contiguous tensor: the metric kernels take any element strides."""

@@ -40,6 +40,7 @@ class OccGridEstimator(nn.Module):
         self._pending = None   # scratch of the duplicate-safe EMA / the selection's popcount prefix (device)
         self._prefix = None
         self._prefix_levels = None  # ... of all levels at once (the fused refresh)
+        self._mask_scratch = None   # partial sums of the masked end of an update (a marked estimator only)
 
     # -- state ---------------------------------------------------------------------
     # The update count is part of the draws' seed (update_seed): the state_dict carries it, so that a resumed run continues
@@ -52,6 +53,13 @@ class OccGridEstimator(nn.Module):
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
         state_dict.setdefault(prefix + "_extra_state", 0)  # (load_state_dict hands each module its own copy)
+        # the visibility mask exists from the first mark_invisible_* call on: a marked state registers it here, a
+        # state without it (saved unmarked, or before the mask existed) loads as all-visible
+        if prefix + "vis_bits" in state_dict:
+            if not self.marked:
+                self.register_buffer("vis_bits", torch.zeros_like(self.bits))
+        elif self.marked:
+            del self._buffers["vis_bits"]
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     # -- helpers -------------------------------------------------------------------
@@ -63,11 +71,115 @@ class OccGridEstimator(nn.Module):
         return b.reshape(self.levels, self.resolution, self.resolution, self.resolution)
 
     def set_binaries(self, binaries: Tensor) -> None:
-        """Load an explicit occupancy ([levels, res, res, res] bool); occs become 1 / 0."""
+        """Load an explicit occupancy ([levels, res, res, res] bool); occs become 1 / 0 (on a marked estimator -1 at
+        the invisible cells, which stay off)."""
         flat = binaries.reshape(-1).to(self.occs.device)
         self.occs.copy_(flat.float())
+        if self.marked:
+            self._finish_masked(0.5)
+            return
         thr = torch.full((1,), 0.5, device=self.occs.device)
         ops.occgrid_update(self.occs, self.bits, None, None, 1.0, thr)
+
+    # -- cells no training camera sees ---------------------------------------------
+    @property
+    def marked(self) -> bool:
+        """mark_invisible_cells / mark_invisible_from_views has run (or a marked state_dict was loaded)."""
+        return "vis_bits" in self._buffers
+
+    @property
+    def visible(self) -> Tensor:
+        """[levels, res, res, res] bool view of the visibility mask, like `binaries`; all True when never marked."""
+        shape = (self.levels, self.resolution, self.resolution, self.resolution)
+        if not self.marked:
+            return torch.ones(shape, dtype=torch.bool, device=self.bits.device)
+        shifts = torch.arange(32, device=self.bits.device, dtype=torch.int32)
+        return ((self.vis_bits[:, None] >> shifts[None, :]) & 1).bool().reshape(shape)
+
+    def _finish_masked(self, occ_thre: float, revive: bool = False) -> None:
+        """The end of an update on a marked estimator: occs = -1 at the invisible cells, bits = (occs > min(mean over the
+        visible cells, occ_thre)) & visible - two launches, no host sync (fsn_occgrid_update_masked)."""
+        if self._mask_scratch is None or self._mask_scratch.device != self.occs.device:
+            self._mask_scratch = torch.empty(2048, dtype=torch.float64, device=self.occs.device)
+        ops.occgrid_update_masked(self.occs, self.bits, self.vis_bits, occ_thre, self._mask_scratch, revive=revive)
+
+    def _mark(self, w2c: Tensor, fx, fy, cx, cy, width: int, height: int, near_plane: float, min_views: int, ndc) -> None:
+        """cameras (world -> camera [N,3,4] in the kernel's convention, float64, any device) -> the mask; replaces an
+        earlier one."""
+        dev = self.occs.device
+        N = w2c.shape[0]
+        intr = torch.stack([torch.as_tensor(v, dtype=torch.float64, device=w2c.device).expand(N) for v in (fx, fy, cx, cy)], 1)
+        cams = torch.cat([w2c.reshape(N, 12), intr], 1).to(torch.float32).contiguous().to(dev)
+        vis = torch.empty_like(self.bits)
+        ops.occgrid_visibility(self.aabb, self.resolution, self.levels, cams, int(width), int(height), float(near_plane),
+                               int(min_views), vis, ndc=ndc)
+        if self.marked:
+            self.vis_bits.copy_(vis)
+        else:
+            self.register_buffer("vis_bits", vis)
+        self.bits &= self.vis_bits
+        if self._mask_scratch is None or self._mask_scratch.device != dev:
+            self._mask_scratch = torch.empty(2048, dtype=torch.float64, device=dev)
+        ops.occgrid_update_masked(self.occs, None, self.vis_bits, 0.0, self._mask_scratch, revive=True)  # (occs only)
+
+    def _check_mark(self, poses: Tensor, width: int, height: int, near_plane: float, min_views: int) -> None:
+        """The argument checks of both mark_invisible_* calls: they run before any launch."""
+        if self.occs.device.type != "cuda":
+            raise RuntimeError("mark_invisible_cells: the estimator must be on the GPU (there is no CPU path)")
+        if int(min_views) < 1:
+            raise ValueError("min_views must be at least 1")
+        if not float(near_plane) >= 0.0:
+            raise ValueError("near_plane must not be negative")
+        if int(width) <= 0 or int(height) <= 0:
+            raise ValueError("the image size must be positive")
+        if poses.dim() != 3 or poses.shape[0] < 1 or poses.shape[1] not in (3, 4) or poses.shape[2] != 4:
+            raise ValueError("camera poses must be [N,3,4] or [N,4,4], N >= 1")
+
+    @staticmethod
+    def _world_to_camera(c2w: Tensor) -> Tensor:
+        """[N,3,4] / [N,4,4] camera -> world (rigid) -> float64 world -> camera [N,3,4]: [R^T | -R^T t]."""
+        c2w = c2w.detach().to(torch.float64)
+        Rt, t = c2w[:, :3, :3].transpose(1, 2), c2w[:, :3, 3]
+        # (written out, not a matmul: tests/occ_invisible_ref.py forms the same table with the same roundings)
+        tt = -((Rt[:, :, 0] * t[:, None, 0] + Rt[:, :, 1] * t[:, None, 1]) + Rt[:, :, 2] * t[:, None, 2])
+        return torch.cat([Rt, tt[:, :, None]], 2)
+
+    @torch.no_grad()
+    def mark_invisible_cells(self, K: Tensor, c2w: Tensor, width: int, height: int, near_plane: float = 0.0,
+                             chunk: Optional[int] = None, *, min_views: int = 1) -> None:
+        """nerfacc's call of the same name: take every cell that fewer than `min_views` of the cameras cover, or that is
+        nearer than `near_plane` to one, out of the grid for good (occs = -1, nerfacc's convention; later updates keep
+        it off).  K [3,3] or [N,3,3], c2w [N,3,4] or [N,4,4], OpenCV convention (x right, y down, z forward); a pixel
+        is in the image iff 0 <= u < width, 0 <= v < height.  Unlike nerfacc's one-point test the rule is a conservative
+        frustum / box test (include/fsnerf_hip.h at fsn_occgrid_visibility): no cell a frustum meets is removed.
+        `near_plane` is a depth along the optical axis.  `chunk` is accepted and ignored; a second call replaces the
+        mask.  No host synchronisation beyond moving the camera table to the device."""
+        K, c2w = torch.as_tensor(K), torch.as_tensor(c2w)
+        self._check_mark(c2w, width, height, near_plane, min_views)
+        if K.dim() == 2:
+            K = K[None].expand(c2w.shape[0], *K.shape)
+        if K.dim() != 3 or K.shape[1:] != (3, 3) or K.shape[0] != c2w.shape[0]:
+            raise ValueError("K must be [3,3] or [N,3,3] with one matrix per pose")
+        w2c = self._world_to_camera(c2w)
+        K = K.detach().to(device=w2c.device, dtype=torch.float64)
+        self._mark(w2c, K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2], width, height, near_plane, min_views, None)
+
+    @torch.no_grad()
+    def mark_invisible_from_views(self, poses: Tensor, hwf, near_plane: float = 0.0, *, ndc: bool = False,
+                                  min_views: int = 1) -> None:
+        """mark_invisible_cells for the reference's cameras: `get_rays` poses (x right, y up, looking down -z) and
+        (H, W, focal), as RayDataset.poses / .hwf / .ndc hold them.  The ray of pixel i passes u = i, so its footprint
+        is [i - 1/2, i + 1/2]: the principal point moves to W/2 + 1/2, H/2 + 1/2 and the frustum 0 <= u' < W is the union
+        of the pixel footprints.  ndc: the grid lives in the NDC space of to_ndc with near = 1 (the LLFF path)."""
+        H, W, focal = int(hwf[0]), int(hwf[1]), float(hwf[2])
+        poses = torch.as_tensor(poses)
+        self._check_mark(poses, W, H, near_plane, min_views)
+        if not focal > 0.0:
+            raise ValueError("the focal length must be positive")
+        flip = torch.tensor([1.0, -1.0, -1.0, 1.0], dtype=torch.float64, device=poses.device)
+        w2c = self._world_to_camera(poses.detach().to(torch.float64)[:, :3, :] * flip)
+        self._mark(w2c, focal, focal, W / 2.0 + 0.5, H / 2.0 + 0.5, W, H, near_plane, min_views,
+                   (W / (2.0 * focal), H / (2.0 * focal), 1.0) if ndc else None)
 
     def level_aabb(self, lvl: int):
         c = [(self.aabb[a] + self.aabb[3 + a]) / 2.0 for a in range(3)]
@@ -150,6 +262,9 @@ class OccGridEstimator(nn.Module):
                 occ = occ_eval_fn(x).reshape(-1).float()
                 ops.occgrid_update_multi(self.occs, self._pending, cells, occ, ema_decay)
         self._updates += 1
+        if self.marked:  # (the EMA wrote max(-0.95, occ) into the invisible cells: restored here)
+            self._finish_masked(occ_thre)
+            return
         thr = torch.clamp(self.occs.mean(), max=occ_thre).reshape(1)
         ops.occgrid_update(self.occs, self.bits, None, None, 1.0, thr)
 

@@ -625,6 +625,32 @@ int fsn_occgrid_refresh(const fsn_mlp_desc* desc, int prec, const void* blob, co
                         const uint64_t* seeds_host, float step, int32_t* prefix_scratch, uint32_t* pending,
                         uint32_t* status, fsn_stream_t stream);
 int fsn_occgrid_apply_pending(float* occs, int64_t n_cells, uint32_t* pending, float decay, fsn_stream_t stream);
+/* OccGridEstimator.mark_invisible_cells (csrc/occ_invisible.hip): which cells any training camera can see.  nerfacc
+ * tests one lattice point per cell; this rule is a conservative frustum / box test instead (a removed cell is a permanent
+ * hole), and it is this build's definition - tests/occ_invisible_ref.py restates it in float32, bit for bit.
+ *   cell box: level l's box [lo, hi] (roi scaled by 2^l about its centre, in double, rounded once), w = (hi - lo) / res
+ *   per axis, cell (ix, iy, iz) = [lo + i w, lo + (i + 1) w]; centre = mean of the two ends per axis.
+ *   cams: DEVICE float [n_cams,16] = world -> camera map [3,4] row major (camera x right, y down, z = depth forward),
+ *   then fx, fy, cx, cy.  Camera-space point (X, Y, D), each ((m0 x + m1 y) + m2 z) + m3, has the margins D - near_plane,
+ *   fx X + cx D, (width - cx) D - fx X, fy Y + cy D, (height - cy) D - fy Y.
+ *   A camera covers a cell unless all 8 corners are negative in one of the five margins; a cell is too near a camera
+ *   when its centre has the four side margins >= 0 and 0 <= D < near_plane (a depth along the optical axis, not a ray
+ *   parameter).  visible = covered by at least min_views cameras and too near to none.
+ *   ndc != 0: the grid lives in the NDC space of to_ndc with near = ndc_near; the box is clipped to z' <= 1 - 1e-6 (a
+ *   cell with nothing left is invisible) and its corners and centre are mapped back first: z = 2 ndc_near / (z' - 1),
+ *   x = ((-x') z) ndc_wf, y = ((-y') z) ndc_hf, with ndc_wf = W / (2 focal), ndc_hf = H / (2 focal).
+ *   visible: DEVICE uint32 [levels res^3 / 32], word / bit layout of `bits`; levels * res^3 % 64 == 0.  Any n_cams >= 1.
+ *   FSN_E_INVALID: null pointers, n_cams < 1, min_views < 1, near_plane < 0, width or height <= 0.
+ * fsn_occgrid_update_masked: the end of an update on a marked grid, two launches, no host synchronisation:
+ *   occs = -1 at the invisible cells (revive != 0: a visible cell holding -1 becomes 0 first - a mask that was replaced),
+ *   threshold = min(mean of occs over the visible cells, occ_thre) (sum in double, fixed order; no visible cell:
+ *   occ_thre), bits = (occs > threshold) & visible (bits == NULL: the first launch only, occs alone).  scratch: DEVICE
+ *   double [2048].  n_cells % 64 == 0. */
+int fsn_occgrid_visibility(const float* aabb_host, int res, int levels, const float* cams, int n_cams, int width,
+                           int height, float near_plane, int min_views, int ndc, float ndc_wf, float ndc_hf,
+                           float ndc_near, uint32_t* visible, fsn_stream_t stream);
+int fsn_occgrid_update_masked(float* occs, int64_t n_cells, const uint32_t* visible, float occ_thre, int revive,
+                              double* scratch, uint32_t* bits, fsn_stream_t stream);
 
 /* f3: to8b(x) = (255 * clip(x, 0, 1)).astype(uint8)                    src/render/rendering.py:21 */
 int fsn_to8b(const float* x, int64_t n, uint8_t* out, fsn_stream_t stream);

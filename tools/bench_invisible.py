@@ -1,0 +1,208 @@
+#!/usr/bin/env python3
+"""What OccGridEstimator.mark_invisible_cells / mark_invisible_from_views costs and what it saves, from device events
+after a warm-up, medians of runs alternated in one process (the method of tools/bench_refresh.py / bench_march.py).
+Appends one JSON line per section to profiles/bench_invisible.jsonl:
+
+  visibility   the visibility kernel alone (ops.occgrid_visibility): 128^3 cells at 1 and 4 levels, 3 and 100 cameras
+  refresh      update_every_n_steps on a marked against an unmarked estimator (the callable route and the fused fp16
+               route), warm-up and steady phase, alternated call by call; "spread" is the unmarked estimator against
+               itself (two instances in the same alternation): the noise the difference has to be read against
+  effect       two scenes, unmarked / min_views 1 / min_views 2: share of cells removed per level, marched samples per
+               4096-ray batch right after the warm-up refresh, and the time of a training step (render_rays(train=True),
+               MSE, backward, FusedAdam) on that batch.  "orbit3": the example's scene seen from 3 of its orbit views
+               (roi +-1.5, 128^3, 1 level); "ndc4": a forward-facing NDC scene with the reference's 4-level LLFF grid
+               (build_rays(ndc=True)'s roi), 3 views
+
+Run it under a time limit of its own:
+
+    timeout -k 10 540 python tools/bench_invisible.py [--iters 20] [--warmup 3] [--sections visibility,refresh,effect]
+"""
+import argparse
+import json
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import fs_nerf_amd  # noqa: E402,F401
+from fs_nerf_amd import ops  # noqa: E402
+from fs_nerf_amd.core.models import NeRF  # noqa: E402
+from fs_nerf_amd.core.optim import FusedAdam  # noqa: E402
+from fs_nerf_amd.render import rendering as R  # noqa: E402
+from fs_nerf_amd.render.occgrid import OccGridEstimator  # noqa: E402
+from fs_nerf_amd.utils import utilities as U  # noqa: E402
+
+AABB = [-1.5, -1.5, -1.5, 1.5, 1.5, 1.5]
+RES, STEP = 128, 5e-3
+
+
+def stats(t):
+    return {"median": round(float(np.median(t)), 4), "min": round(float(np.min(t)), 4), "p90": round(float(np.percentile(t, 90)), 4)}
+
+
+def timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def alternate(variants, iters, warmup):
+    """{name: fn} -> {name: [ms]}: the variants alternated run by run, so that clock and thermal drift hit all alike."""
+    times = {name: [] for name in variants}
+    for it in range(warmup + iters):
+        for name, fn in variants.items():
+            t = timed(fn)
+            if it >= warmup:
+                times[name].append(t)
+    return times
+
+
+def orbit_pose(phi_deg, theta_deg=50.0, radius=4.0311289):
+    th, ph = theta_deg / 180.0 * math.pi, phi_deg / 180.0 * math.pi
+    tr = torch.tensor([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, radius], [0, 0, 0, 1.0]])
+    rt = torch.tensor([[1, 0, 0, 0], [0, math.cos(th), -math.sin(th), 0], [0, math.sin(th), math.cos(th), 0], [0, 0, 0, 1.0]])
+    rp = torch.tensor([[math.cos(ph), -math.sin(ph), 0, 0], [math.sin(ph), math.cos(ph), 0, 0], [0, 0, 1, 0], [0, 0, 0, 1.0]])
+    return rp @ (rt @ tr)
+
+
+def forward_pose(ax, ay, t):
+    rx = torch.tensor([[1, 0, 0], [0, math.cos(ax), -math.sin(ax)], [0, math.sin(ax), math.cos(ax)]])
+    ry = torch.tensor([[math.cos(ay), 0, math.sin(ay)], [0, 1, 0], [-math.sin(ay), 0, math.cos(ay)]])
+    m = torch.eye(4)
+    m[:3, :3], m[:3, 3] = ry @ rx, torch.tensor(t)
+    return m
+
+
+def make_model(dev, seed=2):
+    """The example's student: 8x256, the sigma head scaled and shifted so that part of the volume is dense."""
+    torch.manual_seed(seed)
+    m = NeRF(3, 3, 8, 256, (4,), pos_fn={"n_freqs": 10, "log_space": True}, dir_fn={"n_freqs": 4, "log_space": True})
+    with torch.no_grad():
+        m.sigma.weight.mul_(64.0)
+        m.sigma.bias.add_(3.0)
+    return m.to(dev).train()
+
+
+def make_est(dev, aabb, levels, seed=5):
+    est = OccGridEstimator(aabb, RES, levels).to(dev).train()
+    est.generator = torch.Generator().manual_seed(seed)
+    return est
+
+
+def random_cams(n, dev, seed=0):
+    """n random cameras around the roi in the kernel's form ([n,16] on the device)."""
+    hw, focal = 64, 0.5 * 64 / math.tan(0.5 * 0.6911112)
+    g = torch.Generator().manual_seed(seed)
+    poses = torch.stack([orbit_pose(float(torch.rand(1, generator=g)) * 360.0, 20.0 + float(torch.rand(1, generator=g)) * 60.0)
+                         for _ in range(n)])
+    c2w = poses.double()[:, :3, :] * torch.tensor([1.0, -1.0, -1.0, 1.0], dtype=torch.float64)
+    w2c = OccGridEstimator._world_to_camera(c2w)
+    intr = torch.tensor([focal, focal, hw / 2.0 + 0.5, hw / 2.0 + 0.5], dtype=torch.float64).expand(n, 4)
+    return torch.cat([w2c.reshape(n, 12), intr], 1).float().contiguous().to(dev), hw
+
+
+def bench_visibility(dev, args):
+    out = {}
+    for levels in (1, 4):
+        vis = torch.empty(levels * RES ** 3 // 32, dtype=torch.int32, device=dev)
+        variants = {}
+        for n in (3, 100):
+            cams, hw = random_cams(n, dev)
+            variants[f"cams{n}"] = (lambda c=cams, h=hw: ops.occgrid_visibility(AABB, RES, levels, c, h, h, 0.0, 1, vis))
+        times = alternate(variants, args.iters, args.warmup)
+        out[f"levels{levels}"] = {k + "_ms": stats(t) for k, t in times.items()}
+    return out
+
+
+def bench_refresh(dev, args):
+    model = make_model(dev)
+    closure = lambda x: model(x) * STEP
+    fused = model.occ_eval_fn(STEP, "fp16")
+    poses = torch.stack([orbit_pose(phi) for phi in (0.0, 120.0, 240.0)])
+    hwf = (64, 64, 0.5 * 64 / math.tan(0.5 * 0.6911112))
+    out = {}
+    for levels in (1, 4):
+        for route, fn in (("callable", closure), ("fused_fp16", fused)):
+            ests = {"unmarked": make_est(dev, AABB, levels), "unmarked_again": make_est(dev, AABB, levels),
+                    "marked": make_est(dev, AABB, levels)}
+            ests["marked"].mark_invisible_from_views(poses, hwf, min_views=1)
+            for phase, step in (("warmup", 0), ("steady", 256)):
+                times = alternate({k: (lambda e=e: e.update_every_n_steps(step, fn, occ_thre=1e-2)) for k, e in ests.items()},
+                                  args.iters, args.warmup)
+                med = {k: float(np.median(t)) for k, t in times.items()}
+                out[f"levels{levels}_{route}_{phase}"] = {
+                    **{k + "_ms": stats(t) for k, t in times.items()},
+                    "spread_ms": round(abs(med["unmarked_again"] - med["unmarked"]), 4),
+                    "marked_minus_unmarked_ms": round(med["marked"] - med["unmarked"], 4),
+                    "visible_share": round(float(ests["marked"].visible.float().mean()), 4)}
+    out["precision_after"] = fused.precision
+    return out
+
+
+def bench_effect(dev, args):
+    out = {}
+    hwf = (64, 64, 0.5 * 64 / math.tan(0.5 * 0.6911112))
+    orbit = torch.stack([orbit_pose(phi) for phi in (0.0, 120.0, 240.0)])
+    fwd = torch.stack([forward_pose(0.0, 0.0, (0.0, 0.0, 0.0)), forward_pose(0.08, -0.12, (0.25, -0.1, 0.05)),
+                       forward_pose(-0.06, 0.15, (-0.3, 0.15, -0.04))])
+    for scene, poses, ndc, levels in (("orbit3", orbit, False, 1), ("ndc4", fwd, True, 4)):
+        ro, rd, aabb = U.build_rays(poses, hwf, dev, ndc=ndc)
+        aabb = [float(v) for v in aabb.tolist()]
+        idx = torch.randint(0, ro.shape[0], (4096,), device=dev, generator=torch.Generator(device=dev).manual_seed(0))
+        rays_o, rays_d = ro[idx].contiguous(), rd[idx].contiguous()
+        target = torch.rand(4096, 3, device=dev, generator=torch.Generator(device=dev).manual_seed(1))
+        model = make_model(dev)
+        opt = FusedAdam(model.parameters(), lr=1e-9)  # (the network stays what it is: every variant sees the same one)
+        closure = lambda x: model(x) * STEP
+        ests, res = {}, {}
+        for name, mv in (("unmarked", 0), ("min_views1", 1), ("min_views2", 2)):
+            est = make_est(dev, aabb, levels)
+            est.generator = torch.Generator(device=dev).manual_seed(5)  # (render_rays(train=True) draws its jitter from it)
+            if mv:
+                est.mark_invisible_from_views(poses, hwf, ndc=ndc, min_views=mv)
+            est.update_every_n_steps(0, closure, occ_thre=1e-2)  # the warm-up refresh
+            ri, _, _ = est.sampling(rays_o, rays_d, render_step_size=STEP)
+            res[name] = {"removed_share_per_level": [round(1.0 - float(v), 4) for v in est.visible.float().mean(dim=(1, 2, 3))],
+                         "occupied_cells_per_level": [int(v) for v in est.binaries.sum(dim=(1, 2, 3))],
+                         "marched_samples_per_4096_rays": int(ri.numel())}
+            ests[name] = est
+
+        def train_step(est):
+            (rgb, _, _, _), _, _ = R.render_rays(rays_o, rays_d, est, model, train=True, white_bkgd=True, render_step_size=STEP, device=dev)
+            torch.nn.functional.mse_loss(rgb, target).backward()
+            opt.step()
+            opt.zero_grad()
+
+        times = alternate({k: (lambda e=e: train_step(e)) for k, e in ests.items()}, args.iters, args.warmup)
+        for k, t in times.items():
+            res[k]["train_step_ms"] = stats(t)
+        out[scene] = {"aabb": [round(v, 4) for v in aabb], "levels": levels, "views": int(poses.shape[0]), **res}
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--sections", default="visibility,refresh,effect")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_invisible.jsonl"))
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    sections = {"visibility": bench_visibility, "refresh": bench_refresh, "effect": bench_effect}
+    for name in args.sections.split(","):
+        line = json.dumps({"tool": "bench_invisible", "section": name, "device": torch.cuda.get_device_name(0), "resolution": RES,
+                           "iters": args.iters, "result": sections[name](dev, args)})
+        print(line, flush=True)
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
