@@ -24,6 +24,8 @@ FSN_SSIM_UNIFORM = 1  # ... and its default 7 x 7 box
 FSN_RAY_ORDER_IDENTITY = 0  # fsn_ray_batch orders: index = start + i ...
 FSN_RAY_ORDER_PERMUTED = 1  # ... the epoch permutation of (seed, epoch) ...
 FSN_RAY_ORDER_EXPLICIT = 2  # ... an explicit device index list
+FSN_SCAN_SUM = 0  # fsn_packed_scan_fwd / _bwd ops
+FSN_SCAN_PROD = 1
 
 
 class MlpDesc(C.Structure):
@@ -132,6 +134,15 @@ SIGNATURES = {
                                            _vp, _vp, _vp]),
     "fsn_distortion_fwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "fsn_distortion_bwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    # span arguments of the packed primitives: ray_indices, packed_info, N, R, dense_S
+    "fsn_pack_info": (_i, [_vp, _i64, _i64, _vp, _vp]),
+    "fsn_packed_scan_fwd": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _i, _vp, _vp]),
+    "fsn_packed_scan_bwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _vp, _vp]),
+    "fsn_packed_weights_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "fsn_packed_weights_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fsn_packed_visibility_alpha": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _f, _f, _vp, _vp]),
+    "fsn_accumulate_fwd": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _i64, _i, _vp, _vp]),
+    "fsn_accumulate_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i64, _i64, _i, _vp, _vp, _vp]),
     "fsn_ssim_workspace_doubles": (_i64, [_i64, _i, _i, _i]),
     "fsn_ssim": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp, _vp]),
     "fsn_psnr_workspace_doubles": (_i64, [_i64, _i, _i, _i]),

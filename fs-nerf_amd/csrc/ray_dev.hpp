@@ -31,6 +31,36 @@ __device__ __forceinline__ float wave_excl_scan(float v, float& total) {
   return inc - v;
 }
 
+// exclusive prefix product over the 64 lanes (lane 0 gets 1); no division, so a zero factor stays exact
+__device__ __forceinline__ float wave_excl_scan_prod(float v) {
+  const int lane = lane_id();
+  float inc = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    float o = __shfl_up(inc, d, 64);
+    if (lane >= d) inc = o * inc;
+  }
+  const float before = __shfl_up(inc, 1, 64);
+  return lane > 0 ? before : 1.0f;
+}
+
+// Lane l holds the affine map M_l(s) = a s + b.  Returns M_{l+1}(M_{l+2}(... M_63(0))) (lane 63: 0): the exclusive scan
+// of the maps under composition, taken from the wave's END (Hillis-Steele on __shfl_down).  With a = 1 it is the
+// exclusive suffix sum of b in a fixed order, without a "total - prefix" subtraction.
+__device__ __forceinline__ float wave_excl_scan_affine_rev(float a, float b) {
+  const int lane = lane_id();
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const float oa = __shfl_down(a, d, 64), ob = __shfl_down(b, d, 64);
+    if (lane + d < 64) {
+      b = a * ob + b;
+      a = a * oa;
+    }
+  }
+  const float after = __shfl_down(b, 1, 64);
+  return lane < 63 ? after : 0.0f;
+}
+
 // first index of the sorted a[0..n) that is >= key
 __device__ __forceinline__ int64_t ray_lower_bound(const int64_t* __restrict__ a, int64_t n, int64_t key) {
   int64_t lo = 0, hi = n;

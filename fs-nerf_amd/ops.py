@@ -941,6 +941,161 @@ def distortion(weights: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indices: T
     return _DistortionFn.apply(w, t0, t1, ri, int(n_rays))
 
 
+# ------------------------------------------------------------------ packed volume-rendering primitives (csrc/packed_scan.hip)
+def _gpu_f32(t: Tensor, name: str) -> Tensor:
+    """The packed primitives take GPU float32 as it is: nothing is cast (a cast would hide from autograd)."""
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: expected a GPU tensor (the HIP path has no CPU fallback)")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name}: expected float32, got {t.dtype}")
+    return t.contiguous()
+
+
+class RaySpans:
+    """Where each ray's samples are among N flat samples - the "span" arguments of include/fsnerf_hip.h: exactly one of
+    sorted `ray_indices` [N], `packed_info` [n_rays, 2] = (start, count), dense rows of `dense_S` samples."""
+
+    def __init__(self, N: int, n_rays: int, ray_indices: Optional[Tensor] = None, packed_info: Optional[Tensor] = None,
+                 dense_S: int = 0):
+        if (ray_indices is not None) + (packed_info is not None) + (dense_S > 0) != 1 and N > 0 and n_rays > 0:
+            raise ValueError("RaySpans: exactly one of ray_indices, packed_info and dense_S")
+        self.N, self.R, self.S = int(N), int(n_rays), int(dense_S)
+        self.ri = None if ray_indices is None else _i64(ray_indices, "ray_indices").reshape(-1)
+        self.pi = None if packed_info is None else _i64(packed_info, "packed_info")
+        if self.ri is not None and self.ri.numel() != self.N:
+            raise ValueError(f"ray_indices: expected {self.N} values, got {self.ri.numel()}")
+        if self.pi is not None and tuple(self.pi.shape) != (self.R, 2):
+            raise ValueError(f"packed_info: expected shape ({self.R}, 2), got {tuple(self.pi.shape)}")
+        if self.S > 0 and self.N != self.R * self.S:
+            raise ValueError(f"dense rows: {self.N} values are not {self.R} rows of {self.S}")
+
+    def args(self):
+        return _p(self.ri), _p(self.pi), self.N, self.R, self.S
+
+
+def pack_info(ray_indices: Tensor, n_rays: int) -> Tensor:
+    """(start, count) int64 [n_rays, 2] of every ray in the sorted `ray_indices` (fsn_pack_info)."""
+    ri = _i64(ray_indices, "ray_indices").reshape(-1)
+    info = torch.empty(int(n_rays), 2, dtype=torch.int64, device=ri.device)
+    with torch.cuda.device(ri.device):
+        L.check(L.lib().fsn_pack_info(_p(ri), ri.numel(), int(n_rays), _p(info), _stream()), "fsn_pack_info")
+    return info
+
+
+def _flat(t: Optional[Tensor], name: str, n: int) -> Optional[Tensor]:
+    if t is None:
+        return None
+    t = _gpu_f32(t, name).reshape(-1)
+    if t.numel() != n:
+        raise ValueError(f"{name}: expected {n} values, got {t.numel()}")
+    return t
+
+
+def _zeroed_by_call(shape, spans: RaySpans, dev, dtype=torch.float32) -> Tensor:
+    """An output the entry point zeroes itself before its launch (gradients, keep flags): zeros here only when it
+    returns without one."""
+    make = torch.empty if spans.N > 0 and spans.R > 0 else torch.zeros
+    return make(shape, dtype=dtype, device=dev)
+
+
+def _out(like: Tensor, spans: RaySpans, dtype=torch.float32) -> Tensor:
+    """An output the kernel fills per ray: zeroed where no launch (or no ray) would write it."""
+    if spans.R == 0 or spans.pi is not None:
+        return torch.zeros(like.shape, dtype=dtype, device=like.device)
+    return torch.empty(like.shape, dtype=dtype, device=like.device)
+
+
+def packed_scan_fwd(x: Tensor, spans: RaySpans, prod: bool, exclusive: bool) -> Tensor:
+    x = _flat(x, "inputs", spans.N)
+    out = _out(x, spans)
+    with torch.cuda.device(x.device):
+        L.check(L.lib().fsn_packed_scan_fwd(_p(x), *spans.args(), L.FSN_SCAN_PROD if prod else L.FSN_SCAN_SUM,
+                                            int(exclusive), _p(out), _stream()), "fsn_packed_scan_fwd")
+    return out
+
+
+def packed_scan_bwd(x: Optional[Tensor], d_out: Tensor, spans: RaySpans, prod: bool, exclusive: bool) -> Tensor:
+    g = _flat(d_out, "d_out", spans.N)
+    x = _flat(x, "inputs", spans.N)
+    d_x = _zeroed_by_call(g.shape, spans, g.device)
+    with torch.cuda.device(g.device):
+        L.check(L.lib().fsn_packed_scan_bwd(_p(x), _p(g), *spans.args(), L.FSN_SCAN_PROD if prod else L.FSN_SCAN_SUM,
+                                            int(exclusive), _p(d_x), _stream()), "fsn_packed_scan_bwd")
+    return d_x
+
+
+def packed_weights_fwd(v: Tensor, t_starts: Optional[Tensor], t_ends: Optional[Tensor], spans: RaySpans, from_alpha: bool,
+                       prefix_trans: Optional[Tensor] = None, want=(True, True, True)):
+    """-> (weights, trans, alphas), each [N] or None where `want` says so (fsn_packed_weights_fwd)."""
+    n = spans.N
+    v = _flat(v, "alphas" if from_alpha else "sigmas", n)
+    t0, t1 = _flat(t_starts, "t_starts", n), _flat(t_ends, "t_ends", n)
+    p = _flat(prefix_trans, "prefix_trans", n)
+    if not from_alpha and (t0 is None or t1 is None):
+        raise ValueError("packed_weights_fwd: the density form needs t_starts and t_ends")
+    outs = [_out(v, spans) if k else None for k in want]
+    with torch.cuda.device(v.device):
+        L.check(L.lib().fsn_packed_weights_fwd(_p(v), _p(t0), _p(t1), *spans.args(), int(from_alpha), _p(p),
+                                               *(_p(o) for o in outs), _stream()), "fsn_packed_weights_fwd")
+    return tuple(outs)
+
+
+def packed_weights_bwd(v: Tensor, t_starts: Optional[Tensor], t_ends: Optional[Tensor], spans: RaySpans, from_alpha: bool,
+                       prefix_trans: Optional[Tensor], d_weights: Optional[Tensor], d_trans: Optional[Tensor],
+                       d_alphas: Optional[Tensor]) -> Tensor:
+    """-> d_sigmas (or d_alphas) [N]; a cotangent that is None reaches the kernel as NULL (fsn_packed_weights_bwd)."""
+    n = spans.N
+    v = _flat(v, "alphas" if from_alpha else "sigmas", n)
+    t0, t1 = _flat(t_starts, "t_starts", n), _flat(t_ends, "t_ends", n)
+    p = _flat(prefix_trans, "prefix_trans", n)
+    dw, dtr, dal = _flat(d_weights, "d_weights", n), _flat(d_trans, "d_trans", n), _flat(d_alphas, "d_alphas", n)
+    d_v = _zeroed_by_call(v.shape, spans, v.device)
+    with torch.cuda.device(v.device):
+        L.check(L.lib().fsn_packed_weights_bwd(_p(v), _p(t0), _p(t1), *spans.args(), int(from_alpha), _p(p), _p(dw),
+                                               _p(dtr), _p(dal), _p(d_v), _stream()), "fsn_packed_weights_bwd")
+    return d_v
+
+
+def packed_visibility_alpha(alphas: Tensor, spans: RaySpans, early_stop_eps: float, alpha_thre: float) -> Tensor:
+    a = _flat(alphas, "alphas", spans.N)
+    keep = _zeroed_by_call((spans.N,), spans, a.device, torch.uint8)
+    with torch.cuda.device(a.device):
+        L.check(L.lib().fsn_packed_visibility_alpha(_p(a), *spans.args(), float(early_stop_eps), float(alpha_thre),
+                                                    _p(keep), _stream()), "fsn_packed_visibility_alpha")
+    return keep.bool()
+
+
+def accumulate_fwd(weights: Tensor, values: Optional[Tensor], spans: RaySpans) -> Tensor:
+    """-> [n_rays, C] (C = 1 without values) (fsn_accumulate_fwd)"""
+    w = _flat(weights, "weights", spans.N)
+    C = 1
+    if values is not None:
+        C = int(values.shape[-1])
+        if C < 1:
+            raise ValueError("accumulate: values need at least one channel")
+        values = _flat(values, "values", spans.N * C)
+    out = torch.empty(spans.R, C, device=w.device, dtype=torch.float32)  # (every row is written; N == 0: zeroed by the call)
+    with torch.cuda.device(w.device):
+        L.check(L.lib().fsn_accumulate_fwd(_p(w), _p(values), C, *spans.args(), _p(out), _stream()), "fsn_accumulate_fwd")
+    return out
+
+
+def accumulate_bwd(d_out: Tensor, weights: Tensor, values: Optional[Tensor], spans: RaySpans, want_weights: bool,
+                   want_values: bool):
+    """-> (d_weights [N] or None, d_values [N, C] or None) (fsn_accumulate_bwd)"""
+    w = _flat(weights, "weights", spans.N)
+    C = 1 if values is None else int(values.shape[-1])
+    g = _flat(d_out, "d_out", spans.R * C)
+    v = None if values is None else _flat(values, "values", spans.N * C)
+    d_w = _zeroed_by_call(w.shape, spans, w.device) if want_weights else None
+    d_v = _zeroed_by_call((spans.N, C), spans, w.device) if want_values and v is not None else None
+    if d_w is not None or d_v is not None:
+        with torch.cuda.device(w.device):
+            L.check(L.lib().fsn_accumulate_bwd(_p(g), _p(w), _p(v), C, *spans.args(), _p(d_w), _p(d_v), _stream()),
+                    "fsn_accumulate_bwd")
+    return d_w, d_v
+
+
 # ------------------------------------------------------------------ occupancy-grid sampler (SURVEY 8f, row f2)
 def occgrid_march(rays_o: Tensor, rays_d: Tensor, aabb: Sequence[float], res: int, levels: int, bits: Tensor,
                   near_plane: float, far_plane: float, step: float, u: Optional[Tensor], max_steps: int,

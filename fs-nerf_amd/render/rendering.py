@@ -4,7 +4,7 @@
       -> ((rgb, opacity, depth, extras), ray_indices, t_vals)           (src/render/rendering.py:25-107)
   render_frame(hwf, near, far, pose, chunksize, estimator, model, ...)  (src/render/rendering.py:110-177)
   rendering(t_starts, t_ends, ray_indices, n_rays, rgb_sigma_fn, render_bkgd)
-      the nerfacc.volrend.rendering slot (call site rendering.py:89-96)
+      the nerfacc.volrend.rendering slot (call site rendering.py:89-96); rgb_alpha_fn: its alpha route
   StratifiedEstimator                     the estimator slot (rendering.py:66-74, run-nerf.py:96-98)
 
 `StratifiedEstimator` is the fixed-count sampler `north_star` asks for (64 coarse + 128
@@ -23,6 +23,7 @@ from torch import Tensor, nn
 from .. import ops
 from ..core.models import NeRF, frame_flagged, guarded_launch
 from ..utils import utilities as U
+from . import volrend
 from .occgrid import OccGridEstimator
 
 FUSED_OCC_MAX_STEPS = 2048  # csrc/render_occ.hip: samples of one ray group in LDS
@@ -110,14 +111,40 @@ class _CompositeFn(torch.autograd.Function):
         return ds.reshape(sig.shape), dr.reshape(rgb.shape), None, None, None, None, None, None
 
 
+def _rendering_from_alpha(t_starts, t_ends, ray_indices, n_rays, rgb_alpha_fn, render_bkgd):
+    """`rendering`'s alpha route, composed as nerfacc composes it: weights from the alphas, then one accumulation each
+    for colours, opacity and depth; every step a differentiable HIP primitive of render/volrend.py."""
+    rgbs, alphas = rgb_alpha_fn(t_starts, t_ends, ray_indices)
+    assert rgbs.shape[-1] == 3, "rgbs must have 3 channels, got {}".format(rgbs.shape)
+    assert alphas.shape == t_starts.shape, "alphas must have shape of (N,)! Got {}".format(alphas.shape)
+    weights, trans = volrend.render_weight_from_alpha(alphas, ray_indices=ray_indices, n_rays=n_rays)
+    colors = volrend.accumulate_along_rays(weights, rgbs, ray_indices, n_rays)
+    opacity = volrend.accumulate_along_rays(weights, None, ray_indices, n_rays)
+    mids = ((t_starts + t_ends) / 2.0).detach()[:, None]
+    depth = volrend.accumulate_along_rays(weights, mids, ray_indices, n_rays)
+    depth = depth / opacity.clamp_min(torch.finfo(torch.float32).eps)
+    if render_bkgd is not None:
+        colors = colors + render_bkgd.to(colors) * (1.0 - opacity)
+    return colors, opacity, depth, {"weights": weights, "trans": trans, "alphas": alphas, "rgbs": rgbs}
+
+
 def rendering(t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor, n_rays: int,
-              rgb_sigma_fn: Callable, render_bkgd: Optional[Tensor] = None, full_grad: bool = False):
+              rgb_sigma_fn: Optional[Callable] = None, render_bkgd: Optional[Tensor] = None, full_grad: bool = False,
+              rgb_alpha_fn: Optional[Callable] = None):
     """nerfacc.volrend.rendering's contract: -> (colors [n_rays,3], opacities [n_rays,1],
     depths [n_rays,1], extras).  AssertionError on the same shape violations.  Differentiable with
     respect to the rgbs / sigmas returned by `rgb_sigma_fn`: through colors and opacities by default (the lean
     backward of the timed training step; depth and the extras are detached), through EVERY output - depths and
     extras["weights" | "alphas" | "trans"] as well, as nerfacc's are - with `full_grad=True` (depth supervision,
-    distortion / entropy losses on the weights, opacity priors).  No gradient goes to t_starts / t_ends."""
+    distortion / entropy losses on the weights, opacity priors).  No gradient goes to t_starts / t_ends.
+    Exactly one of `rgb_sigma_fn` and `rgb_alpha_fn` is given (else ValueError).  `rgb_alpha_fn` -> (rgbs [N,3],
+    alphas [N]) takes the alpha route (an opacity-valued field): render_weight_from_alpha, then accumulate_along_rays
+    for colours, opacity and depth, depth / clamp(opacity, eps), the background; extras hold "weights", "trans",
+    "alphas" and "rgbs", and every output is differentiable (`full_grad` has nothing to add there)."""
+    if (rgb_sigma_fn is None) == (rgb_alpha_fn is None):
+        raise ValueError("rendering: exactly one of rgb_sigma_fn and rgb_alpha_fn must be given")
+    if rgb_alpha_fn is not None:
+        return _rendering_from_alpha(t_starts, t_ends, ray_indices, n_rays, rgb_alpha_fn, render_bkgd)
     rgbs, sigmas = rgb_sigma_fn(t_starts, t_ends, ray_indices)
     assert rgbs.shape[-1] == 3, "rgbs must have 3 channels, got {}".format(rgbs.shape)
     assert sigmas.shape == t_starts.shape, "sigmas must have shape of (N,)! Got {}".format(sigmas.shape)

@@ -511,6 +511,63 @@ int fsn_distortion_fwd(const float* weights, const float* t_starts, const float*
 int fsn_distortion_bwd(const float* weights, const float* t_starts, const float* t_ends, const int64_t* ray_indices,
                        int64_t N, int64_t n_rays, const float* d_out, float* d_weights, fsn_stream_t stream);
 
+/* Packed volume-rendering primitives (csrc/packed_scan.hip; render/volrend.py is their Python surface, named after
+ * nerfacc's volrend / scan / pack modules - this package's own definitions of nerfacc's documented semantics).
+ * Every entry point below finds the samples [beg, beg + S) of ray r in ONE of three ways ("span" arguments):
+ *   ray_indices  int64 [N], sorted (non-decreasing): a binary search per ray;
+ *   packed_info  int64 [R,2] = (start, count) per ray, as fsn_pack_info writes it: no search (entries are clamped into
+ *                [0, N]); samples no ray owns get 0 in every gradient / keep output;
+ *   dense_S > 0  dense rows: ray r owns [r dense_S, (r+1) dense_S), N == R * dense_S.
+ * Exactly one of the three is given (the other pointers NULL, dense_S 0); anything else is FSN_E_INVALID, as are
+ * negative sizes and null data pointers; N == 0 or R == 0 returns FSN_OK without a launch.  One wave per ray, lane l
+ * owns the contiguous samples [l per, (l+1) per), per = ceil(S/64); no LDS, no atomics, every sum in a fixed order;
+ * float32.
+ * fsn_pack_info: packed_info[r] = (first index i with ray_indices[i] >= r, number of samples of ray r) - a ray
+ *   without samples has count 0 and the start where its samples would be.  N == 0: all zeros.
+ * fsn_packed_scan_fwd: out[k] = sum (op FSN_SCAN_SUM) or product (FSN_SCAN_PROD) of x[j] over the ray's samples j < k
+ *   (exclusive != 0) or j <= k.
+ * fsn_packed_scan_bwd: d_x from d_out.  Sum: the reverse scan of d_out (x may be NULL).  Product: division-free, so
+ *   that x[k] == 0 has a finite, correct gradient - with P_k = prod_{j<k} x_j:  d_x[k] = P_k S_k,
+ *   S_k = d_out[k+1] + x[k+1] S_{k+1} (exclusive)  or  S_k = d_out[k] + x[k+1] S_{k+1} (inclusive), S = 0 past the end.
+ * fsn_packed_weights_fwd: from_alpha == 0: v = sigmas, alpha = 1 - exp(-sigma (t_ends - t_starts)), T = exp(-exclusive
+ *   sum of sigma dt) - the operation sequence of fsn_composite_packed_fwd, whose weights / trans / alphas these are bit
+ *   for bit; from_alpha != 0: v = alphas (t_starts / t_ends unused, may be NULL), T = exclusive product of 1 - alpha.
+ *   trans = T * prefix_trans[i] when prefix_trans [N] is given, weights = trans * alpha.  Any output may be NULL.
+ * fsn_packed_weights_bwd: d_v (d_sigmas or d_alphas) [N] from the optional cotangents d_weights (u), d_trans (tau),
+ *   d_alphas (a), with p = prefix_trans or 1:
+ *     density: d_sigma_i = dt_i ( (u_i T_i p_i + a_i) e_i - sum_{j>i} (u_j alpha_j + tau_j) p_j T_j ),  e = exp(-sigma dt)
+ *     alpha:   d_alpha_k = u_k T_k p_k + a_k - T_k S_k,  S_k = g_{k+1} + (1 - alpha_{k+1}) S_{k+1},
+ *              g_i = (u_i alpha_i + tau_i) p_i   (division-free: alpha == 1 is fine)
+ *   No gradient goes to t_starts / t_ends / prefix_trans.
+ * fsn_packed_visibility_alpha: fsn_packed_visibility's rule on alphas: keep[i] = (T_i >= early_stop_eps &&
+ *   alpha_i >= alpha_thre), T = exclusive product of 1 - alpha.
+ * fsn_accumulate_fwd: out[r,c] = sum_i weights[i] values[i,c] over the ray's samples, values [N,C], out [R,C];
+ *   values == NULL: out[r,0] = sum_i weights[i] (C must be 1).  A ray without samples gives 0 (N == 0: out zeroed).
+ * fsn_accumulate_bwd: d_weights[i] = sum_c d_out[r,c] values[i,c] (values NULL: d_out[r,0]),
+ *   d_values[i,c] = weights[i] d_out[r,c]; either output may be NULL (not both). */
+#define FSN_SCAN_SUM 0
+#define FSN_SCAN_PROD 1
+int fsn_pack_info(const int64_t* ray_indices, int64_t N, int64_t R, int64_t* packed_info, fsn_stream_t stream);
+int fsn_packed_scan_fwd(const float* x, const int64_t* ray_indices, const int64_t* packed_info, int64_t N, int64_t R,
+                        int dense_S, int op, int exclusive, float* out, fsn_stream_t stream);
+int fsn_packed_scan_bwd(const float* x, const float* d_out, const int64_t* ray_indices, const int64_t* packed_info,
+                        int64_t N, int64_t R, int dense_S, int op, int exclusive, float* d_x, fsn_stream_t stream);
+int fsn_packed_weights_fwd(const float* v, const float* t_starts, const float* t_ends, const int64_t* ray_indices,
+                           const int64_t* packed_info, int64_t N, int64_t R, int dense_S, int from_alpha,
+                           const float* prefix_trans, float* weights, float* trans, float* alphas, fsn_stream_t stream);
+int fsn_packed_weights_bwd(const float* v, const float* t_starts, const float* t_ends, const int64_t* ray_indices,
+                           const int64_t* packed_info, int64_t N, int64_t R, int dense_S, int from_alpha,
+                           const float* prefix_trans, const float* d_weights, const float* d_trans, const float* d_alphas,
+                           float* d_v, fsn_stream_t stream);
+int fsn_packed_visibility_alpha(const float* alphas, const int64_t* ray_indices, const int64_t* packed_info, int64_t N,
+                                int64_t R, int dense_S, float early_stop_eps, float alpha_thre, uint8_t* keep,
+                                fsn_stream_t stream);
+int fsn_accumulate_fwd(const float* weights, const float* values, int C, const int64_t* ray_indices,
+                       const int64_t* packed_info, int64_t N, int64_t R, int dense_S, float* out, fsn_stream_t stream);
+int fsn_accumulate_bwd(const float* d_out, const float* weights, const float* values, int C, const int64_t* ray_indices,
+                       const int64_t* packed_info, int64_t N, int64_t R, int dense_S, float* d_weights, float* d_values,
+                       fsn_stream_t stream);
+
 /* f1: optimizer side of the training step on ONE flat float32 parameter arena (run-nerf.py:217, 266-285).
  * fsn_adam_step: torch.optim.Adam's update (no amsgrad), operation for operation in float32, one launch over the
  *   arena: params / grads / exp_avg / exp_avg_sq [n]; `step` = 1, 2, ... (bias corrections are formed in double on
