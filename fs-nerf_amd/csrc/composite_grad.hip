@@ -2,9 +2,9 @@
 // carry a cotangent: colors, opacity, depth, weights, alphas, trans) and the distortion loss on the compositor's
 // weights, the first consumer of dL/dweights.  ONE kernel serves both entry points: fsn_composite_packed_bwd (the
 // timed training step: colors and opacity only) is fsn_composite_packed_bwd_full with the other cotangents NULL.
-// One wavefront per ray, the ray's sample range by ray_span over ray_indices, lane l owns a contiguous run of samples,
-// prefix by wave_excl_scan, suffix = total - prefix.  No LDS, no atomics, every sum in a fixed order.  DESIGN.md,
-// "Full compositor backward".
+// One wavefront per ray on ray_dev.hpp's skeleton (ray_work / ray_launch); the backward's equations are its
+// density_bwd_ray, which this kernel gives q_i and the d_rgb store.  No LDS, no atomics, every sum in a fixed order.
+// DESIGN.md, "Full compositor backward".
 #include "common.hpp"
 #include "ray_dev.hpp"
 
@@ -16,28 +16,23 @@ namespace fsn {
 //   k_i = (m_i - D)/O  for O >= eps (torch.clamp passes the gradient at equality),  m_i/eps otherwise
 //   q_i = g.c_i - g.bkgd + g_O + g_D k_i + u_i
 //   dL/dalpha_i = A_i = q_i T_i + a_i,   dL/dT_i = B_i = q_i alpha_i + tau_i
-//   dL/dsigma_i = dt_i ( A_i e_i - sum_{j>i} B_j T_j ),   dL/dc_i = w_i g
+//   dL/dsigma_i = dt_i ( A_i e_i - sum_{j>i} B_j T_j ),   dL/dc_i = w_i g          (A, B, the suffix: density_bwd_ray)
 // Every optional pointer is a kernel argument, so its NULL branch is wave-uniform and nothing is loaded through it.
 // (d_colors and d_opacity included: an absent one is zero).  With d_depth = d_w = d_a = d_tr = NULL what is left is
 //   q_i = g.c_i - g.bkgd + g_O,   dL/dsigma_i = dt_i ( q_i T_i e_i - sum_{j>i} q_j w_j ).
 __global__ void k_composite_packed_bwd_full(const float* __restrict__ sig, const float* __restrict__ rgb,
-                                            const float* __restrict__ t0, const float* __restrict__ t1,
-                                            const int64_t* __restrict__ ri, int64_t N, int64_t R, float b0, float b1,
-                                            float b2, const float* __restrict__ d_colors,
-                                            const float* __restrict__ d_opacity, const float* __restrict__ opacity,
-                                            const float* __restrict__ depth, const float* __restrict__ d_depth,
-                                            const float* __restrict__ d_w, const float* __restrict__ d_a,
-                                            const float* __restrict__ d_tr, float* __restrict__ d_sig,
-                                            float* __restrict__ d_rgb) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + wave;
-  if (r >= R) return;
-  const auto [beg, S] = ray_span(ri, N, r);
-  if (S <= 0) return;
-  const float* s_ = sig + beg; const float* c_ = rgb + 3 * beg; const float* a_ = t0 + beg; const float* e_ = t1 + beg;
+                                            const float* __restrict__ t0, const float* __restrict__ t1, SpanArgs sp,
+                                            int64_t R, float b0, float b1, float b2,
+                                            const float* __restrict__ d_colors, const float* __restrict__ d_opacity,
+                                            const float* __restrict__ opacity, const float* __restrict__ depth,
+                                            const float* __restrict__ d_depth, const float* __restrict__ d_w,
+                                            const float* __restrict__ d_a, const float* __restrict__ d_tr,
+                                            float* __restrict__ d_sig, float* __restrict__ d_rgb) {
+  RayWork w;
+  if (!ray_work(sp, R, w)) return;
+  const int64_t r = w.r, beg = w.beg;
+  const float* c_ = rgb + 3 * beg; const float* a_ = t0 + beg; const float* e_ = t1 + beg;
   const float* u_ = d_w ? d_w + beg : nullptr;
-  const float* da_ = d_a ? d_a + beg : nullptr;
-  const float* dt_ = d_tr ? d_tr + beg : nullptr;
   const float g0 = d_colors ? d_colors[3 * r] : 0.f, g1 = d_colors ? d_colors[3 * r + 1] : 0.f,
               g2 = d_colors ? d_colors[3 * r + 2] : 0.f;
   const float gop = d_opacity ? d_opacity[r] : 0.f;
@@ -55,47 +50,13 @@ __global__ void k_composite_packed_bwd_full(const float* __restrict__ sig, const
     if (u_) q += u_[i];
     return q;
   };
-  const int per = (S + 63) >> 6;
-  const int i0 = lane * per, i1 = min(i0 + per, S);
-  // forward quantities: exclusive prefix of sigma*dt
-  float lsum = 0.f;
-  for (int i = i0; i < i1; ++i) lsum += s_[i] * (e_[i] - a_[i]);
-  float tot;
-  float run = wave_excl_scan(lsum, tot);
-  // pass 1: this lane's sum of B_j T_j = q_j w_j + tau_j T_j; pass 2 needs the suffix sums
-  float lq = 0.f;
-  {
-    float rr = run;
-    for (int i = i0; i < i1; ++i) {
-      const float sdt = s_[i] * (e_[i] - a_[i]);
-      const float T = expf(-rr);
-      const float w = T * (1.0f - expf(-sdt));
-      float bt = q_of(i) * w;
-      if (dt_) bt += dt_[i] * T;
-      lq += bt;
-      rr += sdt;
-    }
-  }
-  float qtot;
-  const float qbefore = wave_excl_scan(lq, qtot);  // sum of B_j T_j over lanes before this one
-  float suffix = qtot - qbefore;                    // sum over this lane's samples and all later ones
-  for (int i = i0; i < i1; ++i) {
-    const float dt = e_[i] - a_[i];
-    const float sdt = s_[i] * dt;
-    const float T = expf(-run), ea = expf(-sdt);
-    const float w = T * (1.0f - ea);
-    const float q = q_of(i);
-    float bt = q * w;
-    if (dt_) bt += dt_[i] * T;
-    suffix -= bt;  // now: sum over j > i
-    float A = q * T;
-    if (da_) A += da_[i];
-    d_sig[beg + i] = dt * (A * ea - suffix);
-    d_rgb[3 * (beg + i) + 0] = w * g0;
-    d_rgb[3 * (beg + i) + 1] = w * g1;
-    d_rgb[3 * (beg + i) + 2] = w * g2;
-    run += sdt;
-  }
+  float* dc_ = d_rgb + 3 * beg;
+  density_bwd_ray(sig + beg, a_, e_, w.i0, w.i1, true, q_of, d_tr ? d_tr + beg : nullptr, d_a ? d_a + beg : nullptr,
+                  nullptr, d_sig + beg, [&](int i, float wi) {
+                    dc_[3 * i + 0] = wi * g0;
+                    dc_[3 * i + 1] = wi * g1;
+                    dc_[3 * i + 2] = wi * g2;
+                  });
 }
 
 // ------------------------------------------------------------------ distortion loss (mip-NeRF 360, interval form)
@@ -103,18 +64,15 @@ __global__ void k_composite_packed_bwd_full(const float* __restrict__ sig, const
 // one wavefront per ray, two scans (of w and of w m), the lanes' partial sums added by the wave's butterfly.  A ray
 // without samples gives 0.
 __global__ void k_distortion_fwd(const float* __restrict__ w, const float* __restrict__ t0, const float* __restrict__ t1,
-                                 const int64_t* __restrict__ ri, int64_t N, int64_t R, float* __restrict__ out) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + wave;
-  if (r >= R) return;
-  const auto [beg, S] = ray_span(ri, N, r);
-  if (S <= 0) {
-    if (lane == 0) out[r] = 0.f;
+                                 SpanArgs sp, int64_t R, float* __restrict__ out) {
+  RayWork rw;
+  if (!ray_work(sp, R, rw)) {
+    if (rw.r < R && rw.lane == 0) out[rw.r] = 0.f;
     return;
   }
+  const int64_t r = rw.r, beg = rw.beg;
+  const int lane = rw.lane, i0 = rw.i0, i1 = rw.i1;
   const float* w_ = w + beg; const float* a_ = t0 + beg; const float* e_ = t1 + beg;
-  const int per = (S + 63) >> 6;
-  const int i0 = lane * per, i1 = min(i0 + per, S);
   float lw = 0.f, lv = 0.f;
   for (int i = i0; i < i1; ++i) {
     lw += w_[i];
@@ -136,17 +94,13 @@ __global__ void k_distortion_fwd(const float* __restrict__ w, const float* __res
 // dL_r/dw_k = 2 ( m_k W_k - V_k + V'_k - m_k W'_k ) + 2 w_k dt_k / 3,  W'_k = sum_{j>k} w_j,  V'_k = sum_{j>k} w_j m_j
 // (suffix = total - prefix - own term), times the ray's cotangent d_out[r].
 __global__ void k_distortion_bwd(const float* __restrict__ w, const float* __restrict__ t0, const float* __restrict__ t1,
-                                 const int64_t* __restrict__ ri, int64_t N, int64_t R, const float* __restrict__ d_out,
-                                 float* __restrict__ d_w) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + wave;
-  if (r >= R) return;
-  const auto [beg, S] = ray_span(ri, N, r);
-  if (S <= 0) return;
+                                 SpanArgs sp, int64_t R, const float* __restrict__ d_out, float* __restrict__ d_w) {
+  RayWork rw;
+  if (!ray_work(sp, R, rw)) return;
+  const int64_t beg = rw.beg;
+  const int i0 = rw.i0, i1 = rw.i1;
   const float* w_ = w + beg; const float* a_ = t0 + beg; const float* e_ = t1 + beg;
-  const float g = d_out[r];
-  const int per = (S + 63) >> 6;
-  const int i0 = lane * per, i1 = min(i0 + per, S);
+  const float g = d_out[rw.r];
   float lw = 0.f, lv = 0.f;
   for (int i = i0; i < i1; ++i) {
     lw += w_[i];
@@ -175,15 +129,16 @@ static int composite_bwd_launch(const char* who, const float* sigmas, const floa
                                 const float* d_trans, float* d_sigmas, float* d_rgbs, fsn_stream_t stream) {
   FSN_REQUIRE(N >= 0 && R >= 0, FSN_E_INVALID, "%s: bad sizes", who);
   FSN_REQUIRE(!d_depth || (opacity && depth), FSN_E_INVALID, "%s: d_depth needs the forward's opacity and depth", who);
-  if (N == 0 || R == 0) return FSN_OK;
-  FSN_REQUIRE(sigmas && rgbs && t_starts && t_ends && ray_indices && d_sigmas && d_rgbs, FSN_E_INVALID,
-              "%s: null pointer", who);
+  RayLaunch L;
+  if (int rc = ray_launch(who, ray_indices, nullptr, N, R, 0, false, &L)) return rc;
+  if (!L.launch) return FSN_OK;
+  FSN_REQUIRE(sigmas && rgbs && t_starts && t_ends && d_sigmas && d_rgbs, FSN_E_INVALID, "%s: null pointer", who);
   const float b0 = bkgd_host ? bkgd_host[0] : 0.f, b1 = bkgd_host ? bkgd_host[1] : 0.f, b2 = bkgd_host ? bkgd_host[2] : 0.f;
   FSN_HIP(hipMemsetAsync(d_sigmas, 0, (size_t)N * sizeof(float), as_stream(stream)));
   FSN_HIP(hipMemsetAsync(d_rgbs, 0, (size_t)N * 3 * sizeof(float), as_stream(stream)));
-  k_composite_packed_bwd_full<<<(unsigned)((R + 3) / 4), 256, 0, as_stream(stream)>>>(
-      sigmas, rgbs, t_starts, t_ends, ray_indices, N, R, b0, b1, b2, d_colors, d_opacity, opacity, depth, d_depth,
-      d_weights, d_alphas, d_trans, d_sigmas, d_rgbs);
+  k_composite_packed_bwd_full<<<L.grid, 256, 0, as_stream(stream)>>>(sigmas, rgbs, t_starts, t_ends, L.sp, R, b0, b1, b2,
+                                                                    d_colors, d_opacity, opacity, depth, d_depth, d_weights,
+                                                                    d_alphas, d_trans, d_sigmas, d_rgbs);
   FSN_LAUNCH_CHECK("k_composite_packed_bwd_full");
   return FSN_OK;
 }
@@ -212,15 +167,15 @@ extern "C" int fsn_composite_packed_bwd(const float* sigmas, const float* rgbs, 
 
 extern "C" int fsn_distortion_fwd(const float* weights, const float* t_starts, const float* t_ends,
                                   const int64_t* ray_indices, int64_t N, int64_t n_rays, float* out, fsn_stream_t stream) {
-  FSN_REQUIRE(N >= 0 && n_rays >= 0, FSN_E_INVALID, "fsn_distortion_fwd: bad sizes");
-  if (n_rays == 0) return FSN_OK;
-  if (N == 0) {  // every ray is empty
-    if (out) FSN_HIP(hipMemsetAsync(out, 0, (size_t)n_rays * sizeof(float), as_stream(stream)));
+  RayLaunch L;
+  if (int rc = ray_launch("fsn_distortion_fwd", ray_indices, nullptr, N, n_rays, 0, false, &L)) return rc;
+  if (!L.launch) {
+    if (N == 0 && n_rays > 0 && out)  // every ray is empty
+      FSN_HIP(hipMemsetAsync(out, 0, (size_t)n_rays * sizeof(float), as_stream(stream)));
     return FSN_OK;
   }
-  FSN_REQUIRE(weights && t_starts && t_ends && ray_indices && out, FSN_E_INVALID, "fsn_distortion_fwd: null pointer");
-  k_distortion_fwd<<<(unsigned)((n_rays + 3) / 4), 256, 0, as_stream(stream)>>>(weights, t_starts, t_ends, ray_indices, N,
-                                                                               n_rays, out);
+  FSN_REQUIRE(weights && t_starts && t_ends && out, FSN_E_INVALID, "fsn_distortion_fwd: null pointer");
+  k_distortion_fwd<<<L.grid, 256, 0, as_stream(stream)>>>(weights, t_starts, t_ends, L.sp, n_rays, out);
   FSN_LAUNCH_CHECK("k_distortion_fwd");
   return FSN_OK;
 }
@@ -228,13 +183,12 @@ extern "C" int fsn_distortion_fwd(const float* weights, const float* t_starts, c
 extern "C" int fsn_distortion_bwd(const float* weights, const float* t_starts, const float* t_ends,
                                   const int64_t* ray_indices, int64_t N, int64_t n_rays, const float* d_out,
                                   float* d_weights, fsn_stream_t stream) {
-  FSN_REQUIRE(N >= 0 && n_rays >= 0, FSN_E_INVALID, "fsn_distortion_bwd: bad sizes");
-  if (N == 0 || n_rays == 0) return FSN_OK;
-  FSN_REQUIRE(weights && t_starts && t_ends && ray_indices && d_out && d_weights, FSN_E_INVALID,
-              "fsn_distortion_bwd: null pointer");
+  RayLaunch L;
+  if (int rc = ray_launch("fsn_distortion_bwd", ray_indices, nullptr, N, n_rays, 0, false, &L)) return rc;
+  if (!L.launch) return FSN_OK;
+  FSN_REQUIRE(weights && t_starts && t_ends && d_out && d_weights, FSN_E_INVALID, "fsn_distortion_bwd: null pointer");
   FSN_HIP(hipMemsetAsync(d_weights, 0, (size_t)N * sizeof(float), as_stream(stream)));
-  k_distortion_bwd<<<(unsigned)((n_rays + 3) / 4), 256, 0, as_stream(stream)>>>(weights, t_starts, t_ends, ray_indices, N,
-                                                                               n_rays, d_out, d_weights);
+  k_distortion_bwd<<<L.grid, 256, 0, as_stream(stream)>>>(weights, t_starts, t_ends, L.sp, n_rays, d_out, d_weights);
   FSN_LAUNCH_CHECK("k_distortion_bwd");
   return FSN_OK;
 }

@@ -318,13 +318,14 @@ int input_grad_launch(const fsn_mlp_desc& d, int prec, const float* const* W, in
 
 // ------------------------------------------------------------------ ray form: per-ray sums
 // One wave per ray; lane l takes samples l, l + 64, ... of the ray, then a butterfly over the lanes: a fixed order.
-__global__ void k_ray_grad(const float* __restrict__ d_x, const float* __restrict__ d_dirs, const int64_t* __restrict__ ri,
-                           const float* __restrict__ t0, const float* __restrict__ t1, int64_t N, int64_t R,
+__global__ void k_ray_grad(const float* __restrict__ d_x, const float* __restrict__ d_dirs, SpanArgs sp,
+                           const float* __restrict__ t0, const float* __restrict__ t1, int64_t R,
                            float* __restrict__ d_o, float* __restrict__ d_d) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + wave;
+  RayWork rw;
+  ray_work(sp, R, rw);  // (a ray without samples goes on: it gets zeros)
+  const int64_t r = rw.r, beg = rw.beg;
+  const int S = rw.S, lane = rw.lane;
   if (r >= R) return;
-  const auto [beg, S] = ray_span(ri, N, r);
   float so[3] = {0.f, 0.f, 0.f}, sd[3] = {0.f, 0.f, 0.f};
   for (int i = lane; i < S; i += 64) {
     const int64_t k = beg + i;
@@ -369,14 +370,15 @@ extern "C" int fsn_ray_grad_reduce(const float* d_x, const float* d_dirs, const 
                                    fsn_stream_t stream) {
   FSN_REQUIRE(N >= 0 && R >= 0, FSN_E_INVALID, "fsn_ray_grad_reduce: bad sizes");
   if (R == 0 || (!d_rays_o && !d_rays_d)) return FSN_OK;
-  if (N == 0) {  // nothing to launch: every ray is an empty one
+  RayLaunch L;
+  if (int rc = ray_launch("fsn_ray_grad_reduce", ray_indices, nullptr, N, R, 0, false, &L)) return rc;
+  if (!L.launch) {  // N == 0, nothing to launch: every ray is an empty one
     if (d_rays_o) FSN_HIP(hipMemsetAsync(d_rays_o, 0, (size_t)R * 3 * sizeof(float), as_stream(stream)));
     if (d_rays_d) FSN_HIP(hipMemsetAsync(d_rays_d, 0, (size_t)R * 3 * sizeof(float), as_stream(stream)));
     return FSN_OK;
   }
-  FSN_REQUIRE(ray_indices && t_starts && t_ends, FSN_E_INVALID, "fsn_ray_grad_reduce: null pointer");
-  k_ray_grad<<<(unsigned)((R + 3) / 4), 256, 0, as_stream(stream)>>>(d_x, d_dirs, ray_indices, t_starts, t_ends, N, R,
-                                                                    d_rays_o, d_rays_d);
+  FSN_REQUIRE(t_starts && t_ends, FSN_E_INVALID, "fsn_ray_grad_reduce: null pointer");
+  k_ray_grad<<<L.grid, 256, 0, as_stream(stream)>>>(d_x, d_dirs, L.sp, t_starts, t_ends, R, d_rays_o, d_rays_d);
   FSN_LAUNCH_CHECK("k_ray_grad");
   return FSN_OK;
 }

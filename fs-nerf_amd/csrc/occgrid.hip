@@ -16,11 +16,10 @@
 //    taken once per block of 64 intervals (occ_dev.hpp, march_ray_cone; include/fsnerf_hip.h has the definition,
 //    tests/occ_cone_ref.py restates it).  The plain entry point is the extended one with no bounds and cone_angle 0.
 //  * visibility: T_i = exp(-sum_{j<i} sigma_j dt_j) per ray (prefix scan), keep iff T_i >= early_stop_eps and
-//    alpha_i >= alpha_thre.
+//    alpha_i >= alpha_thre (fsn_packed_visibility: k_packed_visibility in packed_scan.hip, on ray_dev.hpp's trans_walk).
 //  * update: occs[c] = max(occs[c]*decay, occ_c) for the evaluated cells; bit = occs > threshold.
 #include "common.hpp"
 #include "occ_dev.hpp"
-#include "ray_dev.hpp"
 
 namespace fsn {
 
@@ -84,29 +83,6 @@ __global__ void k_ray_aabb(const float* __restrict__ rays_o, const float* __rest
   t_mins[i] = hit ? t0 : miss_value;
   t_maxs[i] = hit ? t1 : miss_value;
   hits[i] = hit ? 1 : 0;
-}
-
-// keep[i] = T_i >= eps && alpha_i >= alpha_thre, packed samples sorted by ray
-__global__ void k_visibility(const float* __restrict__ sig, const float* __restrict__ t0, const float* __restrict__ t1,
-                             const int64_t* __restrict__ ri, int64_t N, int64_t R, float eps, float alpha_thre,
-                             uint8_t* __restrict__ keep) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + wave;
-  if (r >= R) return;
-  const auto [beg, S] = ray_span(ri, N, r);
-  if (S == 0) return;
-  const int per = (S + 63) >> 6;
-  const int i0 = lane * per, i1 = min(i0 + per, S);
-  float lsum = 0.f;
-  for (int i = i0; i < i1; ++i) lsum += sig[beg + i] * (t1[beg + i] - t0[beg + i]);
-  float tot;
-  float run = wave_excl_scan(lsum, tot);
-  for (int i = i0; i < i1; ++i) {
-    const float sdt = sig[beg + i] * (t1[beg + i] - t0[beg + i]);
-    const float T = expf(-run), alpha = 1.0f - expf(-sdt);
-    keep[beg + i] = (T >= eps && alpha >= alpha_thre) ? 1 : 0;
-    run += sdt;
-  }
 }
 
 __global__ void k_occ_ema(float* __restrict__ occs, const int64_t* __restrict__ cells, const float* __restrict__ vals,
@@ -268,18 +244,6 @@ extern "C" int fsn_ray_aabb_intersect(const float* rays_o, const float* rays_d, 
   k_ray_aabb<<<(unsigned)((n + 255) / 256), 256, 0, as_stream(stream)>>>(rays_o, rays_d, R, aabbs, M, near_plane,
                                                                          far_plane, miss_value, t_mins, t_maxs, hits);
   FSN_LAUNCH_CHECK("k_ray_aabb");
-  return FSN_OK;
-}
-
-extern "C" int fsn_packed_visibility(const float* sigmas, const float* t_starts, const float* t_ends,
-                                     const int64_t* ray_indices, int64_t N, int64_t R, float early_stop_eps,
-                                     float alpha_thre, uint8_t* keep, fsn_stream_t stream) {
-  FSN_REQUIRE(N >= 0 && R >= 0, FSN_E_INVALID, "fsn_packed_visibility: bad sizes");
-  if (N == 0 || R == 0) return FSN_OK;
-  FSN_REQUIRE(sigmas && t_starts && t_ends && ray_indices && keep, FSN_E_INVALID, "fsn_packed_visibility: null pointer");
-  k_visibility<<<(unsigned)((R + 3) / 4), 256, 0, as_stream(stream)>>>(sigmas, t_starts, t_ends, ray_indices, N, R,
-                                                                       early_stop_eps, alpha_thre, keep);
-  FSN_LAUNCH_CHECK("k_visibility");
   return FSN_OK;
 }
 

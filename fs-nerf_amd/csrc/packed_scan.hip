@@ -1,50 +1,15 @@
 // packed_scan.hip — the packed volume-rendering primitives behind render/volrend.py: per-ray scans (sum / product,
 // inclusive / exclusive) with their backwards, weights / transmittance / alphas from densities or from alphas with the
-// backward, the alpha form of the visibility rule, the per-ray accumulation with its backward, and pack_info.
-// One wavefront per ray, four rays per 256-thread block; lane l owns the contiguous samples [l per, (l+1) per),
-// per = ceil(S/64); cross-lane prefixes by wave_excl_scan / wave_excl_scan_prod / wave_excl_scan_affine_rev
-// (ray_dev.hpp).  No LDS, no atomics, every sum in a fixed order, float32, -ffp-contract=off.  The two elementwise
-// parts (k_accumulate_bwd) stride the lanes over the ray's samples instead: nothing is summed across samples there.
+// backward, the visibility rule (on densities and on alphas), the per-ray accumulation with its backward, and pack_info.
+// One wavefront per ray, four rays per 256-thread block: ray_work / ray_launch, the density forms' trans_walk and
+// density_bwd_ray, and the cross-lane scans (wave_excl_scan / _prod / _affine_rev) are ray_dev.hpp's.  No LDS, no
+// atomics, every sum in a fixed order, float32, -ffp-contract=off.  The two elementwise parts (k_accumulate_bwd)
+// stride the lanes over the ray's samples instead: nothing is summed across samples there.
 // DESIGN.md, "Packed volume-rendering primitives".
 #include "common.hpp"
 #include "ray_dev.hpp"
 
 namespace fsn {
-
-// Where a ray's samples are: exactly one of sorted ray_indices [N] (searched by ray_span), packed_info [R,2] = (start,
-// count) (read, and clamped into [0, N] so that a wrong table cannot send a wave out of the arrays), dense rows of
-// dense_S samples.
-struct SpanArgs {
-  const int64_t* ri;
-  const int64_t* pi;
-  int64_t N;
-  int dense_S;
-};
-
-__device__ __forceinline__ RaySpan span_of(const SpanArgs& sp, int64_t r) {
-  if (sp.dense_S > 0) return {r * sp.dense_S, sp.dense_S};
-  if (sp.pi) {
-    const int64_t beg = min(max(sp.pi[2 * r], (int64_t)0), sp.N);
-    const int64_t cnt = min(max(sp.pi[2 * r + 1], (int64_t)0), min(sp.N - beg, (int64_t)0x7fffffff));
-    return {beg, (int)cnt};
-  }
-  return ray_span(sp.ri, sp.N, r);
-}
-
-#define FSN_RAY_PROLOGUE(on_empty)                          \
-  const int lane = threadIdx.x & 63;                        \
-  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); \
-  if (r >= R) return;                                       \
-  const RaySpan span_ = span_of(sp, r);                     \
-  const int64_t beg = span_.beg;                            \
-  const int S = span_.S;                                    \
-  if (S <= 0) {                                             \
-    on_empty;                                               \
-    return;                                                 \
-  }                                                         \
-  const int per = (S + 63) >> 6;                            \
-  const int i0 = min(lane * per, S), i1 = min(i0 + per, S); \
-  (void)lane
 
 __global__ void k_pack_info(const int64_t* __restrict__ ri, int64_t N, int64_t R, int64_t* __restrict__ info) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -57,7 +22,10 @@ __global__ void k_pack_info(const int64_t* __restrict__ ri, int64_t N, int64_t R
 // out[k] = sum / product of x[j], j < k (exclusive) or j <= k (inclusive), within the ray
 __global__ void k_packed_scan_fwd(const float* __restrict__ x, SpanArgs sp, int64_t R, int prod, int exclusive,
                                   float* __restrict__ out) {
-  FSN_RAY_PROLOGUE((void)0);
+  RayWork w;
+  if (!ray_work(sp, R, w)) return;
+  const int64_t beg = w.beg;
+  const int i0 = w.i0, i1 = w.i1;
   const float* x_ = x + beg;
   float* o_ = out + beg;
   if (prod) {
@@ -91,7 +59,11 @@ __global__ void k_packed_scan_fwd(const float* __restrict__ x, SpanArgs sp, int6
 // from the ray's end, and the lane walks its samples backwards; the product form then multiplies by P_k going forwards.
 __global__ void k_packed_scan_bwd(const float* __restrict__ x, const float* __restrict__ g, SpanArgs sp, int64_t R,
                                   int prod, int exclusive, float* __restrict__ d_x) {
-  FSN_RAY_PROLOGUE((void)0);
+  RayWork w;
+  if (!ray_work(sp, R, w)) return;
+  const int64_t beg = w.beg;
+  const int i0 = w.i0, i1 = w.i1;
+  const int S = w.S;
   const float* x_ = prod ? x + beg : nullptr;
   const float* g_ = g + beg;
   float* o_ = d_x + beg;
@@ -123,13 +95,16 @@ __global__ void k_packed_scan_bwd(const float* __restrict__ x, const float* __re
   }
 }
 
-// from_alpha = 0: composite_ray's operation sequence (ray_dev.hpp) - dt = t1 - t0, alpha = 1 - exp(-sigma dt),
+// from_alpha = 0: composite_ray's walk (trans_walk, ray_dev.hpp) - dt = t1 - t0, alpha = 1 - exp(-sigma dt),
 // T = exp(-exclusive sum sigma dt); from_alpha = 1: T = exclusive product of (1 - alpha).  T is multiplied by prefix[i]
 // when given; w = T alpha.  Any output may be NULL.
 __global__ void k_packed_weights_fwd(const float* __restrict__ v, const float* __restrict__ t0, const float* __restrict__ t1,
                                      SpanArgs sp, int64_t R, int from_alpha, const float* __restrict__ prefix,
                                      float* __restrict__ weights, float* __restrict__ trans, float* __restrict__ alphas) {
-  FSN_RAY_PROLOGUE((void)0);
+  RayWork w;
+  if (!ray_work(sp, R, w)) return;
+  const int64_t beg = w.beg;
+  const int i0 = w.i0, i1 = w.i1;
   const float* v_ = v + beg;
   const float* p_ = prefix ? prefix + beg : nullptr;
   float* w_ = weights ? weights + beg : nullptr;
@@ -138,22 +113,14 @@ __global__ void k_packed_weights_fwd(const float* __restrict__ v, const float* _
   if (!from_alpha) {
     const float* a_ = t0 + beg;
     const float* e_ = t1 + beg;
-    float lsum = 0.f;
-    for (int i = i0; i < i1; ++i) lsum += v_[i] * (e_[i] - a_[i]);
-    float total;
-    float run = wave_excl_scan(lsum, total);
-    for (int i = i0; i < i1; ++i) {
-      const float a = a_[i], b = e_[i];
-      const float sdt = v_[i] * (b - a);
-      const float alpha = 1.0f - expf(-sdt);
-      float T = expf(-run);
+    trans_walk(i0, i1, [&](int i) { return v_[i] * (e_[i] - a_[i]); }, [&](int i, float T, float e) {
+      const float alpha = 1.0f - e;
       if (p_) T = T * p_[i];
-      const float w = T * alpha;
-      run += sdt;
-      if (w_) w_[i] = w;
+      const float wt = T * alpha;
+      if (w_) w_[i] = wt;
       if (al_) al_[i] = alpha;
       if (tr_) tr_[i] = T;
-    }
+    });
   } else {
     float lp = 1.0f;
     for (int i = i0; i < i1; ++i) lp *= 1.0f - v_[i];
@@ -162,9 +129,9 @@ __global__ void k_packed_weights_fwd(const float* __restrict__ v, const float* _
       const float alpha = v_[i];
       float T = run;
       if (p_) T = T * p_[i];
-      const float w = T * alpha;
+      const float wt = T * alpha;
       run = run * (1.0f - alpha);
-      if (w_) w_[i] = w;
+      if (w_) w_[i] = wt;
       if (al_) al_[i] = alpha;
       if (tr_) tr_[i] = T;
     }
@@ -173,7 +140,7 @@ __global__ void k_packed_weights_fwd(const float* __restrict__ v, const float* _
 
 // Cotangents u (weights), tau (trans), a (alphas), each nullable (a kernel argument: the NULL branch is wave-uniform);
 // p = prefix_trans (1 when absent), T the ray's own transmittance, so that trans = T p and w = T p alpha.
-// Density form (composite_grad.hip's equations with q_i = u_i):
+// Density form: density_bwd_ray (ray_dev.hpp), the compositor backward's routine, with q_i = u_i:
 //   A_i = u_i T_i p_i + a_i,  B_i T_i = (u_i alpha_i + tau_i) p_i T_i,  d_sigma_i = dt_i (A_i e_i - sum_{j>i} B_j T_j)
 // Alpha form, x = 1 - alpha, P_k = prod_{j<k} x_j, g_i = (u_i alpha_i + tau_i) p_i = dL/dP_i:
 //   d_alpha_k = u_k P_k p_k + a_k - P_k S_k,   S_k = g_{k+1} + x_{k+1} S_{k+1}   (the exclusive product's backward)
@@ -181,7 +148,10 @@ __global__ void k_packed_weights_bwd(const float* __restrict__ v, const float* _
                                      SpanArgs sp, int64_t R, int from_alpha, const float* __restrict__ prefix,
                                      const float* __restrict__ d_w, const float* __restrict__ d_tr,
                                      const float* __restrict__ d_a, float* __restrict__ d_v) {
-  FSN_RAY_PROLOGUE((void)0);
+  RayWork w;
+  if (!ray_work(sp, R, w)) return;
+  const int64_t beg = w.beg;
+  const int i0 = w.i0, i1 = w.i1;
   const float* v_ = v + beg;
   const float* p_ = prefix ? prefix + beg : nullptr;
   const float* u_ = d_w ? d_w + beg : nullptr;
@@ -189,45 +159,8 @@ __global__ void k_packed_weights_bwd(const float* __restrict__ v, const float* _
   const float* da_ = d_a ? d_a + beg : nullptr;
   float* o_ = d_v + beg;
   if (!from_alpha) {
-    const float* a_ = t0 + beg;
-    const float* e_ = t1 + beg;
-    float lsum = 0.f;
-    for (int i = i0; i < i1; ++i) lsum += v_[i] * (e_[i] - a_[i]);
-    float tot;
-    float run = wave_excl_scan(lsum, tot);
-    auto bt_of = [&](int i, float Tp, float alpha) {
-      float bt = 0.f;
-      if (u_) bt += u_[i] * (Tp * alpha);
-      if (tau_) bt += tau_[i] * Tp;
-      return bt;
-    };
-    float lq = 0.f;
-    {
-      float rr = run;
-      for (int i = i0; i < i1; ++i) {
-        const float sdt = v_[i] * (e_[i] - a_[i]);
-        float Tp = expf(-rr);
-        if (p_) Tp = Tp * p_[i];
-        lq += bt_of(i, Tp, 1.0f - expf(-sdt));
-        rr += sdt;
-      }
-    }
-    float qtot;
-    const float qbefore = wave_excl_scan(lq, qtot);
-    float suffix = qtot - qbefore;  // over this lane's samples and all later ones
-    for (int i = i0; i < i1; ++i) {
-      const float dt = e_[i] - a_[i];
-      const float sdt = v_[i] * dt;
-      const float ea = expf(-sdt);
-      float Tp = expf(-run);
-      if (p_) Tp = Tp * p_[i];
-      suffix -= bt_of(i, Tp, 1.0f - ea);  // now: over j > i
-      float A = 0.f;
-      if (u_) A += u_[i] * Tp;
-      if (da_) A += da_[i];
-      o_[i] = dt * (A * ea - suffix);
-      run += sdt;
-    }
+    density_bwd_ray(v_, t0 + beg, t1 + beg, i0, i1, u_ != nullptr, [&](int i) { return u_[i]; }, tau_, da_, p_, o_,
+                    [](int, float) {});
   } else {
     auto g_of = [&](int i) {
       float g = 0.f;
@@ -259,18 +192,31 @@ __global__ void k_packed_weights_bwd(const float* __restrict__ v, const float* _
   }
 }
 
-// k_visibility's rule (occgrid.hip) on alphas: keep = T >= eps && alpha >= alpha_thre, T = exclusive product of 1 - alpha
-__global__ void k_packed_visibility_alpha(const float* __restrict__ alphas, SpanArgs sp, int64_t R, float eps,
-                                          float alpha_thre, uint8_t* __restrict__ keep) {
-  FSN_RAY_PROLOGUE((void)0);
-  const float* v_ = alphas + beg;
-  float lp = 1.0f;
-  for (int i = i0; i < i1; ++i) lp *= 1.0f - v_[i];
-  float run = wave_excl_scan_prod(lp);
-  for (int i = i0; i < i1; ++i) {
-    const float alpha = v_[i];
-    keep[beg + i] = (run >= eps && alpha >= alpha_thre) ? 1 : 0;
-    run = run * (1.0f - alpha);
+// keep[i] = T_i >= eps && alpha_i >= alpha_thre, both entry points.  from_alpha = 0: v = sigmas, T and alpha by the
+// compositor's walk; from_alpha = 1: v = alphas, T = exclusive product of 1 - alpha.
+__global__ void k_packed_visibility(const float* __restrict__ v, const float* __restrict__ t0, const float* __restrict__ t1,
+                                    SpanArgs sp, int64_t R, int from_alpha, float eps, float alpha_thre,
+                                    uint8_t* __restrict__ keep) {
+  RayWork w;
+  if (!ray_work(sp, R, w)) return;
+  const int64_t beg = w.beg;
+  const int i0 = w.i0, i1 = w.i1;
+  const float* v_ = v + beg;
+  uint8_t* k_ = keep + beg;
+  if (!from_alpha) {
+    const float* a_ = t0 + beg;
+    const float* e_ = t1 + beg;
+    trans_walk(i0, i1, [&](int i) { return v_[i] * (e_[i] - a_[i]); },
+               [&](int i, float T, float e) { k_[i] = (T >= eps && 1.0f - e >= alpha_thre) ? 1 : 0; });
+  } else {
+    float lp = 1.0f;
+    for (int i = i0; i < i1; ++i) lp *= 1.0f - v_[i];
+    float run = wave_excl_scan_prod(lp);
+    for (int i = i0; i < i1; ++i) {
+      const float alpha = v_[i];
+      k_[i] = (run >= eps && alpha >= alpha_thre) ? 1 : 0;
+      run = run * (1.0f - alpha);
+    }
   }
 }
 
@@ -278,7 +224,15 @@ __global__ void k_packed_visibility_alpha(const float* __restrict__ alphas, Span
 // the lanes' sums are added by the wave's butterfly.  A ray without samples gives 0.
 __global__ void k_accumulate_fwd(const float* __restrict__ w, const float* __restrict__ vals, int C, SpanArgs sp,
                                  int64_t R, float* __restrict__ out) {
-  FSN_RAY_PROLOGUE(for (int c = lane; c < C; c += 64) out[r * C + c] = 0.f);
+  RayWork rw;
+  const bool work = ray_work(sp, R, rw);
+  const int64_t r = rw.r, beg = rw.beg;
+  const int lane = rw.lane, i0 = rw.i0, i1 = rw.i1;
+  if (r >= R) return;
+  if (!work) {
+    for (int c = lane; c < C; c += 64) out[r * C + c] = 0.f;
+    return;
+  }
   const float* w_ = w + beg;
   const float* v_ = vals ? vals + beg * C : nullptr;
   for (int c0 = 0; c0 < C; c0 += 4) {
@@ -301,9 +255,11 @@ __global__ void k_accumulate_fwd(const float* __restrict__ w, const float* __res
 // d_w[i] = sum_c g[r,c] v_ic (values NULL: g[r]),  d_v[i,c] = w_i g[r,c]: elementwise, the lanes stride over the ray
 __global__ void k_accumulate_bwd(const float* __restrict__ g, const float* __restrict__ w, const float* __restrict__ vals,
                                  int C, SpanArgs sp, int64_t R, float* __restrict__ d_w, float* __restrict__ d_v) {
-  FSN_RAY_PROLOGUE((void)0);
-  (void)i0; (void)i1;
-  const float* g_ = g + r * C;
+  RayWork rw;
+  if (!ray_work(sp, R, rw)) return;
+  const int64_t beg = rw.beg;
+  const int S = rw.S, lane = rw.lane;
+  const float* g_ = g + rw.r * C;
   if (d_w) {
     for (int i = lane; i < S; i += 64) {
       float acc = 0.f;
@@ -326,28 +282,10 @@ __global__ void k_accumulate_bwd(const float* __restrict__ g, const float* __res
 
 using namespace fsn;
 
-// The checks every entry point shares.  -> FSN_OK with *launch = 0 for an empty problem.
-static int span_check(const char* who, const int64_t* ri, const int64_t* pi, int64_t N, int64_t R, int dense_S,
-                      int* launch) {
-  *launch = 0;
-  FSN_REQUIRE(N >= 0 && R >= 0 && dense_S >= 0, FSN_E_INVALID, "%s: bad sizes", who);
-  const int modes = (ri ? 1 : 0) + (pi ? 1 : 0) + (dense_S > 0 ? 1 : 0);
-  FSN_REQUIRE(modes <= 1, FSN_E_INVALID, "%s: more than one of ray_indices, packed_info and dense_S given", who);
-  if (N == 0 || R == 0) return FSN_OK;
-  FSN_REQUIRE(modes == 1, FSN_E_INVALID, "%s: null pointer (one of ray_indices, packed_info and dense_S is needed)", who);
-  FSN_REQUIRE(dense_S == 0 || (R <= N && N / R == dense_S && N % R == 0), FSN_E_INVALID,
-              "%s: bad sizes (dense rows need N == R * dense_S)", who);
-  FSN_REQUIRE((R + 3) / 4 <= 0x7fffffff, FSN_E_INVALID, "%s: bad sizes (too many rays)", who);
-  *launch = 1;
-  return FSN_OK;
-}
-
-#define FSN_SPAN_CHECK(who)                                                     \
-  int launch_;                                                                  \
-  if (int rc_ = span_check(who, ray_indices, packed_info, N, R, dense_S, &launch_)) return rc_; \
-  const SpanArgs sp{ray_indices, packed_info, N, dense_S};                      \
-  const unsigned grid = (unsigned)((R + 3) / 4);                                \
-  (void)sp; (void)grid
+// the shared checks of an entry point over (ray_indices, packed_info, N, R, dense_S): ray_launch (ray_dev.hpp)
+#define FSN_SPAN_CHECK(who) \
+  RayLaunch L;              \
+  if (int rc_ = ray_launch(who, ray_indices, packed_info, N, R, dense_S, false, &L)) return rc_
 
 extern "C" int fsn_pack_info(const int64_t* ray_indices, int64_t N, int64_t R, int64_t* packed_info, fsn_stream_t stream) {
   FSN_REQUIRE(N >= 0 && R >= 0, FSN_E_INVALID, "fsn_pack_info: bad sizes");
@@ -367,9 +305,9 @@ extern "C" int fsn_packed_scan_fwd(const float* x, const int64_t* ray_indices, c
                                    int64_t R, int dense_S, int op, int exclusive, float* out, fsn_stream_t stream) {
   FSN_REQUIRE(op == FSN_SCAN_SUM || op == FSN_SCAN_PROD, FSN_E_INVALID, "fsn_packed_scan_fwd: op %d is neither sum nor prod", op);
   FSN_SPAN_CHECK("fsn_packed_scan_fwd");
-  if (!launch_) return FSN_OK;
+  if (!L.launch) return FSN_OK;
   FSN_REQUIRE(x && out, FSN_E_INVALID, "fsn_packed_scan_fwd: null pointer");
-  k_packed_scan_fwd<<<grid, 256, 0, as_stream(stream)>>>(x, sp, R, op == FSN_SCAN_PROD, exclusive != 0, out);
+  k_packed_scan_fwd<<<L.grid, 256, 0, as_stream(stream)>>>(x, L.sp, R, op == FSN_SCAN_PROD, exclusive != 0, out);
   FSN_LAUNCH_CHECK("k_packed_scan_fwd");
   return FSN_OK;
 }
@@ -379,11 +317,11 @@ extern "C" int fsn_packed_scan_bwd(const float* x, const float* d_out, const int
                                    float* d_x, fsn_stream_t stream) {
   FSN_REQUIRE(op == FSN_SCAN_SUM || op == FSN_SCAN_PROD, FSN_E_INVALID, "fsn_packed_scan_bwd: op %d is neither sum nor prod", op);
   FSN_SPAN_CHECK("fsn_packed_scan_bwd");
-  if (!launch_) return FSN_OK;
+  if (!L.launch) return FSN_OK;
   FSN_REQUIRE((x || op == FSN_SCAN_SUM) && d_out && d_x, FSN_E_INVALID, "fsn_packed_scan_bwd: null pointer");
   // a ray_indices / packed_info table need not cover every sample: what no ray owns gets 0
   FSN_HIP(hipMemsetAsync(d_x, 0, (size_t)N * sizeof(float), as_stream(stream)));
-  k_packed_scan_bwd<<<grid, 256, 0, as_stream(stream)>>>(x, d_out, sp, R, op == FSN_SCAN_PROD, exclusive != 0, d_x);
+  k_packed_scan_bwd<<<L.grid, 256, 0, as_stream(stream)>>>(x, d_out, L.sp, R, op == FSN_SCAN_PROD, exclusive != 0, d_x);
   FSN_LAUNCH_CHECK("k_packed_scan_bwd");
   return FSN_OK;
 }
@@ -393,9 +331,9 @@ extern "C" int fsn_packed_weights_fwd(const float* v, const float* t_starts, con
                                       int dense_S, int from_alpha, const float* prefix_trans, float* weights, float* trans,
                                       float* alphas, fsn_stream_t stream) {
   FSN_SPAN_CHECK("fsn_packed_weights_fwd");
-  if (!launch_) return FSN_OK;
+  if (!L.launch) return FSN_OK;
   FSN_REQUIRE(v && (from_alpha || (t_starts && t_ends)), FSN_E_INVALID, "fsn_packed_weights_fwd: null pointer");
-  k_packed_weights_fwd<<<grid, 256, 0, as_stream(stream)>>>(v, t_starts, t_ends, sp, R, from_alpha != 0, prefix_trans,
+  k_packed_weights_fwd<<<L.grid, 256, 0, as_stream(stream)>>>(v, t_starts, t_ends, L.sp, R, from_alpha != 0, prefix_trans,
                                                            weights, trans, alphas);
   FSN_LAUNCH_CHECK("k_packed_weights_fwd");
   return FSN_OK;
@@ -406,12 +344,26 @@ extern "C" int fsn_packed_weights_bwd(const float* v, const float* t_starts, con
                                       int dense_S, int from_alpha, const float* prefix_trans, const float* d_weights,
                                       const float* d_trans, const float* d_alphas, float* d_v, fsn_stream_t stream) {
   FSN_SPAN_CHECK("fsn_packed_weights_bwd");
-  if (!launch_) return FSN_OK;
+  if (!L.launch) return FSN_OK;
   FSN_REQUIRE(v && d_v && (from_alpha || (t_starts && t_ends)), FSN_E_INVALID, "fsn_packed_weights_bwd: null pointer");
   FSN_HIP(hipMemsetAsync(d_v, 0, (size_t)N * sizeof(float), as_stream(stream)));
-  k_packed_weights_bwd<<<grid, 256, 0, as_stream(stream)>>>(v, t_starts, t_ends, sp, R, from_alpha != 0, prefix_trans,
+  k_packed_weights_bwd<<<L.grid, 256, 0, as_stream(stream)>>>(v, t_starts, t_ends, L.sp, R, from_alpha != 0, prefix_trans,
                                                            d_weights, d_trans, d_alphas, d_v);
   FSN_LAUNCH_CHECK("k_packed_weights_bwd");
+  return FSN_OK;
+}
+
+// (no memset here: ray_indices covers every sample, and the caller's keep array stays as it is past them)
+extern "C" int fsn_packed_visibility(const float* sigmas, const float* t_starts, const float* t_ends,
+                                     const int64_t* ray_indices, int64_t N, int64_t R, float early_stop_eps,
+                                     float alpha_thre, uint8_t* keep, fsn_stream_t stream) {
+  RayLaunch L;
+  if (int rc = ray_launch("fsn_packed_visibility", ray_indices, nullptr, N, R, 0, false, &L)) return rc;
+  if (!L.launch) return FSN_OK;
+  FSN_REQUIRE(sigmas && t_starts && t_ends && keep, FSN_E_INVALID, "fsn_packed_visibility: null pointer");
+  k_packed_visibility<<<L.grid, 256, 0, as_stream(stream)>>>(sigmas, t_starts, t_ends, L.sp, R, 0, early_stop_eps,
+                                                            alpha_thre, keep);
+  FSN_LAUNCH_CHECK("k_packed_visibility");
   return FSN_OK;
 }
 
@@ -419,11 +371,12 @@ extern "C" int fsn_packed_visibility_alpha(const float* alphas, const int64_t* r
                                            int64_t N, int64_t R, int dense_S, float early_stop_eps, float alpha_thre,
                                            uint8_t* keep, fsn_stream_t stream) {
   FSN_SPAN_CHECK("fsn_packed_visibility_alpha");
-  if (!launch_) return FSN_OK;
+  if (!L.launch) return FSN_OK;
   FSN_REQUIRE(alphas && keep, FSN_E_INVALID, "fsn_packed_visibility_alpha: null pointer");
   FSN_HIP(hipMemsetAsync(keep, 0, (size_t)N, as_stream(stream)));
-  k_packed_visibility_alpha<<<grid, 256, 0, as_stream(stream)>>>(alphas, sp, R, early_stop_eps, alpha_thre, keep);
-  FSN_LAUNCH_CHECK("k_packed_visibility_alpha");
+  k_packed_visibility<<<L.grid, 256, 0, as_stream(stream)>>>(alphas, nullptr, nullptr, L.sp, R, 1, early_stop_eps,
+                                                            alpha_thre, keep);
+  FSN_LAUNCH_CHECK("k_packed_visibility");
   return FSN_OK;
 }
 
@@ -432,14 +385,14 @@ extern "C" int fsn_accumulate_fwd(const float* weights, const float* values, int
                                   fsn_stream_t stream) {
   FSN_REQUIRE(C >= 1, FSN_E_INVALID, "fsn_accumulate_fwd: bad sizes (C >= 1)");
   FSN_SPAN_CHECK("fsn_accumulate_fwd");
-  if (!launch_) {
+  if (!L.launch) {
     if (N == 0 && R > 0 && out)  // every ray is empty
       FSN_HIP(hipMemsetAsync(out, 0, (size_t)R * C * sizeof(float), as_stream(stream)));
     return FSN_OK;
   }
   FSN_REQUIRE(weights && out, FSN_E_INVALID, "fsn_accumulate_fwd: null pointer");
   FSN_REQUIRE(values || C == 1, FSN_E_INVALID, "fsn_accumulate_fwd: bad sizes (C must be 1 without values)");
-  k_accumulate_fwd<<<grid, 256, 0, as_stream(stream)>>>(weights, values, C, sp, R, out);
+  k_accumulate_fwd<<<L.grid, 256, 0, as_stream(stream)>>>(weights, values, C, L.sp, R, out);
   FSN_LAUNCH_CHECK("k_accumulate_fwd");
   return FSN_OK;
 }
@@ -449,13 +402,13 @@ extern "C" int fsn_accumulate_bwd(const float* d_out, const float* weights, cons
                                   int dense_S, float* d_weights, float* d_values, fsn_stream_t stream) {
   FSN_REQUIRE(C >= 1, FSN_E_INVALID, "fsn_accumulate_bwd: bad sizes (C >= 1)");
   FSN_SPAN_CHECK("fsn_accumulate_bwd");
-  if (!launch_) return FSN_OK;
+  if (!L.launch) return FSN_OK;
   FSN_REQUIRE(d_out && (d_weights || d_values) && (!d_values || (weights && values)), FSN_E_INVALID,
               "fsn_accumulate_bwd: null pointer");
   FSN_REQUIRE(values || C == 1, FSN_E_INVALID, "fsn_accumulate_bwd: bad sizes (C must be 1 without values)");
   if (d_weights) FSN_HIP(hipMemsetAsync(d_weights, 0, (size_t)N * sizeof(float), as_stream(stream)));
   if (d_values) FSN_HIP(hipMemsetAsync(d_values, 0, (size_t)N * C * sizeof(float), as_stream(stream)));
-  k_accumulate_bwd<<<grid, 256, 0, as_stream(stream)>>>(d_out, weights, values, C, sp, R, d_weights, d_values);
+  k_accumulate_bwd<<<L.grid, 256, 0, as_stream(stream)>>>(d_out, weights, values, C, L.sp, R, d_weights, d_values);
   FSN_LAUNCH_CHECK("k_accumulate_bwd");
   return FSN_OK;
 }

@@ -1,8 +1,9 @@
-// ray_dev.hpp — wave-level (64-lane) device routines for the per-ray parts of the path:
-// volume integration (prefix-scan alpha compositing) and hierarchical resampling.
-// One wavefront owns one ray; used by the standalone kernels in ray_ops.hip and by the
-// fused render kernel.  Compiled with -ffp-contract=off so the float op sequence is the
-// one written here (it mirrors oracle/fsnerf_oracle.py).
+// ray_dev.hpp — wave-level (64-lane) device routines for the per-ray parts of the path: the one-wave-per-ray
+// skeleton (where a ray's samples are, which of them a lane owns, the host checks of such a launch), the transmittance
+// walk that every density-form kernel is built on (trans_walk), volume integration and its density backward, and
+// hierarchical resampling.  One wavefront owns one ray; used by the standalone kernels (ray_ops.hip, packed_scan.hip,
+// composite_grad.hip, input_grad.hip) and by the fused render kernels.  Compiled with -ffp-contract=off so the float op
+// sequence is the one written here (it mirrors oracle/fsnerf_oracle.py).
 #pragma once
 #include "common.hpp"
 
@@ -83,6 +84,109 @@ __device__ __forceinline__ RaySpan ray_span(const int64_t* __restrict__ ri, int6
   return {beg, (int)(ray_lower_bound(ri, N, r + 1) - beg)};
 }
 
+// Where a ray's samples are: exactly one of sorted ray_indices [N] (searched by ray_span), packed_info [R,2] = (start,
+// count) (read, and clamped into [0, N] so that a wrong table cannot send a wave out of the arrays), dense rows of
+// dense_S samples.  (N == 0 with no table at all: every ray is empty, nothing is read.)
+struct SpanArgs {
+  const int64_t* ri;
+  const int64_t* pi;
+  int64_t N;
+  int dense_S;
+};
+
+__device__ __forceinline__ RaySpan span_of(const SpanArgs& sp, int64_t r) {
+  if (sp.dense_S > 0) return {r * sp.dense_S, sp.dense_S};
+  if (sp.pi) {
+    const int64_t beg = min(max(sp.pi[2 * r], (int64_t)0), sp.N);
+    const int64_t cnt = min(max(sp.pi[2 * r + 1], (int64_t)0), min(sp.N - beg, (int64_t)0x7fffffff));
+    return {beg, (int)cnt};
+  }
+  return ray_span(sp.ri, sp.N, r);
+}
+
+// lane l owns the contiguous samples [l per, (l+1) per) of a ray's S, per = ceil(S/64)
+__device__ __forceinline__ void lane_range(int S, int lane, int& i0, int& i1) {
+  const int per = (S + 63) >> 6;
+  i0 = lane * per;  // (past the ray's end for the last lanes of a short ray: [i0, i1) is empty then)
+  i1 = min(i0 + per, S);
+}
+
+// The per-ray skeleton of every one-wave-per-ray kernel (four rays per 256-thread block, grid = ceil(R/4)): this
+// wave's ray r, its samples [beg, beg + S) and this lane's share [i0, i1) of them (relative to beg).  ray_work()
+// returns whether the ray has samples; r >= R tells a wave past the last ray from an empty one (S == 0).  Kernels
+// that stride the lanes over the ray (i = lane; i < S; i += 64) take r, beg, S and lane from it.
+struct RayWork {
+  int64_t r, beg;
+  int S, lane, i0, i1;
+};
+__device__ __forceinline__ bool ray_work(const SpanArgs& sp, int64_t R, RayWork& w) {
+  w.lane = lane_id();
+  w.r = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (the ray is the wave's: scalar)
+  w.beg = 0;
+  w.S = 0;
+  if (w.r < R) {
+    const RaySpan span = span_of(sp, w.r);
+    w.beg = span.beg;
+    w.S = max(span.S, 0);
+  }
+  lane_range(w.S, w.lane, w.i0, w.i1);
+  return w.S > 0;
+}
+
+// The host side of such a launch: the checks every one-wave-per-ray entry point shares.  -> FSN_OK with launch = 0
+// when there is nothing to launch: R == 0, or N == 0 unless the kernel still has something to write for rays without
+// samples (launch_empty: the compositor's background, the regulariser's NaN marks).
+struct RayLaunch {
+  SpanArgs sp;
+  unsigned grid;
+  int launch;
+};
+static inline int ray_launch(const char* who, const int64_t* ri, const int64_t* pi, int64_t N, int64_t R, int dense_S,
+                             bool launch_empty, RayLaunch* L) {
+  *L = RayLaunch{SpanArgs{ri, pi, N, dense_S}, (unsigned)((R + 3) / 4), 0};
+  FSN_REQUIRE(N >= 0 && R >= 0 && dense_S >= 0, FSN_E_INVALID, "%s: bad sizes", who);
+  const int modes = (ri ? 1 : 0) + (pi ? 1 : 0) + (dense_S > 0 ? 1 : 0);
+  FSN_REQUIRE(modes <= 1, FSN_E_INVALID, "%s: more than one of ray_indices, packed_info and dense_S given", who);
+  if (R == 0 || (N == 0 && !launch_empty)) return FSN_OK;
+  FSN_REQUIRE((R + 3) / 4 <= 0x7fffffff, FSN_E_INVALID, "%s: bad sizes (too many rays)", who);
+  if (N > 0) {
+    FSN_REQUIRE(modes == 1, FSN_E_INVALID, "%s: null pointer (one of ray_indices, packed_info and dense_S is needed)", who);
+    FSN_REQUIRE(dense_S == 0 || (R <= N && N / R == dense_S && N % R == 0), FSN_E_INVALID,
+                "%s: bad sizes (dense rows need N == R * dense_S)", who);
+  } else {
+    L->sp = SpanArgs{nullptr, nullptr, 0, 0};  // every ray is empty: no table is read
+  }
+  L->launch = 1;
+  return FSN_OK;
+}
+
+// The transmittance walk.  sdt_of(i) = sigma_i dt_i of the lane's samples [i0, i1): sdt_before() sums them and returns
+// the sum over the lanes before this one (wave_excl_scan); trans_walk() hands body(i, T_i, e_i) every sample in order,
+// T_i = exp(-sum_{j<i} sigma_j dt_j), e_i = exp(-sigma_i dt_i) - so alpha_i = 1.0f - e_i and w_i = T_i alpha_i.  The
+// one definition of this arithmetic: the compositor, the fused kernels' weights and cull, the visibility rule, the
+// density primitives and the backwards all run it, which is why their results agree bit for bit.  The samples may be
+// in global memory or in LDS (the functor does the addressing).
+template <class SdtOf>
+__device__ __forceinline__ float sdt_before(int i0, int i1, SdtOf sdt_of) {
+  float lsum = 0.f;
+  for (int i = i0; i < i1; ++i) lsum += sdt_of(i);
+  float total;
+  return wave_excl_scan(lsum, total);
+}
+template <class SdtOf, class Body>
+__device__ __forceinline__ void trans_walk(int i0, int i1, float run, SdtOf sdt_of, Body body) {
+  for (int i = i0; i < i1; ++i) {
+    const float sdt = sdt_of(i);
+    const float e = expf(-sdt), T = expf(-run);
+    run += sdt;
+    body(i, T, e);
+  }
+}
+template <class SdtOf, class Body>
+__device__ __forceinline__ void trans_walk(int i0, int i1, SdtOf sdt_of, Body body) {
+  trans_walk(i0, i1, sdt_before(i0, i1, sdt_of), sdt_of, body);
+}
+
 struct CompositeOut {
   float* colors;   // [3]
   float* opacity;  // [1]
@@ -101,21 +205,13 @@ __device__ __forceinline__ void composite_ray(const float* __restrict__ sig, con
                                               int S, bool has_bkgd, float b0, float b1, float b2,
                                               const CompositeOut& o) {
   const int lane = lane_id();
-  const int per = (S + 63) >> 6;
-  const int i0 = lane * per;
-  const int i1 = min(i0 + per, S);
-  float lsum = 0.f;
-  for (int i = i0; i < i1; ++i) lsum += sig[i] * (t1[i] - t0[i]);
-  float total;
-  float run = wave_excl_scan(lsum, total);
+  int i0, i1;
+  lane_range(S, lane, i0, i1);
   float ar = 0.f, ag = 0.f, ab = 0.f, ao = 0.f, ad = 0.f;
-  for (int i = i0; i < i1; ++i) {
+  trans_walk(i0, i1, [&](int i) { return sig[i] * (t1[i] - t0[i]); }, [&](int i, float T, float e) {
     const float a = t0[i], b = t1[i];
-    const float sdt = sig[i] * (b - a);
-    const float alpha = 1.0f - expf(-sdt);
-    const float T = expf(-run);
+    const float alpha = 1.0f - e;
     const float w = T * alpha;
-    run += sdt;
     ar += w * rgb[3 * i + 0];
     ag += w * rgb[3 * i + 1];
     ab += w * rgb[3 * i + 2];
@@ -124,7 +220,7 @@ __device__ __forceinline__ void composite_ray(const float* __restrict__ sig, con
     if (o.weights) o.weights[i] = w;
     if (o.alphas) o.alphas[i] = alpha;
     if (o.trans) o.trans[i] = T;
-  }
+  });
   ar = wave_sum(ar);
   ag = wave_sum(ag);
   ab = wave_sum(ab);
@@ -149,19 +245,52 @@ __device__ __forceinline__ void composite_ray(const float* __restrict__ sig, con
 // weights only (density pass of the hierarchical sampler): w[i] = T_i * alpha_i
 __device__ __forceinline__ void weights_ray(const float* __restrict__ sig, const float* __restrict__ edges,
                                             int S, float* __restrict__ w_out) {
-  const int lane = lane_id();
-  const int per = (S + 63) >> 6;
-  const int i0 = lane * per;
-  const int i1 = min(i0 + per, S);
-  float lsum = 0.f;
-  for (int i = i0; i < i1; ++i) lsum += sig[i] * (edges[i + 1] - edges[i]);
-  float total;
-  float run = wave_excl_scan(lsum, total);
-  for (int i = i0; i < i1; ++i) {
-    const float sdt = sig[i] * (edges[i + 1] - edges[i]);
-    w_out[i] = expf(-run) * (1.0f - expf(-sdt));
-    run += sdt;
-  }
+  int i0, i1;
+  lane_range(S, lane_id(), i0, i1);
+  trans_walk(i0, i1, [&](int i) { return sig[i] * (edges[i + 1] - edges[i]); },
+             [&](int i, float T, float e) { w_out[i] = T * (1.0f - e); });
+}
+
+// The density backward for ONE ray by ONE wave ("Full compositor backward"): with T_i, e_i, alpha_i as in
+// trans_walk, p_i = prefix[i] (1 when absent), q_i = dL/dw_i (has_q: q_of(i); else absent), tau_i = dL/dtrans_i and
+// a_i = dL/dalpha_i (each nullable):
+//   A_i = q_i T_i p_i + a_i,   B_i T_i = (q_i alpha_i + tau_i) p_i T_i,   dL/dsigma_i = dt_i (A_i e_i - sum_{j>i} B_j T_j)
+// Pass 1 sums B_j T_j over the lane's samples, the suffix is total - prefix (wave_excl_scan), pass 2 walks again and
+// hands per_sample(i, w_i) each sample (the compositor's d_rgb).  Every optional operand is wave-uniform.  The pointers
+// are the ray's own (sample i of the ray at [i]).
+template <class QOf, class PerSample>
+__device__ __forceinline__ void density_bwd_ray(const float* __restrict__ sig, const float* __restrict__ t0,
+                                                const float* __restrict__ t1, int i0, int i1, bool has_q, QOf q_of,
+                                                const float* __restrict__ tau, const float* __restrict__ a,
+                                                const float* __restrict__ prefix, float* __restrict__ d_sig,
+                                                PerSample per_sample) {
+  auto sdt_of = [&](int i) { return sig[i] * (t1[i] - t0[i]); };
+  auto bt_of = [&](int i, float q, float T, float w) {
+    float bt = 0.f;
+    if (has_q) bt = q * w;
+    if (tau) bt += tau[i] * T;
+    return bt;
+  };
+  const float run = sdt_before(i0, i1, sdt_of);
+  float lq = 0.f;
+  trans_walk(i0, i1, run, sdt_of, [&](int i, float T, float e) {
+    if (prefix) T = T * prefix[i];
+    lq += bt_of(i, has_q ? q_of(i) : 0.f, T, T * (1.0f - e));
+  });
+  float qtot;
+  const float qbefore = wave_excl_scan(lq, qtot);  // sum of B_j T_j over the lanes before this one
+  float suffix = qtot - qbefore;                    // over this lane's samples and all later ones
+  trans_walk(i0, i1, run, sdt_of, [&](int i, float T, float e) {
+    if (prefix) T = T * prefix[i];
+    const float w = T * (1.0f - e);
+    const float q = has_q ? q_of(i) : 0.f;
+    suffix -= bt_of(i, q, T, w);  // now: over j > i
+    float A = 0.f;
+    if (has_q) A = q * T;
+    if (a) A += a[i];
+    d_sig[i] = (t1[i] - t0[i]) * (A * e - suffix);
+    per_sample(i, w);
+  });
 }
 
 // torch.linspace(0,1,n) element i, float32 (symmetric evaluation like ATen's CPU kernel)

@@ -163,55 +163,37 @@ __global__ void k_sample_pdf_merge(const float* __restrict__ edges, const float*
 // ---------------------------------------------------------------- compositing
 struct Bkgd { int has; float c[3]; };
 
-__global__ void k_composite_dense(const float* __restrict__ sig, const float* __restrict__ rgb,
-                                  const float* __restrict__ t0, const float* __restrict__ t1, int64_t R, int S,
-                                  Bkgd bk, float* __restrict__ colors, float* __restrict__ opacity,
-                                  float* __restrict__ depth, float* __restrict__ weights,
-                                  float* __restrict__ alphas, float* __restrict__ trans) {
-  const int wave = threadIdx.x >> 6;
-  const int64_t r = (int64_t)blockIdx.x * 4 + wave;
+// One kernel for both forms: the ray's samples by span_of (dense rows or the sorted ray_indices), then composite_ray on
+// that slice.  A ray without samples still runs it with S = 0: background colour, opacity 0, depth 0.
+__global__ void k_composite(const float* __restrict__ sig, const float* __restrict__ rgb, const float* __restrict__ t0,
+                            const float* __restrict__ t1, SpanArgs sp, int64_t R, Bkgd bk, float* __restrict__ colors,
+                            float* __restrict__ opacity, float* __restrict__ depth, float* __restrict__ weights,
+                            float* __restrict__ alphas, float* __restrict__ trans) {
+  RayWork w;
+  ray_work(sp, R, w);
+  const int64_t r = w.r, b = w.beg;
   if (r >= R) return;
-  const int64_t b = r * S;
   CompositeOut o{colors + 3 * r, opacity + r, depth + r, weights ? weights + b : nullptr,
                  alphas ? alphas + b : nullptr, trans ? trans + b : nullptr};
-  composite_ray(sig + b, rgb + 3 * b, t0 + b, t1 + b, S, bk.has != 0, bk.c[0], bk.c[1], bk.c[2], o);
-}
-
-// packed form: the ray's sample range in the sorted ray_indices (ray_span), then the same per-wave routine runs on
-// that slice.
-__global__ void k_composite_packed(const float* __restrict__ sig, const float* __restrict__ rgb,
-                                   const float* __restrict__ t0, const float* __restrict__ t1,
-                                   const int64_t* __restrict__ ri, int64_t N, int64_t R, Bkgd bk,
-                                   float* __restrict__ colors, float* __restrict__ opacity,
-                                   float* __restrict__ depth, float* __restrict__ weights,
-                                   float* __restrict__ alphas, float* __restrict__ trans) {
-  const int wave = threadIdx.x >> 6;
-  const int64_t r = (int64_t)blockIdx.x * 4 + wave;
-  if (r >= R) return;
-  const auto [b, S] = ray_span(ri, N, r);
-  CompositeOut o{colors + 3 * r, opacity + r, depth + r, weights ? weights + b : nullptr,
-                 alphas ? alphas + b : nullptr, trans ? trans + b : nullptr};
-  composite_ray(sig + b, rgb + 3 * b, t0 + b, t1 + b, S, bk.has != 0, bk.c[0], bk.c[1], bk.c[2], o);
+  composite_ray(sig + b, rgb + 3 * b, t0 + b, t1 + b, w.S, bk.has != 0, bk.c[0], bk.c[1], bk.c[2], o);
 }
 
 // ---------------------------------------------------------------- "next" rows
 // OcclusionRegularizer (src/core/loss.py:26-60): one wavefront per ray sums w(t) sigma over the ray's
-// samples (range found like in k_composite_packed); a second, single-block kernel averages the sums of the
+// samples (range found like in k_composite); a second, single-block kernel averages the sums of the
 // non-empty rays in a fixed order (deterministic, no float atomics).
-__global__ void k_occl_ray_sums(const float* __restrict__ sig, const float* __restrict__ t,
-                                const int64_t* __restrict__ ri, int64_t N, int64_t R, float a, float b, int func,
-                                float* __restrict__ sums) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + wave;
-  if (r >= R) return;
-  const auto [beg, S] = ray_span(ri, N, r);
+__global__ void k_occl_ray_sums(const float* __restrict__ sig, const float* __restrict__ t, SpanArgs sp, int64_t R,
+                                float a, float b, int func, float* __restrict__ sums) {
+  RayWork rw;
+  ray_work(sp, R, rw);
+  if (rw.r >= R) return;
   float acc = 0.f;
-  for (int64_t i = beg + lane; i < beg + S; i += 64) {
+  for (int64_t i = rw.beg + rw.lane; i < rw.beg + rw.S; i += 64) {
     const float w = func == 0 ? (-a * t[i] + b) : (a * expf(-b * t[i]));
     acc += w * sig[i];
   }
   acc = wave_sum(acc);
-  if (lane == 0) sums[r] = S > 0 ? acc : __builtin_nanf("");  // NaN marks "no samples"
+  if (rw.lane == 0) sums[rw.r] = rw.S > 0 ? acc : __builtin_nanf("");  // NaN marks "no samples"
 }
 
 __global__ void k_occl_mean(const float* __restrict__ sums, int64_t R, float* __restrict__ out) {
@@ -368,45 +350,48 @@ static Bkgd make_bkgd(const float* b) {
   return k;
 }
 
+// both compositor forwards: a ray without samples still gets its background, so an all-empty problem launches too
+static int composite_fwd_launch(const char* who, const float* sigmas, const float* rgbs, const float* t_starts,
+                                const float* t_ends, const int64_t* ray_indices, int64_t N, int64_t R, int dense_S,
+                                const float* bkgd_host, float* colors, float* opacity, float* depth, float* weights,
+                                float* alphas, float* trans, fsn_stream_t stream) {
+  RayLaunch L;
+  if (int rc = ray_launch(who, ray_indices, nullptr, N, R, dense_S, true, &L)) return rc;
+  if (!L.launch) return FSN_OK;
+  FSN_REQUIRE(colors && opacity && depth, FSN_E_INVALID, "%s: null output", who);
+  FSN_REQUIRE(N == 0 || (sigmas && rgbs && t_starts && t_ends), FSN_E_INVALID, "%s: null input", who);
+  k_composite<<<L.grid, 256, 0, as_stream(stream)>>>(sigmas, rgbs, t_starts, t_ends, L.sp, R, make_bkgd(bkgd_host),
+                                                     colors, opacity, depth, weights, alphas, trans);
+  FSN_LAUNCH_CHECK("k_composite");
+  return FSN_OK;
+}
+
 extern "C" int fsn_composite_fwd(const float* sigmas, const float* rgbs, const float* t_starts, const float* t_ends,
                                  int64_t R, int S, const float* bkgd_host, float* colors, float* opacity,
                                  float* depth, float* weights, float* alphas, float* trans, fsn_stream_t stream) {
   FSN_REQUIRE(R >= 0 && S >= 0, FSN_E_INVALID, "fsn_composite_fwd: bad sizes");
-  if (R == 0) return FSN_OK;
-  FSN_REQUIRE(colors && opacity && depth, FSN_E_INVALID, "fsn_composite_fwd: null output");
-  FSN_REQUIRE(S == 0 || (sigmas && rgbs && t_starts && t_ends), FSN_E_INVALID, "fsn_composite_fwd: null input");
-  k_composite_dense<<<nblocks(R, 4), 256, 0, as_stream(stream)>>>(sigmas, rgbs, t_starts, t_ends, R, S,
-                                                                 make_bkgd(bkgd_host), colors, opacity, depth,
-                                                                 weights, alphas, trans);
-  FSN_LAUNCH_CHECK("k_composite_dense");
-  return FSN_OK;
+  return composite_fwd_launch("fsn_composite_fwd", sigmas, rgbs, t_starts, t_ends, nullptr, R * S, R, S, bkgd_host, colors,
+                              opacity, depth, weights, alphas, trans, stream);
 }
 
 extern "C" int fsn_composite_packed_fwd(const float* sigmas, const float* rgbs, const float* t_starts,
                                         const float* t_ends, const int64_t* ray_indices, int64_t N, int64_t R,
                                         const float* bkgd_host, float* colors, float* opacity, float* depth,
                                         float* weights, float* alphas, float* trans, fsn_stream_t stream) {
-  FSN_REQUIRE(R >= 0 && N >= 0, FSN_E_INVALID, "fsn_composite_packed_fwd: bad sizes");
-  if (R == 0) return FSN_OK;
-  FSN_REQUIRE(colors && opacity && depth, FSN_E_INVALID, "fsn_composite_packed_fwd: null output");
-  FSN_REQUIRE(N == 0 || (sigmas && rgbs && t_starts && t_ends && ray_indices), FSN_E_INVALID,
-              "fsn_composite_packed_fwd: null input");
-  k_composite_packed<<<nblocks(R, 4), 256, 0, as_stream(stream)>>>(sigmas, rgbs, t_starts, t_ends, ray_indices, N, R,
-                                                                  make_bkgd(bkgd_host), colors, opacity, depth,
-                                                                  weights, alphas, trans);
-  FSN_LAUNCH_CHECK("k_composite_packed");
-  return FSN_OK;
+  return composite_fwd_launch("fsn_composite_packed_fwd", sigmas, rgbs, t_starts, t_ends, ray_indices, N, R, 0, bkgd_host,
+                              colors, opacity, depth, weights, alphas, trans, stream);
 }
 
 extern "C" int fsn_occlusion_reg_fwd(const float* sigmas, const float* t_vals, const int64_t* ray_idxs, int64_t N,
                                      int64_t n_rays, float a, float b, int func, float* ray_sums, float* out,
                                      fsn_stream_t stream) {
-  FSN_REQUIRE(N >= 0 && n_rays >= 0 && (func == 0 || func == 1), FSN_E_INVALID, "fsn_occlusion_reg_fwd: bad arguments");
+  FSN_REQUIRE(func == 0 || func == 1, FSN_E_INVALID, "fsn_occlusion_reg_fwd: bad arguments");
+  RayLaunch L;  // (rays without samples are marked, so an all-empty problem launches as well)
+  if (int rc = ray_launch("fsn_occlusion_reg_fwd", ray_idxs, nullptr, N, n_rays, 0, true, &L)) return rc;
   FSN_REQUIRE(out && (n_rays == 0 || ray_sums), FSN_E_INVALID, "fsn_occlusion_reg_fwd: null output");
-  FSN_REQUIRE(N == 0 || (sigmas && t_vals && ray_idxs), FSN_E_INVALID, "fsn_occlusion_reg_fwd: null input");
-  if (n_rays > 0) {
-    k_occl_ray_sums<<<nblocks(n_rays, 4), 256, 0, as_stream(stream)>>>(sigmas, t_vals, ray_idxs, N, n_rays, a, b, func,
-                                                                     ray_sums);
+  FSN_REQUIRE(N == 0 || (sigmas && t_vals), FSN_E_INVALID, "fsn_occlusion_reg_fwd: null input");
+  if (L.launch) {
+    k_occl_ray_sums<<<L.grid, 256, 0, as_stream(stream)>>>(sigmas, t_vals, L.sp, n_rays, a, b, func, ray_sums);
     FSN_LAUNCH_CHECK("k_occl_ray_sums");
   }
   k_occl_mean<<<1, 256, 0, as_stream(stream)>>>(ray_sums, n_rays, out);

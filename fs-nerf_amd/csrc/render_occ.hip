@@ -16,7 +16,7 @@
 // HBM traffic: the rays in (or none: generated from the pose), 20 B per ray out, the bit grid through L2.
 // Every sample is evaluated independently of its tile position and every ray is integrated by one wave with the
 // arithmetic of the standalone kernels (occ_dev.hpp, ray_dev.hpp): the image does not depend on how batches form and is
-// the unfused path's (march -> k_mlp_fwd -> k_visibility -> k_mlp_fwd -> k_composite_packed).
+// the unfused path's (march -> k_mlp_fwd -> k_packed_visibility -> k_mlp_fwd -> k_composite).
 // The march is k_occ_march's in either regime (occ_dev.hpp: ray_range / march_ray_regime - per-ray bounds, and for
 // cone_angle > 0 blocks of 64 intervals whose width grows with distance; include/fsnerf_hip.h has the definition at
 // fsn_occgrid_march_ex), so every candidate carries its own interval END and nothing below assumes a common width.
@@ -283,24 +283,18 @@ __global__ __launch_bounds__(kThreads) void k_render_occ(OccKArgs k) {
         }
       }
       lds_barrier();
-      // keep flags per ray: the arithmetic of k_visibility (occgrid.hip), one wave per ray
+      // keep flags per ray: k_packed_visibility's rule on the same walk (trans_walk, ray_dev.hpp), one wave per ray
       for (int r = wave; r < n_rays; r += kWaves) {
         const int Sn = FSN_AT(S.cand_cnt, r), beg = FSN_AT(S.cand_off, r);
-        const int per = (Sn + 63) >> 6;
-        const int i0 = lane * per, i1 = min(i0 + per, Sn);
-        float lsum = 0.f;
-        for (int i = i0; i < i1; ++i) lsum += FSN_AT(S.sigc, beg + i) * (cand_end(beg + i) - FSN_AT(S.t0c, beg + i));
-        float tot;
-        float run = wave_excl_scan(lsum, tot);
+        int i0, i1;
+        lane_range(Sn, lane, i0, i1);
         int nk = 0;
-        for (int i = i0; i < i1; ++i) {
-          const float sdt = FSN_AT(S.sigc, beg + i) * (cand_end(beg + i) - FSN_AT(S.t0c, beg + i));
-          const float T = expf(-run), alpha = 1.0f - expf(-sdt);
-          const bool kp = T >= a.early_stop_eps && alpha >= a.alpha_thre;
-          FSN_AT(S.keepf, beg + i) = kp ? 1 : 0;
-          nk += kp ? 1 : 0;
-          run += sdt;
-        }
+        trans_walk(i0, i1, [&](int i) { return FSN_AT(S.sigc, beg + i) * (cand_end(beg + i) - FSN_AT(S.t0c, beg + i)); },
+                   [&](int i, float T, float e) {
+                     const bool kp = T >= a.early_stop_eps && 1.0f - e >= a.alpha_thre;
+                     FSN_AT(S.keepf, beg + i) = kp ? 1 : 0;
+                     nk += kp ? 1 : 0;
+                   });
         int tk;
         wave_excl_scan_i(nk, tk);
         if (lane == 0) FSN_AT(S.kept_cnt, r) = tk;

@@ -9,7 +9,9 @@ must describe the same rays.  Metric: test_train_step._rel, max |a - b| / max |b
 (gradients), the project's own for this arithmetic class (tests/test_composite_grad_gpu.py).  Every figure is printed
 before it is asserted.  Measured on the MI355X: every forward figure of this file at or below 3.2e-7, every gradient
 figure at or below 3.9e-7 (the product scans' dense backward), the integration test's colours, opacity and depth
-identical to rendering()'s; no sample of the visibility check lies within 1e-6 of a threshold."""
+identical to rendering()'s; no sample of the visibility check lies within 1e-6 of a threshold.  Two equalities hold by
+construction and are pinned with torch.equal: the dense compositor against the packed one (one kernel), the density
+form's weights backward against the compositor backward (one device routine)."""
 import functools
 
 import pytest
@@ -84,6 +86,41 @@ def test_density_form_equals_the_compositor_bit_for_bit(S):
     ref = CR.forward64(case, None)
     for k, v in (("weights", w), ("trans", tr), ("alphas", al)):
         _check(f"S={S} forward {k}", v, ref[k], TOL_FWD)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S", [1] + SIZES)
+def test_dense_compositor_equals_the_packed_one_bit_for_bit(S):
+    """one kernel behind both entry points: dense rows [9, S] and the same samples flattened under ray_indices"""
+    from fs_nerf_amd import ops
+    case = VR.dense_case(S)
+    R = case["R"]
+    rgb = torch.rand(R * S, 3, generator=torch.Generator().manual_seed(600 + S))
+    sig, t0, t1, rgb = (_g(t) for t in (case["sig"], case["t0"], case["t1"], rgb))
+    dense = ops.composite(sig.reshape(R, S), rgb.reshape(R, S, 3), t0.reshape(R, S), t1.reshape(R, S), _g(BK))
+    ri = torch.arange(R).repeat_interleave(S)
+    packed = ops.composite_packed(sig, rgb, t0, t1, _g(ri), R, _g(BK))
+    for name, a, b in zip(("colors", "opacity", "depth"), dense, packed):
+        assert torch.equal(a, b), name
+    for k in ("weights", "alphas", "trans"):
+        assert dense[3][k].shape == (R, S) and torch.equal(dense[3][k].reshape(-1), packed[3][k]), k
+    assert float(packed[1].min()) > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S", SIZES)
+@pytest.mark.parametrize("which", ["all", "weights", "trans", "alphas"])
+def test_density_weights_backward_equals_the_compositor_backward_bit_for_bit(S, which):
+    """one routine behind both: without a colour cotangent the compositor's q_i = 0 - 0 + 0 + u_i is u_i exactly, so
+    d_sigmas agree to the bit (torch.equal: the two accumulate from a literal 0 in different places, +-0 alike)"""
+    from fs_nerf_amd import ops
+    case, g, _ = _density(S)
+    cot = {k: (_g(v) if which in ("all", k) else None) for k, v in case["cot"].items()}
+    spans = ops.RaySpans(case["sig"].numel(), case["R"], ray_indices=g["ri"])
+    mine = ops.packed_weights_bwd(g["sig"], g["t0"], g["t1"], spans, False, None, cot["weights"], cot["trans"], cot["alphas"])
+    theirs, _ = ops.composite_packed_bwd_full(g["sig"], g["rgb"], g["t0"], g["t1"], g["ri"], case["R"], None, None, None,
+                                              d_weights=cot["weights"], d_alphas=cot["alphas"], d_trans=cot["trans"])
+    assert torch.equal(mine, theirs) and float(mine.abs().max()) > 0
 
 
 @pytest.mark.gpu
