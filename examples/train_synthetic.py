@@ -4,7 +4,7 @@
 (src/run-nerf.py:216-299: ray batch -> render_rays(train=True) -> MSE -> backward -> Adam -> ExponentialDecay ->
 estimator.update_every_n_steps) and evaluated with render_frame + PSNR and SSIM (run-nerf.py:140-190).
 
-    python examples/train_synthetic.py [--estimator occgrid|stratified] [--iters 400] [--hw 64] [--u8-dataset]
+    python examples/train_synthetic.py [--estimator occgrid|stratified|propnet] [--iters 400] [--hw 64] [--u8-dataset]
                                        [--depth-weight W] [--distortion-weight W] [--cone-angle A] [--near-plane T]
                                        [--mark-invisible] [--min-views K]
 
@@ -20,6 +20,11 @@ loss of the compositor's weights (core.loss.DistortionLoss).
 --cone-angle / --near-plane (both 0 by default): `sampling_kwargs` of render_rays / render_frame / render_path - the
 occupancy march's step grows with distance, dt = max(t * cone_angle, step), and nothing is sampled in front of the near
 plane - in training, evaluation and the path render alike.
+
+--estimator propnet: a learned proposal in the estimator slot (render/propnet.py) - one 4x128 proposal network,
+prop_samples=(128,), num_samples=64, uniform in disparity between near and far, its own Adam; after the main step
+`estimator.update_every_n_steps(extras["trans"].reshape(n_rays, 64), requires_grad=True)` takes the interlevel loss's
+step on the proposal network.
 
 --mark-invisible (off by default): before the first step the occupancy estimator takes every cell that fewer than
 --min-views K (default 1) training views see out of the grid for good (OccGridEstimator.mark_invisible_from_views: a
@@ -43,6 +48,7 @@ from fs_nerf_amd.core.scheduler import ExponentialDecay  # noqa: E402
 from fs_nerf_amd.nerfdata import FrameLoader, RayDataset, RayLoader  # noqa: E402
 from fs_nerf_amd.render import rendering as R  # noqa: E402
 from fs_nerf_amd.render.occgrid import OccGridEstimator  # noqa: E402
+from fs_nerf_amd.render.propnet import PropNetEstimator  # noqa: E402
 from fs_nerf_amd.utils import utilities as U  # noqa: E402
 
 
@@ -65,7 +71,7 @@ def make_model(seed, dev):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--estimator", choices=("occgrid", "stratified"), default="occgrid")
+    ap.add_argument("--estimator", choices=("occgrid", "stratified", "propnet"), default="occgrid")
     ap.add_argument("--iters", type=int, default=400)
     ap.add_argument("--hw", type=int, default=64)
     ap.add_argument("--batch", type=int, default=4096)
@@ -133,6 +139,12 @@ def main():
         model.cull_precision = "bf16"
     if a.estimator == "occgrid":
         estimator = OccGridEstimator(roi_aabb=torch.tensor([-1.5, -1.5, -1.5, 1.5, 1.5, 1.5]), resolution=64, levels=1).to(dev)
+    elif a.estimator == "propnet":
+        torch.manual_seed(3)
+        proposal = M.NeRF(3, 3, 4, 128, (), pos_fn={"n_freqs": 10, "log_space": True},
+                          dir_fn={"n_freqs": 4, "log_space": True}).to(dev).train()
+        estimator = PropNetEstimator(torch.optim.Adam(proposal.parameters(), lr=5e-4), prop_models=[proposal],
+                                     prop_samples=(128,), num_samples=64, near_plane=near, far_plane=far)
     else:
         estimator = R.StratifiedEstimator(near, far, 64, 128)
     estimator.train()
@@ -183,10 +195,19 @@ def main():
         optimizer.step()
         scheduler.step()
         optimizer.zero_grad()
-        estimator.update_every_n_steps(step=k, occ_eval_fn=occ_eval_fn, occ_thre=1e-2)
+        if a.estimator == "propnet":  # the proposal network's own step, on the interlevel loss
+            prop_loss = estimator.update_every_n_steps(extras["trans"].reshape(rays_o.shape[0], estimator.num_samples),
+                                                       requires_grad=estimator.proposal_requires_grad)
+            if not math.isfinite(prop_loss):
+                raise RuntimeError(f"iter {k}: the proposal loss is {prop_loss}")
+        else:
+            estimator.update_every_n_steps(step=k, occ_eval_fn=occ_eval_fn, occ_thre=1e-2)
         if k % 100 == 0 or k == a.iters - 1:
             lv = float(loss.detach())
-            print(f"iter {k:5d}  loss {lv:.5f}  psnr {-10 * math.log10(max(lv, 1e-10)):.2f} dB", flush=True)
+            if not math.isfinite(lv):
+                raise RuntimeError(f"iter {k}: the loss is {lv}")
+            print(f"iter {k:5d}  loss {lv:.5f}  psnr {-10 * math.log10(max(lv, 1e-10)):.2f} dB"
+                  + (f"  proposal loss {prop_loss:.3e}" if a.estimator == "propnet" else ""), flush=True)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     model.eval()

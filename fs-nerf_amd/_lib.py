@@ -26,6 +26,10 @@ FSN_RAY_ORDER_PERMUTED = 1  # ... the epoch permutation of (seed, epoch) ...
 FSN_RAY_ORDER_EXPLICIT = 2  # ... an explicit device index list
 FSN_SCAN_SUM = 0  # fsn_packed_scan_fwd / _bwd ops
 FSN_SCAN_PROD = 1
+FSN_PROP_MAX_ROW = 1024  # fsn_importance_sample / fsn_prop_resample / fsn_prop_loss_*: intervals per ray, in and out
+FSN_STOT_NONE = 0  # the samplers' s -> t transforms
+FSN_STOT_UNIFORM = 1
+FSN_STOT_LINDISP = 2
 
 
 class MlpDesc(C.Structure):
@@ -143,7 +147,13 @@ SIGNATURES = {
     "fsn_packed_visibility_alpha": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _f, _f, _vp, _vp]),
     "fsn_accumulate_fwd": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _i64, _i, _vp, _vp]),
     "fsn_accumulate_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i64, _i64, _i, _vp, _vp, _vp]),
-    "fsn_ssim_workspace_doubles": (_i64, [_i64, _i, _i, _i]),
+    # proposal-network sampler (csrc/propnet.hip): dense rows
+    "fsn_importance_sample": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _vp]),
+    "fsn_prop_resample": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    "fsn_searchsorted_dense": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp]),
+    "fsn_prop_loss_fwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
+    "fsn_prop_loss_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
+    "fsn_ssim_workspace_doubles":(_i64, [_i64, _i, _i, _i]),
     "fsn_ssim": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp, _vp]),
     "fsn_psnr_workspace_doubles": (_i64, [_i64, _i, _i, _i]),
     "fsn_psnr": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -1096,6 +1096,105 @@ def accumulate_bwd(d_out: Tensor, weights: Tensor, values: Optional[Tensor], spa
     return d_w, d_v
 
 
+# ------------------------------------------------------------------ proposal-network sampler (csrc/propnet.hip)
+_STOT = {None: L.FSN_STOT_NONE, "uniform": L.FSN_STOT_UNIFORM, "lindisp": L.FSN_STOT_LINDISP}
+
+
+def _rows(t: Tensor, name: str, R: int, cols: int) -> Tensor:
+    t = _gpu_f32(t, name)
+    if tuple(t.shape) != (R, cols):
+        raise ValueError(f"{name}: expected shape ({R}, {cols}), got {tuple(t.shape)}")
+    return t
+
+
+def _stot_args(transform: Optional[str], near: float, far: float):
+    if transform not in _STOT:
+        raise ValueError(f"transform: expected None, 'uniform' or 'lindisp', got {transform!r}")
+    return _STOT[transform], float(near), float(far)
+
+
+def _jitter(b: Optional[Tensor], R: int) -> Optional[Tensor]:
+    return None if b is None else _rows(b.reshape(-1, 1), "b", R, 1)
+
+
+def importance_sample(vals: Tensor, cdfs: Tensor, n: int, b: Optional[Tensor] = None, transform: Optional[str] = None,
+                      near: float = 0.0, far: float = 0.0, want_centres: bool = True):
+    """vals / cdfs [R, S+1] -> (s_edges [R, n+1], centres [R, n] or None, t_edges [R, n+1] or None (no transform));
+    b: one jitter per ray [R], None: 0.5 (fsn_importance_sample)."""
+    vals = _gpu_f32(vals, "vals")
+    R, S, n = int(vals.shape[0]), int(vals.shape[1]) - 1, int(n)
+    vals, cdfs, b = _rows(vals, "vals", R, S + 1), _rows(cdfs, "cdfs", R, S + 1), _jitter(b, R)
+    tf, near, far = _stot_args(transform, near, far)
+    dev = vals.device
+    s = torch.empty(R, max(n, 0) + 1, device=dev)
+    x = torch.empty(R, max(n, 0), device=dev) if want_centres else None
+    t = torch.empty_like(s) if transform is not None else None
+    with torch.cuda.device(dev):
+        L.check(L.lib().fsn_importance_sample(_p(vals), _p(cdfs), R, S, n, _p(b), tf, near, far, _p(s), _p(x), _p(t),
+                                              _stream()), "fsn_importance_sample")
+    return s, x, t
+
+
+def prop_resample(s_edges: Tensor, t_edges: Tensor, sigmas: Tensor, n: int, b: Optional[Tensor] = None,
+                  transform: Optional[str] = None, near: float = 0.0, far: float = 0.0, want_centres: bool = False):
+    """s_edges / t_edges [R, S+1], sigmas [R, S] -> (cdfs [R, S+1], s_out [R, n+1], centres or None, t_out or None):
+    the proposal's cdfs and the next level's intervals in one launch (fsn_prop_resample)."""
+    sigmas = _gpu_f32(sigmas, "sigmas")
+    R, S, n = int(sigmas.shape[0]), int(sigmas.shape[1]), int(n)
+    s_edges, t_edges, b = _rows(s_edges, "s_edges", R, S + 1), _rows(t_edges, "t_edges", R, S + 1), _jitter(b, R)
+    tf, near, far = _stot_args(transform, near, far)
+    dev = sigmas.device
+    cdfs = torch.empty(R, S + 1, device=dev)
+    s = torch.empty(R, max(n, 0) + 1, device=dev)
+    x = torch.empty(R, max(n, 0), device=dev) if want_centres else None
+    t = torch.empty_like(s) if transform is not None else None
+    with torch.cuda.device(dev):
+        L.check(L.lib().fsn_prop_resample(_p(s_edges), _p(t_edges), _p(sigmas), R, S, n, _p(b), tf, near, far, _p(cdfs),
+                                          _p(s), _p(x), _p(t), _stream()), "fsn_prop_resample")
+    return cdfs, s, x, t
+
+
+def searchsorted_dense(keys: Tensor, values: Tensor) -> Tuple[Tensor, Tensor]:
+    """keys [R, K] sorted per row, values [R, Q] -> (ids_left, ids_right) int64 [R, Q] (fsn_searchsorted_dense)."""
+    keys, values = _gpu_f32(keys, "sorted_sequence"), _gpu_f32(values, "values")
+    if keys.dim() != 2 or values.dim() != 2 or keys.shape[0] != values.shape[0]:
+        raise ValueError(f"searchsorted: expected [R, K] and [R, Q], got {tuple(keys.shape)} and {tuple(values.shape)}")
+    R, K, Q = int(keys.shape[0]), int(keys.shape[1]), int(values.shape[1])
+    il = torch.empty(R, Q, dtype=torch.int64, device=keys.device)
+    ir = torch.empty_like(il)
+    with torch.cuda.device(keys.device):
+        L.check(L.lib().fsn_searchsorted_dense(_p(keys), _p(values), R, K, Q, _p(il), _p(ir), _stream()),
+                "fsn_searchsorted_dense")
+    return il, ir
+
+
+def _prop_loss_rows(q_edges, q_cdfs, k_edges, k_cdfs):
+    q_edges = _gpu_f32(q_edges, "segments_query")
+    k_edges = _gpu_f32(k_edges, "segments_key")
+    R, n, S = int(q_edges.shape[0]), int(q_edges.shape[1]) - 1, int(k_edges.shape[1]) - 1
+    return (_rows(q_edges, "segments_query", R, n + 1), _rows(q_cdfs, "cdfs_query", R, n + 1),
+            _rows(k_edges, "segments_key", R, S + 1), _rows(k_cdfs, "cdfs_key", R, S + 1)), R, n, S
+
+
+def prop_loss_fwd(q_edges: Tensor, q_cdfs: Tensor, k_edges: Tensor, k_cdfs: Tensor) -> Tensor:
+    """-> the interlevel loss per query interval [R, n] (fsn_prop_loss_fwd)"""
+    rows, R, n, S = _prop_loss_rows(q_edges, q_cdfs, k_edges, k_cdfs)
+    loss = torch.empty(R, max(n, 0), device=rows[0].device)
+    with torch.cuda.device(loss.device):
+        L.check(L.lib().fsn_prop_loss_fwd(*(_p(t) for t in rows), R, n, S, _p(loss), _stream()), "fsn_prop_loss_fwd")
+    return loss
+
+
+def prop_loss_bwd(q_edges: Tensor, q_cdfs: Tensor, k_edges: Tensor, k_cdfs: Tensor, d_loss: Tensor) -> Tensor:
+    """-> d_cdfs_key [R, S+1] (fsn_prop_loss_bwd)"""
+    rows, R, n, S = _prop_loss_rows(q_edges, q_cdfs, k_edges, k_cdfs)
+    g = _rows(d_loss, "d_loss", R, n)
+    d_ck = torch.empty(R, S + 1, device=g.device)
+    with torch.cuda.device(g.device):
+        L.check(L.lib().fsn_prop_loss_bwd(*(_p(t) for t in rows), _p(g), R, n, S, _p(d_ck), _stream()), "fsn_prop_loss_bwd")
+    return d_ck
+
+
 # ------------------------------------------------------------------ occupancy-grid sampler (SURVEY 8f, row f2)
 def occgrid_march(rays_o: Tensor, rays_d: Tensor, aabb: Sequence[float], res: int, levels: int, bits: Tensor,
                   near_plane: float, far_plane: float, step: float, u: Optional[Tensor], max_steps: int,

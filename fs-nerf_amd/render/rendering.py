@@ -25,6 +25,7 @@ from ..core.models import NeRF, frame_flagged, guarded_launch
 from ..utils import utilities as U
 from . import volrend
 from .occgrid import OccGridEstimator
+from .propnet import PropNetEstimator, prop_sigma_fn
 
 FUSED_OCC_MAX_STEPS = 2048  # csrc/render_occ.hip: samples of one ray group in LDS
 
@@ -370,6 +371,27 @@ def _occ_sampler(rays_o, rays_d, estimator, model, train, render_step_size, u, u
     return _sampler_launch(model, needs_grad, dev, _probe(estimator, rays_o, rays_d), launch)
 
 
+def _propnet_sampler(rays_o, rays_d, estimator, model, train, render_step_size, u, u_fine, needs_grad, opts=None):
+    """propnet: PropNetEstimator.sampling with the estimator's own proposal networks, counts, planes and sampling type
+    (a near_plane / far_plane among the options overrides the planes), flattened to the packed triple - every ray has
+    exactly num_samples samples in order, so extras["trans"].reshape(n_rays, num_samples) is what the estimator's
+    update_every_n_steps takes.  `u`: the per-level jitters, len(prop_samples) + 1 tensors [n_rays]."""
+    opts = opts or {}
+    if any(k not in ("near_plane", "far_plane") for k in opts):
+        raise ValueError("PropNetEstimator: sampling_kwargs may hold near_plane / far_plane only")
+    near, far = opts.get("near_plane", estimator.near_plane), opts.get("far_plane", estimator.far_plane)
+    if near is None or far is None:
+        raise ValueError("PropNetEstimator: near_plane and far_plane are needed (the estimator's, or in sampling_kwargs)")
+    R, dev = rays_o.shape[0], rays_o.device
+    requires_grad = bool(estimator.training and torch.is_grad_enabled() and estimator.proposal_requires_grad)
+    t_starts, t_ends = estimator.sampling([prop_sigma_fn(m, rays_o, rays_d) for m in estimator.prop_models],
+                                          estimator.prop_samples, estimator.num_samples, R, near, far,
+                                          estimator.sampling_type, stratified=train, requires_grad=requires_grad, u=u,
+                                          device=dev)
+    ray_indices = torch.arange(R, device=dev).repeat_interleave(estimator.num_samples)
+    return ray_indices, t_starts.reshape(-1), t_ends.reshape(-1)
+
+
 def _estimator_sampling(rays_o, rays_d, estimator, model, train, render_step_size, u, u_fine, needs_grad, opts=None):
     def sigma_fn(t_starts, t_ends, ray_indices):
         if isinstance(model, NeRF):  # same values, gathers and midpoints inside the launch (no [N,3] tensors)
@@ -458,7 +480,10 @@ def _rays_route(estimator, model, model_fine, needs_grad: bool, want_extras: boo
     """render_rays' launch route, from plain attribute tests (the FUSED_OCC_* switches are read at call time).  The
     scalar sampling options (planes, thresholds) are arguments of every route's kernels and choose nothing; a cone
     angle or per-ray bounds take the standalone march unless FUSED_OCC_CONE opens the one-launch routes to them, which
-    then apply the rules below with the cone march's interval count."""
+    then apply the rules below with the cone march's interval count.  A PropNetEstimator always takes its own route
+    (it is its own sampler; the options it cannot honour are a ValueError there)."""
+    if isinstance(estimator, PropNetEstimator):
+        return "propnet"
     if _march_only(sampling_kwargs):
         return "estimator-sampling"
     opts = sampling_kwargs
@@ -484,7 +509,7 @@ def _rays_route(estimator, model, model_fine, needs_grad: bool, want_extras: boo
 
 _ONE_LAUNCH = {"occ-frame": _fused_occ_launch, "occ-extras": _fused_occ_launch, "stratified-fused": _fused_launch}
 _SAMPLERS = {"stratified-sampler": _stratified_sampler, "occ-sampler": _occ_sampler,
-             "estimator-sampling": _estimator_sampling}
+             "estimator-sampling": _estimator_sampling, "propnet": _propnet_sampler}
 
 
 def render_rays(rays_o: Tensor, rays_d: Tensor, estimator, model: nn.Module, train: bool = False,
@@ -502,7 +527,9 @@ def render_rays(rays_o: Tensor, rays_d: Tensor, estimator, model: nn.Module, tra
     `early_stop_eps`, `alpha_thre` (every occupancy route takes them) - and of the occupancy march: `cone_angle`
     (dt = max(t cone_angle, render_step_size)) and per-ray `t_min` / `t_max` [n_rays], which go through
     `estimator.sampling` (with FUSED_OCC_CONE on: through the route the call takes without them).  None is the
-    reference's call; an unknown key is a TypeError."""
+    reference's call; an unknown key is a TypeError.  A `PropNetEstimator` in the estimator slot (render/propnet.py) takes
+    the "propnet" route: its own `sampling` (near_plane / far_plane are the only options it knows; `u`: its per-level
+    jitters, len(prop_samples) + 1 tensors [n_rays]), then the full pass and `rendering`."""
     opts = _sampling_options(sampling_kwargs)
     rays_o = rays_o.to(device)
     rays_d = rays_d.to(device)

@@ -568,6 +568,50 @@ int fsn_accumulate_bwd(const float* d_out, const float* weights, const float* va
                        const int64_t* packed_info, int64_t N, int64_t R, int dense_S, float* d_weights, float* d_values,
                        fsn_stream_t stream);
 
+/* Proposal-network sampler (csrc/propnet.hip; render/pdf.py and render/propnet.py are the Python surface, named after
+ * nerfacc's pdf module and PropNetEstimator - this package's own definitions of nerfacc's documented semantics, see
+ * DESIGN.md "Proposal-network estimator").  Dense rows only: every array is [R, .] float32 on the DEVICE, one wave per
+ * ray, no atomics, every sum in a fixed order.  A ray's histogram is S intervals: edges v[0..S] (non-decreasing) and cdf
+ * c[0..S] (non-decreasing, c[0] = 0, c[S] = 1).
+ * fsn_importance_sample: n intervals per ray from the inverse cdf.  Centre i: u = (i + b) / n (one float32 add, one
+ *   divide), b = 0.5 (b == NULL) or b[r] (DEVICE [R]: one jitter per ray, in [0, 1)); k = clamp(#{c <= u} - 1, 0, S-1),
+ *   frac = c[k+1] > c[k] ? clamp((u - c[k]) / (c[k+1] - c[k]), 0, 1) : 0, x_i = v[k] + frac (v[k+1] - v[k]).  Edges:
+ *   e_j = (x_{j-1} + x_j) / 2 inside, e_0 = max(2 x_0 - e_1, v[0]), e_n = min(2 x_{n-1} - e_{n-1}, v[S]); n == 1:
+ *   (v[0], v[S]).  s_edges [R, n+1]; centres [R, n] (may be NULL); with transform FSN_STOT_UNIFORM, t = s far +
+ *   (1 - s) near, or FSN_STOT_LINDISP, t = 1 / (s (1/far) + (1 - s) (1/near)), t_edges [R, n+1] = the transformed
+ *   s_edges (FSN_STOT_NONE: t_edges is not written).  A cdf that is not monotone is outside the contract: the kernel
+ *   still reads and writes its own rows only and returns finite values inside [v[0], v[S]], not necessarily sorted.
+ * fsn_prop_resample: the step between two proposal evaluations in one launch: cdfs [R, S+1] = 1 - (T_0 .. T_{S-1}, 0),
+ *   T the transmittance of sigmas [R, S] on the intervals t_edges [R, S+1] (the values of fsn_packed_weights_fwd on
+ *   t_starts = t_edges[:, :-1], t_ends = t_edges[:, 1:], bit for bit), then fsn_importance_sample on (s_edges, cdfs),
+ *   bit for bit.
+ * fsn_searchsorted_dense: keys [R, K] sorted per row, values [R, Q]; with h = #{key <= q}: ids_left = max(h - 1, 0),
+ *   ids_right = min(h, K - 1), int64 [R, Q] (inside the range key[ids_left] <= q < key[ids_right]; below the first key
+ *   both 0, at or beyond the last both K - 1).
+ * fsn_prop_loss_fwd: the interlevel loss of query intervals q_edges / q_cdfs [R, n+1] against a proposal's k_edges /
+ *   k_cdfs [R, S+1] (both in s-space, sorted): w_i = cq[i+1] - cq[i], wo_i = ck[ids_right(q[i+1])] - ck[ids_left(q[i])],
+ *   loss [R, n] = max(w_i - wo_i, 0)^2 / (w_i + 1e-7) where w_i > 0, else 0.
+ * fsn_prop_loss_bwd: d_k_cdfs [R, S+1] from d_loss [R, n] (the query side carries no gradient): coef_i =
+ *   -2 max(w_i - wo_i, 0) / (w_i + 1e-7) d_loss_i, d_ck[m] = sum of coef_i over ids_right(q[i+1]) == m minus the sum over
+ *   ids_left(q[i]) == m, each one run of the sorted queries, summed in ascending i.
+ * FSN_E_INVALID: null pointers, S < 1, n < 1, K < 1, near <= 0 or far <= 0 with FSN_STOT_LINDISP.  FSN_E_UNSUPPORTED:
+ *   the sampler and loss kernels hold a ray's rows in LDS, S and n <= FSN_PROP_MAX_ROW each.  R == 0: FSN_OK, no launch. */
+#define FSN_PROP_MAX_ROW 1024
+#define FSN_STOT_NONE 0
+#define FSN_STOT_UNIFORM 1
+#define FSN_STOT_LINDISP 2
+int fsn_importance_sample(const float* vals, const float* cdfs, int64_t R, int S, int n, const float* b, int transform,
+                          float near, float far, float* s_edges, float* centres, float* t_edges, fsn_stream_t stream);
+int fsn_prop_resample(const float* s_edges, const float* t_edges, const float* sigmas, int64_t R, int S, int n,
+                      const float* b, int transform, float near, float far, float* cdfs, float* s_out, float* centres,
+                      float* t_out, fsn_stream_t stream);
+int fsn_searchsorted_dense(const float* keys, const float* values, int64_t R, int K, int Q, int64_t* ids_left,
+                           int64_t* ids_right, fsn_stream_t stream);
+int fsn_prop_loss_fwd(const float* q_edges, const float* q_cdfs, const float* k_edges, const float* k_cdfs, int64_t R,
+                      int n, int S, float* loss, fsn_stream_t stream);
+int fsn_prop_loss_bwd(const float* q_edges, const float* q_cdfs, const float* k_edges, const float* k_cdfs,
+                      const float* d_loss, int64_t R, int n, int S, float* d_k_cdfs, fsn_stream_t stream);
+
 /* f1: optimizer side of the training step on ONE flat float32 parameter arena (run-nerf.py:217, 266-285).
  * fsn_adam_step: torch.optim.Adam's update (no amsgrad), operation for operation in float32, one launch over the
  *   arena: params / grads / exp_avg / exp_avg_sq [n]; `step` = 1, 2, ... (bias corrections are formed in double on
