@@ -8,7 +8,6 @@ import ctypes as C
 import torch
 from torch import Tensor
 
-from .. import _lib as L
 from .. import ops
 
 
@@ -50,14 +49,10 @@ class _WeightNormFn(torch.autograd.Function):
         flat, offs, lens = reg._arena(params)
         n = len(offs)
         off_t, len_t = (C.c_int64 * n)(*offs), (C.c_int64 * n)(*lens)
-        nws = L.lib().fsn_weight_norm_workspace_floats(n, len_t)
-        if nws < 0:
-            L.check(int(nws), "fsn_weight_norm_workspace_floats")
-        ws = torch.empty(int(nws), device=flat.device, dtype=torch.float32)
+        nws = ops._size("fsn_weight_norm_workspace_floats", None, n, len_t)
+        ws = torch.empty(nws, device=flat.device, dtype=torch.float32)
         out = torch.empty(1, device=flat.device, dtype=torch.float32)
-        with torch.cuda.device(flat.device):
-            L.check(L.lib().fsn_weight_norm_fwd(ops._p(flat), n, off_t, len_t, int(reg.l2), ops._p(ws), ops._p(out),
-                                                ops._stream()), "fsn_weight_norm_fwd")
+        ops._launch("fsn_weight_norm_fwd", flat.device, ops._p(flat), n, off_t, len_t, int(reg.l2), ops._p(ws), ops._p(out))
         ctx.reg, ctx.flat, ctx.ws, ctx.tabs, ctx.shapes = reg, flat, ws, (n, off_t, len_t, offs, lens), [p.shape for p in params]
         return out.reshape(())
 
@@ -67,9 +62,8 @@ class _WeightNormFn(torch.autograd.Function):
         flat = ctx.flat
         g = torch.zeros_like(flat)
         d = d_out.reshape(1).to(torch.float32).contiguous()
-        with torch.cuda.device(flat.device):
-            L.check(L.lib().fsn_weight_norm_bwd(ops._p(flat), n, off_t, len_t, int(ctx.reg.l2), ops._p(ctx.ws), ops._p(d),
-                                                ops._p(g), ops._stream()), "fsn_weight_norm_bwd")
+        ops._launch("fsn_weight_norm_bwd", flat.device, ops._p(flat), n, off_t, len_t, int(ctx.reg.l2), ops._p(ctx.ws),
+                    ops._p(d), ops._p(g))
         return (None,) + tuple(g[o:o + ln].view(sh) for o, ln, sh in zip(offs, lens, ctx.shapes))
 
 

@@ -24,7 +24,6 @@ from typing import Iterable, List, Optional
 import torch
 from torch import Tensor
 
-from .. import _lib as L
 from .. import ops
 from ..shard import FlatGrads
 
@@ -110,12 +109,10 @@ class FusedAdam(torch.optim.Optimizer):
         self.arena.grads.bind()
         a = self.arena
         flag = a.grads.step_flag  # the word of THIS optimizer's parameters (shard.FlatGrads), not a per-device one
-        with torch.cuda.device(a.flat.device):
-            L.check(L.lib().fsn_adam_step_dev(ops._p(a.flat), ops._p(a.grads.flat), ops._p(self.exp_avg),
-                                              ops._p(self.exp_avg_sq), a.numel, ops._p(self.step_count), ops._p(self._tick),
-                                              float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
-                                              float(g["weight_decay"]), float(grad_div), ops._p(flag),
-                                              ops._p(a.grads.flag_slot), ops._stream()), "fsn_adam_step_dev")
+        ops._launch("fsn_adam_step_dev", a.flat.device, ops._p(a.flat), ops._p(a.grads.flat), ops._p(self.exp_avg),
+                    ops._p(self.exp_avg_sq), a.numel, ops._p(self.step_count), ops._p(self._tick), float(g["lr"]),
+                    float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), float(grad_div),
+                    ops._p(flag), ops._p(a.grads.flag_slot))
         flag.zero_()  # the step's flag is consumed (stream order: after the launch that read it)
         a.grads.flag_slot.zero_()
         self._bump_versions()

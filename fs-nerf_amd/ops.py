@@ -1,6 +1,10 @@
 """Tensor-level wrappers over the C-ABI (include/fsnerf_hip.h).  Every function here launches
 HIP kernels on the current torch stream; inputs must live on the GPU (float32, contiguous).
-No function in this module computes anything on the CPU."""
+No function in this module computes anything on the CPU.
+
+A wrapper has one shape: convert the inputs, allocate the outputs, `_launch(symbol, device, *args)`.  `_launch` is the one
+door to a C entry point that takes a stream, `_size` the door of the size queries, `_Held` the argument struct that owns
+its tensors (DESIGN.md section 1 has the two rules they enforce)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -17,12 +21,83 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+# profiling hook (bench.py): a list -> every render_fused / render_occ_fused launch appends a pair of HIP events recorded
+# on the launch stream right around the C-ABI call (the kernel's own duration, without the host path around it)
+launch_timer: Optional[list] = None
+# measurement hook (bench.py): a uint64 [2] device tensor -> every render_fused launch adds its (s_memtime, s_memrealtime)
+# differences to it (fsn_render_args.clock_out): the clock the chip held during the launches
+clock_buffer: Optional[Tensor] = None
+
+
+def _launch(name: str, dev, *args, what: Optional[str] = None, timed: bool = False, counts: bool = False) -> int:
+    """The one door to a C entry point that takes a stream: `name(*args, stream)` under the device guard of `dev` (the
+    tensors' device), with the stream handle read INSIDE the guard - outside it the handle is the current device's, not
+    theirs.  `what`: the error's text where it says more than the symbol.  `timed`: the `launch_timer` bracket.
+    `counts`: the symbol returns a count (> 0) instead of a status code; -> that value."""
+    fn = getattr(L.lib(), name)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        if timed and launch_timer is not None:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            rc = fn(*args, stream)
+            e1.record()
+            launch_timer.append((e0, e1))
+        else:
+            rc = fn(*args, stream)
+    if counts:
+        if rc <= 0:
+            L.check(rc if rc < 0 else -3, what or name)
+    elif rc != 0:
+        L.check(rc, what or name)
+    return rc
+
+
+def _size(name: str, dev, *args) -> int:
+    """The door of the size queries (workspace floats / doubles, blob bytes, compute units): -> the size; a negative
+    value is an error code and raises.  `dev`: the device the answer is for (fsn_nerf_train_workspace_floats looks at
+    its compute units), None where the arguments alone decide."""
+    fn = getattr(L.lib(), name)
+    if dev is None:
+        n = int(fn(*args))
+    else:
+        with torch.cuda.device(dev):
+            n = int(fn(*args))
+    if n < 0:
+        L.check(n, name)
+    return n
+
+
 def _f32(t: Tensor, name: str) -> Tensor:
     if not t.is_cuda:
         raise RuntimeError(f"{name}: expected a GPU tensor (the HIP path has no CPU fallback)")
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
+
+
+def _opt_f32(t: Optional[Tensor], name: str) -> Optional[Tensor]:
+    return None if t is None else _f32(t, name)
+
+
+def _gpu_f32(t: Tensor, name: str) -> Tensor:
+    """The packed primitives take GPU float32 as it is: nothing is cast (a cast would hide from autograd)."""
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: expected a GPU tensor (the HIP path has no CPU fallback)")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name}: expected float32, got {t.dtype}")
+    return t.contiguous()
+
+
+def _flat(t: Optional[Tensor], name: str, n: int, cast: bool = False) -> Optional[Tensor]:
+    """An optional tensor of `n` values, flat.  Two policies that stay apart: `_gpu_f32` (float32 or an error) and,
+    with `cast`, `_f32` (any dtype, converted)."""
+    if t is None:
+        return None
+    t = (_f32 if cast else _gpu_f32)(t, name).reshape(-1)
+    if t.numel() != n:
+        raise ValueError(f"{name}: expected {n} values, got {t.numel()}")
+    return t
 
 
 def _i64(t: Tensor, name: str) -> Tensor:
@@ -46,6 +121,49 @@ def _bk(bkgd) -> Optional[C.Array]:
     return (C.c_float * 3)(*vals)
 
 
+class _Held:
+    """An argument struct `a` and the tensors its pointers name.  A tensor a conversion made (`_f32` of a float64 mask,
+    a reshaped `u`) must stay referenced until the call is enqueued: the outputs are allocated after it, and the caching
+    allocator hands a dropped temporary's block to the next torch.empty of its size class.  So a pointer enters the
+    struct (`set`) or the argument list (`p`) only through the holder, which the wrapper keeps until it returns."""
+
+    def __init__(self, a: C.Structure):
+        self.a, self.tensors = a, []
+
+    def set(self, field: str, t: Optional[Tensor]) -> None:
+        if t is not None:
+            self.tensors.append(t)
+            setattr(self.a, field, t.data_ptr())
+
+    def p(self, t: Optional[Tensor]):
+        self.tensors.append(t)
+        return _p(t)
+
+
+def _ray_source(h: _Held, rays_o: Optional[Tensor], rays_d: Optional[Tensor], camera) -> Tuple[int, torch.device]:
+    """Ray tensors, or `camera` = (pose [3or4,4], H, W, focal, row0, nrows, device): the rays of the image rows
+    [row0, row0+nrows) are generated inside the launch.  Fills R and rays_o / rays_d or cam_* -> (R, device)."""
+    a = h.a
+    if camera is None:
+        o, d = _f32(rays_o, "rays_o").reshape(-1, 3), _f32(rays_d, "rays_d").reshape(-1, 3)
+        a.R = o.shape[0]
+        h.set("rays_o", o)
+        h.set("rays_d", d)
+        return o.shape[0], o.device
+    pose, cH, cW, cfocal, crow0, cnrows, dev = camera
+    a.R = int(cnrows) * int(cW)
+    pm = pose.detach().to("cpu", torch.float32)[:3, :4].contiguous().reshape(-1).tolist()
+    for i in range(12):
+        a.cam_pose[i] = pm[i]
+    a.cam_H, a.cam_W, a.cam_row0, a.cam_focal = int(cH), int(cW), int(crow0), float(cfocal)
+    return a.R, torch.device(dev)
+
+
+def _masks(h: _Held, pos_mask: Optional[Tensor], dir_mask: Optional[Tensor]) -> None:
+    h.set("pos_mask", _opt_f32(pos_mask, "pos_mask"))
+    h.set("dir_mask", _opt_f32(dir_mask, "dir_mask"))
+
+
 # ------------------------------------------------------------------ rays
 def get_rays(pose: Tensor, H: int, W: int, focal: float, device, row0: int = 0,
              nrows: Optional[int] = None, out: Optional[Tuple[Tensor, Tensor]] = None) -> Tuple[Tensor, Tensor]:
@@ -59,9 +177,7 @@ def get_rays(pose: Tensor, H: int, W: int, focal: float, device, row0: int = 0,
     else:
         o, d = out
         assert o.is_contiguous() and d.is_contiguous() and o.shape == (nrows * W, 3) and d.shape == o.shape
-    with torch.cuda.device(o.device):
-        L.check(L.lib().fsn_get_rays(pose_host, H, W, float(focal), row0, nrows, _p(o), _p(d), _stream()),
-                "fsn_get_rays")
+    _launch("fsn_get_rays", o.device, pose_host, H, W, float(focal), row0, nrows, _p(o), _p(d))
     return o, d
 
 
@@ -76,9 +192,8 @@ def build_rays(poses: Tensor, H: int, W: int, focal: float, device, ndc: bool = 
     d = torch.empty_like(o)
     aabb = torch.empty(6, device=P.device, dtype=torch.float32) if want_aabb else None
     keys = torch.empty(6, device=P.device, dtype=torch.int32) if want_aabb else None
-    with torch.cuda.device(P.device):
-        L.check(L.lib().fsn_build_rays(_p(P), n, int(H), int(W), float(focal), 1 if ndc else 0, float(near), _p(o), _p(d),
-                                       _p(aabb), _p(keys), _stream()), "fsn_build_rays")
+    _launch("fsn_build_rays", P.device, _p(P), n, int(H), int(W), float(focal), 1 if ndc else 0, float(near), _p(o), _p(d),
+            _p(aabb), _p(keys))
     return o, d, aabb
 
 
@@ -108,17 +223,15 @@ def ray_batch(poses12: Tensor, images: Tensor, H: int, W: int, focal: float, *, 
     d = torch.empty(count, 3, device=dev, dtype=torch.float32) if want_rays else None
     rgb = torch.empty(count, 3, device=dev, dtype=torch.float32) if want_rgb else None
     index = torch.empty(count, device=dev, dtype=torch.int64) if want_index else None
-    with torch.cuda.device(dev):
-        L.check(L.lib().fsn_ray_batch(_p(poses12), poses12.shape[0], _p(images), int(H), int(W), images.shape[3], float(focal),
-                                      1 if ndc else 0, float(near), 1 if white_bkgd else 0, _RAY_ORDERS[order],
-                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), _p(indices), int(start), int(count),
-                                      _p(o), _p(d), _p(rgb), _p(index), _stream()), "fsn_ray_batch")
+    _launch("fsn_ray_batch", dev, _p(poses12), poses12.shape[0], _p(images), int(H), int(W), images.shape[3], float(focal),
+            1 if ndc else 0, float(near), 1 if white_bkgd else 0, _RAY_ORDERS[order], int(seed) & 0xFFFFFFFFFFFFFFFF,
+            int(epoch), _p(indices), int(start), int(count), _p(o), _p(d), _p(rgb), _p(index))
     return o, d, rgb, index
 
 
 def ray_perm_host(n: int, seed: int, epoch: int, start: int = 0, count: Optional[int] = None) -> Tensor:
     """Positions [start, start + count) of the epoch permutation of [0, n) as a CPU int64 tensor (fsn_ray_perm_host: the
-    kernel's own function compiled for the host; no device is touched)."""
+    kernel's own function compiled for the host; no device is touched, so it takes no stream and needs no door)."""
     count = n - start if count is None else count
     out = torch.empty(max(count, 0), dtype=torch.int64)
     L.check(L.lib().fsn_ray_perm_host(int(n), int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), int(start), int(count),
@@ -130,9 +243,7 @@ def to_ndc(rays_o: Tensor, rays_d: Tensor, H: int, W: int, focal: float, near: f
     o, d = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d")
     n = o.numel() // 3
     no, nd = torch.empty_like(o), torch.empty_like(d)
-    with torch.cuda.device(o.device):
-        L.check(L.lib().fsn_to_ndc(_p(o), _p(d), n, H, W, float(focal), float(near), _p(no), _p(nd), _stream()),
-                "fsn_to_ndc")
+    _launch("fsn_to_ndc", o.device, _p(o), _p(d), n, H, W, float(focal), float(near), _p(no), _p(nd))
     return no, nd
 
 
@@ -143,9 +254,8 @@ def posenc(x: Tensor, freqs: Sequence[float], mask: Optional[Tensor] = None) -> 
     nf = len(freqs)
     out = torch.empty(*x.shape[:-1], d_in * (1 + 2 * nf), device=x.device, dtype=torch.float32)
     fr = (C.c_float * max(nf, 1))(*[float(f) for f in freqs])
-    m = None if mask is None else _f32(mask, "mask")
-    with torch.cuda.device(x.device):
-        L.check(L.lib().fsn_posenc_fwd(_p(x), n, d_in, nf, fr, _p(m), _p(out), _stream()), "fsn_posenc_fwd")
+    m = _opt_f32(mask, "mask")
+    _launch("fsn_posenc_fwd", x.device, _p(x), n, d_in, nf, fr, _p(m), _p(out))
     return out
 
 
@@ -164,9 +274,7 @@ def _u_mode(u: Optional[Tensor], R: int, S: int) -> Tuple[int, Optional[Tensor]]
 def stratified_edges(near: float, far: float, S: int, R: int, u: Optional[Tensor], device) -> Tensor:
     mode, u = _u_mode(u, R, S)
     edges = torch.empty(R, S + 1, device=device, dtype=torch.float32)
-    with torch.cuda.device(edges.device):
-        L.check(L.lib().fsn_stratified_edges(float(near), float(far), S, R, _p(u), mode, _p(edges), _stream()),
-                "fsn_stratified_edges")
+    _launch("fsn_stratified_edges", edges.device, float(near), float(far), S, R, _p(u), mode, _p(edges))
     return edges
 
 
@@ -176,9 +284,7 @@ def edges_to_packed(edges: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
     ri = torch.empty(R * S, device=edges.device, dtype=torch.int64)
     t0 = torch.empty(R * S, device=edges.device, dtype=torch.float32)
     t1 = torch.empty_like(t0)
-    with torch.cuda.device(edges.device):
-        L.check(L.lib().fsn_edges_to_packed(_p(edges), R, S, _p(ri), _p(t0), _p(t1), _stream()),
-                "fsn_edges_to_packed")
+    _launch("fsn_edges_to_packed", edges.device, _p(edges), R, S, _p(ri), _p(t0), _p(t1))
     return ri, t0, t1
 
 
@@ -186,11 +292,9 @@ def sample_pdf_merge(edges: Tensor, weights: Tensor, n_imp: int, u: Optional[Ten
     edges, weights = _f32(edges, "edges"), _f32(weights, "weights")
     R, S = weights.shape
     assert edges.shape == (R, S + 1)
-    u = None if u is None else _f32(u, "u")
+    u = _opt_f32(u, "u")
     out = torch.empty(R, S + 1 + n_imp, device=edges.device, dtype=torch.float32)
-    with torch.cuda.device(edges.device):
-        L.check(L.lib().fsn_sample_pdf_merge(_p(edges), _p(weights), R, S, n_imp, _p(u), _p(out), _stream()),
-                "fsn_sample_pdf_merge")
+    _launch("fsn_sample_pdf_merge", edges.device, _p(edges), _p(weights), R, S, n_imp, _p(u), _p(out))
     return out
 
 
@@ -207,9 +311,8 @@ def composite(sigmas: Tensor, rgbs: Tensor, t_starts: Tensor, t_ends: Tensor, bk
     w = torch.empty(R, S, device=dev) if extras else None
     a = torch.empty(R, S, device=dev) if extras else None
     tr = torch.empty(R, S, device=dev) if extras else None
-    with torch.cuda.device(dev):
-        L.check(L.lib().fsn_composite_fwd(_p(sig), _p(rgb), _p(t0), _p(t1), R, S, _bk(bkgd), _p(colors), _p(opacity),
-                                          _p(depth), _p(w), _p(a), _p(tr), _stream()), "fsn_composite_fwd")
+    _launch("fsn_composite_fwd", dev, _p(sig), _p(rgb), _p(t0), _p(t1), R, S, _bk(bkgd), _p(colors), _p(opacity), _p(depth),
+            _p(w), _p(a), _p(tr))
     ex = {"weights": w, "alphas": a, "trans": tr, "sigmas": sig, "rgbs": rgb} if extras else {}
     return colors, opacity, depth, ex
 
@@ -225,32 +328,34 @@ def composite_packed(sigmas: Tensor, rgbs: Tensor, t_starts: Tensor, t_ends: Ten
     opacity = torch.empty(n_rays, 1, device=dev)
     depth = torch.empty(n_rays, 1, device=dev)
     w, a, tr = (torch.empty(N, device=dev) for _ in range(3))
-    with torch.cuda.device(dev):
-        L.check(L.lib().fsn_composite_packed_fwd(_p(sig), _p(rgb), _p(t0), _p(t1), _p(ri), N, n_rays, _bk(bkgd),
-                                                 _p(colors), _p(opacity), _p(depth), _p(w), _p(a), _p(tr), _stream()),
-                "fsn_composite_packed_fwd")
+    _launch("fsn_composite_packed_fwd", dev, _p(sig), _p(rgb), _p(t0), _p(t1), _p(ri), N, n_rays, _bk(bkgd), _p(colors),
+            _p(opacity), _p(depth), _p(w), _p(a), _p(tr))
     return colors, opacity, depth, {"weights": w, "alphas": a, "trans": tr, "sigmas": sig, "rgbs": rgb}
 
 
 # ------------------------------------------------------------------ MLP
 SD_ORDER_TAIL = ("sigma", "connection", "branch", "rgb")
 
-# Range guard of the fp16 modes (include/fsnerf_hip.h, FSN_STATUS_FP16_RANGE): one sticky device word per GPU that
-# every MLP launch of this process reports into.
-_status_words: Dict[torch.device, Tensor] = {}
 
-
-def status_word(device) -> Tensor:
+def _device_word(cache: Dict[torch.device, Tensor], device) -> Tensor:
+    """One zero-initialised int32 word per GPU in `cache`, made on first use."""
     device = torch.device(device)
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    w = _status_words.get(device)
+    w = cache.get(device)
     if w is None:
-        w = _status_words[device] = torch.zeros(1, dtype=torch.int32, device=device)
+        w = cache[device] = torch.zeros(1, dtype=torch.int32, device=device)
     return w
 
 
+# Range guard of the fp16 modes (include/fsnerf_hip.h, FSN_STATUS_FP16_RANGE): one sticky device word per GPU that
+# every MLP launch of this process reports into.
+_status_words: Dict[torch.device, Tensor] = {}
 _step_flags: Dict[torch.device, Tensor] = {}
+
+
+def status_word(device) -> Tensor:
+    return _device_word(_status_words, device)
 
 
 def step_flag(device) -> Tensor:
@@ -258,13 +363,7 @@ def step_flag(device) -> Tensor:
     optimizers): a NeRF backward ORs its per-call range word into it (device op).  Parameters in a `shard.FlatGrads`
     bucket (`FusedAdam`) report into the bucket's own `step_flag` instead, which that optimizer hands to its
     Adam launch (bit 0 / bit 2 set: the update is skipped on the device) and clears.  Never read by the host."""
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    w = _step_flags.get(device)
-    if w is None:
-        w = _step_flags[device] = torch.zeros(1, dtype=torch.int32, device=device)
-    return w
+    return _device_word(_step_flags, device)
 
 
 def range_flags(device) -> int:
@@ -356,10 +455,7 @@ class PackedMLP:
 
     def __init__(self, desc: L.MlpDesc, prec: int, device):
         self.desc, self.prec = desc, prec
-        nbytes = L.lib().fsn_mlp_blob_bytes(C.byref(desc), prec)
-        if nbytes < 0:
-            L.check(int(nbytes), "fsn_mlp_blob_bytes")
-        self.blob = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+        self.blob = torch.empty(_size("fsn_mlp_blob_bytes", None, C.byref(desc), prec), dtype=torch.uint8, device=device)
 
     def pack(self, weights: Sequence[Tensor], biases: Sequence[Tensor], exps: Optional[Sequence[int]] = None) -> "PackedMLP":
         """`exps`: n_layers + 2 per-GEMM activation exponents (fsn_mlp_pack_scaled: the blob then holds the network whose
@@ -368,16 +464,13 @@ class PackedMLP:
         assert len(weights) == n and len(biases) == n
         ws = [_f32(w.detach(), "weight") for w in weights]
         bs = [_f32(b.detach(), "bias") for b in biases]
-        Wp = (C.c_void_p * n)(*[w.data_ptr() for w in ws])
-        Bp = (C.c_void_p * n)(*[b.data_ptr() for b in bs])
         ex = None
         if exps is not None:
             assert len(exps) == self.desc.n_layers + 2
             ex = (C.c_int32 * len(exps))(*[int(e) for e in exps])
         self.exps = None if exps is None else tuple(int(e) for e in exps)
-        with torch.cuda.device(self.blob.device):
-            L.check(L.lib().fsn_mlp_pack_scaled(C.byref(self.desc), self.prec, Wp, Bp, ex, _p(self.blob), _stream()),
-                    "fsn_mlp_pack_scaled")
+        _launch("fsn_mlp_pack_scaled", self.blob.device, C.byref(self.desc), self.prec, _ptr_array(ws), _ptr_array(bs), ex,
+                _p(self.blob))
         self._keep = (ws, bs)  # alive until the stream work is queued behind later launches
         return self
 
@@ -388,13 +481,11 @@ def mlp_layer_maxima(pm: PackedMLP, x: Tensor, dirs: Tensor, pos_mask: Optional[
     float32 [n_layers + 2] on the device, in the scale of the blob `pm`.  `out`: accumulate into an earlier result."""
     x, d = _f32(x, "x").reshape(-1, 3), _f32(dirs, "dirs").reshape(-1, 3)
     assert x.shape == d.shape
-    pmk = None if pos_mask is None else _f32(pos_mask, "pos_mask")
-    dmk = None if dir_mask is None else _f32(dir_mask, "dir_mask")
+    pmk, dmk = _opt_f32(pos_mask, "pos_mask"), _opt_f32(dir_mask, "dir_mask")
     if out is None:
         out = torch.zeros(pm.desc.n_layers + 2, device=x.device, dtype=torch.float32)
-    with torch.cuda.device(x.device):
-        L.check(L.lib().fsn_mlp_layer_maxima(C.byref(pm.desc), pm.prec, _p(pm.blob), _p(x), _p(d), _p(pmk), _p(dmk),
-                                             x.shape[0], _p(out), _stream()), "fsn_mlp_layer_maxima")
+    _launch("fsn_mlp_layer_maxima", x.device, C.byref(pm.desc), pm.prec, _p(pm.blob), _p(x), _p(d), _p(pmk), _p(dmk),
+            x.shape[0], _p(out))
     return out
 
 
@@ -403,22 +494,13 @@ def mlp_fwd(pm: PackedMLP, x: Tensor, dirs: Optional[Tensor] = None, pos_mask: O
     x = _f32(x, "x")
     lead = x.shape[:-1]
     n = x.numel() // 3
-    d = None if dirs is None else _f32(dirs, "dirs")
-    pmk = None if pos_mask is None else _f32(pos_mask, "pos_mask")
-    dmk = None if dir_mask is None else _f32(dir_mask, "dir_mask")
+    d = _opt_f32(dirs, "dirs")
+    pmk, dmk = _opt_f32(pos_mask, "pos_mask"), _opt_f32(dir_mask, "dir_mask")
     out = torch.empty(*lead, 4 if d is not None else 1, device=x.device, dtype=torch.float32)
-    with torch.cuda.device(x.device):
-        L.check(L.lib().fsn_mlp_fwd(C.byref(pm.desc), pm.prec, _p(pm.blob), _p(x), _p(d), _p(pmk), _p(dmk), n,
-                                    _p(out), _p(status_word(x.device)), _stream()), "fsn_mlp_fwd")
+    _launch("fsn_mlp_fwd", x.device, C.byref(pm.desc), pm.prec, _p(pm.blob), _p(x), _p(d), _p(pmk), _p(dmk), n, _p(out),
+            _p(status_word(x.device)))
     return out
 
-
-# profiling hook (bench.py): a list -> every render_fused launch appends a pair of HIP events recorded on the launch
-# stream right around the C-ABI call (the kernel's own duration, without the host path around it)
-launch_timer: Optional[list] = None
-# measurement hook (bench.py): a uint64 [2] device tensor -> every render_fused launch adds its (s_memtime, s_memrealtime)
-# differences to it (fsn_render_args.clock_out): the clock the chip held during the launches
-clock_buffer: Optional[Tensor] = None
 
 def mlp_fwd_rays(pm: PackedMLP, rays_o: Tensor, rays_d: Tensor, ray_indices: Tensor, t_starts: Tensor, t_ends: Tensor,
                  full: bool, pos_mask: Optional[Tensor] = None, dir_mask: Optional[Tensor] = None) -> Tensor:
@@ -427,13 +509,10 @@ def mlp_fwd_rays(pm: PackedMLP, rays_o: Tensor, rays_d: Tensor, ray_indices: Ten
     o, d = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d")
     ri, t0, t1 = _i64(ray_indices, "ray_indices"), _f32(t_starts, "t_starts"), _f32(t_ends, "t_ends")
     n = ri.numel()
-    pmk = None if pos_mask is None else _f32(pos_mask, "pos_mask")
-    dmk = None if dir_mask is None else _f32(dir_mask, "dir_mask")
+    pmk, dmk = _opt_f32(pos_mask, "pos_mask"), _opt_f32(dir_mask, "dir_mask")
     out = torch.empty(n, 4 if full else 1, device=o.device, dtype=torch.float32)
-    with torch.cuda.device(o.device):
-        L.check(L.lib().fsn_mlp_fwd_rays(C.byref(pm.desc), pm.prec, _p(pm.blob), _p(o), _p(d), _p(ri), _p(t0), _p(t1),
-                                         1 if full else 0, _p(pmk), _p(dmk), n, _p(out), _p(status_word(o.device)),
-                                         _stream()), "fsn_mlp_fwd_rays")
+    _launch("fsn_mlp_fwd_rays", o.device, C.byref(pm.desc), pm.prec, _p(pm.blob), _p(o), _p(d), _p(ri), _p(t0), _p(t1),
+            1 if full else 0, _p(pmk), _p(dmk), n, _p(out), _p(status_word(o.device)))
     return out
 
 
@@ -448,6 +527,24 @@ def _edges_workspace(dev, n: int) -> Tensor:
     if w is None or w.numel() < n:
         w = _edges_ws[(dev, 0)] = torch.empty(n, device=dev, dtype=torch.float32)
     return w
+
+
+def _render_args(rays_o: Optional[Tensor], rays_d: Optional[Tensor], camera, near: float, far: float, S: int, NI: int,
+                 u: Optional[Tensor], u_fine: Optional[Tensor], pos_mask: Optional[Tensor],
+                 dir_mask: Optional[Tensor]) -> Tuple[_Held, int, torch.device]:
+    """The inputs of fsn_render_rays_fused (rays or camera, range, jitter, masks) -> (held RenderArgs, R, device)."""
+    h = _Held(L.RenderArgs())
+    a = h.a
+    R, dev = _ray_source(h, rays_o, rays_d, camera)
+    mode, u = _u_mode(u, R, S)
+    a.near, a.far, a.S, a.n_imp, a.u_mode = float(near), float(far), S, NI, mode
+    h.set("u", u)
+    if u_fine is not None:
+        u_fine = _f32(u_fine, "u_fine")
+        assert tuple(u_fine.shape) == (R, NI)
+        h.set("u_fine", u_fine)
+    _masks(h, pos_mask, dir_mask)
+    return h, R, dev
 
 
 def render_fused(pm_coarse: Optional[PackedMLP], pm_fine: PackedMLP, rays_o: Optional[Tensor], rays_d: Optional[Tensor], *,
@@ -465,37 +562,8 @@ def render_fused(pm_coarse: Optional[PackedMLP], pm_fine: PackedMLP, rays_o: Opt
     one long one, half the register spills); same results, 3 % faster on the 800x800 frame (A/B on one device)."""
     S, NI = n_samples, n_importance
     So = S + NI
-    if camera is not None:
-        pose, cH, cW, cfocal, crow0, cnrows, dev = camera
-        dev = torch.device(dev)
-        R = int(cnrows) * int(cW)
-        o = d = None
-    else:
-        o, d = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d")
-        R = o.shape[0]
-        dev = o.device
-    mode, u = _u_mode(u, R, S)
-    a = L.RenderArgs()
-    a.R = R
-    if camera is None:
-        a.rays_o, a.rays_d = o.data_ptr(), d.data_ptr()
-    else:
-        pm = pose.detach().to("cpu", torch.float32)[:3, :4].contiguous().reshape(-1).tolist()
-        for i in range(12):
-            a.cam_pose[i] = pm[i]
-        a.cam_H, a.cam_W, a.cam_row0, a.cam_focal = int(cH), int(cW), int(crow0), float(cfocal)
-    a.near, a.far, a.S, a.n_imp, a.u_mode = float(near), float(far), S, NI, mode
-    keep = [o, d, u]
-    a.u = None if u is None else u.data_ptr()
-    if u_fine is not None:
-        u_fine = _f32(u_fine, "u_fine")
-        assert tuple(u_fine.shape) == (R, NI)
-        a.u_fine = u_fine.data_ptr()
-    for name, m in (("pos_mask", pos_mask), ("dir_mask", dir_mask)):
-        if m is not None:
-            m = _f32(m, name)
-            keep.append(m)
-            setattr(a, name, m.data_ptr())
+    h, R, dev = _render_args(rays_o, rays_d, camera, near, far, S, NI, u, u_fine, pos_mask, dir_mask)
+    a = h.a
     for i in range(3):
         a.bkgd[i] = float(bkgd[i])
     colors = torch.empty(R, 3, device=dev)
@@ -517,8 +585,7 @@ def render_fused(pm_coarse: Optional[PackedMLP], pm_fine: PackedMLP, rays_o: Opt
         two_phase = NI > 0 and R >= 65536
     if two_phase and NI > 0:
         if "edges" not in ex:
-            keep.append(_edges_workspace(dev, R * (So + 1)))
-            a.edges_out = keep[-1].data_ptr()
+            h.set("edges_out", _edges_workspace(dev, R * (So + 1)))
         a.two_phase = 1
     if NI > 0 and pm_coarse is None:
         pm_coarse = pm_fine
@@ -527,16 +594,8 @@ def render_fused(pm_coarse: Optional[PackedMLP], pm_fine: PackedMLP, rays_o: Opt
     a.status = status_word(dev).data_ptr()
     if clock_buffer is not None:
         a.clock_out = clock_buffer.data_ptr()
-    with torch.cuda.device(dev):
-        if launch_timer is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        L.check(L.lib().fsn_render_rays_fused(C.byref(pm_fine.desc), pm_fine.prec,
-                                              _p(pm_coarse.blob) if pm_coarse is not None else None,
-                                              _p(pm_fine.blob), C.byref(a), _stream()), "fsn_render_rays_fused")
-        if launch_timer is not None:
-            e1.record()
-            launch_timer.append((e0, e1))
+    _launch("fsn_render_rays_fused", dev, C.byref(pm_fine.desc), pm_fine.prec,
+            _p(pm_coarse.blob) if pm_coarse is not None else None, _p(pm_fine.blob), C.byref(a), timed=True)
     return colors, opacity, depth, ex
 
 
@@ -545,13 +604,9 @@ def bench_bare_stream(pm: PackedMLP, layers: int) -> Tuple[int, Tensor]:
     render kernels' own GEMM code, the weight stream walking the hidden phases of `pm`'s blob.  -> (workgroups launched,
     uint64 [workgroups * 8, 2] per-wave (s_memtime, s_memrealtime) differences around the loop)."""
     dev = pm.blob.device
-    with torch.cuda.device(dev):
-        n = L.lib().fsn_device_cus()
-        clk = torch.zeros(max(n, 1) * 8, 2, dtype=torch.int64, device=dev)
-        rc = L.lib().fsn_bench_bare_stream(C.byref(pm.desc), pm.prec, _p(pm.blob), int(layers), _p(clk), _stream())
-        if rc <= 0:
-            L.check(rc if rc < 0 else -3, "fsn_bench_bare_stream")
-    return rc, clk
+    clk = torch.zeros(max(_size("fsn_device_cus", dev), 1) * 8, 2, dtype=torch.int64, device=dev)
+    n = _launch("fsn_bench_bare_stream", dev, C.byref(pm.desc), pm.prec, _p(pm.blob), int(layers), _p(clk), counts=True)
+    return n, clk
 
 
 def sample_fused(pm_coarse: PackedMLP, rays_o: Tensor, rays_d: Tensor, *, near: float, far: float, n_samples: int,
@@ -564,23 +619,8 @@ def sample_fused(pm_coarse: PackedMLP, rays_o: Tensor, rays_d: Tensor, *, near: 
     S, NI = n_samples, n_importance
     if NI <= 0:
         raise ValueError("sample_fused: hierarchical sampling only (n_importance > 0)")
-    o, d = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d")
-    R, dev = o.shape[0], o.device
-    mode, u = _u_mode(u, R, S)
-    a = L.RenderArgs()
-    a.R, a.rays_o, a.rays_d = R, o.data_ptr(), d.data_ptr()
-    a.near, a.far, a.S, a.n_imp, a.u_mode = float(near), float(far), S, NI, mode
-    keep = [o, d, u]
-    a.u = None if u is None else u.data_ptr()
-    if u_fine is not None:
-        u_fine = _f32(u_fine, "u_fine")
-        assert tuple(u_fine.shape) == (R, NI)
-        a.u_fine = u_fine.data_ptr()
-    for name, m in (("pos_mask", pos_mask), ("dir_mask", dir_mask)):
-        if m is not None:
-            m = _f32(m, name)
-            keep.append(m)
-            setattr(a, name, m.data_ptr())
+    h, R, dev = _render_args(rays_o, rays_d, None, near, far, S, NI, u, u_fine, pos_mask, dir_mask)
+    a = h.a
     edges = torch.empty(R, S + NI + 1, device=dev)
     a.edges_out = edges.data_ptr()
     wc = torch.empty(R, S, device=dev) if want_weights else None
@@ -589,9 +629,7 @@ def sample_fused(pm_coarse: PackedMLP, rays_o: Tensor, rays_d: Tensor, *, near: 
     a.two_phase = 2
     a.status = (status_word(dev) if status is None else status).data_ptr()  # `status`: a per-call word (training steps)
     if R > 0:
-        with torch.cuda.device(dev):
-            L.check(L.lib().fsn_render_rays_fused(C.byref(pm_coarse.desc), pm_coarse.prec, _p(pm_coarse.blob), None,
-                                                  C.byref(a), _stream()), "fsn_render_rays_fused")
+        _launch("fsn_render_rays_fused", dev, C.byref(pm_coarse.desc), pm_coarse.prec, _p(pm_coarse.blob), None, C.byref(a))
     return (edges, wc) if want_weights else edges
 
 
@@ -602,9 +640,8 @@ class _OcclusionRegFn(torch.autograd.Function):
         N = sig.numel()
         sums = torch.empty(max(n_rays, 1), device=sig.device, dtype=torch.float32)
         out = torch.empty(1, device=sig.device, dtype=torch.float32)
-        with torch.cuda.device(sig.device):
-            L.check(L.lib().fsn_occlusion_reg_fwd(_p(sig), _p(t), _p(ri), N, n_rays, float(a), float(b), func, _p(sums),
-                                                  _p(out), _stream()), "fsn_occlusion_reg_fwd")
+        _launch("fsn_occlusion_reg_fwd", sig.device, _p(sig), _p(t), _p(ri), N, n_rays, float(a), float(b), func, _p(sums),
+                _p(out))
         ctx.save_for_backward(t, sums)
         ctx.cfg = (N, n_rays, float(a), float(b), func)
         return out.reshape(())
@@ -616,9 +653,7 @@ class _OcclusionRegFn(torch.autograd.Function):
         d_sig = torch.zeros(N, device=t.device, dtype=torch.float32)
         cnt = torch.empty(1, device=t.device, dtype=torch.int32)
         g = _f32(g, "grad").reshape(1)
-        with torch.cuda.device(t.device):
-            L.check(L.lib().fsn_occlusion_reg_bwd(_p(t), N, _p(sums), n_rays, a, b, func, _p(g), _p(cnt), _p(d_sig),
-                                                  _stream()), "fsn_occlusion_reg_bwd")
+        _launch("fsn_occlusion_reg_bwd", t.device, _p(t), N, _p(sums), n_rays, a, b, func, _p(g), _p(cnt), _p(d_sig))
         return d_sig, None, None, None, None, None, None
 
 
@@ -641,8 +676,7 @@ def to8b(x: Tensor) -> Tensor:
     """(255 * clip(x, 0, 1)).astype(uint8) on the device (src/render/rendering.py:21)."""
     x = _f32(x, "x")
     out = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
-    with torch.cuda.device(x.device):
-        L.check(L.lib().fsn_to8b(_p(x), x.numel(), _p(out), _stream()), "fsn_to8b")
+    _launch("fsn_to8b", x.device, _p(x), x.numel(), _p(out))
     return out
 
 
@@ -668,10 +702,8 @@ def video_tensors(frames: Tensor, d_frames: Tensor, cmap: str = "plasma") -> Tup
     if N * H * W == 0:
         return out_f, out_d
     vmm = torch.stack(torch.aminmax(dp)).to(torch.float32).contiguous()  # np.amin / np.amax over ALL frames
-    with torch.cuda.device(dev):
-        L.check(L.lib().fsn_to8b_nchw(_p(fr), N, H * W, _p(out_f), _stream()), "fsn_to8b_nchw")
-        L.check(L.lib().fsn_depth_colormap(_p(dp), N, H * W, _p(vmm), _p(_lut_cache[key]), _p(out_d), _stream()),
-                "fsn_depth_colormap")
+    _launch("fsn_to8b_nchw", dev, _p(fr), N, H * W, _p(out_f))
+    _launch("fsn_depth_colormap", dev, _p(dp), N, H * W, _p(vmm), _p(_lut_cache[key]), _p(out_d))
     return out_f, out_d
 
 
@@ -680,27 +712,29 @@ def _ptr_array(ts: Sequence[Tensor]):
     return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
 
 
+def _nerf_train_fwd(name: str, desc: L.MlpDesc, prec: int, weights, biases, inputs: Sequence[Tensor], n: int, pos_mask,
+                    dir_mask, status):
+    """Both forms of the training forward: `inputs` are the converted sample arguments of `name`, in its order."""
+    dev = inputs[0].device
+    ws_ = [_f32(w.detach(), "weight") for w in weights]
+    bs_ = [_f32(b.detach(), "bias") for b in biases]
+    pm, dm = _opt_f32(pos_mask, "pos_mask"), _opt_f32(dir_mask, "dir_mask")
+    out = torch.empty(n, 4, device=dev, dtype=torch.float32)
+    nfl = _size("fsn_nerf_train_workspace_floats", dev, C.byref(desc), prec, n)
+    work = torch.empty(max(nfl, 1), device=dev, dtype=torch.float32)
+    _launch(name, dev, C.byref(desc), prec, _ptr_array(ws_), _ptr_array(bs_), *(_p(t) for t in inputs), _p(pm), _p(dm), n,
+            _p(work), _p(out), _p(status))
+    return out, work
+
+
 def nerf_train_fwd_rays(desc: L.MlpDesc, prec: int, weights: Sequence[Tensor], biases: Sequence[Tensor], rays_o: Tensor,
                         rays_d: Tensor, ray_indices: Tensor, t_starts: Tensor, t_ends: Tensor, pos_mask: Optional[Tensor],
                         dir_mask: Optional[Tensor], status: Optional[Tensor] = None):
     """nerf_train_fwd with the samples in ray form (midpoints of packed intervals): -> (out [n,4], workspace)."""
     o, d = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d")
     ri, t0, t1 = _i64(ray_indices, "ray_indices"), _f32(t_starts, "t_starts"), _f32(t_ends, "t_ends")
-    n = ri.numel()
-    ws_ = [_f32(w.detach(), "weight") for w in weights]
-    bs_ = [_f32(b.detach(), "bias") for b in biases]
-    with torch.cuda.device(o.device):
-        pm = None if pos_mask is None else _f32(pos_mask, "pos_mask")
-        dm = None if dir_mask is None else _f32(dir_mask, "dir_mask")
-        out = torch.empty(n, 4, device=o.device, dtype=torch.float32)
-        nfl = L.lib().fsn_nerf_train_workspace_floats(C.byref(desc), prec, n)
-        if nfl < 0:
-            L.check(int(nfl), "fsn_nerf_train_workspace_floats")
-        work = torch.empty(max(int(nfl), 1), device=o.device, dtype=torch.float32)
-        L.check(L.lib().fsn_nerf_train_fwd_rays(C.byref(desc), prec, _ptr_array(ws_), _ptr_array(bs_), _p(o), _p(d), _p(ri),
-                                                _p(t0), _p(t1), _p(pm), _p(dm), n, _p(work), _p(out), _p(status), _stream()),
-                "fsn_nerf_train_fwd_rays")
-    return out, work
+    return _nerf_train_fwd("fsn_nerf_train_fwd_rays", desc, prec, weights, biases, (o, d, ri, t0, t1), ri.numel(), pos_mask,
+                           dir_mask, status)
 
 
 def nerf_train_fwd(desc: L.MlpDesc, prec: int, weights: Sequence[Tensor], biases: Sequence[Tensor], x: Tensor,
@@ -708,21 +742,7 @@ def nerf_train_fwd(desc: L.MlpDesc, prec: int, weights: Sequence[Tensor], biases
     """NeRF.forward keeping what the backward needs: -> (out [n,4], workspace).  prec: L.FSN_PREC_*.  `status`: this
     call's range-guard word (int32[1], zeroed by the caller; the same tensor goes to nerf_train_bwd)."""
     x, d = _f32(x, "x").reshape(-1, 3), _f32(dirs, "dirs").reshape(-1, 3)
-    n = x.shape[0]
-    ws_ = [_f32(w.detach(), "weight") for w in weights]
-    bs_ = [_f32(b.detach(), "bias") for b in biases]
-    with torch.cuda.device(x.device):
-        pm = None if pos_mask is None else _f32(pos_mask, "pos_mask")
-        dm = None if dir_mask is None else _f32(dir_mask, "dir_mask")
-        out = torch.empty(n, 4, device=x.device, dtype=torch.float32)
-        nfl = L.lib().fsn_nerf_train_workspace_floats(C.byref(desc), prec, n)
-        if nfl < 0:
-            L.check(int(nfl), "fsn_nerf_train_workspace_floats")
-        work = torch.empty(max(int(nfl), 1), device=x.device, dtype=torch.float32)
-        L.check(L.lib().fsn_nerf_train_fwd(C.byref(desc), prec, _ptr_array(ws_), _ptr_array(bs_), _p(x), _p(d), _p(pm),
-                                           _p(dm), n, _p(work), _p(out), _p(status), _stream()),
-                "fsn_nerf_train_fwd")
-    return out, work
+    return _nerf_train_fwd("fsn_nerf_train_fwd", desc, prec, weights, biases, (x, d), x.shape[0], pos_mask, dir_mask, status)
 
 
 def grad_scale_for(d_out: Tensor) -> Tensor:
@@ -731,8 +751,7 @@ def grad_scale_for(d_out: Tensor) -> Tensor:
     2^clamp(floor(log2(1024 / max|d_out|)), -40, 60), 1 when the maximum is 0 / inf / NaN."""
     d = _f32(d_out.detach(), "d_out").reshape(-1)
     buf = torch.zeros(4, dtype=torch.float32, device=d.device)
-    with torch.cuda.device(d.device):
-        L.check(L.lib().fsn_grad_scale(_p(d), d.numel(), _p(buf), _stream()), "fsn_grad_scale")
+    _launch("fsn_grad_scale", d.device, _p(d), d.numel(), _p(buf))
     return buf[:1]
 
 
@@ -780,12 +799,9 @@ def nerf_train_bwd(desc: L.MlpDesc, prec: int, weights: Sequence[Tensor], work: 
     dW, db, scale = _grad_buffers(ws_, n, into, prec, d_out)
     if n == 0:
         return dW, db
-    with torch.cuda.device(work.device):
-        L.check(L.lib().fsn_nerf_train_bwd(C.byref(desc), prec, _ptr_array(ws_), n, _p(work), _p(out), _p(d_out),
-                                           _p(scale), _ptr_array(dW), _ptr_array(db), 0 if into is None else 1,
-                                           _p(stage_state[0]) if stage_state else None,
-                                           _p(stage_state[1]) if stage_state else None, _p(status), _stream()),
-                "fsn_nerf_train_bwd")
+    _launch("fsn_nerf_train_bwd", work.device, C.byref(desc), prec, _ptr_array(ws_), n, _p(work), _p(out), _p(d_out),
+            _p(scale), _ptr_array(dW), _ptr_array(db), 0 if into is None else 1,
+            _p(stage_state[0]) if stage_state else None, _p(stage_state[1]) if stage_state else None, _p(status))
     return dW, db
 
 
@@ -825,14 +841,12 @@ def nerf_train_bwd_inputs(desc: L.MlpDesc, prec: int, weights: Sequence[Tensor],
     dW, db, scale = _grad_buffers(ws_, n, into, prec, d_out, param_grads)
     if n == 0:
         return dW, db, d_x, d_dirs
-    pm = None if pos_mask is None else _f32(pos_mask, "pos_mask")
-    dm = None if dir_mask is None else _f32(dir_mask, "dir_mask")
-    with torch.cuda.device(work.device):
-        L.check(L.lib().fsn_nerf_train_bwd_inputs(
-            C.byref(desc), prec, _ptr_array(ws_), n, _p(work), _p(out), _p(d_out), _p(scale),
-            _ptr_array(dW) if param_grads else None, _ptr_array(db) if param_grads else None, 0 if into is None else 1,
-            _p(stage_state[0]) if stage_state else None, _p(stage_state[1]) if stage_state else None, _p(status),
-            *[_p(t) for t in src], _p(pm), _p(dm), _p(d_x), _p(d_dirs), _stream()), "fsn_nerf_train_bwd_inputs")
+    pm, dm = _opt_f32(pos_mask, "pos_mask"), _opt_f32(dir_mask, "dir_mask")
+    _launch("fsn_nerf_train_bwd_inputs", work.device, C.byref(desc), prec, _ptr_array(ws_), n, _p(work), _p(out), _p(d_out),
+            _p(scale), _ptr_array(dW) if param_grads else None, _ptr_array(db) if param_grads else None,
+            0 if into is None else 1, _p(stage_state[0]) if stage_state else None,
+            _p(stage_state[1]) if stage_state else None, _p(status), *[_p(t) for t in src], _p(pm), _p(dm), _p(d_x),
+            _p(d_dirs))
     return dW, db, d_x, d_dirs
 
 
@@ -844,16 +858,13 @@ def ray_grad_reduce(d_x: Optional[Tensor], d_dirs: Optional[Tensor], ray_indices
     ri, t0, t1 = _i64(ray_indices, "ray_indices"), _f32(t_starts, "t_starts"), _f32(t_ends, "t_ends")
     n = ri.numel()
     dev = ri.device
-    d_x = None if d_x is None else _f32(d_x, "d_x")
-    d_dirs = None if d_dirs is None else _f32(d_dirs, "d_dirs")
+    d_x, d_dirs = _opt_f32(d_x, "d_x"), _opt_f32(d_dirs, "d_dirs")
     for g in (d_x, d_dirs):
         if g is not None and tuple(g.shape) != (n, 3):
             raise ValueError("ray_grad_reduce: d_x / d_dirs must be [n_samples, 3]")
     d_o = torch.empty(n_rays, 3, device=dev, dtype=torch.float32) if want_o else None
     d_d = torch.empty(n_rays, 3, device=dev, dtype=torch.float32) if want_d else None
-    with torch.cuda.device(dev):
-        L.check(L.lib().fsn_ray_grad_reduce(_p(d_x), _p(d_dirs), _p(ri), _p(t0), _p(t1), n, n_rays, _p(d_o), _p(d_d),
-                                            _stream()), "fsn_ray_grad_reduce")
+    _launch("fsn_ray_grad_reduce", dev, _p(d_x), _p(d_dirs), _p(ri), _p(t0), _p(t1), n, n_rays, _p(d_o), _p(d_d))
     return d_o, d_d
 
 
@@ -865,30 +876,20 @@ def _composite_bwd(lean, sigmas, rgbs, t_starts, t_ends, ray_indices, n_rays, bk
     t0, t1 = _f32(t_starts, "t_starts"), _f32(t_ends, "t_ends")
     ri = _i64(ray_indices, "ray_indices")
     N = sig.numel()
-
-    def opt(t, name, n):
-        if t is None:
-            return None
-        t = _f32(t, name).reshape(-1)
-        if t.numel() != n:
-            raise ValueError(f"{name}: expected {n} values, got {t.numel()}")
-        return t
-
-    dc = opt(d_colors, "d_colors", 3 * n_rays)
-    dop, op, dep, dd = (opt(t, name, n_rays) for t, name in ((d_opacity, "d_opacity"), (opacity, "opacity"), (depth, "depth"),
-                                                            (d_depth, "d_depth")))
-    dw, da, dt = (opt(t, name, N) for t, name in ((d_weights, "d_weights"), (d_alphas, "d_alphas"), (d_trans, "d_trans")))
+    dc = _flat(d_colors, "d_colors", 3 * n_rays, cast=True)
+    dop, op, dep, dd = (_flat(t, name, n_rays, cast=True) for t, name in ((d_opacity, "d_opacity"), (opacity, "opacity"),
+                                                                          (depth, "depth"), (d_depth, "d_depth")))
+    dw, da, dt = (_flat(t, name, N, cast=True) for t, name in ((d_weights, "d_weights"), (d_alphas, "d_alphas"),
+                                                               (d_trans, "d_trans")))
     if t0.numel() != N or t1.numel() != N or ri.numel() != N or rgb.numel() != 3 * N:
         raise ValueError(f"composite_packed_bwd{'' if lean else '_full'}: sigmas, rgbs, t_starts, t_ends and ray_indices "
                          "disagree in length")
     ds, dr = torch.empty_like(sig), torch.empty_like(rgb)
-    head, tail = (_p(sig), _p(rgb), _p(t0), _p(t1), _p(ri), N, n_rays, _bk(bkgd), _p(dc), _p(dop)), (_p(ds), _p(dr), _stream())
-    with torch.cuda.device(sig.device):
-        if lean:
-            L.check(L.lib().fsn_composite_packed_bwd(*head, *tail), "fsn_composite_packed_bwd")
-        else:
-            L.check(L.lib().fsn_composite_packed_bwd_full(*head, _p(op), _p(dep), _p(dd), _p(dw), _p(da), _p(dt), *tail),
-                    "fsn_composite_packed_bwd_full")
+    head, tail = (_p(sig), _p(rgb), _p(t0), _p(t1), _p(ri), N, n_rays, _bk(bkgd), _p(dc), _p(dop)), (_p(ds), _p(dr))
+    if lean:
+        _launch("fsn_composite_packed_bwd", sig.device, *head, *tail)
+    else:
+        _launch("fsn_composite_packed_bwd_full", sig.device, *head, _p(op), _p(dep), _p(dd), _p(dw), _p(da), _p(dt), *tail)
     return ds, dr
 
 
@@ -912,9 +913,7 @@ class _DistortionFn(torch.autograd.Function):
     def forward(ctx, w, t0, t1, ri, n_rays):
         N = w.numel()
         out = torch.empty(n_rays, device=w.device, dtype=torch.float32)
-        with torch.cuda.device(w.device):
-            L.check(L.lib().fsn_distortion_fwd(_p(w), _p(t0), _p(t1), _p(ri), N, n_rays, _p(out), _stream()),
-                    "fsn_distortion_fwd")
+        _launch("fsn_distortion_fwd", w.device, _p(w), _p(t0), _p(t1), _p(ri), N, n_rays, _p(out))
         ctx.save_for_backward(w, t0, t1, ri)
         ctx.n_rays = n_rays
         return out.reshape(n_rays, 1)
@@ -924,9 +923,7 @@ class _DistortionFn(torch.autograd.Function):
         w, t0, t1, ri = ctx.saved_tensors
         g = _f32(g, "grad").reshape(-1)
         d_w = torch.empty_like(w)
-        with torch.cuda.device(w.device):
-            L.check(L.lib().fsn_distortion_bwd(_p(w), _p(t0), _p(t1), _p(ri), w.numel(), ctx.n_rays, _p(g), _p(d_w),
-                                               _stream()), "fsn_distortion_bwd")
+        _launch("fsn_distortion_bwd", w.device, _p(w), _p(t0), _p(t1), _p(ri), w.numel(), ctx.n_rays, _p(g), _p(d_w))
         return d_w, None, None, None, None
 
 
@@ -942,15 +939,6 @@ def distortion(weights: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indices: T
 
 
 # ------------------------------------------------------------------ packed volume-rendering primitives (csrc/packed_scan.hip)
-def _gpu_f32(t: Tensor, name: str) -> Tensor:
-    """The packed primitives take GPU float32 as it is: nothing is cast (a cast would hide from autograd)."""
-    if not t.is_cuda:
-        raise RuntimeError(f"{name}: expected a GPU tensor (the HIP path has no CPU fallback)")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name}: expected float32, got {t.dtype}")
-    return t.contiguous()
-
-
 class RaySpans:
     """Where each ray's samples are among N flat samples - the "span" arguments of include/fsnerf_hip.h: exactly one of
     sorted `ray_indices` [N], `packed_info` [n_rays, 2] = (start, count), dense rows of `dense_S` samples."""
@@ -977,18 +965,8 @@ def pack_info(ray_indices: Tensor, n_rays: int) -> Tensor:
     """(start, count) int64 [n_rays, 2] of every ray in the sorted `ray_indices` (fsn_pack_info)."""
     ri = _i64(ray_indices, "ray_indices").reshape(-1)
     info = torch.empty(int(n_rays), 2, dtype=torch.int64, device=ri.device)
-    with torch.cuda.device(ri.device):
-        L.check(L.lib().fsn_pack_info(_p(ri), ri.numel(), int(n_rays), _p(info), _stream()), "fsn_pack_info")
+    _launch("fsn_pack_info", ri.device, _p(ri), ri.numel(), int(n_rays), _p(info))
     return info
-
-
-def _flat(t: Optional[Tensor], name: str, n: int) -> Optional[Tensor]:
-    if t is None:
-        return None
-    t = _gpu_f32(t, name).reshape(-1)
-    if t.numel() != n:
-        raise ValueError(f"{name}: expected {n} values, got {t.numel()}")
-    return t
 
 
 def _zeroed_by_call(shape, spans: RaySpans, dev, dtype=torch.float32) -> Tensor:
@@ -1008,9 +986,8 @@ def _out(like: Tensor, spans: RaySpans, dtype=torch.float32) -> Tensor:
 def packed_scan_fwd(x: Tensor, spans: RaySpans, prod: bool, exclusive: bool) -> Tensor:
     x = _flat(x, "inputs", spans.N)
     out = _out(x, spans)
-    with torch.cuda.device(x.device):
-        L.check(L.lib().fsn_packed_scan_fwd(_p(x), *spans.args(), L.FSN_SCAN_PROD if prod else L.FSN_SCAN_SUM,
-                                            int(exclusive), _p(out), _stream()), "fsn_packed_scan_fwd")
+    _launch("fsn_packed_scan_fwd", x.device, _p(x), *spans.args(), L.FSN_SCAN_PROD if prod else L.FSN_SCAN_SUM,
+            int(exclusive), _p(out))
     return out
 
 
@@ -1018,9 +995,8 @@ def packed_scan_bwd(x: Optional[Tensor], d_out: Tensor, spans: RaySpans, prod: b
     g = _flat(d_out, "d_out", spans.N)
     x = _flat(x, "inputs", spans.N)
     d_x = _zeroed_by_call(g.shape, spans, g.device)
-    with torch.cuda.device(g.device):
-        L.check(L.lib().fsn_packed_scan_bwd(_p(x), _p(g), *spans.args(), L.FSN_SCAN_PROD if prod else L.FSN_SCAN_SUM,
-                                            int(exclusive), _p(d_x), _stream()), "fsn_packed_scan_bwd")
+    _launch("fsn_packed_scan_bwd", g.device, _p(x), _p(g), *spans.args(), L.FSN_SCAN_PROD if prod else L.FSN_SCAN_SUM,
+            int(exclusive), _p(d_x))
     return d_x
 
 
@@ -1034,9 +1010,8 @@ def packed_weights_fwd(v: Tensor, t_starts: Optional[Tensor], t_ends: Optional[T
     if not from_alpha and (t0 is None or t1 is None):
         raise ValueError("packed_weights_fwd: the density form needs t_starts and t_ends")
     outs = [_out(v, spans) if k else None for k in want]
-    with torch.cuda.device(v.device):
-        L.check(L.lib().fsn_packed_weights_fwd(_p(v), _p(t0), _p(t1), *spans.args(), int(from_alpha), _p(p),
-                                               *(_p(o) for o in outs), _stream()), "fsn_packed_weights_fwd")
+    _launch("fsn_packed_weights_fwd", v.device, _p(v), _p(t0), _p(t1), *spans.args(), int(from_alpha), _p(p),
+            *(_p(o) for o in outs))
     return tuple(outs)
 
 
@@ -1050,18 +1025,15 @@ def packed_weights_bwd(v: Tensor, t_starts: Optional[Tensor], t_ends: Optional[T
     p = _flat(prefix_trans, "prefix_trans", n)
     dw, dtr, dal = _flat(d_weights, "d_weights", n), _flat(d_trans, "d_trans", n), _flat(d_alphas, "d_alphas", n)
     d_v = _zeroed_by_call(v.shape, spans, v.device)
-    with torch.cuda.device(v.device):
-        L.check(L.lib().fsn_packed_weights_bwd(_p(v), _p(t0), _p(t1), *spans.args(), int(from_alpha), _p(p), _p(dw),
-                                               _p(dtr), _p(dal), _p(d_v), _stream()), "fsn_packed_weights_bwd")
+    _launch("fsn_packed_weights_bwd", v.device, _p(v), _p(t0), _p(t1), *spans.args(), int(from_alpha), _p(p), _p(dw), _p(dtr),
+            _p(dal), _p(d_v))
     return d_v
 
 
 def packed_visibility_alpha(alphas: Tensor, spans: RaySpans, early_stop_eps: float, alpha_thre: float) -> Tensor:
     a = _flat(alphas, "alphas", spans.N)
     keep = _zeroed_by_call((spans.N,), spans, a.device, torch.uint8)
-    with torch.cuda.device(a.device):
-        L.check(L.lib().fsn_packed_visibility_alpha(_p(a), *spans.args(), float(early_stop_eps), float(alpha_thre),
-                                                    _p(keep), _stream()), "fsn_packed_visibility_alpha")
+    _launch("fsn_packed_visibility_alpha", a.device, _p(a), *spans.args(), float(early_stop_eps), float(alpha_thre), _p(keep))
     return keep.bool()
 
 
@@ -1075,8 +1047,7 @@ def accumulate_fwd(weights: Tensor, values: Optional[Tensor], spans: RaySpans) -
             raise ValueError("accumulate: values need at least one channel")
         values = _flat(values, "values", spans.N * C)
     out = torch.empty(spans.R, C, device=w.device, dtype=torch.float32)  # (every row is written; N == 0: zeroed by the call)
-    with torch.cuda.device(w.device):
-        L.check(L.lib().fsn_accumulate_fwd(_p(w), _p(values), C, *spans.args(), _p(out), _stream()), "fsn_accumulate_fwd")
+    _launch("fsn_accumulate_fwd", w.device, _p(w), _p(values), C, *spans.args(), _p(out))
     return out
 
 
@@ -1086,13 +1057,11 @@ def accumulate_bwd(d_out: Tensor, weights: Tensor, values: Optional[Tensor], spa
     w = _flat(weights, "weights", spans.N)
     C = 1 if values is None else int(values.shape[-1])
     g = _flat(d_out, "d_out", spans.R * C)
-    v = None if values is None else _flat(values, "values", spans.N * C)
+    v = _flat(values, "values", spans.N * C)
     d_w = _zeroed_by_call(w.shape, spans, w.device) if want_weights else None
     d_v = _zeroed_by_call((spans.N, C), spans, w.device) if want_values and v is not None else None
     if d_w is not None or d_v is not None:
-        with torch.cuda.device(w.device):
-            L.check(L.lib().fsn_accumulate_bwd(_p(g), _p(w), _p(v), C, *spans.args(), _p(d_w), _p(d_v), _stream()),
-                    "fsn_accumulate_bwd")
+        _launch("fsn_accumulate_bwd", w.device, _p(g), _p(w), _p(v), C, *spans.args(), _p(d_w), _p(d_v))
     return d_w, d_v
 
 
@@ -1101,6 +1070,7 @@ _STOT = {None: L.FSN_STOT_NONE, "uniform": L.FSN_STOT_UNIFORM, "lindisp": L.FSN_
 
 
 def _rows(t: Tensor, name: str, R: int, cols: int) -> Tensor:
+    """A required [R, cols] tensor (`_gpu_f32` policy): the dense rows keep their shape, unlike `_flat`."""
     t = _gpu_f32(t, name)
     if tuple(t.shape) != (R, cols):
         raise ValueError(f"{name}: expected shape ({R}, {cols}), got {tuple(t.shape)}")
@@ -1129,9 +1099,7 @@ def importance_sample(vals: Tensor, cdfs: Tensor, n: int, b: Optional[Tensor] = 
     s = torch.empty(R, max(n, 0) + 1, device=dev)
     x = torch.empty(R, max(n, 0), device=dev) if want_centres else None
     t = torch.empty_like(s) if transform is not None else None
-    with torch.cuda.device(dev):
-        L.check(L.lib().fsn_importance_sample(_p(vals), _p(cdfs), R, S, n, _p(b), tf, near, far, _p(s), _p(x), _p(t),
-                                              _stream()), "fsn_importance_sample")
+    _launch("fsn_importance_sample", dev, _p(vals), _p(cdfs), R, S, n, _p(b), tf, near, far, _p(s), _p(x), _p(t))
     return s, x, t
 
 
@@ -1148,9 +1116,8 @@ def prop_resample(s_edges: Tensor, t_edges: Tensor, sigmas: Tensor, n: int, b: O
     s = torch.empty(R, max(n, 0) + 1, device=dev)
     x = torch.empty(R, max(n, 0), device=dev) if want_centres else None
     t = torch.empty_like(s) if transform is not None else None
-    with torch.cuda.device(dev):
-        L.check(L.lib().fsn_prop_resample(_p(s_edges), _p(t_edges), _p(sigmas), R, S, n, _p(b), tf, near, far, _p(cdfs),
-                                          _p(s), _p(x), _p(t), _stream()), "fsn_prop_resample")
+    _launch("fsn_prop_resample", dev, _p(s_edges), _p(t_edges), _p(sigmas), R, S, n, _p(b), tf, near, far, _p(cdfs), _p(s),
+            _p(x), _p(t))
     return cdfs, s, x, t
 
 
@@ -1162,9 +1129,7 @@ def searchsorted_dense(keys: Tensor, values: Tensor) -> Tuple[Tensor, Tensor]:
     R, K, Q = int(keys.shape[0]), int(keys.shape[1]), int(values.shape[1])
     il = torch.empty(R, Q, dtype=torch.int64, device=keys.device)
     ir = torch.empty_like(il)
-    with torch.cuda.device(keys.device):
-        L.check(L.lib().fsn_searchsorted_dense(_p(keys), _p(values), R, K, Q, _p(il), _p(ir), _stream()),
-                "fsn_searchsorted_dense")
+    _launch("fsn_searchsorted_dense", keys.device, _p(keys), _p(values), R, K, Q, _p(il), _p(ir))
     return il, ir
 
 
@@ -1180,8 +1145,7 @@ def prop_loss_fwd(q_edges: Tensor, q_cdfs: Tensor, k_edges: Tensor, k_cdfs: Tens
     """-> the interlevel loss per query interval [R, n] (fsn_prop_loss_fwd)"""
     rows, R, n, S = _prop_loss_rows(q_edges, q_cdfs, k_edges, k_cdfs)
     loss = torch.empty(R, max(n, 0), device=rows[0].device)
-    with torch.cuda.device(loss.device):
-        L.check(L.lib().fsn_prop_loss_fwd(*(_p(t) for t in rows), R, n, S, _p(loss), _stream()), "fsn_prop_loss_fwd")
+    _launch("fsn_prop_loss_fwd", loss.device, *(_p(t) for t in rows), R, n, S, _p(loss))
     return loss
 
 
@@ -1190,8 +1154,7 @@ def prop_loss_bwd(q_edges: Tensor, q_cdfs: Tensor, k_edges: Tensor, k_cdfs: Tens
     rows, R, n, S = _prop_loss_rows(q_edges, q_cdfs, k_edges, k_cdfs)
     g = _rows(d_loss, "d_loss", R, n)
     d_ck = torch.empty(R, S + 1, device=g.device)
-    with torch.cuda.device(g.device):
-        L.check(L.lib().fsn_prop_loss_bwd(*(_p(t) for t in rows), _p(g), R, n, S, _p(d_ck), _stream()), "fsn_prop_loss_bwd")
+    _launch("fsn_prop_loss_bwd", g.device, *(_p(t) for t in rows), _p(g), R, n, S, _p(d_ck))
     return d_ck
 
 
@@ -1205,7 +1168,7 @@ def occgrid_march(rays_o: Tensor, rays_d: Tensor, aabb: Sequence[float], res: in
     goes through fsn_occgrid_march_ex (include/fsnerf_hip.h has the definition), of which fsn_occgrid_march is the form
     without bounds and with cone_angle 0 - one kernel serves both."""
     o, d = _f32(rays_o, "rays_o").reshape(-1, 3), _f32(rays_d, "rays_d").reshape(-1, 3)
-    R = o.shape[0]
+    R, dev = o.shape[0], o.device
     ab = (C.c_float * 6)(*[float(v) for v in aabb])
     u_ = None if u is None else _f32(u, "u").reshape(-1)
     if u_ is not None and u_.numel() != R:
@@ -1215,18 +1178,16 @@ def occgrid_march(rays_o: Tensor, rays_d: Tensor, aabb: Sequence[float], res: in
         raise ValueError("t_min / t_max must hold one value per ray")
     args = (_p(o), _p(d), R, ab, int(res), int(levels), _p(bits), float(near_plane), float(far_plane), float(step), _p(u_),
             int(max_steps), _p(bounds[0]), _p(bounds[1]), float(cone_angle))
-    counts = torch.zeros(R, device=o.device, dtype=torch.int64)
-    with torch.cuda.device(o.device):
-        march = L.lib().fsn_occgrid_march_ex
-        L.check(march(*args, _p(counts), None, None, None, None, _stream()), "fsn_occgrid_march_ex")
-        ends = torch.cumsum(counts, 0)
-        offsets = (ends - counts).contiguous()
-        N = int(ends[-1].item()) if R > 0 else 0
-        ri = torch.empty(N, device=o.device, dtype=torch.int64)
-        t0 = torch.empty(N, device=o.device, dtype=torch.float32)
-        t1 = torch.empty(N, device=o.device, dtype=torch.float32)
-        if N > 0:
-            L.check(march(*args, None, _p(offsets), _p(ri), _p(t0), _p(t1), _stream()), "fsn_occgrid_march_ex")
+    counts = torch.zeros(R, device=dev, dtype=torch.int64)
+    _launch("fsn_occgrid_march_ex", dev, *args, _p(counts), None, None, None, None)
+    ends = torch.cumsum(counts, 0)
+    offsets = (ends - counts).contiguous()
+    N = int(ends[-1].item()) if R > 0 else 0  # the one host read: the sample count sizes the outputs
+    ri = torch.empty(N, device=dev, dtype=torch.int64)
+    t0 = torch.empty(N, device=dev, dtype=torch.float32)
+    t1 = torch.empty(N, device=dev, dtype=torch.float32)
+    if N > 0:
+        _launch("fsn_occgrid_march_ex", dev, *args, None, _p(offsets), _p(ri), _p(t0), _p(t1))
     return ri, t0, t1, counts
 
 
@@ -1240,24 +1201,76 @@ def ray_aabb_intersect(rays_o: Tensor, rays_d: Tensor, aabbs: Tensor, near_plane
     t0 = torch.empty(R, M, device=o.device, dtype=torch.float32)
     t1 = torch.empty(R, M, device=o.device, dtype=torch.float32)
     hits = torch.empty(R, M, device=o.device, dtype=torch.uint8)
-    with torch.cuda.device(o.device):
-        L.check(L.lib().fsn_ray_aabb_intersect(_p(o), _p(d), R, _p(boxes), M, float(near_plane), float(far_plane),
-                                               float(miss_value), _p(t0), _p(t1), _p(hits), _stream()),
-                "fsn_ray_aabb_intersect")
+    _launch("fsn_ray_aabb_intersect", o.device, _p(o), _p(d), R, _p(boxes), M, float(near_plane), float(far_plane),
+            float(miss_value), _p(t0), _p(t1), _p(hits))
     return t0, t1, hits.bool()
 
 
-def _occ_march_options(R: int, cone_angle: float, t_min: Optional[Tensor], t_max: Optional[Tensor], camera, keep: list):
+def _occ_march_options(R: int, cone_angle: float, t_min: Optional[Tensor], t_max: Optional[Tensor], camera, h: _Held):
     """The extended arguments of fsn_render_rays_occgrid_ex (cone_angle, t_min, t_max), checked: per-ray bounds hold one
-    value per ray and need ray tensors.  The bound tensors are appended to `keep`."""
+    value per ray and need ray tensors.  `h` holds the converted bounds."""
     if t_min is not None or t_max is not None:
         if camera is not None:
             raise TypeError("per-ray t_min / t_max need ray tensors, not a camera")
     if any(t is not None and t.numel() != R for t in (t_min, t_max)):
         raise ValueError("t_min / t_max must hold one value per ray")
-    bounds = [None if t is None else _f32(t, k).reshape(-1) for t, k in ((t_min, "t_min"), (t_max, "t_max"))]
-    keep.extend(bounds)
-    return float(cone_angle), _p(bounds[0]), _p(bounds[1])
+    return float(cone_angle), h.p(_flat(t_min, "t_min", R, cast=True)), h.p(_flat(t_max, "t_max", R, cast=True))
+
+
+def _occ_args(rays_o: Optional[Tensor], rays_d: Optional[Tensor], camera, aabb: Sequence[float], res: int, levels: int,
+              bits: Tensor, near_plane: float, far_plane: float, step: float, max_steps: int, u: Optional[Tensor],
+              early_stop_eps: float, alpha_thre: float, pos_mask: Optional[Tensor], dir_mask: Optional[Tensor],
+              cone_angle: float, t_min: Optional[Tensor], t_max: Optional[Tensor]):
+    """The inputs of fsn_render_rays_occgrid_ex (rays or camera, bounds, grid, march, jitter, thresholds, masks) ->
+    (held OccRenderArgs, R, device, march = the extended arguments (cone_angle, t_min, t_max))."""
+    h = _Held(L.OccRenderArgs())
+    a = h.a
+    R, dev = _ray_source(h, rays_o, rays_d, camera)
+    march = _occ_march_options(R, cone_angle, t_min, t_max, camera, h)
+    for i in range(6):
+        a.aabb[i] = float(aabb[i])
+    a.res, a.levels, a.bits = int(res), int(levels), bits.data_ptr()
+    a.near_plane, a.far_plane, a.step, a.max_steps = float(near_plane), float(far_plane), float(step), int(max_steps)
+    if u is not None:
+        u = _f32(u, "u").reshape(-1)
+        if u.numel() != R:
+            raise ValueError("u must hold one value per ray")
+        h.set("u", u)
+    a.early_stop_eps, a.alpha_thre = float(early_stop_eps), float(alpha_thre)
+    _masks(h, pos_mask, dir_mask)
+    return h, R, dev, march
+
+
+def _occ_launch(pm: "PackedMLP", h: _Held, march, ends: Optional[Tensor], dev, status: Optional[Tensor] = None,
+                launch: bool = True, **door) -> None:
+    """The end of both occupancy wrappers: the work counter, the status word and the launch itself."""
+    # (one queue counter PER CALL - ADVICE r3: a per-device buffer let two launches on different streams race on it; the
+    # launch zeroes it itself)
+    h.set("work_counter", torch.empty(1, dtype=torch.int64, device=dev))
+    h.a.status = (status_word(dev) if status is None else status).data_ptr()
+    if launch:
+        _launch("fsn_render_rays_occgrid_ex", dev, C.byref(pm.desc), pm.prec, _p(pm.blob), C.byref(h.a), *march, _p(ends),
+                **door)
+
+
+def _occ_gather(n_kept: Tensor, t0_slots: Tensor, t1_slots: Optional[Tensor], cap: int, R: int, step: float,
+                slots: Optional[Dict[str, Tensor]] = None):
+    """The tail of both occupancy wrappers: exclusive scan of the kept counts, ONE host read, the packed outputs and
+    fsn_occ_gather_ex -> (ray_indices int64 [N], t_starts [N], t_ends [N], extras).  `slots`: the extras' slot rows
+    (weights, alphas, trans, sigmas, rgbs), gathered into `extras`; None: interval starts and ends only."""
+    dev = n_kept.device
+    order = ("weights", "alphas", "trans", "sigmas", "rgbs") if slots is not None else ()
+    incl = torch.cumsum(n_kept, 0, dtype=torch.int64)
+    N = int(incl[-1].item()) if R > 0 else 0  # the one host read: the sample count sizes the outputs
+    ri = torch.empty(N, dtype=torch.int64, device=dev)
+    ts, te = torch.empty(N, device=dev), torch.empty(N, device=dev)
+    ex = {k: torch.empty(N, 3, device=dev) if k == "rgbs" else torch.empty(N, device=dev) for k in order}
+    if N > 0:
+        sp = _ptr_array([slots[k] for k in order]) if order else None
+        op = _ptr_array([ex[k] for k in order]) if order else None
+        _launch("fsn_occ_gather_ex", dev, _p(n_kept), _p(incl - n_kept), _p(t0_slots), _p(t1_slots), cap, R, float(step),
+                _p(ri), _p(ts), _p(te), sp, op)
+    return ri, ts, te, ex
 
 
 def occ_sample_fused(pm: PackedMLP, rays_o: Tensor, rays_d: Tensor, *, aabb: Sequence[float], res: int, levels: int, bits: Tensor,
@@ -1272,51 +1285,15 @@ def occ_sample_fused(pm: PackedMLP, rays_o: Tensor, rays_d: Tensor, *, aabb: Seq
     [N], t_ends [N]): what occgrid_march (two launches + a read) -> density pass -> packed_visibility -> compaction
     (a second read) give, bit for bit.  `cone_angle` / `t_min` / `t_max`: occgrid_march's (fsn_render_rays_occgrid_ex);
     with a cone angle the launch also leaves the kept samples' interval ends in slot rows, which the gather copies."""
-    o, d = _f32(rays_o, "rays_o").reshape(-1, 3), _f32(rays_d, "rays_d").reshape(-1, 3)
-    Rn, dev = o.shape[0], o.device
-    a = L.OccRenderArgs()
-    a.R, a.rays_o, a.rays_d = Rn, o.data_ptr(), d.data_ptr()
-    keep = [o, d]
-    march = _occ_march_options(Rn, cone_angle, t_min, t_max, None, keep)
-    for i in range(6):
-        a.aabb[i] = float(aabb[i])
-    a.res, a.levels, a.bits = int(res), int(levels), bits.data_ptr()
-    a.near_plane, a.far_plane, a.step, a.max_steps = float(near_plane), float(far_plane), float(step), int(max_steps)
-    if u is not None:
-        u = _f32(u, "u").reshape(-1)
-        if u.numel() != Rn:
-            raise ValueError("u must hold one value per ray")
-        keep.append(u)
-        a.u = u.data_ptr()
-    a.early_stop_eps, a.alpha_thre = float(early_stop_eps), float(alpha_thre)
-    for name, m in (("pos_mask", pos_mask), ("dir_mask", dir_mask)):
-        if m is not None:
-            m = _f32(m, name)
-            keep.append(m)
-            setattr(a, name, m.data_ptr())
+    h, Rn, dev, march = _occ_args(rays_o, rays_d, None, aabb, res, levels, bits, near_plane, far_plane, step, max_steps, u,
+                                  early_stop_eps, alpha_thre, pos_mask, dir_mask, cone_angle, t_min, t_max)
+    a, cap = h.a, int(max_steps)
     n_kept = torch.zeros(Rn, dtype=torch.int32, device=dev)
-    slots = torch.empty(max(Rn, 1), int(max_steps), dtype=torch.float32, device=dev)
+    slots = torch.empty(max(Rn, 1), cap, dtype=torch.float32, device=dev)
     ends = torch.empty_like(slots) if cone_angle > 0.0 else None  # (uniform regime: t_end = t_start + step)
-    a.n_kept, a.sample_t0, a.sample_cap = n_kept.data_ptr(), slots.data_ptr(), int(max_steps)
-    # (one queue counter PER CALL - ADVICE r3: a per-device buffer let two launches on different streams race on it; the
-    # launch zeroes it itself)
-    wc = torch.empty(1, dtype=torch.int64, device=dev)
-    keep.append(wc)
-    a.work_counter = wc.data_ptr()
-    a.status = (status_word(dev) if status is None else status).data_ptr()
-    with torch.cuda.device(dev):
-        if Rn > 0:
-            L.check(L.lib().fsn_render_rays_occgrid_ex(C.byref(pm.desc), pm.prec, _p(pm.blob), C.byref(a), *march, _p(ends),
-                                                       _stream()), "fsn_render_rays_occgrid_ex (sampler mode)")
-        incl = torch.cumsum(n_kept, 0, dtype=torch.int64)
-        N = int(incl[-1].item()) if Rn > 0 else 0  # the one host read: the sample count sizes the outputs
-        ri = torch.empty(N, dtype=torch.int64, device=dev)
-        ts, te = torch.empty(N, device=dev), torch.empty(N, device=dev)
-        if N > 0:
-            offs = incl - n_kept
-            L.check(L.lib().fsn_occ_gather_ex(_p(n_kept), _p(offs), _p(slots), _p(ends), int(max_steps), Rn, float(step),
-                                              _p(ri), _p(ts), _p(te), None, None, _stream()), "fsn_occ_gather_ex")
-    return ri, ts, te
+    a.n_kept, a.sample_t0, a.sample_cap = n_kept.data_ptr(), slots.data_ptr(), cap
+    _occ_launch(pm, h, march, ends, dev, status, launch=Rn > 0, what="fsn_render_rays_occgrid_ex (sampler mode)")
+    return _occ_gather(n_kept, slots, ends, cap, Rn, step)[:3]
 
 
 def render_occ_fused(pm: PackedMLP, rays_o: Optional[Tensor], rays_d: Optional[Tensor], *, aabb: Sequence[float], res: int,
@@ -1335,42 +1312,9 @@ def render_occ_fused(pm: PackedMLP, rays_o: Optional[Tensor], rays_d: Optional[T
     contract (rendering.py:88-107) from one launch + one gather.
     `cone_angle` / `t_min` / `t_max`: occgrid_march's (fsn_render_rays_occgrid_ex; the bounds need ray tensors); with a
     cone angle the extras mode holds a ninth slot row per sample, the interval ends."""
-    if camera is not None:
-        pose, cH, cW, cfocal, crow0, cnrows, dev = camera
-        dev = torch.device(dev)
-        R = int(cnrows) * int(cW)
-        o = d = None
-    else:
-        o, d = _f32(rays_o, "rays_o").reshape(-1, 3), _f32(rays_d, "rays_d").reshape(-1, 3)
-        R = o.shape[0]
-        dev = o.device
-    a = L.OccRenderArgs()
-    a.R = R
-    keep = [o, d]
-    march = _occ_march_options(R, cone_angle, t_min, t_max, camera, keep)
-    if camera is None:
-        a.rays_o, a.rays_d = o.data_ptr(), d.data_ptr()
-    else:
-        pmx = pose.detach().to("cpu", torch.float32)[:3, :4].contiguous().reshape(-1).tolist()
-        for i in range(12):
-            a.cam_pose[i] = pmx[i]
-        a.cam_H, a.cam_W, a.cam_row0, a.cam_focal = int(cH), int(cW), int(crow0), float(cfocal)
-    for i in range(6):
-        a.aabb[i] = float(aabb[i])
-    a.res, a.levels, a.bits = int(res), int(levels), bits.data_ptr()
-    a.near_plane, a.far_plane, a.step, a.max_steps = float(near_plane), float(far_plane), float(step), int(max_steps)
-    if u is not None:
-        u = _f32(u, "u").reshape(-1)
-        if u.numel() != R:
-            raise ValueError("u must hold one value per ray")
-        keep.append(u)
-        a.u = u.data_ptr()
-    a.early_stop_eps, a.alpha_thre = float(early_stop_eps), float(alpha_thre)
-    for name, m in (("pos_mask", pos_mask), ("dir_mask", dir_mask)):
-        if m is not None:
-            m = _f32(m, name)
-            keep.append(m)
-            setattr(a, name, m.data_ptr())
+    h, R, dev, march = _occ_args(rays_o, rays_d, camera, aabb, res, levels, bits, near_plane, far_plane, step, max_steps, u,
+                                 early_stop_eps, alpha_thre, pos_mask, dir_mask, cone_angle, t_min, t_max)
+    a, cap = h.a, int(max_steps)
     for i in range(3):
         a.bkgd[i] = float(bkgd[i])
     colors = torch.empty(R, 3, device=dev)
@@ -1381,9 +1325,8 @@ def render_occ_fused(pm: PackedMLP, rays_o: Optional[Tensor], rays_d: Optional[T
     if want_counts or want_extras:
         counts = {"n_cand": torch.zeros(R, dtype=torch.int32, device=dev), "n_kept": torch.zeros(R, dtype=torch.int32, device=dev)}
         a.n_cand, a.n_kept = counts["n_cand"].data_ptr(), counts["n_kept"].data_ptr()
-    slots = None
+    slots = {}
     if want_extras:
-        cap = int(max_steps)
         slots = {k: torch.empty(max(R, 1), cap, device=dev) for k in ("t0", "weights", "alphas", "trans", "sigmas")}
         slots["rgbs"] = torch.empty(max(R, 1), cap, 3, device=dev)
         if cone_angle > 0.0:  # (uniform regime: t_end = t_start + step)
@@ -1391,38 +1334,9 @@ def render_occ_fused(pm: PackedMLP, rays_o: Optional[Tensor], rays_d: Optional[T
         a.sample_t0, a.sample_cap = slots["t0"].data_ptr(), cap
         a.ex_weights, a.ex_alphas, a.ex_trans = slots["weights"].data_ptr(), slots["alphas"].data_ptr(), slots["trans"].data_ptr()
         a.ex_sigmas, a.ex_rgbs = slots["sigmas"].data_ptr(), slots["rgbs"].data_ptr()
-    # (one queue counter PER CALL - ADVICE r3: a per-device buffer let two launches on different streams race on it; the
-    # launch zeroes it itself)
-    wc = torch.empty(1, dtype=torch.int64, device=dev)
-    keep.append(wc)
-    a.work_counter = wc.data_ptr()
-    a.status = status_word(dev).data_ptr()
-    with torch.cuda.device(dev):
-        if launch_timer is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        L.check(L.lib().fsn_render_rays_occgrid_ex(C.byref(pm.desc), pm.prec, _p(pm.blob), C.byref(a), *march,
-                                                   _p(slots.get("t1")) if slots else None, _stream()),
-                "fsn_render_rays_occgrid_ex")
-        if launch_timer is not None:
-            e1.record()
-            launch_timer.append((e0, e1))
-        if want_extras:
-            n_kept = counts["n_kept"]
-            incl = torch.cumsum(n_kept, 0, dtype=torch.int64)
-            N = int(incl[-1].item()) if R > 0 else 0  # the one host read: the sample count sizes the outputs
-            ri = torch.empty(N, dtype=torch.int64, device=dev)
-            ts, te = torch.empty(N, device=dev), torch.empty(N, device=dev)
-            ex = {k: torch.empty(N, device=dev) for k in ("weights", "alphas", "trans", "sigmas")}
-            ex["rgbs"] = torch.empty(N, 3, device=dev)
-            if N > 0:
-                order = ("weights", "alphas", "trans", "sigmas", "rgbs")
-                sp = (C.c_void_p * 5)(*[slots[k].data_ptr() for k in order])
-                op = (C.c_void_p * 5)(*[ex[k].data_ptr() for k in order])
-                L.check(L.lib().fsn_occ_gather_ex(_p(n_kept), _p(incl - n_kept), _p(slots["t0"]), _p(slots.get("t1")),
-                                                  int(max_steps), R, float(step), _p(ri), _p(ts), _p(te), sp, op, _stream()),
-                        "fsn_occ_gather_ex")
-            return colors, opacity, depth, counts, (ri, ts, te, ex)
+    _occ_launch(pm, h, march, slots.get("t1"), dev, timed=True)
+    if want_extras:
+        return colors, opacity, depth, counts, _occ_gather(counts["n_kept"], slots["t0"], slots.get("t1"), cap, R, step, slots)
     return colors, opacity, depth, counts
 
 
@@ -1431,10 +1345,9 @@ def packed_visibility(sigmas: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indi
     sig, t0, t1 = _f32(sigmas, "sigmas").reshape(-1), _f32(t_starts, "t_starts"), _f32(t_ends, "t_ends")
     N = sig.numel()
     keep = torch.zeros(N, device=sig.device, dtype=torch.uint8)
-    with torch.cuda.device(sig.device):
-        L.check(L.lib().fsn_packed_visibility(_p(sig), _p(t0), _p(t1), _p(_i64(ray_indices, "ray_indices")), N, int(n_rays),
-                                              float(early_stop_eps), float(alpha_thre), _p(keep), _stream()),
-                "fsn_packed_visibility")
+    ri = _i64(ray_indices, "ray_indices")
+    _launch("fsn_packed_visibility", sig.device, _p(sig), _p(t0), _p(t1), _p(ri), N, int(n_rays), float(early_stop_eps),
+            float(alpha_thre), _p(keep))
     return keep.bool()
 
 
@@ -1443,9 +1356,8 @@ def occgrid_update(occs: Tensor, bits: Tensor, cells: Optional[Tensor], vals: Op
     """occs[cells] = max(occs[cells]*decay, vals) (unique cells), then bits = occs > threshold (device scalar)."""
     n = 0 if cells is None else cells.numel()
     thr = None if threshold is None else _f32(threshold, "threshold").reshape(1)
-    with torch.cuda.device(occs.device):
-        L.check(L.lib().fsn_occgrid_update(_p(occs), occs.numel(), _p(cells), _p(None if vals is None else _f32(vals, "vals")),
-                                           n, float(decay), _p(thr), _p(bits), _stream()), "fsn_occgrid_update")
+    vals = _opt_f32(vals, "vals")
+    _launch("fsn_occgrid_update", occs.device, _p(occs), occs.numel(), _p(cells), _p(vals), n, float(decay), _p(thr), _p(bits))
 
 
 def occgrid_select(bits: Tensor, aabb: Sequence[float], res: int, levels: int, lvl: int, all_cells: bool, n_uniform: int,
@@ -1464,19 +1376,16 @@ def occgrid_select(bits: Tensor, aabb: Sequence[float], res: int, levels: int, l
     if scratch is None and not all_cells and n_occupied > 0:
         scratch = torch.empty(res3 // 32 + 1, dtype=torch.int32, device=dev)
     ab = (C.c_float * 6)(*[float(v) for v in aabb])
-    with torch.cuda.device(dev):
-        L.check(L.lib().fsn_occgrid_select(_p(bits), int(res), int(levels), int(lvl), ab, 1 if all_cells else 0, int(n_uniform),
-                                           int(n_occupied), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _p(scratch), _p(cells),
-                                           _p(x), _stream()), "fsn_occgrid_select")
+    _launch("fsn_occgrid_select", dev, _p(bits), int(res), int(levels), int(lvl), ab, 1 if all_cells else 0, int(n_uniform),
+            int(n_occupied), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _p(scratch), _p(cells), _p(x))
     return cells, x
 
 
 def occgrid_update_multi(occs: Tensor, pending: Tensor, cells: Tensor, vals: Tensor, decay: float) -> None:
     """occs[c] = max(occs[c]*decay, max of the vals drawn for c); `cells` may repeat (fsn_occgrid_update_multi)."""
     n = cells.numel()
-    with torch.cuda.device(occs.device):
-        L.check(L.lib().fsn_occgrid_update_multi(_p(occs), occs.numel(), _p(pending), _p(cells), _p(_f32(vals, "vals").reshape(-1)),
-                                                 n, float(decay), _stream()), "fsn_occgrid_update_multi")
+    vals = _f32(vals, "vals").reshape(-1)
+    _launch("fsn_occgrid_update_multi", occs.device, _p(occs), occs.numel(), _p(pending), _p(cells), _p(vals), n, float(decay))
 
 
 def occgrid_refresh(pm: PackedMLP, bits: Tensor, aabb: Sequence[float], res: int, levels: int, all_cells: bool,
@@ -1495,19 +1404,16 @@ def occgrid_refresh(pm: PackedMLP, bits: Tensor, aabb: Sequence[float], res: int
         raise ValueError("occgrid_refresh: one seed per level")
     ab = (C.c_float * 6)(*[float(v) for v in aabb])
     sd = (C.c_uint64 * int(levels))(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in seeds])
-    pmk = None if pos_mask is None else _f32(pos_mask, "pos_mask")
-    with torch.cuda.device(dev):
-        L.check(L.lib().fsn_occgrid_refresh(C.byref(pm.desc), pm.prec, _p(pm.blob), _p(pmk), _p(bits), int(res), int(levels), ab,
-                                            1 if all_cells else 0, int(n_uniform), int(n_occupied), sd, float(step),
-                                            _p(prefix), _p(pending), _p(status_word(dev)), _stream()), "fsn_occgrid_refresh")
+    pmk = _opt_f32(pos_mask, "pos_mask")
+    _launch("fsn_occgrid_refresh", dev, C.byref(pm.desc), pm.prec, _p(pm.blob), _p(pmk), _p(bits), int(res), int(levels), ab,
+            1 if all_cells else 0, int(n_uniform), int(n_occupied), sd, float(step), _p(prefix), _p(pending),
+            _p(status_word(dev)))
 
 
 def occgrid_apply_pending(occs: Tensor, pending: Tensor, decay: float) -> None:
     """occs[c] = max(occs[c] * decay, pending[c]) for the cells a refresh touched; `pending` is cleared
     (fsn_occgrid_apply_pending: the second half of occgrid_update_multi)."""
-    with torch.cuda.device(occs.device):
-        L.check(L.lib().fsn_occgrid_apply_pending(_p(occs), occs.numel(), _p(pending), float(decay), _stream()),
-                "fsn_occgrid_apply_pending")
+    _launch("fsn_occgrid_apply_pending", occs.device, _p(occs), occs.numel(), _p(pending), float(decay))
 
 
 def occgrid_visibility(aabb: Sequence[float], res: int, levels: int, cams: Tensor, width: int, height: int,
@@ -1523,10 +1429,8 @@ def occgrid_visibility(aabb: Sequence[float], res: int, levels: int, cams: Tenso
         raise ValueError("occgrid_visibility: visible must be int32 [levels res^3 / 32]")
     ab = (C.c_float * 6)(*[float(v) for v in aabb])
     wf, hf, nr = (0.0, 0.0, 0.0) if ndc is None else (float(v) for v in ndc)
-    with torch.cuda.device(visible.device):
-        L.check(L.lib().fsn_occgrid_visibility(ab, int(res), int(levels), _p(cams), cams.shape[0], int(width), int(height),
-                                               float(near_plane), int(min_views), 0 if ndc is None else 1, wf, hf, nr,
-                                               _p(visible), _stream()), "fsn_occgrid_visibility")
+    _launch("fsn_occgrid_visibility", visible.device, ab, int(res), int(levels), _p(cams), cams.shape[0], int(width),
+            int(height), float(near_plane), int(min_views), 0 if ndc is None else 1, wf, hf, nr, _p(visible))
 
 
 def occgrid_update_masked(occs: Tensor, bits: Optional[Tensor], visible: Tensor, occ_thre: float, scratch: Tensor,
@@ -1536,9 +1440,8 @@ def occgrid_update_masked(occs: Tensor, bits: Optional[Tensor], visible: Tensor,
     holding -1 becomes 0).  scratch: float64 [2048].  No host sync."""
     if scratch.dtype != torch.float64 or scratch.numel() < 2048:
         raise ValueError("occgrid_update_masked: scratch must be float64 [2048]")
-    with torch.cuda.device(occs.device):
-        L.check(L.lib().fsn_occgrid_update_masked(_p(occs), occs.numel(), _p(visible), float(occ_thre), 1 if revive else 0,
-                                                  _p(scratch), _p(bits), _stream()), "fsn_occgrid_update_masked")
+    _launch("fsn_occgrid_update_masked", occs.device, _p(occs), occs.numel(), _p(visible), float(occ_thre),
+            1 if revive else 0, _p(scratch), _p(bits))
 
 
 # ------------------------------------------------------------------ evaluation metrics (run-nerf.py:108-191)
@@ -1563,14 +1466,10 @@ def ssim_nchw(x: Tensor, y: Tensor, window: int, use_sample_covariance: bool, da
     assert y.shape == x.shape and y.device == x.device
     dev = x.device
     out = torch.empty(N + 1, dtype=torch.float64, device=dev)
-    nws = L.lib().fsn_ssim_workspace_doubles(N, Ch, H, W)
-    if nws < 0:
-        L.check(int(nws), "fsn_ssim_workspace_doubles")
-    ws = torch.empty(max(int(nws), 1), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        L.check(L.lib().fsn_ssim(_p(x), _p(y), N, Ch, H, W, _nchw_strides(x), _nchw_strides(y), int(window),
-                                 1 if use_sample_covariance else 0, float(data_range), float(K1), float(K2), _p(ws), _p(out),
-                                 _p(smap), None if smap is None else _nchw_strides(smap), _stream()), "fsn_ssim")
+    ws = torch.empty(max(_size("fsn_ssim_workspace_doubles", None, N, Ch, H, W), 1), dtype=torch.float64, device=dev)
+    _launch("fsn_ssim", dev, _p(x), _p(y), N, Ch, H, W, _nchw_strides(x), _nchw_strides(y), int(window),
+            1 if use_sample_covariance else 0, float(data_range), float(K1), float(K2), _p(ws), _p(out), _p(smap),
+            None if smap is None else _nchw_strides(smap))
     return out
 
 
@@ -1582,13 +1481,8 @@ def psnr_nchw(x: Tensor, y: Tensor) -> Tensor:
     assert y.shape == x.shape and y.device == x.device
     dev = x.device
     out = torch.empty(N + 1, dtype=torch.float32, device=dev)
-    nws = L.lib().fsn_psnr_workspace_doubles(N, Ch, H, W)
-    if nws < 0:
-        L.check(int(nws), "fsn_psnr_workspace_doubles")
-    ws = torch.empty(max(int(nws), 1), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        L.check(L.lib().fsn_psnr(_p(x), _p(y), N, Ch, H, W, _nchw_strides(x), _nchw_strides(y), _p(ws), _p(out), _stream()),
-                "fsn_psnr")
+    ws = torch.empty(max(_size("fsn_psnr_workspace_doubles", None, N, Ch, H, W), 1), dtype=torch.float64, device=dev)
+    _launch("fsn_psnr", dev, _p(x), _p(y), N, Ch, H, W, _nchw_strides(x), _nchw_strides(y), _p(ws), _p(out))
     return out
 
 
@@ -1603,13 +1497,11 @@ def lpips_pack(conv_w: Sequence[Tensor], conv_b: Sequence[Tensor], lin_w: Sequen
              scale.detach().to(dev, torch.float32).reshape(-1).contiguous()]
     if not all(t.is_cuda for t in keep):
         raise RuntimeError("lpips_pack: expected GPU tensors (the HIP path has no CPU fallback)")
-    nbytes = int(L.lib().fsn_lpips_pack_bytes())
+    nbytes = _size("fsn_lpips_pack_bytes", None)
     if out is None or out.numel() != nbytes or out.device != dev:
         out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    ptrs = [C.c_void_p(t.data_ptr()) for t in keep]
-    w_arr, b_arr, l_arr = (C.c_void_p * 13)(*ptrs[:13]), (C.c_void_p * 13)(*ptrs[13:26]), (C.c_void_p * 5)(*ptrs[26:31])
-    with torch.cuda.device(dev):
-        L.check(L.lib().fsn_lpips_pack(w_arr, b_arr, l_arr, ptrs[31], ptrs[32], _p(out), _stream()), "fsn_lpips_pack")
+    _launch("fsn_lpips_pack", dev, _ptr_array(keep[:13]), _ptr_array(keep[13:26]), _ptr_array(keep[26:31]), _p(keep[31]),
+            _p(keep[32]), _p(out))
     return out
 
 
@@ -1622,11 +1514,7 @@ def lpips_vgg(packed: Tensor, x: Tensor, y: Tensor, normalize: bool) -> Tuple[Te
     dev = x.device
     out = torch.empty(N, dtype=torch.float32, device=dev)
     per = torch.empty(5, N, dtype=torch.float32, device=dev)
-    nws = L.lib().fsn_lpips_workspace_floats(H, W)
-    if nws < 0:
-        L.check(int(nws), "fsn_lpips_workspace_floats")
-    ws = torch.empty(int(nws), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        L.check(L.lib().fsn_lpips_vgg(_p(packed), _p(x), _p(y), N, H, W, _nchw_strides(x), _nchw_strides(y),
-                                      1 if normalize else 0, _p(out), _p(per), _p(ws), _stream()), "fsn_lpips_vgg")
+    ws = torch.empty(_size("fsn_lpips_workspace_floats", None, H, W), dtype=torch.float32, device=dev)
+    _launch("fsn_lpips_vgg", dev, _p(packed), _p(x), _p(y), N, H, W, _nchw_strides(x), _nchw_strides(y),
+            1 if normalize else 0, _p(out), _p(per), _p(ws))
     return out, per

@@ -170,7 +170,7 @@ def test_ops_keywords_are_checked_before_the_launch():
     for fn in (ops.render_occ_fused, ops.occ_sample_fused):
         sig = inspect.signature(fn).parameters
         assert sig["cone_angle"].default == 0.0 and sig["t_min"].default is None and sig["t_max"].default is None
-    keep = []
+    keep = ops._Held(None)
     with pytest.raises(TypeError, match="camera"):
         ops._occ_march_options(16, 0.0, torch.zeros(16), None, object(), keep)
     assert ops._occ_march_options(16, 0.5, None, None, object(), keep) == (0.5, None, None)
