@@ -201,8 +201,16 @@ struct WStream {
   // while it runs).  Both kinds of tile stream the SAME blob from its first phase and differ in where they stop, so the
   // stager can always wrap to phase 0; a tile says how long it is when it starts.  At that moment exactly kLook + 1
   // phases of it are staged (the invariant of init() / the phase openings).  init() with nphB = kDynamicPhases.
+  // Invariant on return: s_left >= 1 is the number of stages until the stager goes back to phase 0, i.e. the phases of
+  // this tile not staged yet - or, when the tile has exactly kLook + 1 phases and all of it is staged already, the
+  // stager stands at phase 0 now with the dynamic count.  stage() / next_stage() wrap on --s_left == 0 and so must
+  // never be entered with s_left == 0: it would count down from 2^32 - 1 and the loads would run on past the blob.
+  // Needs nph >= kLook + 1 (build_geom's smallest pass has 3 phases; the host entry point of render_occ.hip checks).
   static constexpr uint32_t kDynamicPhases = 1u << 30;
-  __device__ __forceinline__ void begin_tile(uint32_t nph) { s_left = nph - (uint32_t)(kLook + 1); }
+  __device__ __forceinline__ void begin_tile(uint32_t nph) {
+    s_left = nph - (uint32_t)(kLook + 1);
+    if (__builtin_expect(s_left == 0, 0)) advance_pass_();  // (wave-uniform: one scalar compare per tile)
+  }
   // Open the next phase: its loads have landed for every wave (vmcnt counts in issue order, so
   // allowing the (kLook-1)*kGldsPerWave youngest loads to stay in flight retires exactly the oldest
   // staged phase), every wave is past the phase whose slot is restaged next.

@@ -157,6 +157,10 @@ FSN_HD uint16_t half_rne(float f, bool f16) { return f16 ? f16_rne(f) : bf16_rne
 FSN_HD float half_to_f32(uint16_t h, bool f16) { return f16 ? f16_to_f32(h) : bf16_to_f32(h); }
 
 // Fills `G` from the descriptor; returns 0 or an FSN_E_* code (message via set_error on host).
+// What is accepted here is what can be PACKED: n_layers 2..16 at either width.  The kernels keep the aux area in LDS
+// (kAuxCapFloats = 3456 floats, mlp_dev.hpp) and refuse a geometry whose aux_floats = (n_layers + 5) d_hidden + 36,
+// rounded up to 64, does not fit ("network too deep"): 128-wide networks run up to 16 layers, 256-wide ones up to 8
+// (8x256 needs 3392, 9x256 3648).  The shortest pass - 2 layers x 128, no skip, single-pass units - has 3 phases.
 inline int build_geom(const fsn_mlp_desc& d, int prec, NetGeom& G, const char** why) {
   *why = "";
   if (prec < 0 || (prec > FSN_PREC_FP16X3U && prec != FSN_PREC_FP16X2)) { *why = "unknown precision mode"; return FSN_E_INVALID; }

@@ -468,6 +468,10 @@ static int occ_render_launch(const char* who, const fsn_mlp_desc* desc, int prec
                 FSN_E_INVALID, "%s: no rays and no valid camera", who);
   }
   FSN_REQUIRE(G.aux_floats <= kAuxCapFloats, FSN_E_UNSUPPORTED, "%s: network too deep for LDS", who);
+  // WStream::begin_tile: a tile starts with kLook + 1 of its phases staged.  build_geom's smallest density pass
+  // (2 layers x 128, no skip, single pass) has exactly 3.
+  FSN_REQUIRE(G.nph_density >= kLook + 1, FSN_E_UNSUPPORTED, "%s: a pass of %d phases is shorter than the weight stream's look-ahead",
+              who, G.nph_density);
   k.net = net_params(*desc, G, blob, a.status);
   k.a = a;
   k.cam_hw = (float)(a.cam_W * 0.5);
