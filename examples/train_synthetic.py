@@ -6,7 +6,7 @@ estimator.update_every_n_steps) and evaluated with render_frame + PSNR and SSIM 
 
     python examples/train_synthetic.py [--estimator occgrid|stratified|propnet] [--iters 400] [--hw 64] [--u8-dataset]
                                        [--depth-weight W] [--distortion-weight W] [--cone-angle A] [--near-plane T]
-                                       [--mark-invisible] [--min-views K]
+                                       [--mark-invisible] [--min-views K] [--ssim-weight W --patch P --patches B]
 
 --u8-dataset: the teacher's frames become uint8 "photographs" (R.to8b) held in a device-resident RayDataset; the loop
 takes its batches from a RayLoader the way run-nerf.py:236-240 takes them from its DataLoader, and the held-out view
@@ -26,6 +26,11 @@ prop_samples=(128,), num_samples=64, uniform in disparity between near and far, 
 `estimator.update_every_n_steps(extras["trans"].reshape(n_rays, 64), requires_grad=True)` takes the interlevel loss's
 step on the proposal network.
 
+--ssim-weight W (0 by default: the loop is then the one above; needs --u8-dataset): a structural (D-SSIM) term on
+rendered patches.  A PatchLoader serves --patches B patches of --patch P x P pixels per step; their rays are concatenated
+to the ray batch for ONE render_rays call, and the rendered tail, reshaped to [B, P, P, 3], goes through
+core.loss.SSIMLoss against the photographs' patches: loss = MSE(ray batch) + W * (1 - SSIM(patches)).
+
 --mark-invisible (off by default): before the first step the occupancy estimator takes every cell that fewer than
 --min-views K (default 1) training views see out of the grid for good (OccGridEstimator.mark_invisible_from_views: a
 conservative frustum / box test); no later refresh switches such a cell on.
@@ -42,10 +47,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import fs_nerf_amd  # noqa: E402,F401
 from fs_nerf_amd.core import metrics  # noqa: E402
 from fs_nerf_amd.core import models as M  # noqa: E402
-from fs_nerf_amd.core.loss import DistortionLoss, WeightNormRegularizer  # noqa: E402
+from fs_nerf_amd.core.loss import DistortionLoss, SSIMLoss, WeightNormRegularizer  # noqa: E402
 from fs_nerf_amd.core.optim import FusedAdam  # noqa: E402
 from fs_nerf_amd.core.scheduler import ExponentialDecay  # noqa: E402
-from fs_nerf_amd.nerfdata import FrameLoader, RayDataset, RayLoader  # noqa: E402
+from fs_nerf_amd.nerfdata import FrameLoader, PatchLoader, RayDataset, RayLoader  # noqa: E402
 from fs_nerf_amd.render import rendering as R  # noqa: E402
 from fs_nerf_amd.render.occgrid import OccGridEstimator  # noqa: E402
 from fs_nerf_amd.render.propnet import PropNetEstimator  # noqa: E402
@@ -98,7 +103,13 @@ def main():
                          "(OccGridEstimator.mark_invisible_from_views)")
     ap.add_argument("--min-views", type=int, default=1,
                     help="with --mark-invisible: a cell stays only if at least this many training views see it (few-shot: 2)")
+    ap.add_argument("--ssim-weight", type=float, default=0.0,
+                    help="opt-in: weight of 1 - SSIM on rendered patches (core.loss.SSIMLoss; needs --u8-dataset)")
+    ap.add_argument("--patch", type=int, default=16, help="with --ssim-weight: the patches are PATCH x PATCH pixels (at least 11)")
+    ap.add_argument("--patches", type=int, default=8, help="with --ssim-weight: patches per step")
     a = ap.parse_args()
+    if a.ssim_weight and not a.u8_dataset:
+        ap.error("--ssim-weight takes its patches from the device-resident dataset: add --u8-dataset")
     if a.cone_angle and a.estimator != "occgrid":
         ap.error("--cone-angle belongs to the occupancy estimator")
     if a.mark_invisible and a.estimator != "occgrid":
@@ -129,6 +140,10 @@ def main():
         train_set = RayDataset(frames8, torch.stack(poses), hwf, near=near, far=far, device=dev)
         train_loader = RayLoader(train_set, a.batch, shuffle=True, seed=0)
         iterator = iter(train_loader)
+        if a.ssim_weight:
+            patch_loader = PatchLoader(train_set, a.patch, a.patches, shuffle=True, seed=1)
+            patch_iterator = iter(patch_loader)
+            ssim_loss = SSIMLoss(gaussian_weights=True, data_range=1.0, channel_axis=-1)
         with torch.no_grad():
             ref8 = R.to8b(R.render_frame(hwf, near, far, held_out, 1 << 20, t_est, teacher, white_bkgd=True, device=dev)[0])
         val_loader = FrameLoader(RayDataset(ref8.reshape(1, a.hw, a.hw, 3), held_out[None], hwf, near=near, far=far, device=dev))
@@ -179,10 +194,21 @@ def main():
         else:
             idx = torch.randint(0, ro.shape[0], (a.batch,), device=dev, generator=gen)
             rays_o, rays_d, rgb_gt = ro[idx], rd[idx], gt[idx]
+        n_batch = rays_o.shape[0]
+        if a.ssim_weight:  # the patches' rays ride in the same render_rays call, behind the ray batch
+            try:
+                patch_o, patch_d, patch_gt = next(patch_iterator)
+            except StopIteration:
+                patch_iterator = iter(patch_loader)
+                patch_o, patch_d, patch_gt = next(patch_iterator)
+            rays_o, rays_d = torch.cat([rays_o, patch_o]), torch.cat([rays_d, patch_d])
         (rgb, _, depth, extras), ray_indices, _ = R.render_rays(rays_o, rays_d, estimator, model, train=True, white_bkgd=True,
                                                                 render_step_size=step, device=dev, full_grad=full_grad,
                                                                 sampling_kwargs=sampling_kwargs)
-        loss = torch.nn.functional.mse_loss(rgb, rgb_gt)
+        loss = torch.nn.functional.mse_loss(rgb[:n_batch], rgb_gt)
+        if a.ssim_weight:
+            loss = loss + a.ssim_weight * ssim_loss(rgb[n_batch:].view(-1, a.patch, a.patch, 3),
+                                                    patch_gt.view(-1, a.patch, a.patch, 3))
         if a.depth_weight and depth.requires_grad:  # (an all-background batch renders no samples: nothing to supervise)
             hit = (gd[idx] > near).float()  # render_frame clamps depth to [near, far]: `near` = the teacher saw background
             loss = loss + a.depth_weight * (hit * (depth - gd[idx]) ** 2).sum() / hit.sum().clamp(min=1.0)

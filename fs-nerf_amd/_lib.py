@@ -80,6 +80,8 @@ SIGNATURES = {
     "fsn_build_rays": (_i, [_vp, _i64, _i, _i, _d, _i, _d, _vp, _vp, _vp, _vp, _vp]),
     "fsn_ray_batch": (_i, [_vp, _i64, _vp, _i, _i, _i, _d, _i, _d, _i, _i, C.c_uint64, _i64, _vp, _i64, _i64, _vp, _vp, _vp,
                            _vp, _vp]),
+    "fsn_ray_patch_batch": (_i, [_vp, _i64, _vp, _i, _i, _i, _d, _i, _d, _i, _i, C.c_uint64, _i64, _vp, _i64, _i64, _i, _i,
+                                 _vp, _vp, _vp, _vp, _vp]),
     "fsn_ray_perm_host": (_i, [_i64, C.c_uint64, _i64, _i64, _i64, _vp]),
     "fsn_debug_report_raydata": (_i, [_vp]),
     "fsn_posenc_fwd": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp]),
@@ -158,6 +160,9 @@ SIGNATURES = {
     "fsn_psnr_workspace_doubles": (_i64, [_i64, _i, _i, _i]),
     "fsn_psnr": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "fsn_debug_report_metrics": (_i, [_vp]),
+    "fsn_ssim_grad_workspace_doubles": (_i64, [_i64, _i, _i, _i]),
+    "fsn_ssim_grad": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fsn_debug_report_ssim_grad": (_i, [_vp]),
     "fsn_lpips_pack_bytes": (_i64, []),
     "fsn_lpips_pack": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fsn_lpips_workspace_floats": (_i64, [_i, _i]),

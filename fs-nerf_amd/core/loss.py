@@ -2,13 +2,18 @@
 segmented reduction on the GPU instead of a Python loop with one kernel launch per ray; the distortion loss on the
 compositor's weights (this package's own, the first consumer of `full_grad`); and the weight-norm
 "frequency" regulariser of the training loop (row f1, src/run-nerf.py:266-279) as one reduction over the flat
-parameter arena."""
+parameter arena; and the structural (D-SSIM) term on rendered patches (this package's own: the evaluation metric of
+core/metrics.py with a backward)."""
 import ctypes as C
+from typing import Optional
 
 import torch
 from torch import Tensor
+from torch.autograd.function import once_differentiable
 
+from .. import _lib as L
 from .. import ops
+from . import metrics
 
 
 class OcclusionRegularizer:
@@ -37,6 +42,75 @@ class DistortionLoss:
 
     def __call__(self, weights: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor, n_rays: int) -> Tensor:
         return ops.distortion(weights, t_starts, t_ends, ray_indices, n_rays).mean()
+
+
+class _SSIMLossFn(torch.autograd.Function):
+    """1 - SSIM in one node: forward = fsn_ssim (the evaluation metric's own launch, unchanged), backward = one
+    fsn_ssim_grad launch for the inputs that need a gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, target, loss):
+        x, y = metrics._as_nchw(pred, loss.channel_axis), metrics._as_nchw(target, loss.channel_axis)
+        out = ops.ssim_nchw(x, y, loss.window, loss.use_sample_covariance, loss.data_range, loss.K1, loss.K2)
+        N = x.shape[0]
+        ctx.save_for_backward(pred, target)
+        ctx.loss, ctx.N = loss, N
+        val = out[N] if loss.reduction == "mean" else out[:N]
+        return (1.0 - val).to(torch.float32)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_out):
+        pred, target = ctx.saved_tensors
+        loss, N = ctx.loss, ctx.N
+        want_dx, want_dy = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_dx or want_dy):
+            return None, None, None
+        # loss = 1 - mean_n ssim_n ("mean") or 1 - ssim_n ("none"): dL / d ssim_n
+        up = -d_out.to(torch.float64)
+        up = (up / N).expand(N) if loss.reduction == "mean" else up
+        d_pred = torch.empty_like(pred) if want_dx else None
+        d_target = torch.empty_like(target) if want_dy else None
+        ca = loss.channel_axis
+        ops.ssim_grad_nchw(metrics._as_nchw(pred, ca), metrics._as_nchw(target, ca), loss.window, loss.use_sample_covariance,
+                           loss.data_range, loss.K1, loss.K2, up, want_dx=want_dx, want_dy=want_dy,
+                           dx=None if d_pred is None else metrics._as_nchw(d_pred, ca),
+                           dy=None if d_target is None else metrics._as_nchw(d_target, ca))
+        return d_pred, d_target, None
+
+
+class SSIMLoss:
+    """The structural (D-SSIM) term for patch-mode training: `loss(pred, target)` = 1 - metrics.ssim(pred, target, ...)
+    with gradients to both inputs - 0-dim float32 (reduction="mean", the mean over the N images or patches) or
+    float32 (N,) ("none").  The value is the evaluation metric's own (fsn_ssim, float64; 1 - value is taken in float64
+    and rounded once); the backward is one fsn_ssim_grad launch in float64 (csrc/ssim_grad.hip), only for the inputs
+    that need a gradient, and cannot be differentiated again.  Shapes and `channel_axis` as metrics.ssim: (H, W),
+    (H, W, C), (N, H, W, C) with channel_axis=-1, (N, C, H, W) with 1; float32 GPU tensors of any strides, read in
+    place.  Windows: gaussian_weights=True (sigma 1.5, 11 x 11) and the 7 x 7 box; an image must hold one window."""
+
+    def __init__(self, gaussian_weights: bool = True, use_sample_covariance: bool = True, data_range: float = 1.0,
+                 K1: float = 0.01, K2: float = 0.03, channel_axis: Optional[int] = -1, reduction: str = "mean"):
+        if reduction not in ("mean", "none"):
+            raise ValueError(f"reduction must be 'mean' or 'none', got {reduction!r}")
+        if data_range is None:
+            raise ValueError("data_range is required (the reference passes data_range=1.0)")
+        self.window = L.FSN_SSIM_GAUSSIAN if gaussian_weights else L.FSN_SSIM_UNIFORM
+        self.win = metrics._GAUSS_WIN if gaussian_weights else metrics._UNIFORM_WIN
+        self.use_sample_covariance, self.data_range = bool(use_sample_covariance), float(data_range)
+        self.K1, self.K2, self.channel_axis, self.reduction = float(K1), float(K2), channel_axis, reduction
+
+    def __call__(self, pred: Tensor, target: Tensor) -> Tensor:
+        if pred.shape != target.shape:
+            raise ValueError(f"pred and target must have the same shape: {tuple(pred.shape)} vs {tuple(target.shape)}")
+        x = metrics._as_nchw(pred, self.channel_axis)  # (raises ValueError for a shape metrics.ssim does not take)
+        if x.shape[2] < self.win or x.shape[3] < self.win:
+            raise ValueError(f"win_size exceeds image extent: {x.shape[2]} x {x.shape[3]} image, {self.win} x {self.win} window")
+        for t, name in ((pred, "pred"), (target, "target")):
+            if not t.is_cuda:
+                raise RuntimeError(f"SSIMLoss: {name} is not a GPU tensor (the HIP path has no CPU fallback)")
+            if t.dtype != torch.float32:
+                raise TypeError(f"SSIMLoss: {name} must be float32, got {t.dtype} (a cast would hide it from autograd)")
+        return _SSIMLossFn.apply(pred, target, self)
 
 
 class _WeightNormFn(torch.autograd.Function):

@@ -22,33 +22,15 @@
 #include <cmath>
 
 namespace fsn {
-
 // debug build: the LDS indices of k_ssim_tile are range-checked (common.hpp), read by fsn_debug_report_metrics
 FSN_DEBUG_DEFINE_RECORD(g_dbg_metrics)
+}  // namespace fsn
 #define FSN_DEBUG_RECORD g_dbg_metrics
+#include "ssim_dev.hpp"  // tile geometry, window parameters and the moments of steps 1-3, shared with ssim_grad.hip
 
-constexpr int kSsimTile = 32;
-constexpr int kSsimThreads = 256;
-constexpr int kSsimRowsPerThread = kSsimTile * kSsimTile / kSsimThreads;  // 4
-constexpr int kSqErrChunk = kSsimThreads * 16;                              // elements per squared-error workgroup
+namespace fsn {
 
-struct Strides4 {
-  int64_t n, c, h, w;
-};
-
-struct SsimParams {
-  double taps[11];  // normalised window taps, 2r+1 used
-  double cn;       // NP / (NP - 1) or 1
-  double C1, C2;
-};
-
-// scipy.ndimage mode='reflect' (half-sample symmetric) for |overhang| <= r < n; indices outside that range only feed
-// outputs that are not written and are clamped into the image so that every load stays in bounds.
-__device__ __forceinline__ int reflect_idx(int i, int n) {
-  i = i < 0 ? -i - 1 : i;
-  i = i >= n ? 2 * n - 1 - i : i;
-  return i < 0 ? 0 : (i >= n ? n - 1 : i);
-}
+constexpr int kSqErrChunk = kSsimThreads * 16;  // elements per squared-error workgroup
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -74,7 +56,7 @@ __global__ void __launch_bounds__(kSsimThreads) k_ssim_tile(const float* __restr
                                                             int C, int H, int W, Strides4 sx, Strides4 sy, SsimParams p,
                                                             int tiles_w, int tiles, float* __restrict__ smap, Strides4 ss,
                                                             double* __restrict__ partials) {
-  constexpr int T = kSsimTile, HB = T + 2 * R, K = 2 * R + 1;
+  constexpr int T = kSsimTile, HB = T + 2 * R;
   __shared__ float lx[HB][HB + 1];
   __shared__ float ly[HB][HB + 1];
   __shared__ double hm[5][HB][T + 1];  // horizontal pass: x, y, x^2, y^2, xy
@@ -89,59 +71,11 @@ __global__ void __launch_bounds__(kSsimThreads) k_ssim_tile(const float* __restr
   const float* xb = x + n * sx.n + c * sx.c;
   const float* yb = y + n * sy.n + c * sy.c;
 
-  // 1. halo through reflect indexing
-  for (int i = threadIdx.x; i < HB * HB; i += kSsimThreads) {
-    const int r = i / HB, q = i - r * HB;
-    const int hh = reflect_idx(h0 - R + r, H), ww = reflect_idx(w0 - R + q, W);
-    FSN_AT(FSN_AT(lx, r), q) = xb[hh * sx.h + ww * sx.w];
-    FSN_AT(FSN_AT(ly, r), q) = yb[hh * sy.h + ww * sy.w];
-  }
-  __syncthreads();
-
-  // 2. horizontal pass
-  for (int i = threadIdx.x; i < HB * T; i += kSsimThreads) {
-    const int r = i / T, q = i - r * T;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0;
-#pragma unroll
-    for (int t = 0; t < K; ++t) {
-      const double wt = p.taps[t];
-      const double u = FSN_AT(FSN_AT(lx, r), q + t), v = FSN_AT(FSN_AT(ly, r), q + t);
-      a0 = __builtin_fma(wt, u, a0);
-      a1 = __builtin_fma(wt, v, a1);
-      a2 = __builtin_fma(wt, u * u, a2);  // u * u, v * v, u * v: exact in float64 for float32 inputs
-      a3 = __builtin_fma(wt, v * v, a3);
-      a4 = __builtin_fma(wt, u * v, a4);
-    }
-    FSN_AT(FSN_AT(hm[0], r), q) = a0;
-    FSN_AT(FSN_AT(hm[1], r), q) = a1;
-    FSN_AT(FSN_AT(hm[2], r), q) = a2;
-    FSN_AT(FSN_AT(hm[3], r), q) = a3;
-    FSN_AT(FSN_AT(hm[4], r), q) = a4;
-  }
-  __syncthreads();
-
-  // 3. vertical pass: column q, output rows r0 .. r0+3 of the tile
+  // 1-3. the windowed moments (ssim_dev.hpp): column q, output rows r0 .. r0+3 of the tile
   constexpr int RT = kSsimRowsPerThread;
   const int q = threadIdx.x % T, r0 = (threadIdx.x / T) * RT;
   double m[5][RT];
-#pragma unroll
-  for (int k = 0; k < 5; ++k)
-#pragma unroll
-    for (int j = 0; j < RT; ++j) m[k][j] = 0.0;
-#pragma unroll
-  for (int s = 0; s < K + RT - 1; ++s) {
-    double v[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) v[k] = FSN_AT(FSN_AT(hm[k], r0 + s), q);
-#pragma unroll
-    for (int j = 0; j < RT; ++j) {
-      const int t = s - j;
-      if (t >= 0 && t < K) {
-#pragma unroll
-        for (int k = 0; k < 5; ++k) m[k][j] = __builtin_fma(p.taps[t], v[k], m[k][j]);
-      }
-    }
-  }
+  ssim_tile_moments<R>(xb, yb, H, W, sx, sy, p, h0, w0, lx, ly, hm, m);
 
   // 4. S, map, interior sum
   const int ow = w0 + q;
@@ -216,22 +150,9 @@ __global__ void __launch_bounds__(kSsimThreads) k_psnr_finish(const double* __re
   if (threadIdx.x == 0) out[N] = (float)(-10.0 * log10(total / ((double)per_image * (double)N)));
 }
 
-static int ssim_radius(int window) { return window == FSN_SSIM_GAUSSIAN ? 5 : 3; }
-
-static int check_strides(const int64_t* s, const char* what) {
-  FSN_REQUIRE(s, FSN_E_INVALID, "%s: null stride array", what);
-  return FSN_OK;
-}
-
-static Strides4 strides4(const int64_t* s) { return Strides4{s[0], s[1], s[2], s[3]}; }
-
 }  // namespace fsn
 
 using namespace fsn;
-
-static int64_t ssim_tiles(int H, int W) {
-  return (int64_t)((H + kSsimTile - 1) / kSsimTile) * ((W + kSsimTile - 1) / kSsimTile);
-}
 
 extern "C" int64_t fsn_ssim_workspace_doubles(int64_t N, int C, int H, int W) {
   FSN_REQUIRE(N >= 0 && C >= 1 && H >= 1 && W >= 1, FSN_E_INVALID, "fsn_ssim_workspace_doubles: bad shape");
@@ -242,35 +163,19 @@ extern "C" int fsn_ssim(const float* x, const float* y, int64_t N, int C, int H,
                         const int64_t* y_strides_host, int window, int use_sample_covariance, double data_range,
                         double K1, double K2, double* workspace, double* out, float* smap,
                         const int64_t* smap_strides_host, fsn_stream_t stream) {
-  FSN_REQUIRE(N >= 0 && C >= 1 && H >= 1 && W >= 1, FSN_E_INVALID, "fsn_ssim: bad shape (N=%lld C=%d H=%d W=%d)",
-              (long long)N, C, H, W);
-  FSN_REQUIRE(window == FSN_SSIM_GAUSSIAN || window == FSN_SSIM_UNIFORM, FSN_E_UNSUPPORTED,
-              "fsn_ssim: unknown window code %d", window);
-  const int r = ssim_radius(window), win = 2 * r + 1;
-  FSN_REQUIRE(H >= win && W >= win, FSN_E_INVALID, "fsn_ssim: image %dx%d is smaller than the %dx%d window", H, W,
-              win, win);
+  int rc = ssim_check_shape("fsn_ssim", N, C, H, W, window);
+  if (rc != FSN_OK) return rc;
+  const int r = ssim_radius(window);
   if (N == 0) return FSN_OK;
   FSN_REQUIRE(x && y && workspace && out, FSN_E_INVALID, "fsn_ssim: null pointer");
-  int rc = check_strides(x_strides_host, "fsn_ssim");
+  rc = check_strides(x_strides_host, "fsn_ssim");
   if (rc == FSN_OK) rc = check_strides(y_strides_host, "fsn_ssim");
   if (rc == FSN_OK && smap) rc = check_strides(smap_strides_host, "fsn_ssim");
   if (rc != FSN_OK) return rc;
   const int64_t tiles = ssim_tiles(H, W), blocks = N * C * tiles;
   FSN_REQUIRE(blocks < (int64_t(1) << 31), FSN_E_UNSUPPORTED, "fsn_ssim: %lld tiles in one call", (long long)blocks);
 
-  SsimParams p{};
-  double taps[11], sum = 0.0;
-  for (int t = 0; t < win; ++t) {
-    const double d = t - r;
-    taps[t] = window == FSN_SSIM_GAUSSIAN ? std::exp(-d * d / (2.0 * 1.5 * 1.5)) : 1.0;
-    sum += taps[t];
-  }
-  for (int t = 0; t < win; ++t) p.taps[t] = taps[t] / sum;
-  const double NP = (double)win * win;
-  p.cn = use_sample_covariance ? NP / (NP - 1.0) : 1.0;
-  p.C1 = (K1 * data_range) * (K1 * data_range);
-  p.C2 = (K2 * data_range) * (K2 * data_range);
-
+  const SsimParams p = ssim_params(window, use_sample_covariance, data_range, K1, K2);
   const Strides4 sx = strides4(x_strides_host), sy = strides4(y_strides_host);
   const Strides4 ss = smap ? strides4(smap_strides_host) : Strides4{0, 0, 0, 0};
   const int tiles_w = (W + kSsimTile - 1) / kSsimTile;

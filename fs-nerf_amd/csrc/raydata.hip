@@ -9,6 +9,8 @@
 //                                  bytes; a multiplication by 1.0f / 255.0f is not)
 //   white background (blender.py:114-117): c * a + (1.0f - a), three separate float32 operations in that order.
 // A latency-bound gather of a few hundred KB: 12-byte rows rule out 16-byte vector stores; plain coalesced stores.
+// k_ray_patch_batch serves P x P patches the same way: position -> shuffled ANCHOR (the patch's top-left pixel) ->
+// the patch's pixels -> the rows k_ray_batch writes for them.
 #include "common.hpp"
 #include "ray_dev.hpp"
 #include "ray_perm.hpp"
@@ -85,6 +87,74 @@ __global__ void __launch_bounds__(256) k_ray_batch(RayBatchArgs a) {
   }
 }
 
+// A batch of P x P patches (fsn_ray_patch_batch): one thread per output row (b P + i) P + j = pixel (i, j) of patch b.
+// `r` is fsn_ray_batch's argument block read over ANCHORS (the patches' top-left pixels): start / count count
+// patches, indices is the explicit anchor list, perm permutes [0, n_anchors); n_rays / per_view are not used.  The row
+// written for a flat ray index is k_ray_batch's, operation for operation (the same rays, the same colour arithmetic).
+struct RayPatchArgs {
+  RayBatchArgs r;
+  int64_t n_anchors, per_view_anchors;  // A, AH * AW
+  int P, dilation, AW, H;
+};
+
+__global__ void __launch_bounds__(256) k_ray_patch_batch(RayPatchArgs pa) {
+  const RayBatchArgs& a = pa.r;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t pp = (int64_t)pa.P * pa.P;
+  if (i >= a.count * pp) return;
+  const int64_t b = i / pp;
+  const int in_patch = (int)(i - b * pp), pi = in_patch / pa.P, pj = in_patch - pi * pa.P;
+  int64_t anchor;
+  if (a.order == FSN_RAY_ORDER_IDENTITY) {
+    anchor = a.start + b;
+  } else if (a.order == FSN_RAY_ORDER_PERMUTED) {
+    anchor = (int64_t)ray_perm_at(a.perm, (uint64_t)(a.start + b));
+  } else {
+    anchor = a.indices[b];
+    if (anchor < 0 || anchor >= pa.n_anchors) {  // never reaches memory
+#ifdef FSN_DEBUG
+      if (atomicAdd(g_dbg_raydata, 1u) == 0u) {
+        g_dbg_raydata[1] = (unsigned)__LINE__;
+        g_dbg_raydata[2] = (unsigned)anchor;
+        g_dbg_raydata[3] = (unsigned)pa.n_anchors;
+      }
+#endif
+      return;
+    }
+  }
+  const int64_t view = anchor / pa.per_view_anchors, rest = anchor - view * pa.per_view_anchors;
+  const int row = (int)(rest / pa.AW) + pi * pa.dilation, col = (int)(rest % pa.AW) + pj * pa.dilation;
+  const int64_t idx = (view * pa.H + row) * a.W + col;
+  if (a.index) a.index[i] = idx;
+  if (a.rays_o || a.rays_d) {
+    float o[3], d[3];
+    pinhole_ray(a.poses + 12 * view, a.half_w, a.half_h, a.focal, row, col, o, d);
+    if (a.ndc) ndc_ray(o, d, a.sx, a.sy, a.near, a.two_near);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      if (a.rays_d) a.rays_d[3 * i + k] = d[k];
+      if (a.rays_o) a.rays_o[3 * i + k] = o[k];
+    }
+  }
+  if (a.rgb) {
+    const uint8_t* px = a.images + idx * a.C;
+    float c[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[k] = (float)px[k] / 255.0f;
+    if (a.white_bkgd) {
+      const float al = (float)px[3] / 255.0f;
+      const float rest_w = 1.0f - al;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const float m = c[k] * al;
+        c[k] = m + rest_w;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) a.rgb[3 * i + k] = c[k];
+  }
+}
+
 }  // namespace fsn
 
 using namespace fsn;
@@ -142,6 +212,80 @@ extern "C" int fsn_ray_batch(const float* poses, int64_t n_views, const uint8_t*
   a.index = index;
   k_ray_batch<<<(unsigned)((count + 255) / 256), 256, 0, as_stream(stream)>>>(a);
   FSN_LAUNCH_CHECK("k_ray_batch");
+  return FSN_OK;
+}
+
+extern "C" int fsn_ray_patch_batch(const float* poses, int64_t n_views, const uint8_t* images, int H, int W, int C,
+                                   double focal, int ndc, double near, int white_bkgd, int order, uint64_t seed,
+                                   int64_t epoch, const int64_t* anchors, int64_t start, int64_t count, int P, int dilation,
+                                   float* rays_o, float* rays_d, float* rgb, int64_t* index, fsn_stream_t stream) {
+  FSN_REQUIRE(n_views >= 0 && H > 0 && W > 0 && focal > 0, FSN_E_INVALID,
+              "fsn_ray_patch_batch: bad geometry n=%lld H=%d W=%d focal=%g", (long long)n_views, H, W, focal);
+  FSN_REQUIRE(C == 3 || C == 4, FSN_E_INVALID,
+              "fsn_ray_patch_batch: %d channels (the images are RGB or RGBA bytes: 3 or 4)", C);
+  FSN_REQUIRE(!white_bkgd || C == 4, FSN_E_INVALID,
+              "fsn_ray_patch_batch: white_bkgd composes over the alpha channel and needs 4-channel images, got %d", C);
+  FSN_REQUIRE(order == FSN_RAY_ORDER_IDENTITY || order == FSN_RAY_ORDER_PERMUTED || order == FSN_RAY_ORDER_EXPLICIT,
+              FSN_E_INVALID, "fsn_ray_patch_batch: unknown order %d", order);
+  FSN_REQUIRE(P >= 1 && dilation >= 1, FSN_E_INVALID, "fsn_ray_patch_batch: bad patch P=%d dilation=%d (both at least 1)",
+              P, dilation);
+  const int64_t ext = (int64_t)(P - 1) * dilation + 1;
+  FSN_REQUIRE(ext <= H && ext <= W, FSN_E_INVALID,
+              "fsn_ray_patch_batch: a patch of %d pixels at dilation %d spans %lld pixels and does not fit the %dx%d image",
+              P, dilation, (long long)ext, H, W);
+  FSN_REQUIRE(n_views <= ((int64_t)1 << 62) / ((int64_t)H * W), FSN_E_UNSUPPORTED,
+              "fsn_ray_patch_batch: more than 2^62 rays");
+  const int64_t AH = H - ext + 1, AW = W - ext + 1, n_anchors = n_views * AH * AW;
+  FSN_REQUIRE(start >= 0 && count >= 0 && epoch >= 0, FSN_E_INVALID,
+              "fsn_ray_patch_batch: negative start, count or epoch");
+  if (order == FSN_RAY_ORDER_EXPLICIT) {
+    FSN_REQUIRE(start == 0, FSN_E_INVALID,
+                "fsn_ray_patch_batch: an explicit anchor list is served from its beginning (start = 0)");
+  } else {
+    FSN_REQUIRE(start <= n_anchors && count <= n_anchors - start, FSN_E_INVALID,
+                "fsn_ray_patch_batch: positions [%lld, +%lld) leave the %lld anchors of the dataset (start + count > A)",
+                (long long)start, (long long)count, (long long)n_anchors);
+  }
+  FSN_REQUIRE(poses, FSN_E_INVALID, "fsn_ray_patch_batch: null poses");
+  FSN_REQUIRE(images || !rgb, FSN_E_INVALID, "fsn_ray_patch_batch: null images with colours asked for (rgb)");
+  if (count == 0) return FSN_OK;
+  FSN_REQUIRE(order != FSN_RAY_ORDER_EXPLICIT || anchors, FSN_E_INVALID, "fsn_ray_patch_batch: null anchor list");
+  FSN_REQUIRE(rays_o || rays_d || rgb || index, FSN_E_INVALID, "fsn_ray_patch_batch: null pointer for every output");
+  const int64_t pp = (int64_t)P * P;
+  FSN_REQUIRE(count <= ((int64_t)1 << 38) / pp, FSN_E_UNSUPPORTED, "fsn_ray_patch_batch: more than 2^38 rows in one call");
+  RayPatchArgs pa{};
+  RayBatchArgs& a = pa.r;
+  a.poses = poses;
+  a.images = images;
+  a.indices = anchors;
+  a.start = start;
+  a.count = count;
+  a.W = W;
+  a.C = C;
+  a.ndc = ndc ? 1 : 0;
+  a.white_bkgd = white_bkgd ? 1 : 0;
+  a.order = order;
+  // the same roundings as fsn_ray_batch
+  a.half_w = (float)(W * 0.5);
+  a.half_h = (float)(H * 0.5);
+  a.focal = (float)focal;
+  a.sx = (float)(-1.0 / (W / (2.0 * focal)));
+  a.sy = (float)(-1.0 / (H / (2.0 * focal)));
+  a.near = (float)near;
+  a.two_near = (float)(2.0 * near);
+  if (order == FSN_RAY_ORDER_PERMUTED) a.perm = ray_perm_make((uint64_t)n_anchors, seed, (uint64_t)epoch);
+  a.rays_o = rays_o;
+  a.rays_d = rays_d;
+  a.rgb = rgb;
+  a.index = index;
+  pa.n_anchors = n_anchors;
+  pa.per_view_anchors = AH * AW;
+  pa.P = P;
+  pa.dilation = dilation;
+  pa.AW = (int)AW;
+  pa.H = H;
+  k_ray_patch_batch<<<(unsigned)((count * pp + 255) / 256), 256, 0, as_stream(stream)>>>(pa);
+  FSN_LAUNCH_CHECK("k_ray_patch_batch");
   return FSN_OK;
 }
 

@@ -1,2 +1,3 @@
-"""The reference's data layer (src/nerfdata) on the device: uint8 images and poses resident, every batch one launch."""
-from .raydata import FrameLoader, RayDataset, RayLoader  # noqa: F401
+"""The reference's data layer (src/nerfdata) on the device: uint8 images and poses resident, every batch one launch;
+PatchLoader: batches of P x P pixel patches over the same dataset."""
+from .raydata import FrameLoader, PatchLoader, RayDataset, RayLoader  # noqa: F401

@@ -5,7 +5,10 @@ consume (run-nerf.py:134-152, 236-240, 384-456).
 The ray tables are pure functions of (pose, pixel), so only the uint8 images (3-4 bytes per pixel instead of 36 bytes
 of float tables), the poses and the region of interest are kept on the GPU.  A batch is ONE launch (ops.ray_batch /
 fsn_ray_batch): position in the epoch -> shuffled ray index -> (view, row, column) -> ray (+ NDC) -> ground-truth
-colour, bit for bit what the reference's float tables hold.  There is no CPU implementation."""
+colour, bit for bit what the reference's float tables hold.  There is no CPU implementation.
+
+PatchLoader (this package's own: the reference trains on single rays) serves batches of P x P pixel patches the same
+way (ops.ray_patch_batch / fsn_ray_patch_batch), for losses that need several rendered pixels at once."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -86,6 +89,30 @@ class RayDataset:
                              order=order, seed=seed, epoch=epoch, indices=indices, start=start, count=count,
                              want_rays=want_rays, want_rgb=want_rgb, want_index=want_index)
 
+    def n_anchors(self, patch: int, dilation: int = 1) -> int:
+        """The number of `patch` x `patch` patches at `dilation` that fit the images: n * (H - ext + 1) * (W - ext + 1)
+        anchors (top-left pixels), ext = (patch - 1) * dilation + 1; ValueError for a patch that does not fit."""
+        H, W, _ = self.hwf
+        if patch < 1 or dilation < 1:
+            raise ValueError(f"RayDataset: bad patch {patch} or dilation {dilation} (both at least 1)")
+        ext = (patch - 1) * dilation + 1
+        if ext > H or ext > W:
+            raise ValueError(f"RayDataset: a patch of {patch} pixels at dilation {dilation} spans {ext} pixels and does "
+                             f"not fit the {H} x {W} images")
+        return self.imgs.shape[0] * (H - ext + 1) * (W - ext + 1)
+
+    def patch_batch(self, order: str, patch: int, dilation: int = 1, *, start: int = 0, count: Optional[int] = None,
+                    seed: int = 0, epoch: int = 0, anchors: Optional[Tensor] = None, want_rays: bool = True,
+                    want_rgb: bool = True, want_index: bool = False):
+        """ops.ray_patch_batch on this dataset's tensors: `count` patches of `patch` x `patch` pixels from position
+        `start` of `order` over the n_anchors(patch, dilation) anchors -> (rays_o, rays_d, rgb, index) of
+        count * patch^2 rows, patch after patch, row-major inside a patch; None where not wanted."""
+        self.n_anchors(patch, dilation)
+        H, W, focal = self.hwf
+        return ops.ray_patch_batch(self.poses12, self.imgs, H, W, focal, patch, dilation, ndc=self.ndc, near=_NDC_NEAR,
+                                   white_bkgd=self.white_bkgd, order=order, seed=seed, epoch=epoch, anchors=anchors,
+                                   start=start, count=count, want_rays=want_rays, want_rgb=want_rgb, want_index=want_index)
+
     def __getitem__(self, idx):
         """Not the hot path (the loaders never come here): a tensor of indices costs one min / max read-back so that an
         index outside [0, len) raises IndexError BEFORE anything is launched."""
@@ -134,8 +161,16 @@ class RayLoader:
         self.position = 0     # global batches of that epoch already served
         self._resume = False  # load_state_dict(): the next iter() continues instead of advancing
 
+    def _n_items(self) -> int:
+        """What an epoch serves once each (PatchLoader: anchors instead of rays)."""
+        return len(self.dataset)
+
+    def _serve(self, order: str, start: int, count: int, epoch: int):
+        """The one launch of a next(): `count` items from position `start` of this epoch's order."""
+        return self.dataset.batch(order, start=start, count=count, seed=self.seed, epoch=epoch, want_index=self.with_index)
+
     def __len__(self) -> int:
-        n, stride = len(self.dataset), self.batch_size * self.world
+        n, stride = self._n_items(), self.batch_size * self.world
         return -(-n // stride) if self.world == 1 else n // stride
 
     def __iter__(self) -> "_RayIterator":
@@ -165,14 +200,36 @@ class _RayIterator:
         ld = self.loader
         if self.position >= len(ld):
             raise StopIteration
-        B, n = ld.batch_size, len(ld.dataset)
+        B, n = ld.batch_size, ld._n_items()
         start = (self.position * ld.world + ld.rank) * B
-        o, d, rgb, index = ld.dataset.batch("permuted" if ld.shuffle else "identity", start=start, count=min(B, n - start),
-                                            seed=ld.seed, epoch=self.epoch, want_index=ld.with_index)
+        o, d, rgb, index = ld._serve("permuted" if ld.shuffle else "identity", start, min(B, n - start), self.epoch)
         self.position += 1
         if ld.epoch == self.epoch:  # (an iterator abandoned for a newer one no longer moves the loader's state)
             ld.position = self.position
         return (o, d, rgb, index) if ld.with_index else (o, d, rgb)
+
+
+class PatchLoader(RayLoader):
+    """RayLoader over patches, for losses that need several rendered pixels at once (core/loss.py: SSIMLoss; patch
+    regularisers on depth): every next() is ONE launch (RayDataset.patch_batch) returning (rays_o, rays_d, rgb) of
+    [B * patch^2, 3] (+ index [B * patch^2] with `with_index`) for B = patches_per_batch patches of patch x patch pixels
+    `dilation` apart, patch after patch, so rgb.view(B, patch, patch, 3) is the patch stack.  RayLoader's contract holds
+    over the ANCHORS (top-left pixels, dataset.n_anchors(patch, dilation) of them): a new permutation per iter(), every
+    anchor exactly once per epoch, a short last batch, the world / rank slices, state_dict() / load_state_dict().
+    ValueError for a patch that does not fit the images."""
+
+    def __init__(self, dataset: RayDataset, patch: int, patches_per_batch: int, dilation: int = 1, shuffle: bool = True,
+                 seed: Optional[int] = None, rank: int = 0, world: int = 1, with_index: bool = False):
+        super().__init__(dataset, patches_per_batch, shuffle, seed, rank, world, with_index)
+        self.patch, self.dilation = int(patch), int(dilation)
+        self._anchors = dataset.n_anchors(self.patch, self.dilation)
+
+    def _n_items(self) -> int:
+        return self._anchors
+
+    def _serve(self, order: str, start: int, count: int, epoch: int):
+        return self.dataset.patch_batch(order, self.patch, self.dilation, start=start, count=count, seed=self.seed,
+                                        epoch=epoch, want_index=self.with_index)
 
 
 class FrameLoader:

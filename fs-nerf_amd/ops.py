@@ -229,6 +229,45 @@ def ray_batch(poses12: Tensor, images: Tensor, H: int, W: int, focal: float, *, 
     return o, d, rgb, index
 
 
+def ray_patch_batch(poses12: Tensor, images: Optional[Tensor], H: int, W: int, focal: float, patch: int, dilation: int = 1, *,
+                    ndc: bool = False, near: float = 1.0, white_bkgd: bool = False, order: str = "identity", seed: int = 0,
+                    epoch: int = 0, anchors: Optional[Tensor] = None, start: int = 0, count: Optional[int] = None,
+                    want_rays: bool = True, want_rgb: bool = True, want_index: bool = False):
+    """A batch of `patch` x `patch` pixel patches in ONE launch (fsn_ray_patch_batch), no host synchronisation: `count`
+    patches from position `start` of `order` over the ANCHORS (top-left pixels) of the dataset - n * (H - ext + 1) *
+    (W - ext + 1) of them, ext = (patch - 1) * dilation + 1; "explicit" = the device int64 list `anchors` ->
+    (rays_o, rays_d, rgb [count * patch^2, 3], index [count * patch^2] int64), patch b in rows [b * patch^2, +patch^2),
+    row-major, so rgb.view(count, patch, patch, 3) is the patch stack; an output not asked for is None.
+    images=None (with want_rgb=False): ray-only patches for any poses."""
+    if not (poses12.is_cuda and (images is None or images.is_cuda)):
+        raise RuntimeError("ray_patch_batch: expected GPU tensors (the HIP path has no CPU fallback)")
+    if poses12.dtype != torch.float32 or poses12.dim() != 2 or poses12.shape[1] != 12 or not poses12.is_contiguous():
+        raise TypeError("ray_patch_batch: poses are float32 [n,12], contiguous")
+    if images is None:
+        if want_rgb:
+            raise ValueError("ray_patch_batch: colours (want_rgb) need images")
+        channels = 3
+    else:
+        if images.dtype != torch.uint8 or images.dim() != 4:
+            raise TypeError("ray_patch_batch: images are uint8 [n,H,W,C]")
+        assert images.is_contiguous() and images.shape[:3] == (poses12.shape[0], H, W)
+        channels = images.shape[3]
+    if order == "explicit":
+        anchors = _i64(anchors, "anchors")
+        count = anchors.numel()
+    elif count is None:
+        raise ValueError("ray_patch_batch: count is needed for the identity and permuted orders")
+    dev, rows = poses12.device, count * int(patch) * int(patch)
+    o = torch.empty(rows, 3, device=dev, dtype=torch.float32) if want_rays else None
+    d = torch.empty(rows, 3, device=dev, dtype=torch.float32) if want_rays else None
+    rgb = torch.empty(rows, 3, device=dev, dtype=torch.float32) if want_rgb else None
+    index = torch.empty(rows, device=dev, dtype=torch.int64) if want_index else None
+    _launch("fsn_ray_patch_batch", dev, _p(poses12), poses12.shape[0], _p(images), int(H), int(W), channels, float(focal),
+            1 if ndc else 0, float(near), 1 if white_bkgd else 0, _RAY_ORDERS[order], int(seed) & 0xFFFFFFFFFFFFFFFF,
+            int(epoch), _p(anchors), int(start), int(count), int(patch), int(dilation), _p(o), _p(d), _p(rgb), _p(index))
+    return o, d, rgb, index
+
+
 def ray_perm_host(n: int, seed: int, epoch: int, start: int = 0, count: Optional[int] = None) -> Tensor:
     """Positions [start, start + count) of the epoch permutation of [0, n) as a CPU int64 tensor (fsn_ray_perm_host: the
     kernel's own function compiled for the host; no device is touched, so it takes no stream and needs no door)."""
@@ -1452,6 +1491,15 @@ def _f32_view(t: Tensor, name: str) -> Tensor:
     return t if t.dtype == torch.float32 else t.float()
 
 
+def _gpu_f32_view(t: Tensor, name: str) -> Tensor:
+    """_gpu_f32 without the copy: float32 or an error (a cast would hide the tensor a gradient belongs to)."""
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: expected a GPU tensor (the HIP path has no CPU fallback)")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name}: expected float32, got {t.dtype}")
+    return t
+
+
 def _nchw_strides(t: Tensor):
     assert t.dim() == 4
     return (C.c_int64 * 4)(*t.stride())
@@ -1471,6 +1519,41 @@ def ssim_nchw(x: Tensor, y: Tensor, window: int, use_sample_covariance: bool, da
             1 if use_sample_covariance else 0, float(data_range), float(K1), float(K2), _p(ws), _p(out), _p(smap),
             None if smap is None else _nchw_strides(smap))
     return out
+
+
+def ssim_grad_nchw(x: Tensor, y: Tensor, window: int, use_sample_covariance: bool, data_range: float, K1: float, K2: float,
+                   upstream: Tensor, *, want_dx: bool = True, want_dy: bool = True, dx: Optional[Tensor] = None,
+                   dy: Optional[Tensor] = None) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """fsn_ssim_grad on two float32 (N, C, H, W) views of any strides: the gradient of sum_n upstream[n] * ssim_n
+    (ssim_n = ssim_nchw(...)[n]) -> (dx, dy), float32 (N, C, H, W); a gradient not wanted is None (not both).
+    upstream: N values (float64 on the device as the kernel reads them; anything else is converted).  `dx` / `dy`:
+    optional float32 (N, C, H, W) views of any strides to write into instead of new contiguous tensors."""
+    x, y = _gpu_f32_view(x, "im1"), _gpu_f32_view(y, "im2")
+    N, Ch, H, W = x.shape
+    assert y.shape == x.shape and y.device == x.device
+    if not (want_dx or want_dy):
+        raise ValueError("ssim_grad_nchw: neither dx nor dy is wanted")
+    dev = x.device
+    if not upstream.is_cuda:
+        raise RuntimeError("upstream: expected a GPU tensor (the HIP path has no CPU fallback)")
+    up = upstream.detach().to(torch.float64).reshape(-1).contiguous()
+    if up.numel() != N:
+        raise ValueError(f"upstream: expected {N} values (one per image), got {up.numel()}")
+    outs = []
+    for want, t, name in ((want_dx, dx, "dx"), (want_dy, dy, "dy")):
+        if not want:
+            t = None
+        elif t is None:
+            t = torch.empty(x.shape, dtype=torch.float32, device=dev)
+        elif t.dtype != torch.float32 or t.shape != x.shape or t.device != dev:
+            raise ValueError(f"{name}: expected a float32 {tuple(x.shape)} view on {dev}")
+        outs.append(t)
+    ws = torch.empty(max(_size("fsn_ssim_grad_workspace_doubles", None, N, Ch, H, W), 1), dtype=torch.float64, device=dev)
+    _launch("fsn_ssim_grad", dev, _p(x), _p(y), N, Ch, H, W, _nchw_strides(x), _nchw_strides(y), int(window),
+            1 if use_sample_covariance else 0, float(data_range), float(K1), float(K2), _p(up), _p(ws),
+            _p(outs[0]), None if outs[0] is None else _nchw_strides(outs[0]),
+            _p(outs[1]), None if outs[1] is None else _nchw_strides(outs[1]))
+    return outs[0], outs[1]
 
 
 def psnr_nchw(x: Tensor, y: Tensor) -> Tensor:

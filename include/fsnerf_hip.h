@@ -129,11 +129,27 @@ int fsn_ray_batch(const float* poses, int64_t n_views, const uint8_t* images, in
                   double near, int white_bkgd, int order, uint64_t seed, int64_t epoch, const int64_t* indices,
                   int64_t start, int64_t count, float* rays_o, float* rays_d, float* rgb, int64_t* index,
                   fsn_stream_t stream);
+/* A batch of P x P patches in ONE launch, one thread per output row: the data layer for losses that need several
+ * rendered pixels at once (the SSIM term below, patch regularisers on depth).  With ext = (P-1)*dilation + 1,
+ * AH = H - ext + 1 and AW = W - ext + 1, the ANCHORS (the patches' top-left pixels) number A = n_views*AH*AW;
+ * anchor a is view v = a / (AH*AW), row r0 = (a % (AH*AW)) / AW, column c0 = a % AW; pixel (i, j) of its patch is image
+ * pixel (r0 + i*dilation, c0 + j*dilation), flat ray index (v*H + r)*W + c.  `order`, `seed`, `epoch`, `start` and
+ * `count` are those of the ray batch above read over anchors: start and count count PATCHES, the permutation is of
+ * [0, A), `anchors` is the explicit DEVICE int64 [count] list (an anchor outside [0, A) leaves its P*P rows untouched
+ * and is recorded in the debug build).  Outputs (each may be NULL): rays_o, rays_d, rgb [count*P*P, 3] and index
+ * [count*P*P] int64, row (b*P + i)*P + j for pixel (i, j) of patch b - bit for bit the row the ray batch above serves
+ * for that flat index in explicit order.  images may be NULL when rgb is NULL: ray-only patches for any poses.
+ * Errors (FSN_E_INVALID): P < 1, dilation < 1, ext > H or ext > W, start + count > A, and those of the ray batch. */
+int fsn_ray_patch_batch(const float* poses, int64_t n_views, const uint8_t* images, int H, int W, int C, double focal,
+                        int ndc, double near, int white_bkgd, int order, uint64_t seed, int64_t epoch,
+                        const int64_t* anchors, int64_t start, int64_t count, int P, int dilation, float* rays_o,
+                        float* rays_d, float* rgb, int64_t* index, fsn_stream_t stream);
 /* The same permutation on the host (plain C++, no device is touched): out_host[i] = perm(start + i; N, seed, epoch) for
  * i < count, start + count <= N <= 2^62. */
 int fsn_ray_perm_host(int64_t N, uint64_t seed, int64_t epoch, int64_t start, int64_t count, int64_t* out_host);
-/* Debug build only: the record of explicit indices outside [0, N) met by k_ray_batch (4 uint32: count, source line, the
- * first index and N truncated to 32 bits), cleared by the call.  The release library returns FSN_E_UNSUPPORTED. */
+/* Debug build only: the record of explicit indices outside [0, N) met by k_ray_batch, and of explicit anchors outside
+ * [0, A) met by the patch kernel (4 uint32: count, source line, the first index and N or A truncated to 32 bits),
+ * cleared by the call.  The release library returns FSN_E_UNSUPPORTED. */
 int fsn_debug_report_raydata(uint32_t* out_host);
 
 /* ---- a4: PositionalEncoder.forward(x)                    src/core/models.py:43-50
@@ -790,6 +806,29 @@ int fsn_psnr(const float* x, const float* y, int64_t N, int C, int H, int W, con
 /* Debug build only: the LDS index record of k_ssim_tile (4 uint32, as fsn_debug_report's), cleared by the call.  The
  * release library returns FSN_E_UNSUPPORTED. */
 int fsn_debug_report_metrics(uint32_t* out_host);
+
+/* The backward of the SSIM above (csrc/ssim_grad.hip): the gradient of sum_n upstream[n] * ssim_n, ssim_n = out[n] of
+ * the forward (the mean of S over the interior and the channels of image n), with respect to x and y.  With the
+ * forward's taps w, radius r, cn, C1, C2 and moments, A1 = 2 ux uy + C1, A2 = 2 cn (uxy - ux uy) + C2,
+ * B1 = ux^2 + uy^2 + C1, B2 = cn (uxx - ux^2 + uyy - uy^2) + C2, S = A1 A2 / (B1 B2); on the interior, zero elsewhere,
+ * with g = upstream[n] / (C (H-2r) (W-2r)):
+ *   Suxy = 2 cn A1 / (B1 B2),   Suxx = Suyy = -S cn / B2,
+ *   Sux  = (2 uy A2 - 2 cn uy A1) / (B1 B2) - 2 S ux / B1 + 2 S cn ux / B2,   Suy: x and y swapped;
+ *   dx(p) = F[g Sux](p) + 2 x(p) F[g Suxx](p) + y(p) F[g Suxy](p),  F[m](p) = sum_q w(q - p) m(q),  dy: x and y swapped.
+ * The reflect edges play no part: an interior window never leaves the image.  Float64 throughout, one rounding to the
+ * float32 outputs; every output pixel sums over its own window in a fixed order (no atomics): bitwise reproducible, and
+ * an image's gradient does not depend on the rest of the batch.
+ * x, y, strides, window, use_sample_covariance, data_range, K1, K2: as in the forward, validated alike.  upstream:
+ * DEVICE double [N] = dL/d ssim_n.  dx, dy: DEVICE float32 with their own HOST strides, every element written; one of
+ * them may be NULL, not both.  workspace: the workspace query below, in doubles.  N = 0 is a no-op. */
+int64_t fsn_ssim_grad_workspace_doubles(int64_t N, int C, int H, int W);
+int fsn_ssim_grad(const float* x, const float* y, int64_t N, int C, int H, int W, const int64_t* x_strides_host,
+                  const int64_t* y_strides_host, int window, int use_sample_covariance, double data_range, double K1,
+                  double K2, const double* upstream, double* workspace, float* dx, const int64_t* dx_strides_host,
+                  float* dy, const int64_t* dy_strides_host, fsn_stream_t stream);
+/* Debug build only: the LDS index record of the two kernels behind the SSIM gradient (4 uint32), cleared by the call.
+ * The release library returns FSN_E_UNSUPPORTED. */
+int fsn_debug_report_ssim_grad(uint32_t* out_host);
 
 /* LPIPS v0.1, VGG16 backbone (the `lpips` package's LPIPS(net="vgg")), of N image pairs x, y (float32, DEVICE, 3
  * channels, H x W >= 16 x 16), read through their element strides (n, c, h, w) as the metrics above.  Per pair: the
