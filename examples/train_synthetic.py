@@ -7,6 +7,7 @@ estimator.update_every_n_steps) and evaluated with render_frame + PSNR and SSIM 
     python examples/train_synthetic.py [--estimator occgrid|stratified|propnet] [--iters 400] [--hw 64] [--u8-dataset]
                                        [--depth-weight W] [--distortion-weight W] [--cone-angle A] [--near-plane T]
                                        [--mark-invisible] [--min-views K] [--ssim-weight W --patch P --patches B]
+                                       [--lpips-weight W --lpips-weights FILE]
 
 --u8-dataset: the teacher's frames become uint8 "photographs" (R.to8b) held in a device-resident RayDataset; the loop
 takes its batches from a RayLoader the way run-nerf.py:236-240 takes them from its DataLoader, and the held-out view
@@ -31,6 +32,10 @@ rendered patches.  A PatchLoader serves --patches B patches of --patch P x P pix
 to the ray batch for ONE render_rays call, and the rendered tail, reshaped to [B, P, P, 3], goes through
 core.loss.SSIMLoss against the photographs' patches: loss = MSE(ray batch) + W * (1 - SSIM(patches)).
 
+--lpips-weight W --lpips-weights FILE (0 by default; needs --u8-dataset and --patch of at least 16): the perceptual term
+on the same patches, loss += W * LPIPSLoss(patches) (core.loss.LPIPSLoss on metrics.LPIPS, VGG16).  FILE is a local
+torch.save'd state dict in the `lpips` package's layout; nothing is downloaded.
+
 --mark-invisible (off by default): before the first step the occupancy estimator takes every cell that fewer than
 --min-views K (default 1) training views see out of the grid for good (OccGridEstimator.mark_invisible_from_views: a
 conservative frustum / box test); no later refresh switches such a cell on.
@@ -47,7 +52,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import fs_nerf_amd  # noqa: E402,F401
 from fs_nerf_amd.core import metrics  # noqa: E402
 from fs_nerf_amd.core import models as M  # noqa: E402
-from fs_nerf_amd.core.loss import DistortionLoss, SSIMLoss, WeightNormRegularizer  # noqa: E402
+from fs_nerf_amd.core.loss import DistortionLoss, LPIPSLoss, SSIMLoss, WeightNormRegularizer  # noqa: E402
 from fs_nerf_amd.core.optim import FusedAdam  # noqa: E402
 from fs_nerf_amd.core.scheduler import ExponentialDecay  # noqa: E402
 from fs_nerf_amd.nerfdata import FrameLoader, PatchLoader, RayDataset, RayLoader  # noqa: E402
@@ -107,7 +112,19 @@ def main():
                     help="opt-in: weight of 1 - SSIM on rendered patches (core.loss.SSIMLoss; needs --u8-dataset)")
     ap.add_argument("--patch", type=int, default=16, help="with --ssim-weight: the patches are PATCH x PATCH pixels (at least 11)")
     ap.add_argument("--patches", type=int, default=8, help="with --ssim-weight: patches per step")
+    ap.add_argument("--lpips-weight", type=float, default=0.0,
+                    help="opt-in: weight of LPIPS-VGG on rendered patches (core.loss.LPIPSLoss; needs --u8-dataset, "
+                         "--lpips-weights and --patch >= 16)")
+    ap.add_argument("--lpips-weights", default=None, metavar="FILE",
+                    help="with --lpips-weight: a local torch.save'd state dict of the lpips package's LPIPS(net='vgg')")
     a = ap.parse_args()
+    if a.lpips_weight:
+        if not a.u8_dataset:
+            ap.error("--lpips-weight takes its patches from the device-resident dataset: add --u8-dataset")
+        if not a.lpips_weights:
+            ap.error("--lpips-weight needs --lpips-weights FILE (a local state dict; nothing is downloaded)")
+        if a.patch < 16:
+            ap.error("--lpips-weight needs --patch of at least 16 (LPIPS-VGG has four 2x2 pools)")
     if a.ssim_weight and not a.u8_dataset:
         ap.error("--ssim-weight takes its patches from the device-resident dataset: add --u8-dataset")
     if a.cone_angle and a.estimator != "occgrid":
@@ -140,10 +157,15 @@ def main():
         train_set = RayDataset(frames8, torch.stack(poses), hwf, near=near, far=far, device=dev)
         train_loader = RayLoader(train_set, a.batch, shuffle=True, seed=0)
         iterator = iter(train_loader)
-        if a.ssim_weight:
+        if a.ssim_weight or a.lpips_weight:
             patch_loader = PatchLoader(train_set, a.patch, a.patches, shuffle=True, seed=1)
             patch_iterator = iter(patch_loader)
+        if a.ssim_weight:
             ssim_loss = SSIMLoss(gaussian_weights=True, data_range=1.0, channel_axis=-1)
+        if a.lpips_weight:
+            lpips_net = metrics.LPIPS(net="vgg")
+            lpips_net.load_state_dict(torch.load(a.lpips_weights, map_location="cpu"))
+            lpips_loss = LPIPSLoss(lpips_net.to(dev).eval(), normalize=True, channel_axis=-1)
         with torch.no_grad():
             ref8 = R.to8b(R.render_frame(hwf, near, far, held_out, 1 << 20, t_est, teacher, white_bkgd=True, device=dev)[0])
         val_loader = FrameLoader(RayDataset(ref8.reshape(1, a.hw, a.hw, 3), held_out[None], hwf, near=near, far=far, device=dev))
@@ -195,7 +217,7 @@ def main():
             idx = torch.randint(0, ro.shape[0], (a.batch,), device=dev, generator=gen)
             rays_o, rays_d, rgb_gt = ro[idx], rd[idx], gt[idx]
         n_batch = rays_o.shape[0]
-        if a.ssim_weight:  # the patches' rays ride in the same render_rays call, behind the ray batch
+        if a.ssim_weight or a.lpips_weight:  # the patches' rays ride in the same render_rays call, behind the ray batch
             try:
                 patch_o, patch_d, patch_gt = next(patch_iterator)
             except StopIteration:
@@ -209,6 +231,9 @@ def main():
         if a.ssim_weight:
             loss = loss + a.ssim_weight * ssim_loss(rgb[n_batch:].view(-1, a.patch, a.patch, 3),
                                                     patch_gt.view(-1, a.patch, a.patch, 3))
+        if a.lpips_weight:
+            loss = loss + a.lpips_weight * lpips_loss(rgb[n_batch:].view(-1, a.patch, a.patch, 3),
+                                                      patch_gt.view(-1, a.patch, a.patch, 3))
         if a.depth_weight and depth.requires_grad:  # (an all-background batch renders no samples: nothing to supervise)
             hit = (gd[idx] > near).float()  # render_frame clamps depth to [near, far]: `near` = the teacher saw background
             loss = loss + a.depth_weight * (hit * (depth - gd[idx]) ** 2).sum() / hit.sum().clamp(min=1.0)

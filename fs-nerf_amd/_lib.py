@@ -167,6 +167,11 @@ SIGNATURES = {
     "fsn_lpips_pack": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fsn_lpips_workspace_floats": (_i64, [_i, _i]),
     "fsn_lpips_vgg": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "fsn_lpips_grad_pack_bytes": (_i64, []),
+    "fsn_lpips_grad_pack": (_i, [_vp, _vp, _vp]),
+    "fsn_lpips_train_workspace_floats": (_i64, [_i64, _i, _i, _i, _i]),
+    "fsn_lpips_vgg_fwd_save": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "fsn_lpips_vgg_bwd": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fsn_debug_report_lpips": (_i, [_vp]),
 }
 

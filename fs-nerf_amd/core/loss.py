@@ -2,8 +2,8 @@
 segmented reduction on the GPU instead of a Python loop with one kernel launch per ray; the distortion loss on the
 compositor's weights (this package's own, the first consumer of `full_grad`); and the weight-norm
 "frequency" regulariser of the training loop (row f1, src/run-nerf.py:266-279) as one reduction over the flat
-parameter arena; and the structural (D-SSIM) term on rendered patches (this package's own: the evaluation metric of
-core/metrics.py with a backward)."""
+parameter arena; and the structural (D-SSIM) and perceptual (LPIPS-VGG) terms on rendered patches (this package's own:
+the evaluation metrics of core/metrics.py with a backward)."""
 import ctypes as C
 from typing import Optional
 
@@ -111,6 +111,75 @@ class SSIMLoss:
             if t.dtype != torch.float32:
                 raise TypeError(f"SSIMLoss: {name} must be float32, got {t.dtype} (a cast would hide it from autograd)")
         return _SSIMLossFn.apply(pred, target, self)
+
+
+class LPIPSLoss:
+    """The perceptual term for patch-mode training, the sibling of SSIMLoss: `loss(pred, target)` =
+    lpips_net(pred, target, normalize=normalize) of `metrics.LPIPS` with gradients to the inputs that need one -
+    0-dim float32 (reduction="mean", the mean over the N patches) or float32 (N,) ("none").  Each pair's value is the
+    evaluation metric's own, bit for bit; the backward (csrc/lpips.hip: tap backward in float64, the convolutions'
+    data gradients on the f32 MFMA) cannot be differentiated again.  The VGG and lin weights are frozen.
+    Shapes: (N, H, W, 3) with channel_axis=-1 (render_rays' rows viewed as patches), (N, 3, H, W) with 1; float32 GPU
+    tensors of any strides, read in place; H, W >= 16.  normalize=True: inputs in [0, 1] (the renderer's range).
+    Definitions where autograd has none or a choice: a pixel whose tap vector is all zero has gradient 0 (autograd:
+    NaN); a pooled gradient goes to the first maximum of its 2 x 2 window in row-major order (max_pool2d's rule).
+
+    Memory: a pass keeps about 270 H W floats of activations and 128 H W of gradients per back-propagated image.  N is
+    processed in chunks of `pairs_per_pass` pairs, one forward and one backward call each; by default the most pairs
+    whose workspace fits `max_workspace_bytes` (1 GiB: a setting, not a measurement; one pair always runs, whatever
+    its size).  With more than one chunk the backward runs each chunk's forward again instead of keeping every
+    chunk's activations.  The gradients do not depend on the chunking, bit for bit."""
+
+    def __init__(self, lpips_net, normalize: bool = True, channel_axis: int = -1, reduction: str = "mean"):
+        if not isinstance(lpips_net, metrics.LPIPS):
+            raise TypeError(f"LPIPSLoss: lpips_net must be fs_nerf_amd.core.metrics.LPIPS, got {type(lpips_net).__name__}")
+        if reduction not in ("mean", "none"):
+            raise ValueError(f"reduction must be 'mean' or 'none', got {reduction!r}")
+        if channel_axis not in (-1, 3, 1, -3):
+            raise ValueError(f"channel_axis={channel_axis}: expected -1 (N, H, W, 3) or 1 (N, 3, H, W)")
+        self.net, self.normalize, self.channel_axis, self.reduction = lpips_net, bool(normalize), channel_axis, reduction
+        self.max_workspace_bytes = metrics.TRAIN_WORKSPACE_BYTES
+        self.pairs_per_pass: Optional[int] = None  # None: from max_workspace_bytes
+
+    def __call__(self, pred: Tensor, target: Tensor) -> Tensor:
+        net = self.net
+        if not net._loaded:
+            raise RuntimeError("LPIPSLoss: no weights loaded (load the lpips package's VGG state dict with load_state_dict)")
+        if pred.shape != target.shape:
+            raise ValueError(f"pred and target must have the same shape: {tuple(pred.shape)} vs {tuple(target.shape)}")
+        if pred.dim() != 4:
+            raise ValueError(f"expected (N, H, W, 3) or (N, 3, H, W) patches, got shape {tuple(pred.shape)}")
+        x, y = metrics._as_nchw(pred, self.channel_axis), metrics._as_nchw(target, self.channel_axis)
+        if x.shape[1] != 3:
+            raise ValueError(f"expected 3 channels on axis {self.channel_axis}, got shape {tuple(pred.shape)}")
+        H, W = x.shape[2], x.shape[3]
+        if H < metrics._MIN_SIDE or W < metrics._MIN_SIDE:
+            raise ValueError(f"LPIPS-VGG needs images of at least {metrics._MIN_SIDE} x {metrics._MIN_SIDE}, got {H} x {W}")
+        for t, name in ((pred, "pred"), (target, "target")):
+            if t.dtype != torch.float32:
+                raise TypeError(f"LPIPSLoss: {name} must be float32, got {t.dtype} (a cast would hide it from autograd)")
+        for t, name in ((pred, "pred"), (target, "target")):
+            if not t.is_cuda:
+                raise RuntimeError(f"LPIPSLoss: {name} is not a GPU tensor (the HIP path has no CPU fallback)")
+        dev = net.scaling_layer.shift.device
+        if pred.device != dev or target.device != dev:
+            raise RuntimeError(f"LPIPSLoss: inputs on {pred.device} / {target.device}, weights on {dev} (use .to(device))")
+        N = x.shape[0]
+        want_dx, want_dy = pred.requires_grad, target.requires_grad
+        if N == 0:
+            val = pred.new_empty(0)
+        elif torch.is_grad_enabled() and (want_dx or want_dy):
+            if any(p.requires_grad for p in net.parameters()):
+                raise RuntimeError("LPIPSLoss: the LPIPS weights are frozen (gradients to them are not implemented)")
+            ppp = self.pairs_per_pass
+            if ppp is None:
+                ppp = metrics.lpips_pairs_per_pass(H, W, want_dx, want_dy, int(self.max_workspace_bytes))
+            if int(ppp) < 1:
+                raise ValueError(f"pairs_per_pass must be at least 1, got {ppp}")
+            val, _ = metrics._LPIPSFn.apply(x, y, net, self.normalize, int(ppp))
+        else:
+            val, _ = ops.lpips_vgg(net.packed(), x.detach(), y.detach(), self.normalize)
+        return val.mean() if self.reduction == "mean" else val
 
 
 class _WeightNormFn(torch.autograd.Function):

@@ -11,13 +11,16 @@ tensors raise.
 `LPIPS(net="vgg")` is the `lpips` package's LPIPS v0.1 with the VGG16 backbone, as a module with that package's
 parameter names, run by csrc/lpips.hip (implicit-GEMM convolutions on the f32 MFMA).  It ships no weights and downloads
 nothing: load the package's own state dict (`m.load_state_dict(torch.load("lpips_vgg.pt"))`).  `evaluation()` computes
-LPIPS only when it is given this class; the reference computes it and then discards it (`val_lpips = None`, :178)."""
+LPIPS only when it is given this class; the reference computes it and then discards it (`val_lpips = None`, :178).
+Called with grad enabled on an input that requires grad it returns a value that carries the gradient to that input
+(`_LPIPSFn`; `core.loss.LPIPSLoss` is the training-loop face of it); the weights stay frozen."""
 from __future__ import annotations
 
 from typing import Optional
 
 import torch
 from torch import Tensor, nn
+from torch.autograd.function import once_differentiable
 
 from .. import _lib as L
 from .. import ops
@@ -167,9 +170,66 @@ class _VGG16Slices(nn.Module):
         return [getattr(getattr(self, f"slice{s}"), str(i)) for s, i, _, _ in _VGG_CONVS]
 
 
+TRAIN_WORKSPACE_BYTES = 1 << 30  # default bound of one training pass's workspace (a setting, not a measurement)
+
+
+def lpips_pairs_per_pass(H: int, W: int, want_dx: bool, want_dy: bool, max_workspace_bytes: int) -> int:
+    """The most pairs whose training workspace (fsn_lpips_train_workspace_floats: linear in the pairs) fits
+    `max_workspace_bytes`; at least one, whatever its size."""
+    one = 4 * ops._size("fsn_lpips_train_workspace_floats", None, 1, H, W, int(want_dx), int(want_dy))
+    return int(max(1, min(max_workspace_bytes // one, 32767)))
+
+
+class _LPIPSFn(torch.autograd.Function):
+    """LPIPS of N pairs with gradients to the images in one node: forward = fsn_lpips_vgg_fwd_save per chunk of
+    `pairs_per_pass` pairs (the metric's values bit for bit), backward = fsn_lpips_vgg_bwd per chunk for the inputs
+    that need a gradient.  One chunk keeps its activations for the backward; with several the backward runs each
+    chunk's forward again (the same bits), so that no more than one chunk's workspace is alive at a time.  The per-tap
+    values are returned for reading only (not differentiable)."""
+
+    @staticmethod
+    def forward(ctx, in0, in1, net, normalize, pairs_per_pass):
+        want_dx, want_dy = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        N = in0.shape[0]
+        packed = net.packed()
+        vals, pers, ws = [], [], None
+        for n0 in range(0, N, pairs_per_pass):
+            v, p, ws = ops.lpips_vgg_fwd_save(packed, in0[n0:n0 + pairs_per_pass], in1[n0:n0 + pairs_per_pass], normalize,
+                                              want_dx=want_dx, want_dy=want_dy)
+            vals.append(v)
+            pers.append(p)
+        ctx.save_for_backward(in0, in1)
+        ctx.net, ctx.normalize, ctx.ppp = net, bool(normalize), pairs_per_pass
+        ctx.ws = ws if N <= pairs_per_pass else None
+        val, per = torch.cat(vals), torch.cat(pers, dim=1)
+        ctx.mark_non_differentiable(per)
+        return val, per
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_val, _d_per):
+        in0, in1 = ctx.saved_tensors
+        want_dx, want_dy = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_dx or want_dy):
+            return None, None, None, None, None
+        net, N = ctx.net, in0.shape[0]
+        packed, packed_grad = net.packed(), net.packed_grad()
+        d0 = torch.empty_like(in0) if want_dx else None
+        d1 = torch.empty_like(in1) if want_dy else None
+        for n0 in range(0, N, ctx.ppp):
+            sl = slice(n0, n0 + ctx.ppp)
+            ws = ctx.ws
+            if ws is None:
+                _, _, ws = ops.lpips_vgg_fwd_save(packed, in0[sl], in1[sl], ctx.normalize, want_dx=want_dx, want_dy=want_dy)
+            ops.lpips_vgg_bwd(packed, packed_grad, ws, in0[sl].shape, ctx.normalize, d_val[sl], want_dx=want_dx,
+                              want_dy=want_dy, dx=None if d0 is None else d0[sl], dy=None if d1 is None else d1[sl])
+        ctx.ws = None
+        return d0, d1, None, None, None
+
+
 class LPIPS(nn.Module):
     """LPIPS v0.1 with the VGG16 backbone on the device: the `lpips` package's `LPIPS(net="vgg")` forward (no spatial
-    map, no gradients).  Parameter and buffer names are the package's, so its state dict loads as it is; the
+    map; gradients to the images, not to the weights).  Parameter and buffer names are the package's, so its state dict loads as it is; the
     `lins.K.model.1.weight` aliases of its module list are accepted, and `scaling_layer.*` is optional (the package's
     constants).  The constructor downloads nothing and the module holds no usable weights until `load_state_dict`:
     calling it before raises.  The weights are packed for the kernels once per weight version (csrc/lpips.hip)."""
@@ -189,6 +249,8 @@ class LPIPS(nn.Module):
         self._loaded = False
         self._packed = None
         self._packed_key = None
+        self._packed_grad = None
+        self._packed_grad_key = None
         self._register_load_state_dict_pre_hook(self._accept_package_keys)
 
     @staticmethod
@@ -205,6 +267,7 @@ class LPIPS(nn.Module):
         out = super().load_state_dict(state_dict, strict=strict, **kwargs)
         self._loaded = not out.missing_keys
         self._packed_key = None
+        self._packed_grad_key = None
         return out
 
     def _tensors(self):
@@ -221,9 +284,21 @@ class LPIPS(nn.Module):
             self._packed_key = key
         return self._packed
 
+    def packed_grad(self) -> Tensor:
+        """The data-gradient kernels' weight blob (the convolutions transposed, csrc/lpips.hip), packed on the first
+        loss call and re-packed when a convolution weight changed: keyed like `packed()`."""
+        ws = self._tensors()[:13]
+        key = tuple((t.data_ptr(), t._version) for t in ws)
+        if self._packed_grad is None or key != self._packed_grad_key:
+            self._packed_grad = ops.lpips_grad_pack(ws, out=self._packed_grad)
+            self._packed_grad_key = key
+        return self._packed_grad
+
     def forward(self, in0: Tensor, in1: Tensor, retPerLayer: bool = False, normalize: bool = False):
         """in0, in1: (N, 3, H, W) device tensors (any strides), in [-1, 1], or in [0, 1] with normalize=True.
-        Returns float32 (N, 1, 1, 1), and with retPerLayer the five taps' values as a list of (N, 1, 1, 1) too."""
+        Returns float32 (N, 1, 1, 1), and with retPerLayer the five taps' values as a list of (N, 1, 1, 1) too.
+        With grad enabled and an input that requires grad (float32), the value carries the gradient to that input
+        (the per-tap values do not); the weights are frozen: a parameter that requires grad raises."""
         if not self._loaded:
             raise RuntimeError("LPIPS: no weights loaded (load the lpips package's VGG state dict with load_state_dict)")
         if in0.shape != in1.shape:
@@ -238,12 +313,19 @@ class LPIPS(nn.Module):
         dev = self.scaling_layer.shift.device
         if in0.device != dev or in1.device != dev:
             raise RuntimeError(f"LPIPS: inputs on {in0.device} / {in1.device}, weights on {dev} (use .to(device))")
-        if torch.is_grad_enabled() and (in0.requires_grad or in1.requires_grad
-                                        or any(p.requires_grad for p in self.parameters())):
-            raise RuntimeError("LPIPS: gradients are not implemented (evaluation only); call it under torch.no_grad()")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise RuntimeError("LPIPS: gradients to the weights are not implemented (they are frozen in every use as a "
+                               "loss): call requires_grad_(False), or run under torch.no_grad()")
         N = in0.shape[0]
         if N == 0:
             val, per = in0.new_empty(0, dtype=torch.float32), in0.new_empty(5, 0, dtype=torch.float32)
+        elif torch.is_grad_enabled() and (in0.requires_grad or in1.requires_grad):
+            for t, name in ((in0, "in0"), (in1, "in1")):
+                if t.dtype != torch.float32:
+                    raise TypeError(f"LPIPS: {name} must be float32, got {t.dtype} (a cast would hide it from autograd)")
+            ppp = lpips_pairs_per_pass(in0.shape[2], in0.shape[3], in0.requires_grad, in1.requires_grad,
+                                       TRAIN_WORKSPACE_BYTES)
+            val, per = _LPIPSFn.apply(in0, in1, self, bool(normalize), ppp)
         else:
             val, per = ops.lpips_vgg(self.packed(), in0.detach(), in1.detach(), normalize)
         val = val.view(N, 1, 1, 1)

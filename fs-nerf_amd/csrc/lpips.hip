@@ -22,6 +22,12 @@
 // the workspace (two ping-pong activation buffers of 2 x 64 x H x W floats, the head partials) depends on H and W only.
 // Sums: per-pixel head values in float64, one partial per workgroup, summed by one workgroup in a fixed order: no
 // atomics, the results are bitwise reproducible and independent of the input layout and of the batch.
+//
+// As a loss (second half of the file): fsn_lpips_vgg_fwd_save runs B pairs at once (blockIdx.z over the x images, then
+// the y images) through the same kernels and keeps every layer's post-ReLU activation of the images that need a
+// gradient; fsn_lpips_vgg_bwd walks back: k_lpips_tap_bwd (head gradient in float64 + the gradient arriving through the
+// max-pool, times the ReLU mask), the convolutions' data gradients through k_lpips_conv with Cin and Cout exchanged on
+// weights packed [Cin][9 Cout] with the taps flipped, and k_lpips_first_bwd for conv1_1 and the scaling layer.
 #include "common.hpp"
 
 #include <cmath>
@@ -119,16 +125,18 @@ __global__ void __launch_bounds__(kThreads) k_lpips_copy(const float* __restrict
 }
 
 // ---------------------------------------------------------------- input stage
-// both images of pair n -> act [2][H][W][3]: (v' - shift) / scale with v' = 2v - 1 under normalize (float32, the
-// scaling layer's arithmetic)
+// both images of pair n = n0 + blockIdx.y -> act [H][W][3] each: (v' - shift) / scale with v' = 2v - 1 under normalize
+// (float32, the scaling layer's arithmetic).  The x image goes to slot blockIdx.y, the y image to slot y_slot0 +
+// blockIdx.y (fsn_lpips_vgg: one pair, slots 0 and 1; the batched forward: the x group, then the y group)
 __global__ void __launch_bounds__(kThreads) k_lpips_input(const float* __restrict__ x, const float* __restrict__ y,
-                                                          Strides4 sx, Strides4 sy, int64_t n, int H, int W,
+                                                          Strides4 sx, Strides4 sy, int64_t n0, int H, int W,
                                                           int normalize, const float* __restrict__ shift_scale,
-                                                          float* __restrict__ act) {
+                                                          int64_t y_slot0, float* __restrict__ act) {
   const int64_t per = (int64_t)H * W * 3;
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (i >= 2 * per) return;
   const int img = (int)(i / per);
+  const int64_t n = n0 + blockIdx.y;
   const int64_t e = i - img * per, p = e / 3;
   const int c = (int)(e - p * 3);
   const int h = (int)(p / W), w = (int)(p - (int64_t)h * W);
@@ -136,13 +144,17 @@ __global__ void __launch_bounds__(kThreads) k_lpips_input(const float* __restric
   const float* src = img ? y : x;
   float v = src[n * s.n + c * s.c + h * s.h + w * s.w];
   if (normalize) v = 2.f * v - 1.f;
-  act[i] = (v - shift_scale[c]) / shift_scale[4 + c];
+  act[((img ? y_slot0 : 0) + blockIdx.y) * per + e] = (v - shift_scale[c]) / shift_scale[4 + c];
 }
 
 // ---------------------------------------------------------------- convolution
 struct ConvArgs {
-  const float* in;  // source activations [2][Hs][Ws][Cin]
-  float* out;       // [2][H][W][Cout]
+  const float* in;   // source activations [split][Hs][Ws][Cin] of the images blockIdx.z < split
+  const float* in2;  // ... and of the images blockIdx.z >= split (image blockIdx.z - split)
+  float* out;        // [split][H][W][Cout]
+  float* out2;
+  int split;
+  const float* mask;  // kEpiMask: the saved activation [images][H][W][Cout] whose sign gates the result
   const float* w;   // packed [Cout][Kp]
   const float* b;   // [Cout]
   int H, W;         // output (= input after the pool) size
@@ -152,6 +164,9 @@ struct ConvArgs {
 };
 
 enum { kModeFirst = 0, kModePlain = 1, kModePool = 2 };
+// epilogue: the forward's bias + ReLU; the data gradient as it is (its consumer is the tap kernel); the data gradient
+// times the ReLU mask of the layer input's saved activation
+enum { kEpiRelu = 0, kEpiRaw = 1, kEpiMask = 2 };
 
 // pixel m (0..127) of a workgroup tile: quad m >> 2 in a 4 x 8 quad grid, position m & 3 inside the quad
 __device__ __forceinline__ void tile_pixel(int m, int h0, int w0, int& h, int& w) {
@@ -169,7 +184,7 @@ __device__ __forceinline__ f32x4 max4(f32x4 a, f32x4 b) {
   return r;
 }
 
-template <int BN, int MODE>
+template <int BN, int MODE, int EPI>
 __global__ void __launch_bounds__(kThreads) k_lpips_conv(ConvArgs a) {
   constexpr int TN = BN / 64;                   // 32 x 32 accumulator tiles per wave along N (the wave's M: 2 tiles)
   constexpr int BLD = BN * kBK / 4 / kThreads;  // float4 loads of B per thread and chunk
@@ -180,7 +195,8 @@ __global__ void __launch_bounds__(kThreads) k_lpips_conv(ConvArgs a) {
   const int wm = wave & 1, wn = wave >> 1, li = lane & 31, lh = lane >> 5;
   const int tile = blockIdx.x, img = blockIdx.z, n0 = blockIdx.y * BN;
   const int h0 = (tile / a.tiles_w) * kTileH, w0 = (tile % a.tiles_w) * kTileW;
-  const float* in = a.in + img * a.in_img;
+  const int simg = img < a.split ? img : img - a.split;
+  const float* in = (img < a.split ? a.in : a.in2) + simg * a.in_img;
   const float* wp = a.w + (int64_t)n0 * a.Kp;
   const int H = a.H, W = a.W, Cin = a.Cin;
 
@@ -286,11 +302,12 @@ __global__ void __launch_bounds__(kThreads) k_lpips_conv(ConvArgs a) {
   }
 
   // epilogue: accumulator register r of lane (li, lh) is row (r & 3) + 8 (r >> 2) + 4 lh, column li of its tile
-  float* out = a.out + img * a.out_img;
+  float* out = (img < a.split ? a.out : a.out2) + simg * a.out_img;
+  const float* mask = EPI == kEpiMask ? a.mask + img * a.out_img : nullptr;
 #pragma unroll
   for (int tn = 0; tn < TN; ++tn) {
     const int n = n0 + (BN / 2) * wn + 32 * tn + li;
-    const float bn = a.b[n];
+    const float bn = EPI == kEpiRelu ? a.b[n] : 0.f;
 #pragma unroll
     for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
@@ -298,24 +315,33 @@ __global__ void __launch_bounds__(kThreads) k_lpips_conv(ConvArgs a) {
         int h, w;
         tile_pixel(64 * wm + 32 * tm + (r & 3) + 8 * (r >> 2) + 4 * lh, h0, w0, h, w);
         if (h < H && w < W) {
-          const float v = acc[tm][tn][r] + bn;
-          out[((int64_t)h * W + w) * a.Cout + n] = v < 0.f ? 0.f : v;  // ReLU (a NaN stays a NaN)
+          const int64_t o = ((int64_t)h * W + w) * a.Cout + n;
+          if (EPI == kEpiRelu) {
+            const float v = acc[tm][tn][r] + bn;
+            out[o] = v < 0.f ? 0.f : v;  // ReLU (a NaN stays a NaN)
+          } else if (EPI == kEpiMask) {
+            out[o] = mask[o] > 0.f ? acc[tm][tn][r] : 0.f;
+          } else {
+            out[o] = acc[tm][tn][r];
+          }
         }
       }
   }
 }
 
 // ---------------------------------------------------------------- head
-// per pixel p of a tap [2][HW][C]: sum_c lin[c] (fx / (|fx| + 1e-10) - fy / (|fy| + 1e-10))^2 in float64; one
-// partial (the workgroup's sum) per kHeadPix pixels
-__global__ void __launch_bounds__(kThreads) k_lpips_head(const float* __restrict__ act, int64_t HW, int C,
-                                                         const float* __restrict__ lin, double* __restrict__ partials) {
+// per pixel p of a tap of pair blockIdx.y (ax, ay: the x and the y images [pairs][HW][C]):
+// sum_c lin[c] (fx / (|fx| + 1e-10) - fy / (|fy| + 1e-10))^2 in float64; one partial (the workgroup's sum) per kHeadPix
+// pixels of one pair, pair b's at partials + b * pair_stride
+__global__ void __launch_bounds__(kThreads) k_lpips_head(const float* __restrict__ ax, const float* __restrict__ ay,
+                                                         int64_t HW, int C, const float* __restrict__ lin,
+                                                         double* __restrict__ partials, int64_t pair_stride) {
   __shared__ double red[kThreads / 64];
   const int64_t p = (int64_t)blockIdx.x * kHeadPix + threadIdx.x;
   double v = 0.0;
   if (p < HW) {
-    const float* fx = act + p * C;
-    const float* fy = act + (HW + p) * C;
+    const float* fx = ax + (blockIdx.y * HW + p) * C;
+    const float* fy = ay + (blockIdx.y * HW + p) * C;
     double sxx = 0.0, syy = 0.0;
     for (int c = 0; c < C; c += 4) {
       const f32x4 u = ld4(fx + c), w = ld4(fy + c);
@@ -336,7 +362,7 @@ __global__ void __launch_bounds__(kThreads) k_lpips_head(const float* __restrict
     }
   }
   const double tot = block_sum(v, red);
-  if (threadIdx.x == 0) partials[blockIdx.x] = tot;
+  if (threadIdx.x == 0) partials[blockIdx.y * pair_stride + blockIdx.x] = tot;
 }
 
 struct FinishArgs {
@@ -344,11 +370,14 @@ struct FinishArgs {
   double inv_hw[kTaps];
 };
 
-// pair n: each tap's partials in a fixed order -> its spatial mean; out[n] = the sum over the taps
-__global__ void __launch_bounds__(kThreads) k_lpips_finish(const double* __restrict__ partials, FinishArgs f, int64_t n,
-                                                           int64_t N, float* __restrict__ out,
+// pair n = n0 + blockIdx.x (its partials at blockIdx.x * pair_stride): each tap's partials in a fixed order -> its
+// spatial mean; out[n] = the sum over the taps
+__global__ void __launch_bounds__(kThreads) k_lpips_finish(const double* __restrict__ partials, int64_t pair_stride,
+                                                           FinishArgs f, int64_t n0, int64_t N, float* __restrict__ out,
                                                            float* __restrict__ per_layer) {
   __shared__ double red[kThreads / 64];
+  const int64_t n = n0 + blockIdx.x;
+  partials += blockIdx.x * pair_stride;
   double total = 0.0;
   for (int t = 0; t < kTaps; ++t) {
     double s = 0.0;
@@ -389,9 +418,295 @@ static int64_t partial_count(int H, int W) {
 
 constexpr int kMaxSide = 1 << 14;
 
-template <int BN, int MODE>
-static void launch_conv(const ConvArgs& a, int tiles, hipStream_t s) {
-  k_lpips_conv<BN, MODE><<<dim3((unsigned)tiles, (unsigned)(a.Cout / BN), 2), kThreads, 0, s>>>(a);
+// ================================================================ the gradient with respect to the images
+// ---------------------------------------------------------------- data-gradient weight pack
+// dX = conv3x3(dY, W') with W'[ci][tap][co] = W[co][ci][8 - tap]: the forward's implicit GEMM with Cin and Cout
+// exchanged.  [Cout][Cin][3][3] -> [Cin][9 Cout] with k = tap * Cout + co, the [N][Kp] layout k_lpips_conv reads.
+__global__ void __launch_bounds__(kThreads) k_lpips_pack_dgrad(const float* __restrict__ w, int Cin, int Cout,
+                                                               float* __restrict__ dst) {
+  const int64_t K = 9 * (int64_t)Cout;
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= (int64_t)Cin * K) return;
+  const int ci = (int)(i / K), k = (int)(i - ci * K);
+  const int tap = k / Cout, co = k - tap * Cout;
+  dst[i] = w[((int64_t)co * Cin + ci) * 9 + (8 - tap)];
+}
+
+// the first layer's [64][3][3][3] -> [tap][ci][co] with the tap flipped (k_lpips_first_bwd)
+__global__ void __launch_bounds__(kThreads) k_lpips_pack_dgrad_first(const float* __restrict__ w, float* __restrict__ dst) {
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= 27 * 64) return;
+  const int tap = i / 192, ci = (i - tap * 192) / 64, co = i & 63;
+  dst[i] = w[(co * 3 + ci) * 9 + (8 - tap)];
+}
+
+struct GradBlobLayout {
+  int64_t w[kLayers], total;  // w[0]: the first layer's [9][3][64]; w[l]: [Cin][9 Cout]
+};
+
+static GradBlobLayout grad_blob_layout() {
+  GradBlobLayout L{};
+  int64_t o = 0;
+  for (int l = 0; l < kLayers; ++l) {
+    L.w[l] = o;
+    o += l == 0 ? 27 * 64 : (int64_t)kCin[l] * 9 * kCout[l];
+  }
+  L.total = o;
+  return L;
+}
+
+// ---------------------------------------------------------------- tap backward
+// One tap of pair b = blockIdx.y, eight threads per pixel (thread j of a pixel takes the channel quads j, j + 8, ...),
+// float64.  With s = |f|, u = f / (s + eps), g_c = 2 lin_c (ux_c - uy_c) up[b] / HW the head's gradient is
+//   x image:  g_k / (sx + eps) - fx_k (g . fx) / (sx (sx + eps)^2),     y image: the same with -g and fy;
+// a pixel whose tap vector is all zero gets 0 (autograd: NaN, 0 * inf from sqrt).  To it the kernel adds what arrives
+// through the max-pool from the next stage (`pooled`: the raw data gradient of that stage's first convolution, at the
+// pooled size Hp x Wp = floor(H / 2) x floor(W / 2)): a window's value goes to its FIRST maximum in row-major order
+// (max_pool2d's rule); an odd last row or column lies in no window.  The sum, where f > 0 (the ReLU mask), is the
+// gradient with respect to the tap layer's pre-activation, rounded once to float32.
+struct TapBwdArgs {
+  const float* fx;  // the tap's activations, x group and y group: [B][HW][C]
+  const float* fy;
+  const float* lin;
+  const double* up;  // [B]
+  const float* px;   // pooled gradients [B][Hp Wp][C] of the two groups, or null (relu5_3 starts the chain)
+  const float* py;
+  float* gx;  // out [B][HW][C]; null: that image has no gradient
+  float* gy;
+  int H, W, C, Hp, Wp;
+};
+
+constexpr int kTapSub = 8, kTapPix = kThreads / kTapSub;
+
+__device__ __forceinline__ double sub_sum8(double v) {
+  v += __shfl_xor(v, 1, 64);
+  v += __shfl_xor(v, 2, 64);
+  v += __shfl_xor(v, 4, 64);
+  return v;
+}
+
+__global__ void __launch_bounds__(kThreads) k_lpips_tap_bwd(TapBwdArgs a) {
+  const int sub = threadIdx.x & (kTapSub - 1), C = a.C;
+  const int64_t HW = (int64_t)a.H * a.W, b = blockIdx.y;
+  const int64_t p = (int64_t)blockIdx.x * kTapPix + (threadIdx.x >> 3);
+  const bool ok = p < HW;  // (the threads past the end still take part in the shuffles)
+  const float* fx = a.fx + (b * HW + (ok ? p : 0)) * C;
+  const float* fy = a.fy + (b * HW + (ok ? p : 0)) * C;
+  double sxx = 0.0, syy = 0.0;
+  if (ok)
+    for (int c = 4 * sub; c < C; c += 4 * kTapSub) {
+      const f32x4 u = ld4(fx + c), w = ld4(fy + c);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        sxx += (double)u[j] * (double)u[j];
+        syy += (double)w[j] * (double)w[j];
+      }
+    }
+  sxx = sub_sum8(sxx);
+  syy = sub_sum8(syy);
+  const double sx = sqrt(sxx), sy = sqrt(syy);
+  const double ix = 1.0 / (sx + 1e-10), iy = 1.0 / (sy + 1e-10);
+  double dfx = 0.0, dfy = 0.0;  // sum_c lin_c (ux_c - uy_c) f_c for the two images
+  if (ok)
+    for (int c = 4 * sub; c < C; c += 4 * kTapSub) {
+      const f32x4 u = ld4(fx + c), w = ld4(fy + c), l = ld4(a.lin + c);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const double ld = (double)l[j] * ((double)u[j] * ix - (double)w[j] * iy);
+        dfx += ld * (double)u[j];
+        dfy += ld * (double)w[j];
+      }
+    }
+  dfx = sub_sum8(dfx);
+  dfy = sub_sum8(dfy);
+  if (!ok) return;
+  const double k = 2.0 * a.up[b] / (double)HW;
+  const double cx = sx > 0.0 ? k * dfx * ix * ix / sx : 0.0, cy = sy > 0.0 ? k * dfy * iy * iy / sy : 0.0;
+  const double kx = sx > 0.0 ? k * ix : 0.0, ky = sy > 0.0 ? k * iy : 0.0;
+
+  const int h = (int)(p / a.W), w = (int)(p - (int64_t)h * a.W);
+  const bool pooled = a.px != nullptr && (h >> 1) < a.Hp && (w >> 1) < a.Wp;
+  const int r = 2 * (h & 1) + (w & 1);  // this pixel's place in its window, row-major
+  const int64_t win0 = (b * HW + (int64_t)(h & ~1) * a.W + (w & ~1)) * C;  // the window's first pixel
+  const int64_t pin = pooled ? ((b * a.Hp + (h >> 1)) * a.Wp + (w >> 1)) * C : 0;
+  // the pooled gradient of the channels c .. c + 3 where this pixel is its window's first maximum, else 0
+  auto through_pool = [&](const float* act, const float* pg, int c) {
+    f32x4 out = {0.f, 0.f, 0.f, 0.f};
+    if (!pooled) return out;
+    const float* q = act + win0 + c;
+    const f32x4 v[4] = {ld4(q), ld4(q + C), ld4(q + (int64_t)a.W * C), ld4(q + (int64_t)a.W * C + C)};
+    const f32x4 g = ld4(pg + pin + c);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float mine = r == 0 ? v[0][j] : r == 1 ? v[1][j] : r == 2 ? v[2][j] : v[3][j];
+      bool win = true;
+#pragma unroll
+      for (int o = 0; o < 4; ++o) win = win && (o < r ? mine > v[o][j] : o > r ? mine >= v[o][j] : true);
+      out[j] = win ? g[j] : 0.f;
+    }
+    return out;
+  };
+  for (int c = 4 * sub; c < C; c += 4 * kTapSub) {
+    const f32x4 u = ld4(fx + c), v = ld4(fy + c), l = ld4(a.lin + c);
+    double d[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) d[j] = (double)l[j] * ((double)u[j] * ix - (double)v[j] * iy);
+    if (a.gx) {
+      const f32x4 in = through_pool(a.fx, a.px, c);
+      f32x4 o;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        o[j] = u[j] > 0.f ? (float)(kx * d[j] - (double)u[j] * cx + (double)in[j]) : 0.f;
+      *reinterpret_cast<f32x4*>(a.gx + (b * HW + p) * C + c) = o;
+    }
+    if (a.gy) {
+      const f32x4 in = through_pool(a.fy, a.py, c);
+      f32x4 o;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        o[j] = v[j] > 0.f ? (float)((double)v[j] * cy - ky * d[j] + (double)in[j]) : 0.f;
+      *reinterpret_cast<f32x4*>(a.gy + (b * HW + p) * C + c) = o;
+    }
+  }
+}
+
+// ---------------------------------------------------------------- first layer and input stage, backward
+// conv1_1's data gradient has three channels (a matrix-core tile would be 95 % padding): four threads per pixel, each
+// 16 of the 64 channels of the nine neighbours (576 multiply-adds per colour), summed over the four in a fixed order;
+// then the scaling layer (/ scale, and x 2 under normalize) and the store through the gradient tensor's own strides.
+struct FirstBwdArgs {
+  const float* g;      // gradient w.r.t. conv1_1's pre-activation [B][H][W][64]
+  const float* w;      // [9][3][64], tap flipped
+  const float* scale;  // 3 floats
+  float* d;            // image gradient of pair blockIdx.y, element strides s
+  Strides4 s;
+  int H, W, normalize;
+};
+
+constexpr int kFirstSub = 4, kFirstPix = kThreads / kFirstSub;
+
+__global__ void __launch_bounds__(kThreads) k_lpips_first_bwd(FirstBwdArgs a) {
+  __shared__ __attribute__((aligned(16))) float Wl[27 * 64];
+  for (int e = threadIdx.x; e < 27 * 64; e += kThreads) FSN_AT(Wl, e) = a.w[e];
+  __syncthreads();
+  const int sub = threadIdx.x & (kFirstSub - 1), H = a.H, W = a.W;
+  const int64_t HW = (int64_t)H * W, b = blockIdx.y;
+  const int64_t p = (int64_t)blockIdx.x * kFirstPix + (threadIdx.x >> 2);
+  const bool ok = p < HW;
+  const int h = ok ? (int)(p / W) : 0, w = ok ? (int)(p - (int64_t)h * W) : 0;
+  const float* g = a.g + b * HW * 64;
+  float acc[3] = {0.f, 0.f, 0.f};
+  if (ok)
+    for (int tap = 0; tap < 9; ++tap) {
+      const int sh = h + tap / 3 - 1, sw = w + tap % 3 - 1;
+      if (sh < 0 || sh >= H || sw < 0 || sw >= W) continue;
+      const float* src = g + ((int64_t)sh * W + sw) * 64;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = 4 * (sub + kFirstSub * j);
+        const f32x4 v = ld4(src + c);
+#pragma unroll
+        for (int ci = 0; ci < 3; ++ci) {
+          const f32x4 wv = *reinterpret_cast<const f32x4*>(FSN_SPAN(Wl, (tap * 3 + ci) * 64 + c, 4));
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[ci] = __builtin_fmaf(v[e], wv[e], acc[ci]);
+        }
+      }
+    }
+#pragma unroll
+  for (int ci = 0; ci < 3; ++ci) {
+    acc[ci] += __shfl_xor(acc[ci], 1, 64);
+    acc[ci] += __shfl_xor(acc[ci], 2, 64);
+  }
+  if (ok && sub < 3) {
+    float v = (sub == 0 ? acc[0] : sub == 1 ? acc[1] : acc[2]) / a.scale[sub];
+    if (a.normalize) v *= 2.f;
+    a.d[b * a.s.n + sub * a.s.c + h * a.s.h + w * a.s.w] = v;
+  }
+}
+
+// ---------------------------------------------------------------- training workspace
+// floats: the normalised inputs [2B][HW][3]; every layer's post-ReLU activation - a tap's for all 2B images (x group,
+// then y group: the head reads both), any other layer's for the back-propagated images only; two ping-pong buffers for
+// the images without a gradient; two for the gradients; the head partials (doubles).
+struct TrainLayout {
+  int64_t in0, act[kLayers], pp[2], g[2], partials, pair_partials, total;
+  int nb;  // back-propagated images: B (want_dx + want_dy)
+};
+
+static int64_t round4(int64_t v) { return (v + 3) & ~(int64_t)3; }
+
+static TrainLayout train_layout(int64_t B, int H, int W, int want_dx, int want_dy) {
+  TrainLayout T{};
+  const Dims d = stage_dims(H, W);
+  const int sides = (want_dx ? 1 : 0) + (want_dy ? 1 : 0);
+  T.nb = (int)(B * sides);
+  const int64_t HW = (int64_t)H * W;
+  int64_t o = 0;
+  T.in0 = o;
+  o += round4(2 * B * HW * 3);
+  int stage = 0;
+  for (int l = 0; l < kLayers; ++l) {
+    if (kPoolIn[l]) ++stage;
+    T.act[l] = o;
+    o += (kTapOf[l] >= 0 ? 2 * B : (int64_t)T.nb) * d.H[stage] * d.W[stage] * kCout[l];
+  }
+  for (int k = 0; k < 2; ++k) {
+    T.pp[k] = o;
+    o += sides == 2 ? 0 : B * HW * 64;
+  }
+  for (int k = 0; k < 2; ++k) {
+    T.g[k] = o;
+    o += (int64_t)T.nb * HW * 64;
+  }
+  T.partials = o;  // a multiple of four floats: the doubles are aligned
+  T.pair_partials = partial_count(H, W);
+  o += 2 * B * T.pair_partials;
+  T.total = o;
+  return T;
+}
+
+constexpr int64_t kMaxPairs = 32767;  // 2B images on blockIdx.z
+
+static int check_train_shape(const char* who, int64_t B, int H, int W, int want_dx, int want_dy) {
+  FSN_REQUIRE(B >= 1 && B <= kMaxPairs, FSN_E_INVALID, "%s: B = %lld pairs (1 .. %lld per pass)", who, (long long)B,
+              (long long)kMaxPairs);
+  FSN_REQUIRE(H >= 16 && W >= 16, FSN_E_INVALID, "%s: image %dx%d: LPIPS-VGG needs at least 16x16 (four pools)", who, H,
+              W);
+  FSN_REQUIRE(H <= kMaxSide && W <= kMaxSide, FSN_E_UNSUPPORTED, "%s: image %dx%d above %d", who, H, W, kMaxSide);
+  FSN_REQUIRE(want_dx || want_dy, FSN_E_INVALID, "%s: neither dx nor dy is wanted", who);
+  return FSN_OK;
+}
+
+template <int BN, int MODE, int EPI = kEpiRelu>
+static void launch_conv(const ConvArgs& a, int tiles, int images, hipStream_t s) {
+  k_lpips_conv<BN, MODE, EPI><<<dim3((unsigned)tiles, (unsigned)(a.Cout / BN), (unsigned)images), kThreads, 0, s>>>(a);
+}
+
+// layer l of the forward on `images` images (a.in .. a.out2, a.split set by the caller)
+static void forward_layer(int l, ConvArgs& a, const float* blob, const BlobLayout& L, const Dims& d, int stage, int Hs,
+                          int Ws, int images, hipStream_t s) {
+  a.w = blob + L.w[l];
+  a.b = blob + L.b[l];
+  a.mask = nullptr;
+  a.H = d.H[stage];
+  a.W = d.W[stage];
+  a.Ws = Ws;
+  a.Cin = kCin[l];
+  a.Cout = kCout[l];
+  a.Kp = kp_of(l);
+  a.tiles_w = (a.W + kTileW - 1) / kTileW;
+  a.in_img = (int64_t)Hs * Ws * kCin[l];
+  a.out_img = (int64_t)a.H * a.W * kCout[l];
+  const int tiles = ((a.H + kTileH - 1) / kTileH) * a.tiles_w;
+  if (l == 0)
+    launch_conv<64, kModeFirst>(a, tiles, images, s);
+  else if (kCout[l] == 64)
+    launch_conv<64, kModePlain>(a, tiles, images, s);
+  else if (kPoolIn[l])
+    launch_conv<128, kModePool>(a, tiles, images, s);
+  else
+    launch_conv<128, kModePlain>(a, tiles, images, s);
 }
 
 }  // namespace fsn
@@ -468,47 +783,240 @@ extern "C" int fsn_lpips_vgg(const void* packed, const float* x, const float* y,
   for (int64_t n = 0; n < N; ++n) {
     const int64_t in_elems = 2 * (int64_t)H * W * 3;
     k_lpips_input<<<(unsigned)((in_elems + kThreads - 1) / kThreads), kThreads, 0, s>>>(
-        x, y, sx, sy, n, H, W, normalize, blob + L.shift, buf[0]);
+        x, y, sx, sy, n, H, W, normalize, blob + L.shift, 1, buf[0]);
     FSN_LAUNCH_CHECK("k_lpips_input");
     int cur = 0, stage = 0, Hs = H, Ws = W;
     for (int l = 0; l < kLayers; ++l) {
       if (kPoolIn[l]) ++stage;
       ConvArgs a{};
+      const int64_t in_img = (int64_t)Hs * Ws * kCin[l], out_img = (int64_t)d.H[stage] * d.W[stage] * kCout[l];
       a.in = buf[cur];
+      a.in2 = buf[cur] + in_img;
       a.out = buf[cur ^ 1];
-      a.w = blob + L.w[l];
-      a.b = blob + L.b[l];
-      a.H = d.H[stage];
-      a.W = d.W[stage];
-      a.Ws = Ws;
-      a.Cin = kCin[l];
-      a.Cout = kCout[l];
-      a.Kp = kp_of(l);
-      a.tiles_w = (a.W + kTileW - 1) / kTileW;
-      a.in_img = (int64_t)Hs * Ws * kCin[l];
-      a.out_img = (int64_t)a.H * a.W * kCout[l];
-      const int tiles = ((a.H + kTileH - 1) / kTileH) * a.tiles_w;
-      if (l == 0)
-        launch_conv<64, kModeFirst>(a, tiles, s);
-      else if (kCout[l] == 64)
-        launch_conv<64, kModePlain>(a, tiles, s);
-      else if (kPoolIn[l])
-        launch_conv<128, kModePool>(a, tiles, s);
-      else
-        launch_conv<128, kModePlain>(a, tiles, s);
+      a.out2 = buf[cur ^ 1] + out_img;
+      a.split = 1;
+      forward_layer(l, a, blob, L, d, stage, Hs, Ws, 2, s);
       FSN_LAUNCH_CHECK("k_lpips_conv");
       cur ^= 1;
       Hs = a.H;
       Ws = a.W;
       const int t = kTapOf[l];
       if (t >= 0) {
-        k_lpips_head<<<(unsigned)fin.count[t], kThreads, 0, s>>>(buf[cur], (int64_t)a.H * a.W, kTapC[t],
-                                                                 blob + L.lin[t], partials + fin.off[t]);
+        const int64_t hw = (int64_t)a.H * a.W;
+        k_lpips_head<<<(unsigned)fin.count[t], kThreads, 0, s>>>(buf[cur], buf[cur] + hw * kTapC[t], hw, kTapC[t],
+                                                                 blob + L.lin[t], partials + fin.off[t], 0);
         FSN_LAUNCH_CHECK("k_lpips_head");
       }
     }
-    k_lpips_finish<<<1, kThreads, 0, s>>>(partials, fin, n, N, out, per_layer);
+    k_lpips_finish<<<1, kThreads, 0, s>>>(partials, 0, fin, n, N, out, per_layer);
     FSN_LAUNCH_CHECK("k_lpips_finish");
+  }
+  return FSN_OK;
+}
+
+extern "C" int64_t fsn_lpips_grad_pack_bytes(void) { return grad_blob_layout().total * (int64_t)sizeof(float); }
+
+extern "C" int fsn_lpips_grad_pack(const float* const* conv_w_host, void* packed_grad, fsn_stream_t stream) {
+  FSN_REQUIRE(conv_w_host && packed_grad, FSN_E_INVALID, "fsn_lpips_grad_pack: null pointer");
+  for (int l = 0; l < kLayers; ++l)
+    FSN_REQUIRE(conv_w_host[l], FSN_E_INVALID, "fsn_lpips_grad_pack: null pointer (layer %d)", l);
+  const GradBlobLayout G = grad_blob_layout();
+  float* dst = static_cast<float*>(packed_grad);
+  hipStream_t s = as_stream(stream);
+  k_lpips_pack_dgrad_first<<<(27 * 64 + kThreads - 1) / kThreads, kThreads, 0, s>>>(conv_w_host[0], dst + G.w[0]);
+  for (int l = 1; l < kLayers; ++l) {
+    const int64_t n = (int64_t)kCin[l] * 9 * kCout[l];
+    k_lpips_pack_dgrad<<<(unsigned)((n + kThreads - 1) / kThreads), kThreads, 0, s>>>(conv_w_host[l], kCin[l], kCout[l],
+                                                                                      dst + G.w[l]);
+  }
+  FSN_LAUNCH_CHECK("fsn_lpips_grad_pack");
+  return FSN_OK;
+}
+
+extern "C" int64_t fsn_lpips_train_workspace_floats(int64_t B, int H, int W, int want_dx, int want_dy) {
+  const int rc = check_train_shape("fsn_lpips_train_workspace_floats", B, H, W, want_dx, want_dy);
+  if (rc != FSN_OK) return rc;
+  return train_layout(B, H, W, want_dx, want_dy).total;
+}
+
+extern "C" int fsn_lpips_vgg_fwd_save(const void* packed, const float* x, const float* y, int64_t B, int H, int W,
+                                      const int64_t* x_strides_host, const int64_t* y_strides_host, int normalize,
+                                      int want_dx, int want_dy, float* out, float* per_layer, float* workspace,
+                                      fsn_stream_t stream) {
+  const int rc = check_train_shape("fsn_lpips_vgg_fwd_save", B, H, W, want_dx, want_dy);
+  if (rc != FSN_OK) return rc;
+  FSN_REQUIRE(packed && x && y && out && workspace, FSN_E_INVALID, "fsn_lpips_vgg_fwd_save: null pointer");
+  FSN_REQUIRE(x_strides_host && y_strides_host, FSN_E_INVALID, "fsn_lpips_vgg_fwd_save: null stride array");
+
+  const BlobLayout L = blob_layout();
+  const float* blob = static_cast<const float*>(packed);
+  const Dims d = stage_dims(H, W);
+  const TrainLayout T = train_layout(B, H, W, want_dx, want_dy);
+  double* partials = reinterpret_cast<double*>(workspace + T.partials);
+  FinishArgs fin{};
+  int64_t off = 0;
+  for (int t = 0; t < kTaps; ++t) {
+    const int64_t hw = (int64_t)d.H[t] * d.W[t];
+    fin.off[t] = off;
+    fin.count[t] = head_blocks(hw);
+    fin.inv_hw[t] = 1.0 / (double)hw;
+    off += fin.count[t];
+  }
+  const Strides4 sx{x_strides_host[0], x_strides_host[1], x_strides_host[2], x_strides_host[3]};
+  const Strides4 sy{y_strides_host[0], y_strides_host[1], y_strides_host[2], y_strides_host[3]};
+  hipStream_t s = as_stream(stream);
+  const int want[2] = {want_dx ? 1 : 0, want_dy ? 1 : 0};
+
+  const int64_t in_elems = 2 * (int64_t)H * W * 3;
+  k_lpips_input<<<dim3((unsigned)((in_elems + kThreads - 1) / kThreads), (unsigned)B), kThreads, 0, s>>>(
+      x, y, sx, sy, 0, H, W, normalize, blob + L.shift, B, workspace + T.in0);
+  FSN_LAUNCH_CHECK("k_lpips_input");
+
+  // where group `side` (0: the x images, 1: the y images) keeps layer l's output; l = -1: the normalised input
+  int pcur = 0;  // the ping-pong buffer that holds the latest unsaved activation
+  auto where = [&](int l, int side, int64_t img, int pp) -> float* {
+    if (l < 0 || kTapOf[l] >= 0) return workspace + (l < 0 ? T.in0 : T.act[l]) + side * B * img;
+    if (want[side]) return workspace + T.act[l] + (side == 1 && want[0] ? B * img : 0);
+    return workspace + T.pp[pp];
+  };
+  int stage = 0, Hs = H, Ws = W;
+  for (int l = 0; l < kLayers; ++l) {
+    if (kPoolIn[l]) ++stage;
+    const int64_t in_img = (int64_t)Hs * Ws * kCin[l], out_img = (int64_t)d.H[stage] * d.W[stage] * kCout[l];
+    ConvArgs a{};
+    a.in = where(l - 1, 0, in_img, pcur);
+    a.in2 = where(l - 1, 1, in_img, pcur);
+    a.out = where(l, 0, out_img, pcur ^ 1);
+    a.out2 = where(l, 1, out_img, pcur ^ 1);
+    a.split = (int)B;
+    forward_layer(l, a, blob, L, d, stage, Hs, Ws, (int)(2 * B), s);
+    FSN_LAUNCH_CHECK("k_lpips_conv");
+    Hs = a.H;
+    Ws = a.W;
+    const int t = kTapOf[l];
+    if (t >= 0) {
+      const int64_t hw = (int64_t)a.H * a.W;
+      k_lpips_head<<<dim3((unsigned)fin.count[t], (unsigned)B), kThreads, 0, s>>>(
+          a.out, a.out2, hw, kTapC[t], blob + L.lin[t], partials + fin.off[t], T.pair_partials);
+      FSN_LAUNCH_CHECK("k_lpips_head");
+    } else {
+      pcur ^= 1;
+    }
+  }
+  k_lpips_finish<<<(unsigned)B, kThreads, 0, s>>>(partials, T.pair_partials, fin, 0, B, out, per_layer);
+  FSN_LAUNCH_CHECK("k_lpips_finish");
+  return FSN_OK;
+}
+
+template <int BN, int EPI>
+static void launch_dgrad(const ConvArgs& a, int tiles, int images, hipStream_t s) {
+  launch_conv<BN, kModePlain, EPI>(a, tiles, images, s);
+}
+
+extern "C" int fsn_lpips_vgg_bwd(const void* packed, const void* packed_grad, int64_t B, int H, int W, int normalize,
+                                 int want_dx, int want_dy, const double* upstream, float* workspace, float* dx,
+                                 const int64_t* dx_strides_host, float* dy, const int64_t* dy_strides_host,
+                                 fsn_stream_t stream) {
+  const int rc = check_train_shape("fsn_lpips_vgg_bwd", B, H, W, want_dx, want_dy);
+  if (rc != FSN_OK) return rc;
+  FSN_REQUIRE(packed && packed_grad && upstream && workspace, FSN_E_INVALID, "fsn_lpips_vgg_bwd: null pointer");
+  FSN_REQUIRE(!want_dx || (dx && dx_strides_host), FSN_E_INVALID, "fsn_lpips_vgg_bwd: dx wanted without a tensor");
+  FSN_REQUIRE(!want_dy || (dy && dy_strides_host), FSN_E_INVALID, "fsn_lpips_vgg_bwd: dy wanted without a tensor");
+
+  const BlobLayout L = blob_layout();
+  const GradBlobLayout G = grad_blob_layout();
+  const float* blob = static_cast<const float*>(packed);
+  const float* gblob = static_cast<const float*>(packed_grad);
+  const Dims d = stage_dims(H, W);
+  const TrainLayout T = train_layout(B, H, W, want_dx, want_dy);
+  hipStream_t s = as_stream(stream);
+  const bool wx = want_dx != 0, wy = want_dy != 0;
+  float* gbuf[2] = {workspace + T.g[0], workspace + T.g[1]};
+  int cur = 0;  // gbuf[cur]: the gradient the next kernel reads
+
+  // the tap kernel of tap t (stage t): gbuf[cur] holds the pooled gradient (if any); writes gbuf[cur ^ 1]
+  auto tap_bwd = [&](int t, int l, bool pooled) {
+    const int64_t img = (int64_t)d.H[t] * d.W[t] * kTapC[t];
+    TapBwdArgs a{};
+    a.fx = workspace + T.act[l];
+    a.fy = a.fx + B * img;
+    a.lin = blob + L.lin[t];
+    a.up = upstream;
+    a.H = d.H[t];
+    a.W = d.W[t];
+    a.C = kTapC[t];
+    if (pooled) {
+      a.Hp = d.H[t + 1];
+      a.Wp = d.W[t + 1];
+      const int64_t pimg = (int64_t)a.Hp * a.Wp * kTapC[t];
+      a.px = wx ? gbuf[cur] : nullptr;
+      a.py = wy ? gbuf[cur] + (wx ? B * pimg : 0) : nullptr;
+      if (!a.px) a.px = a.py;  // (non-null marks "pooled"; the x side is not written then)
+    }
+    a.gx = wx ? gbuf[cur ^ 1] : nullptr;
+    a.gy = wy ? gbuf[cur ^ 1] + (wx ? B * img : 0) : nullptr;
+    const int64_t hw = (int64_t)a.H * a.W;
+    k_lpips_tap_bwd<<<dim3((unsigned)((hw + kTapPix - 1) / kTapPix), (unsigned)B), kThreads, 0, s>>>(a);
+    cur ^= 1;
+  };
+
+  tap_bwd(4, 12, false);
+  FSN_LAUNCH_CHECK("k_lpips_tap_bwd");
+  int stage = kTaps - 1;
+  for (int l = kLayers - 1; l >= 1; --l) {
+    // the data gradient of layer l: the forward's GEMM with Cin and Cout exchanged, on the back-propagated images
+    ConvArgs a{};
+    a.in = a.in2 = gbuf[cur];
+    a.out = a.out2 = gbuf[cur ^ 1];
+    a.split = T.nb;
+    a.w = gblob + G.w[l];
+    a.b = nullptr;
+    a.mask = kPoolIn[l] ? nullptr : workspace + T.act[l - 1];
+    a.H = d.H[stage];
+    a.W = d.W[stage];
+    a.Ws = a.W;
+    a.Cin = kCout[l];
+    a.Cout = kCin[l];
+    a.Kp = 9 * kCout[l];
+    a.tiles_w = (a.W + kTileW - 1) / kTileW;
+    a.in_img = (int64_t)a.H * a.W * kCout[l];
+    a.out_img = (int64_t)a.H * a.W * kCin[l];
+    const int tiles = ((a.H + kTileH - 1) / kTileH) * a.tiles_w;
+    if (kCin[l] == 64) {
+      if (kPoolIn[l])
+        launch_dgrad<64, kEpiRaw>(a, tiles, T.nb, s);
+      else
+        launch_dgrad<64, kEpiMask>(a, tiles, T.nb, s);
+    } else {
+      if (kPoolIn[l])
+        launch_dgrad<128, kEpiRaw>(a, tiles, T.nb, s);
+      else
+        launch_dgrad<128, kEpiMask>(a, tiles, T.nb, s);
+    }
+    FSN_LAUNCH_CHECK("k_lpips_conv (data gradient)");
+    cur ^= 1;
+    if (kPoolIn[l]) {
+      --stage;
+      tap_bwd(stage, l - 1, true);
+      FSN_LAUNCH_CHECK("k_lpips_tap_bwd");
+    }
+  }
+  // gbuf[cur]: the gradient w.r.t. conv1_1's pre-activation
+  const int64_t HW = (int64_t)H * W;
+  for (int side = 0; side < 2; ++side) {
+    if (!(side ? wy : wx)) continue;
+    const int64_t* st = side ? dy_strides_host : dx_strides_host;
+    FirstBwdArgs a{};
+    a.g = gbuf[cur] + (side == 1 && wx ? B * HW * 64 : 0);
+    a.w = gblob + G.w[0];
+    a.scale = blob + L.scale;
+    a.d = side ? dy : dx;
+    a.s = Strides4{st[0], st[1], st[2], st[3]};
+    a.H = H;
+    a.W = W;
+    a.normalize = normalize;
+    k_lpips_first_bwd<<<dim3((unsigned)((HW + kFirstPix - 1) / kFirstPix), (unsigned)B), kThreads, 0, s>>>(a);
+    FSN_LAUNCH_CHECK("k_lpips_first_bwd");
   }
   return FSN_OK;
 }

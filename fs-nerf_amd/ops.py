@@ -1601,3 +1601,72 @@ def lpips_vgg(packed: Tensor, x: Tensor, y: Tensor, normalize: bool) -> Tuple[Te
     _launch("fsn_lpips_vgg", dev, _p(packed), _p(x), _p(y), N, H, W, _nchw_strides(x), _nchw_strides(y),
             1 if normalize else 0, _p(out), _p(per), _p(ws))
     return out, per
+
+
+def lpips_grad_pack(conv_w: Sequence[Tensor], out: Optional[Tensor] = None) -> Tensor:
+    """fsn_lpips_grad_pack: the 13 VGG16 convolution weights -> the data-gradient kernels' uint8 blob ([Cin][9 Cout]
+    per layer, taps flipped) on their device (re-uses `out`)."""
+    dev = conv_w[0].device
+    keep = [t.detach().to(dev, torch.float32).contiguous() for t in conv_w]
+    if len(keep) != 13 or not all(t.is_cuda for t in keep):
+        raise RuntimeError("lpips_grad_pack: expected 13 GPU tensors (the HIP path has no CPU fallback)")
+    nbytes = _size("fsn_lpips_grad_pack_bytes", None)
+    if out is None or out.numel() != nbytes or out.device != dev:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _launch("fsn_lpips_grad_pack", dev, _ptr_array(keep), _p(out))
+    return out
+
+
+def lpips_vgg_fwd_save(packed: Tensor, x: Tensor, y: Tensor, normalize: bool, *, want_dx: bool = True,
+                       want_dy: bool = True) -> Tuple[Tensor, Tensor, Tensor]:
+    """fsn_lpips_vgg_fwd_save on two float32 (B, 3, H, W) views of any strides, all B pairs in one pass ->
+    (float32 [B], float32 [5, B], workspace): lpips_vgg's values bit for bit, and the workspace lpips_vgg_bwd reads
+    (the activations of the images that need a gradient)."""
+    x, y = _gpu_f32_view(x, "in0"), _gpu_f32_view(y, "in1")
+    B, Ch, H, W = x.shape
+    assert Ch == 3 and y.shape == x.shape and y.device == x.device
+    if not (want_dx or want_dy):
+        raise ValueError("lpips_vgg_fwd_save: neither dx nor dy is wanted")
+    dev = x.device
+    out = torch.empty(B, dtype=torch.float32, device=dev)
+    per = torch.empty(5, B, dtype=torch.float32, device=dev)
+    ws = torch.empty(_size("fsn_lpips_train_workspace_floats", None, B, H, W, int(want_dx), int(want_dy)),
+                     dtype=torch.float32, device=dev)
+    _launch("fsn_lpips_vgg_fwd_save", dev, _p(packed), _p(x), _p(y), B, H, W, _nchw_strides(x), _nchw_strides(y),
+            1 if normalize else 0, int(want_dx), int(want_dy), _p(out), _p(per), _p(ws))
+    return out, per, ws
+
+
+def lpips_vgg_bwd(packed: Tensor, packed_grad: Tensor, workspace: Tensor, shape: Sequence[int], normalize: bool,
+                  upstream: Tensor, *, want_dx: bool = True, want_dy: bool = True, dx: Optional[Tensor] = None,
+                  dy: Optional[Tensor] = None) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """fsn_lpips_vgg_bwd on the workspace lpips_vgg_fwd_save returned for (B, 3, H, W) = `shape` and the same
+    normalize / want_dx / want_dy: the gradient of sum_b upstream[b] * lpips_b -> (dx, dy), float32 (B, 3, H, W); a
+    gradient not wanted is None.  upstream: B values on the device (converted to float64).  `dx` / `dy`: optional
+    float32 (B, 3, H, W) views of any strides to write into instead of new contiguous tensors."""
+    B, Ch, H, W = (int(v) for v in shape)
+    assert Ch == 3
+    if not (want_dx or want_dy):
+        raise ValueError("lpips_vgg_bwd: neither dx nor dy is wanted")
+    dev = workspace.device
+    need = _size("fsn_lpips_train_workspace_floats", None, B, H, W, int(want_dx), int(want_dy))
+    if workspace.dtype != torch.float32 or workspace.numel() != need or not workspace.is_contiguous():
+        raise ValueError(f"lpips_vgg_bwd: workspace of {workspace.numel()} values, lpips_vgg_fwd_save's has {need}")
+    if not upstream.is_cuda:
+        raise RuntimeError("upstream: expected a GPU tensor (the HIP path has no CPU fallback)")
+    up = upstream.detach().to(torch.float64).reshape(-1).contiguous()
+    if up.numel() != B:
+        raise ValueError(f"upstream: expected {B} values (one per pair), got {up.numel()}")
+    outs = []
+    for want, t, name in ((want_dx, dx, "dx"), (want_dy, dy, "dy")):
+        if not want:
+            t = None
+        elif t is None:
+            t = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+        elif t.dtype != torch.float32 or tuple(t.shape) != (B, 3, H, W) or t.device != dev:
+            raise ValueError(f"{name}: expected a float32 {(B, 3, H, W)} view on {dev}")
+        outs.append(t)
+    _launch("fsn_lpips_vgg_bwd", dev, _p(packed), _p(packed_grad), B, H, W, 1 if normalize else 0, int(want_dx),
+            int(want_dy), _p(up), _p(workspace), _p(outs[0]), None if outs[0] is None else _nchw_strides(outs[0]),
+            _p(outs[1]), None if outs[1] is None else _nchw_strides(outs[1]))
+    return outs[0], outs[1]

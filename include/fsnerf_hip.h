@@ -849,7 +849,35 @@ int64_t fsn_lpips_workspace_floats(int H, int W);
 int fsn_lpips_vgg(const void* packed, const float* x, const float* y, int64_t N, int H, int W,
                   const int64_t* x_strides_host, const int64_t* y_strides_host, int normalize, float* out,
                   float* per_layer, float* workspace, fsn_stream_t stream);
-/* Debug build only: the LDS index record of k_lpips_conv (4 uint32, as fsn_debug_report's), cleared by the call. */
+/* LPIPS-VGG as a loss: the gradient of sum_b upstream[b] * lpips_b with respect to the images (the VGG and lin
+ * weights are frozen).  B pairs go through the network together, the x images and then the y images on blockIdx.z.
+ * fsn_lpips_vgg_fwd_save: fsn_lpips_vgg's values (out: B floats, per_layer (optional): [5][B]), bit for bit, and every
+ *   layer's post-ReLU activation of the images that need a gradient kept in `workspace` (of the other image: the five
+ *   taps only).  want_dx / want_dy: which image of a pair needs a gradient, not both zero.  1 <= B <= 32767.
+ * fsn_lpips_vgg_bwd: on the workspace fsn_lpips_vgg_fwd_save left (same B, H, W, normalize, want_dx, want_dy):
+ *   tap backward in float64 - with s = |f|, u = f / (s + 1e-10), g_c = 2 lin_c (ux_c - uy_c) upstream[b] / HW the x
+ *   image gets g_k / (s + eps) - f_k (g . f) / (s (s + eps)^2), the y image the same with -g; a pixel whose tap
+ *   vector is all zero gets 0 (autograd gives NaN there); plus the gradient arriving through the 2x2 max-pool, which
+ *   goes to the FIRST maximum of its window in row-major order (an odd last row or column lies in no window); times
+ *   the ReLU mask f > 0.  Convolution data gradients: the forward's MFMA kernel with Cin and Cout exchanged, on the
+ *   weights of fsn_lpips_grad_pack ([Cin][9 Cout], taps flipped).  conv1_1 and the scaling layer: one direct kernel
+ *   that writes dx / dy (DEVICE float32, HOST element strides (n, c, h, w), every element written; NULL for a
+ *   gradient not wanted).  upstream: DEVICE double [B].  No atomics, fixed summation orders: bitwise reproducible,
+ *   and a pair's gradient does not depend on the rest of the batch.
+ * fsn_lpips_grad_pack: conv_w_host as in fsn_lpips_pack -> packed_grad (fsn_lpips_grad_pack_bytes() bytes, device).
+ * fsn_lpips_train_workspace_floats: the workspace of the pair of calls, in floats (about 270 H W per back-propagated
+ *   image for the activations, 128 H W for the gradients); validates as fsn_lpips_workspace_floats. */
+int64_t fsn_lpips_grad_pack_bytes(void);
+int fsn_lpips_grad_pack(const float* const* conv_w_host, void* packed_grad, fsn_stream_t stream);
+int64_t fsn_lpips_train_workspace_floats(int64_t B, int H, int W, int want_dx, int want_dy);
+int fsn_lpips_vgg_fwd_save(const void* packed, const float* x, const float* y, int64_t B, int H, int W,
+                           const int64_t* x_strides_host, const int64_t* y_strides_host, int normalize, int want_dx,
+                           int want_dy, float* out, float* per_layer, float* workspace, fsn_stream_t stream);
+int fsn_lpips_vgg_bwd(const void* packed, const void* packed_grad, int64_t B, int H, int W, int normalize, int want_dx,
+                      int want_dy, const double* upstream, float* workspace, float* dx, const int64_t* dx_strides_host,
+                      float* dy, const int64_t* dy_strides_host, fsn_stream_t stream);
+/* Debug build only: the LDS index record of k_lpips_conv and k_lpips_first_bwd (4 uint32, as fsn_debug_report's),
+ * cleared by the call. */
 int fsn_debug_report_lpips(uint32_t* out_host);
 
 #ifdef __cplusplus

@@ -1,0 +1,43 @@
+"""Worker of tests/test_lpips_grad_gpu.py: runs the LPIPS loss (forward-save and backward) through the DEBUG library
+(FSN_LIB_PATH -> libfsnerf_hip_dbg.so: every LDS index of k_lpips_conv and k_lpips_first_bwd range-checked,
+csrc/common.hpp) at 37 x 53, a size that is no multiple of the tile and odd through every pool, and prints the violation
+record as JSON."""
+import ctypes as C
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def main():
+    import fs_nerf_amd  # noqa: F401
+    import lpips_ref as LR
+    from fs_nerf_amd import _lib as L
+    from fs_nerf_amd.core import metrics
+    from fs_nerf_amd.core.loss import LPIPSLoss
+    assert "dbg" in os.path.basename(L.LIB_PATH), L.LIB_PATH
+    dev = torch.device("cuda:0")
+    m = metrics.LPIPS()
+    m.load_state_dict(LR.random_state_dict(seed=1))
+    m = m.to(dev)
+    g = torch.Generator(device=dev).manual_seed(0)
+    x = torch.rand(2, 37, 53, 3, device=dev, generator=g)
+    y = torch.rand(2, 37, 53, 3, device=dev, generator=g)
+    for want in ((True, True), (True, False), (False, True)):
+        a, b = x.clone().requires_grad_(want[0]), y.clone().requires_grad_(want[1])
+        LPIPSLoss(m)(a, b).backward()
+        for t, w in ((a, want[0]), (b, want[1])):
+            assert (t.grad is not None) == w and (not w or bool(torch.isfinite(t.grad).all()))
+    torch.cuda.synchronize()
+    buf = (C.c_uint32 * 4)()
+    L.check(L.lib().fsn_debug_report_lpips(buf), "fsn_debug_report_lpips")
+    print("LPIPS_GRAD_DEBUG_REPORT " + json.dumps(list(buf)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
