@@ -458,6 +458,7 @@ struct NetDev {
   const float* aux;       // LDS copy of the blob's aux region
   const float* pos_mask;  // LDS, 64 floats (ones when no mask)
   const float* dir_mask;  // LDS, 32 floats
+  bool pos_masked;        // a position mask was given (wave-uniform); false: pos_mask is all ones
   int32_t n_layers;
   uint32_t skip_mask;
   int32_t n_freqs_pos, n_freqs_dir;
@@ -493,7 +494,8 @@ __device__ __forceinline__ void sincos_f32(float a, float& s_out, float& c_out) 
 // four lanes g = lane>>4 of a sample share the NKS*32 slots).
 // `save` (training forward only, else null): this lane's column of the encoding's packed T-layout buffer; slot
 // (k-step ks, element j) is row 32 ks + 8 g + j, i.e. B-operand order (train_fused.hip).
-template <int NKS, bool F16, bool X3, bool SAVE = false, bool LS = (F16 && X3)>
+// MASKED = false: the caller knows the mask is all ones (no mask given) and the multiplies by 1.0f - exact - are left out.
+template <int NKS, bool F16, bool X3, bool SAVE = false, bool LS = (F16 && X3), bool MASKED = true>
 __device__ __forceinline__ void encode(float x0, float x1, float x2, int n_freqs, const float* __restrict__ freqs,
                                        const float* __restrict__ mask, int g, Frag (&out)[NKS], uint32_t* save = nullptr) {
   constexpr int SLOTS = 8 * NKS;
@@ -520,14 +522,19 @@ __device__ __forceinline__ void encode(float x0, float x1, float x2, int n_freqs
       s = __builtin_amdgcn_sinf(fr);
       c = __builtin_amdgcn_cosf(fr);
     }
-    v[2 * i] = ok ? s * mask[3 + band * 6 + coord] : 0.f;
-    v[2 * i + 1] = ok ? c * mask[3 + band * 6 + 3 + coord] : 0.f;
+    if constexpr (MASKED) {
+      v[2 * i] = ok ? s * mask[3 + band * 6 + coord] : 0.f;
+      v[2 * i + 1] = ok ? c * mask[3 + band * 6 + 3 + coord] : 0.f;
+    } else {
+      v[2 * i] = ok ? s : 0.f;
+      v[2 * i + 1] = ok ? c : 0.f;
+    }
   }
   if (g == 2) {
-    v[SLOTS - 2] = x0 * mask[0];
-    v[SLOTS - 1] = x1 * mask[1];
+    v[SLOTS - 2] = MASKED ? x0 * mask[0] : x0;
+    v[SLOTS - 1] = MASKED ? x1 * mask[1] : x1;
   }
-  if (g == 3) v[SLOTS - 2] = x2 * mask[2];
+  if (g == 3) v[SLOTS - 2] = MASKED ? x2 * mask[2] : x2;
 #pragma unroll
   for (int k = 0; k < NKS; ++k) split_store<F16, X3, LS>(&v[8 * k], out[k]);
   if constexpr (SAVE) {
@@ -1155,11 +1162,44 @@ struct NoSave {
     else gemm_layer_two_groups<FSN_TEMPLATE_ARGS TA>(st, net, BIAS, IN, ENC, OUT, heads, ring, g);                       \
   } while (0)
 
+// Optional members of a sample source, used in the x3 / x2 modes only (there an encoding is ~50 VALU instructions per
+// sin / cos pair, and the fragments are the same function of the same inputs wherever they are evaluated):
+//   dir_frag(Frag&)                   the direction's fragment of this lane's lane group, encoded once per ray by the
+//                                     kernel (encode_dir below) instead of once per sample in front of the branch layer
+//   stash_pos(pe) / fetch_pos(pe)     park the position's fragments of layer 0 (written only when the network has a
+//                                     skip layer) and hand them back to a skip layer instead of encoding again
+//   kSkipUnitMask = true              without a position mask (NetDev::pos_masked), layer 0 encodes without the reads
+//                                     of the mask's ones and the multiplies by them
+// A source without them (TileSrc, OccSrc) encodes at every use, mask multiplies included.
+template <class S, class = void>
+struct src_skips_unit_mask : std::false_type {};
+template <class S>
+struct src_skips_unit_mask<S, std::enable_if_t<S::kSkipUnitMask>> : std::true_type {};
+template <class S, class = void>
+struct src_has_dir_frag : std::false_type {};
+template <class S>
+struct src_has_dir_frag<S, std::void_t<decltype(&S::dir_frag)>> : std::true_type {};
+template <class S, class = void>
+struct src_has_pos_stash : std::false_type {};
+template <class S>
+struct src_has_pos_stash<S, std::void_t<decltype(&S::stash_pos), decltype(&S::fetch_pos)>> : std::true_type {};
+
+// The direction fragment mlp_tile builds in front of the branch layer, for lane group g (the fill of a dir_frag table)
+template <int NT, int PREC>
+__device__ __forceinline__ void encode_dir(const NetDev& net, float dx, float dy, float dz, int g, Frag (&de)[kKsDir]) {
+  const float* misc = net.aux + (net.n_layers + 5) * (32 * NT);
+  encode<kKsDir, prec_is_f16(PREC), prec_is_x3(PREC), false, prec_lo_scaled(PREC)>(dx, dy, dz, net.n_freqs_dir, misc + 20,
+                                                                                   net.dir_mask, g, de);
+}
+
 template <int NT, int PREC, bool FULL, int NG, class Src, class SV>
 __device__ __forceinline__ void mlp_tile(WStream& st, const NetDev& net, const Src (&src)[NG], ARing& ring,
                                          float (&sigma)[NG], float (&rgb)[NG][3], const SV& sv) {
   constexpr int NA = NT;  // k-steps of 32 across the hidden width
   constexpr bool F16 = prec_is_f16(PREC), X3 = prec_is_x3(PREC), LS = prec_lo_scaled(PREC);
+  constexpr bool kDirFrag = X3 && src_has_dir_frag<Src>::value, kPosStash = X3 && src_has_pos_stash<Src>::value;
+  constexpr bool kUnitMask = X3 && NG == 1 && !SV::kSave && src_skips_unit_mask<Src>::value;
+  static_assert(!(kDirFrag || kPosStash) || (NG == 1 && !SV::kSave), "encoding reuse: one group, nothing saved");
   // one group: every mode, every saver.  Two groups share each A operand (gemm_layer_two_groups): single-pass modes, nothing saved
   static_assert(NG == 1 || (NG == 2 && !X3 && std::is_same<SV, NoSave>::value), "sample groups per wave");
   const int g = (threadIdx.x >> 4) & 3;
@@ -1177,20 +1217,38 @@ __device__ __forceinline__ void mlp_tile(WStream& st, const NetDev& net, const S
                                                   SAVE ? sv.enc_pos(g) : nullptr);)
   {
     Frag pe[NG][kKsPos];
-    FSN_ENC_POS(SV::kSave, pe);
+    if constexpr (kUnitMask) {
+      if (net.pos_masked) {
+        FSN_ENC_POS(false, pe);
+      } else {
+        float px, py, pz;
+        src[0].pos(px, py, pz);
+        encode<kKsPos, F16, X3, false, LS, false>(px, py, pz, net.n_freqs_pos, misc + 4, net.pos_mask, g, pe[0]);
+      }
+    } else {
+      FSN_ENC_POS(SV::kSave, pe);
+    }
+    if constexpr (kPosStash) {
+      if (net.skip_mask) src[0].stash_pos(pe[0]);  // (wave-uniform; a network without a skip layer does not pay the write)
+    }
     typename SV::Hook hk = sv.hidden(0);
     FSN_GEMM_LAYER((PREC, NT, 0, kKsPos, EPI_RELU_CVT), 0, none, pe, A);
     sv.layer_done(0, hk);
   }
-  // Hidden layer LIDX.  A wide (skip) layer re-encodes the position instead of keeping the 16 registers of `pe` alive
-  // across the layers in between (same function of the same inputs: identical values; fused kernel: 360 -> 256 B of
-  // scratch, +1.5 %).
+  // Hidden layer LIDX.  A wide (skip) layer does not keep the 16 registers of `pe` alive across the layers in between
+  // (fused kernel: 360 -> 256 B of scratch, +1.5 %): it takes the fragments back from the source's stash where there is
+  // one (four ds_read_b128 of what layer 0 encoded), and encodes the position again where there is none (same function
+  // of the same inputs: identical values either way).
 #define FSN_HIDDEN(EPI, IN, OUT, LIDX)                                                              \
   do {                                                                                              \
     typename SV::Hook hk = sv.hidden(LIDX);                                                         \
     if ((net.skip_mask >> ((LIDX)-1)) & 1u) {                                                       \
       Frag pe2[NG][kKsPos];                                                                         \
-      FSN_ENC_POS(false, pe2);                                                                      \
+      if constexpr (kPosStash) {                                                                    \
+        src[0].fetch_pos(pe2[0]);                                                                   \
+      } else {                                                                                      \
+        FSN_ENC_POS(false, pe2);                                                                    \
+      }                                                                                             \
       FSN_GEMM_LAYER((PREC, NT, NA, kKsPos, EPI), (LIDX)*D, IN, pe2, OUT);   \
     } else                                                                                          \
       FSN_GEMM_LAYER((PREC, NT, NA, 0, EPI), (LIDX)*D, IN, none, OUT);       \
@@ -1225,8 +1283,12 @@ __device__ __forceinline__ void mlp_tile(WStream& st, const NetDev& net, const S
       sv.layer_done(L, hk);
     }
     Frag de[NG][kKsDir];
-    FSN_PER_GROUP(q, float dx, dy, dz; src[q].dir(dx, dy, dz);
-                  encode<kKsDir, F16, X3, SV::kSave, LS>(dx, dy, dz, net.n_freqs_dir, misc + 20, net.dir_mask, g, de[q], sv.enc_dir(g)););
+    if constexpr (kDirFrag) {
+      src[0].dir_frag(de[0][0]);
+    } else {
+      FSN_PER_GROUP(q, float dx, dy, dz; src[q].dir(dx, dy, dz);
+                    encode<kKsDir, F16, X3, SV::kSave, LS>(dx, dy, dz, net.n_freqs_dir, misc + 20, net.dir_mask, g, de[q], sv.enc_dir(g)););
+    }
     {
       typename SV::Hook hk = sv.branch();
       FSN_GEMM_LAYER((PREC, NT / 2, NA, kKsDir, EPI_RGB), (L + 1) * D, A, de, B);
@@ -1296,6 +1358,7 @@ __device__ __forceinline__ void load_net(const NetParams& p, const float* __rest
   net.aux = lds;
   net.pos_mask = pm;
   net.dir_mask = dm;
+  net.pos_masked = __builtin_amdgcn_readfirstlane(pos_mask_g != nullptr) != 0;
   net.n_layers = p.n_layers;
   net.skip_mask = p.skip_mask;
   net.n_freqs_pos = p.n_freqs_pos;

@@ -40,25 +40,88 @@ struct RenderLds {
   int32_t two_phase;
   float cam_hw, cam_hh, cam_f;
   float rays[kMaxG * 6];
+  // x3 / x2 modes: the direction encoding of each ray of the group as the branch layer's B operand, one fragment per
+  // lane group g = lane >> 4 (fill_dir_frags; read by RaySrc::dir_frag in the fine pass)
+  alignas(16) Frag dirF[kMaxG][4];
   float edgesC[kMaxGroupCoarse + kMaxG];
   float sigC[kMaxGroupCoarse];
-  float wC[kMaxGroupCoarse];
   float edgesF[kMaxGroupSamples + kMaxG];
   float sigF[kMaxGroupSamples];
   float rgbF[3 * kMaxGroupSamples];
-  float cdf[kMaxG][kMaxRaySamples + 1];
-  float vals[kMaxG][kMaxRaySamples + 1];
+  // `stash` (x3 / x2 modes: every lane's position fragments from layer 0 to the skip layers of one mlp_tile, written
+  // and read by that lane alone) shares storage with the scratch of the per-ray resampling stage.  They are never
+  // live together: wC, cdf and vals are written and read only between the lds_barrier() that follows the coarse pass's
+  // st.pass_end() and the lds_barrier() that ends coarse_stage (weights_ray / sample_pdf_merge_ray); the stash is
+  // touched only inside mlp_tile, i.e. between st.pass_begin() and st.pass_end() of either pass - before the first of
+  // those barriers or after the second - and is dead at the end of every tile.
+  union {
+    struct {
+      float wC[kMaxGroupCoarse];
+      float cdf[kMaxG][kMaxRaySamples + 1];
+      float vals[kMaxG][kMaxRaySamples + 1];
+    };
+    s16x8 stash[2 * kKsPos][kThreads];  // [16-byte word of the lane's kKsPos fragments][thread]: conflict-free b128
+  };
 };
 
 constexpr int kNetLdsBytes = (kAuxCapFloats + 96) * 4;
 constexpr int kRenderLdsBytes = kRingBytes + 2 * kNetLdsBytes + (int)sizeof(RenderLds);
 static_assert(kRenderLdsBytes <= 160 * 1024, "LDS budget");
+static_assert((kRingBytes + 2 * kNetLdsBytes) % 16 == 0 && alignof(RenderLds) == 16, "dirF / stash: 16-byte LDS accesses");
+
+// Encoding reuse of the x3 / x2 modes (mlp_dev.hpp, "Optional members of a sample source"): the direction fragments
+// once per ray, the position fragments once per sample and pass, no multiplies by an absent mask.  0 = as before, for
+// A/B builds (tools/build_variant.sh <name> -DFSN_ENC_POS_STASH=0; profiles/EXPERIMENTS_r4.md section 13: 391.2 ->
+// 387.7 -> 385.1 ms per headline frame for the first two, 380.3 -> 377.1 ms for the third on another device).
+#ifndef FSN_ENC_DIR_TABLE
+#define FSN_ENC_DIR_TABLE 1
+#endif
+#ifndef FSN_ENC_POS_STASH
+#define FSN_ENC_POS_STASH 1
+#endif
+#ifndef FSN_ENC_UNIT_MASK_SKIP
+#define FSN_ENC_UNIT_MASK_SKIP 1
+#endif
 
 // sample source of the fused kernel: interval midpoint on the ray, x = o + d*(t0+t1)/2
 // (rendering.py:61,79), rebuilt from LDS whenever the MLP asks for it
 struct RaySrc {
   const float* ray;  // [ox,oy,oz,dx,dy,dz] in LDS
   const float* e;    // &edges[i] of this sample's interval in LDS
+  const Frag* dfr;   // x3 / x2 modes: RenderLds::dirF[this sample's ray][this lane's g]
+  RenderLds* lds;    // x3 / x2 modes: this lane's stash is column threadIdx.x of lds->stash
+#if FSN_ENC_UNIT_MASK_SKIP
+  static constexpr bool kSkipUnitMask = true;
+#endif
+#if FSN_ENC_DIR_TABLE
+  __device__ __forceinline__ void dir_frag(Frag& f) const { f = *dfr; }  // two ds_read_b128
+#endif
+#if FSN_ENC_POS_STASH
+  // The column index is laundered at each use (as FSN_RELAUNDER does per group): the four word addresses are then
+  // one shift of the thread id plus immediate offsets where they are used, not four registers hoisted out of the
+  // layer loop and held across the whole tile.
+  static __device__ __forceinline__ int stash_column() {
+    int t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    return t;
+  }
+  __device__ __forceinline__ void stash_pos(const Frag (&pe)[kKsPos]) const {
+    const int t = stash_column();
+#pragma unroll
+    for (int k = 0; k < kKsPos; ++k) {
+      FSN_AT(FSN_AT(lds->stash, 2 * k), t) = pe[k].hi;
+      FSN_AT(FSN_AT(lds->stash, 2 * k + 1), t) = pe[k].lo;
+    }
+  }
+  __device__ __forceinline__ void fetch_pos(Frag (&pe)[kKsPos]) const {
+    const int t = stash_column();
+#pragma unroll
+    for (int k = 0; k < kKsPos; ++k) {
+      pe[k].hi = FSN_AT(FSN_AT(lds->stash, 2 * k), t);
+      pe[k].lo = FSN_AT(FSN_AT(lds->stash, 2 * k + 1), t);
+    }
+  }
+#endif
   __device__ __forceinline__ void pos(float& x, float& y, float& z) const {
     const float tm = e[0] + e[1];
     x = ray[0] + ray[3] * tm / 2.0f;
@@ -169,6 +232,23 @@ __global__ __launch_bounds__(kThreads) void k_render_fused(RenderKArgs k) {
       for (int c = 0; c < 3; ++c) { FSN_AT(S_.rays, 6 * tid + c) = o[c]; FSN_AT(S_.rays, 6 * tid + 3 + c) = d[c]; }
     }
   };
+  // x3 / x2 modes: the direction fragments of the group's rays for the fine pass, encoded once per ray - mlp_tile's own
+  // encode call on the ray's direction, frequency mask included, so a fragment is what every sample of the ray would
+  // have computed.  Lane 4 r + g of wave 0 encodes ray r for lane group g.  The barrier in front orders the fill after
+  // load_rays (other lanes wrote the rays); every caller has an lds_barrier() between this and the first fine tile, and
+  // the one that ends fine_stage keeps the next group's fill off a table still being read.
+  auto fill_dir_frags = [&]() __attribute__((always_inline)) {
+    if constexpr (FSN_ENC_DIR_TABLE && prec_is_x3(PREC)) {
+      lds_barrier();
+      if (tid < 4 * GRP_G) {
+        const int r = tid >> 2;
+        const float* ray = FSN_SPAN(S_.rays, 6 * r, 6);
+        Frag de[kKsDir];
+        encode_dir<NT, PREC>(netF, ray[3], ray[4], ray[5], tid & 3, de);
+        FSN_AT(FSN_AT(S_.dirF, r), tid & 3) = de[0];
+      }
+    }
+  };
   // stratified interval edges -> density pass of the coarse net (sigma_fn, rendering.py:58-64) -> per-ray weights,
   // inverse-CDF resampling, sorted union (one wave per ray) -> S_.edgesF
   auto coarse_stage = [&](int64_t r0) __attribute__((always_inline)) {
@@ -187,7 +267,7 @@ __global__ __launch_bounds__(kThreads) void k_render_fused(RenderKArgs k) {
       auto source = [&](int idx) {
         const int idc = min(idx, GRP_G * GRP_S - 1);
         const int g = small_div(idc, GRP_S), i = idc - g * GRP_S;
-        return RaySrc{FSN_SPAN(S_.rays, 6 * g, 6), FSN_SPAN(S_.edgesC, g * (GRP_S + 1) + i, 2)};
+        return RaySrc{FSN_SPAN(S_.rays, 6 * g, 6), FSN_SPAN(S_.edgesC, g * (GRP_S + 1) + i, 2), nullptr, &S_};
       };
       const int idx0 = slot(0);
       RaySrc src[NG];
@@ -223,7 +303,7 @@ __global__ __launch_bounds__(kThreads) void k_render_fused(RenderKArgs k) {
       auto source = [&](int idx) {
         const int idc = min(idx, GRP_G * GRP_SO - 1);
         const int g = small_div(idc, GRP_SO), i = idc - g * GRP_SO;
-        return RaySrc{FSN_SPAN(S_.rays, 6 * g, 6), edges + g * (GRP_SO + 1) + i};
+        return RaySrc{FSN_SPAN(S_.rays, 6 * g, 6), edges + g * (GRP_SO + 1) + i, &FSN_AT(FSN_AT(S_.dirF, g), lane >> 4), &S_};
       };
       const int idx0 = slot(0);
       RaySrc src[NG];
@@ -268,6 +348,7 @@ __global__ __launch_bounds__(kThreads) void k_render_fused(RenderKArgs k) {
       FSN_RELAUNDER();
       const int64_t r0 = grp * (int64_t)__builtin_amdgcn_readfirstlane(GRP_G);  // (G comes from LDS: keep r0 scalar)
       load_rays(r0);
+      fill_dir_frags();
       coarse_stage(r0);
       fine_stage(r0, GRP_HIER ? FSN_SPAN(S_.edgesF, 0, GRP_G * (GRP_SO + 1)) : FSN_SPAN(S_.edgesC, 0, GRP_G * (GRP_SO + 1)), true);
     }
@@ -306,6 +387,7 @@ __global__ __launch_bounds__(kThreads) void k_render_fused(RenderKArgs k) {
       FSN_RELAUNDER();
       const int64_t r0 = grp * (int64_t)__builtin_amdgcn_readfirstlane(GRP_G);  // (G comes from LDS: keep r0 scalar)
       load_rays(r0);
+      fill_dir_frags();
       for (int e = tid; e < GRP_G * (GRP_SO + 1); e += kThreads) {
         const int g = small_div(e, GRP_SO + 1), i = e - g * (GRP_SO + 1);
         FSN_AT(S_.edgesF, e) = __builtin_nontemporal_load(a.edges_out + min(r0 + g, GRP_R - 1) * (GRP_SO + 1) + i);
