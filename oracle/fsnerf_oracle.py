@@ -155,12 +155,15 @@ def split_linear(h: Tensor, W: Tensor, scheme: str) -> Tensor:
       "fp16x3u"  ah.wh + al.wh + ah.wl with UNSCALED fp16 low parts (rounds 1-2; round 4's FSN_PREC_FP16X3U, which runs it
                  on the network scaled by scale_state_dict so that every layer's activations sit at 2^4 .. 2^10)
       "bf16x3"   the same on bfloat16 parts, unscaled
+      "fp16x2"   ah.wh + 2^-11 al'.wh: "fp16x3" with the weights' low parts dropped (FSN_PREC_FP16X2, inference only)
       "fp16+f8"  ah.wh in fp16, the two correction products with every operand in block-scaled e4m3 (VERDICT r2 item 4:
                  a candidate mode, measured in tools/emulate_split.py and DESIGN.md 4.3; NOT built)"""
     fmt = "bf16" if scheme == "bf16x3" else "fp16"
-    K = 2048.0 if scheme == "fp16x3" else 1.0  # ("fp16x3u": unscaled low parts - meant for the SCALED network, below)
+    K = 2048.0 if scheme in ("fp16x3", "fp16x2") else 1.0  # ("fp16x3u": unscaled low parts - meant for the SCALED network, below)
     ah, wh = round_to(h, fmt), round_to(W, fmt)
     ar, wr = h - ah, W - wh
+    if scheme == "fp16x2":
+        return ah @ wh.T + (round_to(ar * K, fmt) @ wh.T) / K
     if scheme == "fp16+f8":
         corr = round_e4m3_blocks(ar) @ round_e4m3_blocks(wh).T + round_e4m3_blocks(ah) @ round_e4m3_blocks(wr).T
         return ah @ wh.T + corr
@@ -177,7 +180,7 @@ def nerf_forward(sd: Dict[str, Tensor], x: Tensor, dirs: Optional[Tensor], *,
     Follows `src/core/models.py:111-143`: relu(layer_i(h)); after layer i in `skip`
     h = cat([h, x_in]); sigma head without activation; connection (no activation);
     cat([feat, dir_enc]); relu(branch); sigmoid(rgb); returns [N,1] or [N,4]=[rgb,sigma].
-    `emulate` = "fp16x3" / "bf16x3" / "fp16+f8": the split-precision schemes of split_linear (float32 x only).
+    `emulate` = "fp16x3" / "bf16x3" / "fp16x2" / "fp16+f8": the split-precision schemes of split_linear (float32 x only).
     `emulate` = "bf16" / "fp16" (BASELINE config 5, "bf16 weights/activations"): the same math with the operand
     rounding of a single-pass 16-bit matrix-core kernel restated on the CPU - every Linear layer's weight and input
     are rounded to that format before the product, products and sums are taken in x's dtype (the kernel accumulates
@@ -188,7 +191,7 @@ def nerf_forward(sd: Dict[str, Tensor], x: Tensor, dirs: Optional[Tensor], *,
     dt = x.dtype
     W = lambda k: sd[k].to(dt)
     q = lambda t: round_to(t, emulate)
-    if emulate in ("fp16x3", "fp16x3u", "bf16x3", "fp16+f8"):  # split-precision schemes (see split_linear)
+    if emulate in ("fp16x3", "fp16x3u", "bf16x3", "fp16x2", "fp16+f8"):  # split-precision schemes (see split_linear)
         lin = lambda h, k: split_linear(h, W(k + ".weight"), emulate) + W(k + ".bias")
     else:
         lin = lambda h, k: q(h) @ q(W(k + ".weight")).T + W(k + ".bias")  # a matrix-core GEMM

@@ -1,4 +1,4 @@
-"""Encoding reuse in the fused render (csrc/render.hip, x3 modes): the direction fragments are encoded once per ray
+"""Encoding reuse in the fused render (csrc/render.hip, x3 / x2 modes): the direction fragments are encoded once per ray
 into an LDS table, and the position fragments of layer 0 are parked in LDS for the skip layers.  Both are the same
 function of the same inputs, evaluated less often, so nothing may move by a bit.
 
@@ -11,7 +11,8 @@ buffer, rays from tensors / from the camera) must agree with one another in ever
 Shapes: the smallest at which the table or the stash can go wrong - a fine tile that spans rays with different
 directions, a last group that is partly empty, ragged tiles that end in padding, networks with no reachable skip
 (the stash is never written), with one and with two skips (read once / twice), the 3-phase stream, masks with zeros
-and non-unit entries, both x3 arithmetics, more ray groups than workgroups (a workgroup refills the table).
+and non-unit entries, both x3 arithmetics and the two-pass fp16x2 (prec_is_x3 holds for it: the same table and stash
+path, its own kernel instantiations and k-loop texts), more ray groups than workgroups (a workgroup refills the table).
 """
 import functools
 
@@ -145,6 +146,9 @@ CASES = {
     "bf16x3-8x256": ("8x256", "bf16x3", 64, 128, (1, 5), False),
     "bf16x3-4x128": ("4x128", "bf16x3", 40, 24, (1, 7), False),
     "bf16x3-masks-two-skips": ("8x128-two-skips", "bf16x3", 64, 128, (2, 3), True),
+    "fp16x2-8x256": ("8x256", "fp16x2", 64, 128, (1, 5), False),
+    "fp16x2-ragged-4x128": ("4x128", "fp16x2", 40, 24, (1, 7), False),
+    "fp16x2-masks-two-skips": ("8x128-two-skips", "fp16x2", 64, 128, (2, 3), True),
     # three groups, every ray its own direction
     "rays9-8x256": ("8x256", "fp16x3", 64, 128, (3, 3), False),
     # 259 groups of four rays: more than the part has compute units, so workgroups take a second group and refill
@@ -187,11 +191,12 @@ def test_second_launch_with_other_directions(dev, models):
         assert_matches_standalone_forward(pf, o, d2, second, S, NI, what=f"second launch, two_phase={two_phase}")
 
 
+@pytest.mark.parametrize("prec", ["fp16x3", "fp16x2"])
 @pytest.mark.parametrize("net,S,NI", [("8x256", 64, 128), ("8x128-two-skips", 40, 24)])
-def test_sampler_only_launch_returns_the_full_launch_edges(dev, models, net, S, NI):
+def test_sampler_only_launch_returns_the_full_launch_edges(dev, models, net, S, NI, prec):
     """ops.sample_fused (two_phase == 2: coarse passes only, stash in use, table never filled) on 5 rays."""
     from fs_nerf_amd import ops
-    _, _, pc, pf = models(net, "fp16x3")
+    _, _, pc, pf = models(net, prec)
     R = 5
     o, d = ops.get_rays(O.pose_from_spherical(4.0311289, 50.0, 123.0), 1, R, FOCAL, dev)
     u, uf = jitter(R, NI, dev)

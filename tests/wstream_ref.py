@@ -36,6 +36,21 @@ def units(n_layers, d_hidden, n_skips):
     return hidden, u
 
 
+def gemms(n_layers, d_hidden, skip):
+    """(output pairs, k-steps) of every GEMM in kernel order: hidden 0 .. n_layers-1, connection, branch.  Layer g > 0
+    reads the encoding as well (kKsPos = 2 more k-steps) when g - 1 is in `skip`."""
+    nt = d_hidden // 32
+    out = [(nt, 2)]
+    out += [(nt, nt + (2 if g - 1 in skip else 0)) for g in range(1, n_layers)]
+    return out + [(nt, nt), (nt // 2, nt + 1)]
+
+
+def kloop_shapes(n_layers, d_hidden, skip):
+    """{(units per pair, offset of the pair's first unit in its 8-unit phase)} of the x3 / x2 stream: the block shapes
+    gemm_layer (mlp_dev.hpp) asks kloop_block for on a 256-wide network, NU = 2 KS and OFF = (tp NU) % 8 per pair tp."""
+    return {(2 * ks, (tp * 2 * ks) % 8) for npo, ks in gemms(n_layers, d_hidden, skip) for tp in range(npo)}
+
+
 def phases(n_layers, d_hidden, n_skips, x3):
     """(nph_density, nph_full): 16-KiB phases of the density-only and of the full pass."""
     upp = 8 if x3 else 16
