@@ -8,6 +8,8 @@ estimator.update_every_n_steps) and evaluated with render_frame + PSNR and SSIM 
                                        [--depth-weight W] [--distortion-weight W] [--cone-angle A] [--near-plane T]
                                        [--mark-invisible] [--min-views K] [--ssim-weight W --patch P --patches B]
                                        [--lpips-weight W --lpips-weights FILE]
+                                       [--entropy-weight W] [--depth-kl-weight W --depth-kl-var V]
+                                       [--depth-smooth-weight W]
 
 --u8-dataset: the teacher's frames become uint8 "photographs" (R.to8b) held in a device-resident RayDataset; the loop
 takes its batches from a RayLoader the way run-nerf.py:236-240 takes them from its DataLoader, and the held-out view
@@ -17,6 +19,15 @@ comes from a FrameLoader (fs_nerf_amd.nerfdata).
 renderer's other outputs through render_rays(full_grad=True) - an MSE between the rendered depth and the teacher's on
 the rays where the teacher hit something (float tables only: the uint8 photographs carry no depth), and the distortion
 loss of the compositor's weights (core.loss.DistortionLoss).
+
+--entropy-weight / --depth-kl-weight / --depth-smooth-weight (all 0 by default: the loop is then the one above): the
+few-shot geometry losses of core.loss, through render_rays(full_grad=True).  --entropy-weight: RayEntropyLoss on
+extras["alphas"], the rays masked by the rendered opacity (InfoNeRF's ray entropy).  --depth-kl-weight, with
+--depth-kl-var V (default 0.01): DepthKLLoss on extras["weights"] against the teacher's depth on the rays where the
+teacher hit something (DS-NeRF's depth term; float tables only, as --depth-weight).  --depth-smooth-weight:
+PatchDepthSmoothnessLoss on the rendered depth of --patches B patches of --patch P x P rays from a random orbit pose no
+photograph was taken from (RegNeRF's depth smoothness); their rays come from get_rays and ride in the same render_rays
+call, behind the ray batch and the SSIM / LPIPS patches.
 
 --cone-angle / --near-plane (both 0 by default): `sampling_kwargs` of render_rays / render_frame / render_path - the
 occupancy march's step grows with distance, dt = max(t * cone_angle, step), and nothing is sampled in front of the near
@@ -52,7 +63,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import fs_nerf_amd  # noqa: E402,F401
 from fs_nerf_amd.core import metrics  # noqa: E402
 from fs_nerf_amd.core import models as M  # noqa: E402
-from fs_nerf_amd.core.loss import DistortionLoss, LPIPSLoss, SSIMLoss, WeightNormRegularizer  # noqa: E402
+from fs_nerf_amd.core.loss import (DepthKLLoss, DistortionLoss, LPIPSLoss, PatchDepthSmoothnessLoss,  # noqa: E402
+                                   RayEntropyLoss, SSIMLoss, WeightNormRegularizer)
 from fs_nerf_amd.core.optim import FusedAdam  # noqa: E402
 from fs_nerf_amd.core.scheduler import ExponentialDecay  # noqa: E402
 from fs_nerf_amd.nerfdata import FrameLoader, PatchLoader, RayDataset, RayLoader  # noqa: E402
@@ -98,6 +110,16 @@ def main():
                     help="opt-in: weight of a depth-supervision term against the teacher's depth (render_rays(full_grad=True))")
     ap.add_argument("--distortion-weight", type=float, default=0.0,
                     help="opt-in: weight of the distortion loss on the compositor's weights (render_rays(full_grad=True))")
+    ap.add_argument("--entropy-weight", type=float, default=0.0,
+                    help="opt-in: weight of the ray entropy of the compositor's alphas, rays masked by opacity "
+                         "(core.loss.RayEntropyLoss; render_rays(full_grad=True))")
+    ap.add_argument("--depth-kl-weight", type=float, default=0.0,
+                    help="opt-in: weight of the depth KL term of the compositor's weights against the teacher's depth "
+                         "(core.loss.DepthKLLoss; render_rays(full_grad=True); float tables only)")
+    ap.add_argument("--depth-kl-var", type=float, default=0.01, help="with --depth-kl-weight: the variance around the teacher's depth")
+    ap.add_argument("--depth-smooth-weight", type=float, default=0.0,
+                    help="opt-in: weight of the depth smoothness of --patches patches of --patch x --patch rays from a random "
+                         "unseen orbit pose (core.loss.PatchDepthSmoothnessLoss; render_rays(full_grad=True))")
     ap.add_argument("--cone-angle", type=float, default=0.0,
                     help="opt-in: the occupancy march's step grows with distance, dt = max(t * cone_angle, step) "
                          "(sampling_kwargs of render_rays / render_frame; nerfacc uses 0.004 for unbounded scenes)")
@@ -134,7 +156,12 @@ def main():
     sampling_kwargs = {k: v for k, v in (("cone_angle", a.cone_angle), ("near_plane", a.near_plane)) if v != 0.0} or None
     if a.depth_weight and a.u8_dataset:
         ap.error("--depth-weight needs the float tables: the uint8 dataset carries no depth")
-    full_grad = a.depth_weight != 0.0 or a.distortion_weight != 0.0
+    if a.depth_kl_weight and a.u8_dataset:
+        ap.error("--depth-kl-weight needs the float tables: the uint8 dataset carries no depth")
+    if a.depth_smooth_weight and a.patch < 2:
+        ap.error("--depth-smooth-weight needs --patch of at least 2")
+    full_grad = any(w != 0.0 for w in (a.depth_weight, a.distortion_weight, a.entropy_weight, a.depth_kl_weight,
+                                       a.depth_smooth_weight))
     dev = torch.device("cuda:0")
     hwf = (a.hw, a.hw, 0.5 * a.hw / math.tan(0.5 * 0.6911112))
     near, far, step = 2.0, 6.0, 2e-2
@@ -196,6 +223,8 @@ def main():
     wnorm = WeightNormRegularizer(model.named_parameters(), reg="l2", reg_ratio=0.5, Td=a.iters)  # run-nerf.py:266-279
     alpha = 1e-5
     distortion = DistortionLoss()
+    ray_entropy, depth_kl, depth_smooth = RayEntropyLoss(), DepthKLLoss(), PatchDepthSmoothnessLoss()
+    pose_gen = torch.Generator().manual_seed(4)  # the unseen poses of --depth-smooth-weight
     scheduler = ExponentialDecay(optimizer, a.iters, 5e-4, r=0.1)
     gen = torch.Generator(device=dev).manual_seed(0)
 
@@ -224,22 +253,40 @@ def main():
                 patch_iterator = iter(patch_loader)
                 patch_o, patch_d, patch_gt = next(patch_iterator)
             rays_o, rays_d = torch.cat([rays_o, patch_o]), torch.cat([rays_d, patch_d])
-        (rgb, _, depth, extras), ray_indices, _ = R.render_rays(rays_o, rays_d, estimator, model, train=True, white_bkgd=True,
-                                                                render_step_size=step, device=dev, full_grad=full_grad,
-                                                                sampling_kwargs=sampling_kwargs)
+        n_seen = rays_o.shape[0]
+        if a.depth_smooth_weight:  # B windows of P x P rays of one random pose between the training views, behind the rest
+            phi, theta = 360.0 * float(torch.rand((), generator=pose_gen)), 40.0 + 20.0 * float(torch.rand((), generator=pose_gen))
+            o, d = U.get_rays(orbit_pose(phi, theta), hwf, dev)
+            corner = torch.randint(0, a.hw - a.patch + 1, (a.patches, 2), generator=pose_gen)
+            rows = (corner[:, :1] + torch.arange(a.patch))[:, :, None].expand(-1, -1, a.patch).to(dev)
+            cols = (corner[:, 1:] + torch.arange(a.patch))[:, None, :].expand(-1, a.patch, -1).to(dev)
+            rays_o = torch.cat([rays_o, o[rows, cols].reshape(-1, 3)])
+            rays_d = torch.cat([rays_d, d[rows, cols].reshape(-1, 3)])
+        (rgb, opacity, depth, extras), ray_indices, _ = R.render_rays(rays_o, rays_d, estimator, model, train=True,
+                                                                      white_bkgd=True, render_step_size=step, device=dev,
+                                                                      full_grad=full_grad, sampling_kwargs=sampling_kwargs)
         loss = torch.nn.functional.mse_loss(rgb[:n_batch], rgb_gt)
         if a.ssim_weight:
-            loss = loss + a.ssim_weight * ssim_loss(rgb[n_batch:].view(-1, a.patch, a.patch, 3),
+            loss = loss + a.ssim_weight * ssim_loss(rgb[n_batch:n_seen].view(-1, a.patch, a.patch, 3),
                                                     patch_gt.view(-1, a.patch, a.patch, 3))
         if a.lpips_weight:
-            loss = loss + a.lpips_weight * lpips_loss(rgb[n_batch:].view(-1, a.patch, a.patch, 3),
+            loss = loss + a.lpips_weight * lpips_loss(rgb[n_batch:n_seen].view(-1, a.patch, a.patch, 3),
                                                       patch_gt.view(-1, a.patch, a.patch, 3))
         if a.depth_weight and depth.requires_grad:  # (an all-background batch renders no samples: nothing to supervise)
             hit = (gd[idx] > near).float()  # render_frame clamps depth to [near, far]: `near` = the teacher saw background
-            loss = loss + a.depth_weight * (hit * (depth - gd[idx]) ** 2).sum() / hit.sum().clamp(min=1.0)
+            loss = loss + a.depth_weight * (hit * (depth[:n_batch] - gd[idx]) ** 2).sum() / hit.sum().clamp(min=1.0)
         if a.distortion_weight and extras is not None and extras["weights"].requires_grad:
             loss = loss + a.distortion_weight * distortion(extras["weights"], extras["t_starts"], extras["t_ends"],
                                                            ray_indices, rays_o.shape[0])
+        if a.entropy_weight and extras is not None and extras["alphas"].requires_grad:
+            loss = loss + a.entropy_weight * ray_entropy(extras["alphas"], ray_indices, rays_o.shape[0], opacity=opacity)
+        if a.depth_kl_weight and extras is not None and extras["weights"].requires_grad:
+            target = torch.zeros(rays_o.shape[0], device=dev)  # 0: no depth known (background, the patches' rays)
+            target[:n_batch] = torch.where(gd[idx] > near, gd[idx], torch.zeros_like(gd[idx])).reshape(-1)
+            loss = loss + a.depth_kl_weight * depth_kl(extras["weights"], extras["t_starts"], extras["t_ends"], ray_indices,
+                                                       rays_o.shape[0], target, a.depth_kl_var)
+        if a.depth_smooth_weight and depth.requires_grad:
+            loss = loss + a.depth_smooth_weight * depth_smooth(depth[n_seen:].view(-1, a.patch, a.patch))
         if wnorm.active(k):
             loss = loss + alpha * wnorm()
         loss.backward()

@@ -140,6 +140,13 @@ SIGNATURES = {
                                            _vp, _vp, _vp]),
     "fsn_distortion_fwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "fsn_distortion_bwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    # few-shot geometry losses (csrc/ray_losses.hip)
+    "fsn_ray_entropy_fwd": (_i, [_vp, _vp, _i64, _i64, _vp, _f, _f, _vp, _vp]),
+    "fsn_ray_entropy_bwd": (_i, [_vp, _vp, _i64, _i64, _vp, _f, _f, _vp, _vp, _vp]),
+    "fsn_depth_kl_fwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _f, _vp, _vp]),
+    "fsn_depth_kl_bwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _f, _vp, _vp, _vp]),
+    "fsn_patch_tv_fwd": (_i, [_vp, _i64, _i, _i, _vp, _vp]),
+    "fsn_patch_tv_bwd": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp]),
     # span arguments of the packed primitives: ray_indices, packed_info, N, R, dense_S
     "fsn_pack_info": (_i, [_vp, _i64, _i64, _vp, _vp]),
     "fsn_packed_scan_fwd": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _i, _vp, _vp]),

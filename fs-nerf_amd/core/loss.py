@@ -3,8 +3,11 @@ segmented reduction on the GPU instead of a Python loop with one kernel launch p
 compositor's weights (this package's own, the first consumer of `full_grad`); and the weight-norm
 "frequency" regulariser of the training loop (row f1, src/run-nerf.py:266-279) as one reduction over the flat
 parameter arena; and the structural (D-SSIM) and perceptual (LPIPS-VGG) terms on rendered patches (this package's own:
-the evaluation metrics of core/metrics.py with a backward)."""
+the evaluation metrics of core/metrics.py with a backward); and the few-shot geometry losses on the renderer's other
+outputs (this package's own definitions of InfoNeRF's ray entropy, DS-NeRF's depth KL term and RegNeRF's patch depth
+smoothness: csrc/ray_losses.hip)."""
 import ctypes as C
+import math
 from typing import Optional
 
 import torch
@@ -42,6 +45,69 @@ class DistortionLoss:
 
     def __call__(self, weights: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor, n_rays: int) -> Tensor:
         return ops.distortion(weights, t_starts, t_ends, ray_indices, n_rays).mean()
+
+
+class RayEntropyLoss:
+    """Entropy of each ray's termination distribution (InfoNeRF's ray entropy; this package's OWN definition): with
+    u_i = max(v_i, 0), s = sum_i u_i and p_i = u_i / (s + eps) over the ray's samples,
+        H_r = -scale c_r sum_i p_i log(p_i + eps),   scale = 1 / ln 2 (`log2`, InfoNeRF's) or 1;
+    the call returns the mean over the `n_rays` rays.  `values` [N]: extras["alphas"] of
+    render_rays(..., full_grad=True), as InfoNeRF takes them, or extras["weights"]; negative entries (the raw-sigma
+    network emits them) count as 0 and receive no gradient.  `opacity` [n_rays] (the renderer's, detached here) masks
+    the rays: c_r = (opacity_r > threshold), InfoNeRF's rule - a ray that hits nothing has no distribution to sharpen;
+    a masked ray, like a ray without samples, contributes 0 and gets a gradient of exactly 0.  Without `opacity` every
+    ray counts.  One segmented reduction on the GPU (ops.ray_entropy), differentiable w.r.t. `values` only.
+    InfoNeRF's second term, the KL divergence between the distributions of neighbouring rays, is not built: packed
+    rays have differing sample counts, so their samples do not pair up."""
+
+    def __init__(self, threshold: float = 0.1, eps: float = 1e-10, log2: bool = True):
+        self.threshold, self.eps, self.log2 = float(threshold), float(eps), bool(log2)
+
+    def __call__(self, values: Tensor, ray_indices: Tensor, n_rays: int, opacity: Optional[Tensor] = None) -> Tensor:
+        c = None if opacity is None else (opacity.detach().reshape(-1) > self.threshold)
+        return ops.ray_entropy(values, ray_indices, n_rays, ray_weight=c, eps=self.eps, log2=self.log2).mean()
+
+
+class DepthKLLoss:
+    """Depth supervision of the termination distribution (DS-NeRF's "sigma loss"; this package's OWN definition): with
+    m_i = (t_starts_i + t_ends_i)/2 and dt_i = t_ends_i - t_starts_i, per supervised ray
+        L_r = sum_i -log(max(w_i, 0) + eps) exp(-(m_i - depth_r)^2 / (2 var_r)) dt_i,
+    the cross entropy between a Gaussian around the known depth and the compositor's weights; the call returns the sum
+    over the rays divided by max(number of supervised rays, 1), counted on the device (no host sync).  `depth`
+    [n_rays] and `var` [n_rays] (or one float) are per ray; a ray is supervised when both are finite and > 0 - put 0
+    or NaN where no depth is known: such a ray contributes 0 and gets a gradient of exactly 0.  `weights` are
+    extras["weights"] of render_rays(..., full_grad=True), whose extras hold "t_starts" and "t_ends" as well.  One
+    segmented reduction on the GPU (ops.depth_kl), differentiable w.r.t. `weights` only."""
+
+    def __init__(self, eps: float = 1e-5):
+        self.eps = float(eps)
+
+    def __call__(self, weights: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor, n_rays: int, depth: Tensor,
+                 var) -> Tensor:
+        per_ray = ops.depth_kl(weights, t_starts, t_ends, ray_indices, n_rays, depth, var, eps=self.eps)
+        d = depth.detach().reshape(-1)
+        ok = torch.isfinite(d) & (d > 0)
+        if isinstance(var, Tensor):
+            v = var.detach().reshape(-1)
+            ok = ok & torch.isfinite(v) & (v > 0)
+        elif not (math.isfinite(var) and var > 0):
+            ok = torch.zeros_like(ok)
+        return per_ray.sum() / ok.sum().clamp(min=1).to(per_ray.dtype)
+
+
+class PatchDepthSmoothnessLoss:
+    """Smoothness of rendered depth patches (RegNeRF's depth smoothness, compute_tv_norm with the l2 loss; this
+    package's OWN definition): for `depth` [B, P, Q], rendered from poses no photograph was taken from,
+        S_b = sum_{i < P-1, j < Q-1} (d[i,j] - d[i,j+1])^2 + (d[i,j] - d[i+1,j])^2,
+    and the call returns mean_b S_b / ((P-1)(Q-1)) - 0 when P or Q is 1.  One launch forward, one backward
+    (ops.patch_depth_smoothness); `depth` must carry a gradient itself: render_rays(..., full_grad=True).  The poses
+    are the caller's: examples/train_synthetic.py draws them from its orbit; a sampler class for unseen poses is not
+    built."""
+
+    def __call__(self, depth: Tensor) -> Tensor:
+        per_patch = ops.patch_depth_smoothness(depth)
+        B, P, Q = depth.shape
+        return per_patch.sum() / float(max(B, 1) * max((P - 1) * (Q - 1), 1))
 
 
 class _SSIMLossFn(torch.autograd.Function):

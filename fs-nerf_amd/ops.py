@@ -977,6 +977,113 @@ def distortion(weights: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indices: T
     return _DistortionFn.apply(w, t0, t1, ri, int(n_rays))
 
 
+# ------------------------------------------------------------------ few-shot geometry losses (csrc/ray_losses.hip)
+class _RayEntropyFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, v, ri, n_rays, c, eps, scale):
+        out = torch.empty(n_rays, device=v.device, dtype=torch.float32)
+        _launch("fsn_ray_entropy_fwd", v.device, _p(v), _p(ri), v.numel(), n_rays, _p(c), eps, scale, _p(out))
+        ctx.save_for_backward(v, ri, c)
+        ctx.n_rays, ctx.eps, ctx.scale = n_rays, eps, scale
+        return out.reshape(n_rays, 1)
+
+    @staticmethod
+    def backward(ctx, g):
+        v, ri, c = ctx.saved_tensors
+        g = _f32(g, "grad").reshape(-1)
+        d_v = torch.empty_like(v)
+        _launch("fsn_ray_entropy_bwd", v.device, _p(v), _p(ri), v.numel(), ctx.n_rays, _p(c), ctx.eps, ctx.scale, _p(g),
+                _p(d_v))
+        return d_v, None, None, None, None, None
+
+
+def ray_entropy(values: Tensor, ray_indices: Tensor, n_rays: int, ray_weight: Optional[Tensor] = None, eps: float = 1e-10,
+                log2: bool = True) -> Tensor:
+    """Per-ray entropy of the termination distribution -> [n_rays, 1] (fsn_ray_entropy_fwd / _bwd;
+    core.loss.RayEntropyLoss has the definition): p = max(values, 0) / (sum + eps) over the ray, -sum p log(p + eps), in
+    bits (`log2`) or nats.  `values`: the compositor's alphas (InfoNeRF) or weights.  `ray_weight` [n_rays] scales each
+    ray and is not differentiated; a ray whose weight is 0 is skipped (value 0, gradient exactly 0), as is a ray without
+    samples.  Differentiable w.r.t. `values` only."""
+    if ray_indices.numel() != values.numel():
+        raise ValueError("ray_entropy: values and ray_indices disagree in length")
+    if ray_weight is not None and ray_weight.numel() != int(n_rays):
+        raise ValueError(f"ray_entropy: ray_weight has {ray_weight.numel()} entries for {int(n_rays)} rays")
+    v = _f32(values, "values").reshape(-1)
+    ri = _i64(ray_indices, "ray_indices").reshape(-1)
+    c = None if ray_weight is None else _f32(ray_weight.detach(), "ray_weight").reshape(-1)
+    return _RayEntropyFn.apply(v, ri, int(n_rays), c, float(eps), 1.0 / math.log(2.0) if log2 else 1.0)
+
+
+class _DepthKLFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, w, t0, t1, ri, n_rays, depth, var, eps):
+        out = torch.empty(n_rays, device=w.device, dtype=torch.float32)
+        _launch("fsn_depth_kl_fwd", w.device, _p(w), _p(t0), _p(t1), _p(ri), w.numel(), n_rays, _p(depth), _p(var), eps,
+                _p(out))
+        ctx.save_for_backward(w, t0, t1, ri, depth, var)
+        ctx.n_rays, ctx.eps = n_rays, eps
+        return out.reshape(n_rays, 1)
+
+    @staticmethod
+    def backward(ctx, g):
+        w, t0, t1, ri, depth, var = ctx.saved_tensors
+        g = _f32(g, "grad").reshape(-1)
+        d_w = torch.empty_like(w)
+        _launch("fsn_depth_kl_bwd", w.device, _p(w), _p(t0), _p(t1), _p(ri), w.numel(), ctx.n_rays, _p(depth), _p(var),
+                ctx.eps, _p(g), _p(d_w))
+        return d_w, None, None, None, None, None, None, None
+
+
+def depth_kl(weights: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor, n_rays: int, depth: Tensor, var,
+             eps: float = 1e-5) -> Tensor:
+    """Per-ray depth KL term on the compositor's weights -> [n_rays, 1] (fsn_depth_kl_fwd / _bwd; core.loss.DepthKLLoss
+    has the definition): sum_i -log(max(w_i, 0) + eps) exp(-(m_i - depth_r)^2 / (2 var_r)) dt_i.  `depth` [n_rays] and
+    `var` [n_rays] (or a Python float, expanded on the device) are per ray; a ray whose depth or variance is not finite
+    and positive is unsupervised: value 0, gradient exactly 0.  Differentiable w.r.t. `weights` only."""
+    n_rays = int(n_rays)
+    if not (t_starts.numel() == t_ends.numel() == ray_indices.numel() == weights.numel()):
+        raise ValueError("depth_kl: weights, t_starts, t_ends and ray_indices disagree in length")
+    if depth.numel() != n_rays or (isinstance(var, Tensor) and var.numel() != n_rays):
+        raise ValueError(f"depth_kl: depth and var must have one entry for each of the {n_rays} rays")
+    w = _f32(weights, "weights").reshape(-1)
+    t0, t1 = _f32(t_starts.detach(), "t_starts").reshape(-1), _f32(t_ends.detach(), "t_ends").reshape(-1)
+    ri = _i64(ray_indices, "ray_indices").reshape(-1)
+    d = _f32(depth.detach(), "depth").reshape(-1)
+    if isinstance(var, Tensor):
+        v = _f32(var.detach(), "var").reshape(-1)
+    else:
+        v = torch.full((n_rays,), float(var), device=w.device, dtype=torch.float32)
+    return _DepthKLFn.apply(w, t0, t1, ri, n_rays, d, v, float(eps))
+
+
+class _PatchTVFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, d):
+        B, P, Q = d.shape
+        out = torch.empty(B, device=d.device, dtype=torch.float32)
+        _launch("fsn_patch_tv_fwd", d.device, _p(d), B, P, Q, _p(out))
+        ctx.save_for_backward(d)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        d, = ctx.saved_tensors
+        B, P, Q = d.shape
+        g = _f32(g, "grad").reshape(-1)
+        d_d = torch.empty_like(d)
+        _launch("fsn_patch_tv_bwd", d.device, _p(d), B, P, Q, _p(g), _p(d_d))
+        return d_d
+
+
+def patch_depth_smoothness(depth: Tensor) -> Tensor:
+    """Per-patch l2 total variation of rendered depth patches [B, P, Q] -> [B] (fsn_patch_tv_fwd / _bwd;
+    core.loss.PatchDepthSmoothnessLoss has the definition): the sum over the anchors i < P-1, j < Q-1 of
+    (d[i,j] - d[i,j+1])^2 + (d[i,j] - d[i+1,j])^2; 0 when P or Q is 1.  Any strides (a copy is made when needed)."""
+    if depth.dim() != 3 or depth.shape[1] < 1 or depth.shape[2] < 1:
+        raise ValueError(f"patch_depth_smoothness: expected depth of shape [B, P, Q] with P, Q >= 1, got {tuple(depth.shape)}")
+    return _PatchTVFn.apply(_f32(depth, "depth"))
+
+
 # ------------------------------------------------------------------ packed volume-rendering primitives (csrc/packed_scan.hip)
 class RaySpans:
     """Where each ray's samples are among N flat samples - the "span" arguments of include/fsnerf_hip.h: exactly one of

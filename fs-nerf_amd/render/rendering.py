@@ -137,7 +137,8 @@ def rendering(t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor, n_rays: int
     respect to the rgbs / sigmas returned by `rgb_sigma_fn`: through colors and opacities by default (the lean
     backward of the timed training step; depth and the extras are detached), through EVERY output - depths and
     extras["weights" | "alphas" | "trans"] as well, as nerfacc's are - with `full_grad=True` (depth supervision,
-    distortion / entropy losses on the weights, opacity priors).  No gradient goes to t_starts / t_ends.
+    distortion / entropy / depth KL losses on the weights and alphas - core.loss.DistortionLoss, RayEntropyLoss,
+    DepthKLLoss -, opacity priors).  No gradient goes to t_starts / t_ends.
     Exactly one of `rgb_sigma_fn` and `rgb_alpha_fn` is given (else ValueError).  `rgb_alpha_fn` -> (rgbs [N,3],
     alphas [N]) takes the alpha route (an opacity-valued field): render_weight_from_alpha, then accumulate_along_rays
     for colours, opacity and depth, depth / clamp(opacity, eps), the background; extras hold "weights", "trans",

@@ -527,6 +527,43 @@ int fsn_distortion_fwd(const float* weights, const float* t_starts, const float*
 int fsn_distortion_bwd(const float* weights, const float* t_starts, const float* t_ends, const int64_t* ray_indices,
                        int64_t N, int64_t n_rays, const float* d_out, float* d_weights, fsn_stream_t stream);
 
+/* Few-shot geometry losses (csrc/ray_losses.hip; this package's own definitions of InfoNeRF's ray entropy, DS-NeRF's
+ * depth KL term and RegNeRF's patch depth smoothness - DESIGN.md 6.1).  The two ray losses take sorted ray_indices
+ * int64 [N] and write out [n_rays]; a ray without samples gives 0 (N == 0: out, when given, is zeroed); N == 0 or
+ * n_rays == 0 returns FSN_OK without a launch; null pointers and negative sizes are FSN_E_INVALID.  One wave per ray, no
+ * LDS, no atomics, every sum in a fixed order: deterministic.  Each backward zeroes its output first.
+ * fsn_ray_entropy_fwd: with u_i = max(values_i, 0), s = sum u_i, p_i = u_i / (s + eps):
+ *     out[r] = -scale c_r sum_i p_i log(p_i + eps)
+ *   (scale 1: nats, 1/ln 2: bits).  ray_weight [n_rays] = c_r is optional (NULL: 1) and not differentiated; a ray with
+ *   c_r == 0 is skipped (value 0, gradient exactly 0). */
+int fsn_ray_entropy_fwd(const float* values, const int64_t* ray_indices, int64_t N, int64_t n_rays,
+                        const float* ray_weight, float eps, float scale, float* out, fsn_stream_t stream);
+/* backward of fsn_ray_entropy_fwd w.r.t. values: with f'(p) = -log(p + eps) - p / (p + eps),
+ *   d_values[k] = d_out[r] scale c_r ( f'(p_k) - sum_i p_i f'(p_i) ) / (s + eps)  where values_k >= 0,  0 below
+ * (torch.clamp(min=0)'s rule).  d_out [n_rays]. */
+int fsn_ray_entropy_bwd(const float* values, const int64_t* ray_indices, int64_t N, int64_t n_rays,
+                        const float* ray_weight, float eps, float scale, const float* d_out, float* d_values,
+                        fsn_stream_t stream);
+/* fsn_depth_kl_fwd: with m = (t_starts + t_ends)/2, dt = t_ends - t_starts and per-ray depth, var [n_rays]:
+ *     out[r] = sum_i -log(max(w_i, 0) + eps) exp(-(m_i - depth_r)^2 / (2 var_r)) dt_i
+ *   for a supervised ray (depth_r and var_r both finite and > 0); any other ray gives 0 and gradient exactly 0. */
+int fsn_depth_kl_fwd(const float* weights, const float* t_starts, const float* t_ends, const int64_t* ray_indices,
+                     int64_t N, int64_t n_rays, const float* depth, const float* var, float eps, float* out,
+                     fsn_stream_t stream);
+/* backward of fsn_depth_kl_fwd w.r.t. weights:
+ *   d_weights[k] = -d_out[r] exp(-(m_k - depth_r)^2 / (2 var_r)) dt_k / (w_k + eps)  where w_k >= 0,  0 below. */
+int fsn_depth_kl_bwd(const float* weights, const float* t_starts, const float* t_ends, const int64_t* ray_indices,
+                     int64_t N, int64_t n_rays, const float* depth, const float* var, float eps, const float* d_out,
+                     float* d_weights, fsn_stream_t stream);
+/* fsn_patch_tv_fwd: depth [B, P, Q] contiguous -> out [B],
+ *     out[b] = sum_{i < P-1, j < Q-1} (d[i,j] - d[i,j+1])^2 + (d[i,j] - d[i+1,j])^2       (0 when P or Q is 1).
+ *   One wave per patch, the lanes striding over the anchors (i, j).  B == 0 returns FSN_OK; P, Q >= 1. */
+int fsn_patch_tv_fwd(const float* depth, int64_t B, int P, int Q, float* out, fsn_stream_t stream);
+/* backward of fsn_patch_tv_fwd: d_depth [B, P, Q], one thread per pixel, which sums the up-to-four differences it
+ * appears in (as the anchor, as an anchor's right and lower neighbour) times d_out[b].  No atomics. */
+int fsn_patch_tv_bwd(const float* depth, int64_t B, int P, int Q, const float* d_out, float* d_depth,
+                     fsn_stream_t stream);
+
 /* Packed volume-rendering primitives (csrc/packed_scan.hip; render/volrend.py is their Python surface, named after
  * nerfacc's volrend / scan / pack modules - this package's own definitions of nerfacc's documented semantics).
  * Every entry point below finds the samples [beg, beg + S) of ray r in ONE of three ways ("span" arguments):
