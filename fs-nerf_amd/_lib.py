@@ -73,7 +73,8 @@ SIGNATURES = {
     "fsn_version": (_i, []),
     "fsn_last_error": (C.c_char_p, []),
     "fsn_device_cus": (_i, []),
-    "fsn_debug_report": (_i, [_vp]),
+    "fsn_debug_report": (_i, [C.c_char_p, _vp]),
+    "fsn_debug_units": (C.c_char_p, []),
     "fsn_debug_selftest": (_i, []),
     "fsn_get_rays": (_i, [_vp, _i, _i, _d, _i, _i, _vp, _vp, _vp]),
     "fsn_to_ndc": (_i, [_vp, _vp, _i64, _i, _i, _d, _d, _vp, _vp, _vp]),
@@ -83,7 +84,6 @@ SIGNATURES = {
     "fsn_ray_patch_batch": (_i, [_vp, _i64, _vp, _i, _i, _i, _d, _i, _d, _i, _i, C.c_uint64, _i64, _vp, _i64, _i64, _i, _i,
                                  _vp, _vp, _vp, _vp, _vp]),
     "fsn_ray_perm_host": (_i, [_i64, C.c_uint64, _i64, _i64, _i64, _vp]),
-    "fsn_debug_report_raydata": (_i, [_vp]),
     "fsn_posenc_fwd": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp]),
     "fsn_stratified_edges": (_i, [_f, _f, _i, _i64, _vp, _i, _vp, _vp]),
     "fsn_edges_to_packed": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp]),
@@ -166,10 +166,8 @@ SIGNATURES = {
     "fsn_ssim": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp, _vp]),
     "fsn_psnr_workspace_doubles": (_i64, [_i64, _i, _i, _i]),
     "fsn_psnr": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "fsn_debug_report_metrics": (_i, [_vp]),
     "fsn_ssim_grad_workspace_doubles": (_i64, [_i64, _i, _i, _i]),
     "fsn_ssim_grad": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "fsn_debug_report_ssim_grad": (_i, [_vp]),
     "fsn_lpips_pack_bytes": (_i64, []),
     "fsn_lpips_pack": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fsn_lpips_workspace_floats": (_i64, [_i, _i]),
@@ -179,7 +177,6 @@ SIGNATURES = {
     "fsn_lpips_train_workspace_floats": (_i64, [_i64, _i, _i, _i, _i]),
     "fsn_lpips_vgg_fwd_save": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "fsn_lpips_vgg_bwd": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "fsn_debug_report_lpips": (_i, [_vp]),
 }
 
 _lib = None

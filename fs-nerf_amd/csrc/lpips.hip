@@ -34,8 +34,8 @@
 
 namespace fsn {
 
-// debug build: the LDS indices of k_lpips_conv are range-checked (common.hpp), read by fsn_debug_report_lpips
-FSN_DEBUG_DEFINE_RECORD(g_dbg_lpips)
+// debug build: the LDS indices of k_lpips_conv are range-checked (common.hpp), read by fsn_debug_report("lpips")
+FSN_DEBUG_DEFINE_RECORD(lpips)
 #define FSN_DEBUG_RECORD g_dbg_lpips
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -1019,17 +1019,4 @@ extern "C" int fsn_lpips_vgg_bwd(const void* packed, const void* packed_grad, in
     FSN_LAUNCH_CHECK("k_lpips_first_bwd");
   }
   return FSN_OK;
-}
-
-extern "C" int fsn_debug_report_lpips(uint32_t* out_host) {
-  FSN_REQUIRE(out_host, FSN_E_INVALID, "fsn_debug_report_lpips: null pointer");
-#ifdef FSN_DEBUG
-  FSN_HIP(hipDeviceSynchronize());
-  unsigned zero[4] = {0u, 0u, 0u, 0u};
-  FSN_HIP(hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_dbg_lpips), sizeof(unsigned) * 4));
-  FSN_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_dbg_lpips), zero, sizeof(zero)));
-  return FSN_OK;
-#else
-  FSN_REQUIRE(false, FSN_E_UNSUPPORTED, "fsn_debug_report_lpips: not a debug build (make -C fs-nerf_amd/csrc debug)");
-#endif
 }

@@ -22,8 +22,8 @@
 #include <cmath>
 
 namespace fsn {
-// debug build: the LDS indices of k_ssim_tile are range-checked (common.hpp), read by fsn_debug_report_metrics
-FSN_DEBUG_DEFINE_RECORD(g_dbg_metrics)
+// debug build: the LDS indices of k_ssim_tile are range-checked (common.hpp), read by fsn_debug_report("metrics")
+FSN_DEBUG_DEFINE_RECORD(metrics)
 }  // namespace fsn
 #define FSN_DEBUG_RECORD g_dbg_metrics
 #include "ssim_dev.hpp"  // tile geometry, window parameters and the moments of steps 1-3, shared with ssim_grad.hip
@@ -217,17 +217,4 @@ extern "C" int fsn_psnr(const float* x, const float* y, int64_t N, int C, int H,
   k_psnr_finish<<<1, kSsimThreads, 0, s>>>(workspace, N, chunks, per_image, out);
   FSN_LAUNCH_CHECK("k_psnr_finish");
   return FSN_OK;
-}
-
-extern "C" int fsn_debug_report_metrics(uint32_t* out_host) {
-  FSN_REQUIRE(out_host, FSN_E_INVALID, "fsn_debug_report_metrics: null pointer");
-#ifdef FSN_DEBUG
-  FSN_HIP(hipDeviceSynchronize());
-  unsigned zero[4] = {0u, 0u, 0u, 0u};
-  FSN_HIP(hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_dbg_metrics), sizeof(unsigned) * 4));
-  FSN_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_dbg_metrics), zero, sizeof(zero)));
-  return FSN_OK;
-#else
-  FSN_REQUIRE(false, FSN_E_UNSUPPORTED, "fsn_debug_report_metrics: not a debug build (make -C fs-nerf_amd/csrc debug)");
-#endif
 }

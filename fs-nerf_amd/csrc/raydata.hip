@@ -18,8 +18,8 @@
 namespace fsn {
 
 // debug build: an explicit index outside [0, N) is recorded (count, source line, index, N - both truncated to 32 bits),
-// read by fsn_debug_report_raydata.  In every build such a thread leaves its output rows untouched.
-FSN_DEBUG_DEFINE_RECORD(g_dbg_raydata)
+// read by fsn_debug_report("raydata").  In every build such a thread leaves its output rows untouched.
+FSN_DEBUG_DEFINE_RECORD(raydata)
 
 struct RayBatchArgs {
   const float* poses;      // [n, 12]
@@ -47,11 +47,7 @@ __global__ void __launch_bounds__(256) k_ray_batch(RayBatchArgs a) {
     idx = a.indices[i];
     if (idx < 0 || idx >= a.n_rays) {  // never reaches memory
 #ifdef FSN_DEBUG
-      if (atomicAdd(g_dbg_raydata, 1u) == 0u) {
-        g_dbg_raydata[1] = (unsigned)__LINE__;
-        g_dbg_raydata[2] = (unsigned)idx;
-        g_dbg_raydata[3] = (unsigned)a.n_rays;
-      }
+      fsn_dbg_note(g_dbg_raydata, __LINE__, idx, a.n_rays);
 #endif
       return;
     }
@@ -113,11 +109,7 @@ __global__ void __launch_bounds__(256) k_ray_patch_batch(RayPatchArgs pa) {
     anchor = a.indices[b];
     if (anchor < 0 || anchor >= pa.n_anchors) {  // never reaches memory
 #ifdef FSN_DEBUG
-      if (atomicAdd(g_dbg_raydata, 1u) == 0u) {
-        g_dbg_raydata[1] = (unsigned)__LINE__;
-        g_dbg_raydata[2] = (unsigned)anchor;
-        g_dbg_raydata[3] = (unsigned)pa.n_anchors;
-      }
+      fsn_dbg_note(g_dbg_raydata, __LINE__, anchor, pa.n_anchors);
 #endif
       return;
     }
@@ -298,17 +290,4 @@ extern "C" int fsn_ray_perm_host(int64_t N, uint64_t seed, int64_t epoch, int64_
   const RayPerm p = ray_perm_make((uint64_t)N, seed, (uint64_t)epoch);
   for (int64_t i = 0; i < count; ++i) out_host[i] = (int64_t)ray_perm_at(p, (uint64_t)(start + i));
   return FSN_OK;
-}
-
-extern "C" int fsn_debug_report_raydata(uint32_t* out_host) {
-  FSN_REQUIRE(out_host, FSN_E_INVALID, "fsn_debug_report_raydata: null pointer");
-#ifdef FSN_DEBUG
-  FSN_HIP(hipDeviceSynchronize());
-  unsigned zero[4] = {0u, 0u, 0u, 0u};
-  FSN_HIP(hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_dbg_raydata), sizeof(unsigned) * 4));
-  FSN_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_dbg_raydata), zero, sizeof(zero)));
-  return FSN_OK;
-#else
-  FSN_REQUIRE(false, FSN_E_UNSUPPORTED, "fsn_debug_report_raydata: not a debug build (make -C fs-nerf_amd/csrc debug)");
-#endif
 }

@@ -15,7 +15,7 @@
 
 namespace fsn {
 
-FSN_DEBUG_DEFINE_RECORD(g_dbg_render)
+FSN_DEBUG_DEFINE_RECORD(render)
 #define FSN_DEBUG_RECORD g_dbg_render
 
 constexpr int kMaxGroupSamples = 768;  // G * (S + n_imp) <= this
@@ -579,8 +579,6 @@ extern "C" int fsn_bench_bare_stream(const fsn_mlp_desc* desc, int prec, const v
   return launched == FSN_OK ? cus : launched;
 }
 
-namespace fsn { int debug_report_occ(unsigned* host4); }  // render_occ.hip
-
 #ifdef FSN_DEBUG
 namespace fsn {
 // negative control of the debug build's checks: one deliberate out-of-range index and one out-of-range span
@@ -604,18 +602,5 @@ extern "C" int fsn_debug_selftest(void) {
   return FSN_OK;
 #else
   FSN_REQUIRE(false, FSN_E_UNSUPPORTED, "fsn_debug_selftest: not a debug build");
-#endif
-}
-
-extern "C" int fsn_debug_report(uint32_t* out_host) {
-  FSN_REQUIRE(out_host, FSN_E_INVALID, "fsn_debug_report: null pointer");
-#ifdef FSN_DEBUG
-  FSN_HIP(hipDeviceSynchronize());
-  unsigned zero[4] = {0u, 0u, 0u, 0u};
-  FSN_HIP(hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_dbg_render), sizeof(unsigned) * 4));
-  FSN_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_dbg_render), zero, sizeof(zero)));
-  return fsn::debug_report_occ(out_host + 4);
-#else
-  FSN_REQUIRE(false, FSN_E_UNSUPPORTED, "fsn_debug_report: not a debug build (make -C fs-nerf_amd/csrc debug)");
 #endif
 }

@@ -29,7 +29,7 @@
 
 namespace fsn {
 
-FSN_DEBUG_DEFINE_RECORD(g_dbg_occ)
+FSN_DEBUG_DEFINE_RECORD(occ)
 #define FSN_DEBUG_RECORD g_dbg_occ
 
 constexpr int kCap = 2048;      // samples of a batch (candidates; kept samples are a subset)
@@ -409,19 +409,6 @@ static int launch_occ(const OccKArgs& k, int cus, hipStream_t s) {
   return FSN_OK;
 }
 
-}  // namespace fsn
-
-namespace fsn {
-int debug_report_occ(unsigned* host4) {  // (fsn_debug_report, render.hip)
-#ifdef FSN_DEBUG
-  unsigned zero[4] = {0u, 0u, 0u, 0u};
-  FSN_HIP(hipMemcpyFromSymbol(host4, HIP_SYMBOL(g_dbg_occ), sizeof(unsigned) * 4));
-  FSN_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_dbg_occ), zero, sizeof(zero)));
-#else
-  for (int i = 0; i < 4; ++i) host4[i] = 0u;
-#endif
-  return FSN_OK;
-}
 }  // namespace fsn
 
 using namespace fsn;

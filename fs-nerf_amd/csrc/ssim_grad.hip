@@ -22,8 +22,8 @@
 #include "common.hpp"
 
 namespace fsn {
-// debug build: the LDS indices of both kernels are range-checked (common.hpp), read by fsn_debug_report_ssim_grad
-FSN_DEBUG_DEFINE_RECORD(g_dbg_ssim_grad)
+// debug build: the LDS indices of both kernels are range-checked (common.hpp), read by fsn_debug_report("ssim_grad")
+FSN_DEBUG_DEFINE_RECORD(ssim_grad)
 }  // namespace fsn
 #define FSN_DEBUG_RECORD g_dbg_ssim_grad
 #include "ssim_dev.hpp"
@@ -200,17 +200,4 @@ extern "C" int fsn_ssim_grad(const float* x, const float* y, int64_t N, int C, i
   }
   FSN_LAUNCH_CHECK("k_ssim_grad_filter");
   return FSN_OK;
-}
-
-extern "C" int fsn_debug_report_ssim_grad(uint32_t* out_host) {
-  FSN_REQUIRE(out_host, FSN_E_INVALID, "fsn_debug_report_ssim_grad: null pointer");
-#ifdef FSN_DEBUG
-  FSN_HIP(hipDeviceSynchronize());
-  unsigned zero[4] = {0u, 0u, 0u, 0u};
-  FSN_HIP(hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_dbg_ssim_grad), sizeof(unsigned) * 4));
-  FSN_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_dbg_ssim_grad), zero, sizeof(zero)));
-  return FSN_OK;
-#else
-  FSN_REQUIRE(false, FSN_E_UNSUPPORTED, "fsn_debug_report_ssim_grad: not a debug build (make -C fs-nerf_amd/csrc debug)");
-#endif
 }

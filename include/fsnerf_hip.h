@@ -70,14 +70,23 @@ typedef void* fsn_stream_t; /* hipStream_t */
                                    (an event of the delayed gradient scaling like a loss scaler's, not a range fallback) */
 
 int fsn_version(void);
-/* Debug build only (make -C fs-nerf_amd/csrc debug -> libfsnerf_hip_dbg.so, -DFSN_DEBUG): every index into the
- * LDS arrays of k_render_fused / k_render_occ is range-checked; a violation is recorded and clamped, not trapped (GPU
- * sanitizers are not available on this pool).  out_host: 8 uint32 = {violations, source line of the first, its index,
- * the array's extent} for render.hip and for render_occ.hip; the records are cleared.  The release library returns
- * FSN_E_UNSUPPORTED. */
-int fsn_debug_report(uint32_t* out_host);
+/* Debug build only (make -C fs-nerf_amd/csrc debug -> libfsnerf_hip_dbg.so, -DFSN_DEBUG): the checked kernels'
+ * indices are range-checked; a violation is recorded and clamped (or its thread skipped), not trapped (GPU sanitizers
+ * are not available on this pool).  Each translation unit that checks keeps ONE record and registers it under a name:
+ *   "render"     render.hip      every LDS index of k_render_fused
+ *   "occ"        render_occ.hip  every LDS index of k_render_occ
+ *   "raydata"    raydata.hip     explicit ray indices outside [0, N) and explicit patch anchors outside [0, A)
+ *   "metrics"    metrics.hip     every LDS index of k_ssim_tile
+ *   "ssim_grad"  ssim_grad.hip   every LDS index of the two kernels behind the SSIM gradient
+ *   "lpips"      lpips.hip       every LDS index of k_lpips_conv and k_lpips_first_bwd
+ * A record is 4 uint32 = {violations, source line of the first, its index (or the end of its span), the extent}, the
+ * last two truncated to 32 bits.  fsn_debug_report synchronises the device, copies the record of `unit` to out4 and
+ * clears it; an unknown unit is FSN_E_INVALID (the message lists the known ones), the release library returns
+ * FSN_E_UNSUPPORTED.  fsn_debug_units: the registered names, sorted and comma-separated ("" in the release library). */
+int fsn_debug_report(const char* unit, uint32_t* out4);
+const char* fsn_debug_units(void);
 /* ... its negative control: a one-block launch with one deliberate out-of-range index and one out-of-range span into a
- * 32-element LDS array (the next fsn_debug_report must say 2 violations, extent 32, for render.hip). */
+ * 32-element LDS array (the next fsn_debug_report("render") must say 2 violations, extent 32). */
 int fsn_debug_selftest(void);
 const char* fsn_last_error(void);
 /* number of compute units of the current device (grid sizing), or negative on error */
@@ -115,7 +124,7 @@ int fsn_build_rays(const float* poses, int64_t n_poses, int H, int W, double foc
  *                            (seed, epoch) (csrc/ray_perm.hpp: 4-round Feistel network + cycle walking); no N-sized table
  *   FSN_RAY_ORDER_EXPLICIT   index = indices[i] (DEVICE int64 [count]; start must be 0).  An index outside [0, N) never
  *                            reaches memory: its thread leaves its output rows untouched (and, in the debug build,
- *                            records it for fsn_debug_report_raydata).
+ *                            records it for fsn_debug_report("raydata")).
  * poses: DEVICE [n_views, 12] (rows 0..2 of camera-to-world); images: DEVICE uint8 [n_views, H, W, C], C = 3 or 4;
  * ndc / near as fsn_build_rays.  Outputs (DEVICE; each may be NULL = not wanted): rays_o, rays_d [count, 3] - bit for
  * bit row `index` of fsn_build_rays' tables; rgb [count, 3] - bit for bit the reference's float images: byte / 255 and,
@@ -147,10 +156,6 @@ int fsn_ray_patch_batch(const float* poses, int64_t n_views, const uint8_t* imag
 /* The same permutation on the host (plain C++, no device is touched): out_host[i] = perm(start + i; N, seed, epoch) for
  * i < count, start + count <= N <= 2^62. */
 int fsn_ray_perm_host(int64_t N, uint64_t seed, int64_t epoch, int64_t start, int64_t count, int64_t* out_host);
-/* Debug build only: the record of explicit indices outside [0, N) met by k_ray_batch, and of explicit anchors outside
- * [0, A) met by the patch kernel (4 uint32: count, source line, the first index and N or A truncated to 32 bits),
- * cleared by the call.  The release library returns FSN_E_UNSUPPORTED. */
-int fsn_debug_report_raydata(uint32_t* out_host);
 
 /* ---- a4: PositionalEncoder.forward(x)                    src/core/models.py:43-50
  * x [n, d_in] -> out [n, d_in*(1+2*n_freqs)], block order x, sin f0, cos f0, sin f1, ...
@@ -840,9 +845,6 @@ int fsn_ssim(const float* x, const float* y, int64_t N, int C, int H, int W, con
 int64_t fsn_psnr_workspace_doubles(int64_t N, int C, int H, int W);
 int fsn_psnr(const float* x, const float* y, int64_t N, int C, int H, int W, const int64_t* x_strides_host,
              const int64_t* y_strides_host, double* workspace, float* out, fsn_stream_t stream);
-/* Debug build only: the LDS index record of k_ssim_tile (4 uint32, as fsn_debug_report's), cleared by the call.  The
- * release library returns FSN_E_UNSUPPORTED. */
-int fsn_debug_report_metrics(uint32_t* out_host);
 
 /* The backward of the SSIM above (csrc/ssim_grad.hip): the gradient of sum_n upstream[n] * ssim_n, ssim_n = out[n] of
  * the forward (the mean of S over the interior and the channels of image n), with respect to x and y.  With the
@@ -863,9 +865,6 @@ int fsn_ssim_grad(const float* x, const float* y, int64_t N, int C, int H, int W
                   const int64_t* y_strides_host, int window, int use_sample_covariance, double data_range, double K1,
                   double K2, const double* upstream, double* workspace, float* dx, const int64_t* dx_strides_host,
                   float* dy, const int64_t* dy_strides_host, fsn_stream_t stream);
-/* Debug build only: the LDS index record of the two kernels behind the SSIM gradient (4 uint32), cleared by the call.
- * The release library returns FSN_E_UNSUPPORTED. */
-int fsn_debug_report_ssim_grad(uint32_t* out_host);
 
 /* LPIPS v0.1, VGG16 backbone (the `lpips` package's LPIPS(net="vgg")), of N image pairs x, y (float32, DEVICE, 3
  * channels, H x W >= 16 x 16), read through their element strides (n, c, h, w) as the metrics above.  Per pair: the
@@ -913,9 +912,6 @@ int fsn_lpips_vgg_fwd_save(const void* packed, const float* x, const float* y, i
 int fsn_lpips_vgg_bwd(const void* packed, const void* packed_grad, int64_t B, int H, int W, int normalize, int want_dx,
                       int want_dy, const double* upstream, float* workspace, float* dx, const int64_t* dx_strides_host,
                       float* dy, const int64_t* dy_strides_host, fsn_stream_t stream);
-/* Debug build only: the LDS index record of k_lpips_conv and k_lpips_first_bwd (4 uint32, as fsn_debug_report's),
- * cleared by the call. */
-int fsn_debug_report_lpips(uint32_t* out_host);
 
 #ifdef __cplusplus
 }

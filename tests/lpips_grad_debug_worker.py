@@ -2,25 +2,16 @@
 (FSN_LIB_PATH -> libfsnerf_hip_dbg.so: every LDS index of k_lpips_conv and k_lpips_first_bwd range-checked,
 csrc/common.hpp) at 37 x 53, a size that is no multiple of the tile and odd through every pool, and prints the violation
 record as JSON."""
-import ctypes as C
-import json
-import os
-import sys
-
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import debug_lib as D
 
 
 def main():
-    import fs_nerf_amd  # noqa: F401
+    D.open_debug_library()
     import lpips_ref as LR
-    from fs_nerf_amd import _lib as L
     from fs_nerf_amd.core import metrics
     from fs_nerf_amd.core.loss import LPIPSLoss
-    assert "dbg" in os.path.basename(L.LIB_PATH), L.LIB_PATH
     dev = torch.device("cuda:0")
     m = metrics.LPIPS()
     m.load_state_dict(LR.random_state_dict(seed=1))
@@ -34,9 +25,7 @@ def main():
         for t, w in ((a, want[0]), (b, want[1])):
             assert (t.grad is not None) == w and (not w or bool(torch.isfinite(t.grad).all()))
     torch.cuda.synchronize()
-    buf = (C.c_uint32 * 4)()
-    L.check(L.lib().fsn_debug_report_lpips(buf), "fsn_debug_report_lpips")
-    print("LPIPS_GRAD_DEBUG_REPORT " + json.dumps(list(buf)), flush=True)
+    D.emit({"lpips": D.take("lpips"), "all": D.take_all()})
 
 
 if __name__ == "__main__":

@@ -2,27 +2,17 @@
 with more than half a batch of candidates, cone regime) and a per-ray bounds case in both regimes run through all three
 modes of the occupancy kernel in the DEBUG library (FSN_LIB_PATH -> libfsnerf_hip_dbg.so: every LDS index of k_render_occ
 range-checked, csrc/common.hpp); prints the violation record as JSON."""
-import ctypes as C
-import json
-import os
-import sys
-
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import debug_lib as D
 
 
 def main():
-    import fs_nerf_amd  # noqa: F401
-    from fs_nerf_amd import _lib as L
-    assert "dbg" in os.path.basename(L.LIB_PATH), L.LIB_PATH
+    D.open_debug_library()
     import test_occ_cone_fused_gpu as T
     from test_occ_cone_gpu import BOX1, N_RAYS, STEP, estimator, field, mixed_rays
     dev = torch.device("cuda:0")
-    buf = (C.c_uint32 * 8)()
-    L.check(L.lib().fsn_debug_report(buf), "fsn_debug_report")  # (clears the record)
+    D.take("render"), D.take("occ")  # (clears the records)
     o, d = mixed_rays()
     m = T.thin_model(dev)
     est, ms = T.carry_case(dev)
@@ -33,8 +23,7 @@ def main():
     for cone in (0.0, 0.02):
         T.three_modes(est, m, o, d, dev, STEP, est.max_steps(STEP, cone), f"debug build, bounds cone {cone}", cone=cone, u=u,
                       t_min=t_min, t_max=t_max, athre=1e-3)
-    L.check(L.lib().fsn_debug_report(buf), "fsn_debug_report")
-    print("DEBUG_REPORT " + json.dumps({"occ": list(buf), "carried": int((n_cand > 1024).sum())}), flush=True)
+    D.emit({"render": D.take("render"), "occ": D.take("occ"), "carried": int((n_cand > 1024).sum()), "all": D.take_all()})
 
 
 if __name__ == "__main__":

@@ -11,6 +11,8 @@ import fs_nerf_amd  # noqa: F401
 from fs_nerf_amd import _lib as L
 from fs_nerf_amd import ops
 
+import debug_lib
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -26,6 +28,24 @@ def test_every_declared_symbol_is_exported_and_bound():
     # the #define constants of the header and their Python mirrors
     for name, val in re.findall(r"#define\s+(FSN_(?:STATUS|PREC)_[A-Z0-9_]+)\s+(\d+)u?", hdr):
         assert getattr(L, name) == int(val), name
+
+
+def test_debug_records_register_themselves_and_are_reported_by_name():
+    """The debug library's registry (csrc/common.hip) without a GPU call: every FSN_DEBUG_DEFINE_RECORD(unit) of the
+    sources is reportable by its name, an unknown unit and null arguments are refused before any HIP call."""
+    dbg = C.CDLL(debug_lib.build_debug_library())
+    dbg.fsn_debug_units.restype = dbg.fsn_last_error.restype = C.c_char_p
+    dbg.fsn_debug_report.argtypes = [C.c_char_p, C.c_void_p]
+    csrc = os.path.join(ROOT, "fs-nerf_amd", "csrc")
+    defined = [u for f in sorted(os.listdir(csrc)) if f.endswith(".hip")
+               for u in re.findall(r"^FSN_DEBUG_DEFINE_RECORD\((\w+)\)", open(os.path.join(csrc, f)).read(), re.M)]
+    assert len(defined) >= 6 and len(set(defined)) == len(defined), defined
+    assert dbg.fsn_debug_units() == ",".join(sorted(defined)).encode()
+    buf = (C.c_uint32 * 4)()
+    assert dbg.fsn_debug_report(b"nosuch", buf) == -1 and dbg.fsn_debug_units() in dbg.fsn_last_error()
+    assert dbg.fsn_debug_report(None, buf) == -1
+    assert dbg.fsn_debug_report(b"render", None) == -1
+    assert L.lib().fsn_debug_units() == b""
 
 
 def test_argument_validation_without_gpu():

@@ -4,40 +4,29 @@ a node down, so the debug build RECORDS an index outside one of the render kerne
 clamps it; here small-shape parity cases of every BASELINE shape, ragged single-pass shapes, the launch-shape variants
 and the occupancy kernel run through it in a child process and the record must stay empty - after a negative control
 has shown that the checks fire."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "fs-nerf_amd", "csrc")
-DBG = os.path.join(CSRC, "libfsnerf_hip_dbg.so")
+import debug_lib
 
 
 def test_release_library_says_it_is_not_a_debug_build():
     import ctypes as C
     import fs_nerf_amd  # noqa: F401
     from fs_nerf_amd import _lib as L
-    buf = (C.c_uint32 * 8)()
-    assert L.lib().fsn_debug_report(buf) == -2 and b"not a debug build" in L.lib().fsn_last_error()
+    buf = (C.c_uint32 * 4)()
+    for unit in (b"render", b"occ"):
+        assert L.lib().fsn_debug_report(unit, buf) == -2 and b"not a debug build" in L.lib().fsn_last_error()
     assert L.lib().fsn_debug_selftest() == -2
 
 
 @pytest.mark.gpu
 def test_render_kernels_keep_inside_their_lds_arrays():
-    if not os.path.exists(DBG):  # (__graft_entry__.build() makes it; a bare checkout builds it here)
-        r = subprocess.run(["make", "-C", CSRC, "-j4", "debug"], capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    env = dict(os.environ, FSN_LIB_PATH=DBG)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "debug_build_worker.py")], capture_output=True, text=True,
-                         env=env, cwd=ROOT, timeout=1200)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    line = [ln for ln in out.stdout.splitlines() if ln.startswith("DEBUG_REPORT ")][-1]
-    rep = json.loads(line[len("DEBUG_REPORT "):])
-    st = rep["selftest"]
-    assert st[0] == 2 and st[3] == 32 and st[2] in (32, 34) and st[4:] == [0, 0, 0, 0], f"negative control: {st}"
-    assert rep["after_selftest"] == [0] * 8, "the report clears the record"
-    assert rep["render"] == [0] * 8, f"k_render_fused indexed outside an LDS array: {rep['render']} (count, line, index, extent)"
-    assert rep["occ"] == [0] * 8, f"k_render_occ indexed outside an LDS array: {rep['occ']}"
+    rep = debug_lib.run_worker("debug_build_worker.py", timeout=1200)
+    clean = {"render": [0] * 4, "occ": [0] * 4}
+    st = rep["selftest"]["render"]
+    assert st[0] == 2 and st[3] == 32 and st[2] in (32, 34) and rep["selftest"]["occ"] == [0, 0, 0, 0], \
+        f"negative control: {rep['selftest']}"
+    assert rep["after_selftest"] == clean, "the report clears the record"
+    assert rep["render"] == clean, f"k_render_fused indexed outside an LDS array: {rep['render']} (count, line, index, extent)"
+    assert rep["occ"] == clean, f"k_render_occ indexed outside an LDS array: {rep['occ']}"
+    debug_lib.assert_no_other_unit_recorded(rep)

@@ -176,4 +176,4 @@ def test_lpips_entry_points_validate_without_gpu():
     assert lib.fsn_lpips_pack(ptrs, ptrs, ptrs, fake, fake, fake, None) == -1
     assert lib.fsn_lpips_pack(None, None, None, None, None, None, None) == -1
     buf = (C.c_uint32 * 4)()
-    assert lib.fsn_debug_report_lpips(buf) == -2
+    assert lib.fsn_debug_report(b"lpips", buf) == -2

@@ -1,16 +1,15 @@
 """-m gpu: LPIPS-VGG on the device (fs_nerf_amd.core.metrics.LPIPS, csrc/lpips.hip) against the float64 and float32
 restatements of tests/lpips_ref.py, its determinism and layout independence, evaluation() with it, and the debug
 build's LDS index record of the convolution kernel."""
-import json
 import math
 import os
-import subprocess
 import sys
 
 import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import debug_lib  # noqa: E402
 import lpips_ref as LR  # noqa: E402
 
 import fs_nerf_amd  # noqa: E402,F401
@@ -18,7 +17,6 @@ from fs_nerf_amd.core import metrics  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = [((16, 16), 2), ((37, 53), 2), ((64, 64), 3)]  # ((H, W), N); 37 x 53: odd sizes through every pool
 KINDS = ["uniform", "smooth", "near"]
 
@@ -203,14 +201,6 @@ def test_evaluation_with_lpips(net, sd, dev):
 
 def test_conv_kernel_keeps_inside_its_lds_arrays():
     """The debug library (every LDS index of k_lpips_conv range-checked) in a child process: the record stays empty."""
-    dbg = os.path.join(ROOT, "fs-nerf_amd", "csrc", "libfsnerf_hip_dbg.so")
-    if not os.path.exists(dbg):  # (__graft_entry__.build() makes it)
-        r = subprocess.run(["make", "-C", os.path.dirname(dbg), "-j4", "debug"], capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    env = dict(os.environ, FSN_LIB_PATH=dbg)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "lpips_debug_worker.py")], capture_output=True,
-                         text=True, env=env, cwd=ROOT, timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    line = [ln for ln in out.stdout.splitlines() if ln.startswith("LPIPS_DEBUG_REPORT ")][-1]
-    rep = json.loads(line[len("LPIPS_DEBUG_REPORT "):])
-    assert rep == [0, 0, 0, 0], f"k_lpips_conv indexed outside an LDS array: {rep} (count, line, index, extent)"
+    rep = debug_lib.run_worker("lpips_debug_worker.py")
+    assert rep["lpips"] == [0, 0, 0, 0], f"k_lpips_conv indexed outside an LDS array: {rep['lpips']} (count, line, index, extent)"
+    debug_lib.assert_no_other_unit_recorded(rep)

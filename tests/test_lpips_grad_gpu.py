@@ -7,7 +7,6 @@ keep every ReLU unit and pool winner away from a flip (tests/test_lpips_grad_cpu
 FSN_LPIPS_ACCURACY_OUT=<file> to have the E values written as JSON (profiles/lpips_grad_accuracy.json is such a run)."""
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -15,6 +14,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import debug_lib  # noqa: E402
 import lpips_grad_ref as GR  # noqa: E402
 import lpips_ref as LR  # noqa: E402
 
@@ -25,7 +25,6 @@ from fs_nerf_amd.core.loss import LPIPSLoss  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _ACCURACY = {}
 
 
@@ -253,14 +252,6 @@ def test_lpips_loss_backward_through_render_rays_is_the_explicit_gradient(net, d
 def test_new_kernels_keep_inside_their_lds_arrays():
     """The debug library (every LDS index of k_lpips_conv and k_lpips_first_bwd range-checked) in a child process:
     forward-save and backward at 37 x 53 leave the record empty."""
-    dbg = os.path.join(ROOT, "fs-nerf_amd", "csrc", "libfsnerf_hip_dbg.so")
-    if not os.path.exists(dbg):  # (__graft_entry__.build() makes it)
-        r = subprocess.run(["make", "-C", os.path.dirname(dbg), "-j4", "debug"], capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    env = dict(os.environ, FSN_LIB_PATH=dbg)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "lpips_grad_debug_worker.py")], capture_output=True,
-                         text=True, env=env, cwd=ROOT, timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    line = [ln for ln in out.stdout.splitlines() if ln.startswith("LPIPS_GRAD_DEBUG_REPORT ")][-1]
-    rep = json.loads(line[len("LPIPS_GRAD_DEBUG_REPORT "):])
-    assert rep == [0, 0, 0, 0], f"an LPIPS kernel indexed outside an LDS array: {rep} (count, line, index, extent)"
+    rep = debug_lib.run_worker("lpips_grad_debug_worker.py")
+    assert rep["lpips"] == [0, 0, 0, 0], f"an LPIPS kernel indexed outside an LDS array: {rep['lpips']} (count, line, index, extent)"
+    debug_lib.assert_no_other_unit_recorded(rep)

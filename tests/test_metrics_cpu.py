@@ -123,7 +123,7 @@ def test_metric_entry_points_validate_without_gpu():
                             None) == -2
     # the debug record exists only in the debug build
     buf = (C.c_uint32 * 4)()
-    assert lib.fsn_debug_report_metrics(buf) == -2
+    assert lib.fsn_debug_report(b"metrics", buf) == -2
 
 
 # ---------------------------------------------------------------- the Python layer

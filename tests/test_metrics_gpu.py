@@ -1,10 +1,8 @@
 """-m gpu: device-side PSNR and SSIM (fs_nerf_amd.core.metrics, csrc/metrics.hip) against the float64 restatement of
 skimage 0.22 in tests/metrics_ref.py, their layouts and determinism, the reference-shaped evaluation() on rendered
 frames, and the debug build's LDS index record of the SSIM kernel."""
-import json
 import math
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -12,6 +10,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import debug_lib  # noqa: E402
 import metrics_ref as MR  # noqa: E402
 
 import fs_nerf_amd  # noqa: E402,F401
@@ -19,7 +18,6 @@ from fs_nerf_amd.core import metrics  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MEAN_TOL = 5e-7  # per-image mean SSIM
 MAP_TOL = 3e-4  # every pixel of the full=True map
 SIZES = [(11, 11), (13, 17), (100, 75), (800, 800)]
@@ -245,14 +243,6 @@ def test_evaluation_returns_the_reference_triple(dev):
 
 def test_ssim_kernel_keeps_inside_its_lds_arrays():
     """The debug library (every LDS index of k_ssim_tile range-checked) in a child process: the record stays empty."""
-    dbg = os.path.join(ROOT, "fs-nerf_amd", "csrc", "libfsnerf_hip_dbg.so")
-    if not os.path.exists(dbg):  # (__graft_entry__.build() makes it)
-        r = subprocess.run(["make", "-C", os.path.dirname(dbg), "-j4", "debug"], capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    env = dict(os.environ, FSN_LIB_PATH=dbg)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "metrics_debug_worker.py")], capture_output=True,
-                         text=True, env=env, cwd=ROOT, timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    line = [ln for ln in out.stdout.splitlines() if ln.startswith("METRICS_DEBUG_REPORT ")][-1]
-    rep = json.loads(line[len("METRICS_DEBUG_REPORT "):])
-    assert rep == [0, 0, 0, 0], f"k_ssim_tile indexed outside an LDS array: {rep} (count, line, index, extent)"
+    rep = debug_lib.run_worker("metrics_debug_worker.py")
+    assert rep["metrics"] == [0, 0, 0, 0], f"k_ssim_tile indexed outside an LDS array: {rep['metrics']} (count, line, index, extent)"
+    debug_lib.assert_no_other_unit_recorded(rep)

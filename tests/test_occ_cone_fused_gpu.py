@@ -7,22 +7,18 @@ outputs), extras (+ the packed per-sample arrays) and sampler (the kept samples)
 what can go wrong - block boundaries of the cone march, the variable widths in the cull and the compaction, rays carried
 between batches, truncation, empty rays - does not depend on the size."""
 import ctypes as C
-import json
 import math
-import os
-import subprocess
-import sys
 
 import pytest
 import torch
 
 from oracle import fsnerf_oracle as O
 
+import debug_lib
 import test_occ_fused as TF
 from test_occ_cone_gpu import BOX1, N_RAYS, STEP, estimator, field, mixed_rays, small_setup
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXTRAS = ("weights", "alphas", "trans", "sigmas", "rgbs")
 
 
@@ -353,15 +349,8 @@ def test_lds_indices_stay_inside_with_cone_and_bounds():
     """The debug library (every FSN_AT / FSN_SPAN of k_render_occ range-checked, the candidates' ends included - they
     share storage with the kept samples' densities): the carry case and a bounds case through all three modes in a child
     process; the record must stay empty.  (tests/test_debug_build.py holds the negative control.)"""
-    csrc = os.path.join(ROOT, "fs-nerf_amd", "csrc")
-    dbg = os.path.join(csrc, "libfsnerf_hip_dbg.so")
-    if not os.path.exists(dbg):  # (__graft_entry__.build() makes it; a bare checkout builds it here)
-        r = subprocess.run(["make", "-C", csrc, "-j4", "debug"], capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "occ_cone_debug_worker.py")], capture_output=True,
-                         text=True, env=dict(os.environ, FSN_LIB_PATH=dbg), cwd=ROOT, timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    line = [ln for ln in out.stdout.splitlines() if ln.startswith("DEBUG_REPORT ")][-1]
-    rep = json.loads(line[len("DEBUG_REPORT "):])
-    assert rep["occ"] == [0] * 8, f"k_render_occ indexed outside an LDS array: {rep['occ']} (count, line, index, extent)"
+    rep = debug_lib.run_worker("occ_cone_debug_worker.py")
+    got = rep["render"] + rep["occ"]
+    assert got == [0] * 8, f"k_render_occ indexed outside an LDS array: {got} (count, line, index, extent)"
+    debug_lib.assert_no_other_unit_recorded(rep)
     assert rep["carried"] >= 2

@@ -18,8 +18,8 @@ import test_occ_fused as TF
 pytestmark = pytest.mark.gpu
 R, S, NI, STEP = 40, 8, 8, 0.1
 # symbols whose last pointer argument is an output, not a stream (include/fsnerf_hip.h)
-NO_STREAM = {"fsn_debug_report", "fsn_debug_report_raydata", "fsn_debug_report_metrics", "fsn_debug_report_lpips",
-             "fsn_ray_perm_host", "fsn_mlp_pack_host", "fsn_mlp_pack_scaled_host", "fsn_weight_norm_workspace_floats"}
+NO_STREAM = {"fsn_debug_report", "fsn_ray_perm_host", "fsn_mlp_pack_host", "fsn_mlp_pack_scaled_host",
+             "fsn_weight_norm_workspace_floats"}
 
 
 @pytest.fixture(scope="module")

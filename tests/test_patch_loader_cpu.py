@@ -179,7 +179,7 @@ def test_ssim_grad_argument_validation_without_gpu():
     assert lib.fsn_ssim_grad_workspace_doubles(2, 3, 12, 17) == 2 * 3 * 4 * 12 * 17
     assert lib.fsn_ssim_grad_workspace_doubles(2, 0, 12, 17) == -1
     buf = (C.c_uint32 * 4)()
-    assert lib.fsn_debug_report_ssim_grad(buf) == -2 and b"not a debug build" in lib.fsn_last_error()
+    assert lib.fsn_debug_report(b"ssim_grad", buf) == -2 and b"not a debug build" in lib.fsn_last_error()
 
 
 def test_ssim_loss_refuses_cpu_tensors_and_bad_arguments():

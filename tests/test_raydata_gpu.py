@@ -2,11 +2,8 @@
 colours bit for bit the reference's byte arithmetic (tests/raydata_ref.py), the reference's own LLFFDataset tables
 (tests/golden/g8_raydata.npz), shuffled epochs, resume, rank slices, residency, and the two consumers: evaluation() and
 the training loop body."""
-import json
 import math
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,10 +15,10 @@ from fs_nerf_amd.core import metrics
 from fs_nerf_amd.nerfdata import FrameLoader, RayDataset, RayLoader
 from fs_nerf_amd.utils import utilities as U
 
+import debug_lib
 import raydata_ref as RR
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -334,14 +331,6 @@ def test_training_steps_fed_by_a_ray_loader(dev):
 # ---------------------------------------------------------------- debug build
 def test_ray_batch_kernel_reports_no_out_of_range_index():
     """The debug library in a child process: the smallest identity case and one shuffled epoch of it, all inputs valid."""
-    dbg = os.path.join(ROOT, "fs-nerf_amd", "csrc", "libfsnerf_hip_dbg.so")
-    if not os.path.exists(dbg):  # (__graft_entry__.build() makes it)
-        r = subprocess.run(["make", "-C", os.path.dirname(dbg), "-j4", "debug"], capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    env = dict(os.environ, FSN_LIB_PATH=dbg)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "raydata_debug_worker.py")], capture_output=True,
-                         text=True, env=env, cwd=ROOT, timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    line = [ln for ln in out.stdout.splitlines() if ln.startswith("RAYDATA_DEBUG_REPORT ")][-1]
-    rep = json.loads(line[len("RAYDATA_DEBUG_REPORT "):])
-    assert rep == [0, 0, 0, 0], f"k_ray_batch met an index outside the dataset: {rep} (count, line, index, N)"
+    rep = debug_lib.run_worker("raydata_debug_worker.py")
+    assert rep["raydata"] == [0, 0, 0, 0], f"k_ray_batch met an index outside the dataset: {rep['raydata']} (count, line, index, N)"
+    debug_lib.assert_no_other_unit_recorded(rep)

@@ -4,10 +4,6 @@ NumPy restatement of tests/ssim_grad_ref.py, entry by entry:
 2^-23 |ref| is twice the half-ulp of the one float32 rounding of the output; 2^-38 T allows ~ 1/C2 x 16 float64 roundings
 on the condition magnitude T of the entry (the restatement itself sits near 2^-50 T).  Each case prints its worst ratio
 to the bound (run with -s); the worst seen on one MI355X is 0.499, the float32 rounding itself."""
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -19,10 +15,10 @@ from fs_nerf_amd import ops
 from fs_nerf_amd.core import metrics
 from fs_nerf_amd.core.loss import SSIMLoss
 
+import debug_lib
 import ssim_grad_ref as GR
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # (N, C, H, W, gaussian window): one interior pixel; the box; two images, odd sizes; exactly one tile; two tile
 # boundaries in W and one in H with the halo crossing them
@@ -192,14 +188,6 @@ def test_ssim_loss_forward_is_the_metric_and_backward_is_the_kernel(dev, gauss, 
 
 def test_ssim_grad_kernels_keep_inside_their_lds_arrays():
     """The debug library (every LDS index of the two kernels range-checked) in a child process: the record stays empty."""
-    dbg = os.path.join(ROOT, "fs-nerf_amd", "csrc", "libfsnerf_hip_dbg.so")
-    if not os.path.exists(dbg):  # (__graft_entry__.build() makes it)
-        r = subprocess.run(["make", "-C", os.path.dirname(dbg), "-j4", "debug"], capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    env = dict(os.environ, FSN_LIB_PATH=dbg)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "ssim_grad_debug_worker.py")], capture_output=True,
-                         text=True, env=env, cwd=ROOT, timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    line = [ln for ln in out.stdout.splitlines() if ln.startswith("SSIM_GRAD_DEBUG_REPORT ")][-1]
-    rep = json.loads(line[len("SSIM_GRAD_DEBUG_REPORT "):])
-    assert rep == [0, 0, 0, 0], f"an SSIM gradient kernel indexed outside an LDS array: {rep} (count, line, index, extent)"
+    rep = debug_lib.run_worker("ssim_grad_debug_worker.py")
+    assert rep["ssim_grad"] == [0, 0, 0, 0], f"an SSIM gradient kernel indexed outside an LDS array: {rep['ssim_grad']} (count, line, index, extent)"
+    debug_lib.assert_no_other_unit_recorded(rep)
