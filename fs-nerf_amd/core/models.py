@@ -25,9 +25,12 @@ split-K wgrad kernels in the same precision mode).  Additions over the reference
   "bf16x3"  the same split on bf16 parts: no range limit, ~1e-5 per product;
   "fp16x2"  two passes (weights high part only): measured accuracy in DESIGN.md, not a parity mode;
   "bf16" / "fp16"  one pass (BASELINE config 5), tolerance stated in the tests.
+What follows a range flag, and the state it keeps (`NeRF.act_state`, `NeRF.train_state`), is core/range_guard.py; this
+file holds the encoder, `_NerfTrainFn`, `NeRF` (network, knobs, pack, forward) and `OccEvalFn`.
 """
+import functools
 import warnings
-from typing import Optional, Sequence, Tuple
+from typing import Optional, Tuple
 
 import torch
 from torch import Tensor, nn
@@ -35,6 +38,8 @@ from torch.autograd.function import once_differentiable
 
 from .. import _lib as L
 from .. import ops
+from .range_guard import (ActScaling, PackCache, TrainStatus, _warn_single_pass, choose_exponents, guarded_launch,
+                          single_pass_launch)
 
 
 def _freqs(n_freqs: int, log_space: bool) -> Tensor:
@@ -71,8 +76,7 @@ class _NerfTrainFn(torch.autograd.Function):
         launch (no gathered [N,3] tensors)."""
         n = len(params) // 2
         weights, biases = params[:n], params[n:]
-        desc = ops.make_desc(model.n_layers, model.d_hidden, model.skip, model.pos_encoder.freqs,
-                             model.dir_encoder.freqs)
+        desc = model.desc
         ray_form = packed is not None
         dev = a.device
         prec = model.train_prec()
@@ -121,10 +125,10 @@ class _NerfTrainFn(torch.autograd.Function):
         into = ([p.grad for p in ctx.params[:n]], [p.grad for p in ctx.params[n:]]) if sink else None
         model = ctx.model
         d_out = d_out.contiguous()
-        which = "" if want_params else "_inputs"
-        stage = model._bwd_stage_state(d_out.device, which) if model.fp16_family(ctx.prec) else None
+        kind = model.train_state.train if want_params else model.train_state.inputs
+        stage = kind.stage_on(d_out.device, model.n_layers + 2) if model.fp16_family(ctx.prec) else None
         src = {} if inputs is None else {k: inputs[k] for k in ("x", "dirs", "rays", "pos_mask", "dir_mask") if k in inputs}
-        if stage is not None and not getattr(model, "_bwd_calibrated" + which) and d_out.shape[0] > 0:
+        if stage is not None and not kind.calibrated and d_out.shape[0] > 0:
             # first backward of this model in an fp16 mode: one throw-away pass to measure the per-stage gradient
             # magnitudes (delayed scaling needs a previous call; its own status word, scratch outputs).  A call without
             # samples - the all-background first batch of an empty occupancy grid - launches nothing and calibrates
@@ -135,7 +139,7 @@ class _NerfTrainFn(torch.autograd.Function):
             else:  # (the chain alone)
                 ops.nerf_train_bwd_inputs(ctx.desc, ctx.prec, ctx.weights, ctx.work, ctx.out, d_out, **src, want_x=False,
                                           want_dirs=False, param_grads=False, status=scratch, stage_state=stage)
-            setattr(model, "_bwd_calibrated" + which, True)
+            kind.calibrated = True
         if inputs is None:
             dW, db = ops.nerf_train_bwd(ctx.desc, ctx.prec, ctx.weights, ctx.work, ctx.out, d_out, status=ctx.word,
                                         into=into, stage_state=stage)
@@ -155,28 +159,8 @@ class _NerfTrainFn(torch.autograd.Function):
         ctx.work = None
         ctx.params = None
         ctx.inputs = None
-        # fp16 range guard without a per-step host sync.  When this call's launches reported values outside the fp16
-        # range, the backward kernels have written ITS gradients as zeros on the device; the call's word is folded
-        # (device ops) into the device's step flag, on which FusedAdam skips the whole update - a skipped step, like a
-        # loss scaler's - and into this model's own accumulated word, which the host reads every `range_check_every`
-        # training calls; it then warns and continues in bf16x3.
-        if ctx.word is not None and not want_params:
-            model._fold_input_status(ctx.word, d_out.device)
-        elif ctx.word is not None:
-            model.fold_status(ctx.word, d_out.device, 0)
-            model._train_calls += 1
-            if model.range_check and model._train_calls % model.range_check_every == 0:
-                model._guard_weights("training steps", training=True)
-                bits, sampler_bits = model._read_train_status(d_out.device)
-                if bits:
-                    model.fall_back("training steps (an overflowing step's gradients were zeroed on the device and its "
-                                    "optimizer update skipped)", bits, scaled=False)
-                # The sampler's density pass in front of the training forward is an INFERENCE launch (scaled fp16x3):
-                # a flag there says its per-layer scales no longer fit the weights being trained (the step was skipped
-                # on the device); the next sampler call re-calibrates on its own rays.  Also every 4th look, flag or
-                # not, so that the scales follow the network long before a guard trips.
-                if sampler_bits or (model._train_calls // model.range_check_every) % 4 == 0:
-                    model._needs_calibration = True
+        if ctx.word is not None:  # fp16 range guard without a per-step host sync
+            model.train_state.after_backward(model, ctx.word, d_out.device, step=want_params)
         if sink or not want_params:
             return (None, None, g_a, g_b) + (None,) * (2 * n)
         db = [g.reshape(-1) for g in db]
@@ -214,28 +198,21 @@ class NeRF(nn.Module):
         # small launches: no wait per call; render_frame checks once per frame); False = never look
         self.range_check = True
         self.range_check_every = 16  # ... in training: every that many steps (gradients are guarded on the device)
-        self._train_calls = 0
         self._pack_calls = 0
         self.weight_check = True     # fp16 modes: look at the layers' largest weights when (re-)packing (_guard_weights)
-        self._train_word: Optional[Tensor] = None
-        self._bwd_stage = None       # (scales, maxima) of the backward's delayed per-stage gradient scaling (fp16 modes)
-        self._bwd_calibrated = False
-        self._bwd_stage_inputs = None  # ... of backward calls that compute input gradients only (no training steps)
-        self._bwd_calibrated_inputs = False
-        self._input_word: Optional[Tensor] = None
-        self._input_calls = 0
+        # accumulated range words, call counters and the backward's delayed per-stage gradient scaling (fp16 modes)
+        self.train_state = TrainStatus()
         self.grad_overflow_looks = 0  # host looks that found a step skipped by the delayed gradient scaling
         self.train_precision: Optional[str] = None  # None: same mode as `precision`
         self.pos_mask: Optional[Tensor] = None
         self.dir_mask: Optional[Tensor] = None
-        self._packed = None
-        self._packed_key = None
+        self._packed = PackCache()   # `packed`
         # OPT-IN, not a parity mode: arithmetic of the density pass behind the occupancy estimator's visibility cull when
         # it runs as the sampler in front of a training forward (None = the model's inference mode; "bf16" = one pass).
         # That pass only decides which marched samples are KEPT (transmittance >= early_stop_eps); the kept samples are
         # then evaluated, integrated and differentiated in the model's own mode.  See `packed_cull`.
         self.cull_precision: Optional[str] = None
-        self._packed_single = {}  # mode -> (key, PackedMLP): `packed_single`
+        self._packed_single = {}  # mode -> PackCache: `packed_single`
         # OPT-IN, not a parity mode: this project's equivalent of running under autocast.  "fp16" / "bf16": a `forward`
         # made under torch.no_grad() AND inside an enabled CUDA autocast region (the reference's occupancy refresh,
         # run-nerf.py:288-295) runs in that single-pass mode, float32 tensor out.  None: autocast is ignored.  Training
@@ -244,12 +221,7 @@ class NeRF(nn.Module):
         # per-layer activation scaling of the fp16x3 inference path (module docstring)
         self.act_scaling = True
         self.act_target_exp = self.ACT_TARGET_EXP
-        self._act_exps: Optional[list] = None   # n_layers + 2 exponents (kernel GEMM order), None = not calibrated
-        self._calib_key = None                  # parameter versions the calibration was made with
-        self._calib_moves = 0                   # target moves since then (same weights, data did not fit)
-        self._target_moved_by = 0               # ... and their sum: undone when the weights change
-        self._needs_calibration = False
-        self._calib_blob = None
+        self.act_state = ActScaling()  # what `calibrate` measured, the target moves since
         self.calibrations = 0                   # statistics: calibration launches / range events (fall-backs and
         self.range_events = 0                   # re-calibrations) of this model
 
@@ -273,98 +245,21 @@ class NeRF(nn.Module):
         """`precision` is one of the fp16 modes now (range-guarded; `fall_back` leaves them)."""
         return self.fp16_family(self.PRECISIONS[self.precision])
 
-    def _bwd_stage_state(self, dev, which: str = ""):
-        """(scales, maxima) of the backward chain's delayed per-stage scaling (fsn_nerf_train_bwd), device-resident.
-        `which` = "" for training steps, "_inputs" for calls that compute input gradients only (a frozen network,
-        `density_gradient`): their cotangents are other quantities, so they steer a pair of arrays of their own."""
-        st = getattr(self, "_bwd_stage" + which)
-        if st is None or st[0].device != dev:
-            n = self.n_layers + 2
-            st = (torch.ones(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev))
-            setattr(self, "_bwd_stage" + which, st)
-            setattr(self, "_bwd_calibrated" + which, False)
-        return st
-
-    def _fold_input_status(self, word: Tensor, dev) -> None:
-        """Range word of a backward that computed input gradients only (fp16 modes; its gradients are zeros when the
-        word is set).  Not a training step: it joins neither the optimizer's step flags nor `_train_calls`; it is ORed
-        into a word of its own that the host reads every `range_check_every` such calls - a flagged one then warns and
-        the model continues in the bf16 mode, as after a flagged training step."""
-        w = self._input_word
-        if w is None or w.device != dev:
-            w = self._input_word = torch.zeros(1, dtype=torch.int32, device=dev)
-        w.bitwise_or_(word)
-        self._input_calls += 1
-        if self.range_check and self._input_calls % self.range_check_every == 0:
-            bits = int(w.item())
-            if bits:
-                w.zero_()
-            if bits & L.FSN_STATUS_GRAD_RANGE:
-                self.grad_overflow_looks += 1
-            if bits & (L.FSN_STATUS_FP16_RANGE | L.FSN_STATUS_FP16_SMALL):
-                self.fall_back("input-gradient calls (a flagged call's gradients were written as zeros)", bits, scaled=False)
-
-    def _step_flags(self, dev):
-        """The step-flag words a training launch of this model reports into (device int32 [1] each): the word of every
-        gradient bucket that owns one of its parameters (`shard.FlatGrads.step_flag`, consumed by that bucket's
-        optimizer), and the device's shared word (`ops.step_flag`) for parameters no bucket owns."""
-        flags, loose = {}, False
-        for p in self.parameters():
-            f = getattr(p, "_fsn_step_flag", None)
-            if f is None or f.device != dev:
-                loose = True
-            else:
-                flags[id(f)] = f
-        out = list(flags.values())
-        if loose or not out:
-            out.append(ops.step_flag(dev))
-        return out
-
-    def _train_status(self, dev) -> Tensor:
-        """This model's accumulated training range words (device int32 [2]; OR of its calls' words since the last host
-        look): [0] the training kernels' (forward-with-savers / backward), [1] the sampler's density pass (an inference
-        launch in front of the training forward, rendering.py)."""
-        w = self._train_word
-        if w is None or w.device != dev:
-            w = self._train_word = torch.zeros(2, dtype=torch.int32, device=dev)
-        return w
-
-    def fold_status(self, word: Tensor, dev, slot: int) -> None:
-        """A training-time launch's range word (device int32 [1]) joins the step's guard on the device, no host sync: ORed
-        into every step flag of this model (FusedAdam skips a flagged step) and into slot `slot` of `_train_status`."""
-        for f in self._step_flags(dev):
-            f.bitwise_or_(word)
-        self._train_status(dev)[slot:slot + 1].bitwise_or_(word)
-
-    def _read_train_status(self, dev) -> Tuple[int, int]:
-        """Host look at the accumulated words (one 8-byte read-back) and clear -> (training kernels' bits, sampler's
-        bits).  Data-parallel runs take the MAX over the ranks first (every rank makes the same number of training
-        calls, so all of them are here together): a rank that overflowed and one that did not must not continue in
-        different arithmetic."""
-        w = self._train_status(dev)
-        from ..shard import max_bits_over_ranks
-        local, samp = (int(v) for v in w.tolist())
-        if local & L.FSN_STATUS_GRAD_RANGE:  # delayed gradient scaling skipped a step (and lowered a stage): no fall-back
-            self.grad_overflow_looks += 1
-        env = L.FSN_STATUS_FP16_RANGE | L.FSN_STATUS_FP16_SMALL
-        # (MAX of bit masks 0..3: both bits lead to the same action, so the largest mask is enough; the two words are
-        # reduced separately - a MAX over a combined mask would lose the smaller word's bits)
-        bits = max_bits_over_ranks(local & env, dev)
-        sbits = max_bits_over_ranks(samp & env, dev)
-        if local or samp or bits or sbits:
-            w.zero_()
-        return bits & env, sbits & env
+    @functools.cached_property
+    def desc(self) -> L.MlpDesc:
+        """Descriptor of every launch and blob (frequencies, depth, width and skips do not change after construction)."""
+        return ops.make_desc(self.n_layers, self.d_hidden, self.skip, self.pos_encoder.freqs, self.dir_encoder.freqs)
 
     def fall_back(self, what: str, bits: int = L.FSN_STATUS_FP16_RANGE, probe=None, earlier_invalid: bool = False,
                   scaled: bool = True) -> None:
         """An fp16-mode launch reported values outside the mode's envelope; the caller re-runs the call afterwards.
         Scaled inference (`infer_prec() == FSN_PREC_FP16X3U`, and `scaled`: the report came from an inference launch):
-        the calibration did not fit the data - re-calibrate on `probe` (`_recalibrate`) and stay in fp16x3.  Otherwise,
+        the calibration did not fit the data - re-calibrate on `probe` (`ActScaling.recalibrate`) and stay in fp16x3.  Otherwise,
         or when that does not help: continue in the bf16 mode of the same pass structure, which has float32's range,
         with a RuntimeWarning.  Never silent: `earlier_invalid` (deferred range checks) warns in the re-calibrated case
         too, because results already handed out were invalid."""
         self.range_events += 1
-        if scaled and self.infer_prec() == L.FSN_PREC_FP16X3U and self._recalibrate(bits, probe):
+        if scaled and self.infer_prec() == L.FSN_PREC_FP16X3U and self.act_state.recalibrate(self, bits, probe):
             if earlier_invalid:
                 warnings.warn(f"fs-nerf HIP path: {what}: the per-layer activation scales did not fit the data "
                               f"({ops.describe_flags(bits)}); re-calibrated", RuntimeWarning, stacklevel=3)
@@ -397,14 +292,9 @@ class NeRF(nn.Module):
 
     def load_state_dict(self, *args, **kwargs):
         out = super().load_state_dict(*args, **kwargs)
-        self._act_exps = None  # other weights: calibrate again on the next inference call
-        self._forget_target_moves()
+        self.act_state.exps = None  # other weights: calibrate again on the next inference call
+        self.act_state.forget_target_moves(self)
         return out
-
-    def _forget_target_moves(self) -> None:
-        # target moves answered a probe that did not represent the data under the OLD weights
-        self.act_target_exp -= self._target_moved_by
-        self._target_moved_by = self._calib_moves = 0
 
     def _default_probe(self, dev):
         g = torch.Generator(device="cpu").manual_seed(0)
@@ -421,9 +311,9 @@ class NeRF(nn.Module):
         most PROBE_MAX samples (`fsn_mlp_layer_maxima`) and one small read-back.  `keep_if_close`: an existing exponent
         is kept while it still puts the layer's maximum within [2^-3, 2^1] of the target (periodic re-calibration
         during training: no flapping between neighbouring powers of two).  -> the exponents."""
-        import math
         ws, bs = self._tensors()
         dev = ws[0].device
+        act = self.act_state
         if callable(probe):
             probe = probe()
         x, d = probe if probe is not None else self._default_probe(dev)
@@ -433,11 +323,8 @@ class NeRF(nn.Module):
         if x.shape[0] > self.PROBE_MAX:
             idx = torch.linspace(0, x.shape[0] - 1, self.PROBE_MAX, device=dev).long()
             x, d = x[idx], d[idx]
-        desc = ops.make_desc(self.n_layers, self.d_hidden, self.skip, self.pos_encoder.freqs, self.dir_encoder.freqs)
-        if self._calib_blob is None or self._calib_blob.blob.device != dev:
-            self._calib_blob = ops.PackedMLP(desc, L.FSN_PREC_BF16X3, dev)
-        self._calib_blob.pack(ws, bs)
-        maxima = ops.mlp_layer_maxima(self._calib_blob, x.contiguous(), d.contiguous(), self._mask(self.pos_mask, dev),
+        blob = act.blob.pack(self.desc, L.FSN_PREC_BF16X3, dev, None, ws, bs)  # (every probe launch packs afresh)
+        maxima = ops.mlp_layer_maxima(blob, x.contiguous(), d.contiguous(), self._mask(self.pos_mask, dev),
                                       self._mask(self.dir_mask, dev))
         # largest |weight| per GEMM, activation columns and encoding columns separately (the scaled weights must stay
         # inside fp16 too): one stacked reduction, read back together with the maxima
@@ -450,54 +337,11 @@ class NeRF(nn.Module):
             wmax.append(w[:, :na].amax() if na else w.new_zeros(()))
             wmax.append(w[:, na:].amax() if w.shape[1] > na else w.new_zeros(()))
         host = torch.cat([maxima, torch.stack(wmax).to(torch.float32)]).cpu().tolist()  # the one host sync
-        amax, wmx = host[:n + 2], host[n + 2:]
-        T = int(self.act_target_exp)
-        old = self._act_exps
-        exps = []
-        for g, v in enumerate(amax):
-            if not math.isfinite(v):
-                raise RuntimeError(f"NeRF.calibrate: layer {g} produced non-finite activations on the probe batch")
-            if v <= 0.0:
-                e = old[g] if old is not None else 0  # dead layer on the probe: its scale does not matter
-            else:
-                e = T - math.ceil(math.log2(v))
-                if keep_if_close and old is not None and 2.0 ** (T - 3) <= v * 2.0 ** old[g] <= 2.0 ** (T + 1):
-                    e = old[g]
-            exps.append(max(-60, min(60, e)))
-        # scaled weights: W_g * 2^(e_g - e_prev) on activation columns, W_g * 2^e_g on encoding columns, below 2^15
-        for g in range(n + 2):
-            prev = 0 if g == 0 else (exps[n - 1] if g == n else (exps[n] if g == n + 1 else exps[g - 1]))
-            for wm, sh in ((wmx[2 * g], exps[g] - prev), (wmx[2 * g + 1], exps[g])):
-                if wm > 0.0 and math.isfinite(wm):
-                    over = math.ceil(math.log2(wm)) + sh - 15
-                    if over > 0:
-                        exps[g] -= over
-        self._act_exps = exps
-        self._calib_key = self._param_key()
-        self._needs_calibration = False
+        act.exps = choose_exponents(host[:n + 2], host[n + 2:], int(self.act_target_exp), act.exps, keep_if_close, n)
+        act.key = self._param_key()
+        act.needs_calibration = False
         self.calibrations += 1
-        return exps
-
-    def _recalibrate(self, bits: int, probe) -> bool:
-        """A scaled-mode launch reported that its calibration does not fit the data.  Other weights than the calibration
-        saw: measure again.  Same weights: the probe was not representative - move the target (overflow: 2^4 more
-        headroom; small: 2^3 less) and measure again, at most three times.  False: give up (bf16x3)."""
-        if self._act_exps is not None and self._calib_key == self._param_key():
-            if self._calib_moves >= 3 or bits == (L.FSN_STATUS_FP16_RANGE | L.FSN_STATUS_FP16_SMALL):
-                return False
-            self._calib_moves += 1
-            move = -4 if bits & L.FSN_STATUS_FP16_RANGE else 3
-            self.act_target_exp += move
-            self._target_moved_by += move
-            if not 2 <= self.act_target_exp <= 14:
-                return False
-        else:
-            self._forget_target_moves()
-        try:
-            self.calibrate(probe)
-        except RuntimeError:
-            return False
-        return True
+        return act.exps
 
     def _weights_below_envelope(self) -> bool:
         """fp16 modes: True when some layer's LARGEST weight is below 2^-20.  High parts under 2^-14 are fp16 subnormals
@@ -524,26 +368,22 @@ class NeRF(nn.Module):
         fp16x3 inference: the first call (and the first one after `load_state_dict` or a request of the training
         loop's periodic look) calibrates the per-layer scales on `probe` (see `calibrate`) first."""
         ws, bs = self._tensors()
-        scaled = self.infer_prec() == L.FSN_PREC_FP16X3U
-        if scaled and (self._act_exps is None or self._needs_calibration):
-            self.calibrate(probe, keep_if_close=self._act_exps is not None)
-        exps = tuple(self._act_exps) if scaled else None
-        key = (self.precision, ws[0].device, exps) + self._param_key()
-        if self._packed is None or key != self._packed_key:
+        act, dev, params = self.act_state, ws[0].device, self._param_key()
+        if self.infer_prec() == L.FSN_PREC_FP16X3U and (act.exps is None or act.needs_calibration):
+            self.calibrate(probe, keep_if_close=act.exps is not None)
+
+        def mode():  # -> (exponents to pack with, key of the blob): the weight guard below may leave the fp16 modes
+            exps = tuple(act.exps) if self.infer_prec() == L.FSN_PREC_FP16X3U else None
+            return exps, (self.precision, dev, exps) + params
+
+        exps, key = mode()
+        if self._packed.stale(key):
             if self._pack_calls % max(1, int(self.range_check_every)) == 0:
                 self._guard_weights("NeRF.packed")
-                scaled = self.infer_prec() == L.FSN_PREC_FP16X3U
-                exps = tuple(self._act_exps) if scaled else None
-                key = (self.precision, key[1], exps) + key[3:]
+                exps, key = mode()
             self._pack_calls += 1
-            desc = ops.make_desc(self.n_layers, self.d_hidden, self.skip, self.pos_encoder.freqs,
-                                 self.dir_encoder.freqs)
-            prec = self.infer_prec()
-            if self._packed is None or self._packed.prec != prec or self._packed.blob.device != ws[0].device:
-                self._packed = ops.PackedMLP(desc, prec, ws[0].device)
-            self._packed.pack(ws, bs, exps)
-            self._packed_key = key
-        return self._packed
+            self._packed.pack(self.desc, self.infer_prec(), dev, key, ws, bs, exps)
+        return self._packed.pm
 
     def packed_single(self, precision: str) -> ops.PackedMLP:
         """The weights packed for the single-pass mode `precision` ("fp16" / "bf16": no calibration), one cached blob
@@ -552,15 +392,10 @@ class NeRF(nn.Module):
             raise ValueError(f"single-pass precision: one of {self.SINGLE_PASS}, not {precision!r}")
         ws, bs = self._tensors()
         key = (ws[0].device,) + self._param_key()
-        ent = self._packed_single.get(precision)
-        if ent is None or ent[0] != key:
-            pm = None if ent is None else ent[1]
-            if pm is None or pm.blob.device != ws[0].device:
-                desc = ops.make_desc(self.n_layers, self.d_hidden, self.skip, self.pos_encoder.freqs, self.dir_encoder.freqs)
-                pm = ops.PackedMLP(desc, self.PRECISIONS[precision], ws[0].device)
-            pm.pack(ws, bs)
-            self._packed_single[precision] = (key, pm)
-        return self._packed_single[precision][1]
+        cache = self._packed_single.setdefault(precision, PackCache())
+        if cache.stale(key):
+            cache.pack(self.desc, self.PRECISIONS[precision], ws[0].device, key, ws, bs)
+        return cache.pm
 
     def packed_cull(self) -> ops.PackedMLP:
         """The weights packed for the mode `cull_precision` names (single-pass bf16: float32's range, no calibration and
@@ -669,29 +504,6 @@ class NeRF(nn.Module):
                                                   self._mask(self.dir_mask, dev)))
 
 
-def _warn_single_pass(model: NeRF, what: str, bits: int) -> str:
-    model.range_events += 1
-    warnings.warn(f"fs-nerf HIP path: {what}: hidden activations left the fp16 range envelope of precision 'fp16' "
-                  f"({ops.describe_flags(bits)}); re-running / continuing in 'bf16'", RuntimeWarning, stacklevel=4)
-    return "bf16"
-
-
-def single_pass_launch(model: NeRF, precision: str, dev, what: str, leave_fp16, launch, undo=None):
-    """`launch(packed blob)` in the opt-in single-pass mode `precision` under the fp16 range guard (`guarded_launch`'s
-    policy for a mode that is not the model's own): "bf16" has float32's range and raises no flags - no host read;
-    "fp16" reads the launch's word back (one host sync, unless `model.range_check` is False), and a flagged launch leaves
-    no trace: `undo()`, `leave_fp16(what, bits)` (warns, moves its owner to "bf16" for good), and the call is made again
-    in bf16."""
-    out = launch(model.packed_single(precision))
-    if precision == "fp16" and model.range_check:
-        bits = ops.range_flags(dev)
-        if bits:
-            if undo is not None:
-                undo()
-            out = launch(model.packed_single(leave_fp16(what, bits)))
-    return out
-
-
 class OccEvalFn:
     """`NeRF.occ_eval_fn(render_step_size, precision)`: the callable for the `occ_eval_fn` slot of
     `update_every_n_steps` (run-nerf.py:288-295).  Called with points it returns `model(x) * render_step_size`, the density
@@ -718,58 +530,3 @@ class OccEvalFn:
     def __call__(self, x: Tensor) -> Tensor:
         m, dev = self.model, x.device
         return self.guarded(dev, "OccEvalFn", lambda pm: ops.mlp_fwd(pm, x, None, m._mask(m.pos_mask, dev))) * self.render_step_size
-
-
-def guarded_launch(nets: Sequence[NeRF], dev, what: str, probe, launch, earlier: str = "call"):
-    """`launch()` under the fp16 range guard for the NeRFs `nets` it evaluates (one precision mode for all of them).
-    range_check True: read the launch's word back (one host sync); a flagged call is re-run after `fall_back`
-    (re-calibration of the scaled fp16x3 path, or bf16x3).  "deferred": no wait - the word of the PREVIOUS launch is
-    looked at now (a raised flag re-calibrates / switches the nets and says that the previous call's outputs are
-    invalid), this launch posts its own for the next call / `frame_flagged` to look at.  False: never look."""
-    guarded = [m for m in nets if m.range_check and m.fp16_mode]
-    if guarded and all(m.range_check == "deferred" for m in guarded):
-        bits = ops.range_poll(dev)
-        if bits:
-            _fall_back(nets, f"an EARLIER {earlier} (deferred range check: its outputs are invalid)", bits, probe, True)
-        out = launch()
-        if any(m.fp16_mode for m in nets):
-            ops.range_post(dev)
-        return out
-    out = launch()
-    for _ in range(5):
-        bits = ops.range_flags(dev) if guarded else 0
-        if not bits:
-            break
-        _fall_back(nets, what, bits, probe)
-        out = launch()
-        guarded = [m for m in nets if m.range_check and m.fp16_mode]
-    return out
-
-
-def _fall_back(nets: Sequence[NeRF], what: str, bits: int, probe, earlier_invalid: bool = False) -> None:
-    for m in nets:  # the coarse and the fine pass run in one precision mode
-        if m.fp16_mode:
-            m.fall_back(what, bits, probe, earlier_invalid=earlier_invalid)
-    if len({m.infer_prec() for m in nets}) > 1:  # one net could re-calibrate, another had to give up: both go to bf16x3
-        for m in nets:
-            if m.fp16_mode:
-                m.act_scaling = False
-                m.fall_back(what, bits, scaled=False)
-
-
-def frame_flagged(nets: Sequence[NeRF], dev, events_before: Optional[int] = None, probe=None) -> bool:
-    """Deferred range check (`NeRF.range_check = "deferred"`): the one look per frame.  True when a launch of the frame
-    left the fp16 envelope - the LAST one (its word is polled here) or an EARLIER chunk, which the following chunk's poll
-    has consumed already (the chunk that overflowed is in the list of results all the same): any range event
-    since `events_before` (the nets' summed `range_events`) says so.  The nets have been re-calibrated / switched to
-    their bf16 mode (with a RuntimeWarning); the caller renders the frame again."""
-    earlier = events_before is not None and sum(m.range_events for m in nets) != events_before
-    if not any(m.range_check == "deferred" and m.fp16_mode for m in nets):
-        return earlier
-    bits = ops.range_poll(dev)
-    if not bits:
-        return earlier
-    for m in nets:
-        if m.fp16_mode:
-            m.fall_back("render_frame (deferred range check at the end of the frame)", bits, probe, earlier_invalid=True)
-    return True

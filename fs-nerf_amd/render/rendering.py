@@ -21,7 +21,8 @@ import torch
 from torch import Tensor, nn
 
 from .. import ops
-from ..core.models import NeRF, frame_flagged, guarded_launch
+from ..core.models import NeRF
+from ..core.range_guard import frame_flagged, guarded_launch, sampler_launch
 from ..utils import utilities as U
 from . import volrend
 from .occgrid import OccGridEstimator
@@ -329,29 +330,13 @@ def _fused_occ_launch(rays_o, rays_d, camera, estimator, model, model_fine, trai
     return (rgb, opacity, depth, ex), ray_indices, (t_starts + t_ends) / 2.0
 
 
-def _sampler_launch(model: NeRF, needs_grad: bool, dev, probe, launch):
-    """`launch(packed, status=None)` of a fused sampler (its density pass is an inference launch of `model`).  Training
-    step in a guarded fp16 mode: no host read-back between the sampler and the forward (it cost the step 0.2 ms of idle
-    GPU); the sampler reports into a word of its own, which joins the step's guard on the device like the forward /
-    backward pair's does (NeRF.fold_status): an overflowing density pass makes this a skipped step (FusedAdam); at its
-    next periodic look the host re-calibrates the density pass's per-layer scales (scaled fp16x3 inference) or
-    switches to bf16x3.  Otherwise the launch runs under the range guard."""
-    with torch.no_grad():
-        if needs_grad and model.fp16_mode and model.range_check:
-            word = torch.zeros(1, dtype=torch.int32, device=dev)
-            out = launch(model.packed(probe), status=word)
-            model.fold_status(word, dev, 1)
-            return out
-        return guarded_launch([model], dev, "the sampler's density pass", probe, lambda: launch(model.packed(probe)))
-
-
 def _stratified_sampler(rays_o, rays_d, estimator, model, train, render_step_size, u, u_fine, needs_grad, opts=None):
     """The hierarchical sampler as ONE launch (ops.sample_fused) instead of stratified edges -> packed -> density pass
     -> weights -> resampling -> packed: same edges bit for bit."""
     dev = rays_o.device
     kw = _stratified_args(estimator, model, rays_o.shape[0], dev, u, u_fine, train, opts)
-    edges = _sampler_launch(model, needs_grad, dev, _probe(estimator, rays_o, rays_d),
-                            lambda pm, status=None: ops.sample_fused(pm, rays_o, rays_d, status=status, **kw))
+    edges = sampler_launch(model, needs_grad, dev, _probe(estimator, rays_o, rays_d),
+                           lambda pm, status=None: ops.sample_fused(pm, rays_o, rays_d, status=status, **kw))
     with torch.no_grad():
         return ops.edges_to_packed(edges)
 
@@ -369,7 +354,7 @@ def _occ_sampler(rays_o, rays_d, estimator, model, train, render_step_size, u, u
         # opt-in (NeRF.cull_precision): the cull's density pass in single-pass bf16 - no range flags to guard
         with torch.no_grad():
             return launch(model.packed_cull())
-    return _sampler_launch(model, needs_grad, dev, _probe(estimator, rays_o, rays_d), launch)
+    return sampler_launch(model, needs_grad, dev, _probe(estimator, rays_o, rays_d), launch)
 
 
 def _propnet_sampler(rays_o, rays_d, estimator, model, train, render_step_size, u, u_fine, needs_grad, opts=None):
@@ -548,7 +533,7 @@ def render_rays(rays_o: Tensor, rays_d: Tensor, estimator, model: nn.Module, tra
 
 
 # A frame under the deferred range check is rendered at most this many times: every repeat follows a re-calibration (at
-# most three target moves per set of weights, NeRF._recalibrate) or the switch to bf16x3, which raises no flags.
+# most three target moves per set of weights, ActScaling.recalibrate) or the switch to bf16x3, which raises no flags.
 _FRAME_RERUNS = 6
 
 

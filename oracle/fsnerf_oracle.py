@@ -214,7 +214,7 @@ def nerf_forward(sd: Dict[str, Tensor], x: Tensor, dirs: Optional[Tensor], *,
 
 # ---------------------------------------------------------------- the scaled network (round 4, FSN_PREC_FP16X3U)
 # Restatement of the packer's transformation (csrc/mlp_pack.hpp: fill_scales, pack_piece, aux_value) and of NeRF.calibrate
-# on state dicts: with a power of two s_g = 2^e_g per GEMM (hidden layers 0..L-1, connection, branch) the scaled network's
+# (exponents: core/range_guard.py:choose_exponents) on state dicts: with a power of two s_g = 2^e_g per GEMM (hidden layers 0..L-1, connection, branch) the scaled network's
 # GEMM g produces s_g x the reference's activations and the same outputs (src/core/models.py:111-143), exactly.
 def layer_maxima(sd: Dict[str, Tensor], x: Tensor, dirs: Tensor, *, n_layers: int, skip: Sequence[int], n_freqs: int,
                  n_freqs_dir: int, log_space: bool = True) -> list:
@@ -235,7 +235,7 @@ def layer_maxima(sd: Dict[str, Tensor], x: Tensor, dirs: Tensor, *, n_layers: in
 
 
 def calibrate_exps(maxima: Sequence[float], target_exp: int = 10) -> list:
-    """e_g = target - ceil(log2 max_g): the layer's maximum lands in (2^(target-1), 2^target] (core/models.py:NeRF.calibrate)."""
+    """e_g = target - ceil(log2 max_g): the layer's maximum lands in (2^(target-1), 2^target] (core/range_guard.py:choose_exponents)."""
     import math
     return [0 if v <= 0.0 else max(-60, min(60, target_exp - math.ceil(math.log2(v)))) for v in maxima]
 

@@ -350,11 +350,12 @@ def test_frozen_network_density_gradient_and_null_weights_route():
     # flag are the ones it found (input-only calls keep factors and a range word of their own)
     from fs_nerf_amd import ops
     before = {k: p.grad.clone() for k, p in trainable.named_parameters()}
-    factors, calls, flag = trainable._bwd_stage[0].clone(), trainable._train_calls, ops.step_flag(dev).clone()
+    st = trainable.train_state
+    factors, calls, flag = st.train.stage[0].clone(), st.train.calls, ops.step_flag(dev).clone()
     _, g2 = trainable.density_gradient(x.to(dev))
     assert _rel(g2, gs64) < tol and all(torch.equal(p.grad, before[k]) for k, p in trainable.named_parameters())
-    assert torch.equal(trainable._bwd_stage[0], factors) and trainable._train_calls == calls
-    assert torch.equal(ops.step_flag(dev), flag) and trainable._bwd_stage_inputs is not None
+    assert torch.equal(st.train.stage[0], factors) and st.train.calls == calls
+    assert torch.equal(ops.step_flag(dev), flag) and st.inputs.stage is not None
 
 
 def _wiring_setup(kind, dev):

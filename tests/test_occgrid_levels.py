@@ -502,7 +502,7 @@ def test_zero_rays_with_a_fresh_fp16x3_model(dev, levels):
     step = 2.5e-2  # max_steps <= 2048 at four levels too: the fused routes, which calibrate on the estimator's probe
     for extras in (True, False):
         m, _ = _net(dev)
-        assert m.precision == "fp16x3" and m._act_exps is None
+        assert m.precision == "fp16x3" and m.act_state.exps is None
         assert Rm._rays_route(est, m, None, False, extras, 0, step) == ("occ-extras" if extras else "occ-frame")
         z = torch.zeros(0, 3)
         with torch.no_grad():
@@ -510,7 +510,7 @@ def test_zero_rays_with_a_fresh_fp16x3_model(dev, levels):
                                                       want_extras=extras)
         assert rgb.shape == (0, 3) and op.shape == (0, 1) and dep.shape == (0, 1)
         assert ri is None or ri.numel() == 0
-        assert m._act_exps is not None  # calibrated on the probe of the level boxes
+        assert m.act_state.exps is not None  # calibrated on the probe of the level boxes
 
 
 @pytest.mark.gpu

@@ -477,11 +477,11 @@ def test_scaled_fp16x3_drift_after_calibration_is_detected_and_recalibrated(dev)
             check(m(x, dv), "fresh calibration")
             assert m.calibrations == 1 and m.range_events == 0 and m.precision == "fp16x3"
             for s in (1e3, 1e-9):
-                e_old, ev, cal = list(m._act_exps), m.range_events, m.calibrations
+                e_old, ev, cal = list(m.act_state.exps), m.range_events, m.calibrations
                 drift_(m, s)
                 y = m(x, dv)
                 assert m.precision == "fp16x3" and m.range_events == ev + 1 and m.calibrations == cal + 1, f"drift x{s:g}"
-                shift = [en - eo for en, eo in zip(m._act_exps[:L], e_old[:L])]
+                shift = [en - eo for en, eo in zip(m.act_state.exps[:L], e_old[:L])]
                 assert all(abs(sh + np.log2(s)) <= 1.0 for sh in shift), (s, shift)
                 check(y, f"after a drift of x{s:g}")
                 assert ops.range_ok(dev)
@@ -595,7 +595,7 @@ def test_deferred_single_launch_frame_recalibrates_on_its_own_rays(dev):
     # new weights forget the target moves the old ones needed
     moved = m.act_target_exp
     m.load_state_dict(make_sd(L, D, 43))
-    assert m.act_target_exp == m.ACT_TARGET_EXP and (moved == m.ACT_TARGET_EXP or m._target_moved_by == 0)
+    assert m.act_target_exp == m.ACT_TARGET_EXP and (moved == m.ACT_TARGET_EXP or m.act_state.moved_by == 0)
 
 
 # ------------------------------------------------------------------ BASELINE config 5: bf16 weights / activations

@@ -789,14 +789,14 @@ def test_backward_stage_scales_adapt_and_an_overflowing_stage_is_a_skipped_step(
         return [p.grad.clone() for p in m.parameters()]
 
     g1 = grads(1.0)
-    scales = m._bwd_stage[0].clone()
+    scales = m.train_state.train.stage[0].clone()
     assert float(scales[0]) >= 16.0 * float(scales[L - 1]), scales  # gradients shrink on the way back: earlier layers need more
     g2 = grads(1e-6)  # grad_scale absorbs d(out)'s size: same per-stage factors, gradients scale exactly
-    assert bool((torch.log2(m._bwd_stage[0] / scales).abs() <= 1.0).all())
+    assert bool((torch.log2(m.train_state.train.stage[0] / scales).abs() <= 1.0).all())
     for a, b in zip(g1, g2):
         assert float((a * 1e-6 - b).abs().max()) <= 2e-4 * float(b.abs().max())
     # (b) absurd factors: the next backward overflows and is a skipped step, not a precision fall-back
-    m._bwd_stage[0].fill_(2.0 ** 34)
+    m.train_state.train.stage[0].fill_(2.0 ** 34)
     import warnings
     with warnings.catch_warnings():
         warnings.simplefilter("error", RuntimeWarning)

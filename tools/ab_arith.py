@@ -43,7 +43,7 @@ for name, (pc, pf, c, f) in packs.items():
         x, d = probe()
         for tag, net, pm in (("coarse", c, pc), ("fine", f, pf)):
             mx = ops.mlp_layer_maxima(pm, x, d).cpu().tolist()
-            print(f"{name} {tag}: exps {net._act_exps}  scaled layer maxima {[round(v, 1) for v in mx]}", flush=True)
+            print(f"{name} {tag}: exps {net.act_state.exps}  scaled layer maxima {[round(v, 1) for v in mx]}", flush=True)
 
 
 def run(pc, pf):

@@ -39,7 +39,7 @@ for scaling in (True, False):
     (rgb, opacity, depth, ex), ri, tv = Rm.render_rays(o, d, est, m, train=True, white_bkgd=True, device=dev, u=u.to(dev), u_fine=uf.to(dev))
     torch.nn.functional.mse_loss(rgb, gt.to(dev)).backward()
     print(f"act_scaling={scaling}: t_vals max err vs f64 {float((tv.cpu().double() - wtv).abs().max()):.2e} "
-          f"(f32 oracle e2e: {float(((e32[:, :-1] + e32[:, 1:]) / 2).reshape(-1).double().sub(wtv).abs().max()):.2e})  exps {m._act_exps}")
+          f"(f32 oracle e2e: {float(((e32[:, :-1] + e32[:, 1:]) / 2).reshape(-1).double().sub(wtv).abs().max()):.2e})  exps {m.act_state.exps}")
     res[scaling] = {n: p.grad.clone() for n, p in m.named_parameters()}
 for k in sd:
     print(f"{k:20s} hip scaled {rel(res[True][k], sdg[k].grad):.2e}  hip r3 {rel(res[False][k], sdg[k].grad):.2e}  f32 oracle e2e {rel(sd32[k].grad, sdg[k].grad):.2e}")

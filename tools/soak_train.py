@@ -57,12 +57,12 @@ for name, seed, alpha, norm in (("plain", 22, None, None), ("wnorm_l1", 23, 3e-8
             if it % 100 == 0 or it == iters - 1:
                 losses.append(float(loss.detach()))
         warned = [str(x.message)[:160] for x in w if issubclass(x.category, RuntimeWarning)]
-    sc = [int(round(math.log2(v))) for v in student._bwd_stage[0].tolist()] if student._bwd_stage else None
+    sc = [int(round(math.log2(v))) for v in student.train_state.train.stage[0].tolist()] if student.train_state.train.stage else None
     wmax = {k: float(v.detach().abs().max()) for k, v in student.named_parameters() if k.endswith("weight")}
     out[name] = {"precision_at_end": student.precision, "grad_overflow_looks": student.grad_overflow_looks,
                  "range_warnings": warned, "loss_first": losses[0], "loss_last": losses[-1], "stage_scale_log2": sc,
                  "min_layer_max_weight": min(wmax.values()), "calibrations": student.calibrations,
-                 "range_events": student.range_events, "act_exps": student._act_exps, "act_target_exp": student.act_target_exp,
+                 "range_events": student.range_events, "act_exps": student.act_state.exps, "act_target_exp": student.act_target_exp,
                  "optimizer_steps_applied": opt.steps, "iterations": iters}
     print(name, json.dumps(out[name]), flush=True)
 json.dump(out, open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", "r04_soak.json"), "w"), indent=1)
