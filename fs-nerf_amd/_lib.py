@@ -84,6 +84,9 @@ SIGNATURES = {
     "fsn_ray_patch_batch": (_i, [_vp, _i64, _vp, _i, _i, _i, _d, _i, _d, _i, _i, C.c_uint64, _i64, _vp, _i64, _i64, _i, _i,
                                  _vp, _vp, _vp, _vp, _vp]),
     "fsn_ray_perm_host": (_i, [_i64, C.c_uint64, _i64, _i64, _i64, _vp]),
+    # learnable camera poses (csrc/pose_refine.hip)
+    "fsn_pose_compose": (_i, [_vp, _vp, _i64, _vp, _vp]),
+    "fsn_ray_pose_grad": (_i, [_vp, _vp, _i64, _i, _i, _d, _i, _d, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "fsn_posenc_fwd": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp]),
     "fsn_stratified_edges": (_i, [_f, _f, _i, _i64, _vp, _i, _vp, _vp]),
     "fsn_edges_to_packed": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp]),

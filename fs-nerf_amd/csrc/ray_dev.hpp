@@ -391,15 +391,21 @@ __device__ __forceinline__ void sample_pdf_merge_ray(const float* __restrict__ e
 // Pinhole ray of pixel (h, w) (src/utils/utilities.py:57-80): d_cam = [(w - W/2)/f, -(h - H/2)/f, -1], unit length,
 // rotated by the pose's 3x3 block (row-major [3][4] in m), origin = its last column.  The one definition used by
 // k_get_rays and by the fused render kernel when it generates its own rays.
-__device__ __forceinline__ void pinhole_ray(const float* __restrict__ m, float half_w, float half_h, float focal, int h,
-                                            int w, float (&o)[3], float (&d)[3]) {
+// (pinhole_dir_cam: its unit camera-frame direction alone, for the pose gradient of pose_refine.hip)
+__device__ __forceinline__ void pinhole_dir_cam(float half_w, float half_h, float focal, int h, int w, float (&c)[3]) {
   float dx = ((float)w - half_w) / focal;
   float dy = -((float)h - half_h) / focal;
   float dz = -1.0f;
   const float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
-  dx = dx / nrm;
-  dy = dy / nrm;
-  dz = dz / nrm;
+  c[0] = dx / nrm;
+  c[1] = dy / nrm;
+  c[2] = dz / nrm;
+}
+__device__ __forceinline__ void pinhole_ray(const float* __restrict__ m, float half_w, float half_h, float focal, int h,
+                                            int w, float (&o)[3], float (&d)[3]) {
+  float c[3];
+  pinhole_dir_cam(half_w, half_h, focal, h, w, c);
+  const float dx = c[0], dy = c[1], dz = c[2];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     d[k] = (dx * m[4 * k + 0] + dy * m[4 * k + 1]) + dz * m[4 * k + 2];
@@ -422,6 +428,27 @@ __device__ __forceinline__ void ndc_ray(float (&o)[3], float (&d)[3], float sx, 
   d[0] = sx * (dx / dz - ox / oz);
   d[1] = sy * (dy / dz - oy / oz);
   d[2] = -two_near / oz;
+}
+
+// The backward of ndc_ray: (o, d) the WORLD ray it was given, (go, gd) = dL/d(its outputs) on entry and dL/d(o, d) on
+// return.  The forward's intermediates are formed again with its own operations; the chain is the plain reverse sweep
+// (the intersection p = o + t d is kept a function of its inputs, as autograd through the forward keeps it).
+__device__ __forceinline__ void ndc_ray_bwd(const float (&o)[3], const float (&d)[3], float sx, float sy, float near,
+                                            float two_near, float (&go)[3], float (&gd)[3]) {
+  const float dx = d[0], dy = d[1], dz = d[2];
+  const float t = -(near + o[2]) / dz;
+  const float px = o[0] + t * dx, py = o[1] + t * dy, pz = o[2] + t * dz;
+  const float ux = sx * (go[0] - gd[0]), uy = sy * (go[1] - gd[1]), uz = two_near * (go[2] - gd[2]);
+  const float gpx = ux / pz, gpy = uy / pz;
+  const float gpz = -((ux * px + uy * py) + uz) / (pz * pz);
+  const float bx = sx * gd[0], by = sy * gd[1];
+  const float gt = (gpx * dx + gpy * dy) + gpz * dz;  // dL/dt through p = o + t d
+  go[0] = gpx;
+  go[1] = gpy;
+  go[2] = gpz - gt / dz;  // t = -(near + o_z) / d_z
+  gd[0] = bx / dz + t * gpx;
+  gd[1] = by / dz + t * gpy;
+  gd[2] = (t * gpz - (bx * dx + by * dy) / (dz * dz)) - gt * t / dz;
 }
 
 // edge i of the fixed-count stratified sampler (oracle.stratified_edges)

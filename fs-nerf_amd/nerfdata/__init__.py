@@ -1,3 +1,4 @@
 """The reference's data layer (src/nerfdata) on the device: uint8 images and poses resident, every batch one launch;
-PatchLoader: batches of P x P pixel patches over the same dataset."""
+PatchLoader: batches of P x P pixel patches over the same dataset; CameraRefiner: learnable poses behind both loaders."""
+from .pose_refine import CameraRefiner, pose_error  # noqa: F401
 from .raydata import FrameLoader, PatchLoader, RayDataset, RayLoader  # noqa: F401

@@ -82,10 +82,12 @@ class RayDataset:
         return self.imgs.shape[0] * self.imgs.shape[1] * self.imgs.shape[2]
 
     def batch(self, order: str, *, start: int = 0, count: Optional[int] = None, seed: int = 0, epoch: int = 0,
-              indices: Optional[Tensor] = None, want_rays: bool = True, want_rgb: bool = True, want_index: bool = False):
-        """ops.ray_batch on this dataset's tensors: (rays_o, rays_d, rgb, index), None where not wanted."""
+              indices: Optional[Tensor] = None, want_rays: bool = True, want_rgb: bool = True, want_index: bool = False,
+              poses12: Optional[Tensor] = None):
+        """ops.ray_batch on this dataset's tensors: (rays_o, rays_d, rgb, index), None where not wanted.
+        poses12: other [n,12] matrices than the stored ones (CameraRefiner.poses12())."""
         H, W, focal = self.hwf
-        return ops.ray_batch(self.poses12, self.imgs, H, W, focal, ndc=self.ndc, near=_NDC_NEAR, white_bkgd=self.white_bkgd,
+        return ops.ray_batch(self.poses12 if poses12 is None else poses12, self.imgs, H, W, focal, ndc=self.ndc, near=_NDC_NEAR, white_bkgd=self.white_bkgd,
                              order=order, seed=seed, epoch=epoch, indices=indices, start=start, count=count,
                              want_rays=want_rays, want_rgb=want_rgb, want_index=want_index)
 
@@ -103,13 +105,14 @@ class RayDataset:
 
     def patch_batch(self, order: str, patch: int, dilation: int = 1, *, start: int = 0, count: Optional[int] = None,
                     seed: int = 0, epoch: int = 0, anchors: Optional[Tensor] = None, want_rays: bool = True,
-                    want_rgb: bool = True, want_index: bool = False):
+                    want_rgb: bool = True, want_index: bool = False, poses12: Optional[Tensor] = None):
         """ops.ray_patch_batch on this dataset's tensors: `count` patches of `patch` x `patch` pixels from position
         `start` of `order` over the n_anchors(patch, dilation) anchors -> (rays_o, rays_d, rgb, index) of
-        count * patch^2 rows, patch after patch, row-major inside a patch; None where not wanted."""
+        count * patch^2 rows, patch after patch, row-major inside a patch; None where not wanted.
+        poses12: as batch()."""
         self.n_anchors(patch, dilation)
         H, W, focal = self.hwf
-        return ops.ray_patch_batch(self.poses12, self.imgs, H, W, focal, patch, dilation, ndc=self.ndc, near=_NDC_NEAR,
+        return ops.ray_patch_batch(self.poses12 if poses12 is None else poses12, self.imgs, H, W, focal, patch, dilation, ndc=self.ndc, near=_NDC_NEAR,
                                    white_bkgd=self.white_bkgd, order=order, seed=seed, epoch=epoch, anchors=anchors,
                                    start=start, count=count, want_rays=want_rays, want_rgb=want_rgb, want_index=want_index)
 
@@ -148,12 +151,21 @@ class RayLoader:
     every rank makes the same number of steps.
 
     state_dict() = (seed, epoch, next position); after load_state_dict() the next iter() continues that epoch at that
-    position with the very batches the original would have served."""
+    position with the very batches the original would have served.
+
+    cameras (a CameraRefiner over this dataset's views; None: the stored poses, the code path above): the same one
+    launch runs over cameras.poses12(), and rays_o / rays_d come out of one autograd Function whose backward is one
+    fsn_ray_pose_grad launch into cameras.xi.grad (pose_refine.py); still no host synchronisation.  Intrinsics and the
+    dataset's region of interest (aabb) stay those of the stored poses."""
 
     def __init__(self, dataset: RayDataset, batch_size: int, shuffle: bool = True, seed: Optional[int] = None, rank: int = 0,
-                 world: int = 1, with_index: bool = False):
+                 world: int = 1, with_index: bool = False, cameras=None):
         if batch_size <= 0 or world <= 0 or not 0 <= rank < world:
             raise ValueError(f"RayLoader: bad batch_size {batch_size}, rank {rank} or world {world}")
+        if cameras is not None and (cameras.n_views != dataset.n_views or cameras.poses0.device != dataset.device):
+            raise ValueError(f"RayLoader: cameras of {cameras.n_views} views on {cameras.poses0.device} do not match the "
+                             f"dataset's {dataset.n_views} views on {dataset.device}")
+        self.cameras = cameras
         self.dataset, self.batch_size, self.shuffle = dataset, int(batch_size), bool(shuffle)
         self.seed = _seed_or_default(seed)
         self.rank, self.world, self.with_index = int(rank), int(world), bool(with_index)
@@ -167,7 +179,14 @@ class RayLoader:
 
     def _serve(self, order: str, start: int, count: int, epoch: int):
         """The one launch of a next(): `count` items from position `start` of this epoch's order."""
+        if self.cameras is not None:
+            return self._serve_refined(lambda poses12: self.dataset.batch(
+                order, start=start, count=count, seed=self.seed, epoch=epoch, want_index=True, poses12=poses12))
         return self.dataset.batch(order, start=start, count=count, seed=self.seed, epoch=epoch, want_index=self.with_index)
+
+    def _serve_refined(self, launch):
+        ds = self.dataset
+        return self.cameras.served((ds.hwf[0], ds.hwf[1], ds.hwf[2], ds.ndc, _NDC_NEAR), launch)
 
     def __len__(self) -> int:
         n, stride = self._n_items(), self.batch_size * self.world
@@ -216,11 +235,11 @@ class PatchLoader(RayLoader):
     `dilation` apart, patch after patch, so rgb.view(B, patch, patch, 3) is the patch stack.  RayLoader's contract holds
     over the ANCHORS (top-left pixels, dataset.n_anchors(patch, dilation) of them): a new permutation per iter(), every
     anchor exactly once per epoch, a short last batch, the world / rank slices, state_dict() / load_state_dict().
-    ValueError for a patch that does not fit the images."""
+    ValueError for a patch that does not fit the images.  cameras: as RayLoader."""
 
     def __init__(self, dataset: RayDataset, patch: int, patches_per_batch: int, dilation: int = 1, shuffle: bool = True,
-                 seed: Optional[int] = None, rank: int = 0, world: int = 1, with_index: bool = False):
-        super().__init__(dataset, patches_per_batch, shuffle, seed, rank, world, with_index)
+                 seed: Optional[int] = None, rank: int = 0, world: int = 1, with_index: bool = False, cameras=None):
+        super().__init__(dataset, patches_per_batch, shuffle, seed, rank, world, with_index, cameras)
         self.patch, self.dilation = int(patch), int(dilation)
         self._anchors = dataset.n_anchors(self.patch, self.dilation)
 
@@ -228,6 +247,10 @@ class PatchLoader(RayLoader):
         return self._anchors
 
     def _serve(self, order: str, start: int, count: int, epoch: int):
+        if self.cameras is not None:
+            return self._serve_refined(lambda poses12: self.dataset.patch_batch(
+                order, self.patch, self.dilation, start=start, count=count, seed=self.seed, epoch=epoch, want_index=True,
+                poses12=poses12))
         return self.dataset.patch_batch(order, self.patch, self.dilation, start=start, count=count, seed=self.seed,
                                         epoch=epoch, want_index=self.with_index)
 

@@ -278,6 +278,48 @@ def ray_perm_host(n: int, seed: int, epoch: int, start: int = 0, count: Optional
     return out
 
 
+def _pose_pair(poses0: Tensor, xi: Tensor, who: str) -> None:
+    """The stored poses [n,12] and their corrections [n,6] as the pose kernels read them: nothing is cast or copied
+    (xi is a parameter: a conversion would hide it from the caller)."""
+    if not (poses0.is_cuda and xi.is_cuda):
+        raise RuntimeError(f"{who}: expected GPU tensors (the HIP path has no CPU fallback)")
+    if poses0.dtype != torch.float32 or xi.dtype != torch.float32:
+        raise TypeError(f"{who}: poses and xi are float32, got {poses0.dtype} and {xi.dtype}")
+    if poses0.dim() != 2 or poses0.shape[1] != 12 or tuple(xi.shape) != (poses0.shape[0], 6):
+        raise ValueError(f"{who}: poses are [n,12] and xi [n,6], got {tuple(poses0.shape)} and {tuple(xi.shape)}")
+    if not (poses0.is_contiguous() and xi.is_contiguous()) or poses0.device != xi.device:
+        raise ValueError(f"{who}: poses and xi are contiguous tensors of one device")
+
+
+def pose_compose(poses0: Tensor, xi: Tensor) -> Tensor:
+    """The corrected poses [n,12] = [exp([omega]x) R0 | t0 + tau] of the stored poses0 [n,12] and xi = (omega, tau)
+    [n,6] in ONE launch (fsn_pose_compose)."""
+    _pose_pair(poses0, xi, "pose_compose")
+    xi = xi.detach()
+    out = torch.empty_like(poses0)
+    _launch("fsn_pose_compose", poses0.device, _p(poses0), _p(xi), poses0.shape[0], _p(out))
+    return out
+
+
+def ray_pose_grad(poses0: Tensor, xi: Tensor, H: int, W: int, focal: float, index: Tensor, grad_o: Optional[Tensor],
+                  grad_d: Optional[Tensor], *, ndc: bool = False, near: float = 1.0, want_pose_grad: bool = False):
+    """dL/dxi [n,6] from the gradients of a batch's rays in ONE deterministic launch (fsn_ray_pose_grad): `index`
+    [count] int64 are the batch's flat ray indices (ray_batch's `index` output), grad_o / grad_d [count,3] = dL/drays_o,
+    dL/drays_d (None = zeros) of the rays served over pose_compose(poses0, xi).  A view without a ray gets exactly 0.
+    want_pose_grad: -> (grad_xi, dL/d(corrected poses) [n,12])."""
+    _pose_pair(poses0, xi, "ray_pose_grad")
+    xi = xi.detach()
+    index = _i64(index, "index").reshape(-1)
+    count, dev = index.numel(), poses0.device
+    grad_o = _flat(grad_o, "grad_o", 3 * count)
+    grad_d = _flat(grad_d, "grad_d", 3 * count)
+    grad_xi = torch.empty_like(xi)
+    grad_poses = torch.empty_like(poses0) if want_pose_grad else None
+    _launch("fsn_ray_pose_grad", dev, _p(poses0), _p(xi), poses0.shape[0], int(H), int(W), float(focal), 1 if ndc else 0,
+            float(near), _p(index), _p(grad_o), _p(grad_d), count, _p(grad_xi), _p(grad_poses))
+    return (grad_xi, grad_poses) if want_pose_grad else grad_xi
+
+
 def to_ndc(rays_o: Tensor, rays_d: Tensor, H: int, W: int, focal: float, near: float) -> Tuple[Tensor, Tensor]:
     o, d = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d")
     n = o.numel() // 3

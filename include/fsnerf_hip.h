@@ -79,6 +79,7 @@ int fsn_version(void);
  *   "metrics"    metrics.hip     every LDS index of k_ssim_tile
  *   "ssim_grad"  ssim_grad.hip   every LDS index of the two kernels behind the SSIM gradient
  *   "lpips"      lpips.hip       every LDS index of k_lpips_conv and k_lpips_first_bwd
+ *   "pose_refine" pose_refine.hip  ray indices outside [0, N) handed to fsn_ray_pose_grad
  * A record is 4 uint32 = {violations, source line of the first, its index (or the end of its span), the extent}, the
  * last two truncated to 32 bits.  fsn_debug_report synchronises the device, copies the record of `unit` to out4 and
  * clears it; an unknown unit is FSN_E_INVALID (the message lists the known ones), the release library returns
@@ -156,6 +157,28 @@ int fsn_ray_patch_batch(const float* poses, int64_t n_views, const uint8_t* imag
 /* The same permutation on the host (plain C++, no device is touched): out_host[i] = perm(start + i; N, seed, epoch) for
  * i < count, start + count <= N <= 2^62. */
 int fsn_ray_perm_host(int64_t N, uint64_t seed, int64_t epoch, int64_t start, int64_t count, int64_t* out_host);
+
+/* ---- learnable camera poses behind the data layer (this package's own)       csrc/pose_refine.hip
+ * View v carries a correction xi_v = (omega_v, tau_v) (6 floats) on top of its stored pose [R0_v | t0_v]:
+ *   R_v = exp([omega_v]x) R0_v (left-multiplied, world frame),  t_v = t0_v + tau_v,
+ *   exp([omega]x) = I + A K + B K^2,  K = [omega]x,  A = sin(theta) / theta,  B = (1 - cos(theta)) / theta^2,  theta = |omega|
+ * (Taylor forms below theta = 0.125; supported range theta < pi).  xi = 0 gives the stored pose back value for value.
+ * fsn_pose_compose: poses0 [n, 12], xi [n, 6] -> poses_out [n, 12] (all DEVICE), one thread per view: the matrices that
+ * fsn_ray_batch / fsn_ray_patch_batch are then launched over.
+ * Errors (FSN_E_INVALID): n < 0, a null pointer. */
+int fsn_pose_compose(const float* poses0, const float* xi, int64_t n, float* poses_out, fsn_stream_t stream);
+/* The backward of "flat ray index -> ray of the corrected pose" (the rays fsn_ray_batch serves over fsn_pose_compose's
+ * matrices, NDC map included when `ndc` is set; H, W, focal, ndc, near as there), reduced per view in ONE launch:
+ * index [count] int64 (the batch's flat ray indices), grad_o / grad_d [count, 3] = dL/drays_o, dL/drays_d (either may be
+ * NULL = zeros) -> grad_xi [n_views, 6] = (dL/domega, dL/dtau), WRITTEN (not accumulated) for every view: exactly 0 for
+ * a view without a ray in the batch.  grad_poses [n_views, 12] (may be NULL): dL/d(the corrected 3x4 matrices).
+ * No atomics and a fixed summation order: the same inputs give the same bits.  An index outside [0, n_views*H*W)
+ * contributes nothing (and, in the debug build, is recorded for fsn_debug_report("pose_refine")).
+ * Errors (FSN_E_INVALID): n_views < 0, H, W or focal <= 0, count < 0, null poses0 / xi / grad_xi, null index with
+ * count > 0; FSN_E_UNSUPPORTED: H*W or n_views of 2^31 or more. */
+int fsn_ray_pose_grad(const float* poses0, const float* xi, int64_t n_views, int H, int W, double focal, int ndc,
+                      double near, const int64_t* index, const float* grad_o, const float* grad_d, int64_t count,
+                      float* grad_xi, float* grad_poses, fsn_stream_t stream);
 
 /* ---- a4: PositionalEncoder.forward(x)                    src/core/models.py:43-50
  * x [n, d_in] -> out [n, d_in*(1+2*n_freqs)], block order x, sin f0, cos f0, sin f1, ...
