@@ -261,7 +261,7 @@ class _WeightNormFn(torch.autograd.Function):
         nws = ops._size("fsn_weight_norm_workspace_floats", None, n, len_t)
         ws = torch.empty(nws, device=flat.device, dtype=torch.float32)
         out = torch.empty(1, device=flat.device, dtype=torch.float32)
-        ops._launch("fsn_weight_norm_fwd", flat.device, ops._p(flat), n, off_t, len_t, int(reg.l2), ops._p(ws), ops._p(out))
+        ops._launch("fsn_weight_norm_fwd", flat.device, flat, n, off_t, len_t, int(reg.l2), ws, out)
         ctx.reg, ctx.flat, ctx.ws, ctx.tabs, ctx.shapes = reg, flat, ws, (n, off_t, len_t, offs, lens), [p.shape for p in params]
         return out.reshape(())
 
@@ -271,8 +271,7 @@ class _WeightNormFn(torch.autograd.Function):
         flat = ctx.flat
         g = torch.zeros_like(flat)
         d = d_out.reshape(1).to(torch.float32).contiguous()
-        ops._launch("fsn_weight_norm_bwd", flat.device, ops._p(flat), n, off_t, len_t, int(ctx.reg.l2), ops._p(ctx.ws),
-                    ops._p(d), ops._p(g))
+        ops._launch("fsn_weight_norm_bwd", flat.device, flat, n, off_t, len_t, int(ctx.reg.l2), ctx.ws, d, g)
         return (None,) + tuple(g[o:o + ln].view(sh) for o, ln, sh in zip(offs, lens, ctx.shapes))
 
 

@@ -109,10 +109,10 @@ class FusedAdam(torch.optim.Optimizer):
         self.arena.grads.bind()
         a = self.arena
         flag = a.grads.step_flag  # the word of THIS optimizer's parameters (shard.FlatGrads), not a per-device one
-        ops._launch("fsn_adam_step_dev", a.flat.device, ops._p(a.flat), ops._p(a.grads.flat), ops._p(self.exp_avg),
-                    ops._p(self.exp_avg_sq), a.numel, ops._p(self.step_count), ops._p(self._tick), float(g["lr"]),
+        ops._launch("fsn_adam_step_dev", a.flat.device, a.flat, a.grads.flat, self.exp_avg, self.exp_avg_sq, a.numel,
+                    self.step_count, self._tick, float(g["lr"]),
                     float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), float(grad_div),
-                    ops._p(flag), ops._p(a.grads.flag_slot))
+                    flag, a.grads.flag_slot)
         flag.zero_()  # the step's flag is consumed (stream order: after the launch that read it)
         a.grads.flag_slot.zero_()
         self._bump_versions()

@@ -4,9 +4,11 @@ No function in this module computes anything on the CPU.
 
 A wrapper has one shape: convert the inputs, allocate the outputs, `_launch(symbol, device, *args)`.  `_launch` is the one
 door to a C entry point that takes a stream, `_size` the door of the size queries, `_Held` the argument struct that owns
-its tensors (DESIGN.md section 1 has the two rules they enforce)."""
+its tensors.  The door takes tensors where the header has device pointers and checks each against the declared pointee
+(DESIGN.md section 1 has the rules they enforce)."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -29,22 +31,94 @@ launch_timer: Optional[list] = None
 clock_buffer: Optional[Tensor] = None
 
 
+# What a device pointer of the header points at, as torch holds it: width and kind.  Signedness is ignored (torch callers
+# keep `status`, `bits` and `pending` as int32); void: any dtype.
+_POINTEE_DTYPE = {"float": torch.float32, "double": torch.float64, "int64_t": torch.int64, "uint64_t": torch.int64,
+                  "int32_t": torch.int32, "uint32_t": torch.int32, "uint8_t": torch.uint8, "void": None}
+
+
+def _tensor_plan(params) -> tuple:
+    """Where an entry point takes a tensor: (position, name, dtype, strided) of every device data pointer among its
+    `params` (not the `*_host` ones, pointer arrays and structs).  strided: the header reads it through the element
+    strides `<name>_strides_host`, so any view will do."""
+    names = {p.name for p in params}
+    return tuple((i, p.name, _POINTEE_DTYPE[p.pointee], p.name + "_strides_host" in names) for i, p in enumerate(params)
+                 if p.pointee in _POINTEE_DTYPE and not p.name.endswith("_host"))
+
+
+# built once, from the header (L.FUNCTIONS / L.STRUCTS): per symbol its argument count and tensor plan, per argument
+# struct the dtype behind each pointer field
+_PLANS = {name: (len(params), _tensor_plan(params)) for name, (_, params) in L.FUNCTIONS.items()}
+_FIELDS = {s: {f.name: _POINTEE_DTYPE[f.pointee] for f in s.fields if f.pointee in _POINTEE_DTYPE}
+           for s in L.STRUCTS.values()}
+
+
+_NO_GUARD = contextlib.nullcontext()
+
+
+def _index(dev) -> Optional[int]:
+    """The index of the GPU `dev` names ("cuda" without one: the current device, as the guard reads it); None where
+    there is no GPU to compare with (a size query without a device; a CPU device, which `_addr` then refuses)."""
+    if dev is None:
+        return None
+    dev = dev if isinstance(dev, torch.device) else torch.device(dev)
+    if dev.type != "cuda":
+        return None
+    return torch.cuda.current_device() if dev.index is None else dev.index
+
+
+def _addr(t: Tensor, dtype, strided: bool, idx: Optional[int], what: str, param: str) -> int:
+    """The door's rule for a tensor behind a device pointer -> its address: on the GPU (number `idx`, where one is given),
+    of the pointee's dtype, contiguous unless read through strides.  It checks; it never casts or copies."""
+    if not t.is_cuda:
+        raise RuntimeError(f"{what}: {param}: expected a GPU tensor (the HIP path has no CPU fallback)")
+    if dtype is not None and t.dtype != dtype:
+        raise TypeError(f"{what}: {param}: expected {dtype} (include/fsnerf_hip.h), got {t.dtype}")
+    if not (strided or t.is_contiguous()):
+        raise ValueError(f"{what}: {param}: expected a contiguous tensor")
+    if idx is not None and t.get_device() != idx:
+        raise RuntimeError(f"{what}: {param}: the tensor is on {t.device}, the call on GPU {idx}")
+    return t.data_ptr()
+
+
+def _door(name: str, dev, args: tuple, n_more: int = 0) -> Tuple[list, Optional[int]]:
+    """`args` as the C function takes them: a tensor where the header has a device data pointer becomes its address,
+    checked by `_addr`; None stays NULL; ctypes arrays, byref(...) and pointer arrays pass through.  The caller's
+    `args` keeps every tensor referenced until the call is enqueued.  -> (arguments, `_index(dev)`)."""
+    n, plan = _PLANS[name]
+    if len(args) + n_more != n:
+        raise TypeError(f"{name}: takes {n - n_more} arguments (include/fsnerf_hip.h), got {len(args)}")
+    args, idx = list(args), _index(dev)
+    for i, param, dtype, strided in plan:
+        t = args[i]
+        if t is not None and isinstance(t, Tensor):
+            # (the per-call path: `_addr`'s tests in one expression - a CPU tensor's get_device() is -1; it is called
+            # where one fails, to say which, and where there is no device to compare with)
+            if t.get_device() != idx or (dtype is not None and t.dtype != dtype) or not (strided or t.is_contiguous()):
+                _addr(t, dtype, strided, idx, name, param)
+            args[i] = t.data_ptr()
+    return args, idx
+
+
 def _launch(name: str, dev, *args, what: Optional[str] = None, timed: bool = False, counts: bool = False) -> int:
     """The one door to a C entry point that takes a stream: `name(*args, stream)` under the device guard of `dev` (the
     tensors' device), with the stream handle read INSIDE the guard - outside it the handle is the current device's, not
-    theirs.  `what`: the error's text where it says more than the symbol.  `timed`: the `launch_timer` bracket.
-    `counts`: the symbol returns a count (> 0) instead of a status code; -> that value."""
+    theirs; where that device is the current one already the guard would change nothing and is not entered.  Tensors go
+    in as they are (`_door`).  `what`: the error's text where it says more than the symbol.
+    `timed`: the `launch_timer` bracket.  `counts`: the symbol returns a count (> 0) instead of a status code; -> that
+    value."""
     fn = getattr(L.lib(), name)
-    with torch.cuda.device(dev):
+    cargs, idx = _door(name, dev, args, 1)
+    with _NO_GUARD if idx == torch.cuda.current_device() else torch.cuda.device(dev):
         stream = torch.cuda.current_stream().cuda_stream
         if timed and launch_timer is not None:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            rc = fn(*args, stream)
+            rc = fn(*cargs, stream)
             e1.record()
             launch_timer.append((e0, e1))
         else:
-            rc = fn(*args, stream)
+            rc = fn(*cargs, stream)
     if counts:
         if rc <= 0:
             L.check(rc if rc < 0 else -3, what or name)
@@ -58,11 +132,12 @@ def _size(name: str, dev, *args) -> int:
     value is an error code and raises.  `dev`: the device the answer is for (fsn_nerf_train_workspace_floats looks at
     its compute units), None where the arguments alone decide."""
     fn = getattr(L.lib(), name)
+    cargs, _ = _door(name, dev, args)
     if dev is None:
-        n = int(fn(*args))
+        n = int(fn(*cargs))
     else:
         with torch.cuda.device(dev):
-            n = int(fn(*args))
+            n = int(fn(*cargs))
     if n < 0:
         L.check(n, name)
     return n
@@ -111,6 +186,9 @@ def _i64(t: Tensor, name: str) -> Tensor:
 
 
 def _p(t: Optional[Tensor]):
+    """The bare address of a tensor, for a direct C-ABI call that does not go through the door: the test-only binding
+    of tests/ref_fp32 (a library without a header) and tests that call two entry points side by side.  No wrapper of
+    this package uses it; handed to `_launch` it passes through unchecked, like any ctypes object."""
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
@@ -125,19 +203,17 @@ class _Held:
     """An argument struct `a` and the tensors its pointers name.  A tensor a conversion made (`_f32` of a float64 mask,
     a reshaped `u`) must stay referenced until the call is enqueued: the outputs are allocated after it, and the caching
     allocator hands a dropped temporary's block to the next torch.empty of its size class.  So a pointer enters the
-    struct (`set`) or the argument list (`p`) only through the holder, which the wrapper keeps until it returns."""
+    struct only through `set`, which checks the tensor against the field's declared pointee (`_addr`: the door's rule;
+    the GPU's index once `_ray_source` knows it), and the wrapper keeps the holder until it returns."""
 
     def __init__(self, a: C.Structure):
-        self.a, self.tensors = a, []
+        self.a, self.tensors, self.idx = a, [], None
 
     def set(self, field: str, t: Optional[Tensor]) -> None:
         if t is not None:
             self.tensors.append(t)
-            setattr(self.a, field, t.data_ptr())
-
-    def p(self, t: Optional[Tensor]):
-        self.tensors.append(t)
-        return _p(t)
+            kind = type(self.a)
+            setattr(self.a, field, _addr(t, _FIELDS[kind][field], False, self.idx, kind.__name__, field))
 
 
 def _ray_source(h: _Held, rays_o: Optional[Tensor], rays_d: Optional[Tensor], camera) -> Tuple[int, torch.device]:
@@ -146,12 +222,12 @@ def _ray_source(h: _Held, rays_o: Optional[Tensor], rays_d: Optional[Tensor], ca
     a = h.a
     if camera is None:
         o, d = _f32(rays_o, "rays_o").reshape(-1, 3), _f32(rays_d, "rays_d").reshape(-1, 3)
-        a.R = o.shape[0]
+        a.R, h.idx = o.shape[0], _index(o.device)
         h.set("rays_o", o)
         h.set("rays_d", d)
         return o.shape[0], o.device
     pose, cH, cW, cfocal, crow0, cnrows, dev = camera
-    a.R = int(cnrows) * int(cW)
+    a.R, h.idx = int(cnrows) * int(cW), _index(dev)
     pm = pose.detach().to("cpu", torch.float32)[:3, :4].contiguous().reshape(-1).tolist()
     for i in range(12):
         a.cam_pose[i] = pm[i]
@@ -177,7 +253,7 @@ def get_rays(pose: Tensor, H: int, W: int, focal: float, device, row0: int = 0,
     else:
         o, d = out
         assert o.is_contiguous() and d.is_contiguous() and o.shape == (nrows * W, 3) and d.shape == o.shape
-    _launch("fsn_get_rays", o.device, pose_host, H, W, float(focal), row0, nrows, _p(o), _p(d))
+    _launch("fsn_get_rays", o.device, pose_host, H, W, float(focal), row0, nrows, o, d)
     return o, d
 
 
@@ -192,8 +268,7 @@ def build_rays(poses: Tensor, H: int, W: int, focal: float, device, ndc: bool = 
     d = torch.empty_like(o)
     aabb = torch.empty(6, device=P.device, dtype=torch.float32) if want_aabb else None
     keys = torch.empty(6, device=P.device, dtype=torch.int32) if want_aabb else None
-    _launch("fsn_build_rays", P.device, _p(P), n, int(H), int(W), float(focal), 1 if ndc else 0, float(near), _p(o), _p(d),
-            _p(aabb), _p(keys))
+    _launch("fsn_build_rays", P.device, P, n, int(H), int(W), float(focal), 1 if ndc else 0, float(near), o, d, aabb, keys)
     return o, d, aabb
 
 
@@ -223,9 +298,9 @@ def ray_batch(poses12: Tensor, images: Tensor, H: int, W: int, focal: float, *, 
     d = torch.empty(count, 3, device=dev, dtype=torch.float32) if want_rays else None
     rgb = torch.empty(count, 3, device=dev, dtype=torch.float32) if want_rgb else None
     index = torch.empty(count, device=dev, dtype=torch.int64) if want_index else None
-    _launch("fsn_ray_batch", dev, _p(poses12), poses12.shape[0], _p(images), int(H), int(W), images.shape[3], float(focal),
+    _launch("fsn_ray_batch", dev, poses12, poses12.shape[0], images, int(H), int(W), images.shape[3], float(focal),
             1 if ndc else 0, float(near), 1 if white_bkgd else 0, _RAY_ORDERS[order], int(seed) & 0xFFFFFFFFFFFFFFFF,
-            int(epoch), _p(indices), int(start), int(count), _p(o), _p(d), _p(rgb), _p(index))
+            int(epoch), indices, int(start), int(count), o, d, rgb, index)
     return o, d, rgb, index
 
 
@@ -262,9 +337,9 @@ def ray_patch_batch(poses12: Tensor, images: Optional[Tensor], H: int, W: int, f
     d = torch.empty(rows, 3, device=dev, dtype=torch.float32) if want_rays else None
     rgb = torch.empty(rows, 3, device=dev, dtype=torch.float32) if want_rgb else None
     index = torch.empty(rows, device=dev, dtype=torch.int64) if want_index else None
-    _launch("fsn_ray_patch_batch", dev, _p(poses12), poses12.shape[0], _p(images), int(H), int(W), channels, float(focal),
+    _launch("fsn_ray_patch_batch", dev, poses12, poses12.shape[0], images, int(H), int(W), channels, float(focal),
             1 if ndc else 0, float(near), 1 if white_bkgd else 0, _RAY_ORDERS[order], int(seed) & 0xFFFFFFFFFFFFFFFF,
-            int(epoch), _p(anchors), int(start), int(count), int(patch), int(dilation), _p(o), _p(d), _p(rgb), _p(index))
+            int(epoch), anchors, int(start), int(count), int(patch), int(dilation), o, d, rgb, index)
     return o, d, rgb, index
 
 
@@ -297,7 +372,7 @@ def pose_compose(poses0: Tensor, xi: Tensor) -> Tensor:
     _pose_pair(poses0, xi, "pose_compose")
     xi = xi.detach()
     out = torch.empty_like(poses0)
-    _launch("fsn_pose_compose", poses0.device, _p(poses0), _p(xi), poses0.shape[0], _p(out))
+    _launch("fsn_pose_compose", poses0.device, poses0, xi, poses0.shape[0], out)
     return out
 
 
@@ -315,8 +390,8 @@ def ray_pose_grad(poses0: Tensor, xi: Tensor, H: int, W: int, focal: float, inde
     grad_d = _flat(grad_d, "grad_d", 3 * count)
     grad_xi = torch.empty_like(xi)
     grad_poses = torch.empty_like(poses0) if want_pose_grad else None
-    _launch("fsn_ray_pose_grad", dev, _p(poses0), _p(xi), poses0.shape[0], int(H), int(W), float(focal), 1 if ndc else 0,
-            float(near), _p(index), _p(grad_o), _p(grad_d), count, _p(grad_xi), _p(grad_poses))
+    _launch("fsn_ray_pose_grad", dev, poses0, xi, poses0.shape[0], int(H), int(W), float(focal), 1 if ndc else 0, float(near),
+            index, grad_o, grad_d, count, grad_xi, grad_poses)
     return (grad_xi, grad_poses) if want_pose_grad else grad_xi
 
 
@@ -324,7 +399,7 @@ def to_ndc(rays_o: Tensor, rays_d: Tensor, H: int, W: int, focal: float, near: f
     o, d = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d")
     n = o.numel() // 3
     no, nd = torch.empty_like(o), torch.empty_like(d)
-    _launch("fsn_to_ndc", o.device, _p(o), _p(d), n, H, W, float(focal), float(near), _p(no), _p(nd))
+    _launch("fsn_to_ndc", o.device, o, d, n, H, W, float(focal), float(near), no, nd)
     return no, nd
 
 
@@ -336,7 +411,7 @@ def posenc(x: Tensor, freqs: Sequence[float], mask: Optional[Tensor] = None) -> 
     out = torch.empty(*x.shape[:-1], d_in * (1 + 2 * nf), device=x.device, dtype=torch.float32)
     fr = (C.c_float * max(nf, 1))(*[float(f) for f in freqs])
     m = _opt_f32(mask, "mask")
-    _launch("fsn_posenc_fwd", x.device, _p(x), n, d_in, nf, fr, _p(m), _p(out))
+    _launch("fsn_posenc_fwd", x.device, x, n, d_in, nf, fr, m, out)
     return out
 
 
@@ -355,7 +430,7 @@ def _u_mode(u: Optional[Tensor], R: int, S: int) -> Tuple[int, Optional[Tensor]]
 def stratified_edges(near: float, far: float, S: int, R: int, u: Optional[Tensor], device) -> Tensor:
     mode, u = _u_mode(u, R, S)
     edges = torch.empty(R, S + 1, device=device, dtype=torch.float32)
-    _launch("fsn_stratified_edges", edges.device, float(near), float(far), S, R, _p(u), mode, _p(edges))
+    _launch("fsn_stratified_edges", edges.device, float(near), float(far), S, R, u, mode, edges)
     return edges
 
 
@@ -365,7 +440,7 @@ def edges_to_packed(edges: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
     ri = torch.empty(R * S, device=edges.device, dtype=torch.int64)
     t0 = torch.empty(R * S, device=edges.device, dtype=torch.float32)
     t1 = torch.empty_like(t0)
-    _launch("fsn_edges_to_packed", edges.device, _p(edges), R, S, _p(ri), _p(t0), _p(t1))
+    _launch("fsn_edges_to_packed", edges.device, edges, R, S, ri, t0, t1)
     return ri, t0, t1
 
 
@@ -375,7 +450,7 @@ def sample_pdf_merge(edges: Tensor, weights: Tensor, n_imp: int, u: Optional[Ten
     assert edges.shape == (R, S + 1)
     u = _opt_f32(u, "u")
     out = torch.empty(R, S + 1 + n_imp, device=edges.device, dtype=torch.float32)
-    _launch("fsn_sample_pdf_merge", edges.device, _p(edges), _p(weights), R, S, n_imp, _p(u), _p(out))
+    _launch("fsn_sample_pdf_merge", edges.device, edges, weights, R, S, n_imp, u, out)
     return out
 
 
@@ -392,8 +467,7 @@ def composite(sigmas: Tensor, rgbs: Tensor, t_starts: Tensor, t_ends: Tensor, bk
     w = torch.empty(R, S, device=dev) if extras else None
     a = torch.empty(R, S, device=dev) if extras else None
     tr = torch.empty(R, S, device=dev) if extras else None
-    _launch("fsn_composite_fwd", dev, _p(sig), _p(rgb), _p(t0), _p(t1), R, S, _bk(bkgd), _p(colors), _p(opacity), _p(depth),
-            _p(w), _p(a), _p(tr))
+    _launch("fsn_composite_fwd", dev, sig, rgb, t0, t1, R, S, _bk(bkgd), colors, opacity, depth, w, a, tr)
     ex = {"weights": w, "alphas": a, "trans": tr, "sigmas": sig, "rgbs": rgb} if extras else {}
     return colors, opacity, depth, ex
 
@@ -409,8 +483,7 @@ def composite_packed(sigmas: Tensor, rgbs: Tensor, t_starts: Tensor, t_ends: Ten
     opacity = torch.empty(n_rays, 1, device=dev)
     depth = torch.empty(n_rays, 1, device=dev)
     w, a, tr = (torch.empty(N, device=dev) for _ in range(3))
-    _launch("fsn_composite_packed_fwd", dev, _p(sig), _p(rgb), _p(t0), _p(t1), _p(ri), N, n_rays, _bk(bkgd), _p(colors),
-            _p(opacity), _p(depth), _p(w), _p(a), _p(tr))
+    _launch("fsn_composite_packed_fwd", dev, sig, rgb, t0, t1, ri, N, n_rays, _bk(bkgd), colors, opacity, depth, w, a, tr)
     return colors, opacity, depth, {"weights": w, "alphas": a, "trans": tr, "sigmas": sig, "rgbs": rgb}
 
 
@@ -551,7 +624,7 @@ class PackedMLP:
             ex = (C.c_int32 * len(exps))(*[int(e) for e in exps])
         self.exps = None if exps is None else tuple(int(e) for e in exps)
         _launch("fsn_mlp_pack_scaled", self.blob.device, C.byref(self.desc), self.prec, _ptr_array(ws), _ptr_array(bs), ex,
-                _p(self.blob))
+                self.blob)
         self._keep = (ws, bs)  # alive until the stream work is queued behind later launches
         return self
 
@@ -565,8 +638,7 @@ def mlp_layer_maxima(pm: PackedMLP, x: Tensor, dirs: Tensor, pos_mask: Optional[
     pmk, dmk = _opt_f32(pos_mask, "pos_mask"), _opt_f32(dir_mask, "dir_mask")
     if out is None:
         out = torch.zeros(pm.desc.n_layers + 2, device=x.device, dtype=torch.float32)
-    _launch("fsn_mlp_layer_maxima", x.device, C.byref(pm.desc), pm.prec, _p(pm.blob), _p(x), _p(d), _p(pmk), _p(dmk),
-            x.shape[0], _p(out))
+    _launch("fsn_mlp_layer_maxima", x.device, C.byref(pm.desc), pm.prec, pm.blob, x, d, pmk, dmk, x.shape[0], out)
     return out
 
 
@@ -578,8 +650,7 @@ def mlp_fwd(pm: PackedMLP, x: Tensor, dirs: Optional[Tensor] = None, pos_mask: O
     d = _opt_f32(dirs, "dirs")
     pmk, dmk = _opt_f32(pos_mask, "pos_mask"), _opt_f32(dir_mask, "dir_mask")
     out = torch.empty(*lead, 4 if d is not None else 1, device=x.device, dtype=torch.float32)
-    _launch("fsn_mlp_fwd", x.device, C.byref(pm.desc), pm.prec, _p(pm.blob), _p(x), _p(d), _p(pmk), _p(dmk), n, _p(out),
-            _p(status_word(x.device)))
+    _launch("fsn_mlp_fwd", x.device, C.byref(pm.desc), pm.prec, pm.blob, x, d, pmk, dmk, n, out, status_word(x.device))
     return out
 
 
@@ -592,8 +663,8 @@ def mlp_fwd_rays(pm: PackedMLP, rays_o: Tensor, rays_d: Tensor, ray_indices: Ten
     n = ri.numel()
     pmk, dmk = _opt_f32(pos_mask, "pos_mask"), _opt_f32(dir_mask, "dir_mask")
     out = torch.empty(n, 4 if full else 1, device=o.device, dtype=torch.float32)
-    _launch("fsn_mlp_fwd_rays", o.device, C.byref(pm.desc), pm.prec, _p(pm.blob), _p(o), _p(d), _p(ri), _p(t0), _p(t1),
-            1 if full else 0, _p(pmk), _p(dmk), n, _p(out), _p(status_word(o.device)))
+    _launch("fsn_mlp_fwd_rays", o.device, C.byref(pm.desc), pm.prec, pm.blob, o, d, ri, t0, t1, 1 if full else 0, pmk, dmk, n,
+            out, status_word(o.device))
     return out
 
 
@@ -650,18 +721,16 @@ def render_fused(pm_coarse: Optional[PackedMLP], pm_fine: PackedMLP, rays_o: Opt
     colors = torch.empty(R, 3, device=dev)
     opacity = torch.empty(R, 1, device=dev)
     depth = torch.empty(R, 1, device=dev)
-    a.colors, a.opacity, a.depth = colors.data_ptr(), opacity.data_ptr(), depth.data_ptr()
     ex: Dict[str, Tensor] = {}
     if want_extras:
         for k, shape in (("weights", (R, So)), ("alphas", (R, So)), ("trans", (R, So)), ("sigmas", (R, So)),
                          ("rgbs", (R, So, 3))):
             ex[k] = torch.empty(*shape, device=dev)
-            setattr(a, k, ex[k].data_ptr())
         ex["edges"] = torch.empty(R, So + 1, device=dev)
-        a.edges_out = ex["edges"].data_ptr()
         if NI > 0:
             ex["weights_coarse"] = torch.empty(R, S, device=dev)
-            a.weights_coarse = ex["weights_coarse"].data_ptr()
+    for k, t in (("colors", colors), ("opacity", opacity), ("depth", depth), *ex.items()):
+        h.set("edges_out" if k == "edges" else k, t)
     if two_phase is None:
         two_phase = NI > 0 and R >= 65536
     if two_phase and NI > 0:
@@ -672,11 +741,10 @@ def render_fused(pm_coarse: Optional[PackedMLP], pm_fine: PackedMLP, rays_o: Opt
         pm_coarse = pm_fine
     if pm_coarse is not None and pm_coarse.prec != pm_fine.prec:
         raise ValueError("render_fused: the coarse and the fine network must be packed in the same precision mode")
-    a.status = status_word(dev).data_ptr()
-    if clock_buffer is not None:
-        a.clock_out = clock_buffer.data_ptr()
+    h.set("status", status_word(dev))
+    h.set("clock_out", clock_buffer)
     _launch("fsn_render_rays_fused", dev, C.byref(pm_fine.desc), pm_fine.prec,
-            _p(pm_coarse.blob) if pm_coarse is not None else None, _p(pm_fine.blob), C.byref(a), timed=True)
+            pm_coarse.blob if pm_coarse is not None else None, pm_fine.blob, C.byref(a), timed=True)
     return colors, opacity, depth, ex
 
 
@@ -686,7 +754,7 @@ def bench_bare_stream(pm: PackedMLP, layers: int) -> Tuple[int, Tensor]:
     uint64 [workgroups * 8, 2] per-wave (s_memtime, s_memrealtime) differences around the loop)."""
     dev = pm.blob.device
     clk = torch.zeros(max(_size("fsn_device_cus", dev), 1) * 8, 2, dtype=torch.int64, device=dev)
-    n = _launch("fsn_bench_bare_stream", dev, C.byref(pm.desc), pm.prec, _p(pm.blob), int(layers), _p(clk), counts=True)
+    n = _launch("fsn_bench_bare_stream", dev, C.byref(pm.desc), pm.prec, pm.blob, int(layers), clk, counts=True)
     return n, clk
 
 
@@ -703,14 +771,13 @@ def sample_fused(pm_coarse: PackedMLP, rays_o: Tensor, rays_d: Tensor, *, near: 
     h, R, dev = _render_args(rays_o, rays_d, None, near, far, S, NI, u, u_fine, pos_mask, dir_mask)
     a = h.a
     edges = torch.empty(R, S + NI + 1, device=dev)
-    a.edges_out = edges.data_ptr()
     wc = torch.empty(R, S, device=dev) if want_weights else None
-    if wc is not None:
-        a.weights_coarse = wc.data_ptr()
+    h.set("edges_out", edges)
+    h.set("weights_coarse", wc)
     a.two_phase = 2
-    a.status = (status_word(dev) if status is None else status).data_ptr()  # `status`: a per-call word (training steps)
+    h.set("status", status_word(dev) if status is None else status)  # `status`: a per-call word (training steps)
     if R > 0:
-        _launch("fsn_render_rays_fused", dev, C.byref(pm_coarse.desc), pm_coarse.prec, _p(pm_coarse.blob), None, C.byref(a))
+        _launch("fsn_render_rays_fused", dev, C.byref(pm_coarse.desc), pm_coarse.prec, pm_coarse.blob, None, C.byref(a))
     return (edges, wc) if want_weights else edges
 
 
@@ -721,8 +788,7 @@ class _OcclusionRegFn(torch.autograd.Function):
         N = sig.numel()
         sums = torch.empty(max(n_rays, 1), device=sig.device, dtype=torch.float32)
         out = torch.empty(1, device=sig.device, dtype=torch.float32)
-        _launch("fsn_occlusion_reg_fwd", sig.device, _p(sig), _p(t), _p(ri), N, n_rays, float(a), float(b), func, _p(sums),
-                _p(out))
+        _launch("fsn_occlusion_reg_fwd", sig.device, sig, t, ri, N, n_rays, float(a), float(b), func, sums, out)
         ctx.save_for_backward(t, sums)
         ctx.cfg = (N, n_rays, float(a), float(b), func)
         return out.reshape(())
@@ -734,7 +800,7 @@ class _OcclusionRegFn(torch.autograd.Function):
         d_sig = torch.zeros(N, device=t.device, dtype=torch.float32)
         cnt = torch.empty(1, device=t.device, dtype=torch.int32)
         g = _f32(g, "grad").reshape(1)
-        _launch("fsn_occlusion_reg_bwd", t.device, _p(t), N, _p(sums), n_rays, a, b, func, _p(g), _p(cnt), _p(d_sig))
+        _launch("fsn_occlusion_reg_bwd", t.device, t, N, sums, n_rays, a, b, func, g, cnt, d_sig)
         return d_sig, None, None, None, None, None, None
 
 
@@ -757,7 +823,7 @@ def to8b(x: Tensor) -> Tensor:
     """(255 * clip(x, 0, 1)).astype(uint8) on the device (src/render/rendering.py:21)."""
     x = _f32(x, "x")
     out = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
-    _launch("fsn_to8b", x.device, _p(x), x.numel(), _p(out))
+    _launch("fsn_to8b", x.device, x, x.numel(), out)
     return out
 
 
@@ -783,8 +849,8 @@ def video_tensors(frames: Tensor, d_frames: Tensor, cmap: str = "plasma") -> Tup
     if N * H * W == 0:
         return out_f, out_d
     vmm = torch.stack(torch.aminmax(dp)).to(torch.float32).contiguous()  # np.amin / np.amax over ALL frames
-    _launch("fsn_to8b_nchw", dev, _p(fr), N, H * W, _p(out_f))
-    _launch("fsn_depth_colormap", dev, _p(dp), N, H * W, _p(vmm), _p(_lut_cache[key]), _p(out_d))
+    _launch("fsn_to8b_nchw", dev, fr, N, H * W, out_f)
+    _launch("fsn_depth_colormap", dev, dp, N, H * W, vmm, _lut_cache[key], out_d)
     return out_f, out_d
 
 
@@ -803,8 +869,7 @@ def _nerf_train_fwd(name: str, desc: L.MlpDesc, prec: int, weights, biases, inpu
     out = torch.empty(n, 4, device=dev, dtype=torch.float32)
     nfl = _size("fsn_nerf_train_workspace_floats", dev, C.byref(desc), prec, n)
     work = torch.empty(max(nfl, 1), device=dev, dtype=torch.float32)
-    _launch(name, dev, C.byref(desc), prec, _ptr_array(ws_), _ptr_array(bs_), *(_p(t) for t in inputs), _p(pm), _p(dm), n,
-            _p(work), _p(out), _p(status))
+    _launch(name, dev, C.byref(desc), prec, _ptr_array(ws_), _ptr_array(bs_), *inputs, pm, dm, n, work, out, status)
     return out, work
 
 
@@ -832,7 +897,7 @@ def grad_scale_for(d_out: Tensor) -> Tensor:
     2^clamp(floor(log2(1024 / max|d_out|)), -40, 60), 1 when the maximum is 0 / inf / NaN."""
     d = _f32(d_out.detach(), "d_out").reshape(-1)
     buf = torch.zeros(4, dtype=torch.float32, device=d.device)
-    _launch("fsn_grad_scale", d.device, _p(d), d.numel(), _p(buf))
+    _launch("fsn_grad_scale", d.device, d, d.numel(), buf)
     return buf[:1]
 
 
@@ -880,9 +945,9 @@ def nerf_train_bwd(desc: L.MlpDesc, prec: int, weights: Sequence[Tensor], work: 
     dW, db, scale = _grad_buffers(ws_, n, into, prec, d_out)
     if n == 0:
         return dW, db
-    _launch("fsn_nerf_train_bwd", work.device, C.byref(desc), prec, _ptr_array(ws_), n, _p(work), _p(out), _p(d_out),
-            _p(scale), _ptr_array(dW), _ptr_array(db), 0 if into is None else 1,
-            _p(stage_state[0]) if stage_state else None, _p(stage_state[1]) if stage_state else None, _p(status))
+    _launch("fsn_nerf_train_bwd", work.device, C.byref(desc), prec, _ptr_array(ws_), n, work, out, d_out, scale,
+            _ptr_array(dW), _ptr_array(db), 0 if into is None else 1, stage_state[0] if stage_state else None,
+            stage_state[1] if stage_state else None, status)
     return dW, db
 
 
@@ -923,11 +988,10 @@ def nerf_train_bwd_inputs(desc: L.MlpDesc, prec: int, weights: Sequence[Tensor],
     if n == 0:
         return dW, db, d_x, d_dirs
     pm, dm = _opt_f32(pos_mask, "pos_mask"), _opt_f32(dir_mask, "dir_mask")
-    _launch("fsn_nerf_train_bwd_inputs", work.device, C.byref(desc), prec, _ptr_array(ws_), n, _p(work), _p(out), _p(d_out),
-            _p(scale), _ptr_array(dW) if param_grads else None, _ptr_array(db) if param_grads else None,
-            0 if into is None else 1, _p(stage_state[0]) if stage_state else None,
-            _p(stage_state[1]) if stage_state else None, _p(status), *[_p(t) for t in src], _p(pm), _p(dm), _p(d_x),
-            _p(d_dirs))
+    _launch("fsn_nerf_train_bwd_inputs", work.device, C.byref(desc), prec, _ptr_array(ws_), n, work, out, d_out, scale,
+            _ptr_array(dW) if param_grads else None, _ptr_array(db) if param_grads else None, 0 if into is None else 1,
+            stage_state[0] if stage_state else None, stage_state[1] if stage_state else None, status, *src, pm, dm, d_x,
+            d_dirs)
     return dW, db, d_x, d_dirs
 
 
@@ -945,7 +1009,7 @@ def ray_grad_reduce(d_x: Optional[Tensor], d_dirs: Optional[Tensor], ray_indices
             raise ValueError("ray_grad_reduce: d_x / d_dirs must be [n_samples, 3]")
     d_o = torch.empty(n_rays, 3, device=dev, dtype=torch.float32) if want_o else None
     d_d = torch.empty(n_rays, 3, device=dev, dtype=torch.float32) if want_d else None
-    _launch("fsn_ray_grad_reduce", dev, _p(d_x), _p(d_dirs), _p(ri), _p(t0), _p(t1), n, n_rays, _p(d_o), _p(d_d))
+    _launch("fsn_ray_grad_reduce", dev, d_x, d_dirs, ri, t0, t1, n, n_rays, d_o, d_d)
     return d_o, d_d
 
 
@@ -966,11 +1030,11 @@ def _composite_bwd(lean, sigmas, rgbs, t_starts, t_ends, ray_indices, n_rays, bk
         raise ValueError(f"composite_packed_bwd{'' if lean else '_full'}: sigmas, rgbs, t_starts, t_ends and ray_indices "
                          "disagree in length")
     ds, dr = torch.empty_like(sig), torch.empty_like(rgb)
-    head, tail = (_p(sig), _p(rgb), _p(t0), _p(t1), _p(ri), N, n_rays, _bk(bkgd), _p(dc), _p(dop)), (_p(ds), _p(dr))
+    head, tail = (sig, rgb, t0, t1, ri, N, n_rays, _bk(bkgd), dc, dop), (ds, dr)
     if lean:
         _launch("fsn_composite_packed_bwd", sig.device, *head, *tail)
     else:
-        _launch("fsn_composite_packed_bwd_full", sig.device, *head, _p(op), _p(dep), _p(dd), _p(dw), _p(da), _p(dt), *tail)
+        _launch("fsn_composite_packed_bwd_full", sig.device, *head, op, dep, dd, dw, da, dt, *tail)
     return ds, dr
 
 
@@ -994,7 +1058,7 @@ class _DistortionFn(torch.autograd.Function):
     def forward(ctx, w, t0, t1, ri, n_rays):
         N = w.numel()
         out = torch.empty(n_rays, device=w.device, dtype=torch.float32)
-        _launch("fsn_distortion_fwd", w.device, _p(w), _p(t0), _p(t1), _p(ri), N, n_rays, _p(out))
+        _launch("fsn_distortion_fwd", w.device, w, t0, t1, ri, N, n_rays, out)
         ctx.save_for_backward(w, t0, t1, ri)
         ctx.n_rays = n_rays
         return out.reshape(n_rays, 1)
@@ -1004,7 +1068,7 @@ class _DistortionFn(torch.autograd.Function):
         w, t0, t1, ri = ctx.saved_tensors
         g = _f32(g, "grad").reshape(-1)
         d_w = torch.empty_like(w)
-        _launch("fsn_distortion_bwd", w.device, _p(w), _p(t0), _p(t1), _p(ri), w.numel(), ctx.n_rays, _p(g), _p(d_w))
+        _launch("fsn_distortion_bwd", w.device, w, t0, t1, ri, w.numel(), ctx.n_rays, g, d_w)
         return d_w, None, None, None, None
 
 
@@ -1024,7 +1088,7 @@ class _RayEntropyFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, v, ri, n_rays, c, eps, scale):
         out = torch.empty(n_rays, device=v.device, dtype=torch.float32)
-        _launch("fsn_ray_entropy_fwd", v.device, _p(v), _p(ri), v.numel(), n_rays, _p(c), eps, scale, _p(out))
+        _launch("fsn_ray_entropy_fwd", v.device, v, ri, v.numel(), n_rays, c, eps, scale, out)
         ctx.save_for_backward(v, ri, c)
         ctx.n_rays, ctx.eps, ctx.scale = n_rays, eps, scale
         return out.reshape(n_rays, 1)
@@ -1034,8 +1098,7 @@ class _RayEntropyFn(torch.autograd.Function):
         v, ri, c = ctx.saved_tensors
         g = _f32(g, "grad").reshape(-1)
         d_v = torch.empty_like(v)
-        _launch("fsn_ray_entropy_bwd", v.device, _p(v), _p(ri), v.numel(), ctx.n_rays, _p(c), ctx.eps, ctx.scale, _p(g),
-                _p(d_v))
+        _launch("fsn_ray_entropy_bwd", v.device, v, ri, v.numel(), ctx.n_rays, c, ctx.eps, ctx.scale, g, d_v)
         return d_v, None, None, None, None, None
 
 
@@ -1060,8 +1123,7 @@ class _DepthKLFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, w, t0, t1, ri, n_rays, depth, var, eps):
         out = torch.empty(n_rays, device=w.device, dtype=torch.float32)
-        _launch("fsn_depth_kl_fwd", w.device, _p(w), _p(t0), _p(t1), _p(ri), w.numel(), n_rays, _p(depth), _p(var), eps,
-                _p(out))
+        _launch("fsn_depth_kl_fwd", w.device, w, t0, t1, ri, w.numel(), n_rays, depth, var, eps, out)
         ctx.save_for_backward(w, t0, t1, ri, depth, var)
         ctx.n_rays, ctx.eps = n_rays, eps
         return out.reshape(n_rays, 1)
@@ -1071,8 +1133,7 @@ class _DepthKLFn(torch.autograd.Function):
         w, t0, t1, ri, depth, var = ctx.saved_tensors
         g = _f32(g, "grad").reshape(-1)
         d_w = torch.empty_like(w)
-        _launch("fsn_depth_kl_bwd", w.device, _p(w), _p(t0), _p(t1), _p(ri), w.numel(), ctx.n_rays, _p(depth), _p(var),
-                ctx.eps, _p(g), _p(d_w))
+        _launch("fsn_depth_kl_bwd", w.device, w, t0, t1, ri, w.numel(), ctx.n_rays, depth, var, ctx.eps, g, d_w)
         return d_w, None, None, None, None, None, None, None
 
 
@@ -1103,7 +1164,7 @@ class _PatchTVFn(torch.autograd.Function):
     def forward(ctx, d):
         B, P, Q = d.shape
         out = torch.empty(B, device=d.device, dtype=torch.float32)
-        _launch("fsn_patch_tv_fwd", d.device, _p(d), B, P, Q, _p(out))
+        _launch("fsn_patch_tv_fwd", d.device, d, B, P, Q, out)
         ctx.save_for_backward(d)
         return out
 
@@ -1113,7 +1174,7 @@ class _PatchTVFn(torch.autograd.Function):
         B, P, Q = d.shape
         g = _f32(g, "grad").reshape(-1)
         d_d = torch.empty_like(d)
-        _launch("fsn_patch_tv_bwd", d.device, _p(d), B, P, Q, _p(g), _p(d_d))
+        _launch("fsn_patch_tv_bwd", d.device, d, B, P, Q, g, d_d)
         return d_d
 
 
@@ -1146,14 +1207,14 @@ class RaySpans:
             raise ValueError(f"dense rows: {self.N} values are not {self.R} rows of {self.S}")
 
     def args(self):
-        return _p(self.ri), _p(self.pi), self.N, self.R, self.S
+        return self.ri, self.pi, self.N, self.R, self.S
 
 
 def pack_info(ray_indices: Tensor, n_rays: int) -> Tensor:
     """(start, count) int64 [n_rays, 2] of every ray in the sorted `ray_indices` (fsn_pack_info)."""
     ri = _i64(ray_indices, "ray_indices").reshape(-1)
     info = torch.empty(int(n_rays), 2, dtype=torch.int64, device=ri.device)
-    _launch("fsn_pack_info", ri.device, _p(ri), ri.numel(), int(n_rays), _p(info))
+    _launch("fsn_pack_info", ri.device, ri, ri.numel(), int(n_rays), info)
     return info
 
 
@@ -1174,8 +1235,8 @@ def _out(like: Tensor, spans: RaySpans, dtype=torch.float32) -> Tensor:
 def packed_scan_fwd(x: Tensor, spans: RaySpans, prod: bool, exclusive: bool) -> Tensor:
     x = _flat(x, "inputs", spans.N)
     out = _out(x, spans)
-    _launch("fsn_packed_scan_fwd", x.device, _p(x), *spans.args(), L.FSN_SCAN_PROD if prod else L.FSN_SCAN_SUM,
-            int(exclusive), _p(out))
+    _launch("fsn_packed_scan_fwd", x.device, x, *spans.args(), L.FSN_SCAN_PROD if prod else L.FSN_SCAN_SUM, int(exclusive),
+            out)
     return out
 
 
@@ -1183,8 +1244,8 @@ def packed_scan_bwd(x: Optional[Tensor], d_out: Tensor, spans: RaySpans, prod: b
     g = _flat(d_out, "d_out", spans.N)
     x = _flat(x, "inputs", spans.N)
     d_x = _zeroed_by_call(g.shape, spans, g.device)
-    _launch("fsn_packed_scan_bwd", g.device, _p(x), _p(g), *spans.args(), L.FSN_SCAN_PROD if prod else L.FSN_SCAN_SUM,
-            int(exclusive), _p(d_x))
+    _launch("fsn_packed_scan_bwd", g.device, x, g, *spans.args(), L.FSN_SCAN_PROD if prod else L.FSN_SCAN_SUM, int(exclusive),
+            d_x)
     return d_x
 
 
@@ -1198,8 +1259,7 @@ def packed_weights_fwd(v: Tensor, t_starts: Optional[Tensor], t_ends: Optional[T
     if not from_alpha and (t0 is None or t1 is None):
         raise ValueError("packed_weights_fwd: the density form needs t_starts and t_ends")
     outs = [_out(v, spans) if k else None for k in want]
-    _launch("fsn_packed_weights_fwd", v.device, _p(v), _p(t0), _p(t1), *spans.args(), int(from_alpha), _p(p),
-            *(_p(o) for o in outs))
+    _launch("fsn_packed_weights_fwd", v.device, v, t0, t1, *spans.args(), int(from_alpha), p, *(o for o in outs))
     return tuple(outs)
 
 
@@ -1213,15 +1273,14 @@ def packed_weights_bwd(v: Tensor, t_starts: Optional[Tensor], t_ends: Optional[T
     p = _flat(prefix_trans, "prefix_trans", n)
     dw, dtr, dal = _flat(d_weights, "d_weights", n), _flat(d_trans, "d_trans", n), _flat(d_alphas, "d_alphas", n)
     d_v = _zeroed_by_call(v.shape, spans, v.device)
-    _launch("fsn_packed_weights_bwd", v.device, _p(v), _p(t0), _p(t1), *spans.args(), int(from_alpha), _p(p), _p(dw), _p(dtr),
-            _p(dal), _p(d_v))
+    _launch("fsn_packed_weights_bwd", v.device, v, t0, t1, *spans.args(), int(from_alpha), p, dw, dtr, dal, d_v)
     return d_v
 
 
 def packed_visibility_alpha(alphas: Tensor, spans: RaySpans, early_stop_eps: float, alpha_thre: float) -> Tensor:
     a = _flat(alphas, "alphas", spans.N)
     keep = _zeroed_by_call((spans.N,), spans, a.device, torch.uint8)
-    _launch("fsn_packed_visibility_alpha", a.device, _p(a), *spans.args(), float(early_stop_eps), float(alpha_thre), _p(keep))
+    _launch("fsn_packed_visibility_alpha", a.device, a, *spans.args(), float(early_stop_eps), float(alpha_thre), keep)
     return keep.bool()
 
 
@@ -1235,7 +1294,7 @@ def accumulate_fwd(weights: Tensor, values: Optional[Tensor], spans: RaySpans) -
             raise ValueError("accumulate: values need at least one channel")
         values = _flat(values, "values", spans.N * C)
     out = torch.empty(spans.R, C, device=w.device, dtype=torch.float32)  # (every row is written; N == 0: zeroed by the call)
-    _launch("fsn_accumulate_fwd", w.device, _p(w), _p(values), C, *spans.args(), _p(out))
+    _launch("fsn_accumulate_fwd", w.device, w, values, C, *spans.args(), out)
     return out
 
 
@@ -1249,7 +1308,7 @@ def accumulate_bwd(d_out: Tensor, weights: Tensor, values: Optional[Tensor], spa
     d_w = _zeroed_by_call(w.shape, spans, w.device) if want_weights else None
     d_v = _zeroed_by_call((spans.N, C), spans, w.device) if want_values and v is not None else None
     if d_w is not None or d_v is not None:
-        _launch("fsn_accumulate_bwd", w.device, _p(g), _p(w), _p(v), C, *spans.args(), _p(d_w), _p(d_v))
+        _launch("fsn_accumulate_bwd", w.device, g, w, v, C, *spans.args(), d_w, d_v)
     return d_w, d_v
 
 
@@ -1287,7 +1346,7 @@ def importance_sample(vals: Tensor, cdfs: Tensor, n: int, b: Optional[Tensor] = 
     s = torch.empty(R, max(n, 0) + 1, device=dev)
     x = torch.empty(R, max(n, 0), device=dev) if want_centres else None
     t = torch.empty_like(s) if transform is not None else None
-    _launch("fsn_importance_sample", dev, _p(vals), _p(cdfs), R, S, n, _p(b), tf, near, far, _p(s), _p(x), _p(t))
+    _launch("fsn_importance_sample", dev, vals, cdfs, R, S, n, b, tf, near, far, s, x, t)
     return s, x, t
 
 
@@ -1304,8 +1363,7 @@ def prop_resample(s_edges: Tensor, t_edges: Tensor, sigmas: Tensor, n: int, b: O
     s = torch.empty(R, max(n, 0) + 1, device=dev)
     x = torch.empty(R, max(n, 0), device=dev) if want_centres else None
     t = torch.empty_like(s) if transform is not None else None
-    _launch("fsn_prop_resample", dev, _p(s_edges), _p(t_edges), _p(sigmas), R, S, n, _p(b), tf, near, far, _p(cdfs), _p(s),
-            _p(x), _p(t))
+    _launch("fsn_prop_resample", dev, s_edges, t_edges, sigmas, R, S, n, b, tf, near, far, cdfs, s, x, t)
     return cdfs, s, x, t
 
 
@@ -1317,7 +1375,7 @@ def searchsorted_dense(keys: Tensor, values: Tensor) -> Tuple[Tensor, Tensor]:
     R, K, Q = int(keys.shape[0]), int(keys.shape[1]), int(values.shape[1])
     il = torch.empty(R, Q, dtype=torch.int64, device=keys.device)
     ir = torch.empty_like(il)
-    _launch("fsn_searchsorted_dense", keys.device, _p(keys), _p(values), R, K, Q, _p(il), _p(ir))
+    _launch("fsn_searchsorted_dense", keys.device, keys, values, R, K, Q, il, ir)
     return il, ir
 
 
@@ -1333,7 +1391,7 @@ def prop_loss_fwd(q_edges: Tensor, q_cdfs: Tensor, k_edges: Tensor, k_cdfs: Tens
     """-> the interlevel loss per query interval [R, n] (fsn_prop_loss_fwd)"""
     rows, R, n, S = _prop_loss_rows(q_edges, q_cdfs, k_edges, k_cdfs)
     loss = torch.empty(R, max(n, 0), device=rows[0].device)
-    _launch("fsn_prop_loss_fwd", loss.device, *(_p(t) for t in rows), R, n, S, _p(loss))
+    _launch("fsn_prop_loss_fwd", loss.device, *rows, R, n, S, loss)
     return loss
 
 
@@ -1342,7 +1400,7 @@ def prop_loss_bwd(q_edges: Tensor, q_cdfs: Tensor, k_edges: Tensor, k_cdfs: Tens
     rows, R, n, S = _prop_loss_rows(q_edges, q_cdfs, k_edges, k_cdfs)
     g = _rows(d_loss, "d_loss", R, n)
     d_ck = torch.empty(R, S + 1, device=g.device)
-    _launch("fsn_prop_loss_bwd", g.device, *(_p(t) for t in rows), _p(g), R, n, S, _p(d_ck))
+    _launch("fsn_prop_loss_bwd", g.device, *rows, g, R, n, S, d_ck)
     return d_ck
 
 
@@ -1364,10 +1422,10 @@ def occgrid_march(rays_o: Tensor, rays_d: Tensor, aabb: Sequence[float], res: in
     bounds = [None if t is None else _f32(t, k).reshape(-1) for t, k in ((t_min, "t_min"), (t_max, "t_max"))]
     if any(t is not None and t.numel() != R for t in bounds):
         raise ValueError("t_min / t_max must hold one value per ray")
-    args = (_p(o), _p(d), R, ab, int(res), int(levels), _p(bits), float(near_plane), float(far_plane), float(step), _p(u_),
-            int(max_steps), _p(bounds[0]), _p(bounds[1]), float(cone_angle))
+    args = (o, d, R, ab, int(res), int(levels), bits, float(near_plane), float(far_plane), float(step), u_,
+            int(max_steps), bounds[0], bounds[1], float(cone_angle))
     counts = torch.zeros(R, device=dev, dtype=torch.int64)
-    _launch("fsn_occgrid_march_ex", dev, *args, _p(counts), None, None, None, None)
+    _launch("fsn_occgrid_march_ex", dev, *args, counts, None, None, None, None)
     ends = torch.cumsum(counts, 0)
     offsets = (ends - counts).contiguous()
     N = int(ends[-1].item()) if R > 0 else 0  # the one host read: the sample count sizes the outputs
@@ -1375,7 +1433,7 @@ def occgrid_march(rays_o: Tensor, rays_d: Tensor, aabb: Sequence[float], res: in
     t0 = torch.empty(N, device=dev, dtype=torch.float32)
     t1 = torch.empty(N, device=dev, dtype=torch.float32)
     if N > 0:
-        _launch("fsn_occgrid_march_ex", dev, *args, None, _p(offsets), _p(ri), _p(t0), _p(t1))
+        _launch("fsn_occgrid_march_ex", dev, *args, None, offsets, ri, t0, t1)
     return ri, t0, t1, counts
 
 
@@ -1389,8 +1447,8 @@ def ray_aabb_intersect(rays_o: Tensor, rays_d: Tensor, aabbs: Tensor, near_plane
     t0 = torch.empty(R, M, device=o.device, dtype=torch.float32)
     t1 = torch.empty(R, M, device=o.device, dtype=torch.float32)
     hits = torch.empty(R, M, device=o.device, dtype=torch.uint8)
-    _launch("fsn_ray_aabb_intersect", o.device, _p(o), _p(d), R, _p(boxes), M, float(near_plane), float(far_plane),
-            float(miss_value), _p(t0), _p(t1), _p(hits))
+    _launch("fsn_ray_aabb_intersect", o.device, o, d, R, boxes, M, float(near_plane), float(far_plane), float(miss_value), t0,
+            t1, hits)
     return t0, t1, hits.bool()
 
 
@@ -1402,7 +1460,9 @@ def _occ_march_options(R: int, cone_angle: float, t_min: Optional[Tensor], t_max
             raise TypeError("per-ray t_min / t_max need ray tensors, not a camera")
     if any(t is not None and t.numel() != R for t in (t_min, t_max)):
         raise ValueError("t_min / t_max must hold one value per ray")
-    return float(cone_angle), h.p(_flat(t_min, "t_min", R, cast=True)), h.p(_flat(t_max, "t_max", R, cast=True))
+    bounds = _flat(t_min, "t_min", R, cast=True), _flat(t_max, "t_max", R, cast=True)
+    h.tensors += bounds
+    return (float(cone_angle), *bounds)
 
 
 def _occ_args(rays_o: Optional[Tensor], rays_d: Optional[Tensor], camera, aabb: Sequence[float], res: int, levels: int,
@@ -1417,7 +1477,8 @@ def _occ_args(rays_o: Optional[Tensor], rays_d: Optional[Tensor], camera, aabb: 
     march = _occ_march_options(R, cone_angle, t_min, t_max, camera, h)
     for i in range(6):
         a.aabb[i] = float(aabb[i])
-    a.res, a.levels, a.bits = int(res), int(levels), bits.data_ptr()
+    a.res, a.levels = int(res), int(levels)
+    h.set("bits", bits)
     a.near_plane, a.far_plane, a.step, a.max_steps = float(near_plane), float(far_plane), float(step), int(max_steps)
     if u is not None:
         u = _f32(u, "u").reshape(-1)
@@ -1435,10 +1496,9 @@ def _occ_launch(pm: "PackedMLP", h: _Held, march, ends: Optional[Tensor], dev, s
     # (one queue counter PER CALL - ADVICE r3: a per-device buffer let two launches on different streams race on it; the
     # launch zeroes it itself)
     h.set("work_counter", torch.empty(1, dtype=torch.int64, device=dev))
-    h.a.status = (status_word(dev) if status is None else status).data_ptr()
+    h.set("status", status_word(dev) if status is None else status)
     if launch:
-        _launch("fsn_render_rays_occgrid_ex", dev, C.byref(pm.desc), pm.prec, _p(pm.blob), C.byref(h.a), *march, _p(ends),
-                **door)
+        _launch("fsn_render_rays_occgrid_ex", dev, C.byref(pm.desc), pm.prec, pm.blob, C.byref(h.a), *march, ends, **door)
 
 
 def _occ_gather(n_kept: Tensor, t0_slots: Tensor, t1_slots: Optional[Tensor], cap: int, R: int, step: float,
@@ -1456,8 +1516,7 @@ def _occ_gather(n_kept: Tensor, t0_slots: Tensor, t1_slots: Optional[Tensor], ca
     if N > 0:
         sp = _ptr_array([slots[k] for k in order]) if order else None
         op = _ptr_array([ex[k] for k in order]) if order else None
-        _launch("fsn_occ_gather_ex", dev, _p(n_kept), _p(incl - n_kept), _p(t0_slots), _p(t1_slots), cap, R, float(step),
-                _p(ri), _p(ts), _p(te), sp, op)
+        _launch("fsn_occ_gather_ex", dev, n_kept, incl - n_kept, t0_slots, t1_slots, cap, R, float(step), ri, ts, te, sp, op)
     return ri, ts, te, ex
 
 
@@ -1479,7 +1538,9 @@ def occ_sample_fused(pm: PackedMLP, rays_o: Tensor, rays_d: Tensor, *, aabb: Seq
     n_kept = torch.zeros(Rn, dtype=torch.int32, device=dev)
     slots = torch.empty(max(Rn, 1), cap, dtype=torch.float32, device=dev)
     ends = torch.empty_like(slots) if cone_angle > 0.0 else None  # (uniform regime: t_end = t_start + step)
-    a.n_kept, a.sample_t0, a.sample_cap = n_kept.data_ptr(), slots.data_ptr(), cap
+    a.sample_cap = cap
+    h.set("n_kept", n_kept)
+    h.set("sample_t0", slots)
     _occ_launch(pm, h, march, ends, dev, status, launch=Rn > 0, what="fsn_render_rays_occgrid_ex (sampler mode)")
     return _occ_gather(n_kept, slots, ends, cap, Rn, step)[:3]
 
@@ -1508,20 +1569,21 @@ def render_occ_fused(pm: PackedMLP, rays_o: Optional[Tensor], rays_d: Optional[T
     colors = torch.empty(R, 3, device=dev)
     opacity = torch.empty(R, 1, device=dev)
     depth = torch.empty(R, 1, device=dev)
-    a.colors, a.opacity, a.depth = colors.data_ptr(), opacity.data_ptr(), depth.data_ptr()
     counts = {}
     if want_counts or want_extras:
         counts = {"n_cand": torch.zeros(R, dtype=torch.int32, device=dev), "n_kept": torch.zeros(R, dtype=torch.int32, device=dev)}
-        a.n_cand, a.n_kept = counts["n_cand"].data_ptr(), counts["n_kept"].data_ptr()
     slots = {}
     if want_extras:
         slots = {k: torch.empty(max(R, 1), cap, device=dev) for k in ("t0", "weights", "alphas", "trans", "sigmas")}
         slots["rgbs"] = torch.empty(max(R, 1), cap, 3, device=dev)
         if cone_angle > 0.0:  # (uniform regime: t_end = t_start + step)
             slots["t1"] = torch.empty(max(R, 1), cap, device=dev)
-        a.sample_t0, a.sample_cap = slots["t0"].data_ptr(), cap
-        a.ex_weights, a.ex_alphas, a.ex_trans = slots["weights"].data_ptr(), slots["alphas"].data_ptr(), slots["trans"].data_ptr()
-        a.ex_sigmas, a.ex_rgbs = slots["sigmas"].data_ptr(), slots["rgbs"].data_ptr()
+        a.sample_cap = cap
+    for k, t in (("colors", colors), ("opacity", opacity), ("depth", depth), *counts.items()):
+        h.set(k, t)
+    for k, t in slots.items():  # (the interval ends, "t1", are an argument of the launch, not a field)
+        if k != "t1":
+            h.set("sample_t0" if k == "t0" else "ex_" + k, t)
     _occ_launch(pm, h, march, slots.get("t1"), dev, timed=True)
     if want_extras:
         return colors, opacity, depth, counts, _occ_gather(counts["n_kept"], slots["t0"], slots.get("t1"), cap, R, step, slots)
@@ -1534,8 +1596,8 @@ def packed_visibility(sigmas: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indi
     N = sig.numel()
     keep = torch.zeros(N, device=sig.device, dtype=torch.uint8)
     ri = _i64(ray_indices, "ray_indices")
-    _launch("fsn_packed_visibility", sig.device, _p(sig), _p(t0), _p(t1), _p(ri), N, int(n_rays), float(early_stop_eps),
-            float(alpha_thre), _p(keep))
+    _launch("fsn_packed_visibility", sig.device, sig, t0, t1, ri, N, int(n_rays), float(early_stop_eps), float(alpha_thre),
+            keep)
     return keep.bool()
 
 
@@ -1545,7 +1607,7 @@ def occgrid_update(occs: Tensor, bits: Tensor, cells: Optional[Tensor], vals: Op
     n = 0 if cells is None else cells.numel()
     thr = None if threshold is None else _f32(threshold, "threshold").reshape(1)
     vals = _opt_f32(vals, "vals")
-    _launch("fsn_occgrid_update", occs.device, _p(occs), occs.numel(), _p(cells), _p(vals), n, float(decay), _p(thr), _p(bits))
+    _launch("fsn_occgrid_update", occs.device, occs, occs.numel(), cells, vals, n, float(decay), thr, bits)
 
 
 def occgrid_select(bits: Tensor, aabb: Sequence[float], res: int, levels: int, lvl: int, all_cells: bool, n_uniform: int,
@@ -1564,8 +1626,8 @@ def occgrid_select(bits: Tensor, aabb: Sequence[float], res: int, levels: int, l
     if scratch is None and not all_cells and n_occupied > 0:
         scratch = torch.empty(res3 // 32 + 1, dtype=torch.int32, device=dev)
     ab = (C.c_float * 6)(*[float(v) for v in aabb])
-    _launch("fsn_occgrid_select", dev, _p(bits), int(res), int(levels), int(lvl), ab, 1 if all_cells else 0, int(n_uniform),
-            int(n_occupied), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _p(scratch), _p(cells), _p(x))
+    _launch("fsn_occgrid_select", dev, bits, int(res), int(levels), int(lvl), ab, 1 if all_cells else 0, int(n_uniform),
+            int(n_occupied), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), scratch, cells, x)
     return cells, x
 
 
@@ -1573,7 +1635,7 @@ def occgrid_update_multi(occs: Tensor, pending: Tensor, cells: Tensor, vals: Ten
     """occs[c] = max(occs[c]*decay, max of the vals drawn for c); `cells` may repeat (fsn_occgrid_update_multi)."""
     n = cells.numel()
     vals = _f32(vals, "vals").reshape(-1)
-    _launch("fsn_occgrid_update_multi", occs.device, _p(occs), occs.numel(), _p(pending), _p(cells), _p(vals), n, float(decay))
+    _launch("fsn_occgrid_update_multi", occs.device, occs, occs.numel(), pending, cells, vals, n, float(decay))
 
 
 def occgrid_refresh(pm: PackedMLP, bits: Tensor, aabb: Sequence[float], res: int, levels: int, all_cells: bool,
@@ -1593,15 +1655,14 @@ def occgrid_refresh(pm: PackedMLP, bits: Tensor, aabb: Sequence[float], res: int
     ab = (C.c_float * 6)(*[float(v) for v in aabb])
     sd = (C.c_uint64 * int(levels))(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in seeds])
     pmk = _opt_f32(pos_mask, "pos_mask")
-    _launch("fsn_occgrid_refresh", dev, C.byref(pm.desc), pm.prec, _p(pm.blob), _p(pmk), _p(bits), int(res), int(levels), ab,
-            1 if all_cells else 0, int(n_uniform), int(n_occupied), sd, float(step), _p(prefix), _p(pending),
-            _p(status_word(dev)))
+    _launch("fsn_occgrid_refresh", dev, C.byref(pm.desc), pm.prec, pm.blob, pmk, bits, int(res), int(levels), ab,
+            1 if all_cells else 0, int(n_uniform), int(n_occupied), sd, float(step), prefix, pending, status_word(dev))
 
 
 def occgrid_apply_pending(occs: Tensor, pending: Tensor, decay: float) -> None:
     """occs[c] = max(occs[c] * decay, pending[c]) for the cells a refresh touched; `pending` is cleared
     (fsn_occgrid_apply_pending: the second half of occgrid_update_multi)."""
-    _launch("fsn_occgrid_apply_pending", occs.device, _p(occs), occs.numel(), _p(pending), float(decay))
+    _launch("fsn_occgrid_apply_pending", occs.device, occs, occs.numel(), pending, float(decay))
 
 
 def occgrid_visibility(aabb: Sequence[float], res: int, levels: int, cams: Tensor, width: int, height: int,
@@ -1617,8 +1678,8 @@ def occgrid_visibility(aabb: Sequence[float], res: int, levels: int, cams: Tenso
         raise ValueError("occgrid_visibility: visible must be int32 [levels res^3 / 32]")
     ab = (C.c_float * 6)(*[float(v) for v in aabb])
     wf, hf, nr = (0.0, 0.0, 0.0) if ndc is None else (float(v) for v in ndc)
-    _launch("fsn_occgrid_visibility", visible.device, ab, int(res), int(levels), _p(cams), cams.shape[0], int(width),
-            int(height), float(near_plane), int(min_views), 0 if ndc is None else 1, wf, hf, nr, _p(visible))
+    _launch("fsn_occgrid_visibility", visible.device, ab, int(res), int(levels), cams, cams.shape[0], int(width), int(height),
+            float(near_plane), int(min_views), 0 if ndc is None else 1, wf, hf, nr, visible)
 
 
 def occgrid_update_masked(occs: Tensor, bits: Optional[Tensor], visible: Tensor, occ_thre: float, scratch: Tensor,
@@ -1628,8 +1689,8 @@ def occgrid_update_masked(occs: Tensor, bits: Optional[Tensor], visible: Tensor,
     holding -1 becomes 0).  scratch: float64 [2048].  No host sync."""
     if scratch.dtype != torch.float64 or scratch.numel() < 2048:
         raise ValueError("occgrid_update_masked: scratch must be float64 [2048]")
-    _launch("fsn_occgrid_update_masked", occs.device, _p(occs), occs.numel(), _p(visible), float(occ_thre),
-            1 if revive else 0, _p(scratch), _p(bits))
+    _launch("fsn_occgrid_update_masked", occs.device, occs, occs.numel(), visible, float(occ_thre), 1 if revive else 0,
+            scratch, bits)
 
 
 # ------------------------------------------------------------------ evaluation metrics (run-nerf.py:108-191)
@@ -1664,8 +1725,8 @@ def ssim_nchw(x: Tensor, y: Tensor, window: int, use_sample_covariance: bool, da
     dev = x.device
     out = torch.empty(N + 1, dtype=torch.float64, device=dev)
     ws = torch.empty(max(_size("fsn_ssim_workspace_doubles", None, N, Ch, H, W), 1), dtype=torch.float64, device=dev)
-    _launch("fsn_ssim", dev, _p(x), _p(y), N, Ch, H, W, _nchw_strides(x), _nchw_strides(y), int(window),
-            1 if use_sample_covariance else 0, float(data_range), float(K1), float(K2), _p(ws), _p(out), _p(smap),
+    _launch("fsn_ssim", dev, x, y, N, Ch, H, W, _nchw_strides(x), _nchw_strides(y), int(window),
+            1 if use_sample_covariance else 0, float(data_range), float(K1), float(K2), ws, out, smap,
             None if smap is None else _nchw_strides(smap))
     return out
 
@@ -1698,10 +1759,9 @@ def ssim_grad_nchw(x: Tensor, y: Tensor, window: int, use_sample_covariance: boo
             raise ValueError(f"{name}: expected a float32 {tuple(x.shape)} view on {dev}")
         outs.append(t)
     ws = torch.empty(max(_size("fsn_ssim_grad_workspace_doubles", None, N, Ch, H, W), 1), dtype=torch.float64, device=dev)
-    _launch("fsn_ssim_grad", dev, _p(x), _p(y), N, Ch, H, W, _nchw_strides(x), _nchw_strides(y), int(window),
-            1 if use_sample_covariance else 0, float(data_range), float(K1), float(K2), _p(up), _p(ws),
-            _p(outs[0]), None if outs[0] is None else _nchw_strides(outs[0]),
-            _p(outs[1]), None if outs[1] is None else _nchw_strides(outs[1]))
+    _launch("fsn_ssim_grad", dev, x, y, N, Ch, H, W, _nchw_strides(x), _nchw_strides(y), int(window),
+            1 if use_sample_covariance else 0, float(data_range), float(K1), float(K2), up, ws, outs[0],
+            None if outs[0] is None else _nchw_strides(outs[0]), outs[1], None if outs[1] is None else _nchw_strides(outs[1]))
     return outs[0], outs[1]
 
 
@@ -1714,7 +1774,7 @@ def psnr_nchw(x: Tensor, y: Tensor) -> Tensor:
     dev = x.device
     out = torch.empty(N + 1, dtype=torch.float32, device=dev)
     ws = torch.empty(max(_size("fsn_psnr_workspace_doubles", None, N, Ch, H, W), 1), dtype=torch.float64, device=dev)
-    _launch("fsn_psnr", dev, _p(x), _p(y), N, Ch, H, W, _nchw_strides(x), _nchw_strides(y), _p(ws), _p(out))
+    _launch("fsn_psnr", dev, x, y, N, Ch, H, W, _nchw_strides(x), _nchw_strides(y), ws, out)
     return out
 
 
@@ -1732,8 +1792,8 @@ def lpips_pack(conv_w: Sequence[Tensor], conv_b: Sequence[Tensor], lin_w: Sequen
     nbytes = _size("fsn_lpips_pack_bytes", None)
     if out is None or out.numel() != nbytes or out.device != dev:
         out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    _launch("fsn_lpips_pack", dev, _ptr_array(keep[:13]), _ptr_array(keep[13:26]), _ptr_array(keep[26:31]), _p(keep[31]),
-            _p(keep[32]), _p(out))
+    _launch("fsn_lpips_pack", dev, _ptr_array(keep[:13]), _ptr_array(keep[13:26]), _ptr_array(keep[26:31]), keep[31], keep[32],
+            out)
     return out
 
 
@@ -1747,8 +1807,8 @@ def lpips_vgg(packed: Tensor, x: Tensor, y: Tensor, normalize: bool) -> Tuple[Te
     out = torch.empty(N, dtype=torch.float32, device=dev)
     per = torch.empty(5, N, dtype=torch.float32, device=dev)
     ws = torch.empty(_size("fsn_lpips_workspace_floats", None, H, W), dtype=torch.float32, device=dev)
-    _launch("fsn_lpips_vgg", dev, _p(packed), _p(x), _p(y), N, H, W, _nchw_strides(x), _nchw_strides(y),
-            1 if normalize else 0, _p(out), _p(per), _p(ws))
+    _launch("fsn_lpips_vgg", dev, packed, x, y, N, H, W, _nchw_strides(x), _nchw_strides(y), 1 if normalize else 0, out, per,
+            ws)
     return out, per
 
 
@@ -1762,7 +1822,7 @@ def lpips_grad_pack(conv_w: Sequence[Tensor], out: Optional[Tensor] = None) -> T
     nbytes = _size("fsn_lpips_grad_pack_bytes", None)
     if out is None or out.numel() != nbytes or out.device != dev:
         out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    _launch("fsn_lpips_grad_pack", dev, _ptr_array(keep), _p(out))
+    _launch("fsn_lpips_grad_pack", dev, _ptr_array(keep), out)
     return out
 
 
@@ -1781,8 +1841,8 @@ def lpips_vgg_fwd_save(packed: Tensor, x: Tensor, y: Tensor, normalize: bool, *,
     per = torch.empty(5, B, dtype=torch.float32, device=dev)
     ws = torch.empty(_size("fsn_lpips_train_workspace_floats", None, B, H, W, int(want_dx), int(want_dy)),
                      dtype=torch.float32, device=dev)
-    _launch("fsn_lpips_vgg_fwd_save", dev, _p(packed), _p(x), _p(y), B, H, W, _nchw_strides(x), _nchw_strides(y),
-            1 if normalize else 0, int(want_dx), int(want_dy), _p(out), _p(per), _p(ws))
+    _launch("fsn_lpips_vgg_fwd_save", dev, packed, x, y, B, H, W, _nchw_strides(x), _nchw_strides(y), 1 if normalize else 0,
+            int(want_dx), int(want_dy), out, per, ws)
     return out, per, ws
 
 
@@ -1815,7 +1875,7 @@ def lpips_vgg_bwd(packed: Tensor, packed_grad: Tensor, workspace: Tensor, shape:
         elif t.dtype != torch.float32 or tuple(t.shape) != (B, 3, H, W) or t.device != dev:
             raise ValueError(f"{name}: expected a float32 {(B, 3, H, W)} view on {dev}")
         outs.append(t)
-    _launch("fsn_lpips_vgg_bwd", dev, _p(packed), _p(packed_grad), B, H, W, 1 if normalize else 0, int(want_dx),
-            int(want_dy), _p(up), _p(workspace), _p(outs[0]), None if outs[0] is None else _nchw_strides(outs[0]),
-            _p(outs[1]), None if outs[1] is None else _nchw_strides(outs[1]))
+    _launch("fsn_lpips_vgg_bwd", dev, packed, packed_grad, B, H, W, 1 if normalize else 0, int(want_dx), int(want_dy), up,
+            workspace, outs[0], None if outs[0] is None else _nchw_strides(outs[0]), outs[1],
+            None if outs[1] is None else _nchw_strides(outs[1]))
     return outs[0], outs[1]

@@ -1,8 +1,9 @@
-"""The two rules every wrapper of fs_nerf_amd.ops obeys, checked through its public surface:
+"""The rules every wrapper of fs_nerf_amd.ops obeys, checked through its public surface:
 1. a launch goes to the CURRENT stream of the tensors' device (the handle is read inside that device's guard);
 2. a tensor a conversion made (a float64 mask cast to float32, a non-contiguous `u` copied) stays alive until the call is
    enqueued - the outputs are allocated after it, and the caching allocator hands a dropped block to the next
-   torch.empty of its size class.
+   torch.empty of its size class;
+3. a tensor goes through the door as it is and is checked there against the header's declaration of the parameter.
 And the two measurement hooks (`ops.launch_timer`, `ops.clock_buffer`) that bench.py assigns from outside.
 
 Shapes: a 4 x 128 network, 40 rays, 8 + 8 samples, a 16^3 all-occupied grid with step 0.1.  Forty rays on purpose:
@@ -219,6 +220,42 @@ def test_converted_arguments_outlive_the_launch(dev, scene, fn):
     for i, (a, b) in enumerate(zip(got, want)):
         assert a.shape == b.shape and a.dtype == b.dtype and torch.equal(a, b), f"{fn}: returned tensor {i} differs"
     assert any(t.numel() > 0 and bool((t != 0).any()) for t in want), "the call rendered something"
+
+
+def test_the_door_checks_tensors_against_the_header(dev, scene, monkeypatch):
+    """3. a tensor handed to `_launch` where include/fsnerf_hip.h has a device pointer is checked against the pointee
+    before the C function is called: dtype (width and kind), contiguity, device.  None still arrives as NULL."""
+    from fs_nerf_amd import _lib, ops
+    rec = recorded(monkeypatch)
+    sig = scene["sig"].reshape(-1)
+    info = torch.empty(R, 2, dtype=torch.int64, device=dev)
+    out8 = torch.empty(R * S, dtype=torch.uint8, device=dev)
+    with pytest.raises(TypeError, match="fsn_pack_info: ray_indices: expected torch.int64"):  # const int64_t* ray_indices
+        ops._launch("fsn_pack_info", dev, torch.zeros(R * S, dtype=torch.int32, device=dev), R * S, R, info)
+    with pytest.raises(TypeError, match="fsn_to8b: out: expected torch.uint8"):               # uint8_t* out
+        ops._launch("fsn_to8b", dev, sig, R * S, torch.empty(R * S, dtype=torch.int8, device=dev))
+    with pytest.raises(ValueError, match="fsn_to8b: x: expected a contiguous tensor"):
+        ops._launch("fsn_to8b", dev, strided(sig), R * S, out8)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        ops._launch("fsn_to8b", dev, sig.cpu(), R * S, out8)
+    with pytest.raises(TypeError, match="takes 3 arguments"):
+        ops._launch("fsn_to8b", dev, sig, R * S)
+    h = ops._Held(_lib.RenderArgs())
+    with pytest.raises(TypeError, match="fsn_render_args: u: expected torch.float32"):          # const float* u
+        h.set("u", scene["u"].double())
+    with pytest.raises(ValueError, match="fsn_render_args: u: expected a contiguous tensor"):
+        h.set("u", strided(scene["u"]))
+    assert h.a.u is None and rec.calls == [], "every refusal comes before the call"
+    edges = torch.empty(R, S + 1, device=dev)
+    ops._launch("fsn_stratified_edges", dev, 2.0, 6.0, S, R, None, 0, edges)  # u = NULL: the deterministic edges
+    ops._launch("fsn_to8b", dev, sig, R * S, out8)
+    h.set("u", scene["u"])
+    torch.cuda.synchronize()
+    (n0, a0), (n1, a1) = rec.calls
+    assert n0 == "fsn_stratified_edges" and a0[4] is None and a0[6] == edges.data_ptr() and a0[:4] == (2.0, 6.0, S, R)
+    assert n1 == "fsn_to8b" and a1[:3] == (sig.data_ptr(), R * S, out8.data_ptr())
+    assert h.a.u == scene["u"].data_ptr()
+    assert torch.equal(edges[:, 0], torch.full((R,), 2.0, device=dev)) and torch.equal(out8, ops.to8b(sig))
 
 
 def test_measurement_hooks(dev, scene):
