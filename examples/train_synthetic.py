@@ -9,7 +9,7 @@ estimator.update_every_n_steps) and evaluated with render_frame + PSNR and SSIM 
                                        [--mark-invisible] [--min-views K] [--ssim-weight W --patch P --patches B]
                                        [--lpips-weight W --lpips-weights FILE]
                                        [--entropy-weight W] [--depth-kl-weight W --depth-kl-var V]
-                                       [--depth-smooth-weight W]
+                                       [--depth-smooth-weight W] [--unseen-views shell|box]
                                        [--refine-poses --pose-noise-rot DEG --pose-noise-trans X --pose-lr LR
                                         --c2f-until K]
 
@@ -29,7 +29,9 @@ extras["alphas"], the rays masked by the rendered opacity (InfoNeRF's ray entrop
 teacher hit something (DS-NeRF's depth term; float tables only, as --depth-weight).  --depth-smooth-weight:
 PatchDepthSmoothnessLoss on the rendered depth of --patches B patches of --patch P x P rays from a random orbit pose no
 photograph was taken from (RegNeRF's depth smoothness); their rays come from get_rays and ride in the same render_rays
-call, behind the ray batch and the SSIM / LPIPS patches.
+call, behind the ray batch and the SSIM / LPIPS patches.  --unseen-views shell|box: those patches are instead --patches
+freshly drawn poses' patches from nerfdata.UnseenPatchLoader, one launch per step, its pose distribution fitted to the
+training poses (UnseenViewSampler.from_poses); with --entropy-weight alone the entropy term covers their rays too.
 
 --cone-angle / --near-plane (both 0 by default): `sampling_kwargs` of render_rays / render_frame / render_path - the
 occupancy march's step grows with distance, dt = max(t * cone_angle, step), and nothing is sampled in front of the near
@@ -81,7 +83,8 @@ from fs_nerf_amd.core.loss import (DepthKLLoss, DistortionLoss, LPIPSLoss, Patch
                                    RayEntropyLoss, SSIMLoss, WeightNormRegularizer)
 from fs_nerf_amd.core.optim import FusedAdam  # noqa: E402
 from fs_nerf_amd.core.scheduler import ExponentialDecay  # noqa: E402
-from fs_nerf_amd.nerfdata import CameraRefiner, FrameLoader, PatchLoader, RayDataset, RayLoader, pose_error  # noqa: E402
+from fs_nerf_amd.nerfdata import (CameraRefiner, FrameLoader, PatchLoader, RayDataset, RayLoader, UnseenPatchLoader,  # noqa: E402
+                                  UnseenViewSampler, pose_error)
 from fs_nerf_amd.render import rendering as R  # noqa: E402
 from fs_nerf_amd.render.occgrid import OccGridEstimator  # noqa: E402
 from fs_nerf_amd.render.propnet import PropNetEstimator  # noqa: E402
@@ -156,6 +159,10 @@ def main():
     ap.add_argument("--depth-smooth-weight", type=float, default=0.0,
                     help="opt-in: weight of the depth smoothness of --patches patches of --patch x --patch rays from a random "
                          "unseen orbit pose (core.loss.PatchDepthSmoothnessLoss; render_rays(full_grad=True))")
+    ap.add_argument("--unseen-views", choices=("shell", "box"), default=None,
+                    help="opt-in: the rays of --depth-smooth-weight (and --entropy-weight on them) come from "
+                         "nerfdata.UnseenPatchLoader, one launch per step, its pose distribution fitted to the training "
+                         "poses (UnseenViewSampler.from_poses) - instead of the hard-coded orbit and a host generator")
     ap.add_argument("--cone-angle", type=float, default=0.0,
                     help="opt-in: the occupancy march's step grows with distance, dt = max(t * cone_angle, step) "
                          "(sampling_kwargs of render_rays / render_frame; nerfacc uses 0.004 for unbounded scenes)")
@@ -208,6 +215,8 @@ def main():
         ap.error("--depth-weight needs the float tables: the uint8 dataset carries no depth")
     if a.depth_kl_weight and a.u8_dataset:
         ap.error("--depth-kl-weight needs the float tables: the uint8 dataset carries no depth")
+    if a.unseen_views and not (a.depth_smooth_weight or a.entropy_weight):
+        ap.error("--unseen-views serves the rays of --depth-smooth-weight / --entropy-weight: set one of them")
     if a.depth_smooth_weight and a.patch < 2:
         ap.error("--depth-smooth-weight needs --patch of at least 2")
     full_grad = any(w != 0.0 for w in (a.depth_weight, a.distortion_weight, a.entropy_weight, a.depth_kl_weight,
@@ -281,6 +290,9 @@ def main():
     distortion = DistortionLoss()
     ray_entropy, depth_kl, depth_smooth = RayEntropyLoss(), DepthKLLoss(), PatchDepthSmoothnessLoss()
     pose_gen = torch.Generator().manual_seed(4)  # the unseen poses of --depth-smooth-weight
+    if a.unseen_views:
+        unseen_loader = UnseenPatchLoader(UnseenViewSampler.from_poses(torch.stack(poses), a.unseen_views, device=dev), hwf,
+                                          a.patch, a.patches, seed=4)
     scheduler = ExponentialDecay(optimizer, a.iters, 5e-4, r=0.1)
     gen = torch.Generator(device=dev).manual_seed(0)
 
@@ -313,7 +325,10 @@ def main():
                 patch_o, patch_d, patch_gt = next(patch_iterator)
             rays_o, rays_d = torch.cat([rays_o, patch_o]), torch.cat([rays_d, patch_d])
         n_seen = rays_o.shape[0]
-        if a.depth_smooth_weight:  # B windows of P x P rays of one random pose between the training views, behind the rest
+        if a.unseen_views:  # B patches of P x P rays of B freshly drawn poses in one launch, behind the rest
+            o, d = next(unseen_loader)
+            rays_o, rays_d = torch.cat([rays_o, o]), torch.cat([rays_d, d])
+        elif a.depth_smooth_weight:  # B windows of P x P rays of one random pose between the training views, behind the rest
             phi, theta = 360.0 * float(torch.rand((), generator=pose_gen)), 40.0 + 20.0 * float(torch.rand((), generator=pose_gen))
             o, d = U.get_rays(orbit_pose(phi, theta), hwf, dev)
             corner = torch.randint(0, a.hw - a.patch + 1, (a.patches, 2), generator=pose_gen)

@@ -1,6 +1,6 @@
 """ctypes binding of libfsnerf_hip.so, read from its C-ABI header (include/fsnerf_hip.h) once per process: the
 header is the only place an entry point, an argument struct or an FSN_* constant is written down.  `parse_header`
-gives, per symbol, every parameter's name, ctype and pointee; `SIGNATURES`, the three argument structs and the FSN_*
+gives, per symbol, every parameter's name, ctype and pointee; `SIGNATURES`, the argument structs and the FSN_*
 attributes are derived from that.  The parser is strict: a type outside its table, a statement outside its grammar or
 a non-integer FSN_* #define raises at import and quotes the text - nothing falls back to a void pointer.
 
@@ -118,6 +118,7 @@ def define_int(defines: dict, name: str) -> int:
 with open(HEADER) as _f:
     FUNCTIONS, STRUCTS, DEFINES = parse_header(_f.read())
 MlpDesc, RenderArgs, OccRenderArgs = STRUCTS["fsn_mlp_desc"], STRUCTS["fsn_render_args"], STRUCTS["fsn_occ_render_args"]
+UnseenDist = STRUCTS["fsn_unseen_dist"]
 # name -> (restype, argtypes); every symbol declared in include/fsnerf_hip.h
 SIGNATURES = {name: (ret.ctype, [p.ctype for p in params]) for name, (ret, params) in FUNCTIONS.items()}
 globals().update({name: define_int(DEFINES, name) for name in DEFINES})  # FSN_PREC_*, FSN_STATUS_*, FSN_SCAN_*, ...

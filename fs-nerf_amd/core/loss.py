@@ -101,8 +101,8 @@ class PatchDepthSmoothnessLoss:
         S_b = sum_{i < P-1, j < Q-1} (d[i,j] - d[i,j+1])^2 + (d[i,j] - d[i+1,j])^2,
     and the call returns mean_b S_b / ((P-1)(Q-1)) - 0 when P or Q is 1.  One launch forward, one backward
     (ops.patch_depth_smoothness); `depth` must carry a gradient itself: render_rays(..., full_grad=True).  The poses
-    are the caller's: examples/train_synthetic.py draws them from its orbit; a sampler class for unseen poses is not
-    built."""
+    are the caller's: nerfdata.UnseenPatchLoader serves such patches, one launch per batch, from a pose distribution
+    fitted to the training cameras (nerfdata.UnseenViewSampler.from_poses)."""
 
     def __call__(self, depth: Tensor) -> Tensor:
         per_patch = ops.patch_depth_smoothness(depth)

@@ -353,6 +353,40 @@ def ray_perm_host(n: int, seed: int, epoch: int, start: int = 0, count: Optional
     return out
 
 
+def unseen_poses(dist: L.UnseenDist, count: int, device, *, seed: int = 0, first: int = 0) -> Tensor:
+    """Pose draws [first, first + count) of the distribution `dist` (a filled fsn_unseen_dist; nerfdata.UnseenViewSampler
+    builds it) in ONE launch (fsn_unseen_poses) -> poses12 [count,12] on `device`: a pure function of (dist, seed, draw)."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("unseen_poses: expected a GPU device (the HIP path has no CPU fallback)")
+    out = torch.empty(int(count), 12, device=dev, dtype=torch.float32)
+    _launch("fsn_unseen_poses", dev, C.byref(dist), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), int(count), out)
+    return out
+
+
+def unseen_patch_batch(dist: L.UnseenDist, H: int, W: int, focal: float, patch: int, dilation: int = 1, *, device,
+                       first_patch: int = 0, count: int, patches_per_pose: int = 1, seed: int = 0, ndc: bool = False,
+                       near: float = 1.0, want_rays: bool = True, want_poses: bool = False, want_anchors: bool = False):
+    """`count` patches of `patch` x `patch` rays of freshly drawn poses in ONE launch (fsn_unseen_patch_batch), no host
+    synchronisation: patch q = first_patch + b is seen from pose draw q // patches_per_pose of `dist` at an anchor uniform
+    over the (H - ext + 1) x (W - ext + 1) lattice, ext = (patch - 1) * dilation + 1 -> (rays_o, rays_d [count * patch^2,
+    3], poses12 [count,12], anchors [count] int64 = row0 * (W - ext + 1) + col0); an output not asked for is None.  The
+    rows are those of ray_patch_batch over `poses12` with the explicit anchors b * (H - ext + 1) * (W - ext + 1) +
+    anchors[b], bit for bit."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("unseen_patch_batch: expected a GPU device (the HIP path has no CPU fallback)")
+    count, rows = int(count), int(count) * int(patch) * int(patch)
+    o = torch.empty(rows, 3, device=dev, dtype=torch.float32) if want_rays else None
+    d = torch.empty(rows, 3, device=dev, dtype=torch.float32) if want_rays else None
+    poses = torch.empty(count, 12, device=dev, dtype=torch.float32) if want_poses else None
+    anchors = torch.empty(count, device=dev, dtype=torch.int64) if want_anchors else None
+    _launch("fsn_unseen_patch_batch", dev, C.byref(dist), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_patch), count,
+            int(patches_per_pose), int(H), int(W), float(focal), int(patch), int(dilation), 1 if ndc else 0, float(near),
+            o, d, poses, anchors)
+    return o, d, poses, anchors
+
+
 def _pose_pair(poses0: Tensor, xi: Tensor, who: str) -> None:
     """The stored poses [n,12] and their corrections [n,6] as the pose kernels read them: nothing is cast or copied
     (xi is a parameter: a conversion would hide it from the caller)."""

@@ -180,6 +180,54 @@ int fsn_ray_pose_grad(const float* poses0, const float* xi, int64_t n_views, int
                       double near, const int64_t* index, const float* grad_o, const float* grad_d, int64_t count,
                       float* grad_xi, float* grad_poses, fsn_stream_t stream);
 
+/* ---- unseen views: random poses and their patch rays (this package's own, after RegNeRF's)
+ *                                                                                              csrc/unseen_views.hip
+ * Pose draw g of a distribution is a pure function of (dist, seed, g): no state on the device or the host, no
+ * transcendental function, every operation a float32 +, -, *, / or sqrtf in the order of csrc/unseen_views.hip (the
+ * library is built with -ffp-contract=off), so tests/unseen_ref.py restates it bit for bit in NumPy.
+ *   bits(g, slot) = mix(mix(seed ^ mix(g)) + slot), mix = the splitmix64 finaliser of csrc/ray_perm.hpp;
+ *   u(g, slot) = (bits >> 40) * 2^-24 in [0, 1).  Slots of a pose draw g: 0, 1, 2 origin; 3, 4, 5 target; 6 + 2k, 7 + 2k
+ *   the k-th try (k < 16) of the azimuth's disc rejection.  Slots of a PATCH q: 38 anchor row, 39 anchor column.
+ * mode FSN_UNSEEN_SHELL: z = min(z_lo + u0 (z_hi - z_lo), z_hi), r = min(r_lo + u1 (r_hi - r_lo), r_hi), (c, s) = (a, b) /
+ *   sqrt(a^2 + b^2) of the first try (a, b) = (2 u - 1, 2 u' - 1) with 0 < a^2 + b^2 <= 1, (1, 0) after 16 failures;
+ *   h = sqrt(1 - z z); origin = centre + r ((h c e1 + h s e2) + z up).  Needs -1 < z_lo <= z_hi < 1, 0 <= r_lo <= r_hi.
+ * mode FSN_UNSEEN_BOX: origin_k = min(lo_k + u_k (hi_k - lo_k), hi_k), k = 0, 1, 2.  Needs lo <= hi.
+ * Both: target_k = focus_k + jitter (2 u_{3+k} - 1); v = origin - target, zc = v / |v| (up when |v|^2 < 1e-20);
+ *   x = up x zc (e1 x zc when |up x zc|^2 < 1e-8), xc = x / |x|, yc = zc x xc; the pose is rows [xc_k yc_k zc_k origin_k]:
+ *   the camera looks down its own -z with y up, the convention of fsn_get_rays.  (e1, e2, up) is an orthonormal frame,
+ *   which the caller provides; the entry points check the ranges above, finiteness and jitter >= 0. */
+#define FSN_UNSEEN_SHELL 0
+#define FSN_UNSEEN_BOX 1
+typedef struct fsn_unseen_dist {
+  int32_t mode;
+  float jitter;
+  float focus[3];
+  float up[3];
+  float e1[3];
+  float e2[3];
+  float centre[3]; /* shell */
+  float r_lo, r_hi, z_lo, z_hi;
+  float lo[3]; /* box */
+  float hi[3];
+} fsn_unseen_dist;
+/* Pose draws [first_draw, first_draw + count) -> poses_out [count, 12] (DEVICE), one thread per pose.
+ * Errors (FSN_E_INVALID): a null pointer, negative first_draw or count, a distribution outside the ranges above. */
+int fsn_unseen_poses(const fsn_unseen_dist* dist_host, uint64_t seed, int64_t first_draw, int64_t count, float* poses_out,
+                     fsn_stream_t stream);
+/* `count` patches of P x P rays of freshly drawn poses in ONE launch, one thread per output row (b*P + i)*P + j: patch
+ * q = first_patch + b is seen from pose draw g = q / patches_per_pose; its anchor (row0, col0) is uniform on the
+ * AH x AW lattice, AH = H - ext + 1, AW = W - ext + 1, ext = (P-1)*dilation + 1: row0 = (hi32(bits(q, 38)) * AH) >> 32,
+ * col0 = (hi32(bits(q, 39)) * AW) >> 32; the row is the ray of pixel (row0 + i*dilation, col0 + j*dilation) over that
+ * pose - H, W, focal, ndc, near and the arithmetic are those of fsn_ray_patch_batch, whose rows over poses_out with the
+ * explicit anchors b*AH*AW + anchors_out[b] these are bit for bit.  Every thread recomputes its patch's pose: no LDS, no
+ * atomics, no index is read.  Outputs (DEVICE): rays_o, rays_d [count*P*P, 3] (either may be NULL, not both with the
+ * other two), poses_out [count, 12] and anchors_out [count] int64 = row0*AW + col0 (each may be NULL).
+ * Errors (FSN_E_INVALID): those of fsn_unseen_poses, P < 1, dilation < 1, patches_per_pose < 1, ext > H or ext > W, null
+ * pointer for every output; FSN_E_UNSUPPORTED: more than 2^38 rows in one call. */
+int fsn_unseen_patch_batch(const fsn_unseen_dist* dist_host, uint64_t seed, int64_t first_patch, int64_t count,
+                           int64_t patches_per_pose, int H, int W, double focal, int P, int dilation, int ndc, double near,
+                           float* rays_o, float* rays_d, float* poses_out, int64_t* anchors_out, fsn_stream_t stream);
+
 /* ---- a4: PositionalEncoder.forward(x)                    src/core/models.py:43-50
  * x [n, d_in] -> out [n, d_in*(1+2*n_freqs)], block order x, sin f0, cos f0, sin f1, ...
  * freqs_host: n_freqs float32 values (models.py:31-34).  mask (device, [d_out]) may be NULL:
