@@ -1,10 +1,8 @@
 // mlp.hip — weight packing (host + device) and the standalone NeRF.forward kernel.
 // reference: src/core/models.py:53-143 (NeRF), state_dict layout SURVEY.md 8a (a5).
 #include "common.hpp"
-// x3 modes: pinned one-unit-ahead LDS prefetch of the A operands (mlp_dev.hpp).  +6 % on these kernels; the fused
-// render kernel keeps the compiler's own read placement (with its larger live state the pinned form spills more).
-#define FSN_X3_PF1
-#define FSN_BF16X3_ONEACC 1  // inference: bf16x3 accumulates its three products in one tile (mlp_dev.hpp)
+// The kernels here are fsn::VariantStandalone (mlp_dev.hpp): compiler-scheduled k-loop with the x3 modes' pinned
+// one-unit-ahead prefetch, bf16x3 on one accumulator.
 #include "mlp_dev.hpp"
 #include "mlp_layout.hpp"
 #include "mlp_pack.hpp"
@@ -82,7 +80,7 @@ __global__ __launch_bounds__(kThreads) void k_mlp_fwd(MlpFwdArgs a) {
   st.init(smem, nullptr, 0, 0, sbase, (uint32_t)(full ? a.net.nph_full : a.net.nph_density), 1);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   ARing ring;
-  prime_ring<PREC, NT>(st, ring);
+  prime_ring<VariantStandalone, PREC, NT>(st, ring);
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     // each wave stages (and later reads) only its own 16 NG samples: no workgroup barrier
     if (lane < 16 * NG) {
@@ -101,7 +99,7 @@ __global__ __launch_bounds__(kThreads) void k_mlp_fwd(MlpFwdArgs a) {
     TileSrc src[NG];
     FSN_PER_GROUP(q, src[q] = TileSrc{in_lds + tile_slot<NG>(wave, lane, q) * 6};);
     float sigma[NG], rgb[NG][3] = {};
-    mlp_tile<NT, PREC, FULL>(st, net, src, ring, sigma, rgb);
+    mlp_tile<VariantStandalone, NT, PREC, FULL>(st, net, src, ring, sigma, rgb);
     // (One condition here, the store group formed twice, where the other kernels nest `if (tile_stores)` around the
     // slot: with the nested form hipcc spills ~30 more SGPRs in this kernel's one-group x3 instances - <4, fp16x3, full>
     // 45 -> 77 - and the conjunction costs the others.  Same predicate either way.)
@@ -165,7 +163,7 @@ __global__ __launch_bounds__(kThreads) void k_mlp_maxima(MlpFwdArgs a, float* __
   st.init(smem, nullptr, 0, 0, a.net.blob + a.net.stream_off, (uint32_t)a.net.nph_full, 1);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   ARing ring;
-  prime_ring<PREC, NT>(st, ring);
+  prime_ring<VariantStandalone, PREC, NT>(st, ring);
   const MaxSave sv{max_lds + wave * NSLOT};
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     if (lane < 16) {
@@ -178,7 +176,7 @@ __global__ __launch_bounds__(kThreads) void k_mlp_maxima(MlpFwdArgs a, float* __
     __builtin_amdgcn_wave_barrier();
     const TileSrc src[1] = {{in_lds + tile_slot<1>(wave, lane, 0) * 6}};
     float sigma[1], rgb[1][3] = {};
-    mlp_tile<NT, PREC, true>(st, net, src, ring, sigma, rgb, sv);
+    mlp_tile<VariantStandalone, NT, PREC, true>(st, net, src, ring, sigma, rgb, sv);
   }
   st.drain();
   __syncthreads();
@@ -300,7 +298,8 @@ extern "C" int fsn_mlp_layer_maxima(const fsn_mlp_desc* desc, int prec, const vo
                                     const float* pos_mask, const float* dir_mask, int64_t n, float* maxima,
                                     fsn_stream_t stream) {
   FSN_REQUIRE(desc && n >= 0, FSN_E_INVALID, "fsn_mlp_layer_maxima: bad arguments");
-  FSN_REQUIRE(prec == FSN_PREC_BF16X3 || prec == FSN_PREC_FP16X3U, FSN_E_UNSUPPORTED,
+  using Modes = PrecModes<FSN_PREC_BF16X3, FSN_PREC_FP16X3U>;
+  FSN_REQUIRE(prec_in(Modes{}, prec), FSN_E_UNSUPPORTED,
               "fsn_mlp_layer_maxima: precision mode %d (FSN_PREC_BF16X3 or FSN_PREC_FP16X3U)", prec);
   NetGeom G;
   const char* why;
@@ -315,6 +314,6 @@ extern "C" int fsn_mlp_layer_maxima(const fsn_mlp_desc* desc, int prec, const vo
   a.x = x; a.dirs = dirs; a.pos_mask = pos_mask; a.dir_mask = dir_mask; a.n = n;
   a.net = net_params(*desc, G, blob, nullptr);
   hipStream_t s = as_stream(stream);
-  return dispatch_net(PrecModes<FSN_PREC_BF16X3, FSN_PREC_FP16X3U>{}, desc->d_hidden, prec,
+  return dispatch_net(Modes{}, desc->d_hidden, prec,
                       [&](auto NT, auto PREC) { return launch_mlp_maxima<NT(), PREC()>(a, maxima, cus, s); });
 }

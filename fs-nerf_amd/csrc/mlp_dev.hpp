@@ -25,10 +25,10 @@
 #pragma once
 #include "common.hpp"
 #include "mlp_layout.hpp"
-#ifndef FSN_KLOOP_HEADER
-#define FSN_KLOOP_HEADER "kloop_gen.hpp"
+#include "kloop_gen.hpp"
+#if defined(FSN_KLOOP_ASM) || defined(FSN_X3_PF1) || defined(FSN_BF16X3_ONEACC)
+#error "FSN_KLOOP_ASM / FSN_X3_PF1 / FSN_BF16X3_ONEACC are gone: name a variant type at the call (MlpVariant: VariantStandalone, VariantFused, VariantTrain, VariantPlain in mlp_dev.hpp)"
 #endif
-#include FSN_KLOOP_HEADER
 
 #include <type_traits>
 #include <utility>
@@ -100,11 +100,31 @@ __host__ __device__ constexpr int64_t t_layout_off(int NPL, int P, int pr, int s
   return (((int64_t)(s >> 4) * P + pr) * kTRow + (s & 15)) * NPL;
 }
 
+// ---------------------------------------------------------------- kernel variants
+// What the templates below contain beyond <NT, PREC> is chosen by a policy type that every caller names as the first
+// template argument of unit_mfma(_r), pair_epilogue, gemm_layer(_two_groups), prime_ring and mlp_tile:
+//   kKloopAsm      x3 / x2 modes of 256-wide networks run the hand-scheduled k-loop blocks (kloop_gen.hpp): one inline-asm
+//                  block per output pair, A operands two units ahead in three register sets, counted waits, the weight-
+//                  phase openings inside the stream.  The fused render kernels only: in the training forward they
+//                  spill 38 VGPRs (profiles/EXPERIMENTS_r4.md section 3: 2.936 against 2.883 ms).
+//   kX3Pf1         x3 modes on the compiler-scheduled loop: pinned one-unit-ahead LDS prefetch of the A operands.  +6 %
+//                  on the standalone and training kernels; the fused render kernel's 128-wide networks keep the
+//                  compiler's own read placement (with its larger live state the pinned form spills more).
+//   kBf16x3OneAcc  FSN_PREC_BF16X3 (low parts unscaled anyway) accumulates its three products in ONE tile, no merge, as
+//                  FSN_PREC_FP16X3U does: 383.3 against 399.3 ms per headline frame.  Inference only - training keeps the
+//                  main + correction pair, so bf16x3 is two arithmetics (DESIGN.md section 5 / 10.2 prices the other).
+template <bool KLOOP_ASM, bool X3_PF1, bool BF16X3_ONE_ACC>
+struct MlpVariant {
+  static constexpr bool kKloopAsm = KLOOP_ASM, kX3Pf1 = X3_PF1, kBf16x3OneAcc = BF16X3_ONE_ACC;
+};
+using VariantStandalone = MlpVariant<false, true, true>;  // mlp.hip: k_mlp_fwd, k_mlp_maxima
+using VariantFused = MlpVariant<true, false, true>;       // render.hip, render_occ.hip: k_render_fused, k_bare_stream, k_render_occ
+using VariantTrain = MlpVariant<false, true, false>;      // train_fused.hip: k_train_fwd, k_train_bwd
+using VariantPlain = MlpVariant<false, false, false>;     // occ_refresh.hip: k_occ_refresh (single-pass modes: none applies)
+
 // (properties of an arithmetic mode that host and device share: mlp_layout.hpp, prec_is_x3 ...)
-#ifndef FSN_BF16X3_ONEACC  // bf16x3 (low parts unscaled anyway) on the one-accumulator form too in the INFERENCE kernels:
-#define FSN_BF16X3_ONEACC 0  // 383.3 against 399.3 ms per headline frame (render.hip / render_occ.hip / mlp.hip set it)
-#endif
-constexpr bool prec_one_acc(int P) { return P == FSN_PREC_FP16X3U || (FSN_BF16X3_ONEACC && P == FSN_PREC_BF16X3); }  // one accumulator per tile, no merge
+template <class V>
+constexpr bool prec_one_acc(int P) { return P == FSN_PREC_FP16X3U || (V::kBf16x3OneAcc && P == FSN_PREC_BF16X3); }  // one accumulator per tile, no merge
 
 struct Frag {  // one k-step (32 features x 16 samples) of activations as MFMA B operand
   s16x8 hi, lo;
@@ -426,11 +446,10 @@ inline NetParams net_params(const fsn_mlp_desc& d, const NetGeom& G, const void*
 }
 
 // Host-side dispatch from (d_hidden, prec) to the <NT, PREC> instantiation of an entry point.  MODES is the list of
-// arithmetic modes the entry point instantiates; f(NT, PREC) receives both as std::integral_constant (NT = 8 for
+// arithmetic modes the entry point instantiates (PrecModes, mlp_layout.hpp); f(NT, PREC) receives both as std::integral_constant (NT = 8 for
 // d_hidden 256, 4 for 128) and returns the entry point's code.  Anything else is FSN_E_UNSUPPORTED - unreachable behind
-// the entry points' own argument checks (build_geom and their FSN_REQUIRE on prec), which give the message.
-template <int... MODES>
-struct PrecModes {};
+// the entry points' own argument checks (build_geom and their FSN_REQUIRE on prec_in of the same list), which give the
+// message.
 template <int... MODES, class F>
 inline int dispatch_net(PrecModes<MODES...>, int d_hidden, int prec, F&& f) {
   int rc = FSN_E_UNSUPPORTED;
@@ -451,8 +470,6 @@ inline int dispatch_prec(PrecModes<MODES...>, int prec, F&& f) {
   (void)(mode(std::integral_constant<int, MODES>{}) || ...);
   return rc;
 }
-using PrecInference = PrecModes<FSN_PREC_BF16X3, FSN_PREC_BF16, FSN_PREC_FP16X3, FSN_PREC_FP16, FSN_PREC_FP16X3U, FSN_PREC_FP16X2>;
-using PrecTraining = PrecModes<FSN_PREC_BF16X3, FSN_PREC_BF16, FSN_PREC_FP16X3, FSN_PREC_FP16>;
 
 struct NetDev {
   const float* aux;       // LDS copy of the blob's aux region
@@ -587,24 +604,24 @@ __device__ __forceinline__ void load_afrag(const char* p, AFrag& f) {
   if (prec_reads_w_lo(PREC)) f.lo = *reinterpret_cast<const s16x8*>(p + 1024);
 }
 // acc: main sum (high x high); cor: the correction products (x3 modes; scaled by 2^11 in the fp16 modes)
-template <int PREC>
+template <class V, int PREC>
 __device__ __forceinline__ void unit_mfma_r(const AFrag& a, const Frag& b, f32x4& acc, f32x4& cor) {
   constexpr bool F16 = prec_is_f16(PREC), X3 = prec_is_x3(PREC);
   acc = mfma16<F16>(a.hi, b.hi, acc);
   if (X3) {
-    f32x4& c = prec_one_acc(PREC) ? acc : cor;  // (FSN_PREC_FP16X3U: everything into the main tile)
+    f32x4& c = prec_one_acc<V>(PREC) ? acc : cor;  // (FSN_PREC_FP16X3U: everything into the main tile)
     if (prec_reads_w_lo(PREC)) c = mfma16<F16>(a.lo, b.hi, c);  // (fp16x2: the weights' low parts are dropped)
     c = mfma16<F16>(a.hi, b.lo, c);
   }
 }
 
-template <int PREC>
+template <class V, int PREC>
 __device__ __forceinline__ void unit_mfma(const char* ubase, const Frag& b, f32x4& acc, f32x4& cor) {
   constexpr bool F16 = prec_is_f16(PREC), X3 = prec_is_x3(PREC);
   const s16x8 ah = *reinterpret_cast<const s16x8*>(ubase);
   acc = mfma16<F16>(ah, b.hi, acc);
   if (X3) {
-    f32x4& c = prec_one_acc(PREC) ? acc : cor;
+    f32x4& c = prec_one_acc<V>(PREC) ? acc : cor;
     if (prec_reads_w_lo(PREC)) {
       const s16x8 al = *reinterpret_cast<const s16x8*>(ubase + 1024);
       c = mfma16<F16>(al, b.hi, c);
@@ -631,13 +648,13 @@ struct NoHook {
 
 // Epilogue of one finished output pair (shared by the compiler-scheduled and the hand-scheduled k-loops).
 // acc0 / acc1: main sums of the pair's two tiles; cor0 / cor1: their correction sums (x3 modes, else unused).
-template <int PREC, int NP_OUT, int EPI, int NOUT, class HK>
+template <class V, int PREC, int NP_OUT, int EPI, int NOUT, class HK>
 __device__ __forceinline__ void pair_epilogue(const NetDev& net, int tp, const f32x4& acc0, const f32x4& acc1,
                                               const f32x4& cor0, const f32x4& cor1, Frag (&out)[NOUT], Heads& heads,
                                               int g, HK& hk) {
   constexpr bool F16 = prec_is_f16(PREC), X3 = prec_is_x3(PREC), LS = prec_lo_scaled(PREC);
     float v[8];
-    if constexpr (X3 && !prec_one_acc(PREC)) {
+    if constexpr (X3 && !prec_one_acc<V>(PREC)) {
       // value = main + 2^-11 x corrections (fp16 modes: exact power-of-two unscaling inside the fma); bf16: scale 1
       constexpr float IK = F16 ? 1.0f / kLoScaleF16 : 1.0f;
       // eight v_fma_f32: measured 0.6 % faster on the frame than four v_pk_fma_f32 (418.7 -> 416.2 ms), as
@@ -703,7 +720,7 @@ __device__ __forceinline__ void pair_epilogue(const NetDev& net, int tp, const f
       // split is plain C++.
       // (FSN_PREC_FP16X3U has no merge: where the epilogue has no ReLU either - the connection layer - v[] ARE the
       // accumulators, and the asm split must not read them: the C++ form there)
-      if constexpr (prec_one_acc(PREC) && (EPI == EPI_CVT || EPI == EPI_NONE)) split_store_cpp<F16, X3, LS>(v, o);
+      if constexpr (prec_one_acc<V>(PREC) && (EPI == EPI_CVT || EPI == EPI_NONE)) split_store_cpp<F16, X3, LS>(v, o);
       else split_store<F16, X3, LS>(v, o);
       if constexpr (F16) range_track<EPI == EPI_CVT || EPI == EPI_NONE>(heads.rs.fmax, o.hi);
       if (X3) asm volatile("" : "+v"(o.hi), "+v"(o.lo));
@@ -723,16 +740,9 @@ __device__ __forceinline__ void pair_epilogue(const NetDev& net, int tp, const f
 }
 
 // ---------------------------------------------------------------- hand-scheduled k-loop blocks (kloop_gen.hpp)
-// FSN_KLOOP_ASM (defined by the translation unit) selects them for the x3 / x2 modes of 256-wide networks: one
-// inline-asm block per output pair with the A operands two units ahead of their MFMAs (three register sets in
-// rotation), counted waits, and the weight-phase openings inside the stream.  tools/gen_kloop.py documents the
-// operand contract.  The blocks exist for (units per pair, offset of the pair's first unit inside a phase):
-// 16/0 (256->256), 20/0,4 (skip layer), 18/0,2,4,6 (branch), 4/0,4 (first layer).
-#ifdef FSN_KLOOP_ASM
-constexpr bool kKloopAsm = true;
-#else
-constexpr bool kKloopAsm = false;
-#endif
+// V::kKloopAsm (MlpVariant above) selects them for the x3 / x2 modes of 256-wide networks.  tools/gen_kloop.py
+// documents the operand contract.  The blocks exist for (units per pair, offset of the pair's first unit inside a
+// phase): 16/0 (256->256), 20/0,4 (skip layer), 18/0,2,4,6 (branch), 4/0,4 (first layer).
 
 template <int N, class F, int... I>
 __device__ __forceinline__ void static_for_impl(F& f, std::integer_sequence<int, I...>) {
@@ -866,7 +876,7 @@ __device__ __forceinline__ void kloop_block(WStream& st, const Frag (&act)[NACT]
 //   EPI_CVT      : out[tp] = split(acc)                                        (connection)
 //   EPI_RGB      : heads.rgb[c] += w_rgb[c] . relu(acc)                        (branch)
 //   EPI_NONE     : nothing (the hook consumes the values; last GEMM of the backward chain)
-template <int PREC, int NP_OUT, int KS_ACT, int KS_ENC, int EPI, int NACT, int NENC, int NOUT, class HK>
+template <class V, int PREC, int NP_OUT, int KS_ACT, int KS_ENC, int EPI, int NACT, int NENC, int NOUT, class HK>
 __device__ __forceinline__ void gemm_layer(WStream& st, const NetDev& net, int aux_bias, const Frag (&act)[NACT],
                                            const Frag (&enc)[NENC], Frag (&out)[NOUT], Heads& heads, ARing& ring,
                                            int g, HK& hk) {
@@ -875,21 +885,17 @@ __device__ __forceinline__ void gemm_layer(WStream& st, const NetDev& net, int a
   // forward passes (bias-initialised accumulators; the backward chain starts from zero) also check the layer's scale
   constexpr bool kConverts = EPI == EPI_RELU_CVT || EPI == EPI_CVT || EPI == EPI_LAST_FULL;
   constexpr bool kCheckSmall = X3 && !HK::kZeroInit;
-  constexpr uint32_t kSmallThr = prec_one_acc(PREC) ? kSmallBitsU : kSmallBits;
+  constexpr uint32_t kSmallThr = prec_one_acc<V>(PREC) ? kSmallBitsU : kSmallBits;
   static_assert(kLead >= 2, "the A-operand prefetch distance (one k-step = two units) must not exceed the phase lead");
   constexpr bool PREFETCH = !X3;
-#ifdef FSN_X3_PF1
-  constexpr bool kX3Pf1 = X3;
-#else
-  constexpr bool kX3Pf1 = false;
-#endif
+  constexpr bool kX3Pf1 = V::kX3Pf1 && X3;
   constexpr int UPP = X3 ? 8 : 16;
   constexpr int UB = X3 ? 2048 : 1024;
   constexpr int KS = KS_ACT + KS_ENC;
   constexpr int TOTAL = 2 * NP_OUT * KS;
   static_assert(KS_ACT <= NACT && KS_ENC <= NENC, "operand arrays too small");
   const float* bias = net.aux + aux_bias;
-  if constexpr (kKloopAsm && X3 && (KS == 8 || KS == 10 || KS == 9 || KS == 2) &&
+  if constexpr (V::kKloopAsm && X3 && (KS == 8 || KS == 10 || KS == 9 || KS == 2) &&
                 (KS_ACT == 8 || (KS_ACT == 0 && NP_OUT == 8)) && !HK::kZeroInit) {
     // hand-scheduled path (256-wide networks): ring.cur[0], cur[1] hold this GEMM's units 0 and 1 on entry and the
     // next GEMM's on exit; inside, the three A sets rotate by NU units per pair (compile-time indices).  The pairs
@@ -914,13 +920,13 @@ __device__ __forceinline__ void gemm_layer(WStream& st, const NetDev& net, int a
       const uint64_t ts0 = __builtin_amdgcn_s_memtime();
 #endif
       const uint32_t abn = bias_lds + 128u * (tp + 1 < NP_OUT ? tp + 1 : tp);  // (last pair: a harmless reload)
-      kloop_block<F16, !prec_reads_w_lo(PREC) ? 1 : (prec_one_acc(PREC) ? 2 : 0), KS_ACT, KS_ENC, OFF, PAR>(st, act, enc, acc, abn, ring.cur[R0], ring.cur[(R0 + 1) % NS],
+      kloop_block<F16, !prec_reads_w_lo(PREC) ? 1 : (prec_one_acc<V>(PREC) ? 2 : 0), KS_ACT, KS_ENC, OFF, PAR>(st, act, enc, acc, abn, ring.cur[R0], ring.cur[(R0 + 1) % NS],
                                                             ring.cur[(R0 + 2) % NS]);
 #ifdef FSN_STAMP
       const uint64_t ts1 = __builtin_amdgcn_s_memtime();
 #endif
-      if constexpr (PAR == 0) pair_epilogue<PREC, NP_OUT, EPI>(net, tp, acc.e0, acc.e1, acc.c0, acc.c1, out, heads, g, hk);
-      else pair_epilogue<PREC, NP_OUT, EPI>(net, tp, acc.o0, acc.o1, acc.c0, acc.c1, out, heads, g, hk);
+      if constexpr (PAR == 0) pair_epilogue<V, PREC, NP_OUT, EPI>(net, tp, acc.e0, acc.e1, acc.c0, acc.c1, out, heads, g, hk);
+      else pair_epilogue<V, PREC, NP_OUT, EPI>(net, tp, acc.o0, acc.o1, acc.c0, acc.c1, out, heads, g, hk);
 #ifdef FSN_STAMP
       {
         const uint64_t ts2 = __builtin_amdgcn_s_memtime();
@@ -978,8 +984,8 @@ __device__ __forceinline__ void gemm_layer(WStream& st, const NetDev& net, int a
                                       : st.n_base + (v - TOTAL) * UB;
         load_afrag<PREC>(src, nxt[0]);
         load_afrag<PREC>(src + UB, nxt[1]);
-        unit_mfma_r<PREC>(ring.cur[0], b, acc0, cor0);
-        unit_mfma_r<PREC>(ring.cur[1], b, acc1, cor1);
+        unit_mfma_r<V, PREC>(ring.cur[0], b, acc0, cor0);
+        unit_mfma_r<V, PREC>(ring.cur[1], b, acc1, cor1);
         ring.cur[0] = nxt[0];
         ring.cur[1] = nxt[1];
         __builtin_amdgcn_sched_group_barrier(0x100, X3 ? 4 : 2, 0);  // DS reads
@@ -997,8 +1003,8 @@ __device__ __forceinline__ void gemm_layer(WStream& st, const NetDev& net, int a
                                         : st.n_base + (v - TOTAL) * UB;
           AFrag nxt;
           load_afrag<PREC>(src, nxt);
-          if (sub == 0) unit_mfma_r<PREC>(ring.cur[0], b, acc0, cor0);
-          else unit_mfma_r<PREC>(ring.cur[0], b, acc1, cor1);
+          if (sub == 0) unit_mfma_r<V, PREC>(ring.cur[0], b, acc0, cor0);
+          else unit_mfma_r<V, PREC>(ring.cur[0], b, acc1, cor1);
           ring.cur[0] = nxt;
           __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // DS reads
           __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);  // MFMAs
@@ -1012,12 +1018,12 @@ __device__ __forceinline__ void gemm_layer(WStream& st, const NetDev& net, int a
           if (((u + kLead) % UPP == 0 && u + kLead <= TOTAL) || (u + kLead == TOTAL && TOTAL % UPP != 0)) st.open_next();
           if (u % UPP == 0) st.enter_phase();
           const char* ub = st.c_base + (u % UPP) * UB;
-          if (sub == 0) unit_mfma<PREC>(ub, b, acc0, cor0);
-          else unit_mfma<PREC>(ub, b, acc1, cor1);
+          if (sub == 0) unit_mfma<V, PREC>(ub, b, acc0, cor0);
+          else unit_mfma<V, PREC>(ub, b, acc1, cor1);
         }
       }
     }
-    pair_epilogue<PREC, NP_OUT, EPI>(net, tp, acc0, acc1, cor0, cor1, out, heads, g, hk);
+    pair_epilogue<V, PREC, NP_OUT, EPI>(net, tp, acc0, acc1, cor0, cor1, out, heads, g, hk);
   }
   if constexpr (F16 && kConverts) {
     if constexpr (HK::kLayerEnd) hk.layer_end(heads.rs.fmax);
@@ -1025,12 +1031,12 @@ __device__ __forceinline__ void gemm_layer(WStream& st, const NetDev& net, int a
   }
 }
 
-template <int PREC, int NP_OUT, int KS_ACT, int KS_ENC, int EPI, int NACT, int NENC, int NOUT>
+template <class V, int PREC, int NP_OUT, int KS_ACT, int KS_ENC, int EPI, int NACT, int NENC, int NOUT>
 __device__ __forceinline__ void gemm_layer(WStream& st, const NetDev& net, int aux_bias, const Frag (&act)[NACT],
                                            const Frag (&enc)[NENC], Frag (&out)[NOUT], Heads& heads, ARing& ring,
                                            int g) {
   NoHook hk;
-  gemm_layer<PREC, NP_OUT, KS_ACT, KS_ENC, EPI>(st, net, aux_bias, act, enc, out, heads, ring, g, hk);
+  gemm_layer<V, PREC, NP_OUT, KS_ACT, KS_ENC, EPI>(st, net, aux_bias, act, enc, out, heads, ring, g, hk);
 }
 
 // ---------------------------------------------------------------- two sample groups per wave (single-pass modes)
@@ -1041,7 +1047,7 @@ __device__ __forceinline__ void gemm_layer(WStream& st, const NetDev& net, int a
 // (The NG == 2 body behind mlp_tile's FSN_GEMM_LAYER; nothing else calls it.  The k-loops really differ - one group:
 // the hand-scheduled x3 blocks or the prefetch paths; two groups: every A operand shared by four MFMAs - so each keeps
 // its body.)
-template <int PREC, int NP_OUT, int KS_ACT, int KS_ENC, int EPI, int NACT, int NENC, int NOUT>
+template <class V, int PREC, int NP_OUT, int KS_ACT, int KS_ENC, int EPI, int NACT, int NENC, int NOUT>
 __device__ __forceinline__ void gemm_layer_two_groups(WStream& st, const NetDev& net, int aux_bias,
                                                       const Frag (&act)[2][NACT], const Frag (&enc)[2][NENC],
                                                       Frag (&out)[2][NOUT], Heads (&heads)[2], ARing& ring, int g) {
@@ -1086,30 +1092,26 @@ __device__ __forceinline__ void gemm_layer_two_groups(WStream& st, const NetDev&
     // asm - gained 0.9 % and was NOT safe: hipcc does not see the XDL hazards of registers an asm statement touches,
     // and the bf16 density pass came out different from run to run.  tests/test_parity_fp64.py now renders the
     // same rays alone and inside a frame in this mode too.)
-    pair_epilogue<PREC, NP_OUT, EPI>(net, tp, a00, a01, a00, a01, out[0], heads[0], g, hk);  // (single pass: no corrections)
-    pair_epilogue<PREC, NP_OUT, EPI>(net, tp, a10, a11, a10, a11, out[1], heads[1], g, hk);
+    pair_epilogue<V, PREC, NP_OUT, EPI>(net, tp, a00, a01, a00, a01, out[0], heads[0], g, hk);  // (single pass: no corrections)
+    pair_epilogue<V, PREC, NP_OUT, EPI>(net, tp, a10, a11, a10, a11, out[1], heads[1], g, hk);
   }
 }
 
 // A-operand pair primed for the very first GEMM of a kernel (after WStream::init opened phase 0)
-template <int PREC, int NT = 0>
+template <class V, int PREC, int NT = 0>
 __device__ __forceinline__ void prime_ring(const WStream& st, ARing& ring) {
   constexpr int UB = prec_is_x3(PREC) ? 2048 : 1024;
-  if (kKloopAsm && prec_is_x3(PREC) && NT == 8) {  // hand-scheduled x3 / x2 path: units 0 and 1 of the first GEMM
+  if (V::kKloopAsm && prec_is_x3(PREC) && NT == 8) {  // hand-scheduled x3 / x2 path: units 0 and 1 of the first GEMM
 #pragma unroll
     for (int i = 0; i < kKD; ++i) load_afrag<PREC>(st.n_base + i * UB, ring.cur[i]);
 #pragma unroll
     for (int i = kKD; i < (kNS > 3 ? kNS : 3); ++i) ring.cur[i] = ring.cur[0];
     return;
   }
-#ifdef FSN_X3_PF1
-  if (prec_is_x3(PREC)) {
-    load_afrag<PREC>(st.n_base, ring.cur[0]);
+  if (prec_is_x3(PREC)) {  // one unit ahead, or (no prefetch) the operands are read in place
+    if (V::kX3Pf1) load_afrag<PREC>(st.n_base, ring.cur[0]);
     return;
   }
-#else
-  if (prec_is_x3(PREC)) return;  // the x3 modes read their operands in place
-#endif
   load_afrag<PREC>(st.n_base, ring.cur[0]);
   load_afrag<PREC>(st.n_base + UB, ring.cur[1]);
   if (!prec_is_x3(PREC)) ring.cur[0].lo = ring.cur[1].lo = ring.cur[0].hi;  // single pass: no low parts
@@ -1156,10 +1158,10 @@ struct NoSave {
 // run gemm_layer_two_groups.  A macro, not a function: a forwarding function changes hipcc's code for the one-group
 // kernels.  TA: the template arguments in parentheses.
 #define FSN_TEMPLATE_ARGS(...) __VA_ARGS__
-#define FSN_GEMM_LAYER(TA, BIAS, IN, ENC, OUT)                                                                          \
-  do {                                                                                                                  \
-    if constexpr (NG == 1) gemm_layer<FSN_TEMPLATE_ARGS TA>(st, net, BIAS, IN[0], ENC[0], OUT[0], heads[0], ring, g, hk); \
-    else gemm_layer_two_groups<FSN_TEMPLATE_ARGS TA>(st, net, BIAS, IN, ENC, OUT, heads, ring, g);                       \
+#define FSN_GEMM_LAYER(TA, BIAS, IN, ENC, OUT)                                                                             \
+  do {                                                                                                                     \
+    if constexpr (NG == 1) gemm_layer<V, FSN_TEMPLATE_ARGS TA>(st, net, BIAS, IN[0], ENC[0], OUT[0], heads[0], ring, g, hk); \
+    else gemm_layer_two_groups<V, FSN_TEMPLATE_ARGS TA>(st, net, BIAS, IN, ENC, OUT, heads, ring, g);                       \
   } while (0)
 
 // Optional members of a sample source, used in the x3 / x2 modes only (there an encoding is ~50 VALU instructions per
@@ -1192,7 +1194,7 @@ __device__ __forceinline__ void encode_dir(const NetDev& net, float dx, float dy
                                                                                    net.dir_mask, g, de);
 }
 
-template <int NT, int PREC, bool FULL, int NG, class Src, class SV>
+template <class V, int NT, int PREC, bool FULL, int NG, class Src, class SV>
 __device__ __forceinline__ void mlp_tile(WStream& st, const NetDev& net, const Src (&src)[NG], ARing& ring,
                                          float (&sigma)[NG], float (&rgb)[NG][3], const SV& sv) {
   constexpr int NA = NT;  // k-steps of 32 across the hidden width
@@ -1211,7 +1213,7 @@ __device__ __forceinline__ void mlp_tile(WStream& st, const NetDev& net, const S
   Heads heads[NG];
   FSN_PER_GROUP(q, heads[q] = Heads{0.f, {0.f, 0.f, 0.f}, {0u, 0u, 0u}};);
   // positional encoding of every group's sample into PE (SAVE: the training forward keeps the first one)
-#define FSN_ENC_POS(SAVE, PE)                                                                                 \
+#define FSN_ENCODE_POS(SAVE, PE)                                                                              \
   FSN_PER_GROUP(q, float px, py, pz; src[q].pos(px, py, pz);                                                     \
                 encode<kKsPos, F16, X3, SAVE, LS>(px, py, pz, net.n_freqs_pos, misc + 4, net.pos_mask, g, PE[q], \
                                                   SAVE ? sv.enc_pos(g) : nullptr);)
@@ -1219,14 +1221,14 @@ __device__ __forceinline__ void mlp_tile(WStream& st, const NetDev& net, const S
     Frag pe[NG][kKsPos];
     if constexpr (kUnitMask) {
       if (net.pos_masked) {
-        FSN_ENC_POS(false, pe);
+        FSN_ENCODE_POS(false, pe);
       } else {
         float px, py, pz;
         src[0].pos(px, py, pz);
         encode<kKsPos, F16, X3, false, LS, false>(px, py, pz, net.n_freqs_pos, misc + 4, net.pos_mask, g, pe[0]);
       }
     } else {
-      FSN_ENC_POS(SV::kSave, pe);
+      FSN_ENCODE_POS(SV::kSave, pe);
     }
     if constexpr (kPosStash) {
       if (net.skip_mask) src[0].stash_pos(pe[0]);  // (wave-uniform; a network without a skip layer does not pay the write)
@@ -1247,7 +1249,7 @@ __device__ __forceinline__ void mlp_tile(WStream& st, const NetDev& net, const S
       if constexpr (kPosStash) {                                                                    \
         src[0].fetch_pos(pe2[0]);                                                                   \
       } else {                                                                                      \
-        FSN_ENC_POS(false, pe2);                                                                    \
+        FSN_ENCODE_POS(false, pe2);                                                                 \
       }                                                                                             \
       FSN_GEMM_LAYER((PREC, NT, NA, kKsPos, EPI), (LIDX)*D, IN, pe2, OUT);   \
     } else                                                                                          \
@@ -1266,7 +1268,7 @@ __device__ __forceinline__ void mlp_tile(WStream& st, const NetDev& net, const S
   // last hidden layer (index L-1): sigma head on its fp32 output (models.py:127,141)
   FSN_HIDDEN((FULL ? EPI_LAST_FULL : EPI_LAST_DENS), A, B, L - 1);
 #undef FSN_HIDDEN
-#undef FSN_ENC_POS
+#undef FSN_ENCODE_POS
   {
     // a head's dot product is spread over the four lanes of a sample: two butterfly steps
     float sg[NG];
@@ -1315,10 +1317,10 @@ __device__ __forceinline__ void mlp_tile(WStream& st, const NetDev& net, const S
 #undef FSN_GEMM_LAYER
 #undef FSN_TEMPLATE_ARGS
 
-template <int NT, int PREC, bool FULL, int NG, class Src>
+template <class V, int NT, int PREC, bool FULL, int NG, class Src>
 __device__ __forceinline__ void mlp_tile(WStream& st, const NetDev& net, const Src (&src)[NG], ARing& ring,
                                          float (&sigma)[NG], float (&rgb)[NG][3]) {
-  mlp_tile<NT, PREC, FULL>(st, net, src, ring, sigma, rgb, NoSave{});
+  mlp_tile<V, NT, PREC, FULL>(st, net, src, ring, sigma, rgb, NoSave{});
 }
 
 // Sample source of the kernels that stage a tile's inputs in LDS (k_mlp_fwd, k_mlp_maxima, k_train_fwd)

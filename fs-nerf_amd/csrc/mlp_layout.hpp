@@ -56,6 +56,15 @@ FSN_HD float lo_scale(int prec) { return prec_lo_scaled(prec) ? kLoScaleF16 : 1.
 FSN_HD int unit_bytes(int prec) { return prec_is_x3(prec) ? 2048 : 1024; }
 FSN_HD int units_per_phase(int prec) { return kPhaseBytes / unit_bytes(prec); }
 
+// The list of arithmetic modes an entry point admits, stated once per entry point: prec_in is its argument check,
+// dispatch_net / dispatch_prec (mlp_dev.hpp) instantiate exactly the same list.
+template <int... MODES>
+struct PrecModes {};
+template <int... MODES>
+constexpr bool prec_in(PrecModes<MODES...>, int prec) { return ((prec == MODES) || ...); }
+using PrecInference = PrecModes<FSN_PREC_BF16X3, FSN_PREC_BF16, FSN_PREC_FP16X3, FSN_PREC_FP16, FSN_PREC_FP16X3U, FSN_PREC_FP16X2>;
+using PrecTraining = PrecModes<FSN_PREC_BF16X3, FSN_PREC_BF16, FSN_PREC_FP16X3, FSN_PREC_FP16>;
+
 // One GEMM of the network as the kernel sees it.
 struct LayerGeom {
   int32_t nt_out;      // 32-feature output pairs (two 16-row MFMA tiles each)

@@ -4,6 +4,7 @@
 // k_mlp_fwd in a single-pass mode, occ = sigma * step in float32, and the duplicate-safe maximum into `pending`
 // (occ_key, as k_occ_scatter_max).  Points, cells and densities never go to memory; fsn_occgrid_apply_pending
 // (k_occ_ema_pending) and the threshold / k_occ_binarize follow as in the unfused path.
+// k_occ_refresh is fsn::VariantPlain (mlp_dev.hpp): single-pass modes only, where no variant switch applies.
 #include "common.hpp"
 #include "mlp_dev.hpp"
 #include "mlp_layout.hpp"
@@ -64,7 +65,7 @@ __global__ __launch_bounds__(kThreads) void k_occ_refresh(OccRefreshArgs a) {
   st.init(smem, nullptr, 0, 0, a.net.blob + a.net.stream_off, (uint32_t)a.net.nph_density, 1);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   ARing ring;
-  prime_ring<PREC, NT>(st, ring);
+  prime_ring<VariantPlain, PREC, NT>(st, ring);
   for (int32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     // each wave stages (and later reads) only its own 16 NG draws: no workgroup barrier
     if (lane < 16 * NG) {
@@ -84,7 +85,7 @@ __global__ __launch_bounds__(kThreads) void k_occ_refresh(OccRefreshArgs a) {
     DrawSrc src[NG];
     FSN_PER_GROUP(q, src[q] = DrawSrc{in_lds + tile_slot<NG>(wave, lane, q) * 4};);
     float sigma[NG], rgb[NG][3] = {};
-    mlp_tile<NT, PREC, false>(st, net, src, ring, sigma, rgb);
+    mlp_tile<VariantPlain, NT, PREC, false>(st, net, src, ring, sigma, rgb);
     if (tile_stores<NG>(lane)) {
       const float occ = sigma[tile_store_group<NG>(lane)] * a.step;  // (every lane holds every group's result)
       const int32_t cell = __float_as_int(in_lds[(wave * (16 * NG) + lane) * 4 + 3]);  // (this lane drew it)
@@ -114,7 +115,8 @@ extern "C" int fsn_occgrid_refresh(const fsn_mlp_desc* desc, int prec, const voi
                                    int64_t n_uniform, int64_t n_occupied, const uint64_t* seeds_host, float step,
                                    int32_t* prefix_scratch, uint32_t* pending, uint32_t* status, fsn_stream_t stream) {
   FSN_REQUIRE(desc && n_uniform >= 0 && n_occupied >= 0, FSN_E_INVALID, "fsn_occgrid_refresh: bad arguments");
-  FSN_REQUIRE(prec == FSN_PREC_FP16 || prec == FSN_PREC_BF16, FSN_E_UNSUPPORTED,
+  using Modes = PrecModes<FSN_PREC_BF16, FSN_PREC_FP16>;
+  FSN_REQUIRE(prec_in(Modes{}, prec), FSN_E_UNSUPPORTED,
               "fsn_occgrid_refresh: precision mode %d (the single-pass modes FSN_PREC_FP16 / FSN_PREC_BF16)", prec);
   NetGeom G;
   const char* why;
@@ -153,6 +155,6 @@ extern "C" int fsn_occgrid_refresh(const fsn_mlp_desc* desc, int prec, const voi
     rc = launch_occ_word_prefix(bits, (int)(res3 >> 5), levels, prefix_scratch, s);
     if (rc != FSN_OK) return rc;
   }
-  return dispatch_net(PrecModes<FSN_PREC_BF16, FSN_PREC_FP16>{}, desc->d_hidden, prec,
+  return dispatch_net(Modes{}, desc->d_hidden, prec,
                       [&](auto NT, auto PREC) { return launch_occ_refresh<NT(), PREC()>(a, cus, s); });
 }

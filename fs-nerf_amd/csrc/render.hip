@@ -7,9 +7,8 @@
 // group to ray group; per-ray scans/reductions are done by one wavefront per ray (ray_dev.hpp).
 // HBM traffic is the rays in and the requested outputs out.
 #include "common.hpp"
-// hand-scheduled k-loop of the x3 modes (kloop_gen.hpp): A operands two units ahead, counted waits
-#define FSN_KLOOP_ASM
-#define FSN_BF16X3_ONEACC 1  // inference: bf16x3 accumulates its three products in one tile (mlp_dev.hpp)
+// The kernels here are fsn::VariantFused (mlp_dev.hpp): hand-scheduled k-loop of the x3 modes (kloop_gen.hpp: A
+// operands two units ahead, counted waits), bf16x3 on one accumulator.
 #include "mlp_dev.hpp"
 #include "ray_dev.hpp"
 
@@ -17,6 +16,10 @@ namespace fsn {
 
 FSN_DEBUG_DEFINE_RECORD(render)
 #define FSN_DEBUG_RECORD g_dbg_render
+
+// FSN_PREC_BF16X3 is two arithmetics (mlp_dev.hpp, MlpVariant):
+static_assert(!prec_one_acc<VariantTrain>(FSN_PREC_BF16X3), "bf16x3 in training: main + correction accumulators, merged");
+static_assert(prec_one_acc<VariantFused>(FSN_PREC_BF16X3), "bf16x3 in inference: one accumulator, no merge");
 
 constexpr int kMaxGroupSamples = 768;  // G * (S + n_imp) <= this
 constexpr int kMaxGroupCoarse = 768;   // G * S <= this
@@ -70,18 +73,9 @@ static_assert(kRenderLdsBytes <= 160 * 1024, "LDS budget");
 static_assert((kRingBytes + 2 * kNetLdsBytes) % 16 == 0 && alignof(RenderLds) == 16, "dirF / stash: 16-byte LDS accesses");
 
 // Encoding reuse of the x3 / x2 modes (mlp_dev.hpp, "Optional members of a sample source"): the direction fragments
-// once per ray, the position fragments once per sample and pass, no multiplies by an absent mask.  0 = as before, for
-// A/B builds (tools/build_variant.sh <name> -DFSN_ENC_POS_STASH=0; profiles/EXPERIMENTS_r4.md section 13: 391.2 ->
-// 387.7 -> 385.1 ms per headline frame for the first two, 380.3 -> 377.1 ms for the third on another device).
-#ifndef FSN_ENC_DIR_TABLE
-#define FSN_ENC_DIR_TABLE 1
-#endif
-#ifndef FSN_ENC_POS_STASH
-#define FSN_ENC_POS_STASH 1
-#endif
-#ifndef FSN_ENC_UNIT_MASK_SKIP
-#define FSN_ENC_UNIT_MASK_SKIP 1
-#endif
+// once per ray, the position fragments once per sample and pass, no multiplies by an absent mask.  Measured one by one
+// in profiles/EXPERIMENTS_r4.md section 13 (391.2 -> 387.7 -> 385.1 ms per headline frame for the first two, 380.3 ->
+// 377.1 ms for the third on another device); tests/test_encoding_reuse_gpu.py pins them bit for bit against k_mlp_fwd.
 
 // sample source of the fused kernel: interval midpoint on the ray, x = o + d*(t0+t1)/2
 // (rendering.py:61,79), rebuilt from LDS whenever the MLP asks for it
@@ -90,13 +84,8 @@ struct RaySrc {
   const float* e;    // &edges[i] of this sample's interval in LDS
   const Frag* dfr;   // x3 / x2 modes: RenderLds::dirF[this sample's ray][this lane's g]
   RenderLds* lds;    // x3 / x2 modes: this lane's stash is column threadIdx.x of lds->stash
-#if FSN_ENC_UNIT_MASK_SKIP
   static constexpr bool kSkipUnitMask = true;
-#endif
-#if FSN_ENC_DIR_TABLE
   __device__ __forceinline__ void dir_frag(Frag& f) const { f = *dfr; }  // two ds_read_b128
-#endif
-#if FSN_ENC_POS_STASH
   // The column index is laundered at each use (as FSN_RELAUNDER does per group): the four word addresses are then
   // one shift of the thread id plus immediate offsets where they are used, not four registers hoisted out of the
   // layer loop and held across the whole tile.
@@ -121,7 +110,6 @@ struct RaySrc {
       pe[k].lo = FSN_AT(FSN_AT(lds->stash, 2 * k + 1), t);
     }
   }
-#endif
   __device__ __forceinline__ void pos(float& x, float& y, float& z) const {
     const float tm = e[0] + e[1];
     x = ray[0] + ray[3] * tm / 2.0f;
@@ -200,7 +188,7 @@ __global__ __launch_bounds__(kThreads) void k_render_fused(RenderKArgs k) {
   } while (0)
   constexpr int NG = groups_per_wave<NT, PREC>(), TILE = 128 * NG;
   ARing ring;
-  prime_ring<PREC, NT>(st, ring);
+  prime_ring<VariantFused, PREC, NT>(st, ring);
   // ---- the steps of one ray group (G rays), as the kernel strings them together below
   // rays of the group into LDS: from the caller's tensors, or generated from the camera (pose + pixel index)
   // q = n / d for the small non-negative integers of the group bookkeeping (n < 8192, 0 < d <= 512): one float
@@ -238,7 +226,7 @@ __global__ __launch_bounds__(kThreads) void k_render_fused(RenderKArgs k) {
   // load_rays (other lanes wrote the rays); every caller has an lds_barrier() between this and the first fine tile, and
   // the one that ends fine_stage keeps the next group's fill off a table still being read.
   auto fill_dir_frags = [&]() __attribute__((always_inline)) {
-    if constexpr (FSN_ENC_DIR_TABLE && prec_is_x3(PREC)) {
+    if constexpr (prec_is_x3(PREC)) {
       lds_barrier();
       if (tid < 4 * GRP_G) {
         const int r = tid >> 2;
@@ -273,7 +261,7 @@ __global__ __launch_bounds__(kThreads) void k_render_fused(RenderKArgs k) {
       RaySrc src[NG];
       FSN_PER_GROUP(q, src[q] = source(idx0 + 16 * q););
       float sigma[NG], rgb[NG][3];
-      mlp_tile<NT, PREC, false>(st, netC, src, ring, sigma, rgb);
+      mlp_tile<VariantFused, NT, PREC, false>(st, netC, src, ring, sigma, rgb);
       if (tile_stores<NG>(lane)) {
         const int qs = tile_store_group<NG>(lane), idx = idx0 + 16 * qs;  // (the sample this lane stores)
         if (idx < GRP_G * GRP_S) FSN_AT(S_.sigC, idx) = sigma[qs];
@@ -309,7 +297,7 @@ __global__ __launch_bounds__(kThreads) void k_render_fused(RenderKArgs k) {
       RaySrc src[NG];
       FSN_PER_GROUP(q, src[q] = source(idx0 + 16 * q););
       float sigma[NG], rgb[NG][3];
-      mlp_tile<NT, PREC, true>(st, netF, src, ring, sigma, rgb);
+      mlp_tile<VariantFused, NT, PREC, true>(st, netF, src, ring, sigma, rgb);
       if (tile_stores<NG>(lane)) {
         const int qs = tile_store_group<NG>(lane), idx = idx0 + 16 * qs;
         if (idx < GRP_G * GRP_SO) {
@@ -423,7 +411,7 @@ __global__ __launch_bounds__(kThreads) void k_bare_stream(const char* stream, ui
   WStream st;
   st.init(smem, nullptr, 0, 0, stream, nph, 1);
   ARing ring;
-  prime_ring<PREC, 8>(st, ring);
+  prime_ring<VariantFused, PREC, 8>(st, ring);
   const int g = (threadIdx.x >> 4) & 3;
   // activations as a ReLU layer of the scaled network leaves them: half of them zero, the rest spread over 2^0 .. 2^9,
   // low parts ~2^-11 of the high parts (pseudo-random per lane: the clock the chip holds depends on the data)
@@ -444,7 +432,7 @@ __global__ __launch_bounds__(kThreads) void k_bare_stream(const char* stream, ui
   Heads heads{0.f, {0.f, 0.f, 0.f}, {0u, 0u, 0u}};
   const uint64_t t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
   for (int l = 0; l < layers; ++l) {
-    gemm_layer<PREC, 8, 8, 0, EPI_RELU_CVT>(st, net, 0, A, none, B, heads, ring, g);
+    gemm_layer<VariantFused, PREC, 8, 8, 0, EPI_RELU_CVT>(st, net, 0, A, none, B, heads, ring, g);
     asm volatile("" ::"v"(B[0].hi), "v"(B[7].lo));
   }
   const uint64_t t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
@@ -561,8 +549,9 @@ extern "C" int fsn_render_rays_fused(const fsn_mlp_desc* desc, int prec, const v
 extern "C" int fsn_bench_bare_stream(const fsn_mlp_desc* desc, int prec, const void* blob, int layers, uint64_t* clock_out,
                                      fsn_stream_t stream) {
   FSN_REQUIRE(desc && blob && layers > 0, FSN_E_INVALID, "fsn_bench_bare_stream: bad arguments");
-  FSN_REQUIRE(desc->d_hidden == 256 && (prec == FSN_PREC_BF16X3 || prec == FSN_PREC_FP16X3 || prec == FSN_PREC_FP16X3U),
-              FSN_E_UNSUPPORTED, "fsn_bench_bare_stream: d_hidden 256 in an x3 mode only");
+  using Modes = PrecModes<FSN_PREC_BF16X3, FSN_PREC_FP16X3, FSN_PREC_FP16X3U>;
+  FSN_REQUIRE(desc->d_hidden == 256 && prec_in(Modes{}, prec), FSN_E_UNSUPPORTED,
+              "fsn_bench_bare_stream: d_hidden 256 in an x3 mode only");
   NetGeom G;
   const char* why;
   const int rc = build_geom(*desc, prec, G, &why);
@@ -571,7 +560,7 @@ extern "C" int fsn_bench_bare_stream(const fsn_mlp_desc* desc, int prec, const v
   if (cus <= 0) return FSN_E_HIP;
   const char* sp = static_cast<const char*>(blob) + G.stream_off;
   hipStream_t s = as_stream(stream);
-  const int launched = dispatch_prec(PrecModes<FSN_PREC_BF16X3, FSN_PREC_FP16X3, FSN_PREC_FP16X3U>{}, prec, [&](auto PREC) {
+  const int launched = dispatch_prec(Modes{}, prec, [&](auto PREC) {
     k_bare_stream<PREC()><<<cus, kThreads, 0, s>>>(sp, (uint32_t)G.nph_density, layers, clock_out);
     FSN_LAUNCH_CHECK("k_bare_stream");
     return FSN_OK;

@@ -21,8 +21,8 @@
 // cone_angle > 0 blocks of 64 intervals whose width grows with distance; include/fsnerf_hip.h has the definition at
 // fsn_occgrid_march_ex), so every candidate carries its own interval END and nothing below assumes a common width.
 #include "common.hpp"
-#define FSN_KLOOP_ASM
-#define FSN_BF16X3_ONEACC 1  // inference: bf16x3 accumulates its three products in one tile (mlp_dev.hpp)
+// k_render_occ is fsn::VariantFused (mlp_dev.hpp), as k_render_fused: hand-scheduled k-loop of the x3 modes, bf16x3 on
+// one accumulator.
 #include "mlp_dev.hpp"
 #include "occ_dev.hpp"
 #include "ray_dev.hpp"
@@ -140,7 +140,7 @@ __global__ __launch_bounds__(kThreads) void k_render_occ(OccKArgs k) {
   st.init(smem, nullptr, 0, 0, k.net.blob + k.net.stream_off, WStream::kDynamicPhases, 1);
   const uint32_t nph_density = (uint32_t)k.net.nph_density, nph_full = (uint32_t)k.net.nph_full;
   ARing ring;
-  prime_ring<PREC, NT>(st, ring);
+  prime_ring<VariantFused, PREC, NT>(st, ring);
 
   // interval end of candidate / kept sample i
   auto cand_end = [&](int i) -> float {
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(kThreads) void k_render_occ(OccKArgs k) {
                             src[q] = OccSrc{FSN_SPAN(S.rays, 6 * FSN_AT(S.slotc, ic), 6), FSN_AT(S.t0c, ic), cand_end(ic)};);
         float sigma[NG], rgb[NG][3];
         st.begin_tile(nph_density);
-        mlp_tile<NT, PREC, false>(st, net, src, ring, sigma, rgb);
+        mlp_tile<VariantFused, NT, PREC, false>(st, net, src, ring, sigma, rgb);
         if (tile_stores<NG>(lane)) {
           const int qs = tile_store_group<NG>(lane), idx = idx0 + 16 * qs;  // (the sample this lane stores)
           if (idx < n_cand) FSN_AT(S.sigc, idx) = sigma[qs];
@@ -357,7 +357,7 @@ __global__ __launch_bounds__(kThreads) void k_render_occ(OccKArgs k) {
                        src[q] = OccSrc{FSN_SPAN(S.rays, 6 * FSN_AT(S.slotk, ic), 6), FSN_AT(S.t0k, ic), kept_end(ic)};);
       float sigma[NG], rgb[NG][3];
       st.begin_tile(nph_full);
-      mlp_tile<NT, PREC, true>(st, net, src, ring, sigma, rgb);
+      mlp_tile<VariantFused, NT, PREC, true>(st, net, src, ring, sigma, rgb);
       if (tile_stores<NG>(lane)) {
         const int qs = tile_store_group<NG>(lane), idx = idx0 + 16 * qs;
         if (idx < n_kept) {
@@ -423,7 +423,8 @@ static int occ_render_launch(const char* who, const fsn_mlp_desc* desc, int prec
   FSN_REQUIRE(a.R >= 0 && a.step > 0.f && a.max_steps > 0, FSN_E_INVALID, "%s: bad sizes", who);
   FSN_REQUIRE(cone_angle >= 0.f, FSN_E_INVALID, "%s: cone_angle must not be negative", who);
   FSN_REQUIRE(!(cone_angle > 0.f && a.near_plane < 0.f), FSN_E_INVALID, "%s: the cone regime needs near_plane >= 0", who);
-  FSN_REQUIRE(prec >= 0 && prec <= FSN_PREC_FP16X3U, FSN_E_UNSUPPORTED, "%s: precision mode %d", who, prec);
+  using Modes = PrecModes<FSN_PREC_BF16X3, FSN_PREC_BF16, FSN_PREC_FP16X3, FSN_PREC_FP16, FSN_PREC_FP16X3U>;
+  FSN_REQUIRE(prec_in(Modes{}, prec), FSN_E_UNSUPPORTED, "%s: precision mode %d", who, prec);
   NetGeom G;
   const char* why;
   int rc = build_geom(*desc, prec, G, &why);
@@ -473,8 +474,7 @@ static int occ_render_launch(const char* who, const fsn_mlp_desc* desc, int prec
   if (cus <= 0) return FSN_E_HIP;
   hipStream_t s = as_stream(stream);
   FSN_HIP(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned long long), s));
-  return dispatch_net(PrecModes<FSN_PREC_BF16X3, FSN_PREC_BF16, FSN_PREC_FP16X3, FSN_PREC_FP16, FSN_PREC_FP16X3U>{}, desc->d_hidden,
-                      prec, [&](auto NT, auto PREC) { return launch_occ<NT(), PREC()>(k, cus, s); });
+  return dispatch_net(Modes{}, desc->d_hidden, prec, [&](auto NT, auto PREC) { return launch_occ<NT(), PREC()>(k, cus, s); });
 }
 
 extern "C" int fsn_render_rays_occgrid(const fsn_mlp_desc* desc, int prec, const void* blob,

@@ -29,7 +29,7 @@ int train_bwd_checked(const char* who, const fsn_mlp_desc* desc, int prec, const
                       const InputGradReq* rq) {
   const int rc = check_desc(desc);
   if (rc != FSN_OK) return rc;
-  FSN_REQUIRE(prec >= 0 && prec <= FSN_PREC_FP16, FSN_E_INVALID, "%s: unknown precision", who);
+  FSN_REQUIRE(prec_in(PrecTraining{}, prec), FSN_E_INVALID, "%s: unknown precision", who);
   if (rq) {
     FSN_REQUIRE(n >= 0, FSN_E_INVALID, "%s: n < 0", who);
     if (n == 0) return FSN_OK;
@@ -59,7 +59,7 @@ using namespace fsn;
 extern "C" int64_t fsn_nerf_train_workspace_floats(const fsn_mlp_desc* desc, int prec, int64_t n) {
   if (check_desc(desc) != FSN_OK) return FSN_E_INVALID;
   FSN_REQUIRE(n >= 0, FSN_E_INVALID, "fsn_nerf_train_workspace_floats: n < 0");
-  FSN_REQUIRE(prec >= 0 && prec <= FSN_PREC_FP16, FSN_E_INVALID, "fsn_nerf_train_workspace_floats: unknown precision");
+  FSN_REQUIRE(prec_in(PrecTraining{}, prec), FSN_E_INVALID, "fsn_nerf_train_workspace_floats: unknown precision");
   return fused_train_workspace_floats(*desc, prec, n);
 }
 
@@ -68,7 +68,7 @@ extern "C" int fsn_nerf_train_fwd(const fsn_mlp_desc* desc, int prec, const floa
                                   int64_t n, float* ws, float* out, uint32_t* status, fsn_stream_t stream) {
   int rc = check_desc(desc);
   if (rc != FSN_OK) return rc;
-  FSN_REQUIRE(prec >= 0 && prec <= FSN_PREC_FP16, FSN_E_INVALID, "fsn_nerf_train_fwd: unknown precision");
+  FSN_REQUIRE(prec_in(PrecTraining{}, prec), FSN_E_INVALID, "fsn_nerf_train_fwd: unknown precision");
   if (n == 0) return FSN_OK;
   FSN_REQUIRE(W && b && x && dirs && ws && out, FSN_E_INVALID, "fsn_nerf_train_fwd: null pointer");
   FSN_REQUIRE(n < (1ll << 31), FSN_E_UNSUPPORTED, "fsn_nerf_train_fwd: n too large for one call");
@@ -82,7 +82,7 @@ extern "C" int fsn_nerf_train_fwd_rays(const fsn_mlp_desc* desc, int prec, const
                                        fsn_stream_t stream) {
   int rc = check_desc(desc);
   if (rc != FSN_OK) return rc;
-  FSN_REQUIRE(prec >= 0 && prec <= FSN_PREC_FP16, FSN_E_INVALID, "fsn_nerf_train_fwd_rays: unknown precision");
+  FSN_REQUIRE(prec_in(PrecTraining{}, prec), FSN_E_INVALID, "fsn_nerf_train_fwd_rays: unknown precision");
   if (n == 0) return FSN_OK;
   FSN_REQUIRE(W && b && rays_o && rays_d && ray_indices && t_starts && t_ends && ws && out, FSN_E_INVALID,
               "fsn_nerf_train_fwd_rays: null pointer");

@@ -32,9 +32,8 @@
 // gradients sit in fp16's range; bf16 modes need none.
 //
 // reference: src/core/models.py:111-143 (forward), src/run-nerf.py:243-285 (loss.backward()).
-// x3 modes: pinned one-unit-ahead LDS prefetch of the A operands (mlp_dev.hpp).  +6 % on these kernels; the fused
-// render kernel keeps the compiler's own read placement (with its larger live state the pinned form spills more).
-#define FSN_X3_PF1
+// k_train_fwd and k_train_bwd are fsn::VariantTrain (mlp_dev.hpp): compiler-scheduled k-loop with the x3 modes' pinned
+// one-unit-ahead prefetch, and bf16x3 on a main and a correction accumulator - NOT the inference kernels' one.
 #include <type_traits>
 
 #include "mlp_dev.hpp"
@@ -47,6 +46,10 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 constexpr int kTC = kTileCols;
+
+// FSN_PREC_BF16X3 is two arithmetics (mlp_dev.hpp, MlpVariant):
+static_assert(!prec_one_acc<VariantTrain>(FSN_PREC_BF16X3), "bf16x3 in training: main + correction accumulators, merged");
+static_assert(prec_one_acc<VariantFused>(FSN_PREC_BF16X3), "bf16x3 in inference: one accumulator, no merge");
 
 // ------------------------------------------------------------------ workspace
 struct FusedLayout {
@@ -205,7 +208,7 @@ __global__ __launch_bounds__(kThreads) void k_train_fwd(TrainFwdArgs a) {
   WStream st;
   st.init(smem, nullptr, 0, 0, a.net.blob + a.net.stream_off, (uint32_t)a.net.nph_full, 1);
   ARing ring;
-  prime_ring<PREC>(st, ring);
+  prime_ring<VariantTrain, PREC>(st, ring);
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     // (thread id laundered per tile: lane-derived addresses are recomputed, not hoisted and spilled - render.hip)
     int t_ = threadIdx.x;
@@ -237,7 +240,7 @@ __global__ __launch_bounds__(kThreads) void k_train_fwd(TrainFwdArgs a) {
     sv.mstride = a.mask_stride;
     sv.n_layers = net.n_layers;
     float sigma[1], rgb[1][3] = {};
-    mlp_tile<NT, PREC, true>(st, net, src, ring, sigma, rgb, sv);
+    mlp_tile<VariantTrain, NT, PREC, true>(st, net, src, ring, sigma, rgb, sv);
     if (tile_stores<1>(lane) && s < a.n) {
       f32x4 o = {rgb[0][0], rgb[0][1], rgb[0][2], sigma[0]};
       *reinterpret_cast<f32x4*>(a.out + 4 * s) = o;
@@ -395,7 +398,7 @@ __global__ __launch_bounds__(kThreads) void k_train_bwd(TrainBwdArgs a) {
   const int col = wave * 16 + (lane & 15);
   const float scale = a.scale ? a.scale[0] : 1.0f;
   ARing ring;
-  prime_ring<PREC>(st, ring);
+  prime_ring<VariantTrain, PREC>(st, ring);
   Heads heads{0.f, {0.f, 0.f, 0.f}, {0u, 0u, 0u}};
   Frag none[1];
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -457,7 +460,7 @@ __global__ __launch_bounds__(kThreads) void k_train_bwd(TrainBwdArgs a) {
     }
     {  // d feat = W_branch[:, :D]^T dBo  -> "dPre" of the connection (no activation, models.py:130)
       BwdStoreHook hk{wsu + a.off_dp + L * a.h_stride + lane_off, bs(L) / bs(L + 1), am(L)};
-      gemm_layer<PREC, NT, NT / 2, 0, EPI_CVT>(st, net, 0, B, none, A, heads, ring, g, hk);
+      gemm_layer<VariantTrain, PREC, NT, NT / 2, 0, EPI_CVT>(st, net, 0, B, none, A, heads, ring, g, hk);
     }
     {  // d h_{L-1} = W_conn^T d feat + d sigma w_sigma, masked by h_{L-1} > 0
       BwdMaskHook<true> hk;
@@ -468,7 +471,7 @@ __global__ __launch_bounds__(kThreads) void k_train_bwd(TrainBwdArgs a) {
       hk.amax = am(L - 1);
       hk.dsig = dsig * bs(L - 1);
       hk.wsig = net.aux + (L + 2) * D + 4 * g;
-      gemm_layer<PREC, NT, NT, 0, EPI_CVT>(st, net, 0, A, none, B, heads, ring, g, hk);
+      gemm_layer<VariantTrain, PREC, NT, NT, 0, EPI_CVT>(st, net, 0, A, none, B, heads, ring, g, hk);
     }
     // B = dPre_{l}; layers l = L-1 .. 1: dPre_{l-1} = (W_l[:, :D]^T dPre_l) * (h_{l-1} > 0)
     for (int l = L - 1; l >= 1; l -= 2) {
@@ -479,7 +482,7 @@ __global__ __launch_bounds__(kThreads) void k_train_bwd(TrainBwdArgs a) {
         hk.d = wsu + a.off_dp + (l - 1) * a.h_stride + lane_off;
         hk.r = bs(l - 1) / bs(l);
         hk.amax = am(l - 1);
-        gemm_layer<PREC, NT, NT, 0, EPI_CVT>(st, net, 0, B, none, A, heads, ring, g, hk);
+        gemm_layer<VariantTrain, PREC, NT, NT, 0, EPI_CVT>(st, net, 0, B, none, A, heads, ring, g, hk);
       }
       if (l - 1 >= 1) {
         BwdMaskHook<false> hk;
@@ -488,7 +491,7 @@ __global__ __launch_bounds__(kThreads) void k_train_bwd(TrainBwdArgs a) {
         hk.d = wsu + a.off_dp + (l - 2) * a.h_stride + lane_off;
         hk.r = bs(l - 2) / bs(l - 1);
         hk.amax = am(l - 2);
-        gemm_layer<PREC, NT, NT, 0, EPI_CVT>(st, net, 0, A, none, B, heads, ring, g, hk);
+        gemm_layer<VariantTrain, PREC, NT, NT, 0, EPI_CVT>(st, net, 0, A, none, B, heads, ring, g, hk);
       }
     }
     if constexpr (F16) {  // a scaled gradient left the fp16 range

@@ -15,7 +15,7 @@ sigma.* and rgb.* are aux_value's float32 entries) wl' = 0 and the two modes for
   f  training under fp16x2 is fp16x3 training                 (NeRF.train_prec)
 
 Orders, read before asserting (a).  Compiler-scheduled (mlp_dev.hpp): k_mlp_fwd runs the x3 / x2 modes of BOTH widths
-through unit_mfma_r (mlp.hip defines FSN_X3_PF1 and not FSN_KLOOP_ASM), the fused render its 128-wide networks through
+through unit_mfma_r (mlp.hip is VariantStandalone: kX3Pf1 and not kKloopAsm), the fused render its 128-wide networks through
 unit_mfma; both issue, unit by unit, main = a.hi b.hi into the main tile, then [a.lo b.hi], then a.hi b.lo into the
 correction tile, the bracketed product under prec_reads_w_lo only.  Hand-scheduled (render.hip, 256 wide):
 gen_kloop.py block() emits per unit the same three in the same order, the middle one under `mode in ("X3", "X3S")`;
