@@ -12,6 +12,8 @@ estimator.update_every_n_steps) and evaluated with render_frame + PSNR and SSIM 
                                        [--depth-smooth-weight W] [--unseen-views shell|box]
                                        [--refine-poses --pose-noise-rot DEG --pose-noise-trans X --pose-lr LR
                                         --c2f-until K]
+                                       [--refine-intrinsics --focal-noise PCT --intrinsics-lr LR --per-view-intrinsics
+                                        --learn-principal-point]
 
 --u8-dataset: the teacher's frames become uint8 "photographs" (R.to8b) held in a device-resident RayDataset; the loop
 takes its batches from a RayLoader the way run-nerf.py:236-240 takes them from its DataLoader, and the held-out view
@@ -58,10 +60,18 @@ the PatchLoader) serve their batches over the corrected poses, loss.backward() f
 torch.optim.Adam steps xi (--pose-lr, default 1e-3) beside the network.  --c2f-until K ramps the frequency mask of both
 encodings from the lowest frequency to all of them over the first K steps (BARF's coarse-to-fine schedule through
 NeRF.set_freq_mask).  At the end nerfdata.pose_error prints the rotation and translation error of the perturbed and of
-the refined poses against the true ones, after a similarity alignment.  Intrinsics stay fixed.  (The teacher is a random
-network: its photographs are smooth and constrain the cameras only weakly, so expect the rotation error to shrink by a
+the refined poses against the true ones, after a similarity alignment.  (Intrinsics: --refine-intrinsics.  The teacher
+is a random network: its photographs are smooth and constrain the cameras only weakly, so expect the rotation error to shrink by a
 part, not to vanish - 5.4 -> 3.1 degrees in 800 steps at --hw 64 --estimator stratified --pose-noise-rot 5
 --pose-noise-trans 0.1 --c2f-until 200.)
+
+--refine-intrinsics (off by default; needs --u8-dataset; alone or with --refine-poses): the loop is told a focal length
+wrong by --focal-noise PCT percent; a nerfdata.IntrinsicsRefiner holds phi (log focal factor, principal-point offset in
+image sizes), the loaders serve their batches over its camera table, loss.backward() fills phi.grad, and
+torch.optim.Adam steps phi (--intrinsics-lr, default 1e-3).  --per-view-intrinsics: one row per view instead of a shared
+one; --learn-principal-point: off by default, since with learnable poses the principal point is nearly degenerate with
+the rotation.  At the end the learned K and the focal's relative error are printed.  The held-out frame and the path
+are rendered with the true focal.
 
 --mark-invisible (off by default): before the first step the occupancy estimator takes every cell that fewer than
 --min-views K (default 1) training views see out of the grid for good (OccGridEstimator.mark_invisible_from_views: a
@@ -83,7 +93,7 @@ from fs_nerf_amd.core.loss import (DepthKLLoss, DistortionLoss, LPIPSLoss, Patch
                                    RayEntropyLoss, SSIMLoss, WeightNormRegularizer)
 from fs_nerf_amd.core.optim import FusedAdam  # noqa: E402
 from fs_nerf_amd.core.scheduler import ExponentialDecay  # noqa: E402
-from fs_nerf_amd.nerfdata import (CameraRefiner, FrameLoader, PatchLoader, RayDataset, RayLoader, UnseenPatchLoader,  # noqa: E402
+from fs_nerf_amd.nerfdata import (CameraRefiner, FrameLoader, IntrinsicsRefiner, PatchLoader, RayDataset, RayLoader, UnseenPatchLoader,  # noqa: E402
                                   UnseenViewSampler, pose_error)
 from fs_nerf_amd.render import rendering as R  # noqa: E402
 from fs_nerf_amd.render.occgrid import OccGridEstimator  # noqa: E402
@@ -192,7 +202,20 @@ def main():
     ap.add_argument("--pose-lr", type=float, default=1e-3, help="with --refine-poses: Adam's learning rate for the corrections")
     ap.add_argument("--c2f-until", type=int, default=0, metavar="K",
                     help="ramp the frequency mask of both encodings up over the first K steps (coarse-to-fine; 0: off)")
+    ap.add_argument("--refine-intrinsics", action="store_true",
+                    help="opt-in: learn the focal length (and the principal point) beside the network "
+                         "(nerfdata.IntrinsicsRefiner; needs --u8-dataset)")
+    ap.add_argument("--focal-noise", type=float, default=0.0, metavar="PCT",
+                    help="with --refine-intrinsics: the loop starts from a focal length wrong by this many percent")
+    ap.add_argument("--intrinsics-lr", type=float, default=1e-3, help="with --refine-intrinsics: Adam's learning rate for phi")
+    ap.add_argument("--per-view-intrinsics", action="store_true", help="with --refine-intrinsics: one camera row per view")
+    ap.add_argument("--learn-principal-point", action="store_true",
+                    help="with --refine-intrinsics: learn the principal point too (nearly degenerate with learnable rotations)")
     a = ap.parse_args()
+    if a.refine_intrinsics and not a.u8_dataset:
+        ap.error("--refine-intrinsics learns the camera table behind the device-resident loaders: add --u8-dataset")
+    if (a.focal_noise or a.per_view_intrinsics or a.learn_principal_point) and not a.refine_intrinsics:
+        ap.error("--focal-noise / --per-view-intrinsics / --learn-principal-point belong to --refine-intrinsics")
     if a.refine_poses and not a.u8_dataset:
         ap.error("--refine-poses learns the poses behind the device-resident loaders: add --u8-dataset")
     if (a.pose_noise_rot or a.pose_noise_trans) and not a.refine_poses:
@@ -244,12 +267,19 @@ def main():
         start_poses = true_poses
         if a.refine_poses:  # the photographs are those of the true poses; the loop is told the perturbed ones
             start_poses = perturbed(true_poses, a.pose_noise_rot, a.pose_noise_trans, torch.Generator().manual_seed(5))
-        train_set = RayDataset(frames8, start_poses, hwf, near=near, far=far, device=dev)
+        # (with --refine-intrinsics the photographs are those of the true focal; the loop is told a wrong one)
+        start_hwf = (hwf[0], hwf[1], hwf[2] * (1.0 + a.focal_noise / 100.0)) if a.refine_intrinsics else hwf
+        train_set = RayDataset(frames8, start_poses, start_hwf, near=near, far=far, device=dev)
         cameras = CameraRefiner(train_set) if a.refine_poses else None
-        train_loader = RayLoader(train_set, a.batch, shuffle=True, seed=0, cameras=cameras)
+        intrinsics = None
+        if a.refine_intrinsics:
+            intrinsics = IntrinsicsRefiner(train_set, per_view=a.per_view_intrinsics,
+                                           learn_principal_point=a.learn_principal_point)
+        train_loader = RayLoader(train_set, a.batch, shuffle=True, seed=0, cameras=cameras, intrinsics=intrinsics)
         iterator = iter(train_loader)
         if a.ssim_weight or a.lpips_weight:
-            patch_loader = PatchLoader(train_set, a.patch, a.patches, shuffle=True, seed=1, cameras=cameras)
+            patch_loader = PatchLoader(train_set, a.patch, a.patches, shuffle=True, seed=1, cameras=cameras,
+                                       intrinsics=intrinsics)
             patch_iterator = iter(patch_loader)
         if a.ssim_weight:
             ssim_loss = SSIMLoss(gaussian_weights=True, data_range=1.0, channel_axis=-1)
@@ -285,6 +315,7 @@ def main():
               f"than {a.min_views} of the {len(poses)} training views", flush=True)
     optimizer = FusedAdam(model.parameters(), lr=5e-4)  # torch.optim.Adam's arithmetic, one launch over flat arenas
     pose_optimizer = torch.optim.Adam([cameras.xi], lr=a.pose_lr) if a.refine_poses else None
+    intrinsics_optimizer = torch.optim.Adam([intrinsics.phi], lr=a.intrinsics_lr) if a.refine_intrinsics else None
     wnorm = WeightNormRegularizer(model.named_parameters(), reg="l2", reg_ratio=0.5, Td=a.iters)  # run-nerf.py:266-279
     alpha = 1e-5
     distortion = DistortionLoss()
@@ -370,6 +401,9 @@ def main():
         if pose_optimizer is not None:
             pose_optimizer.step()
             pose_optimizer.zero_grad()
+        if intrinsics_optimizer is not None:
+            intrinsics_optimizer.step()
+            intrinsics_optimizer.zero_grad()
         if a.estimator == "propnet":  # the proposal network's own step, on the interlevel loss
             prop_loss = estimator.update_every_n_steps(extras["trans"].reshape(rays_o.shape[0], estimator.num_samples),
                                                        requires_grad=estimator.proposal_requires_grad)
@@ -406,6 +440,12 @@ def main():
             rot, trans = pose_error(p, true_poses)
             print(f"{name} poses: rotation error {float(rot.mean()):.3f} deg (max {float(rot.max()):.3f}), translation error "
                   f"{float(trans.mean()):.4f} (max {float(trans.max()):.4f})")
+    if a.refine_intrinsics:
+        K = intrinsics.K().cpu()
+        rel = (K[:, :2] / hwf[2] - 1.0).abs().max()
+        print(f"learned K (fx, fy, cx, cy) per row: {[[round(v, 4) for v in row] for row in K.tolist()]}; true focal "
+              f"{hwf[2]:.4f}, started at {start_hwf[2]:.4f} ({a.focal_noise:+.2f} %); focal relative error "
+              f"{100.0 * float(rel):.3f} % (largest over rows and axes)")
 
 
 if __name__ == "__main__":

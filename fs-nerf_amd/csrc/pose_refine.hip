@@ -10,6 +10,9 @@
 // inside the wave, LDS across the sixteen waves, and thread 0 finishes with the derivative of the composition.
 // (1024 threads: the walk is a chain of dependent loads per thread, so a view's time is the number of strides - 4 for
 // a 4096-ray batch: 16 us over 8 views and 14 us over 100; with 256 threads the same launches took 24 us and 17 us.)
+// The learnable intrinsics are the second half of the file: k_intrinsics_compose forms the camera table K = (fx, fy, cx,
+// cy) from its parameter phi, k_ray_camera_grad is k_ray_pose_grad's walk over that table with four more sums (this
+// view's share of dL/dK), and k_intrinsics_grad_* chain dL/dK to dL/dphi.  k_ray_pose_grad itself is left as it was.
 #include "common.hpp"
 #include "ray_dev.hpp"
 
@@ -173,6 +176,181 @@ __global__ void __launch_bounds__(kPoseGradThreads) k_ray_pose_grad(PoseGradArgs
   }
 }
 
+// ---- learnable intrinsics: a table K = (fx, fy, cx, cy) [m, 4] on the device, m = 1 (shared) or n_views,
+// formed from the parameter phi [m, 4] (zeros at the start) and the dataset's (H, W, f0):
+//   fx = f0 exp(phi_0),  fy = f0 exp(phi_1) (tie_focal: fy = fx),  cx = W/2 + W phi_2,  cy = H/2 + H phi_3.
+// phi = 0 gives (f0, f0, (float)(W * 0.5), (float)(H * 0.5)) value for value: expf(0) = 1 and x + W * 0 = x.
+__device__ __forceinline__ void intrinsics_compose(const float* __restrict__ phi, float focal0, float half_w, float half_h,
+                                                   float Wf, float Hf, int tie, float (&K)[4]) {
+  K[0] = focal0 * expf(phi[0]);
+  K[1] = tie ? K[0] : focal0 * expf(phi[1]);
+  K[2] = half_w + Wf * phi[2];
+  K[3] = half_h + Hf * phi[3];
+}
+
+__global__ void __launch_bounds__(256) k_intrinsics_compose(const float* __restrict__ phi, int64_t m, float focal0,
+                                                            float half_w, float half_h, float Wf, float Hf, int tie,
+                                                            float* __restrict__ out) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= m) return;
+  float K[4];
+  intrinsics_compose(phi + 4 * r, focal0, half_w, half_h, Wf, Hf, tie, K);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) out[4 * r + k] = K[k];
+}
+
+// k_ray_camera_grad: k_ray_pose_grad's walk with the camera table in place of the launch constants and four more sums,
+// this view's rays' share of dL/d(fx, fy, cx, cy).  Per ray, with g_c = R^T g_d, u = ((w - cx)/fx, -(h - cy)/fy, -1),
+// c = u / |u|:   g_u = (g_c - c (c . g_c)) / |u|,   dL/dfx = -g_u0 u_0 / fx,  dL/dcx = -g_u0 / fx,
+//                                                    dL/dfy = -g_u1 u_1 / fy,  dL/dcy =  g_u1 / fy.
+// The twelve pose sums are k_ray_pose_grad's, in its order: with the stored intrinsics in K, grad_xi is its bit for bit.
+struct CameraGradArgs {
+  PoseGradArgs p;           // (half_w, half_h and focal are not read: the table's row is; xi may be null)
+  const float* K;           // [k_rows, 4]
+  int64_t k_stride;         // 0 (one shared row) or 4
+  float* grad_K_views;      // [n, 4]
+};
+
+constexpr int kCameraGradSums = 16;
+__device__ const float kZeroXi[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // xi = null: no correction
+
+__global__ void __launch_bounds__(kPoseGradThreads) k_ray_camera_grad(CameraGradArgs ca) {
+  const PoseGradArgs& a = ca.p;
+  const int64_t view = blockIdx.x;
+  const int64_t lo = view * a.per_view, hi = lo + a.per_view;
+  const float* p0 = a.poses0 + 12 * view;
+  float m[12];
+  if (a.xi) {
+    pose_compose(p0, a.xi + 6 * view, m);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) m[k] = p0[k];
+  }
+  const float* Kv = ca.K + ca.k_stride * view;
+  const float fx = Kv[0], fy = Kv[1], cx = Kv[2], cy = Kv[3];
+  float acc[kCameraGradSums];
+#pragma unroll
+  for (int k = 0; k < kCameraGradSums; ++k) acc[k] = 0.f;
+  for (int64_t i = threadIdx.x; i < a.count; i += kPoseGradThreads) {
+    const int64_t idx = a.index[i];
+#ifdef FSN_DEBUG
+    if (view == 0 && (idx < 0 || idx >= a.n_rays)) fsn_dbg_note(g_dbg_pose_refine, __LINE__, idx, a.n_rays);
+#endif
+    if (idx < lo || idx >= hi) continue;  // another view's ray, or no ray at all: skipped before any other access
+    const unsigned pix = (unsigned)(idx - lo), W = (unsigned)a.W;  // (per_view < 2^31: the host checked)
+    const int h = (int)(pix / W), w = (int)(pix % W);
+    float c[3], go[3], gd[3];
+    pinhole_dir_cam_k(fx, fy, cx, cy, h, w, c);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      go[k] = a.grad_o ? a.grad_o[3 * i + k] : 0.f;
+      gd[k] = a.grad_d ? a.grad_d[3 * i + k] : 0.f;
+    }
+    if (a.ndc) {
+      float o[3], d[3];
+      rotate_dir_cam(m, c, o, d);
+      ndc_ray_bwd(o, d, a.sx, a.sy, a.near, a.two_near, go, gd);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      acc[4 * k + 0] += gd[k] * c[0];
+      acc[4 * k + 1] += gd[k] * c[1];
+      acc[4 * k + 2] += gd[k] * c[2];
+      acc[4 * k + 3] += go[k];
+    }
+    // the intrinsics' share: u and |u| as pinhole_dir_cam forms them
+    const float u0 = ((float)w - cx) / fx, u1 = -((float)h - cy) / fy;
+    const float nrm = sqrtf(u0 * u0 + u1 * u1 + 1.0f);
+    float gc[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) gc[j] = (m[j] * gd[0] + m[4 + j] * gd[1]) + m[8 + j] * gd[2];
+    const float cg = (c[0] * gc[0] + c[1] * gc[1]) + c[2] * gc[2];
+    const float gu0 = (gc[0] - c[0] * cg) / nrm, gu1 = (gc[1] - c[1] * cg) / nrm;
+    acc[12] += -(gu0 * u0) / fx;
+    acc[13] += -(gu1 * u1) / fy;
+    acc[14] += -gu0 / fx;
+    acc[15] += gu1 / fy;
+  }
+  __shared__ float part[kPoseGradWaves][kCameraGradSums];
+  const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
+#pragma unroll
+  for (int k = 0; k < kCameraGradSums; ++k) {
+    const float s = wave_sum(acc[k]);
+    if (lane == 0) part[wave][k] = s;
+  }
+  __shared__ float total[kCameraGradSums];
+  __syncthreads();
+  if (threadIdx.x < kCameraGradSums) {  // thread k adds sum k over the waves, in wave order as k_ray_pose_grad does
+    float s = part[0][threadIdx.x];
+    for (int w = 1; w < kPoseGradWaves; ++w) s += part[w][threadIdx.x];
+    total[threadIdx.x] = s;
+    if (threadIdx.x >= 12) ca.grad_K_views[4 * view + (threadIdx.x - 12)] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && a.grad_xi) {
+    float g[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) g[k] = total[k];
+    pose_compose_bwd(p0, a.xi ? a.xi + 6 * view : kZeroXi, g, a.grad_xi + 6 * view);
+  }
+}
+
+// The chain K -> phi: dL/dphi_0 = fx dL/dfx (+ fy dL/dfy when tied, and then dL/dphi_1 = 0), dL/dphi_1 = fy dL/dfy,
+// dL/dphi_2 = W dL/dcx, dL/dphi_3 = H dL/dcy, in float64 over the float32 table values.
+__device__ __forceinline__ void intrinsics_chain(const float* __restrict__ phi, const double (&gK)[4], float focal0, float Wf,
+                                                 float Hf, int tie, float* __restrict__ grad_phi) {
+  const double fx = (double)(focal0 * expf(phi[0]));
+  if (tie) {
+    grad_phi[0] = (float)(fx * gK[0] + fx * gK[1]);
+    grad_phi[1] = 0.f;
+  } else {
+    grad_phi[0] = (float)(fx * gK[0]);
+    grad_phi[1] = (float)((double)(focal0 * expf(phi[1])) * gK[1]);
+  }
+  grad_phi[2] = (float)((double)Wf * gK[2]);
+  grad_phi[3] = (float)((double)Hf * gK[3]);
+}
+
+// per-view parameters: one thread per view
+__global__ void __launch_bounds__(256) k_intrinsics_grad_rows(const float* __restrict__ phi, const float* __restrict__ gKv,
+                                                              int64_t n, float focal0, float Wf, float Hf, int tie,
+                                                              float* __restrict__ grad_phi) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n) return;
+  const double gK[4] = {gKv[4 * v], gKv[4 * v + 1], gKv[4 * v + 2], gKv[4 * v + 3]};
+  intrinsics_chain(phi + 4 * v, gK, focal0, Wf, Hf, tie, grad_phi + 4 * v);
+}
+
+// one shared row: ONE workgroup sums the views in float64 in a fixed order - thread (slot, column) adds the views of
+// its contiguous share [slot per, (slot + 1) per) in view order, thread 0 adds the 64 slots in slot order.
+constexpr int kIntrGradSlots = 64;
+__global__ void __launch_bounds__(4 * kIntrGradSlots) k_intrinsics_grad_shared(const float* __restrict__ phi,
+                                                                               const float* __restrict__ gKv, int64_t n,
+                                                                               float focal0, float Wf, float Hf, int tie,
+                                                                               float* __restrict__ grad_phi) {
+  __shared__ double part[kIntrGradSlots][4];
+  const int col = (int)(threadIdx.x & 3), slot = (int)(threadIdx.x >> 2);
+  const int64_t per = (n + kIntrGradSlots - 1) / kIntrGradSlots;
+  const int64_t v0 = min(slot * per, n), v1 = min(v0 + per, n);
+  __shared__ double total[4];
+  double s = 0.0;
+#pragma unroll 4
+  for (int64_t v = v0; v < v1; ++v) s += (double)gKv[4 * v + col];
+  part[slot][col] = s;
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    double t = part[0][threadIdx.x];
+#pragma unroll 4
+    for (int j = 1; j < kIntrGradSlots; ++j) t += part[j][threadIdx.x];
+    total[threadIdx.x] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double gK[4] = {total[0], total[1], total[2], total[3]};
+    intrinsics_chain(phi, gK, focal0, Wf, Hf, tie, grad_phi);
+  }
+}
+
 }  // namespace fsn
 
 using namespace fsn;
@@ -221,5 +399,82 @@ extern "C" int fsn_ray_pose_grad(const float* poses0, const float* xi, int64_t n
   a.grad_poses = grad_poses;
   k_ray_pose_grad<<<(unsigned)n_views, kPoseGradThreads, 0, as_stream(stream)>>>(a);  // (count = 0: every view's gradient is 0)
   FSN_LAUNCH_CHECK("k_ray_pose_grad");
+  return FSN_OK;
+}
+
+extern "C" int fsn_intrinsics_compose(const float* phi, int64_t m, int H, int W, double focal0, int tie_focal, float* K_out,
+                                      fsn_stream_t stream) {
+  FSN_REQUIRE(m >= 0 && H > 0 && W > 0 && focal0 > 0, FSN_E_INVALID,
+              "fsn_intrinsics_compose: bad geometry m=%lld H=%d W=%d focal0=%g", (long long)m, H, W, focal0);
+  FSN_REQUIRE(phi && K_out, FSN_E_INVALID, "fsn_intrinsics_compose: null pointer");
+  if (m == 0) return FSN_OK;
+  FSN_REQUIRE((m + 255) / 256 <= 0x7fffffff, FSN_E_UNSUPPORTED, "fsn_intrinsics_compose: too many rows");
+  // the same roundings as fsn_ray_batch: phi = 0 gives its launch constants
+  k_intrinsics_compose<<<(unsigned)((m + 255) / 256), 256, 0, as_stream(stream)>>>(
+      phi, m, (float)focal0, (float)(W * 0.5), (float)(H * 0.5), (float)W, (float)H, tie_focal ? 1 : 0, K_out);
+  FSN_LAUNCH_CHECK("k_intrinsics_compose");
+  return FSN_OK;
+}
+
+extern "C" int fsn_ray_camera_grad(const float* poses0, const float* xi, int64_t n_views, int H, int W, double focal0,
+                                   const float* K, int64_t k_rows, int ndc, double near, const int64_t* index,
+                                   const float* grad_o, const float* grad_d, int64_t count, float* grad_xi,
+                                   float* grad_K_views, fsn_stream_t stream) {
+  FSN_REQUIRE(n_views >= 0 && H > 0 && W > 0 && focal0 > 0, FSN_E_INVALID,
+              "fsn_ray_camera_grad: bad geometry n=%lld H=%d W=%d focal0=%g", (long long)n_views, H, W, focal0);
+  FSN_REQUIRE(count >= 0, FSN_E_INVALID, "fsn_ray_camera_grad: negative count %lld", (long long)count);
+  FSN_REQUIRE((int64_t)H * W <= 0x7fffffff, FSN_E_UNSUPPORTED, "fsn_ray_camera_grad: more than 2^31 pixels per view");
+  FSN_REQUIRE(n_views <= 0x7fffffff, FSN_E_UNSUPPORTED, "fsn_ray_camera_grad: too many views");
+  FSN_REQUIRE(poses0 && K && grad_K_views, FSN_E_INVALID, "fsn_ray_camera_grad: null poses0, K or grad_K_views");
+  FSN_REQUIRE(k_rows == 1 || k_rows == n_views, FSN_E_INVALID,
+              "fsn_ray_camera_grad: a camera table of %lld rows (1, or one per view: %lld)", (long long)k_rows,
+              (long long)n_views);
+  FSN_REQUIRE(count == 0 || index, FSN_E_INVALID, "fsn_ray_camera_grad: null index list");
+  if (n_views == 0) return FSN_OK;
+  CameraGradArgs ca{};
+  PoseGradArgs& a = ca.p;
+  a.poses0 = poses0;
+  a.xi = xi;
+  a.index = index;
+  a.grad_o = grad_o;
+  a.grad_d = grad_d;
+  a.per_view = (int64_t)H * W;
+  a.n_rays = n_views * a.per_view;
+  a.count = count;
+  a.W = W;
+  a.ndc = ndc ? 1 : 0;
+  // the NDC map stays that of the stored focal (a fixed warp of space): the same roundings as fsn_ray_batch
+  a.sx = (float)(-1.0 / (W / (2.0 * focal0)));
+  a.sy = (float)(-1.0 / (H / (2.0 * focal0)));
+  a.near = (float)near;
+  a.two_near = (float)(2.0 * near);
+  a.grad_xi = grad_xi;
+  ca.K = K;
+  ca.k_stride = k_rows == 1 ? 0 : 4;
+  ca.grad_K_views = grad_K_views;
+  k_ray_camera_grad<<<(unsigned)n_views, kPoseGradThreads, 0, as_stream(stream)>>>(ca);  // (count = 0: every row is 0)
+  FSN_LAUNCH_CHECK("k_ray_camera_grad");
+  return FSN_OK;
+}
+
+extern "C" int fsn_intrinsics_grad(const float* phi, const float* grad_K_views, int64_t n_views, int64_t m, int H, int W,
+                                   double focal0, int tie_focal, float* grad_phi, fsn_stream_t stream) {
+  FSN_REQUIRE(n_views >= 0 && H > 0 && W > 0 && focal0 > 0, FSN_E_INVALID,
+              "fsn_intrinsics_grad: bad geometry n=%lld H=%d W=%d focal0=%g", (long long)n_views, H, W, focal0);
+  FSN_REQUIRE(m == 1 || m == n_views, FSN_E_INVALID,
+              "fsn_intrinsics_grad: a parameter of %lld rows (1, or one per view: %lld)", (long long)m, (long long)n_views);
+  FSN_REQUIRE(phi && grad_phi && (grad_K_views || n_views == 0), FSN_E_INVALID, "fsn_intrinsics_grad: null pointer");
+  const int tie = tie_focal ? 1 : 0;
+  if (m == 1) {  // (no view at all: the sum is empty and the row is written as 0)
+    k_intrinsics_grad_shared<<<1, 4 * kIntrGradSlots, 0, as_stream(stream)>>>(phi, grad_K_views, n_views, (float)focal0,
+                                                                              (float)W, (float)H, tie, grad_phi);
+    FSN_LAUNCH_CHECK("k_intrinsics_grad_shared");
+    return FSN_OK;
+  }
+  if (n_views == 0) return FSN_OK;
+  FSN_REQUIRE((n_views + 255) / 256 <= 0x7fffffff, FSN_E_UNSUPPORTED, "fsn_intrinsics_grad: too many views");
+  k_intrinsics_grad_rows<<<(unsigned)((n_views + 255) / 256), 256, 0, as_stream(stream)>>>(
+      phi, grad_K_views, n_views, (float)focal0, (float)W, (float)H, tie, grad_phi);
+  FSN_LAUNCH_CHECK("k_intrinsics_grad_rows");
   return FSN_OK;
 }

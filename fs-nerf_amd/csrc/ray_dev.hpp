@@ -412,6 +412,34 @@ __device__ __forceinline__ void pinhole_ray(const float* __restrict__ m, float h
     o[k] = m[4 * k + 3];
   }
 }
+// The same two under a camera table K = (fx, fy, cx, cy) (learnable intrinsics): d_cam = [(w - cx)/fx,
+// -(h - cy)/fy, -1].  The stored intrinsics are K = (focal, focal, W/2, H/2): the same operations on the same values, so
+// the same bits.  (Restated, not shared: the functions above are inlined into the render kernels, whose code must not
+// move with this one.)
+__device__ __forceinline__ void pinhole_dir_cam_k(float fx, float fy, float cx, float cy, int h, int w, float (&c)[3]) {
+  float dx = ((float)w - cx) / fx;
+  float dy = -((float)h - cy) / fy;
+  float dz = -1.0f;
+  const float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
+  c[0] = dx / nrm;
+  c[1] = dy / nrm;
+  c[2] = dz / nrm;
+}
+__device__ __forceinline__ void rotate_dir_cam(const float* __restrict__ m, const float (&c)[3], float (&o)[3],
+                                               float (&d)[3]) {
+  const float dx = c[0], dy = c[1], dz = c[2];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    d[k] = (dx * m[4 * k + 0] + dy * m[4 * k + 1]) + dz * m[4 * k + 2];
+    o[k] = m[4 * k + 3];
+  }
+}
+__device__ __forceinline__ void pinhole_ray_k(const float* __restrict__ m, const float* __restrict__ K, int h, int w,
+                                              float (&o)[3], float (&d)[3]) {
+  float c[3];
+  pinhole_dir_cam_k(K[0], K[1], K[2], K[3], h, w, c);
+  rotate_dir_cam(m, c, o, d);
+}
 
 // World ray -> normalised device coordinates (src/utils/utilities.py:84-120), in place.  The one definition used by
 // k_to_ndc, k_build_rays (ray_ops.hip) and k_ray_batch (raydata.hip).

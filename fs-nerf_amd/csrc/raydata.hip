@@ -11,6 +11,8 @@
 // A latency-bound gather of a few hundred KB: 12-byte rows rule out 16-byte vector stores; plain coalesced stores.
 // k_ray_patch_batch serves P x P patches the same way: position -> shuffled ANCHOR (the patch's top-left pixel) ->
 // the patch's pixels -> the rows k_ray_batch writes for them.
+// fsn_ray_batch_k / fsn_ray_patch_batch_k serve the same batches over a camera table K = (fx, fy, cx, cy) on the device
+// (learnable intrinsics): the same two kernels, instantiated with kTable = true.
 #include "common.hpp"
 #include "ray_dev.hpp"
 #include "ray_perm.hpp"
@@ -35,7 +37,16 @@ struct RayBatchArgs {
   int64_t* index;
 };
 
-__global__ void __launch_bounds__(256) k_ray_batch(RayBatchArgs a) {
+// The camera table of the learnable intrinsics (fsn_ray_batch_k / fsn_ray_patch_batch_k): row v * stride of
+// K = (fx, fy, cx, cy) [k_rows, 4] is view v's, stride = 0 for one shared row.  kTable = false is the stored-intrinsics
+// kernel: it never looks at the table, and its code is what it was before the table existed.
+struct CamTable {
+  const float* K;
+  int64_t stride;
+};
+
+template <bool kTable>
+__global__ void __launch_bounds__(256) k_ray_batch(RayBatchArgs a, CamTable cam) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.count) return;
   int64_t idx;
@@ -56,7 +67,10 @@ __global__ void __launch_bounds__(256) k_ray_batch(RayBatchArgs a) {
   if (a.rays_o || a.rays_d) {
     const int64_t view = idx / a.per_view, pix = idx - view * a.per_view;
     float o[3], d[3];
-    pinhole_ray(a.poses + 12 * view, a.half_w, a.half_h, a.focal, (int)(pix / a.W), (int)(pix % a.W), o, d);
+    if constexpr (kTable)
+      pinhole_ray_k(a.poses + 12 * view, cam.K + cam.stride * view, (int)(pix / a.W), (int)(pix % a.W), o, d);
+    else
+      pinhole_ray(a.poses + 12 * view, a.half_w, a.half_h, a.focal, (int)(pix / a.W), (int)(pix % a.W), o, d);
     if (a.ndc) ndc_ray(o, d, a.sx, a.sy, a.near, a.two_near);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -93,7 +107,8 @@ struct RayPatchArgs {
   int P, dilation, AW, H;
 };
 
-__global__ void __launch_bounds__(256) k_ray_patch_batch(RayPatchArgs pa) {
+template <bool kTable>
+__global__ void __launch_bounds__(256) k_ray_patch_batch(RayPatchArgs pa, CamTable cam) {
   const RayBatchArgs& a = pa.r;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t pp = (int64_t)pa.P * pa.P;
@@ -120,7 +135,10 @@ __global__ void __launch_bounds__(256) k_ray_patch_batch(RayPatchArgs pa) {
   if (a.index) a.index[i] = idx;
   if (a.rays_o || a.rays_d) {
     float o[3], d[3];
-    pinhole_ray(a.poses + 12 * view, a.half_w, a.half_h, a.focal, row, col, o, d);
+    if constexpr (kTable)
+      pinhole_ray_k(a.poses + 12 * view, cam.K + cam.stride * view, row, col, o, d);
+    else
+      pinhole_ray(a.poses + 12 * view, a.half_w, a.half_h, a.focal, row, col, o, d);
     if (a.ndc) ndc_ray(o, d, a.sx, a.sy, a.near, a.two_near);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -151,31 +169,32 @@ __global__ void __launch_bounds__(256) k_ray_patch_batch(RayPatchArgs pa) {
 
 using namespace fsn;
 
-extern "C" int fsn_ray_batch(const float* poses, int64_t n_views, const uint8_t* images, int H, int W, int C, double focal,
-                             int ndc, double near, int white_bkgd, int order, uint64_t seed, int64_t epoch,
-                             const int64_t* indices, int64_t start, int64_t count, float* rays_o, float* rays_d,
-                             float* rgb, int64_t* index, fsn_stream_t stream) {
+// The two batch entry points and their camera-table twins share one body each: `cam` null = the stored intrinsics.
+static int ray_batch_call(const char* who, const CamTable* cam, const float* poses, int64_t n_views,
+                          const uint8_t* images, int H, int W, int C, double focal, int ndc, double near, int white_bkgd,
+                          int order, uint64_t seed, int64_t epoch, const int64_t* indices, int64_t start, int64_t count,
+                          float* rays_o, float* rays_d, float* rgb, int64_t* index, fsn_stream_t stream) {
   FSN_REQUIRE(n_views >= 0 && H > 0 && W > 0 && focal > 0, FSN_E_INVALID,
-              "fsn_ray_batch: bad geometry n=%lld H=%d W=%d focal=%g", (long long)n_views, H, W, focal);
-  FSN_REQUIRE(C == 3 || C == 4, FSN_E_INVALID, "fsn_ray_batch: %d channels (the images are RGB or RGBA bytes: 3 or 4)", C);
+              "%s: bad geometry n=%lld H=%d W=%d focal=%g", who, (long long)n_views, H, W, focal);
+  FSN_REQUIRE(C == 3 || C == 4, FSN_E_INVALID, "%s: %d channels (the images are RGB or RGBA bytes: 3 or 4)", who, C);
   FSN_REQUIRE(!white_bkgd || C == 4, FSN_E_INVALID,
-              "fsn_ray_batch: white_bkgd composes over the alpha channel and needs 4-channel images, got %d", C);
+              "%s: white_bkgd composes over the alpha channel and needs 4-channel images, got %d", who, C);
   FSN_REQUIRE(order == FSN_RAY_ORDER_IDENTITY || order == FSN_RAY_ORDER_PERMUTED || order == FSN_RAY_ORDER_EXPLICIT,
-              FSN_E_INVALID, "fsn_ray_batch: unknown order %d", order);
-  FSN_REQUIRE(n_views <= ((int64_t)1 << 62) / ((int64_t)H * W), FSN_E_UNSUPPORTED, "fsn_ray_batch: more than 2^62 rays");
+              FSN_E_INVALID, "%s: unknown order %d", who, order);
+  FSN_REQUIRE(n_views <= ((int64_t)1 << 62) / ((int64_t)H * W), FSN_E_UNSUPPORTED, "%s: more than 2^62 rays", who);
   const int64_t per_view = (int64_t)H * W, n_rays = n_views * per_view;
-  FSN_REQUIRE(start >= 0 && count >= 0 && epoch >= 0, FSN_E_INVALID, "fsn_ray_batch: negative start, count or epoch");
+  FSN_REQUIRE(start >= 0 && count >= 0 && epoch >= 0, FSN_E_INVALID, "%s: negative start, count or epoch", who);
   if (order == FSN_RAY_ORDER_EXPLICIT) {
-    FSN_REQUIRE(start == 0, FSN_E_INVALID, "fsn_ray_batch: an explicit index list is served from its beginning (start = 0)");
+    FSN_REQUIRE(start == 0, FSN_E_INVALID, "%s: an explicit index list is served from its beginning (start = 0)", who);
   } else {
     FSN_REQUIRE(start <= n_rays && count <= n_rays - start, FSN_E_INVALID,
-                "fsn_ray_batch: positions [%lld, +%lld) leave the %lld rays of the dataset (start + count > N)",
+                "%s: positions [%lld, +%lld) leave the %lld rays of the dataset (start + count > N)", who,
                 (long long)start, (long long)count, (long long)n_rays);
   }
-  FSN_REQUIRE(poses && images, FSN_E_INVALID, "fsn_ray_batch: null poses or images");
+  FSN_REQUIRE(poses && images, FSN_E_INVALID, "%s: null poses or images", who);
   if (count == 0) return FSN_OK;
-  FSN_REQUIRE(order != FSN_RAY_ORDER_EXPLICIT || indices, FSN_E_INVALID, "fsn_ray_batch: null index list");
-  FSN_REQUIRE(rays_o || rays_d || rgb || index, FSN_E_INVALID, "fsn_ray_batch: null pointer for every output");
+  FSN_REQUIRE(order != FSN_RAY_ORDER_EXPLICIT || indices, FSN_E_INVALID, "%s: null index list", who);
+  FSN_REQUIRE(rays_o || rays_d || rgb || index, FSN_E_INVALID, "%s: null pointer for every output", who);
   RayBatchArgs a{};
   a.poses = poses;
   a.images = images;
@@ -202,49 +221,54 @@ extern "C" int fsn_ray_batch(const float* poses, int64_t n_views, const uint8_t*
   a.rays_d = rays_d;
   a.rgb = rgb;
   a.index = index;
-  k_ray_batch<<<(unsigned)((count + 255) / 256), 256, 0, as_stream(stream)>>>(a);
+  const unsigned grid = (unsigned)((count + 255) / 256);
+  if (cam)
+    k_ray_batch<true><<<grid, 256, 0, as_stream(stream)>>>(a, *cam);
+  else
+    k_ray_batch<false><<<grid, 256, 0, as_stream(stream)>>>(a, CamTable{});
   FSN_LAUNCH_CHECK("k_ray_batch");
   return FSN_OK;
 }
 
-extern "C" int fsn_ray_patch_batch(const float* poses, int64_t n_views, const uint8_t* images, int H, int W, int C,
-                                   double focal, int ndc, double near, int white_bkgd, int order, uint64_t seed,
-                                   int64_t epoch, const int64_t* anchors, int64_t start, int64_t count, int P, int dilation,
-                                   float* rays_o, float* rays_d, float* rgb, int64_t* index, fsn_stream_t stream) {
+static int ray_patch_batch_call(const char* who, const CamTable* cam, const float* poses, int64_t n_views,
+                                const uint8_t* images, int H, int W, int C, double focal, int ndc, double near,
+                                int white_bkgd, int order, uint64_t seed, int64_t epoch, const int64_t* anchors,
+                                int64_t start, int64_t count, int P, int dilation, float* rays_o, float* rays_d, float* rgb,
+                                int64_t* index, fsn_stream_t stream) {
   FSN_REQUIRE(n_views >= 0 && H > 0 && W > 0 && focal > 0, FSN_E_INVALID,
-              "fsn_ray_patch_batch: bad geometry n=%lld H=%d W=%d focal=%g", (long long)n_views, H, W, focal);
+              "%s: bad geometry n=%lld H=%d W=%d focal=%g", who, (long long)n_views, H, W, focal);
   FSN_REQUIRE(C == 3 || C == 4, FSN_E_INVALID,
-              "fsn_ray_patch_batch: %d channels (the images are RGB or RGBA bytes: 3 or 4)", C);
+              "%s: %d channels (the images are RGB or RGBA bytes: 3 or 4)", who, C);
   FSN_REQUIRE(!white_bkgd || C == 4, FSN_E_INVALID,
-              "fsn_ray_patch_batch: white_bkgd composes over the alpha channel and needs 4-channel images, got %d", C);
+              "%s: white_bkgd composes over the alpha channel and needs 4-channel images, got %d", who, C);
   FSN_REQUIRE(order == FSN_RAY_ORDER_IDENTITY || order == FSN_RAY_ORDER_PERMUTED || order == FSN_RAY_ORDER_EXPLICIT,
-              FSN_E_INVALID, "fsn_ray_patch_batch: unknown order %d", order);
-  FSN_REQUIRE(P >= 1 && dilation >= 1, FSN_E_INVALID, "fsn_ray_patch_batch: bad patch P=%d dilation=%d (both at least 1)",
+              FSN_E_INVALID, "%s: unknown order %d", who, order);
+  FSN_REQUIRE(P >= 1 && dilation >= 1, FSN_E_INVALID, "%s: bad patch P=%d dilation=%d (both at least 1)", who,
               P, dilation);
   const int64_t ext = (int64_t)(P - 1) * dilation + 1;
   FSN_REQUIRE(ext <= H && ext <= W, FSN_E_INVALID,
-              "fsn_ray_patch_batch: a patch of %d pixels at dilation %d spans %lld pixels and does not fit the %dx%d image",
+              "%s: a patch of %d pixels at dilation %d spans %lld pixels and does not fit the %dx%d image", who,
               P, dilation, (long long)ext, H, W);
   FSN_REQUIRE(n_views <= ((int64_t)1 << 62) / ((int64_t)H * W), FSN_E_UNSUPPORTED,
-              "fsn_ray_patch_batch: more than 2^62 rays");
+              "%s: more than 2^62 rays", who);
   const int64_t AH = H - ext + 1, AW = W - ext + 1, n_anchors = n_views * AH * AW;
   FSN_REQUIRE(start >= 0 && count >= 0 && epoch >= 0, FSN_E_INVALID,
-              "fsn_ray_patch_batch: negative start, count or epoch");
+              "%s: negative start, count or epoch", who);
   if (order == FSN_RAY_ORDER_EXPLICIT) {
     FSN_REQUIRE(start == 0, FSN_E_INVALID,
-                "fsn_ray_patch_batch: an explicit anchor list is served from its beginning (start = 0)");
+                "%s: an explicit anchor list is served from its beginning (start = 0)", who);
   } else {
     FSN_REQUIRE(start <= n_anchors && count <= n_anchors - start, FSN_E_INVALID,
-                "fsn_ray_patch_batch: positions [%lld, +%lld) leave the %lld anchors of the dataset (start + count > A)",
+                "%s: positions [%lld, +%lld) leave the %lld anchors of the dataset (start + count > A)", who,
                 (long long)start, (long long)count, (long long)n_anchors);
   }
-  FSN_REQUIRE(poses, FSN_E_INVALID, "fsn_ray_patch_batch: null poses");
-  FSN_REQUIRE(images || !rgb, FSN_E_INVALID, "fsn_ray_patch_batch: null images with colours asked for (rgb)");
+  FSN_REQUIRE(poses, FSN_E_INVALID, "%s: null poses", who);
+  FSN_REQUIRE(images || !rgb, FSN_E_INVALID, "%s: null images with colours asked for (rgb)", who);
   if (count == 0) return FSN_OK;
-  FSN_REQUIRE(order != FSN_RAY_ORDER_EXPLICIT || anchors, FSN_E_INVALID, "fsn_ray_patch_batch: null anchor list");
-  FSN_REQUIRE(rays_o || rays_d || rgb || index, FSN_E_INVALID, "fsn_ray_patch_batch: null pointer for every output");
+  FSN_REQUIRE(order != FSN_RAY_ORDER_EXPLICIT || anchors, FSN_E_INVALID, "%s: null anchor list", who);
+  FSN_REQUIRE(rays_o || rays_d || rgb || index, FSN_E_INVALID, "%s: null pointer for every output", who);
   const int64_t pp = (int64_t)P * P;
-  FSN_REQUIRE(count <= ((int64_t)1 << 38) / pp, FSN_E_UNSUPPORTED, "fsn_ray_patch_batch: more than 2^38 rows in one call");
+  FSN_REQUIRE(count <= ((int64_t)1 << 38) / pp, FSN_E_UNSUPPORTED, "%s: more than 2^38 rows in one call", who);
   RayPatchArgs pa{};
   RayBatchArgs& a = pa.r;
   a.poses = poses;
@@ -276,9 +300,59 @@ extern "C" int fsn_ray_patch_batch(const float* poses, int64_t n_views, const ui
   pa.dilation = dilation;
   pa.AW = (int)AW;
   pa.H = H;
-  k_ray_patch_batch<<<(unsigned)((count * pp + 255) / 256), 256, 0, as_stream(stream)>>>(pa);
+  const unsigned grid = (unsigned)((count * pp + 255) / 256);
+  if (cam)
+    k_ray_patch_batch<true><<<grid, 256, 0, as_stream(stream)>>>(pa, *cam);
+  else
+    k_ray_patch_batch<false><<<grid, 256, 0, as_stream(stream)>>>(pa, CamTable{});
   FSN_LAUNCH_CHECK("k_ray_patch_batch");
   return FSN_OK;
+}
+
+// The camera table of the _k entry points: K [k_rows, 4], k_rows = 1 (shared by all views) or n_views.
+static int cam_table(const char* who, const float* K, int64_t k_rows, int64_t n_views, CamTable* cam) {
+  FSN_REQUIRE(K, FSN_E_INVALID, "%s: null camera table K", who);
+  FSN_REQUIRE(k_rows == 1 || k_rows == n_views, FSN_E_INVALID,
+              "%s: a camera table of %lld rows (1, or one per view: %lld)", who, (long long)k_rows, (long long)n_views);
+  *cam = CamTable{K, k_rows == 1 ? 0 : 4};
+  return FSN_OK;
+}
+
+extern "C" int fsn_ray_batch(const float* poses, int64_t n_views, const uint8_t* images, int H, int W, int C, double focal,
+                             int ndc, double near, int white_bkgd, int order, uint64_t seed, int64_t epoch,
+                             const int64_t* indices, int64_t start, int64_t count, float* rays_o, float* rays_d,
+                             float* rgb, int64_t* index, fsn_stream_t stream) {
+  return ray_batch_call("fsn_ray_batch", nullptr, poses, n_views, images, H, W, C, focal, ndc, near, white_bkgd, order, seed,
+                        epoch, indices, start, count, rays_o, rays_d, rgb, index, stream);
+}
+
+extern "C" int fsn_ray_batch_k(const float* poses, int64_t n_views, const uint8_t* images, int H, int W, int C, double focal,
+                               const float* K, int64_t k_rows, int ndc, double near, int white_bkgd, int order,
+                               uint64_t seed, int64_t epoch, const int64_t* indices, int64_t start, int64_t count,
+                               float* rays_o, float* rays_d, float* rgb, int64_t* index, fsn_stream_t stream) {
+  CamTable cam;
+  if (int rc = cam_table("fsn_ray_batch_k", K, k_rows, n_views, &cam)) return rc;
+  return ray_batch_call("fsn_ray_batch_k", &cam, poses, n_views, images, H, W, C, focal, ndc, near, white_bkgd, order, seed,
+                        epoch, indices, start, count, rays_o, rays_d, rgb, index, stream);
+}
+
+extern "C" int fsn_ray_patch_batch(const float* poses, int64_t n_views, const uint8_t* images, int H, int W, int C,
+                                   double focal, int ndc, double near, int white_bkgd, int order, uint64_t seed,
+                                   int64_t epoch, const int64_t* anchors, int64_t start, int64_t count, int P, int dilation,
+                                   float* rays_o, float* rays_d, float* rgb, int64_t* index, fsn_stream_t stream) {
+  return ray_patch_batch_call("fsn_ray_patch_batch", nullptr, poses, n_views, images, H, W, C, focal, ndc, near, white_bkgd,
+                              order, seed, epoch, anchors, start, count, P, dilation, rays_o, rays_d, rgb, index, stream);
+}
+
+extern "C" int fsn_ray_patch_batch_k(const float* poses, int64_t n_views, const uint8_t* images, int H, int W, int C,
+                                     double focal, const float* K, int64_t k_rows, int ndc, double near, int white_bkgd,
+                                     int order, uint64_t seed, int64_t epoch, const int64_t* anchors, int64_t start,
+                                     int64_t count, int P, int dilation, float* rays_o, float* rays_d, float* rgb,
+                                     int64_t* index, fsn_stream_t stream) {
+  CamTable cam;
+  if (int rc = cam_table("fsn_ray_patch_batch_k", K, k_rows, n_views, &cam)) return rc;
+  return ray_patch_batch_call("fsn_ray_patch_batch_k", &cam, poses, n_views, images, H, W, C, focal, ndc, near, white_bkgd,
+                              order, seed, epoch, anchors, start, count, P, dilation, rays_o, rays_d, rgb, index, stream);
 }
 
 extern "C" int fsn_ray_perm_host(int64_t N, uint64_t seed, int64_t epoch, int64_t start, int64_t count, int64_t* out_host) {

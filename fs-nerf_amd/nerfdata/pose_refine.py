@@ -2,7 +2,7 @@
 
 View v carries a correction xi_v = (omega_v, tau_v) on top of its stored pose [R0_v | t0_v]:
 R_v = exp([omega_v]x) R0_v (left-multiplied, world frame), t_v = t0_v + tau_v; |omega| < pi; xi = 0 is the stored pose
-value for value.  Intrinsics stay fixed.  CameraRefiner holds xi; RayLoader / PatchLoader(cameras=refiner) serve their
+value for value.  The intrinsics are IntrinsicsRefiner's (intrinsics_refine.py).  CameraRefiner holds xi; RayLoader / PatchLoader(cameras=refiner) serve their
 batches over its corrected poses (one fsn_pose_compose launch per change of xi) and hand rays_o / rays_d out of one
 autograd Function whose backward is the single deterministic fsn_ray_pose_grad launch into xi.grad.  pose_error scores
 refined poses against the truth up to the joint problem's gauge (a similarity transform)."""
@@ -67,33 +67,53 @@ class CameraRefiner(nn.Module):
     def served(self, geometry: Tuple[int, int, float, bool, float], launch: Callable[[Tensor], tuple]):
         """A loader's batch over the corrected poses: `launch(poses12)` is its one ray_batch / ray_patch_batch call
         (with the index) -> (rays_o, rays_d, rgb, index), rays_o / rays_d attached to xi."""
-        return _PoseRays.apply(self.xi, self, geometry, launch)
+        return served_rays(self.poses0, self, None, geometry, lambda poses12, _K: launch(poses12))
 
 
-class _PoseRays(torch.autograd.Function):
-    """forward: the loader's launch over refiner.poses12(); backward: ONE fsn_ray_pose_grad launch -> dL/dxi.  No host
-    synchronisation on either side."""
+def served_rays(poses0: Tensor, cameras: Optional[CameraRefiner], intrinsics, geometry, launch):
+    """A loader's batch over learnable cameras: `cameras` (a CameraRefiner) and / or `intrinsics` (an
+    IntrinsicsRefiner), `poses0` the stored [n,12] poses, geometry = (H, W, focal, ndc, near) of the dataset;
+    `launch(poses12, K)` is the loader's one ray_batch / ray_patch_batch call (with the index) over the matrices and the
+    camera table it is handed (None: the stored ones) -> (rays_o, rays_d, rgb, index), rays_o / rays_d attached to xi
+    and phi through ONE autograd node."""
+    return _CameraRays.apply(None if cameras is None else cameras.xi, None if intrinsics is None else intrinsics.phi,
+                             poses0, cameras, intrinsics, geometry, launch)
+
+
+class _CameraRays(torch.autograd.Function):
+    """forward: the loader's launch over cameras.poses12() and intrinsics.K(); backward, with poses alone: ONE
+    fsn_ray_pose_grad launch -> dL/dxi; with intrinsics: ONE fsn_ray_camera_grad launch -> dL/dxi and the per-view
+    dL/dK, then fsn_intrinsics_grad -> dL/dphi.  No host synchronisation on either side."""
 
     @staticmethod
-    def forward(ctx, xi: Tensor, refiner: CameraRefiner, geometry, launch):
-        o, d, rgb, index = launch(refiner.poses12())
-        ctx.save_for_backward(xi, index)
-        ctx.refiner, ctx.geometry = refiner, geometry
+    def forward(ctx, xi: Optional[Tensor], phi: Optional[Tensor], poses0: Tensor, cameras, intrinsics, geometry, launch):
+        K = None if intrinsics is None else intrinsics.K()
+        o, d, rgb, index = launch(None if cameras is None else cameras.poses12(), K)
+        ctx.save_for_backward(index, *[t for t in (xi, phi) if t is not None])
+        ctx.poses0, ctx.K = poses0, K  # (K: the table of THIS batch - a later step makes a new one)
+        ctx.cameras, ctx.intrinsics, ctx.geometry = cameras, intrinsics, geometry
         ctx.mark_non_differentiable(*[t for t in (rgb, index) if t is not None])
         ctx.set_materialize_grads(False)
         return o, d, rgb, index
 
     @staticmethod
     def backward(ctx, grad_o, grad_d, _grad_rgb, _grad_index):
-        xi, index = ctx.saved_tensors
-        ref = ctx.refiner
+        index, *params = ctx.saved_tensors
+        cam, intr = ctx.cameras, ctx.intrinsics
+        xi = params[0] if cam is not None else None
         H, W, focal, ndc, near = ctx.geometry
-        g = ops.ray_pose_grad(ref.poses0, xi, H, W, focal, index, grad_o, grad_d, ndc=ndc, near=near)
-        if not ref.learn_rotation:
-            g[:, :3].zero_()
-        if not ref.learn_translation:
-            g[:, 3:].zero_()
-        return g, None, None, None
+        if intr is None:
+            g = ops.ray_pose_grad(cam.poses0, xi, H, W, focal, index, grad_o, grad_d, ndc=ndc, near=near)
+            g_phi = None
+        else:
+            g, g_K = ops.ray_camera_grad(ctx.poses0, xi, H, W, focal, ctx.K, index, grad_o, grad_d, ndc=ndc, near=near)
+            g_phi = intr.grad_phi(g_K)
+        if cam is not None:
+            if not cam.learn_rotation:
+                g[:, :3].zero_()
+            if not cam.learn_translation:
+                g[:, 3:].zero_()
+        return g, g_phi, None, None, None, None, None
 
 
 def _poses44(p, name: str) -> Tensor:

@@ -83,13 +83,14 @@ class RayDataset:
 
     def batch(self, order: str, *, start: int = 0, count: Optional[int] = None, seed: int = 0, epoch: int = 0,
               indices: Optional[Tensor] = None, want_rays: bool = True, want_rgb: bool = True, want_index: bool = False,
-              poses12: Optional[Tensor] = None):
+              poses12: Optional[Tensor] = None, K: Optional[Tensor] = None):
         """ops.ray_batch on this dataset's tensors: (rays_o, rays_d, rgb, index), None where not wanted.
-        poses12: other [n,12] matrices than the stored ones (CameraRefiner.poses12())."""
+        poses12: other [n,12] matrices than the stored ones (CameraRefiner.poses12()); K: a camera table [1 or n, 4] in
+        place of the stored intrinsics (IntrinsicsRefiner.K())."""
         H, W, focal = self.hwf
         return ops.ray_batch(self.poses12 if poses12 is None else poses12, self.imgs, H, W, focal, ndc=self.ndc, near=_NDC_NEAR, white_bkgd=self.white_bkgd,
                              order=order, seed=seed, epoch=epoch, indices=indices, start=start, count=count,
-                             want_rays=want_rays, want_rgb=want_rgb, want_index=want_index)
+                             want_rays=want_rays, want_rgb=want_rgb, want_index=want_index, K=K)
 
     def n_anchors(self, patch: int, dilation: int = 1) -> int:
         """The number of `patch` x `patch` patches at `dilation` that fit the images: n * (H - ext + 1) * (W - ext + 1)
@@ -105,16 +106,18 @@ class RayDataset:
 
     def patch_batch(self, order: str, patch: int, dilation: int = 1, *, start: int = 0, count: Optional[int] = None,
                     seed: int = 0, epoch: int = 0, anchors: Optional[Tensor] = None, want_rays: bool = True,
-                    want_rgb: bool = True, want_index: bool = False, poses12: Optional[Tensor] = None):
+                    want_rgb: bool = True, want_index: bool = False, poses12: Optional[Tensor] = None,
+                    K: Optional[Tensor] = None):
         """ops.ray_patch_batch on this dataset's tensors: `count` patches of `patch` x `patch` pixels from position
         `start` of `order` over the n_anchors(patch, dilation) anchors -> (rays_o, rays_d, rgb, index) of
         count * patch^2 rows, patch after patch, row-major inside a patch; None where not wanted.
-        poses12: as batch()."""
+        poses12, K: as batch()."""
         self.n_anchors(patch, dilation)
         H, W, focal = self.hwf
         return ops.ray_patch_batch(self.poses12 if poses12 is None else poses12, self.imgs, H, W, focal, patch, dilation, ndc=self.ndc, near=_NDC_NEAR,
                                    white_bkgd=self.white_bkgd, order=order, seed=seed, epoch=epoch, anchors=anchors,
-                                   start=start, count=count, want_rays=want_rays, want_rgb=want_rgb, want_index=want_index)
+                                   start=start, count=count, want_rays=want_rays, want_rgb=want_rgb, want_index=want_index,
+                                   K=K)
 
     def __getitem__(self, idx):
         """Not the hot path (the loaders never come here): a tensor of indices costs one min / max read-back so that an
@@ -155,17 +158,27 @@ class RayLoader:
 
     cameras (a CameraRefiner over this dataset's views; None: the stored poses, the code path above): the same one
     launch runs over cameras.poses12(), and rays_o / rays_d come out of one autograd Function whose backward is one
-    fsn_ray_pose_grad launch into cameras.xi.grad (pose_refine.py); still no host synchronisation.  Intrinsics and the
-    dataset's region of interest (aabb) stay those of the stored poses."""
+    fsn_ray_pose_grad launch into cameras.xi.grad (pose_refine.py); still no host synchronisation.  The dataset's
+    region of interest (aabb) stays that of the stored poses.
+
+    intrinsics (an IntrinsicsRefiner, alone or with cameras): the launch runs over intrinsics.K() as well, and the one
+    autograd node's backward is fsn_ray_camera_grad (+ fsn_intrinsics_grad) into xi.grad and intrinsics.phi.grad
+    (intrinsics_refine.py).  The NDC map and the aabb stay those of the stored focal."""
 
     def __init__(self, dataset: RayDataset, batch_size: int, shuffle: bool = True, seed: Optional[int] = None, rank: int = 0,
-                 world: int = 1, with_index: bool = False, cameras=None):
+                 world: int = 1, with_index: bool = False, cameras=None, intrinsics=None):
         if batch_size <= 0 or world <= 0 or not 0 <= rank < world:
             raise ValueError(f"RayLoader: bad batch_size {batch_size}, rank {rank} or world {world}")
         if cameras is not None and (cameras.n_views != dataset.n_views or cameras.poses0.device != dataset.device):
             raise ValueError(f"RayLoader: cameras of {cameras.n_views} views on {cameras.poses0.device} do not match the "
                              f"dataset's {dataset.n_views} views on {dataset.device}")
-        self.cameras = cameras
+        if intrinsics is not None and (intrinsics.n_views not in (None, dataset.n_views)
+                                       or intrinsics.device != dataset.device
+                                       or tuple(intrinsics.hwf0) != tuple(dataset.hwf)):
+            raise ValueError(f"RayLoader: intrinsics of {intrinsics.n_views} views over hwf {intrinsics.hwf0} on "
+                             f"{intrinsics.device} do not match the dataset's {dataset.n_views} views over "
+                             f"{dataset.hwf} on {dataset.device}")
+        self.cameras, self.intrinsics = cameras, intrinsics
         self.dataset, self.batch_size, self.shuffle = dataset, int(batch_size), bool(shuffle)
         self.seed = _seed_or_default(seed)
         self.rank, self.world, self.with_index = int(rank), int(world), bool(with_index)
@@ -179,14 +192,16 @@ class RayLoader:
 
     def _serve(self, order: str, start: int, count: int, epoch: int):
         """The one launch of a next(): `count` items from position `start` of this epoch's order."""
-        if self.cameras is not None:
-            return self._serve_refined(lambda poses12: self.dataset.batch(
-                order, start=start, count=count, seed=self.seed, epoch=epoch, want_index=True, poses12=poses12))
+        if self.cameras is not None or self.intrinsics is not None:
+            return self._serve_refined(lambda poses12, K: self.dataset.batch(
+                order, start=start, count=count, seed=self.seed, epoch=epoch, want_index=True, poses12=poses12, K=K))
         return self.dataset.batch(order, start=start, count=count, seed=self.seed, epoch=epoch, want_index=self.with_index)
 
     def _serve_refined(self, launch):
+        from .pose_refine import served_rays  # (pose_refine imports this module)
         ds = self.dataset
-        return self.cameras.served((ds.hwf[0], ds.hwf[1], ds.hwf[2], ds.ndc, _NDC_NEAR), launch)
+        return served_rays(ds.poses12, self.cameras, self.intrinsics, (ds.hwf[0], ds.hwf[1], ds.hwf[2], ds.ndc, _NDC_NEAR),
+                           launch)
 
     def __len__(self) -> int:
         n, stride = self._n_items(), self.batch_size * self.world
@@ -235,11 +250,12 @@ class PatchLoader(RayLoader):
     `dilation` apart, patch after patch, so rgb.view(B, patch, patch, 3) is the patch stack.  RayLoader's contract holds
     over the ANCHORS (top-left pixels, dataset.n_anchors(patch, dilation) of them): a new permutation per iter(), every
     anchor exactly once per epoch, a short last batch, the world / rank slices, state_dict() / load_state_dict().
-    ValueError for a patch that does not fit the images.  cameras: as RayLoader."""
+    ValueError for a patch that does not fit the images.  cameras, intrinsics: as RayLoader."""
 
     def __init__(self, dataset: RayDataset, patch: int, patches_per_batch: int, dilation: int = 1, shuffle: bool = True,
-                 seed: Optional[int] = None, rank: int = 0, world: int = 1, with_index: bool = False, cameras=None):
-        super().__init__(dataset, patches_per_batch, shuffle, seed, rank, world, with_index, cameras)
+                 seed: Optional[int] = None, rank: int = 0, world: int = 1, with_index: bool = False, cameras=None,
+                 intrinsics=None):
+        super().__init__(dataset, patches_per_batch, shuffle, seed, rank, world, with_index, cameras, intrinsics)
         self.patch, self.dilation = int(patch), int(dilation)
         self._anchors = dataset.n_anchors(self.patch, self.dilation)
 
@@ -247,10 +263,10 @@ class PatchLoader(RayLoader):
         return self._anchors
 
     def _serve(self, order: str, start: int, count: int, epoch: int):
-        if self.cameras is not None:
-            return self._serve_refined(lambda poses12: self.dataset.patch_batch(
+        if self.cameras is not None or self.intrinsics is not None:
+            return self._serve_refined(lambda poses12, K: self.dataset.patch_batch(
                 order, self.patch, self.dilation, start=start, count=count, seed=self.seed, epoch=epoch, want_index=True,
-                poses12=poses12))
+                poses12=poses12, K=K))
         return self.dataset.patch_batch(order, self.patch, self.dilation, start=start, count=count, seed=self.seed,
                                         epoch=epoch, want_index=self.with_index)
 

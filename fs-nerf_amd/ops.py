@@ -278,11 +278,13 @@ _RAY_ORDERS = {"identity": L.FSN_RAY_ORDER_IDENTITY, "permuted": L.FSN_RAY_ORDER
 def ray_batch(poses12: Tensor, images: Tensor, H: int, W: int, focal: float, *, ndc: bool = False, near: float = 1.0,
               white_bkgd: bool = False, order: str = "identity", seed: int = 0, epoch: int = 0,
               indices: Optional[Tensor] = None, start: int = 0, count: Optional[int] = None, want_rays: bool = True,
-              want_rgb: bool = True, want_index: bool = False):
+              want_rgb: bool = True, want_index: bool = False, K: Optional[Tensor] = None):
     """One batch of the data layer in ONE launch (fsn_ray_batch), no host synchronisation: `count` rays from position
     `start` of `order` ("identity", "permuted" by (seed, epoch), or "explicit" = the device int64 list `indices`) over
     the rays of the resident dataset (poses12 [n,12] float32, images uint8 [n,H,W,3|4], both on the GPU) ->
-    (rays_o [count,3], rays_d [count,3], rgb [count,3], index [count] int64); an output not asked for is None."""
+    (rays_o [count,3], rays_d [count,3], rgb [count,3], index [count] int64); an output not asked for is None.
+    K: a camera table (intrinsics_compose) [1 or n, 4] -> the same launch over it (fsn_ray_batch_k); `focal` then feeds
+    the NDC constants only."""
     if not (poses12.is_cuda and images.is_cuda):
         raise RuntimeError("ray_batch: expected GPU tensors (the HIP path has no CPU fallback)")
     if images.dtype != torch.uint8 or poses12.dtype != torch.float32 or images.dim() != 4:
@@ -298,22 +300,26 @@ def ray_batch(poses12: Tensor, images: Tensor, H: int, W: int, focal: float, *, 
     d = torch.empty(count, 3, device=dev, dtype=torch.float32) if want_rays else None
     rgb = torch.empty(count, 3, device=dev, dtype=torch.float32) if want_rgb else None
     index = torch.empty(count, device=dev, dtype=torch.int64) if want_index else None
-    _launch("fsn_ray_batch", dev, poses12, poses12.shape[0], images, int(H), int(W), images.shape[3], float(focal),
-            1 if ndc else 0, float(near), 1 if white_bkgd else 0, _RAY_ORDERS[order], int(seed) & 0xFFFFFFFFFFFFFFFF,
+    head = (poses12, poses12.shape[0], images, int(H), int(W), images.shape[3], float(focal))
+    tail = (1 if ndc else 0, float(near), 1 if white_bkgd else 0, _RAY_ORDERS[order], int(seed) & 0xFFFFFFFFFFFFFFFF,
             int(epoch), indices, int(start), int(count), o, d, rgb, index)
+    if K is None:
+        _launch("fsn_ray_batch", dev, *head, *tail)
+    else:
+        _launch("fsn_ray_batch_k", dev, *head, *_camera_table(K, poses12.shape[0], "ray_batch"), *tail)
     return o, d, rgb, index
 
 
 def ray_patch_batch(poses12: Tensor, images: Optional[Tensor], H: int, W: int, focal: float, patch: int, dilation: int = 1, *,
                     ndc: bool = False, near: float = 1.0, white_bkgd: bool = False, order: str = "identity", seed: int = 0,
                     epoch: int = 0, anchors: Optional[Tensor] = None, start: int = 0, count: Optional[int] = None,
-                    want_rays: bool = True, want_rgb: bool = True, want_index: bool = False):
+                    want_rays: bool = True, want_rgb: bool = True, want_index: bool = False, K: Optional[Tensor] = None):
     """A batch of `patch` x `patch` pixel patches in ONE launch (fsn_ray_patch_batch), no host synchronisation: `count`
     patches from position `start` of `order` over the ANCHORS (top-left pixels) of the dataset - n * (H - ext + 1) *
     (W - ext + 1) of them, ext = (patch - 1) * dilation + 1; "explicit" = the device int64 list `anchors` ->
     (rays_o, rays_d, rgb [count * patch^2, 3], index [count * patch^2] int64), patch b in rows [b * patch^2, +patch^2),
     row-major, so rgb.view(count, patch, patch, 3) is the patch stack; an output not asked for is None.
-    images=None (with want_rgb=False): ray-only patches for any poses."""
+    images=None (with want_rgb=False): ray-only patches for any poses.  K: as ray_batch (fsn_ray_patch_batch_k)."""
     if not (poses12.is_cuda and (images is None or images.is_cuda)):
         raise RuntimeError("ray_patch_batch: expected GPU tensors (the HIP path has no CPU fallback)")
     if poses12.dtype != torch.float32 or poses12.dim() != 2 or poses12.shape[1] != 12 or not poses12.is_contiguous():
@@ -337,9 +343,13 @@ def ray_patch_batch(poses12: Tensor, images: Optional[Tensor], H: int, W: int, f
     d = torch.empty(rows, 3, device=dev, dtype=torch.float32) if want_rays else None
     rgb = torch.empty(rows, 3, device=dev, dtype=torch.float32) if want_rgb else None
     index = torch.empty(rows, device=dev, dtype=torch.int64) if want_index else None
-    _launch("fsn_ray_patch_batch", dev, poses12, poses12.shape[0], images, int(H), int(W), channels, float(focal),
-            1 if ndc else 0, float(near), 1 if white_bkgd else 0, _RAY_ORDERS[order], int(seed) & 0xFFFFFFFFFFFFFFFF,
+    head = (poses12, poses12.shape[0], images, int(H), int(W), channels, float(focal))
+    tail = (1 if ndc else 0, float(near), 1 if white_bkgd else 0, _RAY_ORDERS[order], int(seed) & 0xFFFFFFFFFFFFFFFF,
             int(epoch), anchors, int(start), int(count), int(patch), int(dilation), o, d, rgb, index)
+    if K is None:
+        _launch("fsn_ray_patch_batch", dev, *head, *tail)
+    else:
+        _launch("fsn_ray_patch_batch_k", dev, *head, *_camera_table(K, poses12.shape[0], "ray_patch_batch"), *tail)
     return o, d, rgb, index
 
 
@@ -427,6 +437,81 @@ def ray_pose_grad(poses0: Tensor, xi: Tensor, H: int, W: int, focal: float, inde
     _launch("fsn_ray_pose_grad", dev, poses0, xi, poses0.shape[0], int(H), int(W), float(focal), 1 if ndc else 0, float(near),
             index, grad_o, grad_d, count, grad_xi, grad_poses)
     return (grad_xi, grad_poses) if want_pose_grad else grad_xi
+
+
+def _camera_table(K: Tensor, n_views: int, who: str) -> Tuple[Tensor, int]:
+    """A camera table K = (fx, fy, cx, cy) [1 or n_views, 4] as the kernels read it -> (K, its rows); nothing is cast."""
+    if not K.is_cuda:
+        raise RuntimeError(f"{who}: K: expected a GPU tensor (the HIP path has no CPU fallback)")
+    if K.dtype != torch.float32:
+        raise TypeError(f"{who}: the camera table K is float32, got {K.dtype}")
+    if K.dim() != 2 or K.shape[1] != 4 or K.shape[0] not in (1, n_views) or not K.is_contiguous():
+        raise ValueError(f"{who}: the camera table K is [1 or {n_views}, 4], contiguous, got {tuple(K.shape)}")
+    return K.detach(), K.shape[0]
+
+
+def _phi(phi: Tensor, who: str) -> Tensor:
+    if not phi.is_cuda:
+        raise RuntimeError(f"{who}: expected GPU tensors (the HIP path has no CPU fallback)")
+    if phi.dtype != torch.float32:
+        raise TypeError(f"{who}: phi is float32, got {phi.dtype}")
+    if phi.dim() != 2 or phi.shape[1] != 4 or not phi.is_contiguous():
+        raise ValueError(f"{who}: phi is [m, 4], contiguous, got {tuple(phi.shape)}")
+    return phi.detach()
+
+
+def intrinsics_compose(phi: Tensor, H: int, W: int, focal0: float, tie_focal: bool = True) -> Tensor:
+    """The camera table K = (fx, fy, cx, cy) [m,4] of the parameter phi [m,4] over the stored (H, W, focal0) in ONE
+    launch (fsn_intrinsics_compose): fx = f0 exp(phi_0), fy = f0 exp(phi_1) (tie_focal: fy = fx),
+    cx = W/2 + W phi_2, cy = H/2 + H phi_3; phi = 0 gives the stored intrinsics value for value."""
+    phi = _phi(phi, "intrinsics_compose")
+    out = torch.empty_like(phi)
+    _launch("fsn_intrinsics_compose", phi.device, phi, phi.shape[0], int(H), int(W), float(focal0), 1 if tie_focal else 0, out)
+    return out
+
+
+def ray_camera_grad(poses0: Tensor, xi: Optional[Tensor], H: int, W: int, focal0: float, K: Tensor, index: Tensor,
+                    grad_o: Optional[Tensor], grad_d: Optional[Tensor], *, ndc: bool = False, near: float = 1.0,
+                    want_xi_grad: Optional[bool] = None) -> Tuple[Optional[Tensor], Tensor]:
+    """(dL/dxi [n,6] or None, dL/dK per view [n,4]) from the gradients of a batch's rays in ONE deterministic launch
+    (fsn_ray_camera_grad): ray_pose_grad's arguments over the camera table K [1 or n, 4] the rays were served with.
+    xi=None: no pose correction (the rays of poses0).  want_xi_grad: None = where xi is given.  Row v of the second
+    output is view v's rays' share of dL/d(fx, fy, cx, cy) (intrinsics_grad chains it to phi); a view without a ray gets
+    exactly 0 in both."""
+    if xi is None:
+        if not poses0.is_cuda:
+            raise RuntimeError("ray_camera_grad: expected GPU tensors (the HIP path has no CPU fallback)")
+        if poses0.dtype != torch.float32 or poses0.dim() != 2 or poses0.shape[1] != 12 or not poses0.is_contiguous():
+            raise TypeError("ray_camera_grad: poses are float32 [n,12], contiguous")
+    else:
+        _pose_pair(poses0, xi, "ray_camera_grad")
+        xi = xi.detach()
+    n, dev = poses0.shape[0], poses0.device
+    K, k_rows = _camera_table(K, n, "ray_camera_grad")
+    index = _i64(index, "index").reshape(-1)
+    count = index.numel()
+    grad_o = _flat(grad_o, "grad_o", 3 * count)
+    grad_d = _flat(grad_d, "grad_d", 3 * count)
+    want_xi_grad = xi is not None if want_xi_grad is None else want_xi_grad
+    grad_xi = torch.empty(n, 6, device=dev, dtype=torch.float32) if want_xi_grad else None
+    grad_K = torch.empty(n, 4, device=dev, dtype=torch.float32)
+    _launch("fsn_ray_camera_grad", dev, poses0, xi, n, int(H), int(W), float(focal0), K, k_rows, 1 if ndc else 0, float(near),
+            index, grad_o, grad_d, count, grad_xi, grad_K)
+    return grad_xi, grad_K
+
+
+def intrinsics_grad(phi: Tensor, grad_K_views: Tensor, H: int, W: int, focal0: float, tie_focal: bool = True) -> Tensor:
+    """dL/dphi [m,4] from ray_camera_grad's per-view dL/dK [n,4] in ONE launch (fsn_intrinsics_grad): the chain K -> phi
+    and, for a shared row (m = 1), the sum over the views in float64 in a fixed order."""
+    phi = _phi(phi, "intrinsics_grad")
+    g = _gpu_f32(grad_K_views, "grad_K_views")
+    if g.dim() != 2 or g.shape[1] != 4 or phi.shape[0] not in (1, g.shape[0]) or g.device != phi.device:
+        raise ValueError(f"intrinsics_grad: grad_K_views is [n,4] and phi [1 or n,4] on one device, got {tuple(g.shape)} "
+                         f"and {tuple(phi.shape)}")
+    out = torch.empty_like(phi)
+    _launch("fsn_intrinsics_grad", phi.device, phi, g, g.shape[0], phi.shape[0], int(H), int(W), float(focal0),
+            1 if tie_focal else 0, out)
+    return out
 
 
 def to_ndc(rays_o: Tensor, rays_d: Tensor, H: int, W: int, focal: float, near: float) -> Tuple[Tensor, Tensor]:

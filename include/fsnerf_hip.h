@@ -79,7 +79,7 @@ int fsn_version(void);
  *   "metrics"    metrics.hip     every LDS index of k_ssim_tile
  *   "ssim_grad"  ssim_grad.hip   every LDS index of the two kernels behind the SSIM gradient
  *   "lpips"      lpips.hip       every LDS index of k_lpips_conv and k_lpips_first_bwd
- *   "pose_refine" pose_refine.hip  ray indices outside [0, N) handed to fsn_ray_pose_grad
+ *   "pose_refine" pose_refine.hip  ray indices outside [0, N) handed to fsn_ray_pose_grad / fsn_ray_camera_grad
  * A record is 4 uint32 = {violations, source line of the first, its index (or the end of its span), the extent}, the
  * last two truncated to 32 bits.  fsn_debug_report synchronises the device, copies the record of `unit` to out4 and
  * clears it; an unknown unit is FSN_E_INVALID (the message lists the known ones), the release library returns
@@ -179,6 +179,49 @@ int fsn_pose_compose(const float* poses0, const float* xi, int64_t n, float* pos
 int fsn_ray_pose_grad(const float* poses0, const float* xi, int64_t n_views, int H, int W, double focal, int ndc,
                       double near, const int64_t* index, const float* grad_o, const float* grad_d, int64_t count,
                       float* grad_xi, float* grad_poses, fsn_stream_t stream);
+
+/* ---- learnable intrinsics behind the data layer (this package's own)
+ *                                                                           csrc/pose_refine.hip, csrc/raydata.hip
+ * A camera table K = (fx, fy, cx, cy), float32 [k_rows, 4] on the DEVICE, k_rows = 1 (shared by all views) or n_views.
+ * The camera-frame direction of pixel (h, w) is u / |u|, u = ((w - cx)/fx, -(h - cy)/fy, -1): the arithmetic of
+ * fsn_ray_batch with the table's values in place of its launch constants (focal, focal, (float)(W*0.5), (float)(H*0.5)).
+ * fsn_intrinsics_compose: phi [m, 4] -> K_out [m, 4] (both DEVICE), one thread per row:
+ *   fx = f0 exp(phi_0),  fy = f0 exp(phi_1) (tie_focal: fy = fx, phi_1 unused),  cx = W/2 + W phi_2,  cy = H/2 + H phi_3
+ * with f0 = (float)focal0; phi = 0 gives fsn_ray_batch's launch constants value for value.
+ * Errors (FSN_E_INVALID): m < 0, H, W or focal0 <= 0, a null pointer. */
+int fsn_intrinsics_compose(const float* phi, int64_t m, int H, int W, double focal0, int tie_focal, float* K_out,
+                           fsn_stream_t stream);
+/* fsn_ray_batch / fsn_ray_patch_batch over a camera table: the same arguments plus K [k_rows, 4]; the same kernels
+ * (a compile-time switch), the same rows but for the pinhole direction, which is the table's.  `focal` keeps feeding the
+ * NDC constants: the NDC map is a fixed warp of space and does not follow the learned focal.
+ * Errors: those of the two entry points; FSN_E_INVALID for a null K or k_rows not in {1, n_views}. */
+int fsn_ray_batch_k(const float* poses, int64_t n_views, const uint8_t* images, int H, int W, int C, double focal,
+                    const float* K, int64_t k_rows, int ndc, double near, int white_bkgd, int order, uint64_t seed,
+                    int64_t epoch, const int64_t* indices, int64_t start, int64_t count, float* rays_o, float* rays_d,
+                    float* rgb, int64_t* index, fsn_stream_t stream);
+int fsn_ray_patch_batch_k(const float* poses, int64_t n_views, const uint8_t* images, int H, int W, int C, double focal,
+                          const float* K, int64_t k_rows, int ndc, double near, int white_bkgd, int order, uint64_t seed,
+                          int64_t epoch, const int64_t* anchors, int64_t start, int64_t count, int P, int dilation,
+                          float* rays_o, float* rays_d, float* rgb, int64_t* index, fsn_stream_t stream);
+/* The backward of "flat ray index -> ray of the corrected pose under the camera table", reduced per view in ONE launch:
+ * fsn_ray_pose_grad's walk (one workgroup per view, no atomics, a fixed summation order) with four more sums.
+ * xi [n_views, 6] may be NULL = no correction (the rays were served over poses0).  Outputs, WRITTEN for every view and
+ * exactly 0 for a view without a ray in the batch: grad_xi [n_views, 6] (may be NULL) - with the stored intrinsics in K
+ * bit for bit fsn_ray_pose_grad's; grad_K_views [n_views, 4] = this view's rays' share of dL/d(fx, fy, cx, cy).
+ * focal0 feeds the NDC constants only.  An index outside [0, n_views*H*W) contributes nothing (and, in the debug build,
+ * is recorded for fsn_debug_report("pose_refine")).
+ * Errors (FSN_E_INVALID): n_views < 0, H, W or focal0 <= 0, count < 0, null poses0 / K / grad_K_views, null index with
+ * count > 0, k_rows not in {1, n_views}; FSN_E_UNSUPPORTED: H*W or n_views of 2^31 or more. */
+int fsn_ray_camera_grad(const float* poses0, const float* xi, int64_t n_views, int H, int W, double focal0, const float* K,
+                        int64_t k_rows, int ndc, double near, const int64_t* index, const float* grad_o,
+                        const float* grad_d, int64_t count, float* grad_xi, float* grad_K_views, fsn_stream_t stream);
+/* The chain K -> phi: grad_K_views [n_views, 4] -> grad_phi [m, 4] (WRITTEN), m = 1 or n_views:
+ *   dL/dphi_0 = fx dL/dfx (+ fy dL/dfy with tie_focal, and then dL/dphi_1 = 0),  dL/dphi_1 = fy dL/dfy,
+ *   dL/dphi_2 = W dL/dcx,  dL/dphi_3 = H dL/dcy.
+ * m = 1 sums over the views first, in float64, in a fixed order inside one workgroup; m = n_views: one thread per view.
+ * Errors (FSN_E_INVALID): n_views < 0, H, W or focal0 <= 0, m not in {1, n_views}, a null pointer. */
+int fsn_intrinsics_grad(const float* phi, const float* grad_K_views, int64_t n_views, int64_t m, int H, int W,
+                        double focal0, int tie_focal, float* grad_phi, fsn_stream_t stream);
 
 /* ---- unseen views: random poses and their patch rays (this package's own, after RegNeRF's)
  *                                                                                              csrc/unseen_views.hip
