@@ -391,7 +391,7 @@ __device__ __forceinline__ void sample_pdf_merge_ray(const float* __restrict__ e
 // Pinhole ray of pixel (h, w) (src/utils/utilities.py:57-80): d_cam = [(w - W/2)/f, -(h - H/2)/f, -1], unit length,
 // rotated by the pose's 3x3 block (row-major [3][4] in m), origin = its last column.  The one definition used by
 // k_get_rays and by the fused render kernel when it generates its own rays.
-// (pinhole_dir_cam: its unit camera-frame direction alone, for the pose gradient of pose_refine.hip)
+// (pinhole_dir_cam: its unit camera-frame direction alone)
 __device__ __forceinline__ void pinhole_dir_cam(float half_w, float half_h, float focal, int h, int w, float (&c)[3]) {
   float dx = ((float)w - half_w) / focal;
   float dy = -((float)h - half_h) / focal;

@@ -3,6 +3,7 @@
 // composite (dense and packed).  All are streaming kernels: coalesced row-major access,
 // one thread per output element or one wavefront per ray.
 #include "common.hpp"
+#include "pinhole_consts.hpp"
 #include "ray_dev.hpp"
 
 namespace fsn {
@@ -253,9 +254,9 @@ extern "C" int fsn_get_rays(const float* pose_host, int H, int W, double focal, 
   if (npix == 0) return FSN_OK;
   Pose34 P;
   for (int i = 0; i < 12; ++i) P.m[i] = pose_host[i];
-  // W*0.5 and H*0.5 are formed in double by Python and then rounded to float32 (utilities.py:67)
-  k_get_rays<<<nblocks(npix, 256), 256, 0, as_stream(stream)>>>(P, W, (float)(W * 0.5), (float)(H * 0.5),
-                                                               (float)focal, row0, npix, rays_o, rays_d);
+  const PinholeConsts pc = pinhole_consts(H, W, focal, 0.0);
+  k_get_rays<<<nblocks(npix, 256), 256, 0, as_stream(stream)>>>(P, W, pc.half_w, pc.half_h, pc.focal, row0, npix, rays_o,
+                                                               rays_d);
   FSN_LAUNCH_CHECK("k_get_rays");
   return FSN_OK;
 }
@@ -265,10 +266,9 @@ extern "C" int fsn_to_ndc(const float* rays_o, const float* rays_d, int64_t n, i
   FSN_REQUIRE(n >= 0 && H > 0 && W > 0 && focal > 0, FSN_E_INVALID, "fsn_to_ndc: bad arguments");
   if (n == 0) return FSN_OK;
   FSN_REQUIRE(rays_o && rays_d && ndc_o && ndc_d, FSN_E_INVALID, "fsn_to_ndc: null pointer");
-  const float sx = (float)(-1.0 / (W / (2.0 * focal)));
-  const float sy = (float)(-1.0 / (H / (2.0 * focal)));
-  k_to_ndc<<<nblocks(n, 256), 256, 0, as_stream(stream)>>>(rays_o, rays_d, n, sx, sy, (float)near,
-                                                          (float)(2.0 * near), ndc_o, ndc_d);
+  const PinholeConsts pc = pinhole_consts(H, W, focal, near);
+  k_to_ndc<<<nblocks(n, 256), 256, 0, as_stream(stream)>>>(rays_o, rays_d, n, pc.sx, pc.sy, pc.near, pc.two_near, ndc_o,
+                                                          ndc_d);
   FSN_LAUNCH_CHECK("k_to_ndc");
   return FSN_OK;
 }
@@ -285,10 +285,9 @@ extern "C" int fsn_build_rays(const float* poses, int64_t n_poses, int H, int W,
     k_aabb_init<<<1, 64, 0, s>>>(aabb_keys);
     FSN_LAUNCH_CHECK("k_aabb_init");
   }
-  const float sx = (float)(-1.0 / (W / (2.0 * focal))), sy = (float)(-1.0 / (H / (2.0 * focal)));
-  k_build_rays<<<nblocks(total, 256), 256, 0, s>>>(poses, n_poses, H, W, (float)(W * 0.5), (float)(H * 0.5), (float)focal,
-                                                   ndc ? 1 : 0, sx, sy, (float)near, (float)(2.0 * near), rays_o, rays_d,
-                                                   aabb ? aabb_keys : nullptr);
+  const PinholeConsts pc = pinhole_consts(H, W, focal, near);
+  k_build_rays<<<nblocks(total, 256), 256, 0, s>>>(poses, n_poses, H, W, pc.half_w, pc.half_h, pc.focal, ndc ? 1 : 0, pc.sx,
+                                                   pc.sy, pc.near, pc.two_near, rays_o, rays_d, aabb ? aabb_keys : nullptr);
   FSN_LAUNCH_CHECK("k_build_rays");
   if (aabb) {
     k_aabb_finish<<<1, 64, 0, s>>>(aabb_keys, 8.0f, aabb);  // aabb / 2 ** (4 - 1) (llff.py:84)

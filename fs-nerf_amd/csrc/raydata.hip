@@ -2,7 +2,8 @@
 // loaders of src/nerfdata/splitter.py:123-132).  The ray tables are pure functions of (pose, pixel), so a batch needs
 // nothing resident but the uint8 images and the poses: ONE launch, one thread per output ray,
 //   position in the epoch -> shuffled ray index (ray_perm.hpp) -> (view, row, column) -> ray (+ NDC) -> colour.
-// Rays: pinhole_ray / ndc_ray (ray_dev.hpp) with the arguments of k_build_rays: bit for bit row `index` of its tables.
+// Rays: pinhole_ray / ndc_ray (ray_dev.hpp) with the arguments of k_build_rays (pinhole_consts.hpp forms them for both):
+// bit for bit row `index` of its tables.
 // Colours: bit for bit the reference's float images, which fixes the arithmetic (the library is built with
 // -ffp-contract=off):
 //   byte v -> (float)v / 255.0f   (the reference divides in float64 and rounds to float32: the same float for all 256
@@ -10,10 +11,12 @@
 //   white background (blender.py:114-117): c * a + (1.0f - a), three separate float32 operations in that order.
 // A latency-bound gather of a few hundred KB: 12-byte rows rule out 16-byte vector stores; plain coalesced stores.
 // k_ray_patch_batch serves P x P patches the same way: position -> shuffled ANCHOR (the patch's top-left pixel) ->
-// the patch's pixels -> the rows k_ray_batch writes for them.
+// the patch's pixels.  Both kernels only find (flat ray index, view, row, column); the row itself - ray, NDC, stores,
+// colour - is written by the one write_ray_row, so a patch's rows are k_ray_batch's by construction.
 // fsn_ray_batch_k / fsn_ray_patch_batch_k serve the same batches over a camera table K = (fx, fy, cx, cy) on the device
 // (learnable intrinsics): the same two kernels, instantiated with kTable = true.
 #include "common.hpp"
+#include "pinhole_consts.hpp"
 #include "ray_dev.hpp"
 #include "ray_perm.hpp"
 
@@ -29,7 +32,7 @@ struct RayBatchArgs {
   const int64_t* indices;  // explicit order: [count]
   int64_t n_rays, per_view, start, count;
   int W, C, ndc, white_bkgd, order;
-  float half_w, half_h, focal, sx, sy, near, two_near;
+  PinholeConsts pc;
   RayPerm perm;
   float* rays_o;
   float* rays_d;
@@ -39,39 +42,48 @@ struct RayBatchArgs {
 
 // The camera table of the learnable intrinsics (fsn_ray_batch_k / fsn_ray_patch_batch_k): row v * stride of
 // K = (fx, fy, cx, cy) [k_rows, 4] is view v's, stride = 0 for one shared row.  kTable = false is the stored-intrinsics
-// kernel: it never looks at the table, and its code is what it was before the table existed.
+// kernel: it never looks at the table.
 struct CamTable {
   const float* K;
   int64_t stride;
 };
 
-template <bool kTable>
-__global__ void __launch_bounds__(256) k_ray_batch(RayBatchArgs a, CamTable cam) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= a.count) return;
-  int64_t idx;
+// Item b of the batch in the order asked for: a flat ray index (k_ray_batch) or an anchor (k_ray_patch_batch) of [0, n).
+// false: an explicit entry outside the range, which never reaches memory.
+__device__ __forceinline__ bool batch_item(const RayBatchArgs& a, int64_t b, int64_t n, int64_t& item) {
   if (a.order == FSN_RAY_ORDER_IDENTITY) {
-    idx = a.start + i;
+    item = a.start + b;
   } else if (a.order == FSN_RAY_ORDER_PERMUTED) {
-    idx = (int64_t)ray_perm_at(a.perm, (uint64_t)(a.start + i));
+    item = (int64_t)ray_perm_at(a.perm, (uint64_t)(a.start + b));
   } else {
-    idx = a.indices[i];
-    if (idx < 0 || idx >= a.n_rays) {  // never reaches memory
+    item = a.indices[b];
+    if (item < 0 || item >= n) {
 #ifdef FSN_DEBUG
-      fsn_dbg_note(g_dbg_raydata, __LINE__, idx, a.n_rays);
+      fsn_dbg_note(g_dbg_raydata, __LINE__, item, n);
 #endif
-      return;
+      return false;
     }
   }
+  return true;
+}
+
+// Output row i for the flat ray index idx: the index, the ray (+ NDC) and the colour, each if asked for.  `pixel` gives
+// idx's (view, row, column) and is called only when rays are wanted: k_ray_batch's 64-bit division lives in it, and a
+// colour-only batch never pays for it.
+template <bool kTable, class Pixel>
+__device__ __forceinline__ void write_ray_row(const RayBatchArgs& a, const CamTable& cam, int64_t i, int64_t idx,
+                                              Pixel pixel) {
   if (a.index) a.index[i] = idx;
   if (a.rays_o || a.rays_d) {
-    const int64_t view = idx / a.per_view, pix = idx - view * a.per_view;
+    int64_t view;
+    int row, col;
+    pixel(view, row, col);
     float o[3], d[3];
     if constexpr (kTable)
-      pinhole_ray_k(a.poses + 12 * view, cam.K + cam.stride * view, (int)(pix / a.W), (int)(pix % a.W), o, d);
+      pinhole_ray_k(a.poses + 12 * view, cam.K + cam.stride * view, row, col, o, d);
     else
-      pinhole_ray(a.poses + 12 * view, a.half_w, a.half_h, a.focal, (int)(pix / a.W), (int)(pix % a.W), o, d);
-    if (a.ndc) ndc_ray(o, d, a.sx, a.sy, a.near, a.two_near);
+      pinhole_ray(a.poses + 12 * view, a.pc.half_w, a.pc.half_h, a.pc.focal, row, col, o, d);
+    if (a.ndc) ndc_ray(o, d, a.pc.sx, a.pc.sy, a.pc.near, a.pc.two_near);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       if (a.rays_d) a.rays_d[3 * i + k] = d[k];
@@ -97,10 +109,23 @@ __global__ void __launch_bounds__(256) k_ray_batch(RayBatchArgs a, CamTable cam)
   }
 }
 
+template <bool kTable>
+__global__ void __launch_bounds__(256) k_ray_batch(RayBatchArgs a, CamTable cam) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.count) return;
+  int64_t idx;
+  if (!batch_item(a, i, a.n_rays, idx)) return;
+  write_ray_row<kTable>(a, cam, i, idx, [&](int64_t& view, int& row, int& col) {
+    view = idx / a.per_view;
+    const int64_t pix = idx - view * a.per_view;
+    row = (int)(pix / a.W);
+    col = (int)(pix % a.W);
+  });
+}
+
 // A batch of P x P patches (fsn_ray_patch_batch): one thread per output row (b P + i) P + j = pixel (i, j) of patch b.
 // `r` is fsn_ray_batch's argument block read over ANCHORS (the patches' top-left pixels): start / count count
-// patches, indices is the explicit anchor list, perm permutes [0, n_anchors); n_rays / per_view are not used.  The row
-// written for a flat ray index is k_ray_batch's, operation for operation (the same rays, the same colour arithmetic).
+// patches, indices is the explicit anchor list, perm permutes [0, n_anchors); n_rays / per_view are not used.
 struct RayPatchArgs {
   RayBatchArgs r;
   int64_t n_anchors, per_view_anchors;  // A, AH * AW
@@ -116,64 +141,27 @@ __global__ void __launch_bounds__(256) k_ray_patch_batch(RayPatchArgs pa, CamTab
   const int64_t b = i / pp;
   const int in_patch = (int)(i - b * pp), pi = in_patch / pa.P, pj = in_patch - pi * pa.P;
   int64_t anchor;
-  if (a.order == FSN_RAY_ORDER_IDENTITY) {
-    anchor = a.start + b;
-  } else if (a.order == FSN_RAY_ORDER_PERMUTED) {
-    anchor = (int64_t)ray_perm_at(a.perm, (uint64_t)(a.start + b));
-  } else {
-    anchor = a.indices[b];
-    if (anchor < 0 || anchor >= pa.n_anchors) {  // never reaches memory
-#ifdef FSN_DEBUG
-      fsn_dbg_note(g_dbg_raydata, __LINE__, anchor, pa.n_anchors);
-#endif
-      return;
-    }
-  }
-  const int64_t view = anchor / pa.per_view_anchors, rest = anchor - view * pa.per_view_anchors;
-  const int row = (int)(rest / pa.AW) + pi * pa.dilation, col = (int)(rest % pa.AW) + pj * pa.dilation;
-  const int64_t idx = (view * pa.H + row) * a.W + col;
-  if (a.index) a.index[i] = idx;
-  if (a.rays_o || a.rays_d) {
-    float o[3], d[3];
-    if constexpr (kTable)
-      pinhole_ray_k(a.poses + 12 * view, cam.K + cam.stride * view, row, col, o, d);
-    else
-      pinhole_ray(a.poses + 12 * view, a.half_w, a.half_h, a.focal, row, col, o, d);
-    if (a.ndc) ndc_ray(o, d, a.sx, a.sy, a.near, a.two_near);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      if (a.rays_d) a.rays_d[3 * i + k] = d[k];
-      if (a.rays_o) a.rays_o[3 * i + k] = o[k];
-    }
-  }
-  if (a.rgb) {
-    const uint8_t* px = a.images + idx * a.C;
-    float c[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) c[k] = (float)px[k] / 255.0f;
-    if (a.white_bkgd) {
-      const float al = (float)px[3] / 255.0f;
-      const float rest_w = 1.0f - al;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const float m = c[k] * al;
-        c[k] = m + rest_w;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) a.rgb[3 * i + k] = c[k];
-  }
+  if (!batch_item(a, b, pa.n_anchors, anchor)) return;
+  const int64_t v = anchor / pa.per_view_anchors, rest = anchor - v * pa.per_view_anchors;
+  const int r = (int)(rest / pa.AW) + pi * pa.dilation, c = (int)(rest % pa.AW) + pj * pa.dilation;
+  write_ray_row<kTable>(a, cam, i, (v * pa.H + r) * a.W + c, [&](int64_t& view, int& row, int& col) {
+    view = v;
+    row = r;
+    col = c;
+  });
 }
 
 }  // namespace fsn
 
 using namespace fsn;
 
-// The two batch entry points and their camera-table twins share one body each: `cam` null = the stored intrinsics.
-static int ray_batch_call(const char* who, const CamTable* cam, const float* poses, int64_t n_views,
-                          const uint8_t* images, int H, int W, int C, double focal, int ndc, double near, int white_bkgd,
-                          int order, uint64_t seed, int64_t epoch, const int64_t* indices, int64_t start, int64_t count,
-                          float* rays_o, float* rays_d, float* rgb, int64_t* index, fsn_stream_t stream) {
+// What the two batch calls share: the checks on (views, images, order, positions, pointers) and the argument block.
+// `lat` null: a batch of rays, its items the n_views * H * W flat ray indices.  Else a batch of patches, its items the
+// anchors of the lattice this forms from (P, dilation).  A call with nothing to do (count = 0) leaves out->count at 0.
+static int ray_batch_args(const char* who, const float* poses, int64_t n_views, const uint8_t* images, int H, int W, int C,
+                          double focal, int ndc, double near, int white_bkgd, int order, uint64_t seed, int64_t epoch,
+                          const int64_t* list, int64_t start, int64_t count, int P, int dilation, PatchLattice* lat,
+                          float* rays_o, float* rays_d, float* rgb, int64_t* index, RayBatchArgs* out) {
   FSN_REQUIRE(n_views >= 0 && H > 0 && W > 0 && focal > 0, FSN_E_INVALID,
               "%s: bad geometry n=%lld H=%d W=%d focal=%g", who, (long long)n_views, H, W, focal);
   FSN_REQUIRE(C == 3 || C == 4, FSN_E_INVALID, "%s: %d channels (the images are RGB or RGBA bytes: 3 or 4)", who, C);
@@ -181,24 +169,33 @@ static int ray_batch_call(const char* who, const CamTable* cam, const float* pos
               "%s: white_bkgd composes over the alpha channel and needs 4-channel images, got %d", who, C);
   FSN_REQUIRE(order == FSN_RAY_ORDER_IDENTITY || order == FSN_RAY_ORDER_PERMUTED || order == FSN_RAY_ORDER_EXPLICIT,
               FSN_E_INVALID, "%s: unknown order %d", who, order);
+  if (lat)
+    if (int rc = patch_lattice(who, H, W, P, dilation, lat)) return rc;
   FSN_REQUIRE(n_views <= ((int64_t)1 << 62) / ((int64_t)H * W), FSN_E_UNSUPPORTED, "%s: more than 2^62 rays", who);
   const int64_t per_view = (int64_t)H * W, n_rays = n_views * per_view;
+  const int64_t n_items = lat ? n_views * lat->AH * lat->AW : n_rays;
+  const char* item = lat ? "anchor" : "index";
   FSN_REQUIRE(start >= 0 && count >= 0 && epoch >= 0, FSN_E_INVALID, "%s: negative start, count or epoch", who);
   if (order == FSN_RAY_ORDER_EXPLICIT) {
-    FSN_REQUIRE(start == 0, FSN_E_INVALID, "%s: an explicit index list is served from its beginning (start = 0)", who);
+    FSN_REQUIRE(start == 0, FSN_E_INVALID, "%s: an explicit %s list is served from its beginning (start = 0)", who, item);
   } else {
-    FSN_REQUIRE(start <= n_rays && count <= n_rays - start, FSN_E_INVALID,
-                "%s: positions [%lld, +%lld) leave the %lld rays of the dataset (start + count > N)", who,
-                (long long)start, (long long)count, (long long)n_rays);
+    FSN_REQUIRE(start <= n_items && count <= n_items - start, FSN_E_INVALID,
+                "%s: positions [%lld, +%lld) leave the %lld %s of the dataset (start + count > %s)", who,
+                (long long)start, (long long)count, (long long)n_items, lat ? "anchors" : "rays", lat ? "A" : "N");
   }
-  FSN_REQUIRE(poses && images, FSN_E_INVALID, "%s: null poses or images", who);
+  if (lat) {  // (patches of rays alone need no image)
+    FSN_REQUIRE(poses, FSN_E_INVALID, "%s: null poses", who);
+    FSN_REQUIRE(images || !rgb, FSN_E_INVALID, "%s: null images with colours asked for (rgb)", who);
+  } else {
+    FSN_REQUIRE(poses && images, FSN_E_INVALID, "%s: null poses or images", who);
+  }
   if (count == 0) return FSN_OK;
-  FSN_REQUIRE(order != FSN_RAY_ORDER_EXPLICIT || indices, FSN_E_INVALID, "%s: null index list", who);
+  FSN_REQUIRE(order != FSN_RAY_ORDER_EXPLICIT || list, FSN_E_INVALID, "%s: null %s list", who, item);
   FSN_REQUIRE(rays_o || rays_d || rgb || index, FSN_E_INVALID, "%s: null pointer for every output", who);
-  RayBatchArgs a{};
+  RayBatchArgs& a = *out;
   a.poses = poses;
   a.images = images;
-  a.indices = indices;
+  a.indices = list;
   a.n_rays = n_rays;
   a.per_view = per_view;
   a.start = start;
@@ -208,19 +205,24 @@ static int ray_batch_call(const char* who, const CamTable* cam, const float* pos
   a.ndc = ndc ? 1 : 0;
   a.white_bkgd = white_bkgd ? 1 : 0;
   a.order = order;
-  // the same roundings as fsn_build_rays: W * 0.5 etc. formed in double, then float32
-  a.half_w = (float)(W * 0.5);
-  a.half_h = (float)(H * 0.5);
-  a.focal = (float)focal;
-  a.sx = (float)(-1.0 / (W / (2.0 * focal)));
-  a.sy = (float)(-1.0 / (H / (2.0 * focal)));
-  a.near = (float)near;
-  a.two_near = (float)(2.0 * near);
-  if (order == FSN_RAY_ORDER_PERMUTED) a.perm = ray_perm_make((uint64_t)n_rays, seed, (uint64_t)epoch);
+  a.pc = pinhole_consts(H, W, focal, near);
+  if (order == FSN_RAY_ORDER_PERMUTED) a.perm = ray_perm_make((uint64_t)n_items, seed, (uint64_t)epoch);
   a.rays_o = rays_o;
   a.rays_d = rays_d;
   a.rgb = rgb;
   a.index = index;
+  return FSN_OK;
+}
+
+// The two batch entry points and their camera-table twins share one body each: `cam` null = the stored intrinsics.
+static int ray_batch_call(const char* who, const CamTable* cam, const float* poses, int64_t n_views,
+                          const uint8_t* images, int H, int W, int C, double focal, int ndc, double near, int white_bkgd,
+                          int order, uint64_t seed, int64_t epoch, const int64_t* indices, int64_t start, int64_t count,
+                          float* rays_o, float* rays_d, float* rgb, int64_t* index, fsn_stream_t stream) {
+  RayBatchArgs a{};
+  const int rc = ray_batch_args(who, poses, n_views, images, H, W, C, focal, ndc, near, white_bkgd, order, seed, epoch,
+                                indices, start, count, 0, 0, nullptr, rays_o, rays_d, rgb, index, &a);
+  if (rc || a.count == 0) return rc;
   const unsigned grid = (unsigned)((count + 255) / 256);
   if (cam)
     k_ray_batch<true><<<grid, 256, 0, as_stream(stream)>>>(a, *cam);
@@ -235,70 +237,18 @@ static int ray_patch_batch_call(const char* who, const CamTable* cam, const floa
                                 int white_bkgd, int order, uint64_t seed, int64_t epoch, const int64_t* anchors,
                                 int64_t start, int64_t count, int P, int dilation, float* rays_o, float* rays_d, float* rgb,
                                 int64_t* index, fsn_stream_t stream) {
-  FSN_REQUIRE(n_views >= 0 && H > 0 && W > 0 && focal > 0, FSN_E_INVALID,
-              "%s: bad geometry n=%lld H=%d W=%d focal=%g", who, (long long)n_views, H, W, focal);
-  FSN_REQUIRE(C == 3 || C == 4, FSN_E_INVALID,
-              "%s: %d channels (the images are RGB or RGBA bytes: 3 or 4)", who, C);
-  FSN_REQUIRE(!white_bkgd || C == 4, FSN_E_INVALID,
-              "%s: white_bkgd composes over the alpha channel and needs 4-channel images, got %d", who, C);
-  FSN_REQUIRE(order == FSN_RAY_ORDER_IDENTITY || order == FSN_RAY_ORDER_PERMUTED || order == FSN_RAY_ORDER_EXPLICIT,
-              FSN_E_INVALID, "%s: unknown order %d", who, order);
-  FSN_REQUIRE(P >= 1 && dilation >= 1, FSN_E_INVALID, "%s: bad patch P=%d dilation=%d (both at least 1)", who,
-              P, dilation);
-  const int64_t ext = (int64_t)(P - 1) * dilation + 1;
-  FSN_REQUIRE(ext <= H && ext <= W, FSN_E_INVALID,
-              "%s: a patch of %d pixels at dilation %d spans %lld pixels and does not fit the %dx%d image", who,
-              P, dilation, (long long)ext, H, W);
-  FSN_REQUIRE(n_views <= ((int64_t)1 << 62) / ((int64_t)H * W), FSN_E_UNSUPPORTED,
-              "%s: more than 2^62 rays", who);
-  const int64_t AH = H - ext + 1, AW = W - ext + 1, n_anchors = n_views * AH * AW;
-  FSN_REQUIRE(start >= 0 && count >= 0 && epoch >= 0, FSN_E_INVALID,
-              "%s: negative start, count or epoch", who);
-  if (order == FSN_RAY_ORDER_EXPLICIT) {
-    FSN_REQUIRE(start == 0, FSN_E_INVALID,
-                "%s: an explicit anchor list is served from its beginning (start = 0)", who);
-  } else {
-    FSN_REQUIRE(start <= n_anchors && count <= n_anchors - start, FSN_E_INVALID,
-                "%s: positions [%lld, +%lld) leave the %lld anchors of the dataset (start + count > A)", who,
-                (long long)start, (long long)count, (long long)n_anchors);
-  }
-  FSN_REQUIRE(poses, FSN_E_INVALID, "%s: null poses", who);
-  FSN_REQUIRE(images || !rgb, FSN_E_INVALID, "%s: null images with colours asked for (rgb)", who);
-  if (count == 0) return FSN_OK;
-  FSN_REQUIRE(order != FSN_RAY_ORDER_EXPLICIT || anchors, FSN_E_INVALID, "%s: null anchor list", who);
-  FSN_REQUIRE(rays_o || rays_d || rgb || index, FSN_E_INVALID, "%s: null pointer for every output", who);
+  RayPatchArgs pa{};
+  PatchLattice lat{};
+  const int rc = ray_batch_args(who, poses, n_views, images, H, W, C, focal, ndc, near, white_bkgd, order, seed, epoch,
+                                anchors, start, count, P, dilation, &lat, rays_o, rays_d, rgb, index, &pa.r);
+  if (rc || pa.r.count == 0) return rc;
   const int64_t pp = (int64_t)P * P;
   FSN_REQUIRE(count <= ((int64_t)1 << 38) / pp, FSN_E_UNSUPPORTED, "%s: more than 2^38 rows in one call", who);
-  RayPatchArgs pa{};
-  RayBatchArgs& a = pa.r;
-  a.poses = poses;
-  a.images = images;
-  a.indices = anchors;
-  a.start = start;
-  a.count = count;
-  a.W = W;
-  a.C = C;
-  a.ndc = ndc ? 1 : 0;
-  a.white_bkgd = white_bkgd ? 1 : 0;
-  a.order = order;
-  // the same roundings as fsn_ray_batch
-  a.half_w = (float)(W * 0.5);
-  a.half_h = (float)(H * 0.5);
-  a.focal = (float)focal;
-  a.sx = (float)(-1.0 / (W / (2.0 * focal)));
-  a.sy = (float)(-1.0 / (H / (2.0 * focal)));
-  a.near = (float)near;
-  a.two_near = (float)(2.0 * near);
-  if (order == FSN_RAY_ORDER_PERMUTED) a.perm = ray_perm_make((uint64_t)n_anchors, seed, (uint64_t)epoch);
-  a.rays_o = rays_o;
-  a.rays_d = rays_d;
-  a.rgb = rgb;
-  a.index = index;
-  pa.n_anchors = n_anchors;
-  pa.per_view_anchors = AH * AW;
+  pa.n_anchors = n_views * lat.AH * lat.AW;
+  pa.per_view_anchors = lat.AH * lat.AW;
   pa.P = P;
   pa.dilation = dilation;
-  pa.AW = (int)AW;
+  pa.AW = (int)lat.AW;
   pa.H = H;
   const unsigned grid = (unsigned)((count * pp + 255) / 256);
   if (cam)

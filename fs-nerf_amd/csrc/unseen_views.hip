@@ -14,9 +14,11 @@
 // k_unseen_patch_batch: ONE launch, one thread per output row; every thread of a patch recomputes the patch's pose
 // (at most 6 + 32 mixes and about a hundred flops, against a second launch and a [count,12] round trip through
 // memory).  No LDS, no atomics, no index read from memory: nothing here to range-check, so no debug record.
+// The launch constants and the anchor lattice are those of fsn_ray_patch_batch (pinhole_consts.hpp).
 #include <cmath>
 
 #include "common.hpp"
+#include "pinhole_consts.hpp"
 #include "ray_dev.hpp"
 #include "ray_perm.hpp"
 
@@ -114,7 +116,7 @@ struct UnseenPatchArgs {
   uint64_t seed;
   int64_t first, count, per_pose;
   int P, dilation, AH, AW, ndc;
-  float half_w, half_h, focal, sx, sy, near, two_near;
+  PinholeConsts pc;
   float* rays_o;
   float* rays_d;
   float* poses_out;
@@ -141,8 +143,8 @@ __global__ void __launch_bounds__(256) k_unseen_patch_batch(UnseenPatchArgs a) {
   }
   if (a.rays_o || a.rays_d) {
     float o[3], d[3];
-    pinhole_ray(m, a.half_w, a.half_h, a.focal, row0 + pi * a.dilation, col0 + pj * a.dilation, o, d);
-    if (a.ndc) ndc_ray(o, d, a.sx, a.sy, a.near, a.two_near);
+    pinhole_ray(m, a.pc.half_w, a.pc.half_h, a.pc.focal, row0 + pi * a.dilation, col0 + pj * a.dilation, o, d);
+    if (a.ndc) ndc_ray(o, d, a.pc.sx, a.pc.sy, a.pc.near, a.pc.two_near);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       if (a.rays_d) a.rays_d[3 * i + k] = d[k];
@@ -194,12 +196,8 @@ extern "C" int fsn_unseen_patch_batch(const fsn_unseen_dist* dist_host, uint64_t
                                       fsn_stream_t stream) {
   if (int rc = unseen_check_dist("fsn_unseen_patch_batch", dist_host)) return rc;
   FSN_REQUIRE(H > 0 && W > 0 && focal > 0, FSN_E_INVALID, "fsn_unseen_patch_batch: bad geometry H=%d W=%d focal=%g", H, W, focal);
-  FSN_REQUIRE(P >= 1 && dilation >= 1, FSN_E_INVALID, "fsn_unseen_patch_batch: bad patch P=%d dilation=%d (both at least 1)",
-              P, dilation);
-  const int64_t ext = (int64_t)(P - 1) * dilation + 1;
-  FSN_REQUIRE(ext <= H && ext <= W, FSN_E_INVALID,
-              "fsn_unseen_patch_batch: a patch of %d pixels at dilation %d spans %lld pixels and does not fit the %dx%d image",
-              P, dilation, (long long)ext, H, W);
+  PatchLattice lat;
+  if (int rc = patch_lattice("fsn_unseen_patch_batch", H, W, P, dilation, &lat)) return rc;
   FSN_REQUIRE(patches_per_pose >= 1, FSN_E_INVALID, "fsn_unseen_patch_batch: patches_per_pose %lld (at least 1)",
               (long long)patches_per_pose);
   FSN_REQUIRE(first_patch >= 0 && count >= 0 && first_patch <= ((int64_t)1 << 62), FSN_E_INVALID,
@@ -217,17 +215,10 @@ extern "C" int fsn_unseen_patch_batch(const fsn_unseen_dist* dist_host, uint64_t
   a.per_pose = patches_per_pose;
   a.P = P;
   a.dilation = dilation;
-  a.AH = (int)(H - ext + 1);
-  a.AW = (int)(W - ext + 1);
+  a.AH = (int)lat.AH;
+  a.AW = (int)lat.AW;
   a.ndc = ndc ? 1 : 0;
-  // the same roundings as fsn_ray_patch_batch
-  a.half_w = (float)(W * 0.5);
-  a.half_h = (float)(H * 0.5);
-  a.focal = (float)focal;
-  a.sx = (float)(-1.0 / (W / (2.0 * focal)));
-  a.sy = (float)(-1.0 / (H / (2.0 * focal)));
-  a.near = (float)near;
-  a.two_near = (float)(2.0 * near);
+  a.pc = pinhole_consts(H, W, focal, near);  // (fsn_ray_patch_batch's: the same rays for the same pose and pixel)
   a.rays_o = rays_o;
   a.rays_d = rays_d;
   a.poses_out = poses_out;

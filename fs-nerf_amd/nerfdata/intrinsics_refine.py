@@ -5,7 +5,7 @@ the parameter phi (zeros at the start) over the dataset's hwf = (H, W, f0):
     fx = f0 exp(phi_0),  fy = f0 exp(phi_1) (tie_focal: fy = fx),  cx = W/2 + W phi_2,  cy = H/2 + H phi_3
 so that phi = 0 is the stored intrinsics value for value and one learning rate serves all four columns.  RayLoader /
 PatchLoader(intrinsics=refiner), alone or with cameras=, serve their one-launch batches over K() and hand rays_o /
-rays_d out of one autograd node (pose_refine._CameraRays) whose backward is fsn_ray_camera_grad + fsn_intrinsics_grad
+rays_d out of one autograd node (raydata._CameraRays) whose backward is fsn_ray_camera_grad + fsn_intrinsics_grad
 into phi.grad (and xi.grad).  The NDC map keeps the constants of the stored focal: a fixed warp of space."""
 from __future__ import annotations
 
@@ -16,7 +16,7 @@ from torch import Tensor, nn
 
 from .. import ops
 from ..utils import utilities as U
-from .raydata import _NDC_NEAR, RayDataset
+from .raydata import _NDC_NEAR, ParamCache, RayDataset
 
 
 class IntrinsicsRefiner(nn.Module):
@@ -49,21 +49,15 @@ class IntrinsicsRefiner(nn.Module):
         self.per_view, self.tie_focal = bool(per_view), bool(tie_focal)
         self.learn_focal, self.learn_principal_point = bool(learn_focal), bool(learn_principal_point)
         self.phi = nn.Parameter(torch.zeros(self.n_views if self.per_view else 1, 4, device=device, dtype=torch.float32))
-        self._table: Optional[Tensor] = None
-        self._table_key = None
+        self._table = ParamCache()
 
     @property
     def device(self) -> torch.device:
         return self.phi.device
 
     def K(self) -> Tensor:
-        phi = self.phi
-        key = (phi._version, phi.data_ptr())  # (an optimizer step or load_state_dict writes in place; .to() replaces)
-        if self._table is None or key != self._table_key:
-            H, W, f0 = self.hwf0
-            self._table = ops.intrinsics_compose(phi, H, W, f0, self.tie_focal)
-            self._table_key = key
-        return self._table
+        H, W, f0 = self.hwf0
+        return self._table.get(self.phi, lambda: ops.intrinsics_compose(self.phi, H, W, f0, self.tie_focal))
 
     def grad_phi(self, grad_K_views: Tensor) -> Tensor:
         """dL/dphi from ops.ray_camera_grad's per-view dL/dK: one launch, then the learn_* flags."""

@@ -9,13 +9,13 @@ refined poses against the truth up to the joint problem's gauge (a similarity tr
 from __future__ import annotations
 
 import math
-from typing import Callable, Optional, Tuple
+from typing import Tuple
 
 import torch
 from torch import Tensor, nn
 
 from .. import ops
-from .raydata import RayDataset
+from .raydata import ParamCache, RayDataset
 
 
 class CameraRefiner(nn.Module):
@@ -44,76 +44,19 @@ class CameraRefiner(nn.Module):
         self.learn_rotation, self.learn_translation = bool(learn_rotation), bool(learn_translation)
         self.register_buffer("poses0", p0)
         self.xi = nn.Parameter(torch.zeros(p0.shape[0], 6, device=p0.device, dtype=torch.float32))
-        self._composed: Optional[Tensor] = None
-        self._composed_key = None
+        self._composed = ParamCache()
 
     @property
     def n_views(self) -> int:
         return self.poses0.shape[0]
 
     def poses12(self) -> Tensor:
-        xi = self.xi
-        key = (xi._version, xi.data_ptr())  # (an optimizer step or load_state_dict writes in place; .to() replaces)
-        if self._composed is None or key != self._composed_key:
-            self._composed = ops.pose_compose(self.poses0, xi)
-            self._composed_key = key
-        return self._composed
+        return self._composed.get(self.xi, lambda: ops.pose_compose(self.poses0, self.xi))
 
     def poses(self) -> Tensor:
         m = self.poses12().view(-1, 3, 4)
         last = torch.tensor([0.0, 0.0, 0.0, 1.0], device=m.device).expand(m.shape[0], 1, 4)
         return torch.cat([m, last], dim=1)
-
-    def served(self, geometry: Tuple[int, int, float, bool, float], launch: Callable[[Tensor], tuple]):
-        """A loader's batch over the corrected poses: `launch(poses12)` is its one ray_batch / ray_patch_batch call
-        (with the index) -> (rays_o, rays_d, rgb, index), rays_o / rays_d attached to xi."""
-        return served_rays(self.poses0, self, None, geometry, lambda poses12, _K: launch(poses12))
-
-
-def served_rays(poses0: Tensor, cameras: Optional[CameraRefiner], intrinsics, geometry, launch):
-    """A loader's batch over learnable cameras: `cameras` (a CameraRefiner) and / or `intrinsics` (an
-    IntrinsicsRefiner), `poses0` the stored [n,12] poses, geometry = (H, W, focal, ndc, near) of the dataset;
-    `launch(poses12, K)` is the loader's one ray_batch / ray_patch_batch call (with the index) over the matrices and the
-    camera table it is handed (None: the stored ones) -> (rays_o, rays_d, rgb, index), rays_o / rays_d attached to xi
-    and phi through ONE autograd node."""
-    return _CameraRays.apply(None if cameras is None else cameras.xi, None if intrinsics is None else intrinsics.phi,
-                             poses0, cameras, intrinsics, geometry, launch)
-
-
-class _CameraRays(torch.autograd.Function):
-    """forward: the loader's launch over cameras.poses12() and intrinsics.K(); backward, with poses alone: ONE
-    fsn_ray_pose_grad launch -> dL/dxi; with intrinsics: ONE fsn_ray_camera_grad launch -> dL/dxi and the per-view
-    dL/dK, then fsn_intrinsics_grad -> dL/dphi.  No host synchronisation on either side."""
-
-    @staticmethod
-    def forward(ctx, xi: Optional[Tensor], phi: Optional[Tensor], poses0: Tensor, cameras, intrinsics, geometry, launch):
-        K = None if intrinsics is None else intrinsics.K()
-        o, d, rgb, index = launch(None if cameras is None else cameras.poses12(), K)
-        ctx.save_for_backward(index, *[t for t in (xi, phi) if t is not None])
-        ctx.poses0, ctx.K = poses0, K  # (K: the table of THIS batch - a later step makes a new one)
-        ctx.cameras, ctx.intrinsics, ctx.geometry = cameras, intrinsics, geometry
-        ctx.mark_non_differentiable(*[t for t in (rgb, index) if t is not None])
-        ctx.set_materialize_grads(False)
-        return o, d, rgb, index
-
-    @staticmethod
-    def backward(ctx, grad_o, grad_d, _grad_rgb, _grad_index):
-        index, *params = ctx.saved_tensors
-        cam, intr = ctx.cameras, ctx.intrinsics
-        xi = params[0] if cam is not None else None
-        H, W, focal, ndc, near = ctx.geometry
-        if intr is None:
-            g = ops.ray_pose_grad(cam.poses0, xi, H, W, focal, index, grad_o, grad_d, ndc=ndc, near=near)
-            g_phi = None
-        else:
-            g, g_K = ops.ray_camera_grad(ctx.poses0, xi, H, W, focal, ctx.K, index, grad_o, grad_d, ndc=ndc, near=near)
-            g_phi = intr.grad_phi(g_K)
-        if cam is not None:
-            if not cam.learn_rotation:
-                g[:, :3].zero_()
-            if not cam.learn_translation:
-                g[:, 3:].zero_()
-        return g, g_phi, None, None, None, None, None
 
 
 def _poses44(p, name: str) -> Tensor:

@@ -143,6 +143,67 @@ def _seed_or_default(seed: Optional[int]) -> int:
     return int(torch.initial_seed() if seed is None else seed) & 0xFFFFFFFFFFFFFFFF
 
 
+class ParamCache:
+    """What one launch forms from a parameter (CameraRefiner's corrected poses, IntrinsicsRefiner's camera table), formed
+    again only when the parameter changed: an optimizer step or load_state_dict writes in place (a new _version), .to()
+    replaces the tensor (a new data_ptr)."""
+
+    def __init__(self):
+        self._value, self._key = None, None
+
+    def get(self, param: Tensor, compute) -> Tensor:
+        key = (param._version, param.data_ptr())
+        if self._value is None or key != self._key:
+            self._value, self._key = compute(), key
+        return self._value
+
+
+def served_rays(poses0: Tensor, cameras, intrinsics, geometry, launch):
+    """A loader's batch over learnable cameras: `cameras` (a CameraRefiner) and / or `intrinsics` (an
+    IntrinsicsRefiner), `poses0` the stored [n,12] poses, geometry = (H, W, focal, ndc, near) of the dataset;
+    `launch(poses12, K)` is the loader's one ray_batch / ray_patch_batch call (with the index) over the matrices and the
+    camera table it is handed (None: the stored ones) -> (rays_o, rays_d, rgb, index), rays_o / rays_d attached to xi
+    and phi through ONE autograd node."""
+    return _CameraRays.apply(None if cameras is None else cameras.xi, None if intrinsics is None else intrinsics.phi,
+                             poses0, cameras, intrinsics, geometry, launch)
+
+
+class _CameraRays(torch.autograd.Function):
+    """forward: the loader's launch over cameras.poses12() and intrinsics.K(); backward, with poses alone: ONE
+    fsn_ray_pose_grad launch -> dL/dxi; with intrinsics: ONE fsn_ray_camera_grad launch -> dL/dxi and the per-view
+    dL/dK, then fsn_intrinsics_grad -> dL/dphi.  No host synchronisation on either side."""
+
+    @staticmethod
+    def forward(ctx, xi: Optional[Tensor], phi: Optional[Tensor], poses0: Tensor, cameras, intrinsics, geometry, launch):
+        K = None if intrinsics is None else intrinsics.K()
+        o, d, rgb, index = launch(None if cameras is None else cameras.poses12(), K)
+        ctx.save_for_backward(index, *[t for t in (xi, phi) if t is not None])
+        ctx.poses0, ctx.K = poses0, K  # (K: the table of THIS batch - a later step makes a new one)
+        ctx.cameras, ctx.intrinsics, ctx.geometry = cameras, intrinsics, geometry
+        ctx.mark_non_differentiable(*[t for t in (rgb, index) if t is not None])
+        ctx.set_materialize_grads(False)
+        return o, d, rgb, index
+
+    @staticmethod
+    def backward(ctx, grad_o, grad_d, _grad_rgb, _grad_index):
+        index, *params = ctx.saved_tensors
+        cam, intr = ctx.cameras, ctx.intrinsics
+        xi = params[0] if cam is not None else None
+        H, W, focal, ndc, near = ctx.geometry
+        if intr is None:
+            g = ops.ray_pose_grad(cam.poses0, xi, H, W, focal, index, grad_o, grad_d, ndc=ndc, near=near)
+            g_phi = None
+        else:
+            g, g_K = ops.ray_camera_grad(ctx.poses0, xi, H, W, focal, ctx.K, index, grad_o, grad_d, ndc=ndc, near=near)
+            g_phi = intr.grad_phi(g_K)
+        if cam is not None:
+            if not cam.learn_rotation:
+                g[:, :3].zero_()
+            if not cam.learn_translation:
+                g[:, 3:].zero_()
+        return g, g_phi, None, None, None, None, None
+
+
 class RayLoader:
     """The train loader (splitter.py:123-126: DataLoader(train_set, batch_size, shuffle=True)): every next() is ONE
     launch returning device tensors (rays_o [B,3], rays_d [B,3], rgb [B,3]) (+ index [B] with `with_index`), no host
@@ -190,18 +251,19 @@ class RayLoader:
         """What an epoch serves once each (PatchLoader: anchors instead of rays)."""
         return len(self.dataset)
 
-    def _serve(self, order: str, start: int, count: int, epoch: int):
-        """The one launch of a next(): `count` items from position `start` of this epoch's order."""
-        if self.cameras is not None or self.intrinsics is not None:
-            return self._serve_refined(lambda poses12, K: self.dataset.batch(
-                order, start=start, count=count, seed=self.seed, epoch=epoch, want_index=True, poses12=poses12, K=K))
-        return self.dataset.batch(order, start=start, count=count, seed=self.seed, epoch=epoch, want_index=self.with_index)
+    def _batch(self, order: str, **kw):
+        """The dataset call of this loader (PatchLoader: patch_batch)."""
+        return self.dataset.batch(order, **kw)
 
-    def _serve_refined(self, launch):
-        from .pose_refine import served_rays  # (pose_refine imports this module)
+    def _serve(self, order: str, start: int, count: int, epoch: int):
+        """The one launch of a next(): `count` items from position `start` of this epoch's order, over the stored
+        cameras or, through the one autograd node, over the learnable ones (which always needs the index)."""
+        kw = dict(start=start, count=count, seed=self.seed, epoch=epoch)
+        if self.cameras is None and self.intrinsics is None:
+            return self._batch(order, want_index=self.with_index, **kw)
         ds = self.dataset
         return served_rays(ds.poses12, self.cameras, self.intrinsics, (ds.hwf[0], ds.hwf[1], ds.hwf[2], ds.ndc, _NDC_NEAR),
-                           launch)
+                           lambda poses12, K: self._batch(order, want_index=True, poses12=poses12, K=K, **kw))
 
     def __len__(self) -> int:
         n, stride = self._n_items(), self.batch_size * self.world
@@ -262,13 +324,8 @@ class PatchLoader(RayLoader):
     def _n_items(self) -> int:
         return self._anchors
 
-    def _serve(self, order: str, start: int, count: int, epoch: int):
-        if self.cameras is not None or self.intrinsics is not None:
-            return self._serve_refined(lambda poses12, K: self.dataset.patch_batch(
-                order, self.patch, self.dilation, start=start, count=count, seed=self.seed, epoch=epoch, want_index=True,
-                poses12=poses12, K=K))
-        return self.dataset.patch_batch(order, self.patch, self.dilation, start=start, count=count, seed=self.seed,
-                                        epoch=epoch, want_index=self.with_index)
+    def _batch(self, order: str, **kw):
+        return self.dataset.patch_batch(order, self.patch, self.dilation, **kw)
 
 
 class FrameLoader:

@@ -275,6 +275,23 @@ def build_rays(poses: Tensor, H: int, W: int, focal: float, device, ndc: bool = 
 _RAY_ORDERS = {"identity": L.FSN_RAY_ORDER_IDENTITY, "permuted": L.FSN_RAY_ORDER_PERMUTED, "explicit": L.FSN_RAY_ORDER_EXPLICIT}
 
 
+def _row_outputs(rows: int, dev, want_rays: bool, want_rgb: bool, want_index: bool):
+    """The (rays_o, rays_d, rgb, index) outputs of a batch of `rows` rows; None where not asked for."""
+    o = torch.empty(rows, 3, device=dev, dtype=torch.float32) if want_rays else None
+    d = torch.empty(rows, 3, device=dev, dtype=torch.float32) if want_rays else None
+    rgb = torch.empty(rows, 3, device=dev, dtype=torch.float32) if want_rgb else None
+    index = torch.empty(rows, device=dev, dtype=torch.int64) if want_index else None
+    return o, d, rgb, index
+
+
+def _launch_cam(name: str, who: str, dev, head: tuple, K: Optional[Tensor], n_views: int, tail: tuple) -> None:
+    """`name` over the stored intrinsics, or its camera-table form `name`_k with (K, its rows) between head and tail."""
+    if K is None:
+        _launch(name, dev, *head, *tail)
+    else:
+        _launch(name + "_k", dev, *head, *_camera_table(K, n_views, who), *tail)
+
+
 def ray_batch(poses12: Tensor, images: Tensor, H: int, W: int, focal: float, *, ndc: bool = False, near: float = 1.0,
               white_bkgd: bool = False, order: str = "identity", seed: int = 0, epoch: int = 0,
               indices: Optional[Tensor] = None, start: int = 0, count: Optional[int] = None, want_rays: bool = True,
@@ -296,17 +313,11 @@ def ray_batch(poses12: Tensor, images: Tensor, H: int, W: int, focal: float, *, 
     elif count is None:
         raise ValueError("ray_batch: count is needed for the identity and permuted orders")
     dev = images.device
-    o = torch.empty(count, 3, device=dev, dtype=torch.float32) if want_rays else None
-    d = torch.empty(count, 3, device=dev, dtype=torch.float32) if want_rays else None
-    rgb = torch.empty(count, 3, device=dev, dtype=torch.float32) if want_rgb else None
-    index = torch.empty(count, device=dev, dtype=torch.int64) if want_index else None
+    o, d, rgb, index = _row_outputs(count, dev, want_rays, want_rgb, want_index)
     head = (poses12, poses12.shape[0], images, int(H), int(W), images.shape[3], float(focal))
     tail = (1 if ndc else 0, float(near), 1 if white_bkgd else 0, _RAY_ORDERS[order], int(seed) & 0xFFFFFFFFFFFFFFFF,
             int(epoch), indices, int(start), int(count), o, d, rgb, index)
-    if K is None:
-        _launch("fsn_ray_batch", dev, *head, *tail)
-    else:
-        _launch("fsn_ray_batch_k", dev, *head, *_camera_table(K, poses12.shape[0], "ray_batch"), *tail)
+    _launch_cam("fsn_ray_batch", "ray_batch", dev, head, K, poses12.shape[0], tail)
     return o, d, rgb, index
 
 
@@ -338,18 +349,12 @@ def ray_patch_batch(poses12: Tensor, images: Optional[Tensor], H: int, W: int, f
         count = anchors.numel()
     elif count is None:
         raise ValueError("ray_patch_batch: count is needed for the identity and permuted orders")
-    dev, rows = poses12.device, count * int(patch) * int(patch)
-    o = torch.empty(rows, 3, device=dev, dtype=torch.float32) if want_rays else None
-    d = torch.empty(rows, 3, device=dev, dtype=torch.float32) if want_rays else None
-    rgb = torch.empty(rows, 3, device=dev, dtype=torch.float32) if want_rgb else None
-    index = torch.empty(rows, device=dev, dtype=torch.int64) if want_index else None
+    dev = poses12.device
+    o, d, rgb, index = _row_outputs(count * int(patch) * int(patch), dev, want_rays, want_rgb, want_index)
     head = (poses12, poses12.shape[0], images, int(H), int(W), channels, float(focal))
     tail = (1 if ndc else 0, float(near), 1 if white_bkgd else 0, _RAY_ORDERS[order], int(seed) & 0xFFFFFFFFFFFFFFFF,
             int(epoch), anchors, int(start), int(count), int(patch), int(dilation), o, d, rgb, index)
-    if K is None:
-        _launch("fsn_ray_patch_batch", dev, *head, *tail)
-    else:
-        _launch("fsn_ray_patch_batch_k", dev, *head, *_camera_table(K, poses12.shape[0], "ray_patch_batch"), *tail)
+    _launch_cam("fsn_ray_patch_batch", "ray_patch_batch", dev, head, K, poses12.shape[0], tail)
     return o, d, rgb, index
 
 
@@ -410,6 +415,14 @@ def _pose_pair(poses0: Tensor, xi: Tensor, who: str) -> None:
         raise ValueError(f"{who}: poses and xi are contiguous tensors of one device")
 
 
+def _ray_grads(index: Tensor, grad_o: Optional[Tensor], grad_d: Optional[Tensor]):
+    """A batch's flat ray indices and ray gradients as the gradient kernels read them -> (index [count] int64, grad_o,
+    grad_d [3 count] float32 or None, count)."""
+    index = _i64(index, "index").reshape(-1)
+    count = index.numel()
+    return index, _flat(grad_o, "grad_o", 3 * count), _flat(grad_d, "grad_d", 3 * count), count
+
+
 def pose_compose(poses0: Tensor, xi: Tensor) -> Tensor:
     """The corrected poses [n,12] = [exp([omega]x) R0 | t0 + tau] of the stored poses0 [n,12] and xi = (omega, tau)
     [n,6] in ONE launch (fsn_pose_compose)."""
@@ -428,10 +441,8 @@ def ray_pose_grad(poses0: Tensor, xi: Tensor, H: int, W: int, focal: float, inde
     want_pose_grad: -> (grad_xi, dL/d(corrected poses) [n,12])."""
     _pose_pair(poses0, xi, "ray_pose_grad")
     xi = xi.detach()
-    index = _i64(index, "index").reshape(-1)
-    count, dev = index.numel(), poses0.device
-    grad_o = _flat(grad_o, "grad_o", 3 * count)
-    grad_d = _flat(grad_d, "grad_d", 3 * count)
+    index, grad_o, grad_d, count = _ray_grads(index, grad_o, grad_d)
+    dev = poses0.device
     grad_xi = torch.empty_like(xi)
     grad_poses = torch.empty_like(poses0) if want_pose_grad else None
     _launch("fsn_ray_pose_grad", dev, poses0, xi, poses0.shape[0], int(H), int(W), float(focal), 1 if ndc else 0, float(near),
@@ -488,10 +499,7 @@ def ray_camera_grad(poses0: Tensor, xi: Optional[Tensor], H: int, W: int, focal0
         xi = xi.detach()
     n, dev = poses0.shape[0], poses0.device
     K, k_rows = _camera_table(K, n, "ray_camera_grad")
-    index = _i64(index, "index").reshape(-1)
-    count = index.numel()
-    grad_o = _flat(grad_o, "grad_o", 3 * count)
-    grad_d = _flat(grad_d, "grad_d", 3 * count)
+    index, grad_o, grad_d, count = _ray_grads(index, grad_o, grad_d)
     want_xi_grad = xi is not None if want_xi_grad is None else want_xi_grad
     grad_xi = torch.empty(n, 6, device=dev, dtype=torch.float32) if want_xi_grad else None
     grad_K = torch.empty(n, 4, device=dev, dtype=torch.float32)

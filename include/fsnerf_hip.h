@@ -98,7 +98,8 @@ int fsn_device_cus(void);
  * Rows [row0, row0+nrows) of the H x W image are produced (row0=0,nrows=H for a frame; a
  * rank renders its own row block).  rays_o, rays_d: [nrows*W, 3].  focal / near are doubles
  * because the reference forms W*0.5, 2*near and 1/(W/(2 focal)) in Python double precision
- * before rounding to float32 (utilities.py:67, 104-114). */
+ * before rounding to float32 (utilities.py:67, 104-114).  Every entry point below that takes (H, W, focal, near) forms
+ * these constants through the one pinhole_consts() of csrc/pinhole_consts.hpp. */
 int fsn_get_rays(const float* pose_host, int H, int W, double focal, int row0, int nrows,
                  float* rays_o, float* rays_d, fsn_stream_t stream);
 
@@ -148,7 +149,7 @@ int fsn_ray_batch(const float* poses, int64_t n_views, const uint8_t* images, in
  * [0, A), `anchors` is the explicit DEVICE int64 [count] list (an anchor outside [0, A) leaves its P*P rows untouched
  * and is recorded in the debug build).  Outputs (each may be NULL): rays_o, rays_d, rgb [count*P*P, 3] and index
  * [count*P*P] int64, row (b*P + i)*P + j for pixel (i, j) of patch b - bit for bit the row the ray batch above serves
- * for that flat index in explicit order.  images may be NULL when rgb is NULL: ray-only patches for any poses.
+ * for that flat index in explicit order (one device function writes the rows of both).  images may be NULL when rgb is NULL: ray-only patches for any poses.
  * Errors (FSN_E_INVALID): P < 1, dilation < 1, ext > H or ext > W, start + count > A, and those of the ray batch. */
 int fsn_ray_patch_batch(const float* poses, int64_t n_views, const uint8_t* images, int H, int W, int C, double focal,
                         int ndc, double near, int white_bkgd, int order, uint64_t seed, int64_t epoch,
@@ -204,7 +205,8 @@ int fsn_ray_patch_batch_k(const float* poses, int64_t n_views, const uint8_t* im
                           int64_t epoch, const int64_t* anchors, int64_t start, int64_t count, int P, int dilation,
                           float* rays_o, float* rays_d, float* rgb, int64_t* index, fsn_stream_t stream);
 /* The backward of "flat ray index -> ray of the corrected pose under the camera table", reduced per view in ONE launch:
- * fsn_ray_pose_grad's walk (one workgroup per view, no atomics, a fixed summation order) with four more sums.
+ * fsn_ray_pose_grad's walk (the other instantiation of its kernel template: one workgroup per view, no atomics, a fixed
+ * summation order) with four more sums.
  * xi [n_views, 6] may be NULL = no correction (the rays were served over poses0).  Outputs, WRITTEN for every view and
  * exactly 0 for a view without a ray in the batch: grad_xi [n_views, 6] (may be NULL) - with the stored intrinsics in K
  * bit for bit fsn_ray_pose_grad's; grad_K_views [n_views, 4] = this view's rays' share of dL/d(fx, fy, cx, cy).

@@ -1,6 +1,6 @@
 """Worker of tests/test_intrinsics_gpu.py: fsn_ray_camera_grad through the DEBUG library (FSN_LIB_PATH ->
-libfsnerf_hip_dbg.so: k_ray_camera_grad notes an index outside the dataset in the record of pose_refine.hip and skips it
-before any other access) - first a valid list, then the same list with two entries outside [0, N) appended - and prints
+libfsnerf_hip_dbg.so: its kernel, k_ray_view_grad<true>, notes an index outside the dataset in the record of
+pose_refine.hip and skips it before any other access) - first a valid list, then the same list with two entries outside [0, N) appended - and prints
 the records as JSON."""
 import torch
 

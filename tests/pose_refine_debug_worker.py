@@ -1,6 +1,6 @@
 """Worker of tests/test_pose_refine_gpu.py: fsn_ray_pose_grad through the DEBUG library (FSN_LIB_PATH ->
-libfsnerf_hip_dbg.so: k_ray_pose_grad records an index outside the dataset) - first a valid list, then the same list
-with two entries outside [0, N) appended - and prints the records as JSON."""
+libfsnerf_hip_dbg.so: its kernel, k_ray_view_grad<false>, records an index outside the dataset) - first a valid list,
+then the same list with two entries outside [0, N) appended - and prints the records as JSON."""
 import torch
 
 import debug_lib as D
