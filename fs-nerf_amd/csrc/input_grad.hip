@@ -1,9 +1,10 @@
 // input_grad.hip — gradients of the training step with respect to the network's INPUTS: sample positions and
 // directions (point form) or rays_o / rays_d (ray form).  DESIGN.md 6, "Input gradient".
 //
-//   k_pack_input_grad : the encoding columns of the weights that read an encoding - W_0[:, :d_pe], W_l[:, D:D+d_pe] of the
-//                       skip-fed layers, W_branch[:, D:D+d_de] - transposed, split into 16-bit parts the way k_pack_bwd
-//                       splits the chain's stream, as lane-linear MFMA A fragments ("units" of 1 KiB per part).
+//   weight slices     : the encoding columns of the weights that read an encoding - W_0[:, :d_pe], W_l[:, D:D+d_pe] of the
+//                       skip-fed layers, W_branch[:, D:D+d_de] - transposed, as lane-linear MFMA A fragments: the
+//                       kStreamInputGrad weight stream of mlp_layout.hpp (stream_table_input_grad), packed by the one
+//                       device packer (mlp.hip, pack_stream_device).  The jobs below are that table's GEMMs.
 //   k_input_grad      : per 128-sample tile, g_enc^T [encoding slots x samples] = sum over those layers of
 //                       W_enc^T [slots x D] . dPre_l [D x samples] / (grad_scale bs[l]) on v_mfma_f32_16x16x32, the
 //                       gradient tiles read from the packed T-layout the dgrad chain stored them in (train_fused.hip),
@@ -23,6 +24,7 @@
 // from the sample position with sincos_f32 in every mode (arguments reach 512 x 1.5 rad).
 #include "mlp_dev.hpp"
 #include "mlp_layout.hpp"
+#include "mlp_pack.hpp"
 #include "ray_dev.hpp"
 #include "train_internal.hpp"
 
@@ -33,46 +35,7 @@ constexpr int kIgLdsBytes = 144 * 1024;      // weight slices: all of them resid
 constexpr int kIgPosTiles = 4 * kKsPos / 2;  // 16-row output tiles of a position job (64 slots) ...
 constexpr int kIgDirTiles = 4 * kKsDir / 2;  // ... and of the direction job (32 slots)
 static_assert(kIgPosTiles == 4 && kIgDirTiles == 2, "slot q = 4 t + reg of lane group g");
-
-// ------------------------------------------------------------------ weight slices as A operands
-struct IgPackArgs {
-  const float* W[kIgMaxJobs];
-  int32_t ld[kIgMaxJobs], col0[kIgMaxJobs], is_dir[kIgMaxJobs], unit0[kIgMaxJobs + 1];
-  int32_t n_jobs, prec, n_freqs_pos, n_freqs_dir;
-};
-
-// Unit (job, k-step ks, output tile t), in that order: A[row r = 4 gs + reg][k = 8 gk + j] = W[32 ks + 8 gk + j][col0 + f],
-// f = feature of slot q = 4 t + reg of lane group gs (zero for an unused slot).  One thread = 16 bytes of one part.
-__global__ void k_pack_input_grad(IgPackArgs a, char* __restrict__ blob, int64_t n_pieces) {
-  const int64_t piece = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (piece >= n_pieces) return;
-  const int ub = unit_bytes(a.prec), ppu = ub / 16;
-  const int unit = (int)(piece / ppu);
-  const int rem = (int)(piece - (int64_t)unit * ppu);
-  const int part = rem >> 6, lane = rem & 63;
-  int gi = 0;
-  while (gi + 1 < a.n_jobs && a.unit0[gi + 1] <= unit) ++gi;
-  const int lu = unit - a.unit0[gi];
-  const bool dir = a.is_dir[gi] != 0;
-  const int mt = dir ? kIgDirTiles : kIgPosTiles;
-  const int ks = lu / mt, t = lu - ks * mt;
-  const int r = lane & 15, gk = lane >> 4;
-  const int f = enc_slot_feature(4 * t + (r & 3), r >> 2, dir ? a.n_freqs_dir : a.n_freqs_pos, dir ? 8 * kKsDir : 8 * kKsPos);
-  const bool f16 = prec_is_f16(a.prec);
-  uint16_t o8[8];
-  for (int j = 0; j < 8; ++j) {
-    const int o = 32 * ks + 8 * gk + j;
-    const float w = f < 0 ? 0.f : a.W[gi][(int64_t)o * a.ld[gi] + a.col0[gi] + f];
-    const uint16_t hi = half_rne(w, f16);
-    o8[j] = part == 0 ? hi : half_rne((w - half_to_f32(hi, f16)) * lo_scale(a.prec), f16);
-  }
-  uint4 v;
-  v.x = o8[0] | ((uint32_t)o8[1] << 16);
-  v.y = o8[2] | ((uint32_t)o8[3] << 16);
-  v.z = o8[4] | ((uint32_t)o8[5] << 16);
-  v.w = o8[6] | ((uint32_t)o8[7] << 16);
-  *reinterpret_cast<uint4*>(blob + piece * 16) = v;
-}
+static_assert(kIgMaxJobs <= kMaxLayers + 2, "the slices' table (StreamTable) holds every job");
 
 // ------------------------------------------------------------------ the kernel
 struct InputGradArgs {
@@ -266,35 +229,23 @@ int input_grad_launch(const fsn_mlp_desc& d, int prec, const float* const* W, in
                       hipStream_t s) {
   if (!rq.d_x && !rq.d_dirs) return FSN_OK;
   const int L = d.n_layers, D = d.d_hidden, NT = D / 32;
-  const int d_pe = 3 * (1 + 2 * d.n_freqs_pos), d_de = 3 * (1 + 2 * d.n_freqs_dir);
-  IgPackArgs p{};
+  // the jobs are the GEMMs of the slices' table (mlp_layout.hpp): position jobs, then the direction job
+  StreamTable tab;
+  stream_table_input_grad(d, prec, rq.d_x != nullptr, rq.d_dirs != nullptr, tab);
   InputGradArgs a{};
-  int nj = 0, u = 0;
-  auto add = [&](const float* Wl, int ld, int col0, int stage, int64_t src, bool dir) {
-    p.W[nj] = Wl; p.ld[nj] = ld; p.col0[nj] = col0; p.is_dir[nj] = dir ? 1 : 0; p.unit0[nj] = u;
-    a.src[nj] = src; a.stage[nj] = stage; a.unit0[nj] = u;
-    u += dir ? (NT / 2) * kIgDirTiles : NT * kIgPosTiles;
-    ++nj;
-  };
-  if (rq.d_x) {
-    add(W[0], d_pe, 0, 0, o.dp, false);
-    for (int l = 1; l < L; ++l)
-      if ((d.skip_mask >> (l - 1)) & 1u) add(W[l], D + d_pe, D, l, o.dp + l * o.h_stride, false);
-    a.n_pos = nj;
+  a.has_dir = rq.d_dirs ? 1 : 0;
+  a.n_pos = tab.n_gemm - a.has_dir;
+  for (int j = 0; j < tab.n_gemm; ++j) {
+    const int w = tab.g[j].w;  // a hidden layer's index is its stage; the branch (L + 2) is stage L + 1 and reads dBo
+    a.stage[j] = j < a.n_pos ? w : L + 1;
+    a.src[j] = j < a.n_pos ? o.dp + w * o.h_stride : o.dbo;
+    a.unit0[j] = tab.g[j].unit0;
   }
-  if (rq.d_dirs) {
-    add(W[L + 2], D + d_de, D, L + 1, o.dbo, true);
-    a.has_dir = 1;
-  }
-  p.unit0[nj] = a.unit0[nj] = u;
-  p.n_jobs = nj; p.prec = prec; p.n_freqs_pos = d.n_freqs_pos; p.n_freqs_dir = d.n_freqs_dir;
-  const int64_t bytes = (int64_t)u * unit_bytes(prec);
-  FSN_REQUIRE(bytes <= o.blob_floats * 4, FSN_E_HIP, "internal: input-gradient weight slices exceed the backward blob");
+  a.unit0[tab.n_gemm] = tab.units_total;
+  const int64_t bytes = stream_bytes(tab);
   FSN_REQUIRE((int64_t)NT * kIgPosTiles * unit_bytes(prec) <= kIgLdsBytes, FSN_E_HIP, "internal: input-gradient LDS budget");
   char* blob = reinterpret_cast<char*>(ws + o.blob);
-  const int64_t n_pieces = bytes / 16;
-  k_pack_input_grad<<<(unsigned)((n_pieces + 255) / 256), 256, 0, s>>>(p, blob, n_pieces);
-  FSN_LAUNCH_CHECK("k_pack_input_grad");
+  if (int rc = pack_stream_device(tab, W, blob, s)) return rc;
   a.ws = reinterpret_cast<const uint32_t*>(ws);
   a.blob = blob;
   a.resident = bytes <= kIgLdsBytes ? 1 : 0;

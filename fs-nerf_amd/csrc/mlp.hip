@@ -12,17 +12,39 @@
 
 namespace fsn {
 
-__global__ void k_pack_stream(PackArgs a, char* __restrict__ blob, int64_t n_pieces) {
+// The device packer of all three weight streams (mlp_layout.hpp, StreamTable): one thread = one 16-byte piece.  KIND =
+// a.T.kind as a constant: an instantiation carries its own element map only.
+struct StreamPackArgs {
+  StreamTable T;
+  const float* W[kMaxLayers + 2];  // per GEMM of the table (gemm_weights)
+};
+
+template <int KIND>
+__global__ void k_pack_stream(StreamPackArgs a, char* __restrict__ dst, int64_t n_pieces) {
   const int64_t piece = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (piece >= n_pieces) return;
   uint16_t o[8];
-  pack_piece(a, piece, o);
+  pack_piece(a.T, KIND, a.W, piece, o);
   uint4 v;
   v.x = o[0] | ((uint32_t)o[1] << 16);
   v.y = o[2] | ((uint32_t)o[3] << 16);
   v.z = o[4] | ((uint32_t)o[5] << 16);
   v.w = o[6] | ((uint32_t)o[7] << 16);
-  *reinterpret_cast<uint4*>(blob + a.G.stream_off + piece * 16) = v;
+  *reinterpret_cast<uint4*>(dst + piece * 16) = v;
+}
+
+int pack_stream_device(const StreamTable& T, const float* const* W_sd, void* dst, hipStream_t s) {
+  StreamPackArgs a{};
+  a.T = T;
+  gemm_weights(T, W_sd, a.W);
+  const int64_t n_pieces = stream_bytes(T) / 16;
+  const unsigned grid = (unsigned)((n_pieces + 255) / 256);
+  char* out = static_cast<char*>(dst);
+  if (T.kind == kStreamFwd) k_pack_stream<kStreamFwd><<<grid, 256, 0, s>>>(a, out, n_pieces);
+  else if (T.kind == kStreamBwd) k_pack_stream<kStreamBwd><<<grid, 256, 0, s>>>(a, out, n_pieces);
+  else k_pack_stream<kStreamInputGrad><<<grid, 256, 0, s>>>(a, out, n_pieces);
+  FSN_LAUNCH_CHECK("k_pack_stream");
+  return FSN_OK;
 }
 
 __global__ void k_pack_aux(PackArgs a, char* __restrict__ blob) {
@@ -232,9 +254,10 @@ extern "C" int fsn_mlp_pack_scaled(const fsn_mlp_desc* desc, int prec, const flo
   PackArgs a;
   const int rc = fill_pack_args(desc, prec, weights, biases, a, layer_exps);
   if (rc != FSN_OK) return rc;
-  const int64_t n_pieces = (int64_t)a.G.nph_full * kPhaseBytes / 16;
-  k_pack_stream<<<(unsigned)((n_pieces + 255) / 256), 256, 0, as_stream(stream)>>>(a, static_cast<char*>(blob), n_pieces);
-  FSN_LAUNCH_CHECK("k_pack_stream");
+  StreamTable T;
+  stream_table_fwd(a.G, prec, a.sc_act, a.sc_enc, T);
+  const int rcs = pack_stream_device(T, a.W, static_cast<char*>(blob) + a.G.stream_off, as_stream(stream));
+  if (rcs != FSN_OK) return rcs;
   const int naux = a.G.aux_floats > 64 ? a.G.aux_floats : 64;
   k_pack_aux<<<(unsigned)((naux + 255) / 256), 256, 0, as_stream(stream)>>>(a, static_cast<char*>(blob));
   FSN_LAUNCH_CHECK("k_pack_aux");
@@ -256,6 +279,35 @@ extern "C" int fsn_mlp_pack_scaled_host(const fsn_mlp_desc* desc, int prec, cons
   const char* why;
   const int rc = pack_blob_host(desc, prec, weights, biases, blob_host, &why, layer_exps);
   FSN_REQUIRE(rc == FSN_OK, rc, "fsn_mlp_pack_scaled_host: %s", why);
+  return FSN_OK;
+}
+
+extern "C" int64_t fsn_weight_stream_bytes(const fsn_mlp_desc* desc, int prec, int kind, int want_x, int want_dirs) {
+  StreamTable T;
+  const char* why;
+  const int rc = train_stream_table(desc, prec, kind, want_x, want_dirs, T, &why);
+  FSN_REQUIRE(rc == FSN_OK, rc, "fsn_weight_stream_bytes: %s", why);
+  return stream_bytes(T);
+}
+
+extern "C" int fsn_weight_stream_pack(const fsn_mlp_desc* desc, int prec, int kind, int want_x, int want_dirs,
+                                      const float* const* weights, void* dst, fsn_stream_t stream) {
+  StreamTable T;
+  const char* why;
+  int rc = train_stream_table(desc, prec, kind, want_x, want_dirs, T, &why);
+  if (rc == FSN_OK) rc = stream_weights_ok(T, weights, dst, &why);
+  FSN_REQUIRE(rc == FSN_OK, rc, "fsn_weight_stream_pack: %s", why);
+  return pack_stream_device(T, weights, dst, as_stream(stream));
+}
+
+extern "C" int fsn_weight_stream_pack_host(const fsn_mlp_desc* desc, int prec, int kind, int want_x, int want_dirs,
+                                           const float* const* weights, void* dst_host) {
+  StreamTable T;
+  const char* why;
+  int rc = train_stream_table(desc, prec, kind, want_x, want_dirs, T, &why);
+  if (rc == FSN_OK) rc = stream_weights_ok(T, weights, dst_host, &why);
+  FSN_REQUIRE(rc == FSN_OK, rc, "fsn_weight_stream_pack_host: %s", why);
+  pack_stream_host(T, weights, dst_host);
   return FSN_OK;
 }
 

@@ -53,6 +53,7 @@ constexpr float kLoScaleF16 = 2048.0f;
 // layer's scale.
 FSN_HD constexpr bool prec_lo_scaled(int prec) { return prec == FSN_PREC_FP16X3 || prec == FSN_PREC_FP16X2; }
 FSN_HD float lo_scale(int prec) { return prec_lo_scaled(prec) ? kLoScaleF16 : 1.0f; }
+FSN_HD constexpr int enc_width(int n_freqs) { return 3 * (1 + 2 * n_freqs); }  // features of a PositionalEncoder
 FSN_HD int unit_bytes(int prec) { return prec_is_x3(prec) ? 2048 : 1024; }
 FSN_HD int units_per_phase(int prec) { return kPhaseBytes / unit_bytes(prec); }
 
@@ -105,18 +106,6 @@ FSN_HD int enc_slot_feature(int q, int g, int n_freqs, int slots) {
   if (g == 2 && q >= slots - 2) return q - (slots - 2);  // x, y
   if (g == 3 && q == slots - 2) return 2;                // z
   return -1;
-}
-
-// Source column of weight fragment element (k-step ks, lane group g, element j) for a layer;
-// -1 = zero padding.  Activation k-steps use the accumulator-as-operand order: element j of lane
-// group g is register j&3 of output tile 2ks + (j>>2) of the previous layer, i.e.
-//   feature = 32 ks + 16 (j>>2) + 4 g + (j&3).
-FSN_HD int unit_src_col(const LayerGeom& L, int ks, int g, int j) {
-  if (ks < L.ks_act) return 32 * ks + 16 * (j >> 2) + 4 * g + (j & 3);
-  const int e = ks - L.ks_act;
-  const int slots = 8 * L.ks_enc;
-  const int f = enc_slot_feature(8 * e + j, g, L.n_freqs, slots);
-  return f < 0 ? -1 : L.d_act + f;
 }
 
 FSN_HD uint16_t bf16_rne(float f) {
@@ -179,7 +168,7 @@ inline int build_geom(const fsn_mlp_desc& d, int prec, NetGeom& G, const char** 
   if (d.n_freqs_dir < 0 || d.n_freqs_dir > 4) { *why = "n_freqs (direction) must be <= 4"; return FSN_E_UNSUPPORTED; }
   if (d.skip_mask >> (d.n_layers - 1)) { *why = "skip index >= n_layers-1 (the reference model cannot run it either)"; return FSN_E_INVALID; }
   const int D = d.d_hidden, NT = D / 32, L = d.n_layers;
-  const int d_pe = 3 * (1 + 2 * d.n_freqs_pos), d_de = 3 * (1 + 2 * d.n_freqs_dir);
+  const int d_pe = enc_width(d.n_freqs_pos), d_de = enc_width(d.n_freqs_dir);
   int u = 0;
   for (int l = 0; l < L; ++l) {
     LayerGeom& g = G.g[l];
@@ -217,6 +206,92 @@ inline int build_geom(const fsn_mlp_desc& d, int prec, NetGeom& G, const char** 
   G.stream_off = (G.aux_off + (int64_t)G.aux_floats * 4 + 4095) / 4096 * 4096;
   G.total_bytes = G.stream_off + (int64_t)G.nph_full * kPhaseBytes;
   return FSN_OK;
+}
+
+// ------------------------------------------------------------------ weight streams
+// Three streams feed the MFMA kernels in ONE format - a run of units (1 KiB of 16-bit high parts, in the x3 modes 1 KiB
+// of low parts behind them, lane-linear: lane l owns bytes [16 l, 16 l + 16) of a part) - and differ only in which
+// weight element a fragment element is.  A StreamTable says, GEMM by GEMM, where the units come from; pack_piece
+// (mlp_pack.hpp) is the one function that turns (table, weights, piece) into 16 bytes, on the host and on the device.
+//   kStreamFwd        the forward blob's stream: A[row][k] = W[row][source column of k] x the layer's power of two
+//   kStreamBwd        the dgrad chain's stream (train_fused.hip): the same GEMMs transposed, A[row i][k = o] = W[o][i]
+//   kStreamInputGrad  the encoding columns of the layers that read an encoding (input_grad.hip), transposed, rows in
+//                     the encoder's slot order
+// The forward and backward streams are consumed through WStream in 16-KiB phases and padded with zeros to a whole
+// phase; the slices are copied to LDS as they are and end with their last unit.
+enum StreamKind : int32_t { kStreamFwd = 0, kStreamBwd = FSN_WSTREAM_BWD, kStreamInputGrad = FSN_WSTREAM_INPUT_GRAD };
+
+struct StreamGemm {
+  int32_t w;        // source weight: index in state_dict order (layers.0 .., sigma, connection, branch, rgb)
+  int32_t ld;       // its row stride (= in_features)
+  int32_t col0;     // first column read: 0 (backward), the first encoding column (forward, input gradient)
+  int32_t nt_out;   // output tiles: 32-row pairs of two units each (forward, backward), 16-row tiles (input gradient)
+  int32_t ks;       // k-steps (of 32)
+  int32_t unit0;    // first unit in the stream
+  int32_t ks_act;   // forward: the first ks_act k-steps read activations, the others the encoding
+  int32_t n_freqs;  // forward, input gradient: of the encoding read
+  float sc_act, sc_enc;  // forward: power-of-two factors on the activation / encoding columns (fsn_mlp_pack_scaled)
+};
+
+struct StreamTable {
+  int32_t kind, prec, n_gemm, units_total;
+  StreamGemm g[kMaxLayers + 2];
+};
+
+FSN_HD int stream_phases(const StreamTable& T) { return (T.units_total + units_per_phase(T.prec) - 1) / units_per_phase(T.prec); }
+FSN_HD int64_t stream_bytes(const StreamTable& T) {
+  return T.kind == kStreamInputGrad ? (int64_t)T.units_total * unit_bytes(T.prec) : (int64_t)stream_phases(T) * kPhaseBytes;
+}
+
+inline void stream_begin(StreamTable& T, int kind, int prec) { T = StreamTable{}; T.kind = kind; T.prec = prec; }
+inline void stream_add(StreamTable& T, StreamGemm g) {
+  g.unit0 = T.units_total;
+  T.units_total += (T.kind == kStreamInputGrad ? 1 : 2) * g.nt_out * g.ks;
+  T.g[T.n_gemm++] = g;
+}
+
+// weight index (state_dict order) of GEMM g (kernel order: hidden 0..L-1, connection, branch)
+FSN_HD int gemm_to_sd(int g, int L) { return g < L ? g : g + 1; }  // skips "sigma" at index L
+
+// Forward: the GEMMs of `G` in kernel order.  sc_act / sc_enc: per-GEMM factors, or null = 1.
+inline void stream_table_fwd(const NetGeom& G, int prec, const float* sc_act, const float* sc_enc, StreamTable& T) {
+  stream_begin(T, kStreamFwd, prec);
+  const int L = G.n_gemm - 2;
+  for (int g = 0; g < G.n_gemm; ++g) {
+    const LayerGeom& l = G.g[g];
+    stream_add(T, StreamGemm{gemm_to_sd(g, L), l.ld, l.d_act, l.nt_out, l.ks_act + l.ks_enc, 0, l.ks_act, l.n_freqs,
+                             sc_act ? sc_act[g] : 1.0f, sc_enc ? sc_enc[g] : 1.0f});
+  }
+}
+
+// Backward: branch^T restricted to the first D input columns (D/2 outputs = NT/2 k-steps), connection^T, then layers
+// L-1 down to 1, each restricted to its D activation columns.  This IS the order k_train_bwd (train_fused.hip) consumes:
+// its gemm_layer calls are d feat, d h_{L-1}, then dPre_{l-1} for l = L-1 .. 1.  NT^2 (2 L + 1) units.
+inline void stream_table_bwd(const fsn_mlp_desc& d, int prec, StreamTable& T) {
+  stream_begin(T, kStreamBwd, prec);
+  const int L = d.n_layers, D = d.d_hidden, NT = D / 32;
+  stream_add(T, StreamGemm{L + 2, D + enc_width(d.n_freqs_dir), 0, NT, NT / 2, 0, 0, 0, 1.0f, 1.0f});
+  stream_add(T, StreamGemm{L + 1, D, 0, NT, NT, 0, 0, 0, 1.0f, 1.0f});
+  for (int l = L - 1; l >= 1; --l) {
+    const bool wide = (d.skip_mask >> (l - 1)) & 1u;
+    stream_add(T, StreamGemm{l, D + (wide ? enc_width(d.n_freqs_pos) : 0), 0, NT, NT, 0, 0, 0, 1.0f, 1.0f});
+  }
+}
+
+// Input-gradient slices: the position jobs - layer 0 and every skip-fed layer, in layer order - when d_x is wanted, then
+// the direction job (the branch) when d_dirs is.  A lane group owns 8 slots per k-step of the encoding, a 16-row output
+// tile takes 4 of them from each group (slot q = 4 t + reg of lane group gs is row 4 gs + reg of tile t): 2 kKsPos = 4
+// tiles for a position job, 2 kKsDir = 2 for the direction job.  The contraction runs over the layer's outputs; the
+// units are ordered (job, k-step, tile).  At most NT (4 L + 1) units: never more than the backward stream.
+inline void stream_table_input_grad(const fsn_mlp_desc& d, int prec, bool want_x, bool want_dirs, StreamTable& T) {
+  stream_begin(T, kStreamInputGrad, prec);
+  const int L = d.n_layers, D = d.d_hidden, NT = D / 32, d_pe = enc_width(d.n_freqs_pos);
+  if (want_x) {
+    stream_add(T, StreamGemm{0, d_pe, 0, 2 * kKsPos, NT, 0, 0, d.n_freqs_pos, 1.0f, 1.0f});
+    for (int l = 1; l < L; ++l)
+      if ((d.skip_mask >> (l - 1)) & 1u) stream_add(T, StreamGemm{l, D + d_pe, D, 2 * kKsPos, NT, 0, 0, d.n_freqs_pos, 1.0f, 1.0f});
+  }
+  if (want_dirs) stream_add(T, StreamGemm{L + 2, D + enc_width(d.n_freqs_dir), D, 2 * kKsDir, NT / 2, 0, 0, d.n_freqs_dir, 1.0f, 1.0f});
 }
 
 }  // namespace fsn

@@ -1,6 +1,6 @@
-// mlp_pack.hpp — the weight packer's index code (reference state_dict -> packed blob, mlp_layout.hpp), shared by the
-// device packer kernels (mlp.hip), the host packer fsn_mlp_pack_host and the sanitizer build of the host side
-// (csrc/host_pack.cpp: plain C++, no HIP).
+// mlp_pack.hpp — the weight packer's index code (reference state_dict -> packed blob and the training backward's two
+// streams, mlp_layout.hpp), shared by the device packer kernels (mlp.hip), the host packers fsn_mlp_pack_host /
+// fsn_weight_stream_pack_host and the sanitizer builds of the host side (csrc/host_pack.cpp: plain C++, no HIP).
 #pragma once
 #include "mlp_layout.hpp"
 
@@ -42,37 +42,80 @@ inline void fill_scales(PackArgs& a, const int32_t* exps) {
   a.sc_rgb = pow2f(-a.exps[L + 1]);
 }
 
-// weight index (state_dict order) of GEMM g (kernel order: hidden 0..L-1, connection, branch)
-FSN_HD int gemm_to_sd(int g, int L) { return g < L ? g : g + 1; }  // skips "sigma" at index L
-
-// One 16-byte piece = 8 bf16 of (unit, part hi/lo, lane).  Shared by host and device packers.
-FSN_HD void pack_piece(const PackArgs& a, int64_t piece, uint16_t out8[8]) {
-  const int ub = unit_bytes(a.prec);
-  const int ppu = ub / 16;  // pieces per unit
+// One 16-byte piece = the 8 halfwords of (unit, part hi/lo, lane) of a weight stream (mlp_layout.hpp, StreamTable): the
+// ONLY copy of the piece decode, the unit search, the per-kind element map and the high / low split, for all three
+// streams, on the host and on the device.  W[i]: the source weight of the table's GEMM i (gemm_weights below; resolved
+// on the host, so that a thread follows one pointer, not two).  kind: T.kind, handed over apart so that the device
+// kernel's three instantiations see a constant and carry their own element map only.
+// Element j of lane (r = lane & 15, grp = lane >> 4) is A[row r of the unit][k = 8 grp + j of the k-step]:
+//   forward         W[32 t + 16 sub + r][source column of k] x the GEMM's factor.  Activation k-steps use the
+//                   accumulator-as-operand order - element j of lane group grp is register j&3 of output tile
+//                   2 ks + (j>>2) of the previous layer, column 32 ks + 16 (j>>2) + 4 grp + (j&3); encoding k-steps read
+//                   the column of the lane group's slot (enc_slot_feature), zero where the slot is unused
+//   backward        W[32 ks + 16 (j>>2) + 4 grp + (j&3)][32 t + 16 sub + r]: row = an input feature, k = an output in
+//                   that same accumulator-as-operand order (the chain's B operands are accumulators too)
+//   input gradient  W[32 ks + 8 grp + j][col0 + f], f = the feature of slot 4 t + (r&3) of lane group r>>2 (zero for an
+//                   unused slot): k in linear order, the gradient tiles come from the packed T-layout
+FSN_HD void pack_piece(const StreamTable& T, int kind, const float* const* W, int64_t piece, uint16_t out8[8]) {
+  const int ppu = unit_bytes(T.prec) / 16;  // pieces per unit
   const int unit = (int)(piece / ppu);
   const int rem = (int)(piece - (int64_t)unit * ppu);
   const int part = rem >> 6, lane = rem & 63;
   for (int j = 0; j < 8; ++j) out8[j] = 0;
-  if (unit >= a.G.units_total) return;  // tail padding of the last phase
-  int g = 0;
-  while (g + 1 < a.G.n_gemm && a.G.g[g + 1].unit0 <= unit) ++g;
-  const LayerGeom& Lg = a.G.g[g];
-  const int ks_tot = Lg.ks_act + Lg.ks_enc;
-  const int lu = unit - Lg.unit0;          // ((pair * ks_tot) + ks) * 2 + half
-  const int sub = lu & 1;
-  const int t = (lu >> 1) / ks_tot, ks = (lu >> 1) - t * ks_tot;
+  if (unit >= T.units_total) return;  // tail padding of the last phase
+  int gi = 0;
+  while (gi + 1 < T.n_gemm && T.g[gi + 1].unit0 <= unit) ++gi;
+  const StreamGemm& g = T.g[gi];
+  const int lu = unit - g.unit0;  // forward, backward: ((pair * ks) + k-step) * 2 + half; input gradient: k-step * tiles + tile
+  const bool slices = kind == kStreamInputGrad;
+  const int sub = slices ? 0 : lu & 1, lp = slices ? lu : lu >> 1;
+  const int t = slices ? lp % g.nt_out : lp / g.ks, ks = slices ? lp / g.nt_out : lp - t * g.ks;
   const int r = lane & 15, grp = lane >> 4;
-  const float* W = a.W[gemm_to_sd(g, a.n_layers)];
   const int row = 32 * t + 16 * sub + r;
+  const int slot_f = slices ? enc_slot_feature(4 * t + (r & 3), r >> 2, g.n_freqs, 4 * g.nt_out) : 0;
+  const float* Wg = W[gi];
+  const bool f16 = prec_is_f16(T.prec);
   for (int j = 0; j < 8; ++j) {
-    const int col = unit_src_col(Lg, ks, grp, j);
-    if (col < 0) continue;
-    const float w = W[(int64_t)row * Lg.ld + col] * (ks < Lg.ks_act ? a.sc_act[g] : a.sc_enc[g]);  // (exact: powers of two)
-    const bool f16 = prec_is_f16(a.prec);
+    const int acc_k = 32 * ks + 16 * (j >> 2) + 4 * grp + (j & 3);
+    int64_t at = -1;
+    float sc = 1.0f;
+    if (kind == kStreamBwd) {
+      at = (int64_t)acc_k * g.ld + g.col0 + row;
+    } else if (slices) {
+      if (slot_f >= 0) at = (int64_t)(32 * ks + 8 * grp + j) * g.ld + g.col0 + slot_f;
+    } else if (ks < g.ks_act) {
+      at = (int64_t)row * g.ld + acc_k;
+      sc = g.sc_act;
+    } else {
+      const int f = enc_slot_feature(8 * (ks - g.ks_act) + j, grp, g.n_freqs, 8 * (g.ks - g.ks_act));
+      if (f >= 0) at = (int64_t)row * g.ld + g.col0 + f;
+      sc = g.sc_enc;
+    }
+    if (at < 0) continue;
+    const float w = Wg[at] * sc;  // (exact: powers of two)
     const uint16_t hi = half_rne(w, f16);
-    out8[j] = part == 0 ? hi : half_rne((w - half_to_f32(hi, f16)) * lo_scale(a.prec), f16);
+    out8[j] = part == 0 ? hi : half_rne((w - half_to_f32(hi, f16)) * lo_scale(T.prec), f16);
   }
 }
+
+// The GEMMs' source weights out of the list in state_dict order (layers.0 .., sigma, connection, branch, rgb).
+inline void gemm_weights(const StreamTable& T, const float* const* W_sd, const float* Wg[kMaxLayers + 2]) {
+  for (int i = 0; i < kMaxLayers + 2; ++i) Wg[i] = i < T.n_gemm ? W_sd[T.g[i].w] : nullptr;
+}
+
+// A whole stream on the host: stream_bytes(T) bytes at `dst`.
+inline void pack_stream_host(const StreamTable& T, const float* const* W_sd, void* dst) {
+  const float* Wg[kMaxLayers + 2];
+  gemm_weights(T, W_sd, Wg);
+  const int64_t n_pieces = stream_bytes(T) / 16;
+  uint16_t* sp = static_cast<uint16_t*>(dst);
+  for (int64_t p = 0; p < n_pieces; ++p) pack_piece(T, T.kind, Wg, p, sp + p * 8);
+}
+
+#if defined(__HIPCC__)
+// mlp.hip: the same on the device (k_pack_stream, one launch).  W_sd: host array of device pointers, state_dict order.
+int pack_stream_device(const StreamTable& T, const float* const* W_sd, void* dst, hipStream_t s);
+#endif
 
 // aux float `i` of the blob
 FSN_HD float aux_value(const PackArgs& a, int i) {
@@ -141,9 +184,39 @@ inline int pack_blob_host(const fsn_mlp_desc* d, int prec, const float* const* W
   for (int i = 0; i < 64; ++i) reinterpret_cast<uint32_t*>(blob)[i] = hw[i];
   float* aux = reinterpret_cast<float*>(blob + a.G.aux_off);
   for (int i = 0; i < a.G.aux_floats; ++i) aux[i] = aux_value(a, i);
-  const int64_t n_pieces = (int64_t)a.G.nph_full * kPhaseBytes / 16;
-  uint16_t* sp = reinterpret_cast<uint16_t*>(blob + a.G.stream_off);
-  for (int64_t p = 0; p < n_pieces; ++p) pack_piece(a, p, sp + p * 8);
+  StreamTable T;
+  stream_table_fwd(a.G, a.prec, a.sc_act, a.sc_enc, T);
+  pack_stream_host(T, a.W, blob + a.G.stream_off);
+  return FSN_OK;
+}
+
+// Table of one of the training backward's streams as the entry points take it (fsn_weight_stream_*: kind, flags);
+// returns 0 or an FSN_E_* code and a message.
+inline int train_stream_table(const fsn_mlp_desc* d, int prec, int kind, int want_x, int want_dirs, StreamTable& T,
+                              const char** why) {
+  *why = "";
+  if (!d) { *why = "null desc"; return FSN_E_INVALID; }
+  if (!prec_in(PrecTraining{}, prec)) { *why = "not a training precision mode"; return FSN_E_UNSUPPORTED; }
+  NetGeom G;
+  const int rc = build_geom(*d, prec, G, why);
+  if (rc != FSN_OK) return rc;
+  if (kind == kStreamBwd) {
+    stream_table_bwd(*d, prec, T);
+  } else if (kind == kStreamInputGrad) {
+    if (!want_x && !want_dirs) { *why = "input-gradient slices of neither d_x nor d_dirs"; return FSN_E_INVALID; }
+    stream_table_input_grad(*d, prec, want_x != 0, want_dirs != 0, T);
+  } else {
+    *why = "unknown stream kind";
+    return FSN_E_INVALID;
+  }
+  return FSN_OK;
+}
+
+// ... and the check of the weight list against it: every weight the stream reads is there.
+inline int stream_weights_ok(const StreamTable& T, const float* const* W, const void* dst, const char** why) {
+  if (!W || !dst) { *why = "null pointer"; return FSN_E_INVALID; }
+  for (int i = 0; i < T.n_gemm; ++i)
+    if (!W[T.g[i].w]) { *why = "null weight pointer"; return FSN_E_INVALID; }
   return FSN_OK;
 }
 

@@ -4,7 +4,9 @@
 //                   encodings, post-activation hidden layers, connection output and branch output go to HBM.
 //   k_train_bwd   : the dgrad chain in the same register-resident form.  d(out) -> rgb/sigma heads (VALU) ->
 //                   branch^T -> connection^T -> layers L-1..1 transposed, each an MFMA GEMM whose A operands are
-//                   the TRANSPOSED weights streamed through LDS exactly like the forward's; the ReLU mask comes
+//                   the TRANSPOSED weights streamed through LDS exactly like the forward's (the kStreamBwd weight
+//                   stream of mlp_layout.hpp: stream_table_bwd lists its GEMMs in the order of the gemm_layer calls
+//                   here, the one device packer of mlp.hip writes it); the ReLU mask comes
 //                   from the saved activations; every pre-activation gradient dPre_l is stored for the wgrad.
 //   k_wgrad       : dW_l = dPre_l . H_{l-1}^T, a GEMM whose contraction runs over ALL samples (K = millions,
 //                   output 256x256): split-K over sample tiles, v_mfma_f32_32x32x16, one 256x256 (or smaller)
@@ -34,10 +36,12 @@
 // reference: src/core/models.py:111-143 (forward), src/run-nerf.py:243-285 (loss.backward()).
 // k_train_fwd and k_train_bwd are fsn::VariantTrain (mlp_dev.hpp): compiler-scheduled k-loop with the x3 modes' pinned
 // one-unit-ahead prefetch, and bf16x3 on a main and a correction accumulator - NOT the inference kernels' one.
+#include <cassert>
 #include <type_traits>
 
 #include "mlp_dev.hpp"
 #include "mlp_layout.hpp"
+#include "mlp_pack.hpp"
 #include "train_internal.hpp"
 
 namespace fsn {
@@ -58,7 +62,7 @@ struct FusedLayout {
   int64_t blob_f, blob_b;
   int64_t pe, de, h, h_stride, bo, dhead, dbo, dp, part, hpart, total;  // float offsets
   int64_t mask, mask_stride;  // ReLU sign bits: [L hidden layers + branch][tile][4 lane groups][128 samples] x 2 words
-  int nsplit[4], nsplit_heads, n_bwd_units, nph_bwd;
+  int nsplit[4], nsplit_heads, nph_bwd;
   int64_t blob_f_bytes;
 };
 
@@ -90,21 +94,25 @@ static int make_fused_layout(const fsn_mlp_desc& d, int prec, int64_t n, FusedLa
   const int rc = build_geom(d, prec, G, why);
   if (rc != FSN_OK) return rc;
   F.L = d.n_layers; F.D = d.d_hidden; F.NT = F.D / 32; F.prec = prec;
-  F.d_pe = 3 * (1 + 2 * d.n_freqs_pos); F.d_de = 3 * (1 + 2 * d.n_freqs_dir);
+  F.d_pe = enc_width(d.n_freqs_pos); F.d_de = enc_width(d.n_freqs_dir);
   F.T = (n + kTC - 1) / kTC;
   int cus = fsn_device_cus();
   if (cus <= 0) cus = 256;  // sizing query without a device
   for (int k = 0; k < 4; ++k) F.nsplit[k] = split_of(d, k, cus, F.T);
   F.nsplit_heads = (int)(F.T < cus ? (F.T > 0 ? F.T : 1) : cus);
-  const int NT = F.NT;
-  F.n_bwd_units = NT * NT + 2 * NT * NT + (F.L - 1) * 2 * NT * NT;
-  const int upp = units_per_phase(prec);
-  F.nph_bwd = (F.n_bwd_units + upp - 1) / upp;
+  // blob_b holds the chain's transposed-weight stream and, once the chain has run, the input gradient's weight slices
+  // (mlp_layout.hpp: NT^2 (2 L + 1) units against at most NT (4 L + 1), NT >= 4): the larger of the two IS the former
+  StreamTable Tb, Ti;
+  stream_table_bwd(d, prec, Tb);
+  stream_table_input_grad(d, prec, true, true, Ti);
+  F.nph_bwd = stream_phases(Tb);
+  const int64_t blob_b_bytes = stream_bytes(Tb) > stream_bytes(Ti) ? stream_bytes(Tb) : stream_bytes(Ti);
+  assert(blob_b_bytes == stream_bytes(Tb) && "the input-gradient slices fit the backward stream's area");
   F.blob_f_bytes = G.total_bytes;
   auto al = [](int64_t floats) { return (floats + 1023) / 1024 * 1024; };  // 4-KiB granules
   int64_t o = 0;
   F.blob_f = o; o += al(G.total_bytes / 4 + 1);
-  F.blob_b = o; o += al((int64_t)F.nph_bwd * kPhaseBytes / 4);
+  F.blob_b = o; o += al(blob_b_bytes / 4);
   const int64_t T = F.T, D = F.D;
   F.pe = o; o += T * 64 * kTC;
   F.de = o; o += T * 32 * kTC;
@@ -247,49 +255,6 @@ __global__ __launch_bounds__(kThreads) void k_train_fwd(TrainFwdArgs a) {
     }
   }
   st.drain();
-}
-
-// ------------------------------------------------------------------ backward blob (transposed weights)
-struct BwdPackArgs {
-  const float* W[kMaxLayers + 2];
-  int32_t ld[kMaxLayers + 2], ks[kMaxLayers + 2], unit0[kMaxLayers + 2];
-  int32_t n_gemm, units_total, prec, NT;
-};
-
-// A operand element (row i = input feature of the layer, k = o = output feature) = W[o][i]; the k order inside a
-// k-step is the accumulator-as-operand order of mlp_layout.hpp (o = 32 ks + 16 (j>>2) + 4 g + (j&3)).
-__global__ void k_pack_bwd(BwdPackArgs a, char* __restrict__ stream, int64_t n_pieces) {
-  const int64_t piece = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (piece >= n_pieces) return;
-  const int ub = unit_bytes(a.prec), ppu = ub / 16;
-  const int unit = (int)(piece / ppu);
-  const int rem = (int)(piece - (int64_t)unit * ppu);
-  const int part = rem >> 6, lane = rem & 63;
-  uint16_t o8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (unit < a.units_total) {
-    int gi = 0;
-    while (gi + 1 < a.n_gemm && a.unit0[gi + 1] <= unit) ++gi;
-    const int lu = unit - a.unit0[gi];
-    const int sub = lu & 1, kst = a.ks[gi];
-    const int t = (lu >> 1) / kst, ks = (lu >> 1) - t * kst;
-    const int r = lane & 15, grp = lane >> 4;
-    const int row = 32 * t + 16 * sub + r;
-    const float* W = a.W[gi];
-    const int ld = a.ld[gi];
-    const bool f16 = prec_is_f16(a.prec);
-    for (int j = 0; j < 8; ++j) {
-      const int oc = 32 * ks + 16 * (j >> 2) + 4 * grp + (j & 3);
-      const float w = W[(int64_t)oc * ld + row];
-      const uint16_t hi = half_rne(w, f16);
-      o8[j] = part == 0 ? hi : half_rne((w - half_to_f32(hi, f16)) * lo_scale(a.prec), f16);
-    }
-  }
-  uint4 v;
-  v.x = o8[0] | ((uint32_t)o8[1] << 16);
-  v.y = o8[2] | ((uint32_t)o8[3] << 16);
-  v.z = o8[4] | ((uint32_t)o8[5] << 16);
-  v.w = o8[6] | ((uint32_t)o8[7] << 16);
-  *reinterpret_cast<uint4*>(stream + piece * 16) = v;
 }
 
 // ------------------------------------------------------------------ backward chain (dgrad)
@@ -1187,22 +1152,13 @@ int fused_train_bwd(const fsn_mlp_desc* d, int prec, const float* const* W, int6
   build_geom(*d, prec, G, &why);
   const int cus = fsn_device_cus();
   if (cus <= 0) return FSN_E_HIP;
-  const int L = F.L, D = F.D, NT = F.NT;
-  // ---- transposed-weight stream
+  const int L = F.L, D = F.D;
+  // ---- transposed-weight stream (the table make_fused_layout sized blob_b from)
   {
-    BwdPackArgs p{};
-    int u = 0, gi = 0;
-    p.W[gi] = W[L + 2]; p.ld[gi] = D + F.d_de; p.ks[gi] = NT / 2; p.unit0[gi] = u; u += 2 * NT * (NT / 2); ++gi;
-    p.W[gi] = W[L + 1]; p.ld[gi] = D; p.ks[gi] = NT; p.unit0[gi] = u; u += 2 * NT * NT; ++gi;
-    for (int l = L - 1; l >= 1; --l) {
-      const bool wide = (d->skip_mask >> (l - 1)) & 1u;
-      p.W[gi] = W[l]; p.ld[gi] = D + (wide ? F.d_pe : 0); p.ks[gi] = NT; p.unit0[gi] = u; u += 2 * NT * NT; ++gi;
-    }
-    p.n_gemm = gi; p.units_total = u; p.prec = prec; p.NT = NT;
-    FSN_REQUIRE(u == F.n_bwd_units, FSN_E_HIP, "internal: backward unit count");
-    const int64_t n_pieces = (int64_t)F.nph_bwd * kPhaseBytes / 16;
-    k_pack_bwd<<<(unsigned)((n_pieces + 255) / 256), 256, 0, s>>>(p, reinterpret_cast<char*>(ws + F.blob_b), n_pieces);
-    FSN_LAUNCH_CHECK("k_pack_bwd");
+    StreamTable Tb;
+    stream_table_bwd(*d, prec, Tb);
+    rc = pack_stream_device(Tb, W, ws + F.blob_b, s);
+    if (rc != FSN_OK) return rc;
   }
   // ---- dgrad chain
   {
@@ -1223,7 +1179,7 @@ int fused_train_bwd(const fsn_mlp_desc* d, int prec, const float* const* W, int6
     return FSN_OK;
   };
   if (ig) {  // ---- input gradient (input_grad.hip)
-    const InputGradWs o{F.blob_b, F.pe - F.blob_b, F.dp, F.h_stride, F.dbo};
+    const InputGradWs o{F.blob_b, F.dp, F.h_stride, F.dbo};
     rc = input_grad_launch(*d, prec, W, n, ws, o, grad_scale_dev, prec_is_f16(prec) ? bscale : nullptr,
                            prec_is_f16(prec) ? status : nullptr, *ig, s);
     if (rc != FSN_OK) return rc;

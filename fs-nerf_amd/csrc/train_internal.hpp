@@ -35,9 +35,10 @@ int train_bwd_checked(const char* who, const fsn_mlp_desc* desc, int prec, const
                       const InputGradReq* rq);
 
 // k_input_grad (input_grad.hip), launched by fused_train_bwd between the dgrad chain and k_bwd_rescale.  The packed
-// weight slices go where the chain's transposed-weight stream lay (dead once the chain has run).
+// weight slices go where the chain's transposed-weight stream lay (dead once the chain has run; the workspace layout
+// sizes that area for the larger of the two streams).
 struct InputGradWs {
-  int64_t blob, blob_floats;      // float offsets into the workspace: the backward blob and its size
+  int64_t blob;                   // float offsets into the workspace: the backward stream's area
   int64_t dp, h_stride, dbo;      // dPre_0 (stage l at dp + l h_stride), dBo
 };
 int input_grad_launch(const fsn_mlp_desc& d, int prec, const float* const* W, int64_t n, float* ws, const InputGradWs& o,

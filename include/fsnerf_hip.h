@@ -354,6 +354,26 @@ int fsn_mlp_pack_host(const fsn_mlp_desc* desc, int prec, const float* const* we
                       const float* const* biases_host, void* blob_host);
 int fsn_mlp_pack_scaled_host(const fsn_mlp_desc* desc, int prec, const float* const* weights_host,
                              const float* const* biases_host, const int32_t* layer_exps_host, void* blob_host);
+/* The two weight streams the training backward packs into its workspace, on their own (format tests; the backward calls
+ * the same packer).  They have the blob's stream format - units of 1 KiB of 16-bit high parts and, in the x3 modes,
+ * 1 KiB of low parts, lane-linear MFMA A fragments - and no header or aux region:
+ *   FSN_WSTREAM_BWD         the dgrad chain's transposed weights: branch^T (first d_hidden input columns), connection^T,
+ *                           layers n_layers-1 .. 1 (their d_hidden activation columns), padded with zeros to whole
+ *                           16-KiB phases; want_x / want_dirs are not read
+ *   FSN_WSTREAM_INPUT_GRAD  the encoding columns of layer 0 and the skip-fed layers (when want_x != 0), then of the
+ *                           branch (when want_dirs != 0), transposed, rows in the encoder's slot order; no padding
+ * prec: a training mode (FSN_PREC_BF16X3, _BF16, _FP16X3, _FP16), any other value is FSN_E_UNSUPPORTED.  An unknown
+ * kind, a null pointer, or FSN_WSTREAM_INPUT_GRAD with both flags zero is FSN_E_INVALID; a descriptor fsn_mlp_blob_bytes
+ * refuses is refused with the same code.  weights: n_layers+4 pointers in fsn_mlp_pack's order; those the stream does
+ * not read (sigma, rgb, ...) are not dereferenced.
+ * fsn_weight_stream_bytes: the stream's size in bytes (negative on error); dst / dst_host hold that many. */
+#define FSN_WSTREAM_BWD 1
+#define FSN_WSTREAM_INPUT_GRAD 2
+int64_t fsn_weight_stream_bytes(const fsn_mlp_desc* desc, int prec, int kind, int want_x, int want_dirs);
+int fsn_weight_stream_pack(const fsn_mlp_desc* desc, int prec, int kind, int want_x, int want_dirs,
+                           const float* const* weights_host_of_dev, void* dst, fsn_stream_t stream);
+int fsn_weight_stream_pack_host(const fsn_mlp_desc* desc, int prec, int kind, int want_x, int want_dirs,
+                                const float* const* weights_host, void* dst_host);
 /* x [n,3]; dirs [n,3] or NULL.  out [n,4]=[r,g,b,sigma] when dirs != NULL, else [n,1]=sigma.
  * pos_mask [3*(1+2*n_freqs_pos)] / dir_mask [3*(1+2*n_freqs_dir)] device pointers or NULL. */
 int fsn_mlp_fwd(const fsn_mlp_desc* desc, int prec, const void* blob, const float* x,

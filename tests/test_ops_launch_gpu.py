@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 R, S, NI, STEP = 40, 8, 8, 0.1
 # symbols whose last pointer argument is an output, not a stream (include/fsnerf_hip.h)
 NO_STREAM = {"fsn_debug_report", "fsn_ray_perm_host", "fsn_mlp_pack_host", "fsn_mlp_pack_scaled_host",
-             "fsn_weight_norm_workspace_floats"}
+             "fsn_weight_stream_pack_host", "fsn_weight_norm_workspace_floats"}
 
 
 @pytest.fixture(scope="module")

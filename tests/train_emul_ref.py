@@ -17,7 +17,7 @@ Where each rounding point was read (fs-nerf_amd/csrc):
                          forward's own fp32 output; stored unrounded (dhead).
   d Bo                   k_train_bwd, branch block: (dz . w_rgb) in fp32, masked by Bo > 0, split_store -> stored q(dBo),
                          and q(dBo) is the B operand of the next GEMM.
-  d feat, d Pre_l        k_train_bwd: gemm_layer<..., EPI_CVT> on the transposed-weight stream (k_pack_bwd: half_rne(W) =
+  d feat, d Pre_l        k_train_bwd: gemm_layer<..., EPI_CVT> on the transposed-weight stream (kStreamBwd, pack_piece: half_rne(W) =
                          q(W)) with BwdStoreHook / BwdMaskHook: dH = q(dY) @ q(W)[:, :D]; the sigma head's dsig * w_sigma
                          (fp32) is added and the ReLU mask applied in post(), before the split: stored q(dPre), which is
                          the next GEMM's operand and the weight-gradient GEMM's.
@@ -26,7 +26,7 @@ Where each rounding point was read (fs-nerf_amd/csrc):
                          db = sum q(dPre).
   head weight gradients  k_heads_wgrad: accS += ds * h with ds from dhead (fp32) and h = from_h(stored part) = q(h_{L-1});
                          accR the same with q(Bo); biases: accB sums of dhead (fp32).
-  input gradient         input_grad.hip: k_pack_input_grad rounds the encoding columns of W_0, the skip-fed layers and
+  input gradient         input_grad.hip: the slices' stream (kStreamInputGrad, pack_piece) rounds the encoding columns of W_0, the skip-fed layers and
                          the branch layer (half_rne), ig_job multiplies them with the stored q(dPre_l) / q(dBo):
                          d enc = q(dY) @ q(W)[:, encoding columns]; enc_bwd is fp32 (sincos_f32 of the sample position).
   fp16 gradient scale    k_train_bwd multiplies d_out by `scale` on entry, k_wgrad_reduce / k_heads_reduce / k_input_grad
