@@ -10,6 +10,7 @@ estimator.update_every_n_steps) and evaluated with render_frame + PSNR and SSIM 
                                        [--lpips-weight W --lpips-weights FILE]
                                        [--entropy-weight W] [--depth-kl-weight W --depth-kl-var V]
                                        [--depth-smooth-weight W] [--unseen-views shell|box]
+                                       [--warp-weight W --warp-kind l1|l2]
                                        [--refine-poses --pose-noise-rot DEG --pose-noise-trans X --pose-lr LR
                                         --c2f-until K]
                                        [--refine-intrinsics --focal-noise PCT --intrinsics-lr LR --per-view-intrinsics
@@ -34,6 +35,13 @@ photograph was taken from (RegNeRF's depth smoothness); their rays come from get
 call, behind the ray batch and the SSIM / LPIPS patches.  --unseen-views shell|box: those patches are instead --patches
 freshly drawn poses' patches from nerfdata.UnseenPatchLoader, one launch per step, its pose distribution fitted to the
 training poses (UnseenViewSampler.from_poses); with --entropy-weight alone the entropy term covers their rays too.
+
+--warp-weight W [--warp-kind l1|l2] (0 by default; needs --u8-dataset): the depth-warp consistency term
+(core.loss.WarpConsistencyLoss over nerfdata.WarpSource, through render_rays(full_grad=True)): a ray's rendered colour
+against the colour a training photograph shows at its rendered 3-D point, rays masked by the rendered opacity.  With
+--unseen-views the term is put on those patches, each against the training view nearest to its pose
+(WarpSource.nearest_views of the poses the loader reports); otherwise on the batch's own rays, each against the view
+nearest to its own (the view is index // (H W), the source WarpSource.other_views).
 
 --cone-angle / --near-plane (both 0 by default): `sampling_kwargs` of render_rays / render_frame / render_path - the
 occupancy march's step grows with distance, dt = max(t * cone_angle, step), and nothing is sampled in front of the near
@@ -90,11 +98,11 @@ import fs_nerf_amd  # noqa: E402,F401
 from fs_nerf_amd.core import metrics  # noqa: E402
 from fs_nerf_amd.core import models as M  # noqa: E402
 from fs_nerf_amd.core.loss import (DepthKLLoss, DistortionLoss, LPIPSLoss, PatchDepthSmoothnessLoss,  # noqa: E402
-                                   RayEntropyLoss, SSIMLoss, WeightNormRegularizer)
+                                   RayEntropyLoss, SSIMLoss, WarpConsistencyLoss, WeightNormRegularizer)
 from fs_nerf_amd.core.optim import FusedAdam  # noqa: E402
 from fs_nerf_amd.core.scheduler import ExponentialDecay  # noqa: E402
 from fs_nerf_amd.nerfdata import (CameraRefiner, FrameLoader, IntrinsicsRefiner, PatchLoader, RayDataset, RayLoader, UnseenPatchLoader,  # noqa: E402
-                                  UnseenViewSampler, pose_error)
+                                  UnseenViewSampler, WarpSource, pose_error)
 from fs_nerf_amd.render import rendering as R  # noqa: E402
 from fs_nerf_amd.render.occgrid import OccGridEstimator  # noqa: E402
 from fs_nerf_amd.render.propnet import PropNetEstimator  # noqa: E402
@@ -173,6 +181,10 @@ def main():
                     help="opt-in: the rays of --depth-smooth-weight (and --entropy-weight on them) come from "
                          "nerfdata.UnseenPatchLoader, one launch per step, its pose distribution fitted to the training "
                          "poses (UnseenViewSampler.from_poses) - instead of the hard-coded orbit and a host generator")
+    ap.add_argument("--warp-weight", type=float, default=0.0,
+                    help="opt-in: weight of the depth-warp consistency of the rendered colour and depth with the nearest "
+                         "training photograph (core.loss.WarpConsistencyLoss; needs --u8-dataset; render_rays(full_grad=True))")
+    ap.add_argument("--warp-kind", choices=("l1", "l2"), default="l1", help="with --warp-weight: the photometric penalty")
     ap.add_argument("--cone-angle", type=float, default=0.0,
                     help="opt-in: the occupancy march's step grows with distance, dt = max(t * cone_angle, step) "
                          "(sampling_kwargs of render_rays / render_frame; nerfacc uses 0.004 for unbounded scenes)")
@@ -238,12 +250,14 @@ def main():
         ap.error("--depth-weight needs the float tables: the uint8 dataset carries no depth")
     if a.depth_kl_weight and a.u8_dataset:
         ap.error("--depth-kl-weight needs the float tables: the uint8 dataset carries no depth")
-    if a.unseen_views and not (a.depth_smooth_weight or a.entropy_weight):
-        ap.error("--unseen-views serves the rays of --depth-smooth-weight / --entropy-weight: set one of them")
+    if a.unseen_views and not (a.depth_smooth_weight or a.entropy_weight or a.warp_weight):
+        ap.error("--unseen-views serves the rays of --depth-smooth-weight / --entropy-weight / --warp-weight: set one of them")
+    if a.warp_weight and not a.u8_dataset:
+        ap.error("--warp-weight samples the device-resident photographs: add --u8-dataset")
     if a.depth_smooth_weight and a.patch < 2:
         ap.error("--depth-smooth-weight needs --patch of at least 2")
     full_grad = any(w != 0.0 for w in (a.depth_weight, a.distortion_weight, a.entropy_weight, a.depth_kl_weight,
-                                       a.depth_smooth_weight))
+                                       a.depth_smooth_weight, a.warp_weight))
     dev = torch.device("cuda:0")
     hwf = (a.hw, a.hw, 0.5 * a.hw / math.tan(0.5 * 0.6911112))
     near, far, step = 2.0, 6.0, 2e-2
@@ -275,8 +289,14 @@ def main():
         if a.refine_intrinsics:
             intrinsics = IntrinsicsRefiner(train_set, per_view=a.per_view_intrinsics,
                                            learn_principal_point=a.learn_principal_point)
-        train_loader = RayLoader(train_set, a.batch, shuffle=True, seed=0, cameras=cameras, intrinsics=intrinsics)
+        # (the warp term on the batch's own rays needs to know which view each came from: the loader reports the index)
+        warp_own = bool(a.warp_weight) and not a.unseen_views
+        train_loader = RayLoader(train_set, a.batch, shuffle=True, seed=0, cameras=cameras, intrinsics=intrinsics,
+                                 with_index=warp_own)
         iterator = iter(train_loader)
+        if a.warp_weight:
+            warp_source = WarpSource(train_set, cameras=cameras, intrinsics=intrinsics)
+            warp_loss = WarpConsistencyLoss(a.warp_kind, threshold=0.5)
         if a.ssim_weight or a.lpips_weight:
             patch_loader = PatchLoader(train_set, a.patch, a.patches, shuffle=True, seed=1, cameras=cameras,
                                        intrinsics=intrinsics)
@@ -323,7 +343,7 @@ def main():
     pose_gen = torch.Generator().manual_seed(4)  # the unseen poses of --depth-smooth-weight
     if a.unseen_views:
         unseen_loader = UnseenPatchLoader(UnseenViewSampler.from_poses(torch.stack(poses), a.unseen_views, device=dev), hwf,
-                                          a.patch, a.patches, seed=4)
+                                          a.patch, a.patches, seed=4, with_poses=bool(a.warp_weight))
     scheduler = ExponentialDecay(optimizer, a.iters, 5e-4, r=0.1)
     gen = torch.Generator(device=dev).manual_seed(0)
 
@@ -340,10 +360,10 @@ def main():
             model.set_freq_mask(c2f_mask(3, 10, progress, dev), c2f_mask(3, 4, progress, dev))
         if a.u8_dataset:
             try:  # (run-nerf.py:236-240)
-                rays_o, rays_d, rgb_gt = next(iterator)
+                rays_o, rays_d, rgb_gt, *ray_index = next(iterator)
             except StopIteration:
                 iterator = iter(train_loader)
-                rays_o, rays_d, rgb_gt = next(iterator)
+                rays_o, rays_d, rgb_gt, *ray_index = next(iterator)
         else:
             idx = torch.randint(0, ro.shape[0], (a.batch,), device=dev, generator=gen)
             rays_o, rays_d, rgb_gt = ro[idx], rd[idx], gt[idx]
@@ -357,7 +377,7 @@ def main():
             rays_o, rays_d = torch.cat([rays_o, patch_o]), torch.cat([rays_d, patch_d])
         n_seen = rays_o.shape[0]
         if a.unseen_views:  # B patches of P x P rays of B freshly drawn poses in one launch, behind the rest
-            o, d = next(unseen_loader)
+            o, d, *unseen_poses = next(unseen_loader)  # (+ the poses, for the warp term's source views)
             rays_o, rays_d = torch.cat([rays_o, o]), torch.cat([rays_d, d])
         elif a.depth_smooth_weight:  # B windows of P x P rays of one random pose between the training views, behind the rest
             phi, theta = 360.0 * float(torch.rand((), generator=pose_gen)), 40.0 + 20.0 * float(torch.rand((), generator=pose_gen))
@@ -392,6 +412,16 @@ def main():
                                                        rays_o.shape[0], target, a.depth_kl_var)
         if a.depth_smooth_weight and depth.requires_grad:
             loss = loss + a.depth_smooth_weight * depth_smooth(depth[n_seen:].view(-1, a.patch, a.patch))
+        if a.warp_weight and depth.requires_grad:
+            if a.unseen_views:  # the unseen patches, each against the training view nearest to its pose
+                rows = slice(n_seen, None)
+                src_view = warp_source.nearest_views(unseen_poses[0]).repeat_interleave(a.patch * a.patch)
+            else:  # the batch's own rays, each against the view nearest to its own
+                rows = slice(0, n_batch)
+                own_view = torch.div(ray_index[0], a.hw * a.hw, rounding_mode="floor")
+                src_view = warp_source.other_views(1)[own_view, 0]
+            loss = loss + a.warp_weight * warp_loss(rgb[rows], depth[rows].reshape(-1), rays_o[rows], rays_d[rows], src_view,
+                                                    warp_source, opacity=opacity[rows])
         if wnorm.active(k):
             loss = loss + alpha * wnorm()
         loss.backward()

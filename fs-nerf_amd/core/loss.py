@@ -5,7 +5,8 @@ compositor's weights (this package's own, the first consumer of `full_grad`); an
 parameter arena; and the structural (D-SSIM) and perceptual (LPIPS-VGG) terms on rendered patches (this package's own:
 the evaluation metrics of core/metrics.py with a backward); and the few-shot geometry losses on the renderer's other
 outputs (this package's own definitions of InfoNeRF's ray entropy, DS-NeRF's depth KL term and RegNeRF's patch depth
-smoothness: csrc/ray_losses.hip)."""
+smoothness: csrc/ray_losses.hip); and the cross-view reprojection term on nerfdata.WarpSource (depth-warp consistency:
+csrc/warp.hip)."""
 import ctypes as C
 import math
 from typing import Optional
@@ -108,6 +109,45 @@ class PatchDepthSmoothnessLoss:
         per_patch = ops.patch_depth_smoothness(depth)
         B, P, Q = depth.shape
         return per_patch.sum() / float(max(B, 1) * max((P - 1) * (Q - 1), 1))
+
+
+class WarpConsistencyLoss:
+    """Cross-view reprojection (the photometric warping term of GeCoNeRF, SPARF and ConsistentNeRF; this package's OWN
+    definition): a rendered ray's colour against the colour that a training photograph shows at the ray's
+    rendered 3-D point.  With colour_r, valid_r = source.sample(rays_o, rays_d, depth, src_view) (nerfdata.WarpSource,
+    ops.warp_sample: `z_min`, `border` are its keywords), per row
+        l_r = mean_c rho(rgb_c - colour_c),   rho = |.| ("l1"; gradient 0 at 0, torch.abs's rule) or (.)^2 ("l2"),
+        c_r = valid_r  and, when a `threshold` is given,  opacity_r > threshold  (the opacity detached: RayEntropyLoss's
+              rule - a ray that hits nothing has no depth to reproject),
+    and the call returns sum_r c_r l_r / max(sum_r c_r, 1), counted on the device (no host sync).  `rgb` [n,3] and
+    `depth` [n] come from render_rays(..., full_grad=True), whose depth carries a gradient; `src_view` [n] int64 names
+    the source view of each row (WarpSource.other_views for a training batch's own views, nearest_views for the poses of
+    an UnseenPatchLoader; -1 = none).  Gradients go to rgb, to depth and to the rays; a row that is invalid or masked
+    contributes 0 and gets a gradient of exactly 0.  The reduction is a few torch ops around the operator's one launch
+    each way.  Limits: no gradient to the images, to the source poses or to K; one source view per call (call it twice
+    for two); no occlusion reasoning beyond the caller's mask and the operator's uvz output; NDC datasets are refused
+    by WarpSource."""
+
+    def __init__(self, kind: str = "l1", threshold: Optional[float] = None, z_min: float = 1e-3, border: float = 0.5):
+        if kind not in ("l1", "l2"):
+            raise ValueError(f"WarpConsistencyLoss: kind must be 'l1' or 'l2', got {kind!r}")
+        self.kind, self.threshold = kind, None if threshold is None else float(threshold)
+        self.z_min, self.border = float(z_min), float(border)
+
+    def __call__(self, rgb: Tensor, depth: Tensor, rays_o: Tensor, rays_d: Tensor, src_view: Tensor, source,
+                 opacity: Optional[Tensor] = None) -> Tensor:
+        src_view = src_view.reshape(-1)
+        if self.threshold is not None:
+            if opacity is None:
+                raise ValueError("WarpConsistencyLoss: a threshold needs the renderer's opacity")
+            # a masked row goes in without a source view: the operator writes its zeros itself and reads no pixel for it
+            src_view = torch.where(opacity.detach().reshape(-1) > self.threshold, src_view, torch.full_like(src_view, -1))
+        colour, valid, _ = source.sample(rays_o, rays_d, depth, src_view, z_min=self.z_min, border=self.border)
+        diff = rgb.reshape(-1, 3) - colour
+        per_row = (diff.abs() if self.kind == "l1" else diff * diff).mean(dim=1)
+        # (where, not a product: a masked row's difference may be anything and must not reach the sum)
+        total = torch.where(valid, per_row, torch.zeros_like(per_row)).sum()
+        return total / valid.sum().clamp(min=1).to(per_row.dtype)
 
 
 class _SSIMLossFn(torch.autograd.Function):

@@ -1314,6 +1314,78 @@ def patch_depth_smoothness(depth: Tensor) -> Tensor:
     return _PatchTVFn.apply(_f32(depth, "depth"))
 
 
+# ------------------------------------------------------------------ depth-warp sampling (csrc/warp.hip)
+class _WarpSampleFn(torch.autograd.Function):
+    """colour / valid / uvz of fsn_warp_sample_fwd in one node; the backward is one fsn_warp_sample_bwd launch that
+    recomputes the projection and the taps, with NULL where an input needs no gradient."""
+
+    @staticmethod
+    def forward(ctx, o, d, t, sv, poses12, images, K, white_bkgd, z_min, border, want_uvz):
+        n, dev = t.numel(), t.device
+        colour = torch.empty(n, 3, device=dev, dtype=torch.float32)
+        valid = torch.empty(n, device=dev, dtype=torch.uint8)
+        uvz = torch.empty(n, 3, device=dev, dtype=torch.float32) if want_uvz else None
+        ctx.flags = (white_bkgd, z_min, border)
+        if n:
+            _launch("fsn_warp_sample_fwd", dev, o, d, t, sv, n, poses12, poses12.shape[0], images, images.shape[1],
+                    images.shape[2], images.shape[3], white_bkgd, K, K.shape[0], z_min, border, colour, valid, uvz)
+        ctx.save_for_backward(o, d, t, sv, poses12, images, K)
+        valid = valid.view(torch.bool)
+        ctx.mark_non_differentiable(*((valid,) if uvz is None else (valid, uvz)))
+        return colour, valid, uvz
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_valid, _g_uvz):
+        o, d, t, sv, poses12, images, K = ctx.saved_tensors
+        white_bkgd, z_min, border = ctx.flags
+        want_o, want_d, want_t = ctx.needs_input_grad[:3]
+        d_o = torch.empty_like(o) if want_o else None
+        d_d = torch.empty_like(d) if want_d else None
+        d_t = torch.empty_like(t) if want_t else None
+        if t.numel() and (want_o or want_d or want_t):
+            _launch("fsn_warp_sample_bwd", t.device, o, d, t, sv, t.numel(), poses12, poses12.shape[0], images,
+                    images.shape[1], images.shape[2], images.shape[3], white_bkgd, K, K.shape[0], z_min, border,
+                    _f32(g, "grad"), d_t, d_o, d_d)
+        return (d_o, d_d, d_t) + (None,) * 8
+
+
+def warp_sample(rays_o: Tensor, rays_d: Tensor, depth: Tensor, src_view: Tensor, poses12: Tensor, images: Tensor, K: Tensor,
+                *, white_bkgd: bool = False, z_min: float = 1e-3, border: float = 0.0, want_uvz: bool = False):
+    """Depth-warp sampling in ONE launch each way (fsn_warp_sample_fwd / _bwd; DESIGN 6.1 and include/fsnerf_hip.h have
+    the definition): row r's point rays_o_r + depth_r rays_d_r is projected into source view src_view_r (poses12 [V,12]
+    float32, K = (fx, fy, cx, cy) [1 or V, 4] float32) and the resident bytes `images` uint8 [V,H,W,3|4] are sampled
+    bilinearly there, each tap converted as the ray batch converts its pixel (`white_bkgd` composes over alpha) ->
+    (colour [n,3] float32, valid [n] bool, uvz [n,3] or None with want_uvz=False).
+    A row is valid iff 0 <= src_view < V (-1 is the documented "no source view"), depth is finite and > 0, the point lies
+    at least `z_min` in front of the source camera and its pixel coordinates at least `border` pixels inside the image;
+    an invalid row gets colour 0 and every gradient exactly 0.  uvz = (u, v, z), the pixel coordinates and the depth in
+    the source camera, for every row whose view is in range (for an occlusion mask against source depths).
+    rays_o, rays_d [n,3] and depth [n] or [n,1] are float32 GPU tensors taken as they are (nothing is cast); gradients
+    go to whichever of them require one, and the cell of the four taps is a constant of the backward (as for
+    grid_sample).  `valid` and `uvz` are not differentiable, and there is NO gradient to the images, to poses12 or to
+    K: the source cameras are constants here."""
+    o, d = _gpu_f32(rays_o, "warp_sample: rays_o"), _gpu_f32(rays_d, "warp_sample: rays_d")
+    t = _gpu_f32(depth, "warp_sample: depth").reshape(-1)
+    n = t.numel()
+    if o.dim() != 2 or tuple(o.shape) != (n, 3) or tuple(d.shape) != (n, 3):
+        raise ValueError(f"warp_sample: rays_o and rays_d are [n,3] for a depth of n = {n} entries, got {tuple(o.shape)} "
+                         f"and {tuple(d.shape)}")
+    if src_view.numel() != n:
+        raise ValueError(f"warp_sample: src_view has {src_view.numel()} entries for {n} rows")
+    sv = _i64(src_view, "warp_sample: src_view").reshape(-1)
+    if not (poses12.is_cuda and images.is_cuda):
+        raise RuntimeError("warp_sample: poses12 and images: expected GPU tensors (the HIP path has no CPU fallback)")
+    if poses12.dtype != torch.float32 or poses12.dim() != 2 or poses12.shape[1] != 12 or not poses12.is_contiguous():
+        raise TypeError("warp_sample: poses12 is float32 [V,12], contiguous")
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[0] != poses12.shape[0] or not images.is_contiguous():
+        raise TypeError(f"warp_sample: images are uint8 [{poses12.shape[0]},H,W,3|4], contiguous, got {images.dtype} "
+                        f"{tuple(images.shape)}")
+    K, _ = _camera_table(K, poses12.shape[0], "warp_sample")
+    return _WarpSampleFn.apply(o, d, t, sv, poses12.detach(), images, K, 1 if white_bkgd else 0, float(z_min),
+                               float(border), bool(want_uvz))
+
+
 # ------------------------------------------------------------------ packed volume-rendering primitives (csrc/packed_scan.hip)
 class RaySpans:
     """Where each ray's samples are among N flat samples - the "span" arguments of include/fsnerf_hip.h: exactly one of

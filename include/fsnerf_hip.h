@@ -80,6 +80,7 @@ int fsn_version(void);
  *   "ssim_grad"  ssim_grad.hip   every LDS index of the two kernels behind the SSIM gradient
  *   "lpips"      lpips.hip       every LDS index of k_lpips_conv and k_lpips_first_bwd
  *   "pose_refine" pose_refine.hip  ray indices outside [0, N) handed to fsn_ray_pose_grad / fsn_ray_camera_grad
+ *   "warp"       warp.hip        source views outside [-1, n_views) and every tap offset of fsn_warp_sample_fwd / _bwd
  * A record is 4 uint32 = {violations, source line of the first, its index (or the end of its span), the extent}, the
  * last two truncated to 32 bits.  fsn_debug_report synchronises the device, copies the record of `unit` to out4 and
  * clears it; an unknown unit is FSN_E_INVALID (the message lists the known ones), the release library returns
@@ -704,6 +705,49 @@ int fsn_patch_tv_fwd(const float* depth, int64_t B, int P, int Q, float* out, fs
  * appears in (as the anchor, as an anchor's right and lower neighbour) times d_out[b].  No atomics. */
 int fsn_patch_tv_bwd(const float* depth, int64_t B, int P, int Q, const float* d_out, float* d_depth,
                      fsn_stream_t stream);
+
+/* ---- depth-warp sampling: a rendered ray and its depth -> the colour a training photograph shows at that 3-D point
+ *                                                     (this package's own; DESIGN.md 6.1 "Depth-warp consistency")
+ *                                                                                                     csrc/warp.hip
+ * The operator under the cross-view reprojection losses (GeCoNeRF, SPARF, ConsistentNeRF): ONE launch, one thread per
+ * row, no LDS, no atomics, no workspace; rows are independent, so every output is bitwise reproducible.  The library is
+ * built with -ffp-contract=off and every step is a float32 operation in the order written, so tests/warp_ref.py
+ * restates the forward bit for bit in NumPy.  Row r, with (o, d) = (rays_o_r, rays_d_r), t = depth_r, s = src_view_r,
+ * M = poses[s] ([3][4]: rotation columns and centre c, as fsn_ray_batch reads it), (fx, fy, cx, cy) = row s of
+ * K [m, 4] (row 0 when m == 1; the stored intrinsics are (focal, focal, W/2, H/2)):
+ *   X_k = o_k + t d_k,  p_k = X_k - c_k;
+ *   xc = (M[0] p0 + M[4] p1) + M[8] p2, yc and zc likewise with columns 1 and 2 (R^T p);  z = -zc (the camera looks
+ *   down its own -z);
+ *   u = cx + fx (xc / z),  v = cy - fy (yc / z)      (the pixel index w of fsn_ray_batch is the coordinate u = w);
+ *   valid iff 0 <= s < n_views, t finite and > 0, z >= z_min, border <= u <= (W-1) - border and
+ *   border <= v <= (H-1) - border (a NaN anywhere makes the row invalid);
+ *   x0 = min((int)floorf(u), W-2), fu = u - x0; y0 = min((int)floorf(v), H-2), fv = v - y0; the taps c00 at (y0, x0),
+ *   c10 at (y0, x0+1), c01 at (y0+1, x0), c11 at (y0+1, x0+1) of images [n_views, H, W, C] uint8, each converted as
+ *   fsn_ray_batch converts its pixel (byte / 255; with white_bkgd c a + (1 - a) in three float32 operations);
+ *   top = c00 + fu (c10 - c00), bot = c01 + fu (c11 - c01), colour = top + fv (bot - top).
+ * Outputs: colour [n,3]; valid [n] uint8 (0 / 1); uvz [n,3] = (u, v, z) (may be NULL) for every row whose s is in range,
+ * valid or not (a NaN is stored as the canonical quiet NaN), zeros otherwise - for a caller that holds source depths and
+ * builds an occlusion mask; not differentiable.  An invalid row gets colour = 0 and valid = 0 and reads no byte of
+ * `images`.  s = -1 is the documented "no source view"; any other s outside [0, n_views) is invalid too (and, in the
+ * debug build, recorded for fsn_debug_report("warp"), as is a tap offset outside the images).
+ * n == 0 returns FSN_OK without a launch.  Errors (FSN_E_INVALID): n or n_views negative, null pointers, C not in
+ * {3, 4}, white_bkgd with C = 3, H < 2 or W < 2, m not in {1, n_views}, z_min <= 0, border < 0 (or either not finite). */
+int fsn_warp_sample_fwd(const float* rays_o, const float* rays_d, const float* depth, const int64_t* src_view, int64_t n,
+                        const float* poses, int64_t n_views, const uint8_t* images, int H, int W, int C, int white_bkgd,
+                        const float* K, int64_t m, float z_min, float border, float* colour, uint8_t* valid, float* uvz,
+                        fsn_stream_t stream);
+/* backward of fsn_warp_sample_fwd w.r.t. depth and the ray (each of d_depth [n], d_rays_o [n,3], d_rays_d [n,3] may be
+ * NULL = not wanted): ONE launch that recomputes the projection and the four taps from the inputs - nothing is saved.
+ * For a valid row, with g = d_colour_r and per channel dcu = (c10 - c00) + fv ((c11 - c01) - (c10 - c00)),
+ * dcv = bot - top:  gu = sum_c g_c dcu_c,  gv = sum_c g_c dcv_c;
+ *   g_xc = gu fx / z,  g_yc = -gv fy / z,  g_z = (-gu fx xc + gv fy yc) / (z z),  g_zc = -g_z;  gp = R (g_xc, g_yc, g_zc);
+ *   d_rays_o = gp,  d_rays_d = t gp,  d_depth = gp . d.
+ * The cell (x0, y0) is a constant of the backward (as for grid_sample); every gradient of an invalid row is written as
+ * exactly 0.  No gradient to the images, to the source pose or to K. */
+int fsn_warp_sample_bwd(const float* rays_o, const float* rays_d, const float* depth, const int64_t* src_view, int64_t n,
+                        const float* poses, int64_t n_views, const uint8_t* images, int H, int W, int C, int white_bkgd,
+                        const float* K, int64_t m, float z_min, float border, const float* d_colour, float* d_depth,
+                        float* d_rays_o, float* d_rays_d, fsn_stream_t stream);
 
 /* Packed volume-rendering primitives (csrc/packed_scan.hip; render/volrend.py is their Python surface, named after
  * nerfacc's volrend / scan / pack modules - this package's own definitions of nerfacc's documented semantics).
