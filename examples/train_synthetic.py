@@ -36,6 +36,14 @@ call, behind the ray batch and the SSIM / LPIPS patches.  --unseen-views shell|b
 freshly drawn poses' patches from nerfdata.UnseenPatchLoader, one launch per step, its pose distribution fitted to the
 training poses (UnseenViewSampler.from_poses); with --entropy-weight alone the entropy term covers their rays too.
 
+--ray-kl-weight W [--ray-kl-bins N] (0 by default: the loop is then the one above): the KL divergence between the
+termination distributions of neighbouring rays (core.loss.NeighborRayKLLoss, InfoNeRF's second term) on
+extras["weights"] through render_rays(full_grad=True).  Each patch ray's samples are binned into a histogram of N
+(default 64) bins over [near, far] and adjacent pixels of a patch are compared bin by bin, pixels masked by the
+rendered opacity.  It acts on the patches that --depth-smooth-weight renders - the orbit pose's or the --unseen-views
+ones, which sit behind every other ray of the call (first_ray = their offset) - and has them rendered when nothing
+else does; with --ssim-weight / --lpips-weight and no unseen patches it acts on the photographs' patches instead.
+
 --warp-weight W [--warp-kind l1|l2] (0 by default; needs --u8-dataset): the depth-warp consistency term
 (core.loss.WarpConsistencyLoss over nerfdata.WarpSource, through render_rays(full_grad=True)): a ray's rendered colour
 against the colour a training photograph shows at its rendered 3-D point, rays masked by the rendered opacity.  With
@@ -97,7 +105,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import fs_nerf_amd  # noqa: E402,F401
 from fs_nerf_amd.core import metrics  # noqa: E402
 from fs_nerf_amd.core import models as M  # noqa: E402
-from fs_nerf_amd.core.loss import (DepthKLLoss, DistortionLoss, LPIPSLoss, PatchDepthSmoothnessLoss,  # noqa: E402
+from fs_nerf_amd.core.loss import (DepthKLLoss, DistortionLoss, LPIPSLoss, NeighborRayKLLoss, PatchDepthSmoothnessLoss,  # noqa: E402
                                    RayEntropyLoss, SSIMLoss, WarpConsistencyLoss, WeightNormRegularizer)
 from fs_nerf_amd.core.optim import FusedAdam  # noqa: E402
 from fs_nerf_amd.core.scheduler import ExponentialDecay  # noqa: E402
@@ -177,8 +185,14 @@ def main():
     ap.add_argument("--depth-smooth-weight", type=float, default=0.0,
                     help="opt-in: weight of the depth smoothness of --patches patches of --patch x --patch rays from a random "
                          "unseen orbit pose (core.loss.PatchDepthSmoothnessLoss; render_rays(full_grad=True))")
+    ap.add_argument("--ray-kl-weight", type=float, default=0.0,
+                    help="opt-in: weight of the KL divergence between the termination histograms of neighbouring rays of "
+                         "the --patches patches of --patch x --patch rays that --depth-smooth-weight renders (or of the "
+                         "photographs' patches of --ssim-weight / --lpips-weight when only those are rendered), rays masked "
+                         "by opacity (core.loss.NeighborRayKLLoss over [near, far]; render_rays(full_grad=True))")
+    ap.add_argument("--ray-kl-bins", type=int, default=64, help="with --ray-kl-weight: the histograms' bins over [near, far]")
     ap.add_argument("--unseen-views", choices=("shell", "box"), default=None,
-                    help="opt-in: the rays of --depth-smooth-weight (and --entropy-weight on them) come from "
+                    help="opt-in: the rays of --depth-smooth-weight / --ray-kl-weight (and --entropy-weight on them) come from "
                          "nerfdata.UnseenPatchLoader, one launch per step, its pose distribution fitted to the training "
                          "poses (UnseenViewSampler.from_poses) - instead of the hard-coded orbit and a host generator")
     ap.add_argument("--warp-weight", type=float, default=0.0,
@@ -250,14 +264,17 @@ def main():
         ap.error("--depth-weight needs the float tables: the uint8 dataset carries no depth")
     if a.depth_kl_weight and a.u8_dataset:
         ap.error("--depth-kl-weight needs the float tables: the uint8 dataset carries no depth")
-    if a.unseen_views and not (a.depth_smooth_weight or a.entropy_weight or a.warp_weight):
-        ap.error("--unseen-views serves the rays of --depth-smooth-weight / --entropy-weight / --warp-weight: set one of them")
+    if a.unseen_views and not (a.depth_smooth_weight or a.entropy_weight or a.warp_weight or a.ray_kl_weight):
+        ap.error("--unseen-views serves the rays of --depth-smooth-weight / --entropy-weight / --warp-weight / --ray-kl-weight: "
+                 "set one of them")
     if a.warp_weight and not a.u8_dataset:
         ap.error("--warp-weight samples the device-resident photographs: add --u8-dataset")
-    if a.depth_smooth_weight and a.patch < 2:
-        ap.error("--depth-smooth-weight needs --patch of at least 2")
+    if (a.depth_smooth_weight or a.ray_kl_weight) and a.patch < 2:
+        ap.error("--depth-smooth-weight / --ray-kl-weight need --patch of at least 2")
+    if a.ray_kl_weight and not 1 <= a.ray_kl_bins <= 4096:
+        ap.error("--ray-kl-bins is between 1 and 4096")
     full_grad = any(w != 0.0 for w in (a.depth_weight, a.distortion_weight, a.entropy_weight, a.depth_kl_weight,
-                                       a.depth_smooth_weight, a.warp_weight))
+                                       a.depth_smooth_weight, a.warp_weight, a.ray_kl_weight))
     dev = torch.device("cuda:0")
     hwf = (a.hw, a.hw, 0.5 * a.hw / math.tan(0.5 * 0.6911112))
     near, far, step = 2.0, 6.0, 2e-2
@@ -340,6 +357,10 @@ def main():
     alpha = 1e-5
     distortion = DistortionLoss()
     ray_entropy, depth_kl, depth_smooth = RayEntropyLoss(), DepthKLLoss(), PatchDepthSmoothnessLoss()
+    ray_kl = NeighborRayKLLoss(a.ray_kl_bins, t_min=near, t_max=far)
+    # its patches: the unseen ones where they are rendered, else the photographs' (--ssim-weight / --lpips-weight), else
+    # it has the unseen orbit patches of --depth-smooth-weight rendered for itself
+    ray_kl_on_seen = bool(a.ray_kl_weight) and bool(a.ssim_weight or a.lpips_weight) and not (a.unseen_views or a.depth_smooth_weight)
     pose_gen = torch.Generator().manual_seed(4)  # the unseen poses of --depth-smooth-weight
     if a.unseen_views:
         unseen_loader = UnseenPatchLoader(UnseenViewSampler.from_poses(torch.stack(poses), a.unseen_views, device=dev), hwf,
@@ -379,7 +400,7 @@ def main():
         if a.unseen_views:  # B patches of P x P rays of B freshly drawn poses in one launch, behind the rest
             o, d, *unseen_poses = next(unseen_loader)  # (+ the poses, for the warp term's source views)
             rays_o, rays_d = torch.cat([rays_o, o]), torch.cat([rays_d, d])
-        elif a.depth_smooth_weight:  # B windows of P x P rays of one random pose between the training views, behind the rest
+        elif a.depth_smooth_weight or (a.ray_kl_weight and not ray_kl_on_seen):  # B windows of P x P rays of one random pose between the training views, behind the rest
             phi, theta = 360.0 * float(torch.rand((), generator=pose_gen)), 40.0 + 20.0 * float(torch.rand((), generator=pose_gen))
             o, d = U.get_rays(orbit_pose(phi, theta), hwf, dev)
             corner = torch.randint(0, a.hw - a.patch + 1, (a.patches, 2), generator=pose_gen)
@@ -412,6 +433,11 @@ def main():
                                                        rays_o.shape[0], target, a.depth_kl_var)
         if a.depth_smooth_weight and depth.requires_grad:
             loss = loss + a.depth_smooth_weight * depth_smooth(depth[n_seen:].view(-1, a.patch, a.patch))
+        if a.ray_kl_weight and extras is not None and extras["weights"].requires_grad:
+            first_ray = n_batch if ray_kl_on_seen else n_seen  # the patches sit behind the batch's rays
+            loss = loss + a.ray_kl_weight * ray_kl(extras["weights"], extras["t_starts"], extras["t_ends"], ray_indices,
+                                                   rays_o.shape[0], (a.patches, a.patch, a.patch), first_ray=first_ray,
+                                                   opacity=opacity)
         if a.warp_weight and depth.requires_grad:
             if a.unseen_views:  # the unseen patches, each against the training view nearest to its pose
                 rows = slice(n_seen, None)

@@ -5,7 +5,8 @@ compositor's weights (this package's own, the first consumer of `full_grad`); an
 parameter arena; and the structural (D-SSIM) and perceptual (LPIPS-VGG) terms on rendered patches (this package's own:
 the evaluation metrics of core/metrics.py with a backward); and the few-shot geometry losses on the renderer's other
 outputs (this package's own definitions of InfoNeRF's ray entropy, DS-NeRF's depth KL term and RegNeRF's patch depth
-smoothness: csrc/ray_losses.hip); and the cross-view reprojection term on nerfdata.WarpSource (depth-warp consistency:
+smoothness: csrc/ray_losses.hip; InfoNeRF's KL between neighbouring rays on per-ray depth histograms:
+csrc/ray_hist.hip); and the cross-view reprojection term on nerfdata.WarpSource (depth-warp consistency:
 csrc/warp.hip)."""
 import ctypes as C
 import math
@@ -58,8 +59,9 @@ class RayEntropyLoss:
     the rays: c_r = (opacity_r > threshold), InfoNeRF's rule - a ray that hits nothing has no distribution to sharpen;
     a masked ray, like a ray without samples, contributes 0 and gets a gradient of exactly 0.  Without `opacity` every
     ray counts.  One segmented reduction on the GPU (ops.ray_entropy), differentiable w.r.t. `values` only.
-    InfoNeRF's second term, the KL divergence between the distributions of neighbouring rays, is not built: packed
-    rays have differing sample counts, so their samples do not pair up."""
+    InfoNeRF's second term, the KL divergence between the distributions of neighbouring rays, is NeighborRayKLLoss:
+    packed rays have differing sample counts, so their samples do not pair up, and it compares the rays' histograms
+    over common depth bins instead."""
 
     def __init__(self, threshold: float = 0.1, eps: float = 1e-10, log2: bool = True):
         self.threshold, self.eps, self.log2 = float(threshold), float(eps), bool(log2)
@@ -67,6 +69,54 @@ class RayEntropyLoss:
     def __call__(self, values: Tensor, ray_indices: Tensor, n_rays: int, opacity: Optional[Tensor] = None) -> Tensor:
         c = None if opacity is None else (opacity.detach().reshape(-1) > self.threshold)
         return ops.ray_entropy(values, ray_indices, n_rays, ray_weight=c, eps=self.eps, log2=self.log2).mean()
+
+
+class NeighborRayKLLoss:
+    """KL divergence between the termination distributions of neighbouring rays (InfoNeRF's second term, its
+    "information gain reduction"; this package's OWN definition - InfoNeRF's source is absent, parity with it is
+    UNPINNED).  The occupancy march emits a different number of samples on every ray, so two rays are compared on a
+    common depth axis, not sample by sample: each ray's samples are binned into a histogram over `bins` fixed bins of
+    [t_min, t_max] (ops.ray_histogram has the definition: P_rb = sum_i max(v_i, 0) overlap_ib / dt_i / (s_r + 1e-10)),
+    and neighbouring pixels of a rendered patch are compared bin by bin (ops.patch_neighbor_kl):
+        D(p, q) = sum_b p_b (log(p_b + eps) - log(q_b + eps)),
+        out[i,j] = c_ij c_i,j+1 D(P_ij, P_i,j+1) + c_ij c_i+1,j D(P_ij, P_i+1,j)   (each where that neighbour exists).
+    The call returns sum(out) / max(number of counted pairs, 1), the count formed on the device (no host sync).
+    `patch_shape` = (B, Ph, Pw): the B Ph Pw patch rays are the rays first_ray ... of the `n_rays` (the patches ride
+    behind a ray batch: first_ray = the batch's size); the samples of every other ray get a gradient of exactly 0.
+    `opacity` (the renderer's, of the patch rays or of all n_rays; detached here) masks pixels: c = opacity > threshold,
+    RayEntropyLoss's rule; a pair with a masked pixel is skipped.  Without it every pair counts.  `values` [N]:
+    extras["alphas"] or extras["weights"] of render_rays(..., full_grad=True); t_min / t_max: the run's near / far.
+    Two launches forward, two backward, differentiable w.r.t. `values` only.  Limits: no gradient to t_starts, t_ends
+    or the bin edges; neighbours are patch-adjacent pixels only (InfoNeRF's pose-perturbed partner ray is not built:
+    render a second patch and compare two ops.ray_histogram outputs in torch); one direction of KL, InfoNeRF's; with
+    disjoint supports D reaches about -log(eps) per unit of mass and its gradient to q reaches p / eps."""
+
+    def __init__(self, bins: int = 64, *, t_min: float, t_max: float, threshold: float = 0.1, eps: float = 1e-5):
+        self.bins, self.t_min, self.t_max = ops._hist_axis("NeighborRayKLLoss", bins, t_min, t_max)
+        self.threshold, self.eps = float(threshold), float(eps)
+
+    def __call__(self, values: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor, n_rays: int, patch_shape,
+                 first_ray: int = 0, opacity: Optional[Tensor] = None) -> Tensor:
+        B, Ph, Pw = (int(s) for s in patch_shape)
+        n_pix = B * Ph * Pw
+        if min(B, Ph, Pw) < 0 or Ph < 1 or Pw < 1:
+            raise ValueError(f"NeighborRayKLLoss: patch_shape = (B, Ph, Pw) with Ph, Pw >= 1, got {tuple(patch_shape)}")
+        c = None
+        if opacity is not None:
+            c = opacity.detach().reshape(-1)
+            if c.numel() == int(n_rays) and c.numel() != n_pix:
+                c = c[first_ray:first_ray + n_pix]
+            if c.numel() != n_pix:
+                raise ValueError(f"NeighborRayKLLoss: opacity has {opacity.numel()} entries for {n_pix} patch rays "
+                                 f"(or {int(n_rays)} rays)")
+            c = (c > self.threshold).reshape(B, Ph, Pw)
+        P = ops.ray_histogram(values, t_starts, t_ends, ray_indices, n_rays, bins=self.bins, t_min=self.t_min,
+                              t_max=self.t_max, rays=(int(first_ray), n_pix))
+        out = ops.patch_neighbor_kl(P.view(B, Ph, Pw, self.bins), c, eps=self.eps)
+        if c is None:
+            return out.sum() / float(max(ops.patch_neighbor_pairs(B, Ph, Pw), 1))
+        pairs = (c[:, :, :-1] & c[:, :, 1:]).sum() + (c[:, :-1] & c[:, 1:]).sum()
+        return out.sum() / pairs.clamp(min=1).to(out.dtype)
 
 
 class DepthKLLoss:

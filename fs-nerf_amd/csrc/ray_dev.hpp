@@ -114,14 +114,15 @@ __device__ __forceinline__ void lane_range(int S, int lane, int& i0, int& i1) {
 // The per-ray skeleton of every one-wave-per-ray kernel (four rays per 256-thread block, grid = ceil(R/4)): this
 // wave's ray r, its samples [beg, beg + S) and this lane's share [i0, i1) of them (relative to beg).  ray_work()
 // returns whether the ray has samples; r >= R tells a wave past the last ray from an empty one (S == 0).  Kernels
-// that stride the lanes over the ray (i = lane; i < S; i += 64) take r, beg, S and lane from it.
+// that stride the lanes over the ray (i = lane; i < S; i += 64) take r, beg, S and lane from it.  `first`: the grid
+// covers the rays [first, R) only (a row subset: ray_hist.hip); every other kernel starts at ray 0.
 struct RayWork {
   int64_t r, beg;
   int S, lane, i0, i1;
 };
-__device__ __forceinline__ bool ray_work(const SpanArgs& sp, int64_t R, RayWork& w) {
+__device__ __forceinline__ bool ray_work(const SpanArgs& sp, int64_t R, RayWork& w, int64_t first = 0) {
   w.lane = lane_id();
-  w.r = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (the ray is the wave's: scalar)
+  w.r = first + (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (the wave's: scalar)
   w.beg = 0;
   w.S = 0;
   if (w.r < R) {

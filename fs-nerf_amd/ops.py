@@ -1314,6 +1314,118 @@ def patch_depth_smoothness(depth: Tensor) -> Tensor:
     return _PatchTVFn.apply(_f32(depth, "depth"))
 
 
+# ------------------------------------------------------------------ neighbouring-ray KL (csrc/ray_hist.hip)
+def _hist_axis(who: str, bins, t_min, t_max) -> Tuple[int, float, float]:
+    """The histogram's axis as the C-ABI takes it; what it refuses is refused here first, with a ValueError."""
+    bins, t_min, t_max = int(bins), float(t_min), float(t_max)
+    if not 1 <= bins <= 4096:
+        raise ValueError(f"{who}: 1 <= bins <= 4096, got {bins}")
+    if not (math.isfinite(t_min) and math.isfinite(t_max) and t_min < t_max):
+        raise ValueError(f"{who}: t_min < t_max, both finite, got {t_min} and {t_max}")
+    return bins, t_min, t_max
+
+
+def ray_histogram_edges(bins: int = 64, *, t_min: float, t_max: float) -> Tensor:
+    """The bins + 1 float32 edges of `ray_histogram`'s axis, as the kernels form them (fsn_ray_hist_edges: host
+    arithmetic, no GPU): h = (t_max - t_min) / bins, e_b = t_min + b h, every step rounded to float32 -> CPU tensor."""
+    bins, t_min, t_max = _hist_axis("ray_histogram_edges", bins, t_min, t_max)
+    edges = (C.c_float * (bins + 1))()
+    L.check(L.lib().fsn_ray_hist_edges(bins, t_min, t_max, edges), "fsn_ray_hist_edges")
+    return torch.tensor(list(edges), dtype=torch.float32)
+
+
+class _RayHistFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, v, t0, t1, ri, n_rays, first, count, bins, t_min, t_max, normalize, eps):
+        out = torch.empty(count, bins, device=v.device, dtype=torch.float32)
+        _launch("fsn_ray_hist_fwd", v.device, v, t0, t1, ri, v.numel(), n_rays, first, count, bins, t_min, t_max, normalize,
+                eps, out)
+        ctx.save_for_backward(v, t0, t1, ri, out)
+        ctx.args = (n_rays, first, count, bins, t_min, t_max, normalize, eps)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        v, t0, t1, ri, out = ctx.saved_tensors
+        d_v = torch.empty_like(v)
+        _launch("fsn_ray_hist_bwd", v.device, v, t0, t1, ri, v.numel(), *ctx.args, out, _f32(g, "grad"), d_v)
+        return (d_v,) + (None,) * 11
+
+
+def ray_histogram(values: Tensor, t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor, n_rays: int, *, bins: int = 64,
+                  t_min: float, t_max: float, normalize: bool = True, eps: float = 1e-10,
+                  rays: Optional[Tuple[int, int]] = None) -> Tensor:
+    """Each ray's termination histogram over `bins` fixed bins of [t_min, t_max] -> [count, bins] (fsn_ray_hist_fwd /
+    _bwd, one launch each way; this package's own definition, DESIGN 6.1 "Neighbouring-ray KL"): a ray's distribution
+    on a depth axis that all rays share, whatever their sample counts.  Float32, in this order: h = (t_max - t_min) /
+    bins, edges e_b = t_min + b h (`ray_histogram_edges`); sample i with a = t_starts_i, c = t_ends_i counts iff both
+    are finite and c - a > 0, with u_i = max(values_i, 0) (0 where it does not count);
+        H_rb = sum_i u_i max(min(c, e_{b+1}) - max(a, e_b), 0) / (c - a)    (ascending sample order, from +0)
+    and the output is P_rb = H_rb / (sum_i u_i + eps) (`normalize`) or H.  Mass outside [t_min, t_max] is dropped, so a
+    row sums to at most 1; a ray without samples gives a row of zeros.  `rays` = (first, count) computes the rows of the
+    rays first ... first + count - 1 only (the patch rays behind a ray batch); the samples of every other ray get a
+    gradient of exactly 0.  `values`: the compositor's alphas or weights.  Differentiable w.r.t. `values` only (not
+    again): negative entries get no gradient (torch.clamp's rule, passing at 0); there is NO gradient to t_starts,
+    t_ends or the edges.  Bitwise reproducible."""
+    bins, t_min, t_max = _hist_axis("ray_histogram", bins, t_min, t_max)
+    n_rays = int(n_rays)
+    first, count = (0, n_rays) if rays is None else (int(rays[0]), int(rays[1]))
+    if n_rays < 0 or first < 0 or count < 0 or first + count > n_rays:
+        raise ValueError(f"ray_histogram: rays = ({first}, {count}) are not rows of the {n_rays} rays")
+    if not eps > 0.0:
+        raise ValueError(f"ray_histogram: eps must be positive, got {eps}")
+    if not (t_starts.numel() == t_ends.numel() == ray_indices.numel() == values.numel()):
+        raise ValueError("ray_histogram: values, t_starts, t_ends and ray_indices disagree in length")
+    v = _f32(values, "values").reshape(-1)
+    t0, t1 = _f32(t_starts.detach(), "t_starts").reshape(-1), _f32(t_ends.detach(), "t_ends").reshape(-1)
+    ri = _i64(ray_indices, "ray_indices").reshape(-1)
+    return _RayHistFn.apply(v, t0, t1, ri, n_rays, first, count, bins, t_min, t_max, 1 if normalize else 0, float(eps))
+
+
+class _PatchNklFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, P, c, eps):
+        B, Ph, Pw, bins = P.shape
+        out = torch.empty(B, Ph, Pw, device=P.device, dtype=torch.float32)
+        _launch("fsn_patch_nkl_fwd", P.device, P, c, B, Ph, Pw, bins, eps, out)
+        ctx.save_for_backward(P, c)
+        ctx.eps = eps
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        P, c = ctx.saved_tensors
+        B, Ph, Pw, bins = P.shape
+        d_P = torch.empty_like(P)
+        _launch("fsn_patch_nkl_bwd", P.device, P, c, B, Ph, Pw, bins, ctx.eps, _f32(g, "grad"), d_P)
+        return d_P, None, None
+
+
+def patch_neighbor_kl(P: Tensor, pair_weight: Optional[Tensor] = None, eps: float = 1e-5) -> Tensor:
+    """KL divergence between the histograms of neighbouring pixels of rendered patches: P [B, Ph, Pw, bins] ->
+    [B, Ph, Pw] (fsn_patch_nkl_fwd / _bwd, one launch each way; core.loss.NeighborRayKLLoss has the definition): with
+    D(p, q) = sum_b p_b (log(p_b + eps) - log(q_b + eps)), out[i,j] = D(P_ij, P_i,j+1) + D(P_ij, P_i+1,j), each term
+    where that neighbour exists - every adjacent pair once, owned by its left or upper pixel.  `pair_weight`
+    [B, Ph, Pw] is a 0/1 mask, not differentiated (default: all ones): a pair with a masked pixel is skipped, value 0
+    and gradient exactly 0.  Any strides (a copy is made when needed).  Differentiable w.r.t. P (not again)."""
+    if P.dim() != 4 or min(P.shape[1:]) < 1 or P.shape[3] > 4096:
+        raise ValueError(f"patch_neighbor_kl: expected P of shape [B, Ph, Pw, bins] with Ph, Pw >= 1 and 1 <= bins <= 4096, "
+                         f"got {tuple(P.shape)}")
+    if pair_weight is not None and tuple(pair_weight.shape) != tuple(P.shape[:3]):
+        raise ValueError(f"patch_neighbor_kl: pair_weight has shape {tuple(pair_weight.shape)} for patches {tuple(P.shape[:3])}")
+    if not eps > 0.0:
+        raise ValueError(f"patch_neighbor_kl: eps must be positive, got {eps}")
+    c = None if pair_weight is None else _f32(pair_weight.detach(), "pair_weight")
+    return _PatchNklFn.apply(_f32(P, "P"), c, float(eps))
+
+
+def patch_neighbor_pairs(B: int, Ph: int, Pw: int) -> int:
+    """The number of adjacent pairs of B patches of Ph x Pw pixels: what an unmasked `patch_neighbor_kl` counts."""
+    return _size("fsn_patch_nkl_pairs", None, int(B), int(Ph), int(Pw))
+
+
 # ------------------------------------------------------------------ depth-warp sampling (csrc/warp.hip)
 class _WarpSampleFn(torch.autograd.Function):
     """colour / valid / uvz of fsn_warp_sample_fwd in one node; the backward is one fsn_warp_sample_bwd launch that

@@ -706,6 +706,59 @@ int fsn_patch_tv_fwd(const float* depth, int64_t B, int P, int Q, float* out, fs
 int fsn_patch_tv_bwd(const float* depth, int64_t B, int P, int Q, const float* d_out, float* d_depth,
                      fsn_stream_t stream);
 
+/* Neighbouring-ray KL (csrc/ray_hist.hip; this package's own definition of InfoNeRF's second term, the KL divergence
+ * between the termination distributions of neighbouring rays - DESIGN.md 6.1): packed rays have differing sample
+ * counts, so each ray's samples are first binned into a histogram over fixed bins of [t_min, t_max], and neighbouring
+ * pixels of a rendered patch are compared bin by bin.  No LDS, no atomics, every sum in a fixed order: deterministic.
+ * Each backward zeroes its output first.
+ *
+ * The axis, float32, in exactly this order: h = (t_max - t_min) / (float)bins, edge e_b = t_min + (float)b h for
+ * b = 0 ... bins.  Those float32 values ARE the edges.  t_min < t_max, both finite, and 1 <= bins <= 4096, else
+ * FSN_E_INVALID.  fsn_ray_hist_edges writes the bins + 1 edges to host memory (no GPU is touched). */
+int fsn_ray_hist_edges(int bins, float t_min, float t_max, float* edges_host);
+/* fsn_ray_hist_fwd: sorted ray_indices int64 [N]; out [n_rows, bins], row q = ray first_ray + q (the rows are a
+ * subset of the rays: 0 <= first_ray, first_ray + n_rows <= n_rays).  Sample i of ray r, a = t_starts_i, c = t_ends_i:
+ *     ok_i = a, c finite and c - a > 0;   u_i = ok_i ? max(values_i, 0) : 0
+ *     f_ib = max(min(c, e_{b+1}) - max(a, e_b), 0) / (c - a)
+ *     H_rb = sum_i u_i f_ib     in ascending sample order, from +0 (one sequential float32 sum per bin: the lanes own the
+ *                               bins and every lane walks all of the ray's samples; the samples need not be sorted)
+ *     out  = H                                   (normalize == 0)
+ *     out  = P,  P_rb = H_rb / (s_r + eps),  s_r = sum_i u_i             (normalize != 0)
+ *   Mass outside [t_min, t_max] is dropped (sum_b P_rb <= 1); a ray without samples gives a row of zeros (N == 0: out is
+ *   zeroed); n_rows == 0 returns FSN_OK without a launch.  One wave per ray. */
+int fsn_ray_hist_fwd(const float* values, const float* t_starts, const float* t_ends, const int64_t* ray_indices,
+                     int64_t N, int64_t n_rays, int64_t first_ray, int64_t n_rows, int bins, float t_min, float t_max,
+                     int normalize, float eps, float* out, fsn_stream_t stream);
+/* backward of fsn_ray_hist_fwd w.r.t. values, G = d_out [n_rows, bins], hist = the forward's output (read only when
+ * normalize != 0; may be NULL otherwise):
+ *     d u_i = sum_b G_rb f_ib                                             (normalize == 0)
+ *     d u_i = ( sum_b G_rb f_ib - sum_b G_rb P_rb ) / (s_r + eps)          (normalize != 0)
+ *     d_values[i] = d u_i  where ok_i and values_i >= 0 (torch.clamp(min=0)'s rule),  0 elsewhere
+ *   d_values [N] is zeroed first, so the samples of the rays outside the rows get exactly 0.  One wave per ray, the lanes
+ *   striding over the samples; each sums over the bins its interval can touch, in ascending order. */
+int fsn_ray_hist_bwd(const float* values, const float* t_starts, const float* t_ends, const int64_t* ray_indices,
+                     int64_t N, int64_t n_rays, int64_t first_ray, int64_t n_rows, int bins, float t_min, float t_max,
+                     int normalize, float eps, const float* hist, const float* d_out, float* d_values,
+                     fsn_stream_t stream);
+/* fsn_patch_nkl_fwd: P [B, Ph, Pw, bins] contiguous -> out [B, Ph, Pw].  With
+ *     D(p, q) = sum_b p_b ( log(p_b + eps) - log(q_b + eps) ),
+ *     out[i,j] = D(P_ij, P_i,j+1)  (j < Pw-1, the pair counted)  +  D(P_ij, P_i+1,j)  (i < Ph-1, the pair counted):
+ *   every horizontally and every vertically adjacent pair appears once, owned by its left or upper pixel.  pair_weight
+ *   [B, Ph, Pw] = c is a 0/1 mask (NULL: all ones), not differentiated; a pair is counted iff both of its pixels have
+ *   c != 0, any other pair is skipped: value 0 and gradient exactly 0.  B == 0 returns FSN_OK; Ph, Pw >= 1,
+ *   1 <= bins <= 4096, eps > 0.  One wave per pixel, the lanes striding over the bins. */
+int fsn_patch_nkl_fwd(const float* P, const float* pair_weight, int64_t B, int Ph, int Pw, int bins, float eps,
+                      float* out, fsn_stream_t stream);
+/* backward of fsn_patch_nkl_fwd w.r.t. P: d_P [B, Ph, Pw, bins], d_out [B, Ph, Pw]; with
+ *     dD/dp_b = log(p_b + eps) - log(q_b + eps) + p_b / (p_b + eps),   dD/dq_b = -p_b / (q_b + eps)
+ *   bin b of pixel (i, j) adds, in this order, its own right pair, its own down pair, the left neighbour's right pair
+ *   and the upper neighbour's down pair.  One wave per pixel, each lane writes its bins once.  No atomics. */
+int fsn_patch_nkl_bwd(const float* P, const float* pair_weight, int64_t B, int Ph, int Pw, int bins, float eps,
+                      const float* d_out, float* d_P, fsn_stream_t stream);
+/* the number of adjacent pairs of B patches of Ph x Pw pixels, B (Ph (Pw-1) + (Ph-1) Pw): what an unmasked
+ * fsn_patch_nkl_fwd counts (host arithmetic; negative: FSN_E_INVALID) */
+int64_t fsn_patch_nkl_pairs(int64_t B, int Ph, int Pw);
+
 /* ---- depth-warp sampling: a rendered ray and its depth -> the colour a training photograph shows at that 3-D point
  *                                                     (this package's own; DESIGN.md 6.1 "Depth-warp consistency")
  *                                                                                                     csrc/warp.hip
