@@ -22,14 +22,14 @@ comes from a FrameLoader (fs_nerf_amd.nerfdata).
 
 --depth-weight / --distortion-weight (both 0 by default: the loop is then the one above): few-shot regularisers on the
 renderer's other outputs through render_rays(full_grad=True) - an MSE between the rendered depth and the teacher's on
-the rays where the teacher hit something (float tables only: the uint8 photographs carry no depth), and the distortion
+the rays where the teacher hit something (with --u8-dataset the depth is an aux plane of the dataset), and the distortion
 loss of the compositor's weights (core.loss.DistortionLoss).
 
 --entropy-weight / --depth-kl-weight / --depth-smooth-weight (all 0 by default: the loop is then the one above): the
 few-shot geometry losses of core.loss, through render_rays(full_grad=True).  --entropy-weight: RayEntropyLoss on
 extras["alphas"], the rays masked by the rendered opacity (InfoNeRF's ray entropy).  --depth-kl-weight, with
 --depth-kl-var V (default 0.01): DepthKLLoss on extras["weights"] against the teacher's depth on the rays where the
-teacher hit something (DS-NeRF's depth term; float tables only, as --depth-weight).  --depth-smooth-weight:
+teacher hit something (DS-NeRF's depth term; with --u8-dataset from the aux plane, as --depth-weight).  --depth-smooth-weight:
 PatchDepthSmoothnessLoss on the rendered depth of --patches B patches of --patch P x P rays from a random orbit pose no
 photograph was taken from (RegNeRF's depth smoothness); their rays come from get_rays and ride in the same render_rays
 call, behind the ray batch and the SSIM / LPIPS patches.  --unseen-views shell|box: those patches are instead --patches
@@ -89,6 +89,16 @@ one; --learn-principal-point: off by default, since with learnable poses the pri
 the rotation.  At the end the learned K and the focal's relative error are printed.  The held-out frame and the path
 are rendered with the true focal.
 
+--mono-depth-weight W [--mono-depth-kind ssi|rank] [--mono-depth-space depth|disparity] (0 by default; needs
+--u8-dataset): a monocular depth prior.  The teacher's depth frames (their reciprocal with --mono-depth-space disparity)
+become one auxiliary plane of the RayDataset, each view multiplied and shifted by its own random affine pair, as a
+monocular estimator would deliver it, with NaN where the teacher saw background; a PatchLoader(with_aux=True) serves
+--patches patches of --patch x --patch pixels with their prior in the batch's own launch, their rays ride behind the rest
+in the ONE render_rays call, and core.loss.ScaleShiftDepthLoss (ssi: a scale-and-shift-invariant fit per patch) or
+core.loss.DepthRankingLoss (rank: only the prior's ordering) goes on their rendered depth.  With --u8-dataset the
+teacher's metric depth is an auxiliary plane as well, so --depth-weight and --depth-kl-weight take their targets from
+the aux column the RayLoader serves (with_aux=True) instead of a float table.
+
 --mark-invisible (off by default): before the first step the occupancy estimator takes every cell that fewer than
 --min-views K (default 1) training views see out of the grid for good (OccGridEstimator.mark_invisible_from_views: a
 conservative frustum / box test); no later refresh switches such a cell on.
@@ -105,8 +115,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import fs_nerf_amd  # noqa: E402,F401
 from fs_nerf_amd.core import metrics  # noqa: E402
 from fs_nerf_amd.core import models as M  # noqa: E402
-from fs_nerf_amd.core.loss import (DepthKLLoss, DistortionLoss, LPIPSLoss, NeighborRayKLLoss, PatchDepthSmoothnessLoss,  # noqa: E402
-                                   RayEntropyLoss, SSIMLoss, WarpConsistencyLoss, WeightNormRegularizer)
+from fs_nerf_amd.core.loss import (DepthKLLoss, DepthRankingLoss, DistortionLoss, LPIPSLoss, NeighborRayKLLoss,  # noqa: E402
+                                   PatchDepthSmoothnessLoss, RayEntropyLoss, ScaleShiftDepthLoss, SSIMLoss, WarpConsistencyLoss,
+                                   WeightNormRegularizer)
 from fs_nerf_amd.core.optim import FusedAdam  # noqa: E402
 from fs_nerf_amd.core.scheduler import ExponentialDecay  # noqa: E402
 from fs_nerf_amd.nerfdata import (CameraRefiner, FrameLoader, IntrinsicsRefiner, PatchLoader, RayDataset, RayLoader, UnseenPatchLoader,  # noqa: E402
@@ -180,8 +191,16 @@ def main():
                          "(core.loss.RayEntropyLoss; render_rays(full_grad=True))")
     ap.add_argument("--depth-kl-weight", type=float, default=0.0,
                     help="opt-in: weight of the depth KL term of the compositor's weights against the teacher's depth "
-                         "(core.loss.DepthKLLoss; render_rays(full_grad=True); float tables only)")
+                         "(core.loss.DepthKLLoss; render_rays(full_grad=True))")
     ap.add_argument("--depth-kl-var", type=float, default=0.01, help="with --depth-kl-weight: the variance around the teacher's depth")
+    ap.add_argument("--mono-depth-weight", type=float, default=0.0,
+                    help="opt-in: weight of a monocular-depth-prior term on the rendered depth of --patches patches of "
+                         "--patch x --patch pixels, the prior served as an aux plane by a PatchLoader(with_aux=True); needs "
+                         "--u8-dataset (core.loss.ScaleShiftDepthLoss / DepthRankingLoss; render_rays(full_grad=True))")
+    ap.add_argument("--mono-depth-kind", choices=("ssi", "rank"), default="ssi",
+                    help="with --mono-depth-weight: the scale-and-shift-invariant fit, or the ordinal ranking term")
+    ap.add_argument("--mono-depth-space", choices=("depth", "disparity"), default="depth",
+                    help="with --mono-depth-weight: the prior is an affine map of the depth, or of its reciprocal")
     ap.add_argument("--depth-smooth-weight", type=float, default=0.0,
                     help="opt-in: weight of the depth smoothness of --patches patches of --patch x --patch rays from a random "
                          "unseen orbit pose (core.loss.PatchDepthSmoothnessLoss; render_rays(full_grad=True))")
@@ -260,10 +279,10 @@ def main():
     if a.mark_invisible and a.estimator != "occgrid":
         ap.error("--mark-invisible belongs to the occupancy estimator")
     sampling_kwargs = {k: v for k, v in (("cone_angle", a.cone_angle), ("near_plane", a.near_plane)) if v != 0.0} or None
-    if a.depth_weight and a.u8_dataset:
-        ap.error("--depth-weight needs the float tables: the uint8 dataset carries no depth")
-    if a.depth_kl_weight and a.u8_dataset:
-        ap.error("--depth-kl-weight needs the float tables: the uint8 dataset carries no depth")
+    if a.mono_depth_weight and not a.u8_dataset:
+        ap.error("--mono-depth-weight takes its prior from the device-resident dataset's aux planes: add --u8-dataset")
+    if a.mono_depth_weight and a.patch < 2:
+        ap.error("--mono-depth-weight needs --patch of at least 2")
     if a.unseen_views and not (a.depth_smooth_weight or a.entropy_weight or a.warp_weight or a.ray_kl_weight):
         ap.error("--unseen-views serves the rays of --depth-smooth-weight / --entropy-weight / --warp-weight / --ray-kl-weight: "
                  "set one of them")
@@ -274,7 +293,7 @@ def main():
     if a.ray_kl_weight and not 1 <= a.ray_kl_bins <= 4096:
         ap.error("--ray-kl-bins is between 1 and 4096")
     full_grad = any(w != 0.0 for w in (a.depth_weight, a.distortion_weight, a.entropy_weight, a.depth_kl_weight,
-                                       a.depth_smooth_weight, a.warp_weight, a.ray_kl_weight))
+                                       a.depth_smooth_weight, a.warp_weight, a.ray_kl_weight, a.mono_depth_weight))
     dev = torch.device("cuda:0")
     hwf = (a.hw, a.hw, 0.5 * a.hw / math.tan(0.5 * 0.6911112))
     near, far, step = 2.0, 6.0, 2e-2
@@ -300,7 +319,18 @@ def main():
             start_poses = perturbed(true_poses, a.pose_noise_rot, a.pose_noise_trans, torch.Generator().manual_seed(5))
         # (with --refine-intrinsics the photographs are those of the true focal; the loop is told a wrong one)
         start_hwf = (hwf[0], hwf[1], hwf[2] * (1.0 + a.focal_noise / 100.0)) if a.refine_intrinsics else hwf
-        train_set = RayDataset(frames8, start_poses, start_hwf, near=near, far=far, device=dev)
+        # aux planes: the teacher's metric depth (--depth-weight / --depth-kl-weight) and, with --mono-depth-weight, the
+        # prior a monocular estimator would deliver: each view under its own affine map, NaN where nothing was hit
+        depth_frames = gd.reshape(len(poses), a.hw, a.hw, 1)
+        planes = [depth_frames]
+        if a.mono_depth_weight:
+            aff = torch.Generator().manual_seed(6)
+            scale = (0.5 + 1.5 * torch.rand(len(poses), 1, 1, 1, generator=aff)).to(dev)
+            shift = (2.0 * torch.rand(len(poses), 1, 1, 1, generator=aff) - 1.0).to(dev)
+            base = 1.0 / depth_frames if a.mono_depth_space == "disparity" else depth_frames
+            planes.append(torch.where(depth_frames > near, scale * base + shift, torch.full_like(base, float("nan"))))
+        train_set = RayDataset(frames8, start_poses, start_hwf, near=near, far=far, device=dev, aux=torch.cat(planes, dim=-1))
+        ray_aux = bool(a.depth_weight or a.depth_kl_weight)  # the batch's depth targets ride in its own launch
         cameras = CameraRefiner(train_set) if a.refine_poses else None
         intrinsics = None
         if a.refine_intrinsics:
@@ -309,8 +339,16 @@ def main():
         # (the warp term on the batch's own rays needs to know which view each came from: the loader reports the index)
         warp_own = bool(a.warp_weight) and not a.unseen_views
         train_loader = RayLoader(train_set, a.batch, shuffle=True, seed=0, cameras=cameras, intrinsics=intrinsics,
-                                 with_index=warp_own)
+                                 with_index=warp_own, with_aux=ray_aux)
         iterator = iter(train_loader)
+        if a.mono_depth_weight:
+            mono_loader = PatchLoader(train_set, a.patch, a.patches, shuffle=True, seed=2, cameras=cameras,
+                                      intrinsics=intrinsics, with_aux=True)
+            mono_iterator = iter(mono_loader)
+            if a.mono_depth_kind == "ssi":
+                mono_loss = ScaleShiftDepthLoss(space=a.mono_depth_space, threshold=0.5)
+            else:
+                mono_loss = DepthRankingLoss(prior_is_disparity=a.mono_depth_space == "disparity", threshold=0.5)
         if a.warp_weight:
             warp_source = WarpSource(train_set, cameras=cameras, intrinsics=intrinsics)
             warp_loss = WarpConsistencyLoss(a.warp_kind, threshold=0.5)
@@ -327,7 +365,7 @@ def main():
         with torch.no_grad():
             ref8 = R.to8b(R.render_frame(hwf, near, far, held_out, 1 << 20, t_est, teacher, white_bkgd=True, device=dev)[0])
         val_loader = FrameLoader(RayDataset(ref8.reshape(1, a.hw, a.hw, 3), held_out[None], hwf, near=near, far=far, device=dev))
-        del ro, rd, gt
+        del ro, rd, gt, gd
 
     model = make_model(2, dev).train()
     if a.cull_bf16:
@@ -381,13 +419,16 @@ def main():
             model.set_freq_mask(c2f_mask(3, 10, progress, dev), c2f_mask(3, 4, progress, dev))
         if a.u8_dataset:
             try:  # (run-nerf.py:236-240)
-                rays_o, rays_d, rgb_gt, *ray_index = next(iterator)
+                rays_o, rays_d, rgb_gt, *more = next(iterator)
             except StopIteration:
                 iterator = iter(train_loader)
-                rays_o, rays_d, rgb_gt, *ray_index = next(iterator)
+                rays_o, rays_d, rgb_gt, *more = next(iterator)
+            ray_index = more[:1] if warp_own else []
+            gd_batch = more[-1][:, :1] if ray_aux else None  # (aux column 0: the teacher's depth of the batch's rays)
         else:
             idx = torch.randint(0, ro.shape[0], (a.batch,), device=dev, generator=gen)
             rays_o, rays_d, rgb_gt = ro[idx], rd[idx], gt[idx]
+            gd_batch = gd[idx]
         n_batch = rays_o.shape[0]
         if a.ssim_weight or a.lpips_weight:  # the patches' rays ride in the same render_rays call, behind the ray batch
             try:
@@ -408,6 +449,14 @@ def main():
             cols = (corner[:, 1:] + torch.arange(a.patch))[:, None, :].expand(-1, a.patch, -1).to(dev)
             rays_o = torch.cat([rays_o, o[rows, cols].reshape(-1, 3)])
             rays_d = torch.cat([rays_d, d[rows, cols].reshape(-1, 3)])
+        n_geo = rays_o.shape[0]  # (the unseen patches end here)
+        if a.mono_depth_weight:  # B patches of the photographs with their prior, one launch, behind everything else
+            try:
+                mono_o, mono_d, _, mono_aux = next(mono_iterator)
+            except StopIteration:
+                mono_iterator = iter(mono_loader)
+                mono_o, mono_d, _, mono_aux = next(mono_iterator)
+            rays_o, rays_d = torch.cat([rays_o, mono_o]), torch.cat([rays_d, mono_d])
         (rgb, opacity, depth, extras), ray_indices, _ = R.render_rays(rays_o, rays_d, estimator, model, train=True,
                                                                       white_bkgd=True, render_step_size=step, device=dev,
                                                                       full_grad=full_grad, sampling_kwargs=sampling_kwargs)
@@ -419,8 +468,8 @@ def main():
             loss = loss + a.lpips_weight * lpips_loss(rgb[n_batch:n_seen].view(-1, a.patch, a.patch, 3),
                                                       patch_gt.view(-1, a.patch, a.patch, 3))
         if a.depth_weight and depth.requires_grad:  # (an all-background batch renders no samples: nothing to supervise)
-            hit = (gd[idx] > near).float()  # render_frame clamps depth to [near, far]: `near` = the teacher saw background
-            loss = loss + a.depth_weight * (hit * (depth[:n_batch] - gd[idx]) ** 2).sum() / hit.sum().clamp(min=1.0)
+            hit = (gd_batch > near).float()  # render_frame clamps depth to [near, far]: `near` = the teacher saw background
+            loss = loss + a.depth_weight * (hit * (depth[:n_batch] - gd_batch) ** 2).sum() / hit.sum().clamp(min=1.0)
         if a.distortion_weight and extras is not None and extras["weights"].requires_grad:
             loss = loss + a.distortion_weight * distortion(extras["weights"], extras["t_starts"], extras["t_ends"],
                                                            ray_indices, rays_o.shape[0])
@@ -428,11 +477,15 @@ def main():
             loss = loss + a.entropy_weight * ray_entropy(extras["alphas"], ray_indices, rays_o.shape[0], opacity=opacity)
         if a.depth_kl_weight and extras is not None and extras["weights"].requires_grad:
             target = torch.zeros(rays_o.shape[0], device=dev)  # 0: no depth known (background, the patches' rays)
-            target[:n_batch] = torch.where(gd[idx] > near, gd[idx], torch.zeros_like(gd[idx])).reshape(-1)
+            target[:n_batch] = torch.where(gd_batch > near, gd_batch, torch.zeros_like(gd_batch)).reshape(-1)
             loss = loss + a.depth_kl_weight * depth_kl(extras["weights"], extras["t_starts"], extras["t_ends"], ray_indices,
                                                        rays_o.shape[0], target, a.depth_kl_var)
         if a.depth_smooth_weight and depth.requires_grad:
-            loss = loss + a.depth_smooth_weight * depth_smooth(depth[n_seen:].view(-1, a.patch, a.patch))
+            loss = loss + a.depth_smooth_weight * depth_smooth(depth[n_seen:n_geo].view(-1, a.patch, a.patch))
+        if a.mono_depth_weight and depth.requires_grad:
+            shape = (-1, a.patch, a.patch)
+            loss = loss + a.mono_depth_weight * mono_loss(depth[n_geo:].view(shape), mono_aux[:, -1].reshape(shape),
+                                                          opacity=opacity[n_geo:].view(shape))
         if a.ray_kl_weight and extras is not None and extras["weights"].requires_grad:
             first_ray = n_batch if ray_kl_on_seen else n_seen  # the patches sit behind the batch's rays
             loss = loss + a.ray_kl_weight * ray_kl(extras["weights"], extras["t_starts"], extras["t_ends"], ray_indices,
@@ -440,7 +493,7 @@ def main():
                                                    opacity=opacity)
         if a.warp_weight and depth.requires_grad:
             if a.unseen_views:  # the unseen patches, each against the training view nearest to its pose
-                rows = slice(n_seen, None)
+                rows = slice(n_seen, n_geo)
                 src_view = warp_source.nearest_views(unseen_poses[0]).repeat_interleave(a.patch * a.patch)
             else:  # the batch's own rays, each against the view nearest to its own
                 rows = slice(0, n_batch)

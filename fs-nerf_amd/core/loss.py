@@ -161,6 +161,79 @@ class PatchDepthSmoothnessLoss:
         return per_patch.sum() / float(max(B, 1) * max((P - 1) * (Q - 1), 1))
 
 
+def _prior_weight(who: str, weight: Optional[Tensor], opacity: Optional[Tensor], threshold: Optional[float],
+                  like: Tensor) -> Optional[Tensor]:
+    """The weight of the two prior losses after the opacity mask (RayEntropyLoss's rule, the opacity detached): 0 where
+    opacity <= threshold."""
+    if threshold is None:
+        return weight
+    if opacity is None:
+        raise ValueError(f"{who}: a threshold needs the renderer's opacity")
+    keep = opacity.detach().reshape(like.shape) > threshold
+    w = torch.ones_like(like) if weight is None else weight.detach().to(like.dtype)
+    return torch.where(keep, w, torch.zeros_like(w))
+
+
+class ScaleShiftDepthLoss:
+    """Rendered depth against a monocular depth prior that is known only up to a scale and a shift per image (the
+    scale-and-shift-invariant term of MiDaS, used by MonoSDF; this package's OWN definition - parity with either is
+    UNPINNED).  Per patch of `depth`, `prior` [B, P, Q], with x = depth (space="depth") or x = 1 / max(depth, z_min)
+    ("disparity": for a prior that is an inverse depth), w the `weight` of a valid pixel (no weight: 1) and every sum in
+    float64:
+        (s, t) = argmin sum w (s x + t - p)^2 = (cov_w(x, p) / var_w(x),  mean_w(p) - s mean_w(x)),
+        L_b = sum w (s x + t - p)^2 / sum w,
+    and the call returns the sum of L_b over the non-degenerate patches divided by their number (counted on the device,
+    clamped at 1; no host sync).  A pixel is valid iff prior and depth are finite and weight > 0: put NaN in the prior
+    where nothing is known; an invalid pixel gets a gradient of exactly 0.  A patch with fewer than two valid pixels,
+    sum w <= 0 or var_w(x) <= rel_eps mean_w(x)^2 (a constant patch fixes no scale) is degenerate: value 0, gradient
+    exactly 0.  (s, t) minimise L_b, so its gradient is the partial derivative at fixed (s, t) (DESIGN 6.1 has the
+    argument); s is not constrained to be positive - return_fit=True also returns fit [B, 4] = (s, t, sum w, degenerate)
+    so that the caller can watch its sign.  With `threshold`, `opacity` [B, P, Q] (the renderer's, detached) zeroes the
+    weight where opacity <= threshold.  One launch forward, one backward (ops.ssi_depth), P * Q <= 4096; gradients go to
+    `depth` only, which must carry one itself: render_rays(..., full_grad=True).  nerfdata.PatchLoader(with_aux=True)
+    serves the prior's patches in the batch's own launch."""
+
+    def __init__(self, space: str = "depth", z_min: float = 1e-3, threshold: Optional[float] = None, rel_eps: float = 1e-10):
+        if space not in ("depth", "disparity"):
+            raise ValueError(f"ScaleShiftDepthLoss: space must be 'depth' or 'disparity', got {space!r}")
+        self.space, self.z_min, self.rel_eps = space, float(z_min), float(rel_eps)
+        self.threshold = None if threshold is None else float(threshold)
+
+    def __call__(self, depth: Tensor, prior: Tensor, weight: Optional[Tensor] = None, opacity: Optional[Tensor] = None,
+                 return_fit: bool = False):
+        w = _prior_weight("ScaleShiftDepthLoss", weight, opacity, self.threshold, depth)
+        per_patch, fit = ops.ssi_depth(depth, prior, w, inverse=self.space == "disparity", z_min=self.z_min,
+                                       rel_eps=self.rel_eps)
+        fitted = (fit[:, 3] == 0).sum().clamp(min=1).to(per_patch.dtype)
+        loss = per_patch.sum() / fitted
+        return (loss, fit) if return_fit else loss
+
+
+class DepthRankingLoss:
+    """Ordinal depth ranking against a prior whose ordering alone is trusted (SparseNeRF's local depth ranking; this
+    package's OWN, deterministic definition over ALL pairs of a patch instead of random draws - parity with SparseNeRF
+    is UNPINNED).  For `depth`, `prior` [B, P, Q]: an ordered pair (i, j) of valid pixels of one patch counts iff the
+    prior puts i nearer, p_i < p_j - prior_gap (with prior_is_disparity: p_i > p_j + prior_gap), and contributes
+        max(0, d_i - d_j + margin);
+    the call returns the sum over all counted pairs divided by max(their number, 1), counted on the device (no host
+    sync; NeighborRayKLLoss's convention).  A pixel is valid iff prior and depth are finite and `weight` > 0 (a mask
+    here; no weight: all); an invalid pixel gets a gradient of exactly 0, as does a pair whose hinge is exactly 0.  With
+    `threshold`, `opacity` [B, P, Q] (detached) masks the pixels with opacity <= threshold.  One launch forward, one
+    backward (ops.depth_rank), P * Q <= 4096 (16.8 M pair tests per patch at the cap); gradients go to `depth` only."""
+
+    def __init__(self, margin: float = 1e-4, prior_gap: float = 0.0, prior_is_disparity: bool = False,
+                 threshold: Optional[float] = None):
+        self.margin, self.prior_gap, self.prior_is_disparity = float(margin), float(prior_gap), bool(prior_is_disparity)
+        self.threshold = None if threshold is None else float(threshold)
+
+    def __call__(self, depth: Tensor, prior: Tensor, weight: Optional[Tensor] = None,
+                 opacity: Optional[Tensor] = None) -> Tensor:
+        w = _prior_weight("DepthRankingLoss", weight, opacity, self.threshold, depth)
+        per_patch, pairs = ops.depth_rank(depth, prior, w, margin=self.margin, prior_gap=self.prior_gap,
+                                          prior_is_disparity=self.prior_is_disparity)
+        return per_patch.sum() / pairs.sum().clamp(min=1).to(per_patch.dtype)
+
+
 class WarpConsistencyLoss:
     """Cross-view reprojection (the photometric warping term of GeCoNeRF, SPARF and ConsistentNeRF; this package's OWN
     definition): a rendered ray's colour against the colour that a training photograph shows at the ray's

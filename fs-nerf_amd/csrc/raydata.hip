@@ -15,6 +15,8 @@
 // colour - is written by the one write_ray_row, so a patch's rows are k_ray_batch's by construction.
 // fsn_ray_batch_k / fsn_ray_patch_batch_k serve the same batches over a camera table K = (fx, fy, cx, cy) on the device
 // (learnable intrinsics): the same two kernels, instantiated with kTable = true.
+// fsn_ray_batch_aux / fsn_ray_patch_batch_aux also serve the rows of the dataset's auxiliary float planes (depth, masks,
+// monocular priors; DESIGN 7 "Data layer"): the same two kernels again, instantiated with kAux = true.
 #include "common.hpp"
 #include "pinhole_consts.hpp"
 #include "ray_dev.hpp"
@@ -48,6 +50,14 @@ struct CamTable {
   int64_t stride;
 };
 
+// The auxiliary planes (fsn_ray_batch_aux / fsn_ray_patch_batch_aux): src [n_rays, channels] float32 words, row idx copied
+// bit for bit (as 32-bit words: a NaN keeps its payload) to row i of out [rows, channels].  kAux = false never looks at it.
+struct AuxPlanes {
+  const uint32_t* src;
+  uint32_t* out;
+  int channels;
+};
+
 // Item b of the batch in the order asked for: a flat ray index (k_ray_batch) or an anchor (k_ray_patch_batch) of [0, n).
 // false: an explicit entry outside the range, which never reaches memory.
 __device__ __forceinline__ bool batch_item(const RayBatchArgs& a, int64_t b, int64_t n, int64_t& item) {
@@ -70,10 +80,15 @@ __device__ __forceinline__ bool batch_item(const RayBatchArgs& a, int64_t b, int
 // Output row i for the flat ray index idx: the index, the ray (+ NDC) and the colour, each if asked for.  `pixel` gives
 // idx's (view, row, column) and is called only when rays are wanted: k_ray_batch's 64-bit division lives in it, and a
 // colour-only batch never pays for it.
-template <bool kTable, class Pixel>
-__device__ __forceinline__ void write_ray_row(const RayBatchArgs& a, const CamTable& cam, int64_t i, int64_t idx,
-                                              Pixel pixel) {
+template <bool kTable, bool kAux, class Pixel>
+__device__ __forceinline__ void write_ray_row(const RayBatchArgs& a, const CamTable& cam, const AuxPlanes& aux, int64_t i,
+                                              int64_t idx, Pixel pixel) {
   if (a.index) a.index[i] = idx;
+  if constexpr (kAux) {
+    const uint32_t* src = aux.src + idx * aux.channels;
+    uint32_t* dst = aux.out + i * aux.channels;
+    for (int k = 0; k < aux.channels; ++k) dst[k] = src[k];
+  }
   if (a.rays_o || a.rays_d) {
     int64_t view;
     int row, col;
@@ -109,13 +124,13 @@ __device__ __forceinline__ void write_ray_row(const RayBatchArgs& a, const CamTa
   }
 }
 
-template <bool kTable>
-__global__ void __launch_bounds__(256) k_ray_batch(RayBatchArgs a, CamTable cam) {
+template <bool kTable, bool kAux>
+__global__ void __launch_bounds__(256) k_ray_batch(RayBatchArgs a, CamTable cam, AuxPlanes aux) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.count) return;
   int64_t idx;
   if (!batch_item(a, i, a.n_rays, idx)) return;
-  write_ray_row<kTable>(a, cam, i, idx, [&](int64_t& view, int& row, int& col) {
+  write_ray_row<kTable, kAux>(a, cam, aux, i, idx, [&](int64_t& view, int& row, int& col) {
     view = idx / a.per_view;
     const int64_t pix = idx - view * a.per_view;
     row = (int)(pix / a.W);
@@ -132,8 +147,8 @@ struct RayPatchArgs {
   int P, dilation, AW, H;
 };
 
-template <bool kTable>
-__global__ void __launch_bounds__(256) k_ray_patch_batch(RayPatchArgs pa, CamTable cam) {
+template <bool kTable, bool kAux>
+__global__ void __launch_bounds__(256) k_ray_patch_batch(RayPatchArgs pa, CamTable cam, AuxPlanes aux) {
   const RayBatchArgs& a = pa.r;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t pp = (int64_t)pa.P * pa.P;
@@ -144,7 +159,7 @@ __global__ void __launch_bounds__(256) k_ray_patch_batch(RayPatchArgs pa, CamTab
   if (!batch_item(a, b, pa.n_anchors, anchor)) return;
   const int64_t v = anchor / pa.per_view_anchors, rest = anchor - v * pa.per_view_anchors;
   const int r = (int)(rest / pa.AW) + pi * pa.dilation, c = (int)(rest % pa.AW) + pj * pa.dilation;
-  write_ray_row<kTable>(a, cam, i, (v * pa.H + r) * a.W + c, [&](int64_t& view, int& row, int& col) {
+  write_ray_row<kTable, kAux>(a, cam, aux, i, (v * pa.H + r) * a.W + c, [&](int64_t& view, int& row, int& col) {
     view = v;
     row = r;
     col = c;
@@ -161,7 +176,8 @@ using namespace fsn;
 static int ray_batch_args(const char* who, const float* poses, int64_t n_views, const uint8_t* images, int H, int W, int C,
                           double focal, int ndc, double near, int white_bkgd, int order, uint64_t seed, int64_t epoch,
                           const int64_t* list, int64_t start, int64_t count, int P, int dilation, PatchLattice* lat,
-                          float* rays_o, float* rays_d, float* rgb, int64_t* index, RayBatchArgs* out) {
+                          float* rays_o, float* rays_d, float* rgb, int64_t* index, const void* aux_out,
+                          RayBatchArgs* out) {
   FSN_REQUIRE(n_views >= 0 && H > 0 && W > 0 && focal > 0, FSN_E_INVALID,
               "%s: bad geometry n=%lld H=%d W=%d focal=%g", who, (long long)n_views, H, W, focal);
   FSN_REQUIRE(C == 3 || C == 4, FSN_E_INVALID, "%s: %d channels (the images are RGB or RGBA bytes: 3 or 4)", who, C);
@@ -191,7 +207,7 @@ static int ray_batch_args(const char* who, const float* poses, int64_t n_views, 
   }
   if (count == 0) return FSN_OK;
   FSN_REQUIRE(order != FSN_RAY_ORDER_EXPLICIT || list, FSN_E_INVALID, "%s: null %s list", who, item);
-  FSN_REQUIRE(rays_o || rays_d || rgb || index, FSN_E_INVALID, "%s: null pointer for every output", who);
+  FSN_REQUIRE(rays_o || rays_d || rgb || index || aux_out, FSN_E_INVALID, "%s: null pointer for every output", who);
   RayBatchArgs& a = *out;
   a.poses = poses;
   a.images = images;
@@ -214,25 +230,33 @@ static int ray_batch_args(const char* who, const float* poses, int64_t n_views, 
   return FSN_OK;
 }
 
-// The two batch entry points and their camera-table twins share one body each: `cam` null = the stored intrinsics.
-static int ray_batch_call(const char* who, const CamTable* cam, const float* poses, int64_t n_views,
+// The two batch entry points, their camera-table twins and their aux forms share one body each: `cam` null = the stored
+// intrinsics, `aux` null (or without an output) = no auxiliary rows.
+static int ray_batch_call(const char* who, const CamTable* cam, const AuxPlanes* aux, const float* poses, int64_t n_views,
                           const uint8_t* images, int H, int W, int C, double focal, int ndc, double near, int white_bkgd,
                           int order, uint64_t seed, int64_t epoch, const int64_t* indices, int64_t start, int64_t count,
                           float* rays_o, float* rays_d, float* rgb, int64_t* index, fsn_stream_t stream) {
   RayBatchArgs a{};
   const int rc = ray_batch_args(who, poses, n_views, images, H, W, C, focal, ndc, near, white_bkgd, order, seed, epoch,
-                                indices, start, count, 0, 0, nullptr, rays_o, rays_d, rgb, index, &a);
+                                indices, start, count, 0, 0, nullptr, rays_o, rays_d, rgb, index,
+                                aux ? aux->out : nullptr, &a);
   if (rc || a.count == 0) return rc;
   const unsigned grid = (unsigned)((count + 255) / 256);
-  if (cam)
-    k_ray_batch<true><<<grid, 256, 0, as_stream(stream)>>>(a, *cam);
-  else
-    k_ray_batch<false><<<grid, 256, 0, as_stream(stream)>>>(a, CamTable{});
+  if (aux && aux->out) {
+    if (cam)
+      k_ray_batch<true, true><<<grid, 256, 0, as_stream(stream)>>>(a, *cam, *aux);
+    else
+      k_ray_batch<false, true><<<grid, 256, 0, as_stream(stream)>>>(a, CamTable{}, *aux);
+  } else if (cam) {
+    k_ray_batch<true, false><<<grid, 256, 0, as_stream(stream)>>>(a, *cam, AuxPlanes{});
+  } else {
+    k_ray_batch<false, false><<<grid, 256, 0, as_stream(stream)>>>(a, CamTable{}, AuxPlanes{});
+  }
   FSN_LAUNCH_CHECK("k_ray_batch");
   return FSN_OK;
 }
 
-static int ray_patch_batch_call(const char* who, const CamTable* cam, const float* poses, int64_t n_views,
+static int ray_patch_batch_call(const char* who, const CamTable* cam, const AuxPlanes* aux, const float* poses, int64_t n_views,
                                 const uint8_t* images, int H, int W, int C, double focal, int ndc, double near,
                                 int white_bkgd, int order, uint64_t seed, int64_t epoch, const int64_t* anchors,
                                 int64_t start, int64_t count, int P, int dilation, float* rays_o, float* rays_d, float* rgb,
@@ -240,7 +264,8 @@ static int ray_patch_batch_call(const char* who, const CamTable* cam, const floa
   RayPatchArgs pa{};
   PatchLattice lat{};
   const int rc = ray_batch_args(who, poses, n_views, images, H, W, C, focal, ndc, near, white_bkgd, order, seed, epoch,
-                                anchors, start, count, P, dilation, &lat, rays_o, rays_d, rgb, index, &pa.r);
+                                anchors, start, count, P, dilation, &lat, rays_o, rays_d, rgb, index,
+                                aux ? aux->out : nullptr, &pa.r);
   if (rc || pa.r.count == 0) return rc;
   const int64_t pp = (int64_t)P * P;
   FSN_REQUIRE(count <= ((int64_t)1 << 38) / pp, FSN_E_UNSUPPORTED, "%s: more than 2^38 rows in one call", who);
@@ -251,10 +276,16 @@ static int ray_patch_batch_call(const char* who, const CamTable* cam, const floa
   pa.AW = (int)lat.AW;
   pa.H = H;
   const unsigned grid = (unsigned)((count * pp + 255) / 256);
-  if (cam)
-    k_ray_patch_batch<true><<<grid, 256, 0, as_stream(stream)>>>(pa, *cam);
-  else
-    k_ray_patch_batch<false><<<grid, 256, 0, as_stream(stream)>>>(pa, CamTable{});
+  if (aux && aux->out) {
+    if (cam)
+      k_ray_patch_batch<true, true><<<grid, 256, 0, as_stream(stream)>>>(pa, *cam, *aux);
+    else
+      k_ray_patch_batch<false, true><<<grid, 256, 0, as_stream(stream)>>>(pa, CamTable{}, *aux);
+  } else if (cam) {
+    k_ray_patch_batch<true, false><<<grid, 256, 0, as_stream(stream)>>>(pa, *cam, AuxPlanes{});
+  } else {
+    k_ray_patch_batch<false, false><<<grid, 256, 0, as_stream(stream)>>>(pa, CamTable{}, AuxPlanes{});
+  }
   FSN_LAUNCH_CHECK("k_ray_patch_batch");
   return FSN_OK;
 }
@@ -272,7 +303,7 @@ extern "C" int fsn_ray_batch(const float* poses, int64_t n_views, const uint8_t*
                              int ndc, double near, int white_bkgd, int order, uint64_t seed, int64_t epoch,
                              const int64_t* indices, int64_t start, int64_t count, float* rays_o, float* rays_d,
                              float* rgb, int64_t* index, fsn_stream_t stream) {
-  return ray_batch_call("fsn_ray_batch", nullptr, poses, n_views, images, H, W, C, focal, ndc, near, white_bkgd, order, seed,
+  return ray_batch_call("fsn_ray_batch", nullptr, nullptr, poses, n_views, images, H, W, C, focal, ndc, near, white_bkgd, order, seed,
                         epoch, indices, start, count, rays_o, rays_d, rgb, index, stream);
 }
 
@@ -282,7 +313,7 @@ extern "C" int fsn_ray_batch_k(const float* poses, int64_t n_views, const uint8_
                                float* rays_o, float* rays_d, float* rgb, int64_t* index, fsn_stream_t stream) {
   CamTable cam;
   if (int rc = cam_table("fsn_ray_batch_k", K, k_rows, n_views, &cam)) return rc;
-  return ray_batch_call("fsn_ray_batch_k", &cam, poses, n_views, images, H, W, C, focal, ndc, near, white_bkgd, order, seed,
+  return ray_batch_call("fsn_ray_batch_k", &cam, nullptr, poses, n_views, images, H, W, C, focal, ndc, near, white_bkgd, order, seed,
                         epoch, indices, start, count, rays_o, rays_d, rgb, index, stream);
 }
 
@@ -290,7 +321,7 @@ extern "C" int fsn_ray_patch_batch(const float* poses, int64_t n_views, const ui
                                    double focal, int ndc, double near, int white_bkgd, int order, uint64_t seed,
                                    int64_t epoch, const int64_t* anchors, int64_t start, int64_t count, int P, int dilation,
                                    float* rays_o, float* rays_d, float* rgb, int64_t* index, fsn_stream_t stream) {
-  return ray_patch_batch_call("fsn_ray_patch_batch", nullptr, poses, n_views, images, H, W, C, focal, ndc, near, white_bkgd,
+  return ray_patch_batch_call("fsn_ray_patch_batch", nullptr, nullptr, poses, n_views, images, H, W, C, focal, ndc, near, white_bkgd,
                               order, seed, epoch, anchors, start, count, P, dilation, rays_o, rays_d, rgb, index, stream);
 }
 
@@ -301,8 +332,52 @@ extern "C" int fsn_ray_patch_batch_k(const float* poses, int64_t n_views, const 
                                      int64_t* index, fsn_stream_t stream) {
   CamTable cam;
   if (int rc = cam_table("fsn_ray_patch_batch_k", K, k_rows, n_views, &cam)) return rc;
-  return ray_patch_batch_call("fsn_ray_patch_batch_k", &cam, poses, n_views, images, H, W, C, focal, ndc, near, white_bkgd,
+  return ray_patch_batch_call("fsn_ray_patch_batch_k", &cam, nullptr, poses, n_views, images, H, W, C, focal, ndc, near, white_bkgd,
                               order, seed, epoch, anchors, start, count, P, dilation, rays_o, rays_d, rgb, index, stream);
+}
+
+// The camera table and the planes of the _aux entry points: K null with k_rows = 0 is the stored intrinsics (*use_cam
+// false); aux [n_rays, channels], 1 <= channels <= 4, aux_out null = no auxiliary rows.
+static int aux_call_args(const char* who, const float* K, int64_t k_rows, int64_t n_views, const float* aux,
+                         int aux_channels, float* aux_out, CamTable* cam, bool* use_cam, AuxPlanes* planes) {
+  *use_cam = !(K == nullptr && k_rows == 0);
+  if (*use_cam)
+    if (int rc = cam_table(who, K, k_rows, n_views, cam)) return rc;
+  FSN_REQUIRE(aux_channels >= 1 && aux_channels <= 4, FSN_E_INVALID, "%s: %d aux channels (1 to 4)", who, aux_channels);
+  FSN_REQUIRE(aux || !aux_out, FSN_E_INVALID, "%s: aux_out without aux planes to read", who);
+  *planes = AuxPlanes{reinterpret_cast<const uint32_t*>(aux), reinterpret_cast<uint32_t*>(aux_out), aux_channels};
+  return FSN_OK;
+}
+
+extern "C" int fsn_ray_batch_aux(const float* poses, int64_t n_views, const uint8_t* images, int H, int W, int C,
+                                 double focal, const float* K, int64_t k_rows, int ndc, double near, int white_bkgd,
+                                 int order, uint64_t seed, int64_t epoch, const int64_t* indices, int64_t start,
+                                 int64_t count, float* rays_o, float* rays_d, float* rgb, int64_t* index, const float* aux,
+                                 int aux_channels, float* aux_out, fsn_stream_t stream) {
+  CamTable cam{};
+  AuxPlanes planes{};
+  bool use_cam;
+  if (int rc = aux_call_args("fsn_ray_batch_aux", K, k_rows, n_views, aux, aux_channels, aux_out, &cam, &use_cam, &planes))
+    return rc;
+  return ray_batch_call("fsn_ray_batch_aux", use_cam ? &cam : nullptr, &planes, poses, n_views, images, H, W, C, focal, ndc,
+                        near, white_bkgd, order, seed, epoch, indices, start, count, rays_o, rays_d, rgb, index, stream);
+}
+
+extern "C" int fsn_ray_patch_batch_aux(const float* poses, int64_t n_views, const uint8_t* images, int H, int W, int C,
+                                       double focal, const float* K, int64_t k_rows, int ndc, double near, int white_bkgd,
+                                       int order, uint64_t seed, int64_t epoch, const int64_t* anchors, int64_t start,
+                                       int64_t count, int P, int dilation, float* rays_o, float* rays_d, float* rgb,
+                                       int64_t* index, const float* aux, int aux_channels, float* aux_out,
+                                       fsn_stream_t stream) {
+  CamTable cam{};
+  AuxPlanes planes{};
+  bool use_cam;
+  if (int rc = aux_call_args("fsn_ray_patch_batch_aux", K, k_rows, n_views, aux, aux_channels, aux_out, &cam, &use_cam,
+                             &planes))
+    return rc;
+  return ray_patch_batch_call("fsn_ray_patch_batch_aux", use_cam ? &cam : nullptr, &planes, poses, n_views, images, H, W, C,
+                              focal, ndc, near, white_bkgd, order, seed, epoch, anchors, start, count, P, dilation, rays_o,
+                              rays_d, rgb, index, stream);
 }
 
 extern "C" int fsn_ray_perm_host(int64_t N, uint64_t seed, int64_t epoch, int64_t start, int64_t count, int64_t* out_host) {

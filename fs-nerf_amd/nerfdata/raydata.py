@@ -8,7 +8,11 @@ fsn_ray_batch): position in the epoch -> shuffled ray index -> (view, row, colum
 colour, bit for bit what the reference's float tables hold.  There is no CPU implementation.
 
 PatchLoader (this package's own: the reference trains on single rays) serves batches of P x P pixel patches the same
-way (ops.ray_patch_batch / fsn_ray_patch_batch), for losses that need several rendered pixels at once."""
+way (ops.ray_patch_batch / fsn_ray_patch_batch), for losses that need several rendered pixels at once.
+
+Auxiliary planes (this package's own): per-pixel float targets other than colour - sparse or sensor depth, a mask, a
+monocular depth prior - kept beside the images as `dataset.aux` [n,H,W,A] float32 and served by the batch's own launch
+(`want_aux` / `with_aux`), bit for bit; NaN is the documented "nothing known here"."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -28,10 +32,11 @@ class RayDataset:
 
     len() = n*H*W rays in the reference's order (view-major, then row-major pixels); dataset[i] and
     dataset[index_tensor] -> (ray_o, ray_d, rgb), rows `i` of the reference's tables.  Attributes the reference's loops
-    read: near, far, ndc, hwf, aabb (device), poses ([n,4,4] float32 on the host, as the reference keeps them)."""
+    read: near, far, ndc, hwf, aabb (device), poses ([n,4,4] float32 on the host, as the reference keeps them).
+    aux: auxiliary planes (`set_aux`), None for a dataset without."""
 
     def __init__(self, imgs, poses, hwf: Tuple[int, int, float], *, near: float, far: float, ndc: bool = False,
-                 white_bkgd: bool = False, device=torch.device("cuda")):
+                 white_bkgd: bool = False, device=torch.device("cuda"), aux=None):
         device = U._need_gpu(device, "RayDataset")
         imgs = torch.as_tensor(imgs)
         if imgs.dtype != torch.uint8:
@@ -54,6 +59,9 @@ class RayDataset:
         self.imgs = imgs.to(device).contiguous()
         self.poses12 = self.poses[:, :3, :4].reshape(-1, 12).contiguous().to(device)
         self.device = self.imgs.device
+        self.aux: Optional[Tensor] = None
+        if aux is not None:
+            self.set_aux(aux)
         # the region of interest of the occupancy estimator (llff.py:77-86, blender.py:140)
         if self.ndc and len(self):
             _o, _d, self.aabb = U.build_rays(self.poses, self.hwf, self.device, ndc=True)  # the existing reduction;
@@ -73,6 +81,29 @@ class RayDataset:
         near, far = (0.0, 1.0) if ndc else (min_bound * 0.9, max_bound * 1.0)
         return cls(imgs, poses, hwf, near=near, far=far, ndc=ndc, white_bkgd=False, device=device)
 
+    def set_aux(self, planes) -> None:
+        """Store auxiliary planes: float32 [n,H,W,A] or [n,H,W] (numpy or tensor), 1 <= A <= 4, kept contiguous on the
+        dataset's device as `aux` [n,H,W,A] and served by batch(..., want_aux=True) and the loaders' with_aux.  Any bit
+        pattern is kept as it is, NaN and Inf included; None drops the planes."""
+        if planes is None:
+            self.aux = None
+            return
+        planes = torch.as_tensor(planes)
+        if planes.dtype != torch.float32:
+            raise TypeError(f"RayDataset: aux planes must be float32, got {planes.dtype}")
+        n, (H, W, _) = self.imgs.shape[0], self.hwf
+        if planes.dim() == 3:
+            planes = planes.unsqueeze(-1)
+        if planes.dim() != 4 or tuple(planes.shape[:3]) != (n, H, W) or not 1 <= planes.shape[3] <= 4:
+            raise ValueError(f"RayDataset: aux planes {tuple(planes.shape)} are not [{n}, {H}, {W}] or [{n}, {H}, {W}, 1 to 4]")
+        self.aux = planes.detach().to(self.device).contiguous()
+
+    def _want_aux(self, who: str) -> dict:
+        """The keywords of a batch that wants its aux rows."""
+        if self.aux is None:
+            raise ValueError(f"RayDataset.{who}: want_aux on a dataset without aux planes (set_aux)")
+        return dict(aux=self.aux, want_aux=True)
+
     # ------------------------------------------------------------------
     @property
     def n_views(self) -> int:
@@ -83,14 +114,16 @@ class RayDataset:
 
     def batch(self, order: str, *, start: int = 0, count: Optional[int] = None, seed: int = 0, epoch: int = 0,
               indices: Optional[Tensor] = None, want_rays: bool = True, want_rgb: bool = True, want_index: bool = False,
-              poses12: Optional[Tensor] = None, K: Optional[Tensor] = None):
-        """ops.ray_batch on this dataset's tensors: (rays_o, rays_d, rgb, index), None where not wanted.
+              poses12: Optional[Tensor] = None, K: Optional[Tensor] = None, want_aux: bool = False):
+        """ops.ray_batch on this dataset's tensors: (rays_o, rays_d, rgb, index), None where not wanted; with want_aux
+        a 5-tuple whose last element is the rows of the aux planes [count, A].
         poses12: other [n,12] matrices than the stored ones (CameraRefiner.poses12()); K: a camera table [1 or n, 4] in
         place of the stored intrinsics (IntrinsicsRefiner.K())."""
         H, W, focal = self.hwf
         return ops.ray_batch(self.poses12 if poses12 is None else poses12, self.imgs, H, W, focal, ndc=self.ndc, near=_NDC_NEAR, white_bkgd=self.white_bkgd,
                              order=order, seed=seed, epoch=epoch, indices=indices, start=start, count=count,
-                             want_rays=want_rays, want_rgb=want_rgb, want_index=want_index, K=K)
+                             want_rays=want_rays, want_rgb=want_rgb, want_index=want_index, K=K,
+                             **(self._want_aux("batch") if want_aux else {}))
 
     def n_anchors(self, patch: int, dilation: int = 1) -> int:
         """The number of `patch` x `patch` patches at `dilation` that fit the images: n * (H - ext + 1) * (W - ext + 1)
@@ -107,17 +140,17 @@ class RayDataset:
     def patch_batch(self, order: str, patch: int, dilation: int = 1, *, start: int = 0, count: Optional[int] = None,
                     seed: int = 0, epoch: int = 0, anchors: Optional[Tensor] = None, want_rays: bool = True,
                     want_rgb: bool = True, want_index: bool = False, poses12: Optional[Tensor] = None,
-                    K: Optional[Tensor] = None):
+                    K: Optional[Tensor] = None, want_aux: bool = False):
         """ops.ray_patch_batch on this dataset's tensors: `count` patches of `patch` x `patch` pixels from position
         `start` of `order` over the n_anchors(patch, dilation) anchors -> (rays_o, rays_d, rgb, index) of
         count * patch^2 rows, patch after patch, row-major inside a patch; None where not wanted.
-        poses12, K: as batch()."""
+        poses12, K, want_aux: as batch() (aux [count * patch^2, A])."""
         self.n_anchors(patch, dilation)
         H, W, focal = self.hwf
         return ops.ray_patch_batch(self.poses12 if poses12 is None else poses12, self.imgs, H, W, focal, patch, dilation, ndc=self.ndc, near=_NDC_NEAR,
                                    white_bkgd=self.white_bkgd, order=order, seed=seed, epoch=epoch, anchors=anchors,
                                    start=start, count=count, want_rays=want_rays, want_rgb=want_rgb, want_index=want_index,
-                                   K=K)
+                                   K=K, **(self._want_aux("patch_batch") if want_aux else {}))
 
     def __getitem__(self, idx):
         """Not the hot path (the loaders never come here): a tensor of indices costs one min / max read-back so that an
@@ -163,7 +196,7 @@ def served_rays(poses0: Tensor, cameras, intrinsics, geometry, launch):
     IntrinsicsRefiner), `poses0` the stored [n,12] poses, geometry = (H, W, focal, ndc, near) of the dataset;
     `launch(poses12, K)` is the loader's one ray_batch / ray_patch_batch call (with the index) over the matrices and the
     camera table it is handed (None: the stored ones) -> (rays_o, rays_d, rgb, index), rays_o / rays_d attached to xi
-    and phi through ONE autograd node."""
+    and phi through ONE autograd node.  A launch that serves aux rows as well returns them fifth, and so does this."""
     return _CameraRays.apply(None if cameras is None else cameras.xi, None if intrinsics is None else intrinsics.phi,
                              poses0, cameras, intrinsics, geometry, launch)
 
@@ -176,16 +209,16 @@ class _CameraRays(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xi: Optional[Tensor], phi: Optional[Tensor], poses0: Tensor, cameras, intrinsics, geometry, launch):
         K = None if intrinsics is None else intrinsics.K()
-        o, d, rgb, index = launch(None if cameras is None else cameras.poses12(), K)
+        o, d, rgb, index, *aux = launch(None if cameras is None else cameras.poses12(), K)
         ctx.save_for_backward(index, *[t for t in (xi, phi) if t is not None])
         ctx.poses0, ctx.K = poses0, K  # (K: the table of THIS batch - a later step makes a new one)
         ctx.cameras, ctx.intrinsics, ctx.geometry = cameras, intrinsics, geometry
-        ctx.mark_non_differentiable(*[t for t in (rgb, index) if t is not None])
+        ctx.mark_non_differentiable(*[t for t in (rgb, index, *aux) if t is not None])
         ctx.set_materialize_grads(False)
-        return o, d, rgb, index
+        return (o, d, rgb, index, *aux)
 
     @staticmethod
-    def backward(ctx, grad_o, grad_d, _grad_rgb, _grad_index):
+    def backward(ctx, grad_o, grad_d, _grad_rgb, _grad_index, *_grad_aux):
         index, *params = ctx.saved_tensors
         cam, intr = ctx.cameras, ctx.intrinsics
         xi = params[0] if cam is not None else None
@@ -206,8 +239,8 @@ class _CameraRays(torch.autograd.Function):
 
 class RayLoader:
     """The train loader (splitter.py:123-126: DataLoader(train_set, batch_size, shuffle=True)): every next() is ONE
-    launch returning device tensors (rays_o [B,3], rays_d [B,3], rgb [B,3]) (+ index [B] with `with_index`), no host
-    synchronisation.  Every iter() starts the next epoch under a new permutation (an abandoned iterator counts), an
+    launch returning device tensors (rays_o [B,3], rays_d [B,3], rgb [B,3]) (+ index [B] with `with_index`, then
+    + aux [B,A], the rows of the dataset's aux planes, with `with_aux`: the last element), no host synchronisation.  Every iter() starts the next epoch under a new permutation (an abandoned iterator counts), an
     epoch serves every ray exactly once, the last batch is short, then StopIteration.
 
     world > 1 (ray-batch data parallelism, shard.py): all ranks walk the same permutation; global batch g is positions
@@ -227,7 +260,7 @@ class RayLoader:
     (intrinsics_refine.py).  The NDC map and the aabb stay those of the stored focal."""
 
     def __init__(self, dataset: RayDataset, batch_size: int, shuffle: bool = True, seed: Optional[int] = None, rank: int = 0,
-                 world: int = 1, with_index: bool = False, cameras=None, intrinsics=None):
+                 world: int = 1, with_index: bool = False, cameras=None, intrinsics=None, with_aux: bool = False):
         if batch_size <= 0 or world <= 0 or not 0 <= rank < world:
             raise ValueError(f"RayLoader: bad batch_size {batch_size}, rank {rank} or world {world}")
         if cameras is not None and (cameras.n_views != dataset.n_views or cameras.poses0.device != dataset.device):
@@ -239,7 +272,9 @@ class RayLoader:
             raise ValueError(f"RayLoader: intrinsics of {intrinsics.n_views} views over hwf {intrinsics.hwf0} on "
                              f"{intrinsics.device} do not match the dataset's {dataset.n_views} views over "
                              f"{dataset.hwf} on {dataset.device}")
-        self.cameras, self.intrinsics = cameras, intrinsics
+        if with_aux and dataset.aux is None:
+            raise ValueError("RayLoader: with_aux on a dataset without aux planes (RayDataset.set_aux)")
+        self.cameras, self.intrinsics, self.with_aux = cameras, intrinsics, bool(with_aux)
         self.dataset, self.batch_size, self.shuffle = dataset, int(batch_size), bool(shuffle)
         self.seed = _seed_or_default(seed)
         self.rank, self.world, self.with_index = int(rank), int(world), bool(with_index)
@@ -259,6 +294,8 @@ class RayLoader:
         """The one launch of a next(): `count` items from position `start` of this epoch's order, over the stored
         cameras or, through the one autograd node, over the learnable ones (which always needs the index)."""
         kw = dict(start=start, count=count, seed=self.seed, epoch=epoch)
+        if self.with_aux:  # (a loader without aux makes the very call it made before the planes existed)
+            kw["want_aux"] = True
         if self.cameras is None and self.intrinsics is None:
             return self._batch(order, want_index=self.with_index, **kw)
         ds = self.dataset
@@ -298,17 +335,20 @@ class _RayIterator:
             raise StopIteration
         B, n = ld.batch_size, ld._n_items()
         start = (self.position * ld.world + ld.rank) * B
-        o, d, rgb, index = ld._serve("permuted" if ld.shuffle else "identity", start, min(B, n - start), self.epoch)
+        served = ld._serve("permuted" if ld.shuffle else "identity", start, min(B, n - start), self.epoch)
         self.position += 1
         if ld.epoch == self.epoch:  # (an iterator abandoned for a newer one no longer moves the loader's state)
             ld.position = self.position
+        if ld.with_aux:  # (o, d, rgb, index, aux)
+            return tuple(served) if ld.with_index else (served[0], served[1], served[2], served[4])
+        o, d, rgb, index = served
         return (o, d, rgb, index) if ld.with_index else (o, d, rgb)
 
 
 class PatchLoader(RayLoader):
     """RayLoader over patches, for losses that need several rendered pixels at once (core/loss.py: SSIMLoss; patch
     regularisers on depth): every next() is ONE launch (RayDataset.patch_batch) returning (rays_o, rays_d, rgb) of
-    [B * patch^2, 3] (+ index [B * patch^2] with `with_index`) for B = patches_per_batch patches of patch x patch pixels
+    [B * patch^2, 3] (+ index [B * patch^2] with `with_index`, + aux [B * patch^2, A] with `with_aux`) for B = patches_per_batch patches of patch x patch pixels
     `dilation` apart, patch after patch, so rgb.view(B, patch, patch, 3) is the patch stack.  RayLoader's contract holds
     over the ANCHORS (top-left pixels, dataset.n_anchors(patch, dilation) of them): a new permutation per iter(), every
     anchor exactly once per epoch, a short last batch, the world / rank slices, state_dict() / load_state_dict().
@@ -316,8 +356,8 @@ class PatchLoader(RayLoader):
 
     def __init__(self, dataset: RayDataset, patch: int, patches_per_batch: int, dilation: int = 1, shuffle: bool = True,
                  seed: Optional[int] = None, rank: int = 0, world: int = 1, with_index: bool = False, cameras=None,
-                 intrinsics=None):
-        super().__init__(dataset, patches_per_batch, shuffle, seed, rank, world, with_index, cameras, intrinsics)
+                 intrinsics=None, with_aux: bool = False):
+        super().__init__(dataset, patches_per_batch, shuffle, seed, rank, world, with_index, cameras, intrinsics, with_aux)
         self.patch, self.dilation = int(patch), int(dilation)
         self._anchors = dataset.n_anchors(self.patch, self.dilation)
 

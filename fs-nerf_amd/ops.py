@@ -284,9 +284,30 @@ def _row_outputs(rows: int, dev, want_rays: bool, want_rgb: bool, want_index: bo
     return o, d, rgb, index
 
 
-def _launch_cam(name: str, who: str, dev, head: tuple, K: Optional[Tensor], n_views: int, tail: tuple) -> None:
-    """`name` over the stored intrinsics, or its camera-table form `name`_k with (K, its rows) between head and tail."""
-    if K is None:
+def _aux_planes(aux: Optional[Tensor], n_views: int, H: int, W: int, rows: int, dev, who: str):
+    """The auxiliary planes of a batch that wants them, as the C-ABI takes them -> (aux, channels, aux_out [rows,
+    channels]).  aux: float32 [n, H, W, A] or [n, H, W] on the batch's GPU, contiguous, 1 <= A <= 4."""
+    if aux is None:
+        raise ValueError(f"{who}: want_aux needs the aux planes")
+    if not aux.is_cuda:
+        raise RuntimeError(f"{who}: expected GPU aux planes (the HIP path has no CPU fallback)")
+    if aux.dtype != torch.float32:
+        raise TypeError(f"{who}: aux planes are float32, got {aux.dtype}")
+    if aux.dim() not in (3, 4) or tuple(aux.shape[:3]) != (n_views, H, W) or not aux.is_contiguous():
+        raise ValueError(f"{who}: aux planes {tuple(aux.shape)} are not a contiguous [{n_views}, {H}, {W}(, A)]")
+    channels = 1 if aux.dim() == 3 else aux.shape[3]
+    if not 1 <= channels <= 4:
+        raise ValueError(f"{who}: {channels} aux channels (1 to 4)")
+    return aux, channels, torch.empty(rows, channels, device=dev, dtype=torch.float32)
+
+
+def _launch_cam(name: str, who: str, dev, head: tuple, K: Optional[Tensor], n_views: int, tail: tuple, planes=None) -> None:
+    """`name` over the stored intrinsics, or its camera-table form `name`_k with (K, its rows) between head and tail;
+    with `planes` (`_aux_planes`) its aux form `name`_aux, which takes both (no table: NULL and 0 rows)."""
+    if planes is not None:
+        table = (None, 0) if K is None else _camera_table(K, n_views, who)
+        _launch(name + "_aux", dev, *head, *table, *tail, *planes)
+    elif K is None:
         _launch(name, dev, *head, *tail)
     else:
         _launch(name + "_k", dev, *head, *_camera_table(K, n_views, who), *tail)
@@ -295,13 +316,16 @@ def _launch_cam(name: str, who: str, dev, head: tuple, K: Optional[Tensor], n_vi
 def ray_batch(poses12: Tensor, images: Tensor, H: int, W: int, focal: float, *, ndc: bool = False, near: float = 1.0,
               white_bkgd: bool = False, order: str = "identity", seed: int = 0, epoch: int = 0,
               indices: Optional[Tensor] = None, start: int = 0, count: Optional[int] = None, want_rays: bool = True,
-              want_rgb: bool = True, want_index: bool = False, K: Optional[Tensor] = None):
+              want_rgb: bool = True, want_index: bool = False, K: Optional[Tensor] = None, aux: Optional[Tensor] = None,
+              want_aux: bool = False):
     """One batch of the data layer in ONE launch (fsn_ray_batch), no host synchronisation: `count` rays from position
     `start` of `order` ("identity", "permuted" by (seed, epoch), or "explicit" = the device int64 list `indices`) over
     the rays of the resident dataset (poses12 [n,12] float32, images uint8 [n,H,W,3|4], both on the GPU) ->
     (rays_o [count,3], rays_d [count,3], rgb [count,3], index [count] int64); an output not asked for is None.
     K: a camera table (intrinsics_compose) [1 or n, 4] -> the same launch over it (fsn_ray_batch_k); `focal` then feeds
-    the NDC constants only."""
+    the NDC constants only.
+    aux, want_aux: auxiliary float planes [n,H,W,A] or [n,H,W] (1 <= A <= 4) of the dataset; with want_aux the same
+    launch (fsn_ray_batch_aux) also copies their rows, bit for bit, and a 5-tuple (..., index, aux [count, A]) comes back."""
     if not (poses12.is_cuda and images.is_cuda):
         raise RuntimeError("ray_batch: expected GPU tensors (the HIP path has no CPU fallback)")
     if images.dtype != torch.uint8 or poses12.dtype != torch.float32 or images.dim() != 4:
@@ -314,23 +338,26 @@ def ray_batch(poses12: Tensor, images: Tensor, H: int, W: int, focal: float, *, 
         raise ValueError("ray_batch: count is needed for the identity and permuted orders")
     dev = images.device
     o, d, rgb, index = _row_outputs(count, dev, want_rays, want_rgb, want_index)
+    planes = _aux_planes(aux, poses12.shape[0], int(H), int(W), count, dev, "ray_batch") if want_aux else None
     head = (poses12, poses12.shape[0], images, int(H), int(W), images.shape[3], float(focal))
     tail = (1 if ndc else 0, float(near), 1 if white_bkgd else 0, _RAY_ORDERS[order], int(seed) & 0xFFFFFFFFFFFFFFFF,
             int(epoch), indices, int(start), int(count), o, d, rgb, index)
-    _launch_cam("fsn_ray_batch", "ray_batch", dev, head, K, poses12.shape[0], tail)
-    return o, d, rgb, index
+    _launch_cam("fsn_ray_batch", "ray_batch", dev, head, K, poses12.shape[0], tail, planes)
+    return (o, d, rgb, index, planes[2]) if want_aux else (o, d, rgb, index)
 
 
 def ray_patch_batch(poses12: Tensor, images: Optional[Tensor], H: int, W: int, focal: float, patch: int, dilation: int = 1, *,
                     ndc: bool = False, near: float = 1.0, white_bkgd: bool = False, order: str = "identity", seed: int = 0,
                     epoch: int = 0, anchors: Optional[Tensor] = None, start: int = 0, count: Optional[int] = None,
-                    want_rays: bool = True, want_rgb: bool = True, want_index: bool = False, K: Optional[Tensor] = None):
+                    want_rays: bool = True, want_rgb: bool = True, want_index: bool = False, K: Optional[Tensor] = None,
+                    aux: Optional[Tensor] = None, want_aux: bool = False):
     """A batch of `patch` x `patch` pixel patches in ONE launch (fsn_ray_patch_batch), no host synchronisation: `count`
     patches from position `start` of `order` over the ANCHORS (top-left pixels) of the dataset - n * (H - ext + 1) *
     (W - ext + 1) of them, ext = (patch - 1) * dilation + 1; "explicit" = the device int64 list `anchors` ->
     (rays_o, rays_d, rgb [count * patch^2, 3], index [count * patch^2] int64), patch b in rows [b * patch^2, +patch^2),
     row-major, so rgb.view(count, patch, patch, 3) is the patch stack; an output not asked for is None.
-    images=None (with want_rgb=False): ray-only patches for any poses.  K: as ray_batch (fsn_ray_patch_batch_k)."""
+    images=None (with want_rgb=False): ray-only patches for any poses.  K: as ray_batch (fsn_ray_patch_batch_k).
+    aux, want_aux: as ray_batch (fsn_ray_patch_batch_aux): a 5-tuple with aux [count * patch^2, A] last."""
     if not (poses12.is_cuda and (images is None or images.is_cuda)):
         raise RuntimeError("ray_patch_batch: expected GPU tensors (the HIP path has no CPU fallback)")
     if poses12.dtype != torch.float32 or poses12.dim() != 2 or poses12.shape[1] != 12 or not poses12.is_contiguous():
@@ -351,11 +378,14 @@ def ray_patch_batch(poses12: Tensor, images: Optional[Tensor], H: int, W: int, f
         raise ValueError("ray_patch_batch: count is needed for the identity and permuted orders")
     dev = poses12.device
     o, d, rgb, index = _row_outputs(count * int(patch) * int(patch), dev, want_rays, want_rgb, want_index)
+    planes = None
+    if want_aux:
+        planes = _aux_planes(aux, poses12.shape[0], int(H), int(W), count * int(patch) * int(patch), dev, "ray_patch_batch")
     head = (poses12, poses12.shape[0], images, int(H), int(W), channels, float(focal))
     tail = (1 if ndc else 0, float(near), 1 if white_bkgd else 0, _RAY_ORDERS[order], int(seed) & 0xFFFFFFFFFFFFFFFF,
             int(epoch), anchors, int(start), int(count), int(patch), int(dilation), o, d, rgb, index)
-    _launch_cam("fsn_ray_patch_batch", "ray_patch_batch", dev, head, K, poses12.shape[0], tail)
-    return o, d, rgb, index
+    _launch_cam("fsn_ray_patch_batch", "ray_patch_batch", dev, head, K, poses12.shape[0], tail, planes)
+    return (o, d, rgb, index, planes[2]) if want_aux else (o, d, rgb, index)
 
 
 def ray_perm_host(n: int, seed: int, epoch: int, start: int = 0, count: Optional[int] = None) -> Tensor:
@@ -1312,6 +1342,97 @@ def patch_depth_smoothness(depth: Tensor) -> Tensor:
     if depth.dim() != 3 or depth.shape[1] < 1 or depth.shape[2] < 1:
         raise ValueError(f"patch_depth_smoothness: expected depth of shape [B, P, Q] with P, Q >= 1, got {tuple(depth.shape)}")
     return _PatchTVFn.apply(_f32(depth, "depth"))
+
+
+# ------------------------------------------------------------------ monocular depth priors (csrc/depth_prior.hip)
+def _prior_patches(who: str, depth: Tensor, prior: Tensor, weight: Optional[Tensor]):
+    """depth, prior and the optional weight of the two prior losses as the kernels read them: [B, P, Q] float32,
+    contiguous; prior and weight detached (gradients go to depth only)."""
+    if depth.dim() != 3 or depth.shape[1] < 1 or depth.shape[2] < 1:
+        raise ValueError(f"{who}: expected depth of shape [B, P, Q] with P, Q >= 1, got {tuple(depth.shape)}")
+    for t, name in ((prior, "prior"), (weight, "weight")):
+        if t is not None and tuple(t.shape) != tuple(depth.shape):
+            raise ValueError(f"{who}: {name} has shape {tuple(t.shape)} for depth {tuple(depth.shape)}")
+    return (_f32(depth, "depth"), _f32(prior.detach(), "prior"),
+            None if weight is None else _f32(weight.detach(), "weight"))
+
+
+class _SsiDepthFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, d, p, w, inverse, z_min, rel_eps):
+        B, P, Q = d.shape
+        out = torch.empty(B, device=d.device, dtype=torch.float32)
+        fit = torch.empty(B, 4, device=d.device, dtype=torch.float32)
+        fit64 = torch.empty(B, 4, device=d.device, dtype=torch.float64)  # (unrounded, for the backward's residual)
+        _launch("fsn_ssi_depth_fwd", d.device, d, p, w, B, P, Q, inverse, z_min, rel_eps, out, fit, fit64)
+        ctx.save_for_backward(d, p, w, fit64)
+        ctx.args = (inverse, z_min)
+        ctx.mark_non_differentiable(fit)
+        return out, fit
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_fit):
+        d, p, w, fit64 = ctx.saved_tensors
+        B, P, Q = d.shape
+        d_d = torch.empty_like(d)
+        _launch("fsn_ssi_depth_bwd", d.device, d, p, w, fit64, B, P, Q, *ctx.args, _f32(g, "grad").reshape(-1), d_d)
+        return d_d, None, None, None, None, None
+
+
+def ssi_depth(depth: Tensor, prior: Tensor, weight: Optional[Tensor] = None, *, inverse: bool = False, z_min: float = 1e-3,
+              rel_eps: float = 1e-10) -> Tuple[Tensor, Tensor]:
+    """Scale-and-shift-invariant fit of rendered depth patches to a prior: depth, prior, weight [B, P, Q] ->
+    (out [B], fit [B, 4]) (fsn_ssi_depth_fwd / _bwd, one launch each way; core.loss.ScaleShiftDepthLoss has the
+    definition).  Per patch x = depth or, with `inverse`, 1 / max(depth, z_min); over the VALID pixels (prior and depth
+    finite, weight > 0; no weight: 1), in float64: the weighted least-squares (s, t) of s x + t against the prior and
+    out = sum w (s x + t - p)^2 / sum w.  fit = (s, t, sum w, degenerate): a patch with fewer than two valid pixels,
+    sum w <= 0 or var(x) <= rel_eps mean(x)^2 is degenerate - value 0, gradient exactly 0, flag 1.  P * Q <= 4096.
+    Differentiable w.r.t. depth only (not again); an invalid pixel gets a gradient of exactly 0.  Any strides (a copy is
+    made when needed).  Bitwise reproducible."""
+    d, p, w = _prior_patches("ssi_depth", depth, prior, weight)
+    if inverse and not z_min > 0.0:
+        raise ValueError(f"ssi_depth: z_min must be positive in disparity space, got {z_min}")
+    if not rel_eps >= 0.0:
+        raise ValueError(f"ssi_depth: rel_eps must not be negative, got {rel_eps}")
+    return _SsiDepthFn.apply(d, p, w, 1 if inverse else 0, float(z_min), float(rel_eps))
+
+
+class _DepthRankFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, d, p, w, margin, gap, disparity):
+        B, P, Q = d.shape
+        out = torch.empty(B, device=d.device, dtype=torch.float32)
+        pairs = torch.empty(B, device=d.device, dtype=torch.int64)
+        _launch("fsn_depth_rank_fwd", d.device, d, p, w, B, P, Q, margin, gap, disparity, out, pairs)
+        ctx.save_for_backward(d, p, w)
+        ctx.args = (margin, gap, disparity)
+        ctx.mark_non_differentiable(pairs)
+        return out, pairs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_pairs):
+        d, p, w = ctx.saved_tensors
+        B, P, Q = d.shape
+        d_d = torch.empty_like(d)
+        _launch("fsn_depth_rank_bwd", d.device, d, p, w, B, P, Q, *ctx.args, _f32(g, "grad").reshape(-1), d_d)
+        return d_d, None, None, None, None, None
+
+
+def depth_rank(depth: Tensor, prior: Tensor, weight: Optional[Tensor] = None, *, margin: float = 1e-4, prior_gap: float = 0.0,
+               prior_is_disparity: bool = False) -> Tuple[Tensor, Tensor]:
+    """Ordinal ranking of rendered depth patches against a prior over ALL pairs of a patch: depth, prior, weight
+    [B, P, Q] -> (out [B], pairs [B] int64) (fsn_depth_rank_fwd / _bwd, one launch each way;
+    core.loss.DepthRankingLoss has the definition).  An ordered pair (i, j) of VALID pixels (prior and depth finite,
+    weight > 0: the weight is a mask here) counts iff the prior puts i nearer - p_i < p_j - prior_gap, or
+    p_i > p_j + prior_gap with `prior_is_disparity` - and adds max(0, d_i - d_j + margin) to out.  P * Q <= 4096.
+    Differentiable w.r.t. depth only (not again): +1 / -1 per active pair, 0 at a hinge of exactly 0 and for an invalid
+    pixel.  Any strides (a copy is made when needed).  Bitwise reproducible."""
+    d, p, w = _prior_patches("depth_rank", depth, prior, weight)
+    if not prior_gap >= 0.0:
+        raise ValueError(f"depth_rank: prior_gap must not be negative, got {prior_gap}")
+    return _DepthRankFn.apply(d, p, w, float(margin), float(prior_gap), 1 if prior_is_disparity else 0)
 
 
 # ------------------------------------------------------------------ neighbouring-ray KL (csrc/ray_hist.hip)

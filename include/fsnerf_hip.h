@@ -205,6 +205,25 @@ int fsn_ray_patch_batch_k(const float* poses, int64_t n_views, const uint8_t* im
                           const float* K, int64_t k_rows, int ndc, double near, int white_bkgd, int order, uint64_t seed,
                           int64_t epoch, const int64_t* anchors, int64_t start, int64_t count, int P, int dilation,
                           float* rays_o, float* rays_d, float* rgb, int64_t* index, fsn_stream_t stream);
+/* ---- auxiliary planes behind the data layer (this package's own; DESIGN.md 7 "Data layer")       csrc/raydata.hip
+ * Per-pixel float targets other than colour (sparse or sensor depth, masks, a monocular depth prior), served in the
+ * batch's own launch: aux DEVICE float32 [n_views*H*W, aux_channels] (1 <= aux_channels <= 4; any bit pattern, NaN is
+ * the documented "nothing known here"), aux_out DEVICE [count, aux_channels] ([count*P*P, aux_channels] for patches; may
+ * be NULL = not wanted).  Row i of aux_out is aux[idx_i*aux_channels .. idx_i*aux_channels + aux_channels) for the flat
+ * ray index idx_i of that row, copied bit for bit.  Every other argument and output is that of fsn_ray_batch_k /
+ * fsn_ray_patch_batch_k, and K == NULL with k_rows == 0 means the stored intrinsics (fsn_ray_batch / fsn_ray_patch_batch):
+ * the same kernels behind a second compile-time switch, the same rows.  An explicit index or anchor outside the range
+ * leaves its aux row untouched like every other output (recorded for fsn_debug_report("raydata") in the debug build).
+ * Errors (FSN_E_INVALID): aux_out without aux, aux_channels outside 1..4, and those of the underlying calls. */
+int fsn_ray_batch_aux(const float* poses, int64_t n_views, const uint8_t* images, int H, int W, int C, double focal,
+                      const float* K, int64_t k_rows, int ndc, double near, int white_bkgd, int order, uint64_t seed,
+                      int64_t epoch, const int64_t* indices, int64_t start, int64_t count, float* rays_o, float* rays_d,
+                      float* rgb, int64_t* index, const float* aux, int aux_channels, float* aux_out, fsn_stream_t stream);
+int fsn_ray_patch_batch_aux(const float* poses, int64_t n_views, const uint8_t* images, int H, int W, int C, double focal,
+                            const float* K, int64_t k_rows, int ndc, double near, int white_bkgd, int order, uint64_t seed,
+                            int64_t epoch, const int64_t* anchors, int64_t start, int64_t count, int P, int dilation,
+                            float* rays_o, float* rays_d, float* rgb, int64_t* index, const float* aux, int aux_channels,
+                            float* aux_out, fsn_stream_t stream);
 /* The backward of "flat ray index -> ray of the corrected pose under the camera table", reduced per view in ONE launch:
  * fsn_ray_pose_grad's walk (the other instantiation of its kernel template: one workgroup per view, no atomics, a fixed
  * summation order) with four more sums.
@@ -758,6 +777,44 @@ int fsn_patch_nkl_bwd(const float* P, const float* pair_weight, int64_t B, int P
 /* the number of adjacent pairs of B patches of Ph x Pw pixels, B (Ph (Pw-1) + (Ph-1) Pw): what an unmasked
  * fsn_patch_nkl_fwd counts (host arithmetic; negative: FSN_E_INVALID) */
 int64_t fsn_patch_nkl_pairs(int64_t B, int Ph, int Pw);
+
+/* Monocular depth priors (csrc/depth_prior.hip; this package's own definitions of the scale-and-shift-invariant depth
+ * term of MonoSDF / MiDaS and of SparseNeRF's ordinal ranking term - DESIGN.md 6.1; parity with either is unpinned).
+ * depth (the renderer's), prior and the optional weight (NULL: 1; a confidence or a mask) are [B, P, Q] float32,
+ * contiguous, 1 <= P * Q <= 4096 (larger: FSN_E_UNSUPPORTED); B == 0 returns FSN_OK without a launch; null pointers and
+ * negative sizes are FSN_E_INVALID.  A pixel is VALID iff prior and depth are finite and weight > 0; an invalid pixel
+ * contributes nothing and gets a gradient of exactly 0.  No LDS, no atomics, every sum in a fixed order: deterministic.
+ * Gradients go to depth only; each backward writes every entry of d_depth once.
+ * fsn_ssi_depth_fwd: per patch, x = depth (inverse == 0) or x = 1 / max(depth, z_min) (inverse != 0; z_min > 0), w the
+ *   weight of a valid pixel and 0 otherwise, every sum in float64:
+ *     M = sum w,  mx = sum w x / M,  mp = sum w p / M
+ *     vx = sum w (x - mx)^2 / M,  cxp = sum w (x - mx)(p - mp) / M          (a second, centred pass)
+ *     s = cxp / vx,  t = mp - s mx,   out[b] = L_b = sum w (s x + t - p)^2 / M
+ *   A patch is DEGENERATE with fewer than two valid pixels, M <= 0 or vx <= rel_eps mx^2: out[b] = 0, gradient exactly 0.
+ *   fit [B, 4] = (s, t, M, degenerate ? 1 : 0) as float32 (s, t = 0 when degenerate); s may be negative, it is not
+ *   clamped.  fit64 [B, 4] float64: the same four values unrounded, for the backward.  One wave per patch, four per
+ *   workgroup. */
+int fsn_ssi_depth_fwd(const float* depth, const float* prior, const float* weight, int64_t B, int P, int Q, int inverse,
+                      float z_min, float rel_eps, float* out, float* fit, double* fit64, fsn_stream_t stream);
+/* backward of fsn_ssi_depth_fwd w.r.t. depth.  (s, t) minimise L_b, so its total derivative is the partial at fixed
+ * (s, t):  dL_b/dx_k = 2 w_k s (s x_k + t - p_k) / M, the residual formed again (float64) from `fit64`, the forward's -
+ * near a perfect fit it cancels to nothing, and (s, t) rounded to float32 would leave it an error of 2^-24 |s x|;
+ * with inverse, times dx/ddepth = -1 / depth^2, and 0 where depth < z_min.  d_out [B]; one thread per pixel. */
+int fsn_ssi_depth_bwd(const float* depth, const float* prior, const float* weight, const double* fit64, int64_t B, int P,
+                      int Q, int inverse, float z_min, const float* d_out, float* d_depth, fsn_stream_t stream);
+/* fsn_depth_rank_fwd: ALL ordered pairs (i, j) of valid pixels of a patch instead of random draws.  The prior puts i
+ *   nearer iff p_i < p_j - prior_gap (prior_is_disparity: p_i > p_j + prior_gap), prior_gap >= 0; such a pair adds
+ *     max(0, (d_i - d_j) + margin)            (float32, in that order)
+ *   to out[b] and 1 to pairs[b] (int64 [B]).  weight acts as a mask here.  Summation: per i a float32 sum over ascending
+ *   j from +0, the rows added in float64, rounded once to out[b].  One wave per patch: the lanes stride over i and every
+ *   lane walks all j (P * Q = 4096: 16.8 M pair tests per patch). */
+int fsn_depth_rank_fwd(const float* depth, const float* prior, const float* weight, int64_t B, int P, int Q, float margin,
+                       float prior_gap, int prior_is_disparity, float* out, int64_t* pairs, fsn_stream_t stream);
+/* backward of fsn_depth_rank_fwd w.r.t. depth, gather form: pixel k walks all partners of its patch and counts +1 for
+ * every active pair (hinge > 0) in which it is the nearer pixel and -1 for every active pair in which it is the farther;
+ * d_depth[k] = d_out[b] * (float)count.  One thread per pixel. */
+int fsn_depth_rank_bwd(const float* depth, const float* prior, const float* weight, int64_t B, int P, int Q, float margin,
+                       float prior_gap, int prior_is_disparity, const float* d_out, float* d_depth, fsn_stream_t stream);
 
 /* ---- depth-warp sampling: a rendered ray and its depth -> the colour a training photograph shows at that 3-D point
  *                                                     (this package's own; DESIGN.md 6.1 "Depth-warp consistency")
