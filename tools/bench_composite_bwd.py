@@ -1,36 +1,30 @@
 #!/usr/bin/env python3
-"""Time the backward of the packed compositor at the training step's shape (4096 rays x 192 samples): the lean entry
-point (fsn_composite_packed_bwd: colours and opacity, the default training step) and the full one
+"""Time the backward of the packed compositor at the training step's shape (4096 rays x 192 samples): the lean entry point
+(fsn_composite_packed_bwd: colours and opacity, the default training step) and the full one
 (fsn_composite_packed_bwd_full) with the same two cotangents, with d_depth, with d_weights and with all six (one kernel
-behind both entry points: "lean" and "full_colors_opacity" differ in the host call only; lines recorded before the
-merge timed a separate lean kernel); and the
-distortion loss's two kernels.  Device events around the ops-level call (its two memsets and the kernel) after
-warm-ups, the variants alternated run by run, median of --iters runs.  GB/s is against the byte model: 40 B per sample
-for the lean backward (sigma, rgb, t0, t1 read; d_sigma, d_rgb written) plus 4 B per sample for each per-sample
-cotangent present; the per-ray arrays and the binary search over ray_indices are not counted.  Prints one JSON line.
+behind both entry points: "lean" and "full_colors_opacity" differ in the host call only; lines recorded before the merge
+timed a separate lean kernel); and the distortion loss's two kernels.  The timed call is the ops-level call (its two
+memsets and the kernel). Schedule: interleaved (tools/benchlib.py), one round, median and minimum in us.  GB/s is
+against the byte model: 40 B per sample for the lean backward (sigma, rgb, t0, t1 read; d_sigma, d_rgb written) plus 4 B
+per sample for each per-sample cotangent present; the per-ray arrays and the binary search over ray_indices are not
+counted.  Prints one JSON line.
 
     timeout -k 10 120 python tools/bench_composite_bwd.py [--iters 20] [--warmup 5] [--rays 4096] [--samples 192] [--tag NAME]
 """
 import argparse
-import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import benchlib
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
+    benchlib.common_args(ap, iters=20, warmup=5)
     ap.add_argument("--rays", type=int, default=4096)
     ap.add_argument("--samples", type=int, default=192)
-    ap.add_argument("--tag", default="")
     args = ap.parse_args()
     import numpy as np
     import torch
-    sys.path.insert(0, ROOT)
-    import fs_nerf_amd  # noqa: F401
+    benchlib.package()
     from fs_nerf_amd import ops
     dev = torch.device("cuda:0")
     R, S = args.rays, args.samples
@@ -61,23 +55,14 @@ def main():
     wg = ex["weights"].clone().requires_grad_(True)
     dist = ops.distortion(wg, t0, t1, ri, R)
     variants["distortion_bwd"] = (lambda: torch.autograd.grad(dist, wg, dray, retain_graph=True), 16)
-    times = {k: [] for k in variants}
-    for it in range(args.warmup + args.iters):
-        for name, (fn, _) in variants.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            if it >= args.warmup:
-                times[name].append(a.elapsed_time(b) * 1e3)
-    out = {"tool": "bench_composite_bwd", "tag": args.tag, "device": torch.cuda.get_device_name(0), "rays": R,
+    times = benchlib.interleaved({name: fn for name, (fn, _) in variants.items()}, args.iters, args.warmup, keep="samples")
+    out = {**benchlib.header("bench_composite_bwd", args.tag), "rays": R,
            "samples_per_ray": S, "iters": args.iters, "variants": {}}
     for name, (_, bps) in variants.items():
-        med = float(np.median(times[name]))
-        out["variants"][name] = {"us_median": round(med, 2), "us_min": round(float(np.min(times[name])), 2),
+        med = float(np.median(times[name])) * 1e3  # us
+        out["variants"][name] = {"us_median": round(med, 2), "us_min": round(float(np.min(times[name])) * 1e3, 2),
                                  "bytes_per_sample": bps, "gb_per_s": round(N * bps / (med * 1e-6) / 1e9, 1)}
-    print(json.dumps(out))
+    benchlib.emit(out)
 
 
 if __name__ == "__main__":

@@ -8,34 +8,24 @@
   aux_loader / index_gather   one PatchLoader next() with with_aux=True against with_index=True plus one torch gather
                               from a float table (the LLFF few-shot shape 8 x 378 x 504, --patches patches of --patch)
 
-Device events with the host path included; the variants alternate run by run, three rounds of --iters runs, the median
-of each round and the median of those.  There is no pass or fail on these times.  Appends one JSON line to
-profiles/bench_depth_prior.jsonl (--out) and prints it.
+Schedule: interleaved (tools/benchlib.py), --rounds 3 rounds, us.  There is no pass or fail on these times.  Appends one
+JSON line to profiles/bench_depth_prior.jsonl (--out) and prints it.
 
     timeout -k 10 300 python tools/bench_depth_prior.py [--iters 20] [--warmup 5] [--patches 64] [--patch 32] [--tag NAME]
 """
 import argparse
-import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import benchlib
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--rounds", type=int, default=3)
+    benchlib.common_args(ap, iters=20, warmup=5, rounds=3, out="bench_depth_prior.jsonl")
     ap.add_argument("--patches", type=int, default=64)
     ap.add_argument("--patch", type=int, default=32)
-    ap.add_argument("--tag", default="")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_depth_prior.jsonl"))
     args = ap.parse_args()
-    import numpy as np
     import torch
-    sys.path.insert(0, ROOT)
-    import fs_nerf_amd  # noqa: F401
+    benchlib.package()
     from fs_nerf_amd.core.loss import DepthRankingLoss, ScaleShiftDepthLoss
     from fs_nerf_amd.nerfdata import PatchLoader, RayDataset
     dev = torch.device("cuda:0")
@@ -95,31 +85,13 @@ def main():
     agree = {}
     for name, a, b in (("ssi", ssi(depth, prior), torch_ssi()), ("rank", rank(depth, prior), torch_rank())):
         agree[name] = abs(float(a.detach()) - float(b.detach())) / max(abs(float(b.detach())), 1e-12)
-    rounds = {k: [] for k in variants}
-    for _ in range(args.rounds):
-        times = {k: [] for k in variants}
-        for it in range(args.warmup + args.iters):
-            for name, fn in variants.items():
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                fn()
-                b.record()
-                b.synchronize()
-                if it >= args.warmup:
-                    times[name].append(a.elapsed_time(b) * 1e3)
-        for name in variants:
-            rounds[name].append(float(np.median(times[name])))
-    out = {"tool": "bench_depth_prior", "tag": args.tag, "device": torch.cuda.get_device_name(0),
+    rounds = benchlib.interleaved(variants, args.iters, args.warmup, args.rounds)
+    out = {**benchlib.header("bench_depth_prior", args.tag),
            "patches": [B, P, P], "loader_dataset": [n, H, W], "iters": args.iters, "rounds": args.rounds,
            "what": "loss forward + backward / one loader next(), device events with the host path, us",
            "relative_difference_of_the_two_spellings": agree,
-           "variants": {name: {"us_median": round(float(np.median(r)), 2), "us_rounds": [round(x, 2) for x in r]}
-                        for name, r in rounds.items()}}
-    line = json.dumps(out)
-    print(line)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "a") as f:
-        f.write(line + "\n")
+           "variants": {name: benchlib.rounds_summary(r, "us") for name, r in rounds.items()}}
+    benchlib.emit(out, args.out)
 
 
 if __name__ == "__main__":

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Fused-kernel timing for a few sampler configurations (tuning aid): ns per MLP sample evaluation."""
-import os, sys, torch
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import sys, torch
+import benchlib
+benchlib.package()
 from fs_nerf_amd import ops
 from fs_nerf_amd.core.models import NeRF
 dev = torch.device("cuda:0")
@@ -19,9 +20,7 @@ for S, NI in ((128, 0), (64, 0), (64, 128), (64, 64), (128, 256)):
     def run():
         return ops.render_fused(pc if NI else None, pf, o, d, near=2.0, far=6.0, n_samples=S, n_importance=NI,
                                 bkgd=(1, 1, 1), want_extras=False)
-    run(); torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(); run(); e1.record(); torch.cuda.synchronize()
-    t = e0.elapsed_time(e1) * 1e-3
+    run(); torch.cuda.synchronize()  # ad hoc: one warm call, one timed call
+    t = benchlib.call_ms(run)[0] * 1e-3
     evals = R * ((S if NI else 0) + S + NI)
     print(f"S={S:3d} n_imp={NI:3d}: {t*1e3:8.2f} ms  {R/t/1e6:6.3f} Mrays/s  {t/evals*1e9:6.3f} ns per MLP evaluation", flush=True)

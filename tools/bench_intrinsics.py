@@ -12,39 +12,29 @@ times these two alone; --root DIR imports the package from another tree (the par
     python tools/bench_intrinsics.py --baseline --root ../parent --tag parent
     python tools/bench_intrinsics.py --baseline --tag this
 
-in one session give the two sides; compare their difference with the spread of either side's own rounds.  Device events
-around change + batch + backward, so CALL times with the host path included; the variants alternate run by run, three
-rounds of --iters runs, the median of each round and the median of those.  There is no pass or fail on these times.
-Appends one JSON line to profiles/bench_intrinsics.jsonl (--out) and prints it.
+in one session give the two sides; compare their difference with the spread of either side's own rounds.  The timed call
+is change + batch + backward.  Schedule: interleaved (tools/benchlib.py), --rounds 3 rounds, us.  There is no pass or
+fail on these times. Appends one JSON line to profiles/bench_intrinsics.jsonl (--out) and prints it.
 
     timeout -k 10 300 python tools/bench_intrinsics.py [--iters 20] [--warmup 5] [--rays 4096] [--hw 64] [--tag NAME]
 """
 import argparse
-import json
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import benchlib
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--rounds", type=int, default=3)
+    benchlib.common_args(ap, iters=20, warmup=5, rounds=3, out="bench_intrinsics.jsonl")
     ap.add_argument("--rays", type=int, default=4096)
     ap.add_argument("--hw", type=int, default=64)
-    ap.add_argument("--tag", default="")
     ap.add_argument("--baseline", action="store_true", help="only the variants whose code the intrinsics did not change")
-    ap.add_argument("--root", default=ROOT, help="the tree to import the package (and tests/pose_refine_ref.py) from")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_intrinsics.jsonl"))
+    ap.add_argument("--root", default=benchlib.ROOT, help="the tree to import the package (and tests/pose_refine_ref.py) from")
     args = ap.parse_args()
-    import numpy as np
     import torch
-    root = os.path.abspath(args.root)
-    sys.path.insert(0, root)
-    sys.path.insert(0, os.path.join(root, "tests"))
-    import fs_nerf_amd  # noqa: F401
+    sys.path.insert(0, os.path.join(benchlib.package(args.root), "tests"))
     from fs_nerf_amd import nerfdata
     from fs_nerf_amd.nerfdata import CameraRefiner, RayDataset, RayLoader
     import pose_refine_ref as PR  # the fixtures' poses
@@ -151,30 +141,12 @@ def main():
 
     cases = {f"{'ndc' if ndc else 'world'}_{n}views": case(n, ndc) for n in (8, 100) for ndc in (False, True)}
     variants = {f"{c}_{which}": fn for c, fns in cases.items() for which, fn in fns.items()}
-    rounds = {k: [] for k in variants}
-    for _ in range(args.rounds):
-        times = {k: [] for k in variants}
-        for it in range(args.warmup + args.iters):
-            for name, fn in variants.items():
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                fn()
-                b.record()
-                b.synchronize()
-                if it >= args.warmup:
-                    times[name].append(a.elapsed_time(b) * 1e3)
-        for name in variants:
-            rounds[name].append(float(np.median(times[name])))
-    out = {"tool": "bench_intrinsics", "tag": args.tag, "device": torch.cuda.get_device_name(0), "rays": B,
+    rounds = benchlib.interleaved(variants, args.iters, args.warmup, args.rounds)
+    out = {**benchlib.header("bench_intrinsics", args.tag), "rays": B,
            "image": [H, W], "iters": args.iters, "rounds": args.rounds, "baseline_only": bool(args.baseline),
            "what": "change of phi (xi) + batch + backward to dL/dphi (dL/dxi), device events, us",
-           "variants": {name: {"us_median": round(float(np.median(r)), 2), "us_rounds": [round(x, 2) for x in r]}
-                        for name, r in rounds.items()}}
-    line = json.dumps(out)
-    print(line)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "a") as f:
-        f.write(line + "\n")
+           "variants": {name: benchlib.rounds_summary(r, "us") for name, r in rounds.items()}}
+    benchlib.emit(out, args.out)
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""What OccGridEstimator.mark_invisible_cells / mark_invisible_from_views costs and what it saves, from device events
-after a warm-up, medians of runs alternated in one process (the method of tools/bench_refresh.py / bench_march.py).
+"""What OccGridEstimator.mark_invisible_cells / mark_invisible_from_views costs and what it saves.  Schedule: interleaved
+(tools/benchlib.py), one round, median / min / p90 in ms.
 Appends one JSON line per section to profiles/bench_invisible.jsonl:
 
   visibility   the visibility kernel alone (ops.occgrid_visibility): 128^3 cells at 1 and 4 levels, 3 and 100 cameras
@@ -18,17 +18,15 @@ Run it under a time limit of its own:
     timeout -k 10 540 python tools/bench_invisible.py [--iters 20] [--warmup 3] [--sections visibility,refresh,effect]
 """
 import argparse
-import json
 import math
-import os
-import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import fs_nerf_amd  # noqa: E402,F401
+import benchlib
+from benchlib import stats
+
+benchlib.package()
 from fs_nerf_amd import ops  # noqa: E402
 from fs_nerf_amd.core.models import NeRF  # noqa: E402
 from fs_nerf_amd.core.optim import FusedAdam  # noqa: E402
@@ -38,30 +36,6 @@ from fs_nerf_amd.utils import utilities as U  # noqa: E402
 
 AABB = [-1.5, -1.5, -1.5, 1.5, 1.5, 1.5]
 RES, STEP = 128, 5e-3
-
-
-def stats(t):
-    return {"median": round(float(np.median(t)), 4), "min": round(float(np.min(t)), 4), "p90": round(float(np.percentile(t, 90)), 4)}
-
-
-def timed(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b)
-
-
-def alternate(variants, iters, warmup):
-    """{name: fn} -> {name: [ms]}: the variants alternated run by run, so that clock and thermal drift hit all alike."""
-    times = {name: [] for name in variants}
-    for it in range(warmup + iters):
-        for name, fn in variants.items():
-            t = timed(fn)
-            if it >= warmup:
-                times[name].append(t)
-    return times
 
 
 def orbit_pose(phi_deg, theta_deg=50.0, radius=4.0311289):
@@ -116,7 +90,7 @@ def bench_visibility(dev, args):
         for n in (3, 100):
             cams, hw = random_cams(n, dev)
             variants[f"cams{n}"] = (lambda c=cams, h=hw: ops.occgrid_visibility(AABB, RES, levels, c, h, h, 0.0, 1, vis))
-        times = alternate(variants, args.iters, args.warmup)
+        times = benchlib.interleaved(variants, args.iters, args.warmup, keep="samples")
         out[f"levels{levels}"] = {k + "_ms": stats(t) for k, t in times.items()}
     return out
 
@@ -134,8 +108,8 @@ def bench_refresh(dev, args):
                     "marked": make_est(dev, AABB, levels)}
             ests["marked"].mark_invisible_from_views(poses, hwf, min_views=1)
             for phase, step in (("warmup", 0), ("steady", 256)):
-                times = alternate({k: (lambda e=e: e.update_every_n_steps(step, fn, occ_thre=1e-2)) for k, e in ests.items()},
-                                  args.iters, args.warmup)
+                times = benchlib.interleaved({k: (lambda e=e: e.update_every_n_steps(step, fn, occ_thre=1e-2)) for k, e in ests.items()},
+                                             args.iters, args.warmup, keep="samples")
                 med = {k: float(np.median(t)) for k, t in times.items()}
                 out[f"levels{levels}_{route}_{phase}"] = {
                     **{k + "_ms": stats(t) for k, t in times.items()},
@@ -180,7 +154,7 @@ def bench_effect(dev, args):
             opt.step()
             opt.zero_grad()
 
-        times = alternate({k: (lambda e=e: train_step(e)) for k, e in ests.items()}, args.iters, args.warmup)
+        times = benchlib.interleaved({k: (lambda e=e: train_step(e)) for k, e in ests.items()}, args.iters, args.warmup, keep="samples")
         for k, t in times.items():
             res[k]["train_step_ms"] = stats(t)
         out[scene] = {"aabb": [round(v, 4) for v in aabb], "levels": levels, "views": int(poses.shape[0]), **res}
@@ -189,19 +163,14 @@ def bench_effect(dev, args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    benchlib.common_args(ap, iters=20, warmup=3, tag=False, out="bench_invisible.jsonl")
     ap.add_argument("--sections", default="visibility,refresh,effect")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_invisible.jsonl"))
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     sections = {"visibility": bench_visibility, "refresh": bench_refresh, "effect": bench_effect}
     for name in args.sections.split(","):
-        line = json.dumps({"tool": "bench_invisible", "section": name, "device": torch.cuda.get_device_name(0), "resolution": RES,
-                           "iters": args.iters, "result": sections[name](dev, args)})
-        print(line, flush=True)
-        with open(args.out, "a") as f:
-            f.write(line + "\n")
+        benchlib.emit({"tool": "bench_invisible", "section": name, "device": torch.cuda.get_device_name(0), "resolution": RES,
+                       "iters": args.iters, "result": sections[name](dev, args)}, args.out)
 
 
 if __name__ == "__main__":

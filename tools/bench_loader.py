@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Time the feed of the training loop: what it costs to get one batch (rays_o, rays_d, rgb) of B rays, and what the
-`train-occ` loop body costs when it is fed each way.  Device events after a warm-up, variants alternated batch by batch
-in one process; B in {1024, 4096, 32768}; two datasets generated from a seed: the LLFF few-shot shape 8x378x504x3 and
-the full Blender shape 100x800x800x4 (256 MB of bytes; its float tables are 2.3 GB).
+`train-occ` loop body costs when it is fed each way.  Schedule: interleaved (tools/benchlib.py), one round, median / min
+/ p90 in ms; B in {1024, 4096, 32768}; two datasets generated from a seed: the LLFF few-shot shape 8x378x504x3 and the
+full Blender shape 100x800x800x4 (256 MB of bytes; its float tables are 2.3 GB).
 
   loader          one RayLoader batch (fs_nerf_amd.nerfdata: uint8 images resident, one fsn_ray_batch launch)
   tables          the feed of examples/train_synthetic.py without --u8-dataset: torch.randint + three gathers from float
@@ -25,6 +25,7 @@ Run it under a time limit of its own:
     timeout -k 10 600 python tools/bench_loader.py [--iters 50] [--warmup 5] [--steps 48] [--tag NAME] [--skip-blender]
 """
 import argparse
+import itertools
 import json
 import math
 import os
@@ -32,10 +33,11 @@ import subprocess
 import sys
 import time
 
+import benchlib
+
 BATCHES = (1024, 4096, 32768)
 LLFF = (8, 378, 504, 3, 407.6)
 BLENDER = (100, 800, 800, 4, 0.5 * 800 / math.tan(0.5 * 0.6911112))
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ------------------------------------------------------------------ the child: CPU only
@@ -68,19 +70,7 @@ def cpu_child(seconds: float) -> None:
 
 # ------------------------------------------------------------------ the parent: GPU
 def stats(t):
-    import numpy as np
-    if not t:
-        return None
-    return {"median": round(float(np.median(t)), 4), "min": round(float(np.min(t)), 4), "p90": round(float(np.percentile(t, 90)), 4)}
-
-
-def timed(torch, fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b)
+    return benchlib.stats(t) if t else None
 
 
 def orbit_pose(torch, phi_deg):
@@ -131,12 +121,7 @@ def bench_feed(torch, U, nerfdata, dev, shape, args):
                     state["it"] = iter(loader)
                     return next(state["it"])
             variants.append(("loader", from_loader))
-        times = {name: [] for name, _ in variants}
-        for it in range(args.warmup + args.iters):
-            for name, fn in variants:  # alternated: clock and thermal drift hit every variant alike
-                t = timed(torch, fn)
-                if it >= args.warmup:
-                    times[name].append(t)
+        times = benchlib.interleaved(dict(variants), args.iters, args.warmup, keep="samples")
         res[f"B{B}"] = {"tables_ms": stats(times["tables"]), "loader_ms": stats(times.get("loader"))}
     return res
 
@@ -210,15 +195,12 @@ def bench_step(torch, U, nerfdata, dev, args):
     if ds is not None:
         variants.append(("step_loader", make("loader")))
     variants.append(("step_tables_b", make("tables")))
-    times = {name: [] for name, _ in variants}
     import gc
     gc.collect()
     gc.disable()
-    for it in range(args.warmup + args.steps):
-        for name, fn in variants:
-            t = timed(torch, lambda: fn(it))
-            if it >= args.warmup:
-                times[name].append(t)
+    # every step takes its own iteration number (the shadow estimator's refresh period counts it)
+    times = benchlib.interleaved({name: (lambda fn=fn, it=itertools.count(): fn(next(it))) for name, fn in variants},
+                                 args.steps, args.warmup, keep="samples")
     gc.enable()
     import numpy as np
     out = {name + "_ms": stats(t) for name, t in times.items()}
@@ -241,13 +223,11 @@ def bench_step(torch, U, nerfdata, dev, args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=5)
+    benchlib.common_args(ap, iters=50, warmup=5)
     ap.add_argument("--steps", type=int, default=48, help="timed steps per variant of the train-occ body (a multiple of 16: whole refresh periods)")
     ap.add_argument("--cpu-seconds", type=float, default=6.0)
     ap.add_argument("--skip-blender", action="store_true")
     ap.add_argument("--skip-cpu", action="store_true")
-    ap.add_argument("--tag", default="")
     ap.add_argument("--cpu-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_child:
@@ -261,22 +241,21 @@ def main():
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("CPU_DATALOADER ")]
         cpu = json.loads(lines[-1][len("CPU_DATALOADER "):]) if r.returncode == 0 and lines else {"error": (r.stdout + r.stderr)[-500:]}
     import torch
-    sys.path.insert(0, ROOT)
-    import fs_nerf_amd  # noqa: F401
+    benchlib.package()
     from fs_nerf_amd.utils import utilities as U
     try:
         from fs_nerf_amd import nerfdata
     except ImportError:
         nerfdata = None
     dev = torch.device("cuda:0")
-    out = {"tool": "bench_loader", "tag": args.tag, "device": torch.cuda.get_device_name(0), "has_loader": nerfdata is not None,
+    out = {**benchlib.header("bench_loader", args.tag), "has_loader": nerfdata is not None,
            "iters": args.iters, "cpu_dataloader_llff": cpu, "feed": {}}
     shapes = [("llff_8x378x504x3", LLFF)] + ([] if args.skip_blender else [("blender_100x800x800x4", BLENDER)])
     for name, shape in shapes:
         out["feed"][name] = bench_feed(torch, U, nerfdata, dev, shape, args)
         torch.cuda.empty_cache()
     out["train_occ_step_8x800x800"] = bench_step(torch, U, nerfdata, dev, args)
-    print(json.dumps(out))
+    benchlib.emit(out)
 
 
 if __name__ == "__main__":

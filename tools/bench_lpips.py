@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Time fs_nerf_amd.core.metrics.LPIPS (VGG16, csrc/lpips.hip) with device events: median of --iters calls at 800x800
+"""Time fs_nerf_amd.core.metrics.LPIPS (VGG16, csrc/lpips.hip; schedule: in turns, tools/benchlib.py, one variant and one
+round at a time, warm-up 3): median of --iters calls at 800x800
 and 378x504, one pair and eight pairs.  Prints ms per pair and the achieved TFLOP/s of the convolutions (2 * pixels *
 Cout * 9 * Cin summed over the 13 layers and both images; 391.6 GFLOP per 800x800 image).  Random weights in the
 package's layout (timing does not depend on their values).
@@ -7,33 +8,22 @@ package's layout (timing does not depend on their values).
     python tools/bench_lpips.py [--n 1 8] [--iters 50]
 """
 import argparse
-import json
 import os
 import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import fs_nerf_amd  # noqa: E402,F401
+import benchlib
+
+sys.path.insert(0, os.path.join(benchlib.package(), "tests"))
 from fs_nerf_amd.core import metrics  # noqa: E402
 import lpips_ref as LR  # noqa: E402
 
 
 def device_ms(fn, iters, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
+    """(median, min) of the in-turns schedule's samples for one variant."""
+    times = benchlib.in_turns({"fn": fn}, iters, warmup, keep="samples")["fn"]
     return float(np.median(times)), float(np.min(times))
 
 
@@ -51,7 +41,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--sizes", type=str, nargs="+", default=["800x800", "378x504"])
-    ap.add_argument("--iters", type=int, default=50)
+    benchlib.common_args(ap, iters=50, tag=False)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     m = metrics.LPIPS()
@@ -66,9 +56,9 @@ def main():
             with torch.no_grad():
                 med, mn = device_ms(lambda: m(x, y, normalize=True), a.iters)
             flop = 2 * n * conv_flop(H, W)
-            print(json.dumps({"hw": f"{H}x{W}", "pairs": n, "ms": round(med, 3), "ms_min": round(mn, 3),
-                              "ms_per_pair": round(med / n, 3), "conv_gflop_per_image": round(conv_flop(H, W) / 1e9, 1),
-                              "tflops": round(flop / (med * 1e-3) / 1e12, 1)}), flush=True)
+            benchlib.emit({"hw": f"{H}x{W}", "pairs": n, "ms": round(med, 3), "ms_min": round(mn, 3),
+                           "ms_per_pair": round(med / n, 3), "conv_gflop_per_image": round(conv_flop(H, W) / 1e9, 1),
+                           "tflops": round(flop / (med * 1e-3) / 1e12, 1)})
 
 
 if __name__ == "__main__":

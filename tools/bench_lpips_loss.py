@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Time the LPIPS loss on the GPU (device events around work that ends in a synchronise):
+"""Time the LPIPS loss on the GPU.  Schedule: in turns (tools/benchlib.py), warm-up 3, ms:
 
 * forward + backward of core.loss.LPIPSLoss (gradient to the first input) on 64 patches of 32x32, 16 patches of 64x64
   and one 800x800 pair, against the same network written with F.conv2d / F.max_pool2d and torch autograd in float32 -
-  what a user would otherwise build next to the package's own VGG16.  The two alternate within one process, three
-  rounds, medians of the rounds' medians; the largest gradient difference between them is reported next to the times.
+  what a user would otherwise build next to the package's own VGG16.  Medians of the --rounds 3 rounds'
+  medians; the largest gradient difference between them is reported next to the times.
 * the evaluation forward (metrics.LPIPS under no_grad) on the 800x800 pair; with --parent-lib LIB (a libfsnerf_hip.so
   built from the parent commit) a child process times the same call through that library, the two processes taking
   turns, to show that the metric's path did not slow down.  Without it that line says "not measured".
@@ -14,42 +14,23 @@
 import argparse
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import fs_nerf_amd  # noqa: E402,F401
+import benchlib
+
+sys.path.insert(0, os.path.join(benchlib.package(), "tests"))
 import lpips_ref as LR  # noqa: E402
 from fs_nerf_amd.core import metrics  # noqa: E402
 from fs_nerf_amd.core.loss import LPIPSLoss  # noqa: E402
 
 
-def device_ms(fn, iters, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
-    return float(np.median(times))
-
-
 def alternate(fns, iters, rounds):
-    per = {k: [] for k in fns}
-    for _ in range(rounds):
-        for k, fn in fns.items():
-            per[k].append(device_ms(fn, iters))
+    """{name: median over rounds of the round's median ms} and the rounds themselves; schedule: in turns, warm-up 3."""
+    per = benchlib.in_turns(fns, iters, 3, rounds)
     return {k: float(np.median(v)) for k, v in per.items()}, {k: [round(t, 4) for t in v] for k, v in per.items()}
 
 
@@ -94,16 +75,14 @@ def eval_forward_ms(iters):
     def run():
         with torch.no_grad():
             net(x, y, normalize=True)
-    return device_ms(run, iters)
+    return benchlib.in_turns({"eval": run}, iters, 3)["eval"][0]
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--rounds", type=int, default=3)
+    benchlib.common_args(ap, iters=20, rounds=3, tag=False, out="bench_lpips_loss.jsonl")
     ap.add_argument("--parent-lib", default=None, help="libfsnerf_hip.so of the parent commit (evaluation-forward comparison)")
     ap.add_argument("--eval-forward-only", action="store_true", help="(child mode) print the evaluation forward's ms and exit")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_lpips_loss.jsonl"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_lpips_loss: needs the GPU (a CPU run measures nothing)")
@@ -141,7 +120,7 @@ def main():
                       "pairs_per_pass": metrics.lpips_pairs_per_pass(shape[2], shape[3], True, False, loss_fn.max_workspace_bytes),
                       "max_abs_grad_difference_conv2d_f32_vs_hip": float((g_hip - g_conv).abs().max()),
                       "max_abs_grad_hip": float(g_hip.abs().max())})
-        print(json.dumps(lines[-1]), flush=True)
+        benchlib.emit(lines[-1])
         del x, y, g_hip, g_conv
         torch.cuda.empty_cache()
 
@@ -156,18 +135,15 @@ def main():
                     env["FSN_LIB_PATH"], env["FSN_LIB_PARTIAL"] = os.path.abspath(lib), "1"
                 else:
                     env.pop("FSN_LIB_PATH", None)
-                out = subprocess.run([sys.executable, os.path.abspath(__file__), "--eval-forward-only", "--iters", str(a.iters)],
-                                     capture_output=True, text=True, env=env, cwd=ROOT, timeout=600)
-                if out.returncode != 0:
-                    raise SystemExit("bench_lpips_loss: the child failed:\n" + out.stdout[-2000:] + out.stderr[-2000:])
-                ms = [ln for ln in out.stdout.splitlines() if ln.startswith("EVAL_FORWARD_MS ")][-1]
-                per[key].append(json.loads(ms[len("EVAL_FORWARD_MS "):]))
+                per[key].append(benchlib.run_child(
+                    [sys.executable, os.path.abspath(__file__), "--eval-forward-only", "--iters", str(a.iters)], env, 600,
+                    "bench_lpips_loss: the evaluation-forward child", "EVAL_FORWARD_MS "))
         line.update({k: round(float(np.median(v)), 4) for k, v in per.items()})
         line["rounds"] = {k: [round(t, 4) for t in v] for k, v in per.items()}
     else:
         line.update({"this_commit_ms": round(eval_forward_ms(a.iters), 4), "parent_commit_ms": "not measured"})
     lines.append(line)
-    print(json.dumps(line), flush=True)
+    benchlib.emit(line)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         for ln in lines:

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Time OccGridEstimator.sampling with and without cone-angle steps, from device events after a warm-up: 4096 rays
+"""Time OccGridEstimator.sampling with and without cone-angle steps (schedule: interleaved, tools/benchlib.py): 4096 rays
 through the sphere grid of tests/test_occgrid.py at 128^3 cells, step 5e-3 (the reference's LLFF configuration,
-run-nerf.py:92-98), one level and four, cone_angle 0 (the uniform march) against 0.004, alternated call by call in one
-process.  Both go through fsn_occgrid_march_ex and its one kernel (lines recorded before the plain and the extended
-kernel were merged timed the plain kernel as "uniform"):
+run-nerf.py:92-98), one level and four, cone_angle 0 (the uniform march) against 0.004.  Both go through
+fsn_occgrid_march_ex and its one kernel (lines recorded before the plain and the extended kernel were merged timed the
+plain kernel as "uniform"):
 
   march      sampling without sigma_fn: count pass, scan, one host read, fill pass
   sampling   with the model's density pass and the visibility cull behind it (sigma_fn = forward_rays)
@@ -15,17 +15,14 @@ One JSON line per case, printed and appended to --out.  Run it under a time limi
     timeout -k 10 300 python tools/bench_march.py [--iters 20] [--warmup 3] [--out profiles/bench_march.jsonl]
 """
 import argparse
-import json
 import os
 import sys
 
-import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import fs_nerf_amd  # noqa: E402,F401
+import benchlib
+
+sys.path.insert(0, os.path.join(benchlib.package(), "tests"))
 from fs_nerf_amd.core.models import NeRF  # noqa: E402
 from fs_nerf_amd.render import rendering as Rm  # noqa: E402
 from fs_nerf_amd.render.occgrid import OccGridEstimator  # noqa: E402
@@ -48,26 +45,9 @@ def make_model(dev):
     return m
 
 
-def timed(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), out
-
-
-def stats(t):
-    return {"median": round(float(np.median(t)), 4), "min": round(float(np.min(t)), 4),
-            "p90": round(float(np.percentile(t, 90)), 4)}
-
-
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_march.jsonl"))
-    ap.add_argument("--tag", default="")
+    benchlib.common_args(ap, iters=20, warmup=3, out="bench_march.jsonl")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     model = make_model(dev)
@@ -75,23 +55,18 @@ def main():
     o, d = o.reshape(-1, 3).contiguous().to(dev), d.reshape(-1, 3).contiguous().to(dev)
     target = torch.rand(o.shape[0], 3, device=dev, generator=torch.Generator(device=dev).manual_seed(2))
     sigma_fn = lambda a, b, c: model.forward_rays(o, d, c, a, b, full=False).squeeze(-1)
-    lines = []
 
     def emit(case, levels, variants, run):
-        """`run(cone)` -> sample count; the variants alternate call by call (clock and thermal drift hit both alike)."""
-        times, counts = {k: [] for k in variants}, {}
-        for it in range(args.warmup + args.iters):
-            for name, cone in variants.items():
-                ms, counts[name] = timed(lambda: run(cone))
-                if it >= args.warmup:
-                    times[name].append(ms)
-        line = {"tool": "bench_march", "tag": args.tag, "device": torch.cuda.get_device_name(0), "case": case,
+        """`run(cone)` -> sample count (the last call's is recorded); interleaved schedule."""
+        counts = {}
+        times = benchlib.interleaved({name: (lambda name=name, cone=cone: counts.__setitem__(name, run(cone)))
+                                      for name, cone in variants.items()}, args.iters, args.warmup, keep="samples")
+        line = {**benchlib.header("bench_march", args.tag), "case": case,
                 "levels": levels, "rays": int(o.shape[0]), "resolution": RES, "step": STEP, "iters": args.iters}
         for name, cone in variants.items():
-            line[name] = {"cone_angle": cone, "ms": stats(times[name]), **counts[name]}
+            line[name] = {"cone_angle": cone, "ms": benchlib.stats(times[name]), **counts[name]}
         line["speedup_median"] = round(line["uniform"]["ms"]["median"] / line["cone"]["ms"]["median"], 3)
-        lines.append(line)
-        print(json.dumps(line), flush=True)
+        benchlib.emit(line, args.out)
 
     variants = {"uniform": 0.0, "cone": CONE}
     for levels in (1, 4):
@@ -119,10 +94,6 @@ def main():
             return {"samples": int(ri.numel()), "route": Rm._rays_route(est, model, None, True, True, o.shape[0], STEP, opts)}
 
         emit("train", levels, variants, train)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "a") as fh:
-        for line in lines:
-            fh.write(json.dumps(line) + "\n")
 
 
 if __name__ == "__main__":

@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""Time fs_nerf_amd.core.metrics.ssim + psnr on N pairs of 800x800x3 frames with device events, and, for comparison,
+"""Time fs_nerf_amd.core.metrics.ssim + psnr on N pairs of 800x800x3 frames (schedule: in turns, tools/benchlib.py, one
+variant and one round at a time, warm-up 5), and, for comparison,
 the float64 restatement of skimage's SSIM on the host (tests/metrics_ref.py; scipy's filters when scipy is present).
 
     python tools/bench_metrics.py [--n 1 8] [--iters 50] [--host-iters 1]
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -13,25 +13,15 @@ import time
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import fs_nerf_amd  # noqa: E402,F401
+import benchlib
+
+sys.path.insert(0, os.path.join(benchlib.package(), "tests"))
 from fs_nerf_amd.core import metrics  # noqa: E402
 
 
 def device_ms(fn, iters, warmup=5):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
+    """(median, min) of the in-turns schedule's samples for one variant."""
+    times = benchlib.in_turns({"fn": fn}, iters, warmup, keep="samples")["fn"]
     return float(np.median(times)), float(np.min(times))
 
 
@@ -59,7 +49,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--hw", type=int, default=800)
-    ap.add_argument("--iters", type=int, default=50)
+    benchlib.common_args(ap, iters=50, tag=False)
     ap.add_argument("--host-iters", type=int, default=1)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -72,9 +62,9 @@ def main():
         b_med, b_min = device_ms(lambda: (metrics.ssim(x, y), metrics.psnr(x, y)), a.iters)
         xh, yh = x.cpu().numpy(), y.cpu().numpy()
         host = min(host_ssim_s(xh, yh) for _ in range(a.host_iters))
-        print(json.dumps({"pairs": n, "hw": a.hw, "ssim_ms": round(s_med, 4), "psnr_ms": round(p_med, 4),
-                          "ssim_psnr_ms": round(b_med, 4), "ssim_psnr_ms_min": round(b_min, 4),
-                          "per_pair_ms": round(b_med / n, 4), "host_filters_s": round(host, 3)}), flush=True)
+        benchlib.emit({"pairs": n, "hw": a.hw, "ssim_ms": round(s_med, 4), "psnr_ms": round(p_med, 4),
+                       "ssim_psnr_ms": round(b_med, 4), "ssim_psnr_ms_min": round(b_min, 4),
+                       "per_pair_ms": round(b_med / n, 4), "host_filters_s": round(host, 3)})
 
 
 if __name__ == "__main__":

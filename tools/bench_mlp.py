@@ -4,12 +4,12 @@
 Prints samples/s, algorithmic TFLOP/s and the matrix-pipe utilisation this implies
 (x3 modes issue 3 MFMA passes per algorithmic product)."""
 import argparse
-import os
-import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import benchlib
+
+benchlib.package()
 
 
 def main():
@@ -33,14 +33,7 @@ def main():
     dd = None if a.density else d
     ops.mlp_fwd(pm, x, dd)
     torch.cuda.synchronize()
-    ts = []
-    for _ in range(a.reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        ops.mlp_fwd(pm, x, dd)
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1) * 1e-3)
+    ts = [benchlib.call_ms(lambda: ops.mlp_fwd(pm, x, dd))[0] * 1e-3 for _ in range(a.reps)]  # ad hoc: one warm call, --reps calls
     t = sorted(ts)[len(ts) // 2]
     flop = {(8, False): 1186816, (8, True): 982528, (4, False): 167680, (4, True): 114688}[(L, a.density)]
     tf = a.n * flop / t / 1e12

@@ -5,38 +5,28 @@ into the per-ray histograms (float atomics: not reproducible), slicing and log f
 chunks of samples when it would exceed --max-matrix-bytes (its temporaries are what the chunks bound; autograd keeps the
 matrix itself either way).  Shapes: --patches 16 patches of --patch 16 x 16 rays with ragged spans (about --samples 150
 samples per ray: a uniform count in [samples/2, 3 samples/2], every 64th ray empty - the input family of
-tools/bench_ray_losses.py), --bins 64 over [2, 6], rays masked by opacity.  Device events around loss + backward, host
-path included; the kernel call and the torch spelling alternate run by run, three rounds of --iters runs, the median of
-each round and the median of those.  There is no pass or fail on these times.  Appends one JSON line to
-profiles/bench_neighbor_kl.jsonl (--out) and prints it.
+tools/bench_ray_losses.py), --bins 64 over [2, 6], rays masked by opacity.  The timed call is loss + backward. Schedule:
+interleaved (tools/benchlib.py), --rounds 3 rounds, us.  There is no pass or fail on these times.  Appends one JSON line
+to profiles/bench_neighbor_kl.jsonl (--out) and prints it.
 
     timeout -k 10 300 python tools/bench_neighbor_kl.py [--iters 20] [--warmup 5] [--patches 16] [--patch 16] [--tag NAME]
 """
 import argparse
-import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import benchlib
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--rounds", type=int, default=3)
+    benchlib.common_args(ap, iters=20, warmup=5, rounds=3, out="bench_neighbor_kl.jsonl")
     ap.add_argument("--patches", type=int, default=16)
     ap.add_argument("--patch", type=int, default=16)
     ap.add_argument("--samples", type=int, default=150)
     ap.add_argument("--bins", type=int, default=64)
     ap.add_argument("--max-matrix-bytes", type=int, default=1 << 30)
-    ap.add_argument("--tag", default="")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_neighbor_kl.jsonl"))
     args = ap.parse_args()
-    import numpy as np
     import torch
-    sys.path.insert(0, ROOT)
-    import fs_nerf_amd  # noqa: F401
+    benchlib.package()
     from fs_nerf_amd import ops
     from fs_nerf_amd.core.loss import NeighborRayKLLoss
     dev = torch.device("cuda:0")
@@ -86,31 +76,14 @@ def main():
     }
     a, b = (float(fn().detach()) for fn in variants.values())  # the two spellings compute the same loss
     agree = abs(a - b) / max(abs(b), 1e-12)
-    rounds = {k: [] for k in variants}
-    for _ in range(args.rounds):
-        times = {k: [] for k in variants}
-        for it in range(args.warmup + args.iters):
-            for name, fn in variants.items():
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                torch.autograd.grad(fn(), weights)
-                e1.record()
-                e1.synchronize()
-                if it >= args.warmup:
-                    times[name].append(e0.elapsed_time(e1) * 1e3)
-        for name in variants:
-            rounds[name].append(float(np.median(times[name])))
-    out = {"tool": "bench_neighbor_kl", "tag": args.tag, "device": torch.cuda.get_device_name(0), "rays": R, "samples": N,
+    rounds = benchlib.interleaved({name: (lambda fn=fn: torch.autograd.grad(fn(), weights)) for name, fn in variants.items()},
+                                  args.iters, args.warmup, args.rounds)
+    out = {**benchlib.header("bench_neighbor_kl", args.tag), "rays": R, "samples": N,
            "patches": [B, Pp, Pp], "bins": bins, "matrix_chunks": -(-N // chunk), "iters": args.iters, "rounds": args.rounds,
            "what": "loss forward + backward, device events, us", "loss": a,
            "relative_difference_of_the_two_spellings": agree,
-           "variants": {name: {"us_median": round(float(np.median(r)), 2), "us_rounds": [round(x, 2) for x in r]}
-                        for name, r in rounds.items()}}
-    line = json.dumps(out)
-    print(line)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "a") as f:
-        f.write(line + "\n")
+           "variants": {name: benchlib.rounds_summary(r, "us") for name, r in rounds.items()}}
+    benchlib.emit(out, args.out)
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What cone-angle steps in the one-launch occupancy kernel cost and buy, timed from device events after a warm-up.  The
+"""What cone-angle steps in the one-launch occupancy kernel cost and buy (each child: interleaved, tools/benchlib.py).  The
 scene is tools/bench_march.py's: the sphere grid of tests/test_occgrid.py at 128^3 cells over +-1.5, step 5e-3 (the
 reference's LLFF configuration, run-nerf.py:92-98), its seeded 8 x 256 network, an orbit camera.
 
@@ -13,18 +13,18 @@ reference's LLFF configuration, run-nerf.py:92-98), its seeded 8 x 256 network, 
   cone-train      (c) the same grid, a 4096-ray training call + backward: estimator-sampling against occ-sampler.
 
 Every run of a variant is a fresh child process (the library is chosen when it is loaded); the variants alternate, three
-runs each, and a variant's figure is the median of its runs' medians.  Every child runs under a time limit of its own and
-the first one that fails ends the tool.  One JSON line per case, printed and appended to --out:
+runs each, and a variant's figure is the median of its runs' medians.  Every child runs under a time limit of its own
+and the first one that fails ends the tool.  One JSON line per case, printed and appended to --out:
 
     timeout -k 10 900 python tools/bench_occ_cone.py --parent-lib PATH [--out profiles/bench_occ_cone.jsonl]
 """
 import argparse
 import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import benchlib
+from benchlib import ROOT
 STEP, RES, CONE, HW, CHUNK = 5e-3, 128, 0.004, 800, 32768
 CASES = {"default-frame": dict(levels=1, frame=True, cone=0.0), "cone-frame": dict(levels=4, frame=True, cone=CONE),
          "cone-train": dict(levels=4, frame=False, cone=CONE)}
@@ -34,15 +34,12 @@ def child(args):
     """One run of one variant -> one JSON line: per-iteration milliseconds and the route taken."""
     import numpy as np
     import torch
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import fs_nerf_amd  # noqa: F401
+    sys.path.insert(0, os.path.join(benchlib.package(), "tests"))
     from fs_nerf_amd import _lib as L
     from fs_nerf_amd.render import rendering as Rm
     from fs_nerf_amd.render.occgrid import OccGridEstimator
     from oracle import fsnerf_oracle as O
-    from bench_march import make_model, timed
+    from bench_march import make_model
     from test_occgrid import AABB, _sphere_binaries
     lib = L.lib()
     if not hasattr(lib, "fsn_render_rays_occgrid_ex"):
@@ -87,11 +84,7 @@ def child(args):
             model.zero_grad(set_to_none=True)
             return ri
         rays = int(o.shape[0])
-    times = []
-    for it in range(args.warmup + args.iters):
-        ms, _ = timed(run)
-        if it >= args.warmup:
-            times.append(ms)
+    times = benchlib.interleaved({"run": run}, args.iters, args.warmup, keep="samples")["run"]
     print("CHILD " + json.dumps({"ms": [round(t, 4) for t in times], "median": round(float(np.median(times)), 4),
                                  "route": route, "rays": rays, "max_steps": est.max_steps(STEP, case["cone"]),
                                  "lib": os.path.basename(os.path.dirname(L.LIB_PATH)) + "/" + os.path.basename(L.LIB_PATH),
@@ -106,13 +99,7 @@ def run_child(case, variant, args):
         env.update(FSN_LIB_PATH=variant["lib"], FSN_LIB_PARTIAL="1")  # (the parent exports no *_ex render entry)
     cmd = [sys.executable, os.path.abspath(__file__), "--child", case, "--cone-switch", str(int(variant.get("switch", 0))),
            "--iters", str(iters), "--warmup", str(warmup)]
-    try:
-        r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=limit)
-    except subprocess.TimeoutExpired:
-        raise SystemExit(f"bench_occ_cone: {case} / {variant['name']} ran past its {limit} s limit; stopping")
-    if r.returncode != 0:
-        raise SystemExit(f"bench_occ_cone: {case} / {variant['name']} failed ({r.returncode}); stopping\n" + r.stdout[-2000:] + r.stderr[-3000:])
-    return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("CHILD ")][-1][6:])
+    return benchlib.run_child(cmd, env, limit, f"bench_occ_cone: {case} / {variant['name']}", "CHILD ")
 
 
 def main():
@@ -132,7 +119,6 @@ def main():
     if args.child:
         return child(args)
     import statistics
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     for case in args.cases.split(","):
         if case == "default-frame":
             if not args.parent_lib or not os.path.exists(args.parent_lib):
@@ -156,9 +142,7 @@ def main():
             line["inside_parent_spread"] = line["excess_ms"] <= a["spread_ms"]
         else:
             line["speedup_median"] = round(a["median_ms"] / b["median_ms"], 3)
-        print(json.dumps(line), flush=True)
-        with open(args.out, "a") as fh:
-            fh.write(json.dumps(line) + "\n")
+        benchlib.emit(line, args.out)
 
 
 if __name__ == "__main__":

@@ -5,35 +5,27 @@ csrc/pose_refine.hip) against the torch spelling a user writes without it: the i
 launch, then matrix_exp of the skew matrices, a gather of the corrected poses by view, an einsum with the pixel's camera
 direction, the NDC map under autograd, and autograd's backward of all that (index_add_ per view: float atomics, not
 reproducible).  Shapes: --rays 4096 per batch over 8 and 100 views of --hw 64 x 64 pixels, world and NDC rays.  xi is
-changed before every batch, as an optimizer step does.  Device events around batch + backward; the two spellings
-alternate run by run, three rounds of --iters runs, the median of each round and the median of those.  There is no pass
-or fail on these times.  Appends one JSON line to profiles/bench_pose_refine.jsonl (--out) and prints it.
+changed before every batch, as an optimizer step does.  The timed call is batch + backward.  Schedule: interleaved
+(tools/benchlib.py), --rounds 3 rounds, us. There is no pass or fail on these times.  Appends one JSON line to
+profiles/bench_pose_refine.jsonl (--out) and prints it.
 
     timeout -k 10 300 python tools/bench_pose_refine.py [--iters 20] [--warmup 5] [--rays 4096] [--hw 64] [--tag NAME]
 """
 import argparse
-import json
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import benchlib
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--rounds", type=int, default=3)
+    benchlib.common_args(ap, iters=20, warmup=5, rounds=3, out="bench_pose_refine.jsonl")
     ap.add_argument("--rays", type=int, default=4096)
     ap.add_argument("--hw", type=int, default=64)
-    ap.add_argument("--tag", default="")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_pose_refine.jsonl"))
     args = ap.parse_args()
-    import numpy as np
     import torch
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import fs_nerf_amd  # noqa: F401
+    sys.path.insert(0, os.path.join(benchlib.package(), "tests"))
     from fs_nerf_amd.nerfdata import CameraRefiner, RayDataset, RayLoader
     import pose_refine_ref as PR  # the fixtures' poses
     dev = torch.device("cuda:0")
@@ -92,30 +84,12 @@ def main():
 
     cases = {f"{'ndc' if ndc else 'world'}_{n}views": case(n, ndc) for n in (8, 100) for ndc in (False, True)}
     variants = {f"{c}_{which}": fn for c, fns in cases.items() for which, fn in fns.items()}
-    rounds = {k: [] for k in variants}
-    for _ in range(args.rounds):
-        times = {k: [] for k in variants}
-        for it in range(args.warmup + args.iters):
-            for name, fn in variants.items():
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                fn()
-                b.record()
-                b.synchronize()
-                if it >= args.warmup:
-                    times[name].append(a.elapsed_time(b) * 1e3)
-        for name in variants:
-            rounds[name].append(float(np.median(times[name])))
-    out = {"tool": "bench_pose_refine", "tag": args.tag, "device": torch.cuda.get_device_name(0), "rays": B,
+    rounds = benchlib.interleaved(variants, args.iters, args.warmup, args.rounds)
+    out = {**benchlib.header("bench_pose_refine", args.tag), "rays": B,
            "image": [H, W], "iters": args.iters, "rounds": args.rounds,
            "what": "xi update + batch + backward to dL/dxi, device events, us",
-           "variants": {name: {"us_median": round(float(np.median(r)), 2), "us_rounds": [round(x, 2) for x in r]}
-                        for name, r in rounds.items()}}
-    line = json.dumps(out)
-    print(line)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "a") as f:
-        f.write(line + "\n")
+           "variants": {name: benchlib.rounds_summary(r, "us") for name, r in rounds.items()}}
+    benchlib.emit(out, args.out)
 
 
 if __name__ == "__main__":

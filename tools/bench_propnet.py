@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time the proposal-network sampler (csrc/propnet.hip, render/propnet.py) at 4096 rays, prop_samples=(128,),
-num_samples=64, from device events after a warm-up, the profiler off.  Three cases, one JSON line each, printed and
+num_samples=64, the profiler off.  Three cases, one JSON line each, printed and
 appended to --out:
 
   level      one level between two network evaluations, 128 intervals in -> 64 out, no gradients:
@@ -15,22 +15,17 @@ appended to --out:
              network: forward, MSE, backward - with the proposal update (proposal graph kept, interlevel loss, its
              backward, both Adam steps) and without it (proposal_requires_grad off, the main Adam step only)
 
-The variants of a case are alternated run by run in one process, --runs runs of --iters timed calls each; the figure is
-the median of the runs' per-call times.  Run it under a time limit of its own:
+Schedule: windows (tools/benchlib.py), --runs 3 runs of --iters calls each, ms.  Run it under a time limit of its own:
 
     timeout -k 10 300 python tools/bench_propnet.py [--iters 200] [--warmup 10] [--out profiles/bench_propnet.jsonl]
 """
 import argparse
-import json
-import os
-import sys
 
-import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import fs_nerf_amd  # noqa: E402,F401
+import benchlib
+
+benchlib.package()
 from fs_nerf_amd import ops  # noqa: E402
 from fs_nerf_amd.core import models as M  # noqa: E402
 from fs_nerf_amd.render import propnet as P  # noqa: E402
@@ -40,27 +35,9 @@ from fs_nerf_amd.render import volrend as V  # noqa: E402
 RAYS, N_PROP, N_FINAL, NEAR, FAR = 4096, 128, 64, 2.0, 6.0
 
 
-def timed_run(fn, iters):
-    """ms per call over one window of `iters` calls between two device events"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / iters
-
-
 def alternate(variants, iters, warmup, runs):
-    for fn in variants.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in variants}
-    for _ in range(runs):
-        for name, fn in variants.items():
-            times[name].append(timed_run(fn, iters))
-    return {name: {"ms_median": round(float(np.median(t)), 4), "ms_runs": [round(x, 4) for x in t]} for name, t in times.items()}
+    times = benchlib.windows(variants, iters, warmup, runs)
+    return {name: benchlib.rounds_summary(t, "ms", per="runs") for name, t in times.items()}
 
 
 def level_case(dev):
@@ -117,22 +94,15 @@ def rays(dev):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--runs", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_propnet.jsonl"))
-    ap.add_argument("--tag", default="")
+    benchlib.common_args(ap, iters=200, warmup=10, runs=3, out="bench_propnet.jsonl")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_propnet needs the GPU: there is nothing to time without one"
     dev = torch.device("cuda:0")
-    head = {"tool": "bench_propnet", "tag": args.tag, "device": torch.cuda.get_device_name(0), "rays": RAYS,
+    head = {**benchlib.header("bench_propnet", args.tag), "rays": RAYS,
             "prop_samples": [N_PROP], "num_samples": N_FINAL, "iters": args.iters, "runs": args.runs}
-    lines = []
 
     def emit(case, extra, times):
-        line = dict(head, case=case, **extra, **times)
-        lines.append(line)
-        print(json.dumps(line), flush=True)
+        benchlib.emit(dict(head, case=case, **extra, **times), args.out)
 
     # (a) one level
     s, t, sig = level_case(dev)
@@ -192,11 +162,6 @@ def main():
     times = alternate({"with_proposal_update": lambda: step(True), "without_proposal_update": lambda: step(False)}, steps,
                       max(args.warmup // 2, 3), args.runs)
     emit("step", {"steps_per_run": steps, "final_network": "8x256", "proposal_network": "4x128"}, times)
-
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "a") as fh:
-        for line in lines:
-            fh.write(json.dumps(line) + "\n")
 
 
 if __name__ == "__main__":

@@ -1,40 +1,30 @@
 #!/usr/bin/env python3
 """Time forward + backward of the few-shot geometry losses (core.loss.RayEntropyLoss, DepthKLLoss,
-PatchDepthSmoothnessLoss: csrc/ray_losses.hip) against the torch spelling a user writes without the kernels:
-clamp / index_add_ / log over the packed samples for the two ray losses (float atomics: not reproducible), slicing for
-the patch loss.  Shapes: --rays 4096 rays with ragged spans (about --samples 150 samples per ray: a uniform count in
-[samples/2, 3 samples/2], every 64th ray empty), and --patches 64 patches of --patch 32 x 32.  Device events around
-loss + backward; the kernel call and the torch spelling alternate run by run, three rounds of --iters runs, the median
-of each round and the median of those.  There is no pass or fail on these times.  Appends one JSON line to
-profiles/bench_ray_losses.jsonl (--out) and prints it.
+PatchDepthSmoothnessLoss: csrc/ray_losses.hip) against the torch spelling a user writes without the kernels: clamp /
+index_add_ / log over the packed samples for the two ray losses (float atomics: not reproducible), slicing for the patch
+loss.  Shapes: --rays 4096 rays with ragged spans (about --samples 150 samples per ray: a uniform count in [samples/2, 3
+samples/2], every 64th ray empty), and --patches 64 patches of --patch 32 x 32.  The timed call is loss + backward.
+Schedule: interleaved (tools/benchlib.py), --rounds 3 rounds, us.  There is no pass or fail on these times.  Appends one
+JSON line to profiles/bench_ray_losses.jsonl (--out) and prints it.
 
     timeout -k 10 300 python tools/bench_ray_losses.py [--iters 20] [--warmup 5] [--rays 4096] [--samples 150] [--tag NAME]
 """
 import argparse
-import json
 import math
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import benchlib
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--rounds", type=int, default=3)
+    benchlib.common_args(ap, iters=20, warmup=5, rounds=3, out="bench_ray_losses.jsonl")
     ap.add_argument("--rays", type=int, default=4096)
     ap.add_argument("--samples", type=int, default=150)
     ap.add_argument("--patches", type=int, default=64)
     ap.add_argument("--patch", type=int, default=32)
-    ap.add_argument("--tag", default="")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_ray_losses.jsonl"))
     args = ap.parse_args()
-    import numpy as np
     import torch
-    sys.path.insert(0, ROOT)
-    import fs_nerf_amd  # noqa: F401
+    benchlib.package()
     from fs_nerf_amd import ops
     from fs_nerf_amd.core.loss import DepthKLLoss, PatchDepthSmoothnessLoss, RayEntropyLoss
     dev = torch.device("cuda:0")
@@ -92,30 +82,13 @@ def main():
     for name in ("entropy", "depth_kl", "smooth"):  # the two spellings compute the same loss
         a, b = float(variants[name + "_kernel"][0]().detach()), float(variants[name + "_torch"][0]().detach())
         agree[name] = abs(a - b) / max(abs(b), 1e-12)
-    rounds = {k: [] for k in variants}
-    for _ in range(args.rounds):
-        times = {k: [] for k in variants}
-        for it in range(args.warmup + args.iters):
-            for name, (fn, leaf) in variants.items():
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                torch.autograd.grad(fn(), leaf)
-                b.record()
-                b.synchronize()
-                if it >= args.warmup:
-                    times[name].append(a.elapsed_time(b) * 1e3)
-        for name in variants:
-            rounds[name].append(float(np.median(times[name])))
-    out = {"tool": "bench_ray_losses", "tag": args.tag, "device": torch.cuda.get_device_name(0), "rays": R, "samples": N,
+    rounds = benchlib.interleaved({name: (lambda fn=fn, leaf=leaf: torch.autograd.grad(fn(), leaf))
+                                   for name, (fn, leaf) in variants.items()}, args.iters, args.warmup, args.rounds)
+    out = {**benchlib.header("bench_ray_losses", args.tag), "rays": R, "samples": N,
            "patches": [args.patches, args.patch, args.patch], "iters": args.iters, "rounds": args.rounds,
            "what": "loss forward + backward, device events, us", "relative_difference_of_the_two_spellings": agree,
-           "variants": {name: {"us_median": round(float(np.median(r)), 2), "us_rounds": [round(x, 2) for x in r]}
-                        for name, r in rounds.items()}}
-    line = json.dumps(out)
-    print(line)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "a") as f:
-        f.write(line + "\n")
+           "variants": {name: benchlib.rounds_summary(r, "us") for name, r in rounds.items()}}
+    benchlib.emit(out, args.out)
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Time OccGridEstimator.update_every_n_steps (the occupancy refresh of the training loop, run-nerf.py:288-295) per call,
-from device events after a warm-up: 128^3 cells at 1 and 4 levels, warm-up phase (every cell) and steady phase (uniform +
-occupied draws), one estimator per configuration, three variants alternated call by call in one process:
+"""Time OccGridEstimator.update_every_n_steps (the occupancy refresh of the training loop, run-nerf.py:288-295) per call
+(schedule: interleaved, tools/benchlib.py): 128^3 cells at 1 and 4 levels, warm-up phase (every cell) and steady phase
+(uniform + occupied draws), one estimator per configuration, three variants:
 
   closure_parity     the plain closure `model(x) * step`, the model's own (parity) mode: the level loop
   closure_autocast   the same closure under torch.autocast("cuda") with NeRF.autocast_precision set: the level loop in a
@@ -14,16 +14,12 @@ the same file gives the baseline of an earlier commit.  Prints one JSON line.  R
     timeout -k 10 300 python tools/bench_refresh.py [--precision fp16] [--iters 20] [--warmup 3] [--tag NAME]
 """
 import argparse
-import json
-import os
-import sys
 
-import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import fs_nerf_amd  # noqa: E402,F401
+import benchlib
+
+benchlib.package()
 from fs_nerf_amd.core.models import NeRF  # noqa: E402
 from fs_nerf_amd.render.occgrid import OccGridEstimator  # noqa: E402
 
@@ -57,9 +53,7 @@ def unused_share(est):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--precision", default="fp16", choices=["fp16", "bf16"])
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--tag", default="")
+    benchlib.common_args(ap, iters=20, warmup=3)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     model = make_model(dev)
@@ -79,27 +73,18 @@ def main():
         fused_fn = model.occ_eval_fn(STEP, args.precision)
         variants += [("closure_autocast", run_autocast),
                      ("fused", lambda est, step: est.update_every_n_steps(step, fused_fn, occ_thre=1e-2))]
-    out = {"tool": "bench_refresh", "tag": args.tag, "device": torch.cuda.get_device_name(0), "resolution": RES,
+    out = {**benchlib.header("bench_refresh", args.tag), "resolution": RES,
            "precision": args.precision if HAS_SINGLE_PASS else None, "iters": args.iters, "configs": {}}
     for levels in (1, 4):
         est = OccGridEstimator(AABB, RES, levels).to(dev).train()
         est.generator = torch.Generator().manual_seed(5)
         for phase, step in (("warmup", 0), ("steady", 256)):
-            times = {name: [] for name, _ in variants}
-            for it in range(args.warmup + args.iters):
-                for name, fn in variants:  # alternated: clock and thermal drift hit every variant alike
-                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    a.record()
-                    fn(est, step)
-                    b.record()
-                    b.synchronize()
-                    if it >= args.warmup:
-                        times[name].append(a.elapsed_time(b))
+            times = benchlib.interleaved({name: (lambda fn=fn: fn(est, step)) for name, fn in variants}, args.iters, args.warmup,
+                                         keep="samples")
             cfg = {}
             for name in ("closure_parity", "closure_autocast", "fused"):
                 t = times.get(name)
-                cfg[name + "_ms"] = None if not t else {"median": round(float(np.median(t)), 4), "min": round(float(np.min(t)), 4),
-                                                         "p90": round(float(np.percentile(t, 90)), 4)}
+                cfg[name + "_ms"] = None if not t else benchlib.stats(t)
             share, occupied = unused_share(est)
             cfg["occupied_cells_per_level"] = occupied
             if phase == "steady":
@@ -107,7 +92,7 @@ def main():
             out["configs"][f"levels{levels}_{phase}"] = cfg
     if HAS_SINGLE_PASS:
         out["precision_after"] = fused_fn.precision  # ("bf16" here: an fp16 refresh left the range envelope and fell back)
-    print(json.dumps(out))
+    benchlib.emit(out)
 
 
 if __name__ == "__main__":

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Time the SSIM loss and the patch loader on the GPU (device events around work that ends in a synchronise):
+"""Time the SSIM loss and the patch loader on the GPU.  Schedule: in turns (tools/benchlib.py), warm-up 5, ms:
 
 * forward + backward of core.loss.SSIMLoss on 64 patches of 32x32x3 and on one 800x800x3 pair, against the formulation
   a user would otherwise write - F.conv2d with the 11x11 Gaussian window per channel (float32, no padding: the
-  'valid' output is the interior the mean is taken over) + autograd.  The two alternate within one process, three rounds, medians of the rounds' medians;
+  'valid' output is the interior the mean is taken over) + autograd.  Medians of the --rounds 3 rounds' medians;
   the largest gradient difference between them is reported next to the times (the conv2d route is float32).
 * one PatchLoader batch (64 patches of 32x32) against the explicit-index route: the anchor -> index arithmetic in torch
   followed by RayDataset.batch("explicit").
@@ -13,40 +13,21 @@
 import argparse
 import json
 import os
-import sys
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import fs_nerf_amd  # noqa: E402,F401
+import benchlib
+
+benchlib.package()
 from fs_nerf_amd.core.loss import SSIMLoss  # noqa: E402
 from fs_nerf_amd.nerfdata import PatchLoader, RayDataset  # noqa: E402
 
 
-def device_ms(fn, iters, warmup=5):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
-    return float(np.median(times))
-
-
 def alternate(fns, iters, rounds):
-    """{name: median over rounds of the round's median ms}, the candidates taking turns inside every round."""
-    per = {k: [] for k in fns}
-    for _ in range(rounds):
-        for k, fn in fns.items():
-            per[k].append(device_ms(fn, iters))
+    """{name: median over rounds of the round's median ms} and the rounds themselves; schedule: in turns, warm-up 5."""
+    per = benchlib.in_turns(fns, iters, 5, rounds)
     return {k: float(np.median(v)) for k, v in per.items()}, {k: [round(t, 4) for t in v] for k, v in per.items()}
 
 
@@ -66,9 +47,7 @@ def conv2d_ssim_loss(x, y, window):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=50)
-    ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_ssim_loss.jsonl"))
+    benchlib.common_args(ap, iters=50, rounds=3, tag=False, out="bench_ssim_loss.jsonl")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_ssim_loss: needs the GPU (a CPU run measures nothing)")
@@ -99,7 +78,7 @@ def main():
         lines.append({"case": name, "what": "forward + backward, gradient to one input", **{k: round(v, 4) for k, v in med.items()},
                       "rounds": rounds, "max_abs_grad_difference_conv2d_f32_vs_hip": float((g_hip - g_conv).abs().max()),
                       "max_abs_grad_hip": float(g_hip.abs().max())})
-        print(json.dumps(lines[-1]), flush=True)
+        benchlib.emit(lines[-1])
 
     # the loader: 8 views of 400x400, 64 patches of 32x32 per batch
     H = W = 400
@@ -128,7 +107,7 @@ def main():
     med, rounds = alternate({"patch_loader_ms": patch_loader, "explicit_index_route_ms": explicit_route}, a.iters, a.rounds)
     lines.append({"case": "one batch: 64 patches 32x32 from 8 views 400x400", **{k: round(v, 4) for k, v in med.items()},
                   "rounds": rounds})
-    print(json.dumps(lines[-1]), flush=True)
+    benchlib.emit(lines[-1])
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         for ln in lines:

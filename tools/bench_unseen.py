@@ -2,39 +2,29 @@
 """Time one next() of nerfdata.UnseenPatchLoader (fsn_unseen_patch_batch, csrc/unseen_views.hip: ONE launch from a step
 counter to the rays of --patches 64 patches of --patch 32 x 32 on --hw 800 x 800 intrinsics) against the torch spelling
 a user writes without it, as examples/train_synthetic.py did: random numbers from torch.rand on the device, the shell
-point and the look-at with torch ops, utilities.get_rays of the whole frame per pose (its pose goes through the host,
-as get_rays takes it), and the windows sliced out with index tensors.  Both serve the same distribution (fitted to eight
-orbit cameras), not the same random numbers.  --poses-per-batch: 1 and 8 poses shared by the batch's patches.  Device
-events around the call with the host path included; the two spellings alternate run by run, three rounds of --iters
-runs, the median of each round and the median of those.  There is no pass or fail on these times.  Appends one JSON
-line to profiles/bench_unseen.jsonl (--out) and prints it.
+point and the look-at with torch ops, utilities.get_rays of the whole frame per pose (its pose goes through the host, as
+get_rays takes it), and the windows sliced out with index tensors.  Both serve the same distribution (fitted to eight
+orbit cameras), not the same random numbers.  --poses-per-batch: 1 and 8 poses shared by the batch's patches.  Schedule:
+interleaved (tools/benchlib.py), --rounds 3 rounds, us. There is no pass or fail on these times.  Appends one JSON line
+to profiles/bench_unseen.jsonl (--out) and prints it.
 
     timeout -k 10 300 python tools/bench_unseen.py [--iters 20] [--warmup 5] [--patches 64] [--patch 32] [--hw 800] [--tag NAME]
 """
 import argparse
-import json
 import math
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import benchlib
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--rounds", type=int, default=3)
+    benchlib.common_args(ap, iters=20, warmup=5, rounds=3, out="bench_unseen.jsonl")
     ap.add_argument("--patches", type=int, default=64)
     ap.add_argument("--patch", type=int, default=32)
     ap.add_argument("--hw", type=int, default=800)
-    ap.add_argument("--tag", default="")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_unseen.jsonl"))
     args = ap.parse_args()
-    import numpy as np
     import torch
-    sys.path.insert(0, ROOT)
-    import fs_nerf_amd  # noqa: F401
+    benchlib.package()
     from fs_nerf_amd.nerfdata import UnseenPatchLoader, UnseenViewSampler
     from fs_nerf_amd.utils import utilities as U
     from oracle import fsnerf_oracle as O
@@ -81,30 +71,12 @@ def main():
     for name, fn in variants.items():  # both spellings serve B * P * P rays
         o, d = fn()
         assert o.shape == d.shape == (B * P * P, 3) and bool(torch.isfinite(o).all()) and bool(torch.isfinite(d).all()), name
-    rounds = {k: [] for k in variants}
-    for _ in range(args.rounds):
-        times = {k: [] for k in variants}
-        for it in range(args.warmup + args.iters):
-            for name, fn in variants.items():
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                fn()
-                b.record()
-                b.synchronize()
-                if it >= args.warmup:
-                    times[name].append(a.elapsed_time(b) * 1e3)
-        for name in variants:
-            rounds[name].append(float(np.median(times[name])))
-    out = {"tool": "bench_unseen", "tag": args.tag, "device": torch.cuda.get_device_name(0), "patches": [B, P, P],
+    rounds = benchlib.interleaved(variants, args.iters, args.warmup, args.rounds)
+    out = {**benchlib.header("bench_unseen", args.tag), "patches": [B, P, P],
            "image": [H, W], "iters": args.iters, "rounds": args.rounds,
            "what": "one batch of unseen-view patch rays (rays_o, rays_d), device events with the host path, us",
-           "variants": {name: {"us_median": round(float(np.median(r)), 2), "us_rounds": [round(x, 2) for x in r]}
-                        for name, r in rounds.items()}}
-    line = json.dumps(out)
-    print(line)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "a") as f:
-        f.write(line + "\n")
+           "variants": {name: benchlib.rounds_summary(r, "us") for name, r in rounds.items()}}
+    benchlib.emit(out, args.out)
 
 
 if __name__ == "__main__":

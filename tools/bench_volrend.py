@@ -1,30 +1,26 @@
 #!/usr/bin/env python3
-"""Time the packed volume-rendering primitives against the plain torch ops a user writes without them, from device
-events after a warm-up: 4096 rays at about 40 and about 150 kept samples per ray (counts uniform in [m/2, 3m/2], seeded),
-render_weight_from_density + accumulate_along_rays(C = 3), forward alone and forward + backward (gradients to sigmas
-and rgbs through a loss on the colours).
+"""Time the packed volume-rendering primitives against the plain torch ops a user writes without them: 4096 rays at about
+40 and about 150 kept samples per ray (counts uniform in [m/2, 3m/2], seeded), render_weight_from_density +
+accumulate_along_rays(C = 3), forward alone and forward + backward (gradients to sigmas and rgbs through a loss on the
+colours).
 
   hip     render/volrend.py: one launch for the weights, one for the accumulation, one each for their backwards
   torch   the same results from torch ops on the device: a GLOBAL cumsum of sigma dt minus its value at each ray's
           first sample, exp, index_add_ - and the autograd nodes behind them
 
-The two are alternated run by run, three runs each of --iters timed calls; the figure is the median of the three runs'
-per-call times.  The results are compared first (max |hip - torch| / max |torch|), so that the times are of the same
-answer.  One JSON line per case, printed and appended to --out.  Run it under a time limit of its own:
+Schedule: windows (tools/benchlib.py), three runs of --iters calls each, ms.  The results are compared first (max |hip -
+torch| / max |torch|), so that the times are of the same answer.  One JSON line per case, printed and appended to --out.
+Run it under a time limit of its own:
 
     timeout -k 10 300 python tools/bench_volrend.py [--iters 500] [--warmup 20] [--out profiles/bench_volrend.jsonl]
 """
 import argparse
-import json
-import os
-import sys
 
-import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import fs_nerf_amd  # noqa: E402,F401
+import benchlib
+
+benchlib.package()
 from fs_nerf_amd.render import volrend as V  # noqa: E402
 
 RAYS, RUNS = 4096, 3
@@ -69,31 +65,16 @@ def step(fwd, c, backward):
     return out.detach(), sig.grad, rgb.grad
 
 
-def timed_run(fn, iters):
-    """ms per call over one window of `iters` calls between two device events"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / iters
-
-
 def rel(a, b):
     return float((a.double() - b.double()).abs().max() / b.double().abs().max().clamp(min=1e-30))
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=500)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_volrend.jsonl"))
-    ap.add_argument("--tag", default="")
+    benchlib.common_args(ap, iters=500, warmup=20, out="bench_volrend.jsonl")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_volrend needs the GPU: there is nothing to time without one"
     dev = torch.device("cuda:0")
-    lines = []
     for mean in (40, 150):
         c = make_case(mean, dev, seed=mean)
         variants = {"hip": hip_forward, "torch": torch_forward}
@@ -101,27 +82,15 @@ def main():
             outs = {name: step(fwd, c, backward) for name, fwd in variants.items()}
             pairs = zip(outs["hip"], outs["torch"]) if backward else [(outs["hip"], outs["torch"])]
             agree = [round(rel(a, b), 9) for a, b in pairs]
-            runs = {name: [] for name in variants}
-            for name, fwd in variants.items():
-                for _ in range(args.warmup):
-                    step(fwd, c, backward)
-            torch.cuda.synchronize()
-            for _ in range(RUNS):
-                for name, fwd in variants.items():
-                    runs[name].append(timed_run(lambda: step(fwd, c, backward), args.iters))
-            line = {"tool": "bench_volrend", "tag": args.tag, "device": torch.cuda.get_device_name(0),
+            runs = benchlib.windows({name: (lambda fwd=fwd: step(fwd, c, backward)) for name, fwd in variants.items()},
+                                    args.iters, args.warmup, RUNS)
+            line = {**benchlib.header("bench_volrend", args.tag),
                     "case": "forward+backward" if backward else "forward", "rays": RAYS, "samples": c["N"],
                     "samples_per_ray": round(c["N"] / RAYS, 1), "channels": 3, "iters": args.iters, "runs": RUNS,
                     "max_rel_diff_hip_vs_torch": agree}
             for name in variants:
-                line[name] = {"ms_median": round(float(np.median(runs[name])), 4),
-                              "ms_runs": [round(t, 4) for t in runs[name]]}
-            lines.append(line)
-            print(json.dumps(line), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "a") as fh:
-        for line in lines:
-            fh.write(json.dumps(line) + "\n")
+                line[name] = benchlib.rounds_summary(runs[name], "ms", per="runs")
+            benchlib.emit(line, args.out)
 
 
 if __name__ == "__main__":

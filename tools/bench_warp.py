@@ -1,44 +1,34 @@
 #!/usr/bin/env python3
 """Time forward + backward of the depth-warp consistency term (core.loss.WarpConsistencyLoss over nerfdata.WarpSource:
-csrc/warp.hip, one launch each way over the resident uint8 images) against the torch spelling a user writes today:
-float copies of the images (here 12 bytes per pixel beside the dataset's 4), the projection as torch ops, one
+csrc/warp.hip, one launch each way over the resident uint8 images) against the torch spelling a user writes today: float
+copies of the images (here 12 bytes per pixel beside the dataset's 4), the projection as torch ops, one
 F.grid_sample(align_corners=True) over the view stack (the view index as the third grid coordinate, so that rays with
-different source views share one call without a host synchronisation), the same masked mean, autograd.
-Shapes: --views 8 views of --hw 800 x 800 RGBA bytes on an orbit; --rays 4096 scattered rays (random pixels of random
-views, depth 4 +- 0.5) and --patches 64 patches of --patch 32 x 32, each against the view nearest to its own.
-Device events around loss + backward to the depth, the host path included; the two spellings alternate run by run,
-three rounds of --iters runs, the median of each round and the median of those.  There is no pass or fail on these
-times.  Appends one JSON line to profiles/bench_warp.jsonl (--out) and prints it.
+different source views share one call without a host synchronisation), the same masked mean, autograd. Shapes: --views 8
+views of --hw 800 x 800 RGBA bytes on an orbit; --rays 4096 scattered rays (random pixels of random views, depth 4 +-
+0.5) and --patches 64 patches of --patch 32 x 32, each against the view nearest to its own. The timed call is loss +
+backward to the depth.  Schedule: interleaved (tools/benchlib.py), --rounds 3 rounds, us.  There is no pass or fail on
+these times.  Appends one JSON line to profiles/bench_warp.jsonl (--out) and prints it.
 
     timeout -k 10 300 python tools/bench_warp.py [--iters 20] [--warmup 5] [--tag NAME]
 """
 import argparse
-import json
 import math
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import benchlib
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--rounds", type=int, default=3)
+    benchlib.common_args(ap, iters=20, warmup=5, rounds=3, out="bench_warp.jsonl")
     ap.add_argument("--views", type=int, default=8)
     ap.add_argument("--hw", type=int, default=800)
     ap.add_argument("--rays", type=int, default=4096)
     ap.add_argument("--patches", type=int, default=64)
     ap.add_argument("--patch", type=int, default=32)
-    ap.add_argument("--tag", default="")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_warp.jsonl"))
     args = ap.parse_args()
-    import numpy as np
     import torch
     import torch.nn.functional as F
-    sys.path.insert(0, ROOT)
-    import fs_nerf_amd  # noqa: F401
+    benchlib.package()
     from fs_nerf_amd.core.loss import WarpConsistencyLoss
     from fs_nerf_amd.nerfdata import RayDataset, WarpSource
     dev = torch.device("cuda:0")
@@ -99,32 +89,15 @@ def main():
         x, y = float(variants[name + "_kernel"][0]().detach()), float(variants[name + "_torch"][0]().detach())
         agree[name] = abs(x - y) / max(abs(y), 1e-12)
         valid_rows[name] = int(source.sample(b[2], b[3], b[1].detach(), b[4], border=border)[1].sum())
-    rounds = {k: [] for k in variants}
-    for _ in range(args.rounds):
-        times = {k: [] for k in variants}
-        for it in range(args.warmup + args.iters):
-            for name, (fn, leaf) in variants.items():
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                torch.autograd.grad(fn(), leaf)
-                b.record()
-                b.synchronize()
-                if it >= args.warmup:
-                    times[name].append(a.elapsed_time(b) * 1e3)
-        for name in variants:
-            rounds[name].append(float(np.median(times[name])))
-    out = {"tool": "bench_warp", "tag": args.tag, "device": torch.cuda.get_device_name(0), "views": [V, H, W, 4],
+    rounds = benchlib.interleaved({name: (lambda fn=fn, leaf=leaf: torch.autograd.grad(fn(), leaf))
+                                   for name, (fn, leaf) in variants.items()}, args.iters, args.warmup, args.rounds)
+    out = {**benchlib.header("bench_warp", args.tag), "views": [V, H, W, 4],
            "rays": args.rays, "patches": [args.patches, args.patch, args.patch], "valid_rows": valid_rows,
            "iters": args.iters, "rounds": args.rounds, "what": "loss forward + backward to the depth, device events, us",
            "float_table_bytes": table.numel() * 4, "uint8_image_bytes": images.numel(),
            "relative_difference_of_the_two_spellings": agree,
-           "variants": {name: {"us_median": round(float(np.median(r)), 2), "us_rounds": [round(x, 2) for x in r]}
-                        for name, r in rounds.items()}}
-    line = json.dumps(out)
-    print(line)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "a") as f:
-        f.write(line + "\n")
+           "variants": {name: benchlib.rounds_summary(r, "us") for name, r in rounds.items()}}
+    benchlib.emit(out, args.out)
 
 
 if __name__ == "__main__":
